@@ -2,7 +2,7 @@
 """bench.py -- ProcessText hot path on MI355X: documents/s and input GB/s, 10 k-term dictionary + 1 k expressions
 over 1 M synthetic ~4 KB documents per GPU (BASELINE.json configs[2]; SURVEY.md 8(d) workload).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,8 +12,16 @@ plus (N > 1) one RCCL gather of every rank's bitmap to rank 0.  Documents are in
 disjoint document ranges and nothing else is exchanged: --scaling strong (default, the configuration the metric is quoted
 on: 1 M documents in total, sharded across the N GPUs) or weak (1 M documents per GPU).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (scan kernel, live HIP-event
-timing) and `cpu_baseline` (the CPU oracle timed on this host, rank 0 / N=1 only).
+Prints ONE JSON line on rank 0: `value` (documents/s), `ms_per_step` and the configuration.  A plain run does only what
+that line needs: set up, warm up, time the K steps, print.  --full adds everything else, measured and checked in the same
+run as before: `roofline` (scan kernel, live HIP-event timing inside the timed region, match volume, measured read
+ceiling), `kernels_ms_per_step` (the step run again behind the timed region), `cpu_baseline` (the CPU oracle timed on this
+host, rank 0 / N=1 only, its bitmap compared with the GPU's), the corpus generator's host / device agreement and, N > 1,
+the gather's checksums (`parity`; exit status 3 when a check fails).
+
+--dump-outputs DIR writes the hit bitmap of the last timed step (what a caller of Finder.ProcessDevice receives) as .npy
+files under DIR, at most 64 MB in all (see dump_outputs).  The inputs depend on the arguments only, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -23,6 +31,46 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+DUMP_LIMIT = 60_000_000          # bytes of array data --dump-outputs writes (64 MB in all with the .npy headers)
+DOC_COUNTS_MAX = 4_000_000       # documents whose per-document hit count is written (4 bytes each)
+DUMP_SEED = 20240917             # the row sample of a bitmap too large to write whole
+
+
+def dump_outputs(out_dir, bitmap, n_exprs):
+    """Write what the timed path returned: `bitmap` is the [documents, words] int32 hit bitmap of the last timed step (bit
+    e % 32 of word e / 32 of a row = expression e matched that document), on the device.  Files (exact values, at most
+    DUMP_LIMIT bytes of data in all):
+      hit_rows.npy         float64 [S]          document indices of the rows below, ascending: every document when the
+                                                bitmap fits, else a fixed sample drawn with DUMP_SEED
+      hit_bitmap.npy       float64 [S, words]   those rows, each word as its unsigned 32-bit value
+      expr_doc_counts.npy  float64 [n_exprs]    over ALL documents: how many documents matched each expression
+      doc_expr_counts.npy  float32 [min(D, DOC_COUNTS_MAX)]  how many expressions each of the first documents matched"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_docs, words = bitmap.shape
+    u = bitmap.to(torch.int64) & 0xFFFFFFFF
+    per_expr = torch.zeros(words * 32, dtype=torch.int64, device=u.device)
+    per_doc = torch.zeros(n_docs, dtype=torch.int64, device=u.device)
+    for b in range(32):
+        bit = (u >> b) & 1
+        per_expr[b::32] = bit.sum(0)
+        per_doc += bit.sum(1)
+    n_doc_counts = min(n_docs, DOC_COUNTS_MAX)
+    room = DUMP_LIMIT - 8 * n_exprs - 4 * n_doc_counts
+    n_rows = min(n_docs, room // (8 * words + 8))
+    if n_rows < 1:
+        raise SystemExit("--dump-outputs: %d expressions leave no room for bitmap rows in %d bytes" % (n_exprs, DUMP_LIMIT))
+    if n_rows == n_docs:
+        rows = np.arange(n_docs, dtype=np.int64)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_docs, size=n_rows, replace=False)).astype(np.int64)
+    sample = u[torch.from_numpy(rows).to(u.device)].cpu().numpy().astype(np.float64)
+    np.save(os.path.join(out_dir, "hit_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "hit_bitmap.npy"), sample)
+    np.save(os.path.join(out_dir, "expr_doc_counts.npy"), per_expr[:n_exprs].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "doc_expr_counts.npy"), per_doc[:n_doc_counts].cpu().numpy().astype(np.float32))
 
 
 def main():
@@ -47,7 +95,14 @@ def main():
                     help="lower: SURVEY.md 8(d) corpus over a-z (the configuration the metric is quoted on); mixed: the same "
                          "words with capitals, digits, punctuation and two-byte UTF-8 letters (> 48 byte classes, a real "
                          "word list's shape)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: roofline, per-kernel times, CPU "
+                         "baseline, the generator and gather checks (--cpu-docs, --cpu-threads and --parity-docs apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit bitmap of the last timed step to DIR/*.npy (float64 / float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -145,121 +200,130 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # match volume H (drives the algorithmic bytes of the scan kernel)
-    m = _lib.GftMatches()
-    rc = L.gft_scan_device(eh, text.data_ptr(), doc_off.data_ptr(), args.docs, _lib.GFT_FOLD_ASCII, C.byref(m))
-    assert rc == 0, L.gft_last_error(eh)
-    n_matches = int(m.n_matches)
-    # hits per document (the CSR offsets of that scan live in engine-owned device memory)
-    hits_max = None
-    try:
-        moff = torch.empty(args.docs + 1, dtype=torch.int64, device=dev)
-        hip = C.CDLL("libamdhip64.so")
-        if hip.hipMemcpy(C.c_void_p(moff.data_ptr()), C.c_void_p(m.match_off), C.c_size_t(8 * (args.docs + 1)), C.c_int(3)) == 0:
-            hits_max = int((moff[1:] - moff[:-1]).max().item())
-    except OSError:
-        pass
-    from gofindthem_amd.workload import read_ceiling_gbps
-    ceiling_gbps = read_ceiling_gbps(text)
+    n_matches = hits_max = ceiling_gbps = None
+    if args.full:
+        # match volume H (drives the algorithmic bytes of the scan kernel)
+        m = _lib.GftMatches()
+        rc = L.gft_scan_device(eh, text.data_ptr(), doc_off.data_ptr(), args.docs, _lib.GFT_FOLD_ASCII, C.byref(m))
+        assert rc == 0, L.gft_last_error(eh)
+        n_matches = int(m.n_matches)
+        # hits per document (the CSR offsets of that scan live in engine-owned device memory)
+        hits_max = None
+        try:
+            moff = torch.empty(args.docs + 1, dtype=torch.int64, device=dev)
+            hip = C.CDLL("libamdhip64.so")
+            if hip.hipMemcpy(C.c_void_p(moff.data_ptr()), C.c_void_p(m.match_off), C.c_size_t(8 * (args.docs + 1)), C.c_int(3)) == 0:
+                hits_max = int((moff[1:] - moff[:-1]).max().item())
+        except OSError:
+            pass
+        from gofindthem_amd.workload import read_ceiling_gbps
+        ceiling_gbps = read_ceiling_gbps(text)
     setup_s = time.time() - t_setup
 
     # ---- timed region -------------------------------------------------------------------------------------
     for _ in range(args.warmup):
         step()
     fence()                                # (the warm-up batches are complete -- a rerun of the last one included -- before anything is counted)
-    # (mode 2: HIP events around the scan kernel's launches only -- the kernel the roofline prices.  Every bracket is two
-    # event nodes on the stream, a few microseconds between two kernels each; the solver's and the auxiliary kernels'
-    # times are read from the same step run again behind the timed region, below)
-    L.gft_profile_enable(eh, 2)
-    L.gft_profile_reset(eh)
-    fence()
+    if args.full:
+        # (mode 2: HIP events around the scan kernel's launches only -- the kernel the roofline prices.  Every bracket is two
+        # event nodes on the stream, a few microseconds between two kernels each; the solver's and the auxiliary kernels'
+        # times are read from the same step run again behind the timed region, below)
+        L.gft_profile_enable(eh, 2)
+        L.gft_profile_reset(eh)
+        fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    L.gft_profile_enable(eh, 0)
+    if args.full:
+        L.gft_profile_enable(eh, 0)
     elapsed = max_over_ranks(elapsed, dev)
 
-    def prof(name):
-        ms, n = C.c_double(), C.c_uint64()
-        L.gft_profile_read(eh, name.encode(), C.byref(ms), C.byref(n))
-        return ms.value, int(n.value)
-    scan_ms, scan_n = prof("scan")
-    # the spread of the dominant kernel from launch to launch: the same step again, every launch read on its own (behind the
-    # timed region -- reading the events synchronises)
-    scan_each = []
-    solve_ms = aux_ms = 0.0
-    again_steps = min(args.steps, 20)
-    L.gft_profile_enable(eh, 1)
-    for _ in range(again_steps):
-        L.gft_profile_reset(eh)
-        step()
-        fence()
-        ms1, n1 = prof("scan")
-        if n1:
-            scan_each.append(ms1 / n1)
-        solve_ms += prof("solve")[0]
-        aux_ms += prof("aux")[0]
-    L.gft_profile_enable(eh, 0)
-
-    # ---- same-run consistency that needs no oracle: the corpus generator's host and device forms agree on a sample,
-    # and (N > 1) rank 0's slice of the gathered result is what it computed itself --------------------------------
-    bitmap = bitmaps[(n_steps_done[0] - 1) % len(bitmaps)]     # what the last step wrote
-    S = min(args.parity_docs, args.docs)
-    h_text, h_off = wl.docs_host(first, S)
-    d_off = doc_off[:S + 1].cpu().numpy().astype(np.uint64)
-    gen_ok = bool(np.array_equal(d_off, h_off)) and bool(
-        np.array_equal(text[:int(h_off[-1])].cpu().numpy(), h_text))
-    parity_ok = all_ranks_ok(gen_ok, dev)
-    parity = "not checked in this run (the CPU oracle runs in the cpu_baseline leg, N = 1 only); tests/ -m gpu hold the parity proofs"
-    if world > 1:
-        # the exchange itself: every rank's checksum of what it computed against rank 0's checksum of what it received
-        # (one tiny all_gather, outside the timed region)
-        from gofindthem_amd.sharding import verify_gather
+    # ---- outputs of the last timed step, before any further step reuses its buffer ------------------------------------
+    if args.dump_outputs and rank == 0:
         last = (n_steps_done[0] - 1) % len(bitmaps)
-        arrived, n_shards = verify_gather(gather, last, args.docs)
-        arrived = all_ranks_ok(arrived, dev)
-        parity_ok = parity_ok and arrived
-        bitmap = bitmaps[last]
-        parity = ("gathered bitmap verified against the per-rank checksums of all %d shards (the CPU oracle runs in the cpu_baseline "
-                  "leg, N = 1 only)" % n_shards) if arrived else "MISMATCH between a rank's bitmap and what rank 0 received"
+        if world > 1:                      # rank 0 holds every rank's rows; a shard's buffer may carry one row of padding
+            counts = [n for _, n in shards] if args.scaling == "strong" else [args.docs] * world
+            result = torch.cat([p[:n] for p, n in zip(gather.slot_parts[last], counts)], 0)
+        else:
+            result = bitmaps[last][:args.docs]
+        dump_outputs(args.dump_outputs, result, args.exprs)
 
-    # ---- CPU baseline (rank 0, N == 1): the oracle = our restatement of the reference path, on this host ---------------
-    cpu = None
-    if rank == 0 and world == 1 and args.cpu_docs != 0:
-        cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-        cores = min(cores, args.cpu_threads)      # a 1-GPU box's CPU share is 16 cores
-        n_cpu = args.cpu_docs if args.cpu_docs > 0 else min(args.docs, 24000 * cores)   # ~10-15 s of CPU work
-        n_cpu = min(n_cpu, args.docs)
-        from oracle.pyoracle import Oracle     # the checker: only this leg touches oracle/
-        orc = Oracle(sorted(k.encode("utf-8") for k in finder.GetKeywords()))   # BuildEngine receives the finder's keyword set
-        orc.set_expressions(exprs, case_sensitive=False)
-        c_off = doc_off[:n_cpu + 1].cpu().numpy().astype(np.uint64)
-        c_text = text[:int(c_off[-1])].cpu().numpy()
-        n1 = min(n_cpu, 6000)                   # the reference's own execution model: one goroutine (benchmark_test.go:422-425)
-        t1 = time.perf_counter()
-        orc.process(c_text[:int(c_off[n1])], c_off[:n1 + 1], fold=True, n_threads=1)
-        t1 = time.perf_counter() - t1
-        tc = time.perf_counter()
-        ref = orc.process(c_text, c_off, fold=True, n_threads=cores)
-        tc = time.perf_counter() - tc
-        same = bool(np.array_equal(ref, bitmap[:n_cpu].cpu().numpy().view(np.uint32)))
-        parity_ok = parity_ok and same
-        parity = ("bit-exact vs CPU oracle on the first %d documents" % n_cpu) if same else "MISMATCH vs CPU oracle"
-        cpu = {"value": n_cpu / tc, "unit": "docs/s", "cores": cores, "kind": "port",
-               "single_thread_docs_per_s": n1 / t1,
-               "input_GBps": float(c_off[-1]) / tc / 1e9,
-               "sample": "first %d documents of the same corpus (%.1f MB), oracle/ac_oracle.cpp ProcessText "
-                         "restatement, %d std::thread workers, %.1f s; bitmap equal to the GPU's: %s"
-                         % (n_cpu, float(c_off[-1]) / 1e6, cores, tc, same)}
+    parity_ok, parity, cpu, scan_ms, scan_n, scan_each, solve_ms, aux_ms, again_steps = True, None, None, 0.0, 0, [], 0.0, 0.0, 0
+    if args.full:
+        def prof(name):
+            ms, n = C.c_double(), C.c_uint64()
+            L.gft_profile_read(eh, name.encode(), C.byref(ms), C.byref(n))
+            return ms.value, int(n.value)
+        scan_ms, scan_n = prof("scan")
+        # the spread of the dominant kernel from launch to launch: the same step again, every launch read on its own (behind the
+        # timed region -- reading the events synchronises)
+        again_steps = min(args.steps, 20)
+        L.gft_profile_enable(eh, 1)
+        for _ in range(again_steps):
+            L.gft_profile_reset(eh)
+            step()
+            fence()
+            ms1, n1 = prof("scan")
+            if n1:
+                scan_each.append(ms1 / n1)
+            solve_ms += prof("solve")[0]
+            aux_ms += prof("aux")[0]
+        L.gft_profile_enable(eh, 0)
+
+        # ---- same-run consistency that needs no oracle: the corpus generator's host and device forms agree on a sample,
+        # and (N > 1) rank 0's slice of the gathered result is what it computed itself --------------------------------
+        bitmap = bitmaps[(n_steps_done[0] - 1) % len(bitmaps)]     # what the last step wrote
+        S = min(args.parity_docs, args.docs)
+        h_text, h_off = wl.docs_host(first, S)
+        d_off = doc_off[:S + 1].cpu().numpy().astype(np.uint64)
+        gen_ok = bool(np.array_equal(d_off, h_off)) and bool(
+            np.array_equal(text[:int(h_off[-1])].cpu().numpy(), h_text))
+        parity_ok = all_ranks_ok(gen_ok, dev)
+        parity = "not checked in this run (the CPU oracle runs in the cpu_baseline leg, N = 1 only); tests/ -m gpu hold the parity proofs"
+        if world > 1:
+            # the exchange itself: every rank's checksum of what it computed against rank 0's checksum of what it received
+            # (one tiny all_gather, outside the timed region)
+            from gofindthem_amd.sharding import verify_gather
+            last = (n_steps_done[0] - 1) % len(bitmaps)
+            arrived, n_shards = verify_gather(gather, last, args.docs)
+            arrived = all_ranks_ok(arrived, dev)
+            parity_ok = parity_ok and arrived
+            bitmap = bitmaps[last]
+            parity = ("gathered bitmap verified against the per-rank checksums of all %d shards (the CPU oracle runs in the cpu_baseline "
+                      "leg, N = 1 only)" % n_shards) if arrived else "MISMATCH between a rank's bitmap and what rank 0 received"
+
+        # ---- CPU baseline (rank 0, N == 1): the oracle = our restatement of the reference path, on this host ---------------
+        cpu = None
+        if rank == 0 and world == 1 and args.cpu_docs != 0:
+            cores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+            cores = min(cores, args.cpu_threads)      # a 1-GPU box's CPU share is 16 cores
+            n_cpu = args.cpu_docs if args.cpu_docs > 0 else min(args.docs, 24000 * cores)   # ~10-15 s of CPU work
+            n_cpu = min(n_cpu, args.docs)
+            from oracle.pyoracle import Oracle     # the checker: only this leg touches oracle/
+            orc = Oracle(sorted(k.encode("utf-8") for k in finder.GetKeywords()))   # BuildEngine receives the finder's keyword set
+            orc.set_expressions(exprs, case_sensitive=False)
+            c_off = doc_off[:n_cpu + 1].cpu().numpy().astype(np.uint64)
+            c_text = text[:int(c_off[-1])].cpu().numpy()
+            n1 = min(n_cpu, 6000)                   # the reference's own execution model: one goroutine (benchmark_test.go:422-425)
+            t1 = time.perf_counter()
+            orc.process(c_text[:int(c_off[n1])], c_off[:n1 + 1], fold=True, n_threads=1)
+            t1 = time.perf_counter() - t1
+            tc = time.perf_counter()
+            ref = orc.process(c_text, c_off, fold=True, n_threads=cores)
+            tc = time.perf_counter() - tc
+            same = bool(np.array_equal(ref, bitmap[:n_cpu].cpu().numpy().view(np.uint32)))
+            parity_ok = parity_ok and same
+            parity = ("bit-exact vs CPU oracle on the first %d documents" % n_cpu) if same else "MISMATCH vs CPU oracle"
+            cpu = {"value": n_cpu / tc, "unit": "docs/s", "cores": cores, "kind": "port",
+                   "single_thread_docs_per_s": n1 / t1,
+                   "input_GBps": float(c_off[-1]) / tc / 1e9,
+                   "sample": "first %d documents of the same corpus (%.1f MB), oracle/ac_oracle.cpp ProcessText "
+                             "restatement, %d std::thread workers, %.1f s; bitmap equal to the GPU's: %s"
+                             % (n_cpu, float(c_off[-1]) / 1e6, cores, tc, same)}
 
     if rank == 0:
-        import shutil
-        # the unmodified reference is timed beside the path only where a Go toolchain and a module cache exist
-        go_ref = ("Go reference not runnable (no `go` binary on this box, and the module github.com/pedroegsilva/ahocorasick is not "
-                  "vendored); CPU baseline = C++ restatement (oracle/ac_oracle.cpp)") if shutil.which("go") is None else \
-                 "a `go` binary exists here, but /root/reference does not travel to the GPU box: CPU baseline = C++ restatement (oracle/ac_oracle.cpp)"
         # which BASELINE.json configuration the arguments describe
         if args.alphabet != "lower":
             cfg_name = "BASELINE.json configs[2] shape on the MIXED alphabet (not a BASELINE configuration)"
@@ -273,30 +337,18 @@ def main():
             cfg_name = "BASELINE.json configs[1] dictionary through the ProcessText path"
         else:
             cfg_name = "custom (not a BASELINE configuration)"
-        scan_kernel = (L.gft_scan_kernel(eh) or b"").decode()
-        kernel_names = {"scan5": "k_scan5 (suffix-window scan, one probe per two bytes)", "scan2": "k_scan2 (suffix-window scan)", "scan4": "k_scan4 (streaming suffix-window scan)", "scan3": "k_scan3 (stride-2 suffix-window scan)", "dfa": "k_scan_units (two-tier DFA)"}
         docs_total = total_docs * args.steps
         ms_per_step = elapsed / args.steps * 1e3
-        # algorithmic bytes of the dominant (scan) kernel per launch: text once + one offset entry per document +
-        # 8 bytes per match written
-        # (u32 term id + u32 position per match; without INORD expressions the path is presence-only and
-        # writes the term ids alone, so only those 4 bytes count)
-        per_match = 8 if args.inord > 0 else 4
-        alg_bytes = text_bytes + 8 * args.docs + per_match * n_matches
-        scan_avg_ms = scan_ms / max(scan_n, 1)
-        achieved = alg_bytes / (scan_avg_ms * 1e-3) / 1e9 if scan_n else 0.0
-        # HBM traffic of the scan kernel from rocprofv3 PMC passes (profiles/r3_pmc_traffic.json; it cannot be
-        # collected from inside this process) -- only attached when this run uses the profiled configuration
-        traffic = None
-        for name in ("r4_pmc_traffic.json", "r3_pmc_traffic.json", "r2_pmc_traffic.json"):   # (the newest set that has this kernel)
-            try:
-                with open(os.path.join(ROOT, "profiles", name)) as fh:
-                    pmc = json.load(fh)
-                if args.alphabet == "lower" and pmc["config"] == {"docs": args.docs, "terms": args.terms, "exprs": args.exprs, "inord": args.inord}:
-                    traffic = next(v["traffic_bytes"] for k, v in pmc["kernels"].items() if k.startswith("k_" + scan_kernel))
-                    break
-            except (OSError, KeyError, ValueError, StopIteration):
-                pass
+        config = {"workload": "%s: %d terms + %d %s expressions, %d docs x ~4 KB on this GPU "
+                              "(SURVEY.md 8(d) generator%s), case-insensitive finder, inputs resident in HBM"
+                              % (cfg_name, args.terms, args.exprs, "AND/OR/NOT" if args.inord == 0 else
+                                 "AND/OR/NOT + %.0f%% INORD" % (args.inord * 100), args.docs,
+                                 "" if args.alphabet == "lower" else ", MIXED alphabet: capitals, digits, punctuation, UTF-8 letters"),
+                  "alphabet": args.alphabet, "keywords": n_keywords,
+                  "docs_total": total_docs, "docs_per_gpu": args.docs, "text_bytes_per_gpu": text_bytes}
+        if args.full:
+            config.update({"matches_per_gpu": n_matches, "matches_per_doc": n_matches / args.docs, "matches_per_doc_max": hits_max})
+        config.update({"parallelism": "docs sharded x%d" % world, "cu_margin": cu_margin})
         out = {
             "metric": "ProcessText throughput: documents/s (and input GB/s), %d-term dictionary + %d expressions, "
                       "%d docs of ~4 KB %s" % (args.terms, args.exprs, total_docs if args.scaling == "strong" else args.docs,
@@ -307,33 +359,55 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "%s: %d terms + %d %s expressions, %d docs x ~4 KB on this GPU "
-                                   "(SURVEY.md 8(d) generator%s), case-insensitive finder, inputs resident in HBM"
-                                   % (cfg_name, args.terms, args.exprs, "AND/OR/NOT" if args.inord == 0 else
-                                      "AND/OR/NOT + %.0f%% INORD" % (args.inord * 100), args.docs,
-                                      "" if args.alphabet == "lower" else ", MIXED alphabet: capitals, digits, punctuation, UTF-8 letters"),
-                       "alphabet": args.alphabet, "keywords": n_keywords,
-                       "docs_total": total_docs, "docs_per_gpu": args.docs, "text_bytes_per_gpu": text_bytes, "matches_per_gpu": n_matches,
-                       "matches_per_doc": n_matches / args.docs, "matches_per_doc_max": hits_max,
-                       "parallelism": "docs sharded x%d" % world, "cu_margin": cu_margin},
-            "roofline": {"bound": "hbm", "kernel": kernel_names.get(scan_kernel, scan_kernel), "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic,
-                         "measured_read_ceiling": ceiling_gbps, "frac_of_measured_ceiling": achieved / ceiling_gbps,
-                         "guide_achievable_read": 6300.0, "frac_of_guide_achievable": achieved / 6300.0,
-                         "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": scan_avg_ms, "launches": scan_n,
-                         "scan_ms_min": float(np.min(scan_each)) if scan_each else None,
-                         "scan_ms_median": float(np.median(scan_each)) if scan_each else None,
-                         "scan_ms_stddev": float(np.std(scan_each)) if scan_each else None,
-                         "scan_ms_spread_launches": len(scan_each)},
-            "kernels_ms_per_step": {"scan": scan_ms / args.steps, "solve": solve_ms / max(again_steps, 1),
-                                    "aux(units+prefix sums+gather)": aux_ms / max(again_steps, 1),
-                                    "how": "scan: HIP events inside the timed region; solve, aux: the same step run %d more "
-                                           "times behind it with every launch bracketed" % again_steps},
-            "cpu_baseline": cpu,
-            "go_reference": go_ref,
-            "parity": parity if parity_ok else "PARITY FAILED",
-            "setup_s": setup_s,
+            "config": config,
         }
+        if args.full:
+            import shutil
+            # the unmodified reference is timed beside the path only where a Go toolchain and a module cache exist
+            go_ref = ("Go reference not runnable (no `go` binary on this box, and the module github.com/pedroegsilva/ahocorasick is not "
+                      "vendored); CPU baseline = C++ restatement (oracle/ac_oracle.cpp)") if shutil.which("go") is None else \
+                     "a `go` binary exists here, but the reference's sources are not part of this repository: CPU baseline = C++ restatement (oracle/ac_oracle.cpp)"
+            scan_kernel = (L.gft_scan_kernel(eh) or b"").decode()
+            kernel_names = {"scan5": "k_scan5 (suffix-window scan, one probe per two bytes)", "scan2": "k_scan2 (suffix-window scan)", "scan4": "k_scan4 (streaming suffix-window scan)", "scan3": "k_scan3 (stride-2 suffix-window scan)", "dfa": "k_scan_units (two-tier DFA)"}
+            # algorithmic bytes of the dominant (scan) kernel per launch: text once + one offset entry per document +
+            # 8 bytes per match written
+            # (u32 term id + u32 position per match; without INORD expressions the path is presence-only and
+            # writes the term ids alone, so only those 4 bytes count)
+            per_match = 8 if args.inord > 0 else 4
+            alg_bytes = text_bytes + 8 * args.docs + per_match * n_matches
+            scan_avg_ms = scan_ms / max(scan_n, 1)
+            achieved = alg_bytes / (scan_avg_ms * 1e-3) / 1e9 if scan_n else 0.0
+            # HBM traffic of the scan kernel from rocprofv3 PMC passes (profiles/r3_pmc_traffic.json; it cannot be
+            # collected from inside this process) -- only attached when this run uses the profiled configuration
+            traffic = None
+            for name in ("r4_pmc_traffic.json", "r3_pmc_traffic.json", "r2_pmc_traffic.json"):   # (the newest set that has this kernel)
+                try:
+                    with open(os.path.join(ROOT, "profiles", name)) as fh:
+                        pmc = json.load(fh)
+                    if args.alphabet == "lower" and pmc["config"] == {"docs": args.docs, "terms": args.terms, "exprs": args.exprs, "inord": args.inord}:
+                        traffic = next(v["traffic_bytes"] for k, v in pmc["kernels"].items() if k.startswith("k_" + scan_kernel))
+                        break
+                except (OSError, KeyError, ValueError, StopIteration):
+                    pass
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": kernel_names.get(scan_kernel, scan_kernel), "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                             "frac": achieved / 8000.0, "traffic": traffic,
+                             "measured_read_ceiling": ceiling_gbps, "frac_of_measured_ceiling": achieved / ceiling_gbps,
+                             "guide_achievable_read": 6300.0, "frac_of_guide_achievable": achieved / 6300.0,
+                             "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": scan_avg_ms, "launches": scan_n,
+                             "scan_ms_min": float(np.min(scan_each)) if scan_each else None,
+                             "scan_ms_median": float(np.median(scan_each)) if scan_each else None,
+                             "scan_ms_stddev": float(np.std(scan_each)) if scan_each else None,
+                             "scan_ms_spread_launches": len(scan_each)},
+                "kernels_ms_per_step": {"scan": scan_ms / args.steps, "solve": solve_ms / max(again_steps, 1),
+                                        "aux(units+prefix sums+gather)": aux_ms / max(again_steps, 1),
+                                        "how": "scan: HIP events inside the timed region; solve, aux: the same step run %d more "
+                                               "times behind it with every launch bracketed" % again_steps},
+                "cpu_baseline": cpu,
+                "go_reference": go_ref,
+                "parity": parity if parity_ok else "PARITY FAILED",
+            })
+        out["setup_s"] = setup_s
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -3,7 +3,7 @@
 # interleaved so that clock drift hits every build alike -> gpurun_out/ab/<name>_<round>.json, one summary line per run
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/ab
-ARGS=${AB_ARGS:---steps 20 --warmup 3 --cpu-docs 0}
+ARGS=${AB_ARGS:---full --steps 20 --warmup 3 --cpu-docs 0}
 for r in 1 2 3; do
   for n in "$@"; do
     lib=gofindthem_amd/libgft_$n.so; [ $n = cur ] && lib=gofindthem_amd/libgft.so

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/c5_bloom
 mkdir -p $O
-C5="--terms 100000 --exprs 1000 --inord 0.5 --docs 200000 --steps 5 --warmup 2"
+C5="--full --terms 100000 --exprs 1000 --inord 0.5 --docs 200000 --steps 5 --warmup 2"
 for kb in 0 16 32 64; do
   echo "== GFT_SCAN5_BLOOM_KB=$kb" >> $O/log.txt
   GFT_SCAN_DEBUG=0 GFT_SCAN5_BLOOM_KB=$kb timeout -k 10 200 python3 bench.py $C5 --cpu-docs $([ $kb = 32 ] && echo 2000 || echo 0) > $O/out.txt 2> $O/err.txt || exit 1

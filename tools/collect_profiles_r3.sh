@@ -11,9 +11,9 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 set -e
 O=gpurun_out/r3
 mkdir -p $O
-B="python3 bench.py --steps 5 --warmup 2 --cpu-docs 0"
+B="python3 bench.py --full --steps 5 --warmup 2 --cpu-docs 0"
 if [ "$1" = "a" ]; then
-python3 bench.py --steps 20 --warmup 3 > $O/bench_default.log 2>&1
+python3 bench.py --full --steps 20 --warmup 3 > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > $O/r3_final_bench.json
 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- $B > $O/stats.log 2>&1
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/r3_final_kernel_stats.csv \;
@@ -29,7 +29,7 @@ python3 tools/sq_summary.py $O/sq2 --docs 1000000 > $O/r3_sq_counters_b.json
 rm -rf $O/stats $O/pmc_fetch $O/pmc_write $O/pmc_tcc $O/sq1 $O/sq2
 # the one-probe-per-byte kernel (GFT_SCAN_KERNEL=scan2), same configuration
 export GFT_SCAN_KERNEL=scan2
-python3 bench.py --steps 20 --warmup 3 --cpu-docs 0 > $O/bench_scan2.log 2>&1
+python3 bench.py --full --steps 20 --warmup 3 --cpu-docs 0 > $O/bench_scan2.log 2>&1
 tail -1 $O/bench_scan2.log > $O/r3_scan2_bench.json
 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- $B > $O/stats2.log 2>&1
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/r3_scan2_kernel_stats.csv \;
@@ -48,9 +48,9 @@ echo part a collected
 else
 # BASELINE configs[4]'s device half: 100 000 terms, 1 000 expressions with INORD, 200 000 documents
 C5="--terms 100000 --exprs 1000 --inord 0.5 --docs 200000"
-python3 bench.py --steps 5 --warmup 2 $C5 --cpu-docs 2000 > $O/bench_c5.log 2>&1
+python3 bench.py --full --steps 5 --warmup 2 $C5 --cpu-docs 2000 > $O/bench_c5.log 2>&1
 tail -1 $O/bench_c5.log > $O/r3_c5_bench.json
-BC="python3 bench.py --steps 3 --warmup 1 --cpu-docs 0 $C5"
+BC="python3 bench.py --full --steps 3 --warmup 1 --cpu-docs 0 $C5"
 rocprofv3 --kernel-trace --stats -d $O/stats_c5 -o run --output-format csv -- $BC > $O/stats_c5.log 2>&1
 find $O/stats_c5 -name "*kernel_stats.csv" -exec cp {} $O/r3_c5_kernel_stats.csv \;
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o runc --output-format csv -- $BC > $O/pmc_fetch_c5.log 2>&1
@@ -59,9 +59,9 @@ python3 tools/pmc_summary.py $O/pmc_fetch $O/pmc_write $O/r3_c5_pmc_traffic.json
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum -d $O/pmc_tcc -o runc --output-format csv -- $BC > $O/pmc_tcc_c5.log 2>&1
 python3 tools/sq_summary.py $O/pmc_tcc > $O/r3_c5_tcc_counters.json
 rm -rf $O/stats_c5 $O/pmc_fetch $O/pmc_write $O/pmc_tcc
-python3 bench.py --steps 10 --warmup 2 --inord 0.5 --cpu-docs 20000 > $O/bench_inord.log 2>&1
+python3 bench.py --full --steps 10 --warmup 2 --inord 0.5 --cpu-docs 20000 > $O/bench_inord.log 2>&1
 tail -1 $O/bench_inord.log > $O/r3_inord_bench.json
-python3 bench.py --steps 10 --warmup 2 --alphabet mixed > $O/bench_mixed.log 2>&1
+python3 bench.py --full --steps 10 --warmup 2 --alphabet mixed > $O/bench_mixed.log 2>&1
 tail -1 $O/bench_mixed.log > $O/r3_mixed_bench.json
 python3 tools/bench_c1.py > $O/r3_c1_bench.json 2> $O/c1.log
 python3 tools/bench_latency.py --batch-docs 250000 --reps 50 > $O/r3_host_path.json 2> $O/lat.log

@@ -11,13 +11,13 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/r4
 mkdir -p $O
-B="python3 bench.py --steps 5 --warmup 2 --cpu-docs 0"
+B="python3 bench.py --full --steps 5 --warmup 2 --cpu-docs 0"
 pmc() {   # $1 = output dir, rest = counters; the program itself follows `--` (no env / shell hop under the profiler)
   d=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --pmc "$@" -d $d -o run --output-format csv -- $RUN > $d.log 2>&1
 }
 if [ "$1" = "a" ]; then
-python3 bench.py --steps 20 --warmup 3 > $O/bench_default.log 2>&1
+python3 bench.py --full --steps 20 --warmup 3 > $O/bench_default.log 2>&1
 tail -1 $O/bench_default.log > $O/r4_final_bench.json
 RUN=$B
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- $B > $O/stats.log 2>&1
@@ -42,14 +42,14 @@ for m in 0 1 12 4 8; do
 done
 echo part a collected
 elif [ "$1" = "b" ]; then
-python3 bench.py --steps 40 --warmup 5 --docs 125000 --cpu-docs 20000 > $O/bench_share.log 2>&1
+python3 bench.py --full --steps 40 --warmup 5 --docs 125000 --cpu-docs 20000 > $O/bench_share.log 2>&1
 tail -1 $O/bench_share.log > $O/r4_share_bench.json
-timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 bench.py --steps 20 --warmup 3 --docs 125000 --cpu-docs 0 > $O/stats_share.log 2>&1
+timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $O/stats -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 3 --docs 125000 --cpu-docs 0 > $O/stats_share.log 2>&1
 find $O/stats -name "*kernel_stats.csv" -exec cp {} $O/r4_share_kernel_stats.csv \;
 rm -rf $O/stats
-python3 bench.py --steps 10 --warmup 2 --inord 0.5 --cpu-docs 20000 > $O/bench_inord.log 2>&1
+python3 bench.py --full --steps 10 --warmup 2 --inord 0.5 --cpu-docs 20000 > $O/bench_inord.log 2>&1
 tail -1 $O/bench_inord.log > $O/r4_inord_bench.json
-python3 bench.py --steps 10 --warmup 2 --alphabet mixed > $O/bench_mixed.log 2>&1
+python3 bench.py --full --steps 10 --warmup 2 --alphabet mixed > $O/bench_mixed.log 2>&1
 tail -1 $O/bench_mixed.log > $O/r4_mixed_bench.json
 python3 tools/bench_c1.py > $O/r4_c1_bench.json 2> $O/c1.log
 GFT_SOLVE_DEBUG=8 python3 tools/bench_c1.py 2>&1 | grep "solve debug" | tail -18 > $O/r4_c1_solver_phase_clocks.txt || true
@@ -58,9 +58,9 @@ python3 tools/bench_latency.py --batch-docs 250000 --reps 50 > $O/r4_host_path.j
 echo part b collected
 else
 C5="--terms 100000 --exprs 1000 --inord 0.5 --docs 200000"
-python3 bench.py --steps 5 --warmup 2 $C5 --cpu-docs 2000 > $O/bench_c5.log 2>&1
+python3 bench.py --full --steps 5 --warmup 2 $C5 --cpu-docs 2000 > $O/bench_c5.log 2>&1
 tail -1 $O/bench_c5.log > $O/r4_c5_bench.json
-RUN="python3 bench.py --steps 3 --warmup 1 --cpu-docs 0 $C5"
+RUN="python3 bench.py --full --steps 3 --warmup 1 --cpu-docs 0 $C5"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_c5 -o run --output-format csv -- $RUN > $O/stats_c5.log 2>&1
 find $O/stats_c5 -name "*kernel_stats.csv" -exec cp {} $O/r4_c5_kernel_stats.csv \;
 pmc $O/pmc_fetch FETCH_SIZE

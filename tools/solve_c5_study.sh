@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/solve_c5
 mkdir -p $O
-C5="--terms 100000 --exprs 1000 --docs 200000 --cpu-docs 0 --steps 3 --warmup 1"
+C5="--full --terms 100000 --exprs 1000 --docs 200000 --cpu-docs 0 --steps 3 --warmup 1"
 for inord in 0.5 0; do
   for dbg in 0 8 1 2; do
     echo "== inord $inord GFT_SOLVE_DEBUG=$dbg" >> $O/log.txt

@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 O=gpurun_out/tq_$$
 rm -rf $O && mkdir -p $O
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/f -o runc --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-docs 0 > $O/log 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/f -o runc --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --cpu-docs 0 > $O/log 2>&1
 python3 - <<PY
 import csv,glob,re
 from collections import defaultdict
