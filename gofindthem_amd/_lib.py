@@ -60,6 +60,7 @@ SYMBOLS = {
     "gft_process_device": (_i, [_vp, _vp, _vp, _u64, _u32, C.POINTER(GftExtra), _vp]),
     "gft_process_device_begin": (_i, [_vp, _vp, _vp, _u64, _u32, C.POINTER(GftExtra), _vp]),
     "gft_process_device_end": (_i, [_vp]),
+    "gft_process_device_complete": (_i, [_vp]),
     "gft_finder_create": (_i, [C.POINTER(_vp), _i, _i]),
     "gft_finder_create_multi": (_i, [C.POINTER(_vp), _i, _vp, _i]),
     "gft_finder_destroy": (None, [_vp]),

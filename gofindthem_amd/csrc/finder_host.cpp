@@ -440,6 +440,7 @@ Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, ui
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
     }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
@@ -475,10 +476,10 @@ Error Finder::ProcessDeviceEnd() {
     int rc = gft_process_device_end(gpu_->handle());
     if (rc) return fail_gft(rc);
     if (n_begun_ && !caseSensitive_ && b.n_docs && gft_last_nonascii(gpu_->handle())) {
-        // (the host repeat below uses the handle's synchronous entry points: the younger batch is completed first -- its
-        // verdict is kept for its own End)
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "a batch that leaves ASCII cannot be repeated on the host while another batch is in flight: end that one first (or use ProcessDevice)";
+        // (the host repeat below uses the handle's synchronous entry points: the younger batch is completed in place first --
+        // its status and verdict are kept for its own End)
+        rc = gft_process_device_complete(gpu_->handle());
+        if (rc) return fail_gft(rc);
     }
     return repeat_if_not_ascii(b.d_blob, b.d_doc_off, b.n_docs, b.d_bitmap);
 }

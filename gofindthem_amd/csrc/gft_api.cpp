@@ -126,7 +126,7 @@ struct gft_engine {
     uint32_t scan2_unit_max = kScan2UnitMax;            // bytes per work unit (adapts to the match density)
     // a scan launched without knowing the unit count / pool need (gft_process*: one read-back per batch, after the solver)
     bool deferred = false;
-    uint64_t deferred_unit_cap = 0;
+    uint64_t deferred_unit_cap = 0, deferred_pool_cap = 0;   // the unit table and the pool that launch ran with
     uint32_t last_nonascii_bits = 0;                    // what the scan kernels said: 1 = bytes >= 0x80 seen, not judged; 2 = judged unsafe
     bool last_nonascii = false;                         // the last GFT_FOLD_ASCII scan ran over text that ASCII folding does not
                                                         // lower-case the way strings.ToLower does (gft_last_nonascii)
@@ -185,8 +185,10 @@ struct gft_engine {
         int rc = 0;
         const uint8_t* d_text = nullptr; const uint64_t* d_doc_off = nullptr; uint64_t n_docs = 0; uint32_t flags = 0;
         uint32_t* d_bitmap = nullptr;
-        bool single = false; uint32_t epoch = 0; uint64_t n_docs_cap = 0, unit_cap = 0, static_slabs = 0;     // deferred_check's view of the launch
+        bool single = false; uint32_t epoch = 0; uint64_t n_docs_cap = 0, unit_cap = 0, pool_cap = 0, static_slabs = 0;   // deferred_check's view of the launch
         uint64_t* rb = nullptr; hipEvent_t ev = nullptr;
+        // the batch's verdict once it is complete (gft_last_nonascii for its _end: a younger batch may be judged in between)
+        bool nonascii = false; uint32_t nonascii_bits = 0; uint64_t text_lo = 0, text_hi = 0;
     };
     Pending pend[2];
     unsigned pend_head = 0, pend_count = 0;
@@ -654,6 +656,7 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     }
 
     // 2. automaton walk into the slab pool; grow the pool and re-run if it overflowed (never truncate)
+    if (e->deferred) e->deferred_pool_cap = e->pool_cap;
     int rc = e->deferred ? GFT_OK : ensure_pool(e, std::max<uint64_t>(1u << 20, (text_hi - text_lo) / 16));
     if (!rc && !e->deferred && (e->use_scan2 || e->use_scan3)) {
         // (every wave of the grid owns a slab from the start: the pool holds those twice over, or a small batch on a fresh
@@ -896,8 +899,9 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
 // After the last kernel of a batch whose scan was launched blind (scan_pipeline, defer_ok): ONE read-back of the control
 // block -- the batch's only host synchronisation.  *again = the unit table or the match pool was too small (they have
 // been grown): the caller runs the batch once more, this time with the sizes known.
-// (what the launch of a deferred batch knew: the engine's fields at that time, or a pipelined batch's snapshot of them)
-struct DeferredLaunch { bool single; uint64_t n_docs, unit_cap, static_slabs; uint32_t epoch; };   // epoch: of a k_units_single batch (its flags)
+// (what the launch of a deferred batch knew: the engine's fields at that time, or a pipelined batch's snapshot of them --
+// the pool may have grown since, for another batch, but the kernels of this one wrote nothing past pool_cap)
+struct DeferredLaunch { bool single; uint64_t n_docs, unit_cap, pool_cap, static_slabs; uint32_t epoch; };   // epoch: of a k_units_single batch (its flags)
 int deferred_interpret(gft_engine* e, const uint64_t* rb, const DeferredLaunch& dl, bool* again);
 
 int deferred_check(gft_engine* e, bool* again) {
@@ -909,7 +913,7 @@ int deferred_check(gft_engine* e, bool* again) {
     uint64_t* rb = e->pin_rb;
     HIP_TRY(hipMemcpyAsync(rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
     HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
-    return deferred_interpret(e, rb, DeferredLaunch{e->deferred_single, e->deferred_n_docs, e->deferred_unit_cap, e->last_static_slabs, e->deferred_single ? e->deferred_epoch : 0u}, again);
+    return deferred_interpret(e, rb, DeferredLaunch{e->deferred_single, e->deferred_n_docs, e->deferred_unit_cap, e->deferred_pool_cap, e->last_static_slabs, e->deferred_single ? e->deferred_epoch : 0u}, again);
 }
 
 int deferred_interpret(gft_engine* e, const uint64_t* rb, const DeferredLaunch& dl, bool* again) {
@@ -929,8 +933,8 @@ int deferred_interpret(gft_engine* e, const uint64_t* rb, const DeferredLaunch& 
     if (text_hi < text_lo) return fail(e, GFT_E_INVALID, "doc_off is not ascending");
     if (flag_bad) return fail(e, GFT_E_INVALID, "doc_off is not ascending, or a document is longer than 4 GiB - 1 bytes (positions are 32-bit)");
     // (the DFA kernel's cursor counts matches, the suffix-window kernels' slabs: both must fit the pool)
-    if (n_units > dl.unit_cap || cursor > e->pool_cap) {
-        if (cursor > e->pool_cap) { int rc = ensure_pool(e, cursor + cursor / 16); if (rc) return rc; }
+    if (n_units > dl.unit_cap || cursor > dl.pool_cap) {
+        if (cursor > dl.pool_cap) { int rc = ensure_pool(e, cursor + cursor / 16); if (rc) return rc; }     // (a no-op when it has grown past the cursor since)
         *again = true;
         return GFT_OK;
     }
@@ -956,12 +960,21 @@ int refine_nonascii(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_
     uint32_t flag = 0;
     {
         ProfScope ps(e, "aux");
+        // (the word starts at zero: a younger batch in flight may have left its own bits there since this batch's scan)
+        HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint32_t>() + 6, 0, 4, e->stream), "memset");
         HIP_TRY(launch_fold_safe(d_text, e->last_text_lo, e->last_text_hi, d_doc_off, n_docs, e->d_ctl.as<uint32_t>() + 6, e->stream), "fold check");
     }
     HIP_TRY(hipMemcpyAsync(&flag, e->d_ctl.as<uint32_t>() + 6, 4, hipMemcpyDeviceToHost, e->stream), "readback");
     HIP_TRY(hipStreamSynchronize(e->stream), "fold check");
     e->last_nonascii = (flag & 2u) != 0;
     return GFT_OK;
+}
+
+// gft_process_device_begin / _end: no batch in flight is still to be completed (the synchronous entry points may run)
+bool pend_settled(const gft_engine* e) {
+    for (unsigned i = 0; i < e->pend_count; i++)
+        if (!e->pend[(e->pend_head + i) % 2].done) return false;
+    return true;
 }
 
 // GFT_SCAN_UNIQUE: the canonical CSR in d_match_off / d_term -> every term once per document, first occurrences in order.
@@ -2100,7 +2113,7 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
     if (n_docs && e->n_exprs && !d_hit_bitmap) return fail(e, GFT_E_INVALID, "null bitmap");
-    if (e->pend_count) return fail(e, GFT_E_INVALID, "batches of gft_process_device_begin are in flight: gft_process_device_end first");
+    if (!pend_settled(e)) return fail(e, GFT_E_INVALID, "batches of gft_process_device_begin are in flight: gft_process_device_end (or _complete) first");
     DeviceGuard g(e->device);
     // what the host solves (normally nothing): expressions beyond the device solver's limits, and INORD expressions in
     // documents where the caller's matches make a slot's list non-ascending -- for that the caller's (device) arrays are
@@ -2152,6 +2165,36 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
 
 // ---- two batches in flight (at 125 000 documents -- one GPU's share of 1 M over 8 -- a step is 0.5 ms of
 // kernels, and the read-back of the control block plus the launches of the next step are a tenth of it) -----------------------
+namespace {
+// a batch in flight is complete: its status and its verdict (gft_last_nonascii) are kept in its slot until its _end
+void keep_verdict(const gft_engine* e, gft_engine::Pending& p, int rc) {
+    p.rc = rc; p.done = true;
+    p.nonascii = e->last_nonascii; p.nonascii_bits = e->last_nonascii_bits; p.text_lo = e->last_text_lo; p.text_hi = e->last_text_hi;
+}
+void restore_verdict(gft_engine* e, const gft_engine::Pending& p) {
+    e->last_nonascii = p.nonascii; e->last_nonascii_bits = p.nonascii_bits; e->last_text_lo = p.text_lo; e->last_text_hi = p.text_hi;
+}
+// Completes a deferred batch in place: the wait for its read-back, its verdict, and a second run when it outgrew the unit
+// table or the match pool it was launched with.  `young`: the batch begun after it, still in flight behind it on the stream
+// -- its read-back must have landed before a second run reuses the control block.
+void complete_pending(gft_engine* e, gft_engine::Pending& p, gft_engine::Pending* young) {
+    if (p.done) return;
+    if (hipEventSynchronize(p.ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
+    bool again = false;
+    int rc = deferred_interpret(e, p.rb, DeferredLaunch{p.single, p.n_docs_cap, p.unit_cap, p.pool_cap, p.static_slabs, p.single ? p.epoch : 0u}, &again);
+    if (!rc && again) {
+        if (young && !young->done && hipEventSynchronize(young->ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
+        const unsigned keep_count = e->pend_count;
+        e->pend_count = 0;                                      // (the synchronous entry point refuses to run beside batches in flight)
+        rc = gft_process_device(e, p.d_text, p.d_doc_off, p.n_docs, p.flags, nullptr, p.d_bitmap);
+        e->pend_count = keep_count;
+    } else if (!rc) {
+        rc = refine_nonascii(e, p.d_text, p.d_doc_off, p.n_docs, p.flags);
+    }
+    keep_verdict(e, p, rc);
+}
+}  // namespace
+
 int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                              uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap) try {
     if (!e || (n_docs && (!d_text_blob || !d_doc_off))) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
@@ -2162,50 +2205,37 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
     gft_engine::Pending& pb = e->pend[k];
     pb.done = false; pb.rc = GFT_OK;
     pb.d_text = d_text_blob; pb.d_doc_off = d_doc_off; pb.n_docs = n_docs; pb.flags = flags; pb.d_bitmap = d_hit_bitmap;
-    auto sync_path = [&]() {
-        // (whatever cannot be deferred -- caller-supplied matches, host-solved expressions, the first batches of an engine,
-        // an empty batch -- completes here; _end then only hands its status back.  Batches before it are finished first: the
-        // synchronous path reuses the control block they are still to read)
-        int rc = GFT_OK;
-        while (e->pend_count && rc == GFT_OK) {
-            // (statuses of the older batches stay theirs: they are completed, not consumed)
-            gft_engine::Pending& o = e->pend[e->pend_head];
-            if (!o.done) {
-                if (hipEventSynchronize(o.ev) != hipSuccess) { o.rc = fail(e, GFT_E_HIP, "event wait"); o.done = true; break; }
-                bool again = false;
-                o.rc = deferred_interpret(e, o.rb, DeferredLaunch{o.single, o.n_docs_cap, o.unit_cap, o.static_slabs, o.single ? o.epoch : 0u}, &again);
-                if (!o.rc && again) { e->pend_count = 0; o.rc = gft_process_device(e, o.d_text, o.d_doc_off, o.n_docs, o.flags, nullptr, o.d_bitmap); e->pend_count = 1; }
-                else if (!o.rc) { DeviceGuard g2(e->device); o.rc = refine_nonascii(e, o.d_text, o.d_doc_off, o.n_docs, o.flags); }
-                o.done = true;
-            }
-            break;                                              // (at most one older batch: k is the second slot then)
-        }
-        const unsigned keep_head = e->pend_head, keep_count = e->pend_count;
-        e->pend_count = 0;                                      // (the synchronous entry point refuses to run beside batches in flight)
-        pb.rc = gft_process_device(e, d_text_blob, d_doc_off, n_docs, flags, d_extra, d_hit_bitmap);
-        e->pend_head = keep_head; e->pend_count = keep_count;
-        pb.done = true;
-    };
     const bool simple = n_docs && e->device >= 0 && e->built && e->have_programs && !(d_extra && d_extra->off) && e->host_only.empty() &&
                         (!e->n_exprs || d_hit_bitmap);
-    if (!simple) { sync_path(); e->pend_count++; return GFT_OK; }
+    if (!simple) {
+        // (whatever cannot be deferred -- caller-supplied matches, host-solved expressions, the first batches of an engine,
+        // an empty batch -- completes here; _end then only hands its status and verdict back.  A batch before it is
+        // completed first: the synchronous path reuses the control block it is still to read)
+        if (e->pend_count) { DeviceGuard g2(e->device); complete_pending(e, e->pend[e->pend_head], nullptr); }
+        const int rc = gft_process_device(e, d_text_blob, d_doc_off, n_docs, flags, d_extra, d_hit_bitmap);
+        keep_verdict(e, pb, rc);
+        e->pend_count++;
+        return GFT_OK;
+    }
     DeviceGuard g(e->device);
     uint64_t nm = 0;
     int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, false, &nm, nullptr, true);
-    if (rc) { pb.rc = rc; pb.done = true; e->pend_count++; return GFT_OK; }
+    if (rc) { keep_verdict(e, pb, rc); e->pend_count++; return GFT_OK; }
     const bool was_deferred = e->deferred;
     rc = solve_pipeline(e, n_docs, nullptr, d_hit_bitmap);
     if (rc || !was_deferred) {
         // (sizes were not known yet: this batch ran with its own synchronisations, like gft_process_device's first pass)
         if (!rc) { rc = hipStreamSynchronize(e->stream) == hipSuccess ? GFT_OK : fail(e, GFT_E_HIP, "process pipeline"); }
         if (!rc) rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags);
-        pb.rc = rc; pb.done = true; e->pend_count++;
+        keep_verdict(e, pb, rc);
+        e->pend_count++;
         return GFT_OK;
     }
     e->deferred = false;
     if (!pb.rb) HIP_TRY(hipHostMalloc((void**)&pb.rb, 64, hipHostMallocDefault), "pinned alloc");
     if (!pb.ev) HIP_TRY(hipEventCreateWithFlags(&pb.ev, hipEventDisableTiming), "event");
-    pb.single = e->deferred_single; pb.epoch = e->deferred_epoch; pb.n_docs_cap = e->deferred_n_docs; pb.unit_cap = e->deferred_unit_cap; pb.static_slabs = e->last_static_slabs;
+    pb.single = e->deferred_single; pb.epoch = e->deferred_epoch; pb.n_docs_cap = e->deferred_n_docs; pb.unit_cap = e->deferred_unit_cap;
+    pb.pool_cap = e->deferred_pool_cap; pb.static_slabs = e->last_static_slabs;
     HIP_TRY(hipMemcpyAsync(pb.rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
     HIP_TRY(hipEventRecord(pb.ev, e->stream), "event");
     e->pend_count++;
@@ -2217,29 +2247,31 @@ int gft_process_device_end(gft_engine* e) try {
     GFT_LOCK(e);
     if (!e->pend_count) return fail(e, GFT_E_INVALID, "gft_process_device_end: no batch in flight");
     gft_engine::Pending& pb = e->pend[e->pend_head];
-    auto pop = [&]() { e->pend_head = (e->pend_head + 1) % 2; e->pend_count--; };
-    if (pb.done) { const int rc = pb.rc; pop(); return rc; }
-    DeviceGuard g(e->device);
-    if (hipEventSynchronize(pb.ev) != hipSuccess) { pop(); return fail(e, GFT_E_HIP, "event wait"); }
-    bool again = false;
-    int rc = deferred_interpret(e, pb.rb, DeferredLaunch{pb.single, pb.n_docs_cap, pb.unit_cap, pb.static_slabs, pb.single ? pb.epoch : 0u}, &again);
-    if (!rc && again) {
-        // this batch outgrew the unit table or the match pool (both have been grown): once more, with its own synchronisations.
-        // A younger batch in flight is behind it on the stream; it keeps its own bitmap and its own verdict.
-        const unsigned keep_head = e->pend_head, keep_count = e->pend_count;
-        gft_engine::Pending* young = keep_count == 2 ? &e->pend[(keep_head + 1) % 2] : nullptr;
-        if (young && !young->done) {
-            // (its read-back must be taken before the control block is used again)
-            if (hipEventSynchronize(young->ev) != hipSuccess) { pop(); return fail(e, GFT_E_HIP, "event wait"); }
-        }
-        e->pend_count = 0;
-        rc = gft_process_device(e, pb.d_text, pb.d_doc_off, pb.n_docs, pb.flags, nullptr, pb.d_bitmap);
-        e->pend_head = keep_head; e->pend_count = keep_count;
-    } else if (!rc) {
-        rc = refine_nonascii(e, pb.d_text, pb.d_doc_off, pb.n_docs, pb.flags);
+    if (!pb.done) {
+        // a batch that outgrew the unit table or the match pool (both have been grown) runs once more here, with its own
+        // synchronisations.  A younger batch in flight is behind it on the stream; it keeps its own bitmap and verdict.
+        DeviceGuard g(e->device);
+        complete_pending(e, pb, e->pend_count == 2 ? &e->pend[(e->pend_head + 1) % 2] : nullptr);
     }
-    pop();
+    restore_verdict(e, pb);
+    const int rc = pb.rc;
+    e->pend_head = (e->pend_head + 1) % 2;
+    e->pend_count--;
     return rc;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int gft_process_device_complete(gft_engine* e) try {
+    if (!e) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    if (pend_settled(e)) return GFT_OK;
+    DeviceGuard g(e->device);
+    // (what gft_last_nonascii says -- the verdict of the batch ended last -- stays)
+    gft_engine::Pending last;
+    keep_verdict(e, last, GFT_OK);
+    for (unsigned i = 0; i < e->pend_count; i++)
+        complete_pending(e, e->pend[(e->pend_head + i) % 2], i + 1 < e->pend_count ? &e->pend[(e->pend_head + i + 1) % 2] : nullptr);
+    restore_verdict(e, last);
+    return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
 namespace {
@@ -2298,6 +2330,7 @@ int gft_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
+    if (!pend_settled(e)) return fail(e, GFT_E_INVALID, "batches of gft_process_device_begin are in flight: gft_process_device_end (or _complete) first");
     DeviceGuard g(e->device);
     SyncOnExit drained(e);      // host buffers are read by asynchronous copies: drained on every way out
     // GFT_HOST_TIMING=1: where a call from host memory spends its time (stderr; tools/bench_latency.py)

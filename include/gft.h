@@ -195,11 +195,17 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
  * batch i keeps the device busy while the host reads batch i's verdict and launches the next one -- what a step of 0.5 ms
  * (125 000 documents: one GPU's share of 1 M over 8) needs.  Inputs and the bitmap of a batch must stay untouched until its
  * _end has returned: a batch that outgrew the engine's unit table or match pool is run again there.  A batch that cannot be
- * deferred (caller-supplied matches, host-solved expressions, an engine's first batches) completes inside _begin; _end
- * then only hands its status back.  Single-device handles; no other entry point of the handle between _begin and _end. */
+ * deferred (caller-supplied matches, host-solved expressions, an engine's first batches, more documents than the unit
+ * table holds) completes inside _begin; _end then only hands its status and its verdict back.  A batch is run again when
+ * its scan overflowed the match pool IT was launched with, even if another batch has grown the pool since.  Single-device
+ * handles.  Between _begin and _end no other entry point of the handle, except: _complete completes every batch in flight
+ * in place (each keeps its status and verdict for its own _end; gft_last_nonascii keeps saying what it said), after which
+ * the synchronous entry points (gft_process, gft_process_device) may run -- the finder repeats a batch that leaves ASCII
+ * through them while a younger batch is in flight. */
 int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                              uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap);
 int gft_process_device_end(gft_engine* e);
+int gft_process_device_complete(gft_engine* e);
 
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
