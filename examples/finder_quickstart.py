@@ -30,3 +30,10 @@ for t in texts:
 # ... or the batch extension: one uint32 bitmap row per document (bit i = expression i)
 bitmap = f.ProcessTexts(texts)
 print("batch bitmap:", [hex(int(row[0])) for row in bitmap])
+
+# ... and the batch form of the reference's result: per text the []ExpressionResult ProcessText would return, built from
+# three arrays (row offsets, expression indices, tag ids) that were compacted from the bitmap on the device
+for t, hits in zip(texts, f.ProcessTextsResults(texts)):
+    print("%-75s -> %s" % (t[:75], [(r.ExpresionIndex, r.Tag) for r in hits]))
+row_off, expr_idx, tag_id = f.ProcessTextsSparse(texts)
+print("batch lists: row_off %s expr_idx %s tags %s" % (row_off.tolist(), expr_idx.tolist(), [f.tags()[t] for t in tag_id.tolist()]))

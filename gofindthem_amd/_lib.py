@@ -21,6 +21,11 @@ class GftMatches(C.Structure):
                 ("term_id", C.c_void_p), ("pos", C.c_void_p)]
 
 
+class GftSparse(C.Structure):
+    _fields_ = [("n_docs", C.c_uint64), ("total", C.c_uint64), ("row_off", C.c_void_p), ("expr_idx", C.c_void_p),
+                ("label", C.c_void_p)]
+
+
 class GftExtra(C.Structure):
     _fields_ = [("off", C.c_void_p), ("slot", C.c_void_p), ("pos", C.c_void_p)]
 
@@ -61,6 +66,15 @@ SYMBOLS = {
     "gft_process_device_begin": (_i, [_vp, _vp, _vp, _u64, _u32, C.POINTER(GftExtra), _vp]),
     "gft_process_device_end": (_i, [_vp]),
     "gft_process_device_complete": (_i, [_vp]),
+    "gft_set_expr_labels": (_i, [_vp, _vp, _u32]),
+    "gft_compact_device": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "gft_process_sparse": (_i, [_vp, _vp, _vp, _u64, _u32, C.POINTER(GftExtra), C.POINTER(GftSparse)]),
+    "gft_debug_compact_host": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "gft_finder_n_tags": (_u32, [_vp]),
+    "gft_finder_tag": (_i, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u32)]),
+    "gft_finder_expression_tag_id": (C.c_int64, [_vp, _u32]),
+    "gft_finder_process_texts_sparse": (_i, [_vp, _vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "gft_finder_compact_device": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_finder_create": (_i, [C.POINTER(_vp), _i, _i]),
     "gft_finder_create_multi": (_i, [C.POINTER(_vp), _i, _vp, _i]),
     "gft_finder_destroy": (None, [_vp]),

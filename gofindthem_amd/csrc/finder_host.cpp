@@ -7,6 +7,7 @@
 #include <cstring>
 #include <thread>
 
+#include "compact_host.hpp"
 #include "gft_guard.hpp"
 
 namespace gft {
@@ -119,6 +120,9 @@ Error Finder::AddExpressionWithTag(const std::string& expression, const std::str
     if (!r.err.empty()) { last_code_ = GFT_E_PARSE; return r.err; }
     if (solve_error_.empty()) solve_error_ = dsl::SolveError(*r.expr);   // first failing expression wins (finder.go:201-205)
     expressions_.push_back(ExprWrapper{expression, std::move(r.expr), tag});
+    auto tid = tag_id_of_.find(tag);
+    if (tid == tag_id_of_.end()) { tid = tag_id_of_.emplace(tag, (uint32_t)tags_.size()).first; tags_.push_back(tag); }
+    tag_ids_.push_back(tid->second);
     // the reference clears the dirty flag for every key of the parser's set, new or not (finder.go:123-131)
     for (const auto& k : r.keywords) {
         if (kw_set_.insert(k).second) keywords_.push_back(k);
@@ -210,6 +214,11 @@ Error Finder::sync_device() {
         }
     if (words.empty()) words.push_back(0);
     int rc = gft_set_programs(h, words.data(), poff.data(), (uint32_t)(poff.size() - 1), n_extra);
+    if (rc) return fail_gft(rc);
+    // the label of an expression is its tag id (the prefilter's hidden programs behind them are never reported)
+    std::vector<uint32_t> labels(tag_ids_);
+    labels.resize(poff.size() - 1, 0);
+    rc = gft_set_expr_labels(h, labels.empty() ? nullptr : labels.data(), (uint32_t)labels.size());
     if (rc) return fail_gft(rc);
     slot_of_ = std::move(slots);   // literal -> slot, for addMatchesToSolverMap
     seen_builds_ = gpu_->builds();
@@ -319,7 +328,7 @@ Error Finder::ProcessText(const std::string& text_in, std::vector<ExpressionResu
     return "";
 }
 
-Error Finder::ProcessTexts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap) {
+Error Finder::process_texts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap, bool sparse) {
     last_code_ = 0;
     // case folding: ASCII-only batches fold on the device while the text is read; anything else goes through
     // strings.ToLower on the host first (it may change byte lengths, finder.go:140-142)
@@ -339,7 +348,21 @@ Error Finder::ProcessTexts(const uint8_t* blob, const uint64_t* doc_off, uint64_
         if (ascii) flags = GFT_FOLD_ASCII;
     }
     const bool need_host_text = !caseSensitive_ && !ascii;
-    if (prefilter_active() && n_docs) return process_texts_prefiltered(blob, doc_off, n_docs, bitmap, flags, need_host_text);
+    if (prefilter_active() && n_docs) {
+        if (!sparse) return process_texts_prefiltered(blob, doc_off, n_docs, bitmap, flags, need_host_text);
+        // (the regex pass completes these rows on the host: compacted here, by the code behind gft_debug_compact_host)
+        const size_t uw = (expressions_.size() + 31) / 32;
+        std::vector<uint32_t> bm((size_t)n_docs * uw + 1, 0);
+        Error err = process_texts_prefiltered(blob, doc_off, n_docs, bm.data(), flags, need_host_text);
+        if (!err.empty()) return err;
+        sp_row_off_.assign(n_docs + 1, 0);
+        const uint32_t n_user = (uint32_t)expressions_.size();
+        const uint64_t total = compact_host(bm.data(), n_docs, n_user, tag_ids_.data(), sp_row_off_.data(), nullptr, nullptr, 0);
+        sp_idx_.assign(total + 1, 0); sp_tag_.assign(total + 1, 0);
+        compact_host(bm.data(), n_docs, n_user, tag_ids_.data(), sp_row_off_.data(), sp_idx_.data(), sp_tag_.data(), total);
+        sparse_ = Sparse{sp_row_off_.data(), sp_idx_.data(), sp_tag_.data()};
+        return "";
+    }
     const bool per_doc_engines = !gpu_sub_ || !regexes_.empty();
     std::vector<Record> recs;
     std::vector<uint64_t> xoff(1, 0);
@@ -365,14 +388,34 @@ Error Finder::ProcessTexts(const uint8_t* blob, const uint64_t* doc_off, uint64_
     for (size_t i = 0; i < recs.size(); i++) { xs[i] = recs[i].slot; xp[i] = recs[i].pos; }
     gft_extra_matches x{xoff.data(), xs.data(), xp.data()};
     // (a disabled prefilter still leaves its programs out: total_programs() == expressions_.size() then)
-    int rc = gft_process(gpu_->handle(), blob, doc_off, n_docs, flags, per_doc_engines && n_docs ? &x : nullptr, bitmap);
+    gft_sparse sp{};
+    int rc = sparse ? gft_process_sparse(gpu_->handle(), blob, doc_off, n_docs, flags, per_doc_engines && n_docs ? &x : nullptr, &sp)
+                    : gft_process(gpu_->handle(), blob, doc_off, n_docs, flags, per_doc_engines && n_docs ? &x : nullptr, bitmap);
     if (rc) return fail_gft(rc);
+    if (sparse) {
+        // (a finder without expressions has no labels on its engine: every list is empty, sp.label is then null)
+        sp_tag_.assign(1, 0);
+        sparse_ = Sparse{sp.row_off, sp.expr_idx, sp.label ? sp.label : sp_tag_.data()};
+    }
     if (optimistic && gft_last_nonascii(gpu_->handle())) {
         // text that ASCII folding does not lower-case the way strings.ToLower does (finder.go:140-142): once more, through it
         struct Reset { bool& f; ~Reset() { f = false; } } reset{force_host_lower_};
         force_host_lower_ = true;
-        return ProcessTexts(blob, doc_off, n_docs, bitmap);
+        return process_texts(blob, doc_off, n_docs, bitmap, sparse);
     }
+    return "";
+}
+
+Error Finder::CompactDevice(const uint32_t* d_bitmap, uint64_t n_docs, uint64_t* d_row_off, uint32_t* d_expr_idx, uint32_t* d_tag_id,
+                            uint64_t cap, uint64_t* total) {
+    last_code_ = 0;
+    if (!gpu_ || !gpu_->handle()) { last_code_ = GFT_E_HIP; return gpu_ ? gpu_->create_error() : "no GPU engine"; }
+    if (programs_dirty_ || gpu_->builds() != seen_builds_) {
+        last_code_ = GFT_E_NOT_BUILT;
+        return "no bitmap of this finder's current expressions to compact: process a batch first";
+    }
+    int rc = gft_compact_device(gpu_->handle(), d_bitmap, n_docs, d_row_off, d_expr_idx, d_tag_id, cap, total);
+    if (rc) return fail_gft(rc);
     return "";
 }
 
@@ -664,6 +707,42 @@ int gft_finder_process_texts(gft_finder* f, const uint8_t* text_blob, const uint
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->ProcessTexts(text_blob, doc_off, n_docs, hit_bitmap), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_process_texts_sparse(gft_finder* f, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs,
+                                    const uint64_t** row_off, const uint32_t** expr_idx, const uint32_t** tag_id) try {
+    if (!f || (n_docs && !doc_off) || !row_off || !expr_idx || !tag_id) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    Finder::Sparse sp;
+    Error e = f->finder->ProcessTextsSparse(text_blob, doc_off, n_docs, sp);
+    if (!e.empty()) return finder_ret(f, e, GFT_E_ENGINE);
+    *row_off = sp.row_off; *expr_idx = sp.expr_idx; *tag_id = sp.tag_id;
+    return GFT_OK;
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_compact_device(gft_finder* f, const uint32_t* d_hit_bitmap, uint64_t n_docs, uint64_t* d_row_off,
+                              uint32_t* d_expr_idx, uint32_t* d_tag_id, uint64_t cap, uint64_t* total) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->CompactDevice(d_hit_bitmap, n_docs, d_row_off, d_expr_idx, d_tag_id, cap, total), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+uint32_t gft_finder_n_tags(const gft_finder* f) { return f && f->finder ? (uint32_t)f->finder->tags().size() : 0; }
+
+int gft_finder_tag(const gft_finder* f, uint32_t i, const uint8_t** ptr, uint32_t* len) try {
+    if (!f || !ptr || !len) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    const auto& t = f->finder->tags();
+    if (i >= t.size()) return GFT_E_INVALID;
+    *ptr = (const uint8_t*)t[i].data(); *len = (uint32_t)t[i].size();
+    return GFT_OK;
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int64_t gft_finder_expression_tag_id(const gft_finder* f, uint32_t expr_i) try {
+    if (!f || !f->finder) return -1;
+    GFT_FLOCK(f);
+    const auto& ids = f->finder->tag_ids();
+    return expr_i < ids.size() ? (int64_t)ids[expr_i] : -1;
+} GFT_CATCH_VALUE(-1)
 
 int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint32_t* d_hit_bitmap) try {

@@ -106,7 +106,23 @@ public:
     // returns the expressions that evaluated true, in registration order (never "nil": empty vector)
     Error ProcessText(const std::string& text, std::vector<ExpressionResult>& expRes);
     // batch extension: bitmap[d * words + (i >> 5)] bit (i & 31); words = ceil(n_expressions / 32)
-    Error ProcessTexts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap);
+    Error ProcessTexts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap) {
+        return process_texts(blob, doc_off, n_docs, bitmap, false);
+    }
+    // the batch form of ProcessText's result: document d's true expressions are expr_idx[row_off[d] .. row_off[d + 1]) in
+    // registration order, tag_id[k] = tag id of expression expr_idx[k]; the arrays stay valid until the next call
+    struct Sparse { const uint64_t* row_off = nullptr; const uint32_t* expr_idx = nullptr; const uint32_t* tag_id = nullptr; };
+    Error ProcessTextsSparse(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, Sparse& out) {
+        Error err = process_texts(blob, doc_off, n_docs, nullptr, true);
+        if (err.empty()) out = sparse_;
+        return err;
+    }
+    // gft_compact_device on the engine: a bitmap of ProcessDevice / ProcessDeviceBegin + End -> CSR on the device
+    Error CompactDevice(const uint32_t* d_bitmap, uint64_t n_docs, uint64_t* d_row_off, uint32_t* d_expr_idx, uint32_t* d_tag_id,
+                        uint64_t cap, uint64_t* total);
+    // distinct tags in order of first registration ("" included), and the tag id of every expression
+    const std::vector<std::string>& tags() const { return tags_; }
+    const std::vector<uint32_t>& tag_ids() const { return tag_ids_; }
     Error ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, host ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
@@ -137,6 +153,14 @@ private:
     Error collect(const std::string& lowered, bool run_sub, std::vector<Record>& out, bool run_rgx = true);
     Error process_texts_prefiltered(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap,
                                     uint32_t flags, bool need_host_text);
+    // ProcessTexts (sparse == false: rows into bitmap) and ProcessTextsSparse (sparse == true: sparse_) are one function
+    Error process_texts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap, bool sparse);
+    std::vector<std::string> tags_;
+    std::unordered_map<std::string, uint32_t> tag_id_of_;
+    std::vector<uint32_t> tag_ids_;      // per expression
+    Sparse sparse_;                      // the last sparse result: the engine's buffers, or the three below (host route)
+    std::vector<uint64_t> sp_row_off_;
+    std::vector<uint32_t> sp_idx_, sp_tag_;
 
     // ---- regex prefilter.  With the GPU substring engine every regex that has required literals
     // (dsl::RegexRequiredLiterals) gets a hidden AND-of-literals program behind the user's expressions; the literals

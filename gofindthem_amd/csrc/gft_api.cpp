@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include "ac_tables.hpp"
+#include "compact_host.hpp"
 #include "copy_pool.hpp"
 #include "gft_guard.hpp"
 #include "gft_kernels.hpp"
@@ -213,6 +214,13 @@ struct gft_engine {
     DevBuf d_rn_cnt, d_rn_base, d_rn_starts, d_rn_prefix;   // GFT_POS_RUNES: blocks per document, their rune starts, prefix sums
     std::vector<uint64_t> h_match_off;
     std::vector<uint32_t> h_term, h_pos;
+    // sparse results (gft_compact.hip): a label per expression (gft_set_expr_labels), the compaction's scratch -- counts and
+    // scan partials of its own, so that it may run beside batches in flight --, and the CSR of gft_process_sparse
+    bool have_labels = false;
+    std::vector<uint32_t> h_labels;
+    DevBuf d_labels, d_cp_cnt, d_cp_partial, d_cp_row_off, d_cp_idx, d_cp_label;
+    std::vector<uint64_t> h_row_off;
+    std::vector<uint32_t> h_expr_idx, h_label, h_sparse_bm;
 
     // profiling
     int profiling = 0;                     // gft_profile_enable: 0 off, 1 every category, 2 the scan kernel only
@@ -1394,7 +1402,8 @@ void gft_engine_destroy(gft_engine* e) {
 &e->d_unit_cnt, &e->d_unit_base, &e->d_units, &e->d_partial,
                          &e->d_pool_term, &e->d_pool_pos, &e->d_unit_start, &e->d_unit_count, &e->d_unit_out,
                          &e->d_term, &e->d_pos, &e->d_match_off, &e->d_text, &e->d_doc_off, &e->d_bitmap, &e->d_xoff,
-                         &e->d_xslot, &e->d_xpos, &e->d_uq_first, &e->d_uq_cnt, &e->d_uq_off, &e->d_uq_term, &e->d_patch, &e->d_rn_cnt, &e->d_rn_base, &e->d_rn_starts, &e->d_rn_prefix};
+                         &e->d_xslot, &e->d_xpos, &e->d_uq_first, &e->d_uq_cnt, &e->d_uq_off, &e->d_uq_term, &e->d_patch, &e->d_rn_cnt, &e->d_rn_base, &e->d_rn_starts, &e->d_rn_prefix,
+                         &e->d_labels, &e->d_cp_cnt, &e->d_cp_partial, &e->d_cp_row_off, &e->d_cp_idx, &e->d_cp_label};
         for (DevBuf* b : all) b->release();
         for (int k = 0; k < 2; k++) {
             if (e->pin[k]) (void)hipHostFree(e->pin[k]);
@@ -1922,6 +1931,8 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
                      uint32_t n_extra) try {
     if (!e || (n_exprs && (!prog_words || !prog_off))) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
     GFT_LOCK(e);
+    e->have_labels = false;     // (labels belong to a set of programs: gft_set_expr_labels)
+    e->h_labels.clear();
     if (!e->peers.empty() && !e->in_multi) return multi_set_programs(e, prog_words, prog_off, n_exprs, n_extra);
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
@@ -2322,11 +2333,107 @@ int gft_process_again(gft_engine* e, uint64_t n_docs, const gft_extra_matches* e
     return host_eval(e, pdx ? extra : nullptr, n_docs, plan, hit_bitmap, nullptr);
 } GFT_CATCH((e ? &e->err : nullptr))
 
+namespace {
+
+// The three launches of the compaction on the engine's stream: popcount per row, the exclusive scan of the counts
+// (k_scan_* of gft_kernels.hip), the fill.  fill == false: row_off only.  Nothing waits here.
+int compact_enqueue(gft_engine* e, const uint32_t* d_bitmap, uint64_t n_docs, uint64_t* d_row_off, uint32_t* d_expr_idx,
+                    uint32_t* d_label, uint64_t cap, bool count, bool fill) {
+    hipStream_t st = e->stream;
+    if (!n_docs || !e->n_exprs) {
+        if (count) HIP_TRY(hipMemsetAsync(d_row_off, 0, (n_docs + 1) * 8, st), "row_off");
+        return GFT_OK;
+    }
+    if (count) {
+        HIP_TRY(e->d_cp_cnt.ensure(n_docs * 4), "compact alloc");
+        HIP_TRY(e->d_cp_partial.ensure(scan_partials_needed(n_docs) * 8), "compact alloc");
+        {
+            ProfScope ps(e, "compact_count");
+            HIP_TRY(launch_compact_count(d_bitmap, n_docs, e->n_exprs, e->d_cp_cnt.as<uint32_t>(), e->n_cus, st), "compact count");
+        }
+        {
+            ProfScope ps(e, "compact_scan");
+            HIP_TRY(launch_exclusive_scan(e->d_cp_cnt.as<uint32_t>(), n_docs, d_row_off, e->d_cp_partial.as<uint64_t>(), st), "compact scan");
+        }
+    }
+    if (fill && cap) {
+        ProfScope ps(e, "compact_fill");
+        HIP_TRY(launch_compact_fill(d_bitmap, n_docs, e->n_exprs, d_row_off, d_expr_idx, d_label, e->d_labels.as<uint32_t>(), cap,
+                                    e->n_cus, st), "compact fill");
+    }
+    return GFT_OK;
+}
+
+// the CSR of a bitmap that is complete on the HOST (n_exprs columns) into the engine's result buffers
+void sparse_from_host(gft_engine* e, const uint32_t* h_bitmap, uint64_t n_docs, gft_sparse* out) {
+    e->h_row_off.assign(n_docs + 1, 0);
+    const uint32_t* labels = e->have_labels ? e->h_labels.data() : nullptr;
+    const uint64_t total = compact_host(h_bitmap, n_docs, e->n_exprs, labels, e->h_row_off.data(), nullptr, nullptr, 0);
+    e->h_expr_idx.assign(total + 1, 0);
+    e->h_label.assign(labels ? total + 1 : 1, 0);
+    compact_host(h_bitmap, n_docs, e->n_exprs, labels, e->h_row_off.data(), e->h_expr_idx.data(), labels ? e->h_label.data() : nullptr, total);
+    out->n_docs = n_docs; out->total = total;
+    out->row_off = e->h_row_off.data(); out->expr_idx = e->h_expr_idx.data(); out->label = labels ? e->h_label.data() : nullptr;
+}
+
+// ... of a bitmap that is complete on the DEVICE: compacted there, only the CSR comes down (staged like every large result)
+int sparse_from_device(gft_engine* e, const uint32_t* d_bitmap, uint64_t n_docs, gft_sparse* out) {
+    HIP_TRY(e->d_cp_row_off.ensure((n_docs + 1) * 8), "compact alloc");
+    int rc = compact_enqueue(e, d_bitmap, n_docs, e->d_cp_row_off.as<uint64_t>(), nullptr, nullptr, 0, true, false);
+    if (rc) return rc;
+    e->h_row_off.assign(n_docs + 1, 0);
+    if ((rc = d2h_staged(e, e->h_row_off.data(), e->d_cp_row_off.p, (n_docs + 1) * 8))) return rc;
+    const uint64_t total = e->h_row_off[n_docs];
+    const bool labels = e->have_labels;
+    e->h_expr_idx.assign(total + 1, 0);
+    e->h_label.assign(labels ? total + 1 : 1, 0);
+    if (total) {
+        HIP_TRY(e->d_cp_idx.ensure(total * 4), "compact alloc");
+        if (labels) HIP_TRY(e->d_cp_label.ensure(total * 4), "compact alloc");
+        rc = compact_enqueue(e, d_bitmap, n_docs, e->d_cp_row_off.as<uint64_t>(), e->d_cp_idx.as<uint32_t>(),
+                             labels ? e->d_cp_label.as<uint32_t>() : nullptr, total, false, true);
+        if (rc) return rc;
+        if ((rc = d2h_staged(e, e->h_expr_idx.data(), e->d_cp_idx.p, total * 4))) return rc;
+        if (labels && (rc = d2h_staged(e, e->h_label.data(), e->d_cp_label.p, total * 4))) return rc;
+    }
+    out->n_docs = n_docs; out->total = total;
+    out->row_off = e->h_row_off.data(); out->expr_idx = e->h_expr_idx.data(); out->label = labels ? e->h_label.data() : nullptr;
+    return GFT_OK;
+}
+
+int process_host(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
+                 const gft_extra_matches* extra, uint32_t* hit_bitmap, gft_sparse* sparse);
+
+}  // namespace
+
 int gft_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
                 const gft_extra_matches* extra, uint32_t* hit_bitmap) try {
     if (!e || (n_docs && !doc_off)) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
     GFT_LOCK(e);
     if (!e->peers.empty() && !e->in_multi && n_docs) return multi_process(e, text_blob, doc_off, n_docs, flags, extra, hit_bitmap);
+    return process_host(e, text_blob, doc_off, n_docs, flags, extra, hit_bitmap, nullptr);
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int gft_process_sparse(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
+                       const gft_extra_matches* extra, gft_sparse* out) try {
+    if (!e || !out || (n_docs && !doc_off)) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
+    GFT_LOCK(e);
+    if (!e->peers.empty() && !e->in_multi && n_docs) {
+        // (several devices: every shard's rows come to the host as they do for gft_process; sparse gathers are not built)
+        e->h_sparse_bm.assign(n_docs * ((e->n_exprs + 31) / 32) + 1, 0);
+        const int rc = multi_process(e, text_blob, doc_off, n_docs, flags, extra, e->h_sparse_bm.data());
+        if (rc) return rc;
+        sparse_from_host(e, e->h_sparse_bm.data(), n_docs, out);
+        return GFT_OK;
+    }
+    return process_host(e, text_blob, doc_off, n_docs, flags, extra, nullptr, out);
+} GFT_CATCH((e ? &e->err : nullptr))
+
+namespace {
+
+// gft_process, and gft_process_sparse (sparse != nullptr: the CSR instead of the rows) on one device
+int process_host(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
+                 const gft_extra_matches* extra, uint32_t* hit_bitmap, gft_sparse* sparse) {
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
@@ -2362,14 +2469,72 @@ int gft_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off
     if (rc) return rc;
     if ((rc = refine_nonascii(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags))) return rc;
     since("scanned and solved");
+    if (sparse && plan.empty()) {
+        // the rows are complete where they are: compacted on the device, only the CSR comes down
+        rc = sparse_from_device(e, e->d_bitmap.as<uint32_t>(), n_docs, sparse);
+        since("compacted, lists downloaded");
+        return rc;
+    }
+    if (sparse) {
+        e->h_sparse_bm.assign(n_docs * words + 1, 0);
+        hit_bitmap = e->h_sparse_bm.data();
+    }
     if (n_docs * words) {
         if (!hit_bitmap) return fail(e, GFT_E_INVALID, "null bitmap");
         if ((rc = d2h_staged(e, hit_bitmap, e->d_bitmap.p, n_docs * words * 4))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
     since("bitmap downloaded");
-    return host_eval(e, pdx ? extra : nullptr, n_docs, plan, hit_bitmap, nullptr);
+    rc = host_eval(e, pdx ? extra : nullptr, n_docs, plan, hit_bitmap, nullptr);
+    if (!rc && sparse) sparse_from_host(e, hit_bitmap, n_docs, sparse);
+    return rc;
+}
+
+}  // namespace
+
+int gft_set_expr_labels(gft_engine* e, const uint32_t* labels, uint32_t n) try {
+    if (!e) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    e->have_labels = false;
+    e->h_labels.clear();
+    if (!labels || !n) {
+        if (labels || n) return fail(e, GFT_E_INVALID, "gft_set_expr_labels: labels and n go together (NULL, 0 clears)");
+        return GFT_OK;
+    }
+    if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
+    if (n != e->n_exprs) return fail(e, GFT_E_INVALID, "gft_set_expr_labels: one label per expression (n != gft_n_exprs)");
+    if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
+    DeviceGuard g(e->device);
+    SyncOnExit drained(e);
+    e->h_labels.assign(labels, labels + n);
+    const int rc = upload(e, e->d_labels, e->h_labels, "label upload");
+    if (rc) { e->h_labels.clear(); return rc; }
+    e->have_labels = true;
+    return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
+
+int gft_compact_device(gft_engine* e, const uint32_t* d_hit_bitmap, uint64_t n_docs, uint64_t* d_row_off, uint32_t* d_expr_idx,
+                       uint32_t* d_label, uint64_t cap, uint64_t* total) try {
+    if (!e || !d_row_off) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
+    GFT_LOCK(e);
+    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, "gft_compact_device: single-device handles only (sparse gathers between devices are not built)");
+    if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
+    if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
+    if (n_docs && e->n_exprs && !d_hit_bitmap) return fail(e, GFT_E_INVALID, "null bitmap");
+    if (cap && !d_expr_idx) return fail(e, GFT_E_INVALID, "gft_compact_device: cap entries but no expr_idx buffer");
+    if (d_label && !e->have_labels) return fail(e, GFT_E_INVALID, "gft_compact_device: labels asked for, gft_set_expr_labels has not been called");
+    if (total && !pend_settled(e))
+        return fail(e, GFT_E_INVALID, "gft_compact_device: batches of gft_process_device_begin are in flight -- total must be NULL (the call must not wait)");
+    DeviceGuard g(e->device);
+    int rc = compact_enqueue(e, d_hit_bitmap, n_docs, d_row_off, d_expr_idx, d_label, cap, true, true);
+    if (rc) return rc;
+    if (total) {
+        HIP_TRY(hipMemcpyAsync(total, d_row_off + n_docs, 8, hipMemcpyDeviceToHost, e->stream), "total read-back");
+        HIP_TRY(hipStreamSynchronize(e->stream), "compaction");
+    }
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
 
 int gft_debug_emulate_scan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* text,
                            uint32_t len, uint32_t lo, uint32_t flags, uint32_t scan_flags, uint32_t* out_term,

@@ -415,6 +415,14 @@ uint64_t scan_partials_needed(uint64_t n);
 // d_out has n+1 entries; d_partial has scan_partials_needed(n) entries
 hipError_t launch_exclusive_scan(const uint32_t* d_in, uint64_t n, uint64_t* d_out, uint64_t* d_partial,
                                  hipStream_t st);
+// gft_compact.hip: hit bitmap [n_docs][ceil(n_exprs / 32)] -> CSR of the true expressions.  d_cnt[d] = set bits of row d below
+// n_exprs; after launch_exclusive_scan(d_cnt -> d_row_off) the fill pass writes entry k of the result unless k >= cap
+// (d_label nullable; d_label[k] = d_expr_label[d_expr_idx[k]])
+hipError_t launch_compact_count(const uint32_t* d_bitmap, uint64_t n_docs, uint32_t n_exprs, uint32_t* d_cnt, unsigned n_cus,
+                                hipStream_t st);
+hipError_t launch_compact_fill(const uint32_t* d_bitmap, uint64_t n_docs, uint32_t n_exprs, const uint64_t* d_row_off,
+                               uint32_t* d_expr_idx, uint32_t* d_label, const uint32_t* d_expr_label, uint64_t cap, unsigned n_cus,
+                               hipStream_t st);
 size_t scan_units_lds_bytes(uint32_t n_lds_states, uint32_t n_classes);
 hipError_t launch_scan_units(const ScanParams& P, unsigned n_cus, hipStream_t st);
 // d_units_to_sort != nullptr: the slabs come from gft_scan2's balanced path and are sorted into emission order on the way

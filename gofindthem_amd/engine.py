@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import GftExtra, GftMatches
+from ._lib import GftExtra, GftMatches, GftSparse
 
 
 class GftError(RuntimeError):
@@ -161,6 +161,36 @@ class Engine:
         self._check(self._L.gft_process_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, 1 if fold else 0,
                                                C.byref(x) if x is not None else None, d_bitmap_ptr))
 
+    # -- sparse results: the batch form of []ExpressionResult ----------------------------------------------
+    def set_expr_labels(self, labels):
+        """one uint32 per expression (the finder puts tag ids there); None clears.  Any set_programs clears them"""
+        if labels is None:
+            self._check(self._L.gft_set_expr_labels(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(labels, dtype=np.uint32)
+        self._check(self._L.gft_set_expr_labels(self._h, _p(a) if a.size else None, a.size))
+
+    def compact_device(self, d_bitmap_ptr, n_docs, d_row_off_ptr, d_expr_idx_ptr, d_label_ptr, cap, want_total=True):
+        """device bitmap -> device CSR (gft_compact_device).  Entries at positions >= cap are not written; row_off is always
+        complete.  want_total=True: waits and returns the total; False: only enqueues (the total is in d_row_off[n_docs])
+        and returns None -- the form that is allowed while batches of process_device_begin are in flight"""
+        total = C.c_uint64(0)
+        self._check(self._L.gft_compact_device(self._h, d_bitmap_ptr, n_docs, d_row_off_ptr, d_expr_idx_ptr, d_label_ptr, cap,
+                                               C.byref(total) if want_total else None))
+        return int(total.value) if want_total else None
+
+    def process_sparse(self, blob, doc_off, fold=False, extra=None):
+        """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""
+        n_docs = len(doc_off) - 1
+        x = None
+        if extra is not None:
+            eo, es, ep = extra
+            x = GftExtra(eo.ctypes.data, es.ctypes.data, ep.ctypes.data)
+        sp = GftSparse()
+        self._check(self._L.gft_process_sparse(self._h, _p(blob), _p(doc_off), n_docs, 1 if fold else 0,
+                                               C.byref(x) if x is not None else None, C.byref(sp)))
+        return _sparse_arrays(sp.row_off, sp.expr_idx, sp.label, n_docs)
+
     # -- measurement ------------------------------------------------------------------------------------
     def profile(self, on=True):
         self._check(self._L.gft_profile_enable(self._h, 1 if on else 0))
@@ -172,3 +202,37 @@ class Engine:
         ms, n = C.c_double(), C.c_uint64()
         self._check(self._L.gft_profile_read(self._h, name.encode(), C.byref(ms), C.byref(n)))
         return ms.value, int(n.value)
+
+
+def _sparse_arrays(row_off_ptr, expr_idx_ptr, label_ptr, n_docs):
+    """copies of a library-owned CSR result"""
+    ro = np.ctypeslib.as_array(C.cast(row_off_ptr, C.POINTER(C.c_uint64)), shape=(n_docs + 1,)).copy()
+    total = int(ro[n_docs])
+    if total == 0:
+        return ro, np.zeros(0, np.uint32), (np.zeros(0, np.uint32) if label_ptr else None)
+    ei = np.ctypeslib.as_array(C.cast(expr_idx_ptr, C.POINTER(C.c_uint32)), shape=(total,)).copy()
+    lb = np.ctypeslib.as_array(C.cast(label_ptr, C.POINTER(C.c_uint32)), shape=(total,)).copy() if label_ptr else None
+    return ro, ei, lb
+
+
+def compact_host(bitmap, n_exprs, labels=None, cap=None):
+    """gft_debug_compact_host: bitmap [n_docs, ceil(n_exprs / 32)] (host) -> (row_off, expr_idx, label or None, total).
+    cap=None: buffers of the size the result needs (two calls); otherwise the first min(total, cap) entries"""
+    L = _lib.load()
+    bm = np.ascontiguousarray(bitmap, dtype=np.uint32)
+    n_docs = bm.shape[0]
+    lab = np.ascontiguousarray(labels, dtype=np.uint32) if labels is not None else None
+    ro = np.zeros(n_docs + 1, dtype=np.uint64)
+    total = C.c_uint64(0)
+    if cap is None:
+        rc = L.gft_debug_compact_host(_p(bm) if bm.size else None, n_docs, n_exprs, _p(lab), _p(ro), None, None, 0, C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_compact_host failed")
+        cap = int(total.value)
+    ei = np.zeros(max(cap, 1), dtype=np.uint32)
+    lb = np.zeros(max(cap, 1), dtype=np.uint32) if lab is not None else None
+    rc = L.gft_debug_compact_host(_p(bm) if bm.size else None, n_docs, n_exprs, _p(lab), _p(ro), _p(ei), _p(lb), cap, C.byref(total))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_compact_host failed")
+    n = min(cap, int(total.value))
+    return ro, ei[:n], (lb[:n] if lb is not None else None), int(total.value)

@@ -11,7 +11,7 @@ import re
 import numpy as np
 
 from . import _lib
-from .engine import Engine, GftError, pack
+from .engine import Engine, GftError, _sparse_arrays, pack
 
 
 class FinderError(Exception):
@@ -245,6 +245,26 @@ class Finder:
         j = json.loads(C.string_at(ptrs[2], lens[2].value).decode("utf-8")) if tree else None
         return s.decode("utf-8", "surrogateescape"), t.decode("utf-8", "surrogateescape"), j
 
+    def tags(self):
+        """distinct tags, numbered by first appearance in registration order (the empty tag of AddExpression included):
+        tags()[k] is the tag whose id is k in the tag_id arrays"""
+        out = []
+        p, n = C.c_void_p(), C.c_uint32()
+        for i in range(self._L.gft_finder_n_tags(self._h)):
+            self._check(self._L.gft_finder_tag(self._h, i, C.byref(p), C.byref(n)))
+            out.append(C.string_at(p, n.value).decode("utf-8", "surrogateescape"))
+        return out
+
+    def expression_tag_id(self, i):
+        return int(self._L.gft_finder_expression_tag_id(self._h, i))
+
+    def _pairs(self):
+        cache = self.__dict__.setdefault("_expr_cache", [])      # (source, tag) per registered expression
+        while len(cache) < self.n_expressions:
+            s, t, _ = self.expression(len(cache), tree=False)
+            cache.append((s, t))
+        return cache
+
     # -- processing -----------------------------------------------------------------------------------
     def ForceBuild(self):
         self._check(self._L.gft_finder_force_build(self._h))
@@ -256,10 +276,7 @@ class Finder:
         idx = np.zeros(cap, dtype=np.uint32)
         n = C.c_uint32()
         self._check(self._L.gft_finder_process_text(self._h, b, len(b), idx.ctypes.data, cap, C.byref(n)))
-        cache = self.__dict__.setdefault("_expr_cache", [])      # (source, tag) per registered expression
-        while len(cache) < self.n_expressions:
-            s, t, _ = self.expression(len(cache), tree=False)
-            cache.append((s, t))
+        cache = self._pairs()
         return [ExpressionResult(i, cache[i][0], cache[i][1]) for i in idx[:n.value].tolist()]
 
     def ProcessTexts(self, texts=None, blob=None, doc_off=None, out=None):
@@ -278,6 +295,35 @@ class Finder:
         self._check(self._L.gft_finder_process_texts(self._h, blob.ctypes.data, doc_off.ctypes.data, n_docs,
                                                      bm.ctypes.data if bm.size else None))
         return bm
+
+    def ProcessTextsSparse(self, texts=None, blob=None, doc_off=None):
+        """batch form of ProcessText's result -> (row_off u64 [n_docs + 1], expr_idx u32, tag_id u32): document d's true
+        expressions are expr_idx[row_off[d]:row_off[d + 1]] in registration order, tag_id[k] indexes tags().  Where the
+        batch's bitmap is complete on the device it is compacted there and only these arrays are downloaded"""
+        if texts is not None:
+            blob, doc_off = pack(texts)
+        n_docs = len(doc_off) - 1
+        ro, ei, tg = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._check(self._L.gft_finder_process_texts_sparse(self._h, blob.ctypes.data, doc_off.ctypes.data, n_docs,
+                                                            C.byref(ro), C.byref(ei), C.byref(tg)))
+        return _sparse_arrays(ro, ei, tg, n_docs)
+
+    def ProcessTextsResults(self, texts=None, blob=None, doc_off=None):
+        """-> one list of ExpressionResult per document: what the reference's ProcessText returns for each of them"""
+        ro, ei, _ = self.ProcessTextsSparse(texts, blob, doc_off)
+        cache = self._pairs()
+        ro, ei = ro.tolist(), ei.tolist()
+        return [[ExpressionResult(i, cache[i][0], cache[i][1]) for i in ei[ro[d]:ro[d + 1]]] for d in range(len(ro) - 1)]
+
+    def CompactDevice(self, d_bitmap_ptr, n_docs, d_row_off_ptr, d_expr_idx_ptr, d_tag_id_ptr, cap, want_total=True):
+        """a device bitmap of ProcessDevice / ProcessDeviceBegin + End -> device CSR (gft_finder_compact_device): row_off
+        (n_docs + 1 u64), expr_idx and tag_id (cap u32 each; tag_id may be None).  Entries at positions >= cap are not
+        written, row_off is always complete.  want_total=True: waits and returns the total; False: only enqueues (the
+        total is in d_row_off[n_docs]) and returns None -- allowed while a younger batch is in flight"""
+        total = C.c_uint64(0)
+        self._check(self._L.gft_finder_compact_device(self._h, d_bitmap_ptr, n_docs, d_row_off_ptr, d_expr_idx_ptr, d_tag_id_ptr,
+                                                      cap, C.byref(total) if want_total else None))
+        return int(total.value) if want_total else None
 
     def ProcessDevice(self, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr):
         self._check(self._L.gft_finder_process_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr))

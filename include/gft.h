@@ -201,11 +201,48 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
  * handles.  Between _begin and _end no other entry point of the handle, except: _complete completes every batch in flight
  * in place (each keeps its status and verdict for its own _end; gft_last_nonascii keeps saying what it said), after which
  * the synchronous entry points (gft_process, gft_process_device) may run -- the finder repeats a batch that leaves ASCII
- * through them while a younger batch is in flight. */
+ * through them while a younger batch is in flight; gft_compact_device with total == NULL only enqueues (below). */
 int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                              uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap);
 int gft_process_device_end(gft_engine* e);
 int gft_process_device_complete(gft_engine* e);
+
+/* ---- Sparse results: the batch form of []ExpressionResult (finder/finder.go:25-29, 199-215) ------------------------------
+ * A hit bitmap as CSR: the true expressions of document d are expr_idx[row_off[d] .. row_off[d + 1]), strictly ascending
+ * (registration order, as solveExpressions emits them), row_off[n_docs] = their number over the batch; label[k] =
+ * the label of expression expr_idx[k].  Labels are any uint32 per expression (the finder puts tag ids there); they belong to
+ * a set of programs: labels is a host array of n == gft_n_exprs(e) entries, copied to the device; NULL / 0 clears; any
+ * gft_set_programs clears them. */
+int gft_set_expr_labels(gft_engine* e, const uint32_t* labels, uint32_t n);
+/* Bitmap (device, layout as gft_process, gft_n_exprs(e) columns; bits at and above n_exprs in a row's last word are ignored)
+ * -> CSR (device), built by three launches on the engine's stream (gft_profile_read: "compact_count", "compact_scan",
+ * "compact_fill").  d_row_off: n_docs + 1 entries; d_expr_idx: cap entries (NULL with cap 0: count only); d_label: cap
+ * entries or NULL (non-NULL without labels set: GFT_E_INVALID).  An entry whose position is >= cap is NOT written and nothing
+ * is stored past cap entries, but d_row_off is always complete: GFT_OK is returned in both cases, the caller compares the
+ * total with cap and calls again with larger buffers.  total (host) != NULL: the call waits for the stream and hands the
+ * total back.  total == NULL: the call only enqueues and does not wait; the total is then in d_row_off[n_docs].  In that form
+ * it may be called between gft_process_device_begin and _end: a pipelined caller compacts batch i, whose _end has returned,
+ * while batch i + 1 is in flight.  n_docs == 0 and n_exprs == 0 are valid (d_row_off all zero).  Handles over several
+ * devices (gft_engine_create_multi): GFT_E_UNSUPPORTED -- sparse gathers between devices are not built. */
+int gft_compact_device(gft_engine* e, const uint32_t* d_hit_bitmap, uint64_t n_docs, uint64_t* d_row_off, uint32_t* d_expr_idx,
+                       uint32_t* d_label, uint64_t cap, uint64_t* total);
+/* gft_process with the CSR as its result (host buffers in; out's buffers are library-owned and stay valid until the next call
+ * on the same engine; label == NULL when no labels are set).  When the rows are complete on the device -- no expression or
+ * document the host solves -- they are compacted there and only the CSR comes down; otherwise, and on a handle over several
+ * devices, the rows come down as for gft_process and are compacted on the host.  Both routes give the same arrays. */
+typedef struct gft_sparse {
+    uint64_t n_docs;
+    uint64_t total;
+    const uint64_t* row_off;   /* n_docs + 1 */
+    const uint32_t* expr_idx;  /* total */
+    const uint32_t* label;     /* total, or NULL */
+} gft_sparse;
+int gft_process_sparse(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
+                       const gft_extra_matches* extra, gft_sparse* out);
+/* The compaction alone on the host, same contract (all pointers host; labels: n_exprs entries, needed when label != NULL).
+ * No HIP device is needed: the finder uses this code for a batch whose bitmap was completed on the host, tests use it. */
+int gft_debug_compact_host(const uint32_t* bitmap, uint64_t n_docs, uint32_t n_exprs, const uint32_t* labels, uint64_t* row_off,
+                           uint32_t* expr_idx, uint32_t* label, uint64_t cap, uint64_t* total);
 
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
@@ -254,6 +291,19 @@ int gft_finder_process_texts(gft_finder* f, const uint8_t* text_blob, const uint
 /* documents the host regex engine was called on by the last gft_finder_process_texts (the regex prefilter, SURVEY.md
  * 8(f) #3, sends it only documents that contain every required literal of some regex; GFT_REGEX_PREFILTER=0 disables) */
 uint64_t gft_finder_last_regex_docs(const gft_finder* f);
+/* Tags.  Distinct tags are numbered by first appearance in registration order; the empty tag of AddExpression
+ * (finder.go:80-82) is a tag like any other.  The finder hands the tag id of every expression to its engine
+ * (gft_set_expr_labels) whenever it sets the programs.  Pointers are valid until the next call on f. */
+uint32_t gft_finder_n_tags(const gft_finder* f);
+int gft_finder_tag(const gft_finder* f, uint32_t i, const uint8_t** ptr, uint32_t* len);
+int64_t gft_finder_expression_tag_id(const gft_finder* f, uint32_t expr_i);   /* -1: no such expression */
+/* The batch form of ProcessText's result: document d's true expressions are expr_idx[row_off[d] .. row_off[d + 1]) in
+ * registration order, tag_id[k] the tag id of expression expr_idx[k].  Same semantics as gft_finder_process_texts (regex
+ * prefilter, injected engines, the ToLower repeat of a batch that leaves ASCII, error propagation).  The three buffers are
+ * library-owned and stay valid until the next call on f.  A batch whose bitmap is complete on the device is compacted there
+ * and only these arrays are downloaded (gft_process_sparse). */
+int gft_finder_process_texts_sparse(gft_finder* f, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs,
+                                    const uint64_t** row_off, const uint32_t** expr_idx, const uint32_t** tag_id);
 /* Same with the corpus resident in HBM (GPU substring engine, no regex terms). */
 int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint32_t* d_hit_bitmap);
@@ -261,6 +311,10 @@ int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const u
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                                     uint32_t* d_hit_bitmap);
 int gft_finder_process_device_end(gft_finder* f);
+/* gft_compact_device on the finder's engine (d_tag_id: the tag id of every entry, or NULL): pairs with
+ * gft_finder_process_device, and with _begin / _end in the total == NULL form -- after a batch's _end has returned. */
+int gft_finder_compact_device(gft_finder* f, const uint32_t* d_hit_bitmap, uint64_t n_docs, uint64_t* d_row_off,
+                              uint32_t* d_expr_idx, uint32_t* d_tag_id, uint64_t cap, uint64_t* total);
 /* test hooks mirroring what finder_test.go does by poking struct fields (finder/finder_test.go:205-217) */
 int gft_finder_debug_add_literal(gft_finder* f, int which, const uint8_t* lit, uint32_t len);
 int gft_finder_debug_set_updated(gft_finder* f, int updated_sub, int updated_rgx);
