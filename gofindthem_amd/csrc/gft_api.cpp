@@ -51,6 +51,26 @@ struct ProfCat {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
 };
 
+// The kernel that scans the text: the two-tier DFA kernel (gft_kernels.hip: an independent algorithm, the cross-check) or
+// one of the suffix-window kernels.  Those count the slabs of the match pool that their waves take, the DFA kernel counts
+// its matches.
+enum class ScanKernel { dfa, scan2, scan3, scan4, scan5 };
+constexpr const char* kScanKernelName[] = {"dfa", "scan2", "scan3", "scan4", "scan5"};
+constexpr bool counts_slabs(ScanKernel k) { return k != ScanKernel::dfa; }     // ... and leaves a unit's matches unsorted
+constexpr bool on_scan2_tables(ScanKernel k) { return k == ScanKernel::scan2 || k == ScanKernel::scan4 || k == ScanKernel::scan5; }
+
+// What a scan launch knew.  A deferred launch (scan_pipeline) ran without a read-back of the unit count or the pool need:
+// its caller judges it against these numbers after its last kernel -- the engine's own may have changed by then, for a
+// younger batch, but the kernels of this launch wrote nothing beyond unit_cap and pool_cap.
+struct ScanLaunch {
+    bool deferred = false;
+    bool single = false;                   // the unit table came from k_units_single ...
+    uint32_t epoch = 0;                    // ... which raises the batch's control-block flags to this number
+    bool ordered = false;                  // every unit went through scan2's per-lane staging path (GFT_SCAN_ORDERED)
+    uint64_t n_docs = 0, unit_cap = 0, pool_cap = 0;
+    uint64_t static_slabs = 0;             // pool entries that the waves of the grid owned from the start (the cursor counts behind them)
+};
+
 }  // namespace
 
 #ifndef GFT_EXTRA_KERNELS
@@ -88,46 +108,43 @@ struct gft_engine {
     uint32_t build_flags = 0;
     uint32_t n_lds_states = 0;
     DevBuf d_byte_class, d_delta, d_out_term, d_out_link, d_term_len;
-    // suffix-window scan (gft_scan2.hip); the two-tier DFA kernel above stays as the general fallback
-    Scan2Tables s2;
-    bool use_scan2 = false;
-    DevBuf d_s2_filter, d_s2_slots, d_s2_more, d_s2_cls, d_s2_cls_fold, d_s2_term_blob, d_s2_term_off, d_dbg;
-    // stride-2 suffix-window scan (gft_scan3.hip): the default kernel
-    Scan3Tables s3;
-    bool use_scan3 = false;
-    DevBuf d_s3_filter, d_s3_short3, d_s3_srec, d_s3_short3_big, d_s3_srec_big, d_s3_bloom, d_s3_slots, d_s3_more, d_s3_cls,
-        d_s3_cls_fold, d_s3_term_blob, d_s3_term_off;
-    uint32_t scan3_waves = 0, scan3_cand_cap = 0;
+    // the scan kernel of the built dictionary (choose_scan_kernel) and its waves per workgroup (dfa: 0, it owns no slabs)
+    ScanKernel kernel = ScanKernel::dfa;
+    uint32_t scan_waves = 0;
     // control block (64 B): [0] u32 bad-offsets flag, [8] u64 pool cursor, [16] u64 exact match count, [24] u32 a folded scan
     // saw a byte >= 0x80, [32] u64 n_units,
     // [40] u64 first text offset, [48] u64 last text offset -- one memset per batch, one read-back per synchronisation
-    DevBuf d_ctl;
+    DevBuf d_ctl, d_dbg;
+    uint64_t scan_valid_docs = ~0ull;                   // documents of the last gft_process scan still in the pool (~0: none)
+    // scan3 (gft_scan3.hip): the stride-2 suffix-window kernel, any alphabet
+    Scan3Tables s3;
+    DevBuf d_s3_filter, d_s3_short3, d_s3_srec, d_s3_short3_big, d_s3_srec_big, d_s3_bloom, d_s3_slots, d_s3_more, d_s3_cls,
+        d_s3_cls_fold, d_s3_term_blob, d_s3_term_off;
+    uint32_t scan3_cand_cap = 0;                        // scan3_plan
+    // scan2's tables: what scan2, scan4 and scan5 run on
+    Scan2Tables s2;
+    DevBuf d_s2_filter, d_s2_slots, d_s2_more, d_s2_cls, d_s2_cls_fold, d_s2_term_blob, d_s2_term_off;
     DevBuf d_s2_short3, d_s2_shorts_packed, d_s2_short3_big, d_s2_fpt;
     uint32_t scan2_short3_bytes = 0;
-    uint32_t scan2_k2_waves = 0, scan2_cand_cap = 0;    // scan2_plan
-    // the streaming form of the suffix-window kernel (gft_scan4.hip): same tables, its own LDS plan; a unit's region of the
-    // match pool is sized from the match density (matches per text byte) of the batches before
-    bool use_scan4 = false;
-    uint32_t scan4_waves = 0, scan4_fifo[2] = {0, 0};   // fifo entries without / with positions
+    uint32_t scan2_unit_max = kScan2UnitMax;            // bytes per work unit of these three (adapts to the match density)
+    // scan2 (gft_scan2.hip): the suffix-window kernel, one filter probe per byte
+    uint32_t scan2_cand_cap = 0;                        // scan2_plan
+    // scan4 (gft_scan4.hip): its streaming form, with an LDS plan of its own; a unit's region of the match pool is sized
+    // from the match density (matches per text byte) of the batches before
+    uint32_t scan4_fifo[2] = {0, 0};                    // fifo entries without / with positions
     double scan4_density = 0.06;
-    // the suffix-window kernel with the unit's text in LDS (gft_scan5.hip): scan2's tables + a filter over merged classes
-    bool use_scan5 = false;
+    // scan5 (gft_scan5.hip): the unit's text in LDS, a filter over merged classes in front of scan2's tables
     Scan5Plan s5plan{0, 0, 0, 0};
     Scan5Tables s5;
     DevBuf d_s5_grp, d_s5_grp_fold, d_s5_filter, d_s5_bloom;
     std::vector<uint32_t> s5_bloom;                     // the Bloom level in front of a global fingerprint table (gft_kernels.hpp scan5_bloom_g)
     uint32_t s5_bloom_lg = 0;                           // 2^lg bits; 0: none
-    uint32_t opt_scan5_bloom_kb = 32;                   // GFT_SCAN5_BLOOM_KB: its size in LDS (0: none; a power of two up to 64)
     uint32_t s5_term_bits = 0, s5_pos_bias = 0;
-    bool s5_short_groups = false;                       // scan5 takes its short terms from the stride-2 kernel's tables (> 32 byte classes)
-    uint32_t opt_scan5_large = 1;                       // GFT_SCAN5_LARGE=0: dictionaries over more than 32 byte classes stay on the stride-2 kernel
+    bool s5_short_groups = false;                       // its short terms come from scan3's tables (> 32 byte classes)
+    uint32_t opt_scan5_bloom_kb = 32;                   // GFT_SCAN5_BLOOM_KB: the Bloom level's size in LDS (0: none; a power of two up to 64)
+    uint32_t opt_scan5_large = 1;                       // GFT_SCAN5_LARGE=0: dictionaries over more than 32 byte classes stay on scan3
     uint32_t opt_scan5_fifo = 0;                        // GFT_SCAN5_FIFO: entries of a wave's match fifo (0: 256; timing study)
     uint32_t opt_scan5_groups = 0;                      // GFT_SCAN5_GROUPS: forced number of filter groups (tests)
-    uint64_t scan_valid_docs = ~0ull;                   // documents of the last gft_process scan still in the pool (~0: none)
-    uint32_t scan2_unit_max = kScan2UnitMax;            // bytes per work unit (adapts to the match density)
-    // a scan launched without knowing the unit count / pool need (gft_process*: one read-back per batch, after the solver)
-    bool deferred = false;
-    uint64_t deferred_unit_cap = 0, deferred_pool_cap = 0;   // the unit table and the pool that launch ran with
     uint32_t last_nonascii_bits = 0;                    // what the scan kernels said: 1 = bytes >= 0x80 seen, not judged; 2 = judged unsafe
     bool last_nonascii = false;                         // the last GFT_FOLD_ASCII scan ran over text that ASCII folding does not
                                                         // lower-case the way strings.ToLower does (gft_last_nonascii)
@@ -176,17 +193,14 @@ struct gft_engine {
     // that path and held a longer document after all sets it well below zero, so that a corpus whose batches alternate does
     // not pay for the miss every other time)
     int single_streak = 0;
-    uint64_t last_static_slabs = 0;        // pool entries the waves of the last scan launch owned from the start (gft_scan2 / 3)
-    bool deferred_single = false;          // ... and this one took that path
-    uint32_t ctl_epoch = 1, deferred_epoch = 0;   // k_units_single batches are numbered from 2 (their control-block flags)
-    uint64_t deferred_n_docs = 0;
+    uint32_t ctl_epoch = 1;                // k_units_single batches are numbered from 2 (their control-block flags)
     // gft_process_device_begin / _end: up to two batches enqueued, their read-backs landing in pinned slots of their own
     struct Pending {
         bool done = false;                 // completed inside begin (a batch that could not be deferred): rc is its status
         int rc = 0;
         const uint8_t* d_text = nullptr; const uint64_t* d_doc_off = nullptr; uint64_t n_docs = 0; uint32_t flags = 0;
         uint32_t* d_bitmap = nullptr;
-        bool single = false; uint32_t epoch = 0; uint64_t n_docs_cap = 0, unit_cap = 0, pool_cap = 0, static_slabs = 0;   // deferred_check's view of the launch
+        ScanLaunch launch;
         uint64_t* rb = nullptr; hipEvent_t ev = nullptr;
         // the batch's verdict once it is complete (gft_last_nonascii for its _end: a younger batch may be judged in between)
         bool nonascii = false; uint32_t nonascii_bits = 0; uint64_t text_lo = 0, text_hi = 0;
@@ -527,7 +541,7 @@ int csr_from_pool(gft_engine* e, uint64_t n_docs) {
                                   e->d_partial.as<uint64_t>(), st), "unit_out scan");
     // (the suffix-window kernels leave a unit's matches in any order -- shifted anchors report a term from another position
     // than its end, also on scan2's per-lane path: the gather sorts them)
-    const bool sort_units = e->use_scan2 || e->use_scan3;
+    const bool sort_units = counts_slabs(e->kernel);
     HIP_TRY(launch_gather(e->d_unit_start.as<uint64_t>(), e->d_unit_count.as<uint32_t>(),
                           e->d_unit_out.as<uint64_t>(), n_units, e->d_pool_term.as<uint32_t>(),
                           e->d_pool_pos.as<uint32_t>(), e->d_term.as<uint32_t>(), e->d_pos.as<uint32_t>(),
@@ -539,18 +553,220 @@ int csr_from_pool(gft_engine* e, uint64_t n_docs) {
     return GFT_OK;
 }
 
+// What varies from batch to batch in the parameters of a scan launch
+struct ScanBatch {
+    const uint8_t* d_text; const uint64_t* d_doc_off;
+    uint64_t n_docs, n_units, text_hi;
+    uint32_t flags, unit_max;
+    bool need_csr;
+};
+
+// the fields that every scan kernel's parameter struct has
+template <class Params>
+void fill_common(const gft_engine* e, const ScanBatch& b, Params& P) {
+    P.text = b.d_text; P.doc_off = b.d_doc_off; P.units = e->d_units.as<Unit>(); P.n_units = b.n_units;
+    P.pos_end = (e->build_flags & GFT_POS_END) ? 1 : 0;
+    P.fold = (b.flags & GFT_FOLD_ASCII) ? 1 : 0;
+    P.nonascii = e->d_ctl.as<uint32_t>() + 6;
+    P.cursor = e->d_ctl.as<uint64_t>() + 1; P.pool_cap = e->pool_cap;
+    P.pool_term = e->d_pool_term.as<uint32_t>(); P.pool_pos = e->d_pool_pos.as<uint32_t>();
+    P.unit_start = e->d_unit_start.as<uint64_t>(); P.unit_count = e->d_unit_count.as<uint32_t>();
+}
+// ... and those of the suffix-window kernels
+template <class Params>
+void fill_window(const gft_engine* e, const ScanBatch& b, Params& P) {
+    fill_common(e, b, P);
+    P.text_bytes = b.text_hi;
+    P.n_matches = e->d_ctl.as<uint64_t>() + 2;
+    // presence-only mode: positions are only read by INORD groups (and by CSR callers)
+    P.want_pos = (b.need_csr || e->n_inord_groups > 0) ? 1 : 0;
+    // wave priorities: the latency-bound verification stages overtake the filter phase of the other waves (5 % on
+    // the benchmark; GFT_SCAN_PRIO=0 switches it off)
+    P.prio = e->opt_scan_prio;
+    P.dbg = e->opt_scan_dbg;
+}
+
+// The waves of a launch over `work` items (units; chunks for scan4): every wave of the grid owns a slab from the start
+uint64_t grid_waves(const gft_engine* e, uint64_t work) {
+    const uint64_t wpw = e->scan_waves;
+    return std::min<uint64_t>(std::max<uint64_t>((work + wpw - 1) / wpw, 1), e->n_cus) * wpw;
+}
+// the smallest slab of scan2 / scan3 / scan5 (scan4 sizes its slabs from a chunk's need)
+constexpr uint64_t slab_floor(ScanKernel k) { return k == ScanKernel::scan3 ? 2 * kScan3MinRoom : 64; }
+// ... and their slab: the slack is at most one slab per resident wave, keep it below half the pool
+uint32_t slab_size(const gft_engine* e) {
+    const uint64_t n_waves = (uint64_t)e->n_cus * e->scan_waves;
+    return (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(slab_floor(e->kernel), e->pool_cap / (2 * n_waves)));
+}
+
+ScanParams dfa_params(const gft_engine* e, const ScanBatch& b) {
+    ScanParams P;
+    fill_common(e, b, P);
+    P.byte_class = e->d_byte_class.as<uint8_t>(); P.delta = e->d_delta.as<uint32_t>();
+    P.out_term = e->d_out_term.as<uint32_t>(); P.out_link = e->d_out_link.as<uint32_t>();
+    P.term_len = e->d_term_len.as<uint32_t>();
+    P.n_classes = e->tab.n_classes; P.n_states = e->tab.n_states; P.n_lds_states = e->n_lds_states;
+    P.max_term_len = e->tab.max_term_len;
+    return P;
+}
+
+Scan3Params scan3_params(const gft_engine* e, const ScanBatch& b) {
+    Scan3Params P;
+    fill_window(e, b, P);
+    P.cls = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
+    P.filter = e->d_s3_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s3.filter.size();
+    P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
+    P.srec = e->d_s3_srec.as<uint32_t>(); P.srec_words = (uint32_t)e->s3.srec.size();
+    P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
+    P.srec_big = e->d_s3_srec_big.as<uint32_t>();
+    P.bloom = e->d_s3_bloom.as<uint32_t>(); P.bloom_lg = e->s3.bloom_lg; P.bloom_lds = e->s3.bloom_lg <= kScan3BloomLdsLg ? 1 : 0;
+    P.slots = e->d_s3_slots.as<Scan2Slot>(); P.slot_shift = e->s3.slot_shift; P.slot_seed = e->s3.slot_seed;
+    P.more = e->d_s3_more.as<Scan2Slot>();
+    P.term_blob = e->d_s3_term_blob.as<uint8_t>(); P.term_off = e->d_s3_term_off.as<uint32_t>();
+    P.G = e->s3.G; P.grouped = e->s3.grouped ? 1 : 0;
+    P.cand_cap = e->scan3_cand_cap;
+    P.slab = slab_size(e);
+    return P;
+}
+
+// scan2's parameters, with what scan4 / scan5 add to them when one of those is the engine's kernel
+Scan2Params scan2_params(const gft_engine* e, const ScanBatch& b) {
+    Scan2Params P;
+    fill_window(e, b, P);
+    P.filter = e->d_s2_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s2.filter.size();
+    P.hashed = e->s2.hashed ? 1 : 0; P.hash_shift = e->s2.hash_shift;
+    P.short3 = e->d_s2_short3.as<uint8_t>(); P.short3_bytes = e->scan2_short3_bytes;
+    P.fpt = e->d_s2_fpt.as<uint8_t>(); P.fpt_lg = e->s2.fpt_lg;
+    P.shorts_packed = e->d_s2_shorts_packed.as<uint32_t>(); P.shorts_words = (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
+    P.short3_big = e->s2.short3_big.empty() ? nullptr : e->d_s2_short3_big.as<uint32_t>();
+    P.cand_cap = e->scan2_cand_cap;
+    P.slots = e->d_s2_slots.as<Scan2Slot>(); P.slot_shift = e->s2.slot_shift; P.slot_seed = e->s2.slot_seed;
+    P.more = e->d_s2_more.as<Scan2Slot>();
+    P.cls = P.fold ? e->d_s2_cls_fold.as<uint8_t>() : e->d_s2_cls.as<uint8_t>();
+    P.term_blob = e->d_s2_term_blob.as<uint8_t>(); P.term_off = e->d_s2_term_off.as<uint32_t>();
+    P.kp = e->s2.kp; P.pad_class = e->s2.pad_class;
+    // the balanced path serves both callers: the solver reads presence / successor positions in any order, and
+    // CSR results are put into emission order by the gather (k_gather_sorted).  GFT_SCAN_ORDERED=1 sends every unit
+    // through the kernel's per-lane staging path (normally the fallback for units whose matches overflow the LDS
+    // fifo): a second implementation of the verification, kept as a cross-check
+    P.ordered = (b.need_csr && e->opt_scan_ordered) ? 1 : 0;
+    P.dbg_counters = (P.dbg & (2 | 64)) ? e->d_dbg.as<uint64_t>() : nullptr;
+    P.slab = slab_size(e);
+    if (e->kernel == ScanKernel::scan4) {
+        // the streaming form: chunks of up to eight units (fewer when the batch is small: every wave should get several
+        // chunks), a fifo in place of the candidate list, per-unit regions sized from the density seen so far
+        const uint64_t n_waves = (uint64_t)e->n_cus * e->scan_waves;
+        P.chunk_units = (uint32_t)std::min<uint64_t>(kScan4ChunkUnits, std::max<uint64_t>(1, b.n_docs / (n_waves * 4)));
+        if (e->opt_scan4_chunk) P.chunk_units = std::min<uint32_t>(e->opt_scan4_chunk, kScan4ChunkUnits);      // (GFT_SCAN4_CHUNK: tests)
+        P.cand_cap = e->scan4_fifo[P.want_pos ? 1 : 0];
+        P.bound_q16 = (uint32_t)std::min<double>(e->scan4_density * 1.6 * 65536.0 + 1.0, 4.0e9);
+        P.bound_add = 48;
+        P.round_c = e->opt_scan4_round ? std::min<uint32_t>(64, std::max<uint32_t>(16, e->opt_scan4_round & ~15u)) : 64;   // (GFT_SCAN4_ROUND: timing studies)
+        // a slab should hold a few chunks' regions (the rest of a slab that the next chunk does not fit is lost)
+        const uint64_t chunk_need = (uint64_t)P.chunk_units * (((uint64_t)b.unit_max * P.bound_q16 >> 16) + P.bound_add);
+        P.slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kScan2Slab, 4 * chunk_need), std::max<uint64_t>(chunk_need, e->pool_cap / (2 * n_waves)));
+    } else if (e->kernel == ScanKernel::scan5) {
+        // one filter probe per two bytes: scan2's tables behind the 3-gram filter over merged classes
+        P.s5_filter = e->d_s5_filter.as<uint64_t>(); P.s5_dual = (uint32_t)e->s5.filter.size();
+        P.s5_grp = P.fold ? e->d_s5_grp_fold.as<uint8_t>() : e->d_s5_grp.as<uint8_t>();
+        P.s5_G = e->s5.G; P.s5_pad_g = e->s5.pad_group;
+        P.s5_fifo_cap = e->s5plan.fifo_cap; P.cand_cap = e->s5plan.cand_cap;
+        P.s5_sG = 0; P.s5_sgrp = nullptr; P.s5_srec_big = nullptr;
+        if (e->s5_short_groups) {
+            // more than 32 byte classes: the short terms through the group-indexed tables of scan3's set
+            P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
+            P.shorts_packed = e->d_s3_srec.as<uint32_t>(); P.shorts_words = (uint32_t)e->s3.srec.size();
+            P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
+            P.s5_srec_big = e->d_s3_srec_big.as<uint32_t>();
+            P.s5_sgrp = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
+            P.s5_sG = e->s3.G;
+        }
+        P.s5_term_bits = e->s5_term_bits; P.s5_pos_bias = e->s5_pos_bias;
+        P.s5_bloom = e->s5_bloom_lg ? e->d_s5_bloom.as<uint32_t>() : nullptr; P.s5_bloom_lg = e->s5_bloom_lg;
+    }
+    return P;
+}
+
+// Puts the engine's scan kernel on the stream once, over the whole pool as it is now; L learns what the launch owned.
+int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
+    hipStream_t st = e->stream;
+    const ScanKernel k = e->kernel;
+    ScanParams Pd; Scan3Params P3; Scan2Params P2;
+    uint64_t work = b.n_units, slab = 0;
+    L.ordered = false;
+    if (k == ScanKernel::dfa) Pd = dfa_params(e, b);
+    else if (k == ScanKernel::scan3) { P3 = scan3_params(e, b); slab = P3.slab; }
+    else {
+        if (e->opt_scan_dbg & (2 | 64)) {
+            HIP_TRY(e->d_dbg.ensure(128), "debug alloc");
+            HIP_TRY(hipMemsetAsync(e->d_dbg.p, 0, 128, st), "memset");
+        }
+        P2 = scan2_params(e, b); slab = P2.slab;
+        L.ordered = P2.ordered != 0;
+        if (k == ScanKernel::scan4) work = (b.n_units + P2.chunk_units - 1) / P2.chunk_units;
+    }
+    // every wave of the grid owns one slab from the start; the cursor counts what is taken behind those (the DFA kernel's
+    // counts matches: nothing is owned)
+    L.static_slabs = counts_slabs(k) ? grid_waves(e, work) * slab : 0;
+    {
+        ProfScope ps(e, "scan");
+        HIP_TRY(k == ScanKernel::dfa     ? launch_scan_units(Pd, e->n_cus, st)
+                : k == ScanKernel::scan2 ? launch_scan2(P2, e->scan_waves, e->n_cus, st)
+                : k == ScanKernel::scan3 ? launch_scan3(P3, e->scan_waves, e->n_cus, st)
+                : k == ScanKernel::scan4 ? launch_scan4(P2, e->scan_waves, e->n_cus, st)
+                                         : launch_scan5(P2, e->n_cus, st), "scan kernel launch");
+    }
+    if (on_scan2_tables(k) && (e->opt_scan_dbg & 64)) {
+        // phase clocks: a wave's cycles per unit (0 first bytes, 1 filter, 2 candidate list, 3 stage A, 4 stage B, 5 flush,
+        // 7 unit record), averaged over all units
+        const uint64_t n_units = b.n_units;
+        uint64_t t[16];
+        HIP_TRY(hipMemcpyAsync(t, e->d_dbg.p, sizeof t, hipMemcpyDeviceToHost, st), "debug read-back");
+        HIP_TRY(hipStreamSynchronize(st), "debug read-back");
+        if (k == ScanKernel::scan5) fprintf(stderr, "[gft scan debug] scan5 (G=%u, list %u):\n", e->s5.G, e->s5plan.cand_cap);
+        if (k == ScanKernel::scan4)
+            fprintf(stderr, "[gft scan debug] scan4 wave cycles per unit: chunk set-up %.0f, filter %.0f, queue push %.0f, stage A issue %.0f, stage A %.0f, stage B %.0f, flush %.0f, unit records %.0f\n",
+                    (double)t[4] / n_units, (double)t[5] / n_units, (double)t[6] / n_units, (double)t[7] / n_units, (double)t[8] / n_units,
+                    (double)t[9] / n_units, (double)t[10] / n_units, (double)t[11] / n_units);
+        else
+            fprintf(stderr, "[gft scan debug] wave cycles per unit: first bytes %.0f, filter %.0f, list %.0f, stage A %.0f (scan5: trips %.0f + stage-B issue and short-term trips %.0f), stage B %.0f, flush %.0f, unit record %.0f\n",
+                (double)t[4] / n_units, (double)t[5] / n_units, (double)t[6] / n_units, (double)(t[7] + t[10]) / n_units, (double)t[10] / n_units, (double)t[7] / n_units,
+                (double)t[8] / n_units, (double)t[9] / n_units, (double)t[11] / n_units);
+        double sum = 0;
+        for (int ph = 4; ph < 12; ph++) sum += (double)t[ph];
+        if (t[13]) fprintf(stderr, "[gft scan debug] %llu waves: mean %.0f cycles in all, the slowest %.0f (+%.1f %%)\n", (unsigned long long)t[13],
+                           sum / (double)t[13], (double)t[12], 100.0 * ((double)t[12] * (double)t[13] / sum - 1.0));
+    }
+    return GFT_OK;
+}
+
+// What a completed batch teaches the next ones: scan4's match density, and the unit size of the kernels on scan2's tables
+void learn_from_batch(gft_engine* e, const ScanLaunch& L, uint64_t total, uint64_t text_lo, uint64_t text_hi) {
+    if (text_hi <= text_lo) return;
+    const double per_byte = (double)total / (double)(text_hi - text_lo);
+    if (e->kernel == ScanKernel::scan4) e->scan4_density = std::max(0.002, per_byte);
+    if (on_scan2_tables(e->kernel) && !L.ordered) {
+        // a unit's matches should fit the wave's LDS fifo: a unit of maximal size should fill ~75 % of it (dense
+        // dictionaries -> smaller units; results do not depend on the unit size)
+        const double want = per_byte > 0 ? 0.75 * (e->kernel == ScanKernel::scan5 ? e->s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
+        const uint32_t um = want >= kScan2UnitMax ? kScan2UnitMax : (uint32_t)want & ~255u;
+        e->scan2_unit_max = std::max<uint32_t>(512, um);
+    }
+}
+
 // The device pipeline shared by scan and process.  On success the canonical CSR sits in e->d_match_off /
 // d_term / d_pos and *n_matches is set.
 constexpr uint64_t kHostUnitDocs = 1024;   // batches up to this many documents get their unit table from the host
 
-// defer_ok: the caller reads the control block back itself after its last kernel (deferred_check) -- the unit table and
-// the match pool are then sized from the previous batch, and a batch that outgrew them is run again.
+// defer != nullptr: the launch may be deferred -- the caller reads the control block back itself after its last kernel
+// (deferred_interpret), the unit table and the match pool are sized from the previous batch, and a batch that outgrew them is
+// run again.  *defer says whether it was, and what the launch knew.
 int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
-                  bool need_csr, uint64_t* n_matches, const uint64_t* h_doc_off = nullptr, bool defer_ok = false) {
+                  bool need_csr, uint64_t* n_matches, const uint64_t* h_doc_off = nullptr, ScanLaunch* defer = nullptr) {
     hipStream_t st = e->stream;
     *n_matches = 0;
-    e->deferred = false;
-    e->deferred_single = false;
+    ScanLaunch L;
+    if (defer) *defer = L;
     e->scan_valid_docs = ~0ull;           // the pool is about to be overwritten
     e->csr_valid = false;
     HIP_TRY(e->d_match_off.ensure((n_docs + 1) * 8), "match_off alloc");
@@ -568,7 +784,8 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     const uint32_t warm = e->tab.max_term_len ? e->tab.max_term_len - 1 : 0;
     // gft_scan2: a unit's matches should fit the wave's LDS fifo (kScan2FifoCap), so the unit size follows the match
     // density the previous call saw (dense dictionaries -> smaller units); results do not depend on it
-    const uint32_t unit_max = e->use_scan3 ? kScan3UnitMax : e->use_scan4 ? kScan4UnitMax : e->use_scan2 ? e->scan2_unit_max : kTextBuf - warm;
+    const uint32_t unit_max = e->kernel == ScanKernel::scan3 ? kScan3UnitMax : e->kernel == ScanKernel::scan4 ? kScan4UnitMax
+                              : on_scan2_tables(e->kernel) ? e->scan2_unit_max : kTextBuf - warm;
 
     // 1. work units
     HIP_TRY(e->d_ctl.ensure(64), "control alloc");
@@ -580,11 +797,11 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     // table is a few entries, computed here and uploaded instead of five kernel launches and a synchronising read-back
     const bool host_units = h_doc_off != nullptr && n_docs <= kHostUnitDocs;
     // The batch before was one unit per document: this one gets its unit table from ONE launch on that assumption
-    // (k_units_single) instead of count + prefix sum + fill + clamp; deferred_check learns whether it held.  That launch
+    // (k_units_single) instead of count + prefix sum + fill + clamp; deferred_interpret learns whether it held.  That launch
     // also clears the control block (its two flags are raised to the batch's EPOCH, a number no earlier batch wrote there,
     // so they need no clearing): one node less on the stream of every batch
-    bool units_single = !host_units && defer_ok && !need_csr && e->single_streak >= 2 && e->pool_cap > 0 &&
-                        std::min(std::min(e->d_units.cap / sizeof(Unit), e->d_unit_start.cap / 8), e->d_unit_count.cap / 4) >= n_docs;
+    const uint64_t cap_units = std::min(std::min(e->d_units.cap / sizeof(Unit), e->d_unit_start.cap / 8), e->d_unit_count.cap / 4);
+    bool units_single = !host_units && defer && !need_csr && e->single_streak >= 2 && e->pool_cap > 0 && cap_units >= n_docs;
     if (units_single && ++e->ctl_epoch < 2) { e->ctl_epoch = 1; units_single = false; }      // (wrapped: this batch the general way)
     if (!units_single) HIP_TRY(hipMemsetAsync(e->d_ctl.p, 0, 32, st), "memset");     // flag, cursor, match count, non-ASCII flag
     std::vector<uint64_t> hub;
@@ -612,8 +829,8 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         HIP_TRY(launch_units_single(d_doc_off, n_docs, unit_max, e->d_units.as<Unit>(), e->d_unit_base.as<uint64_t>(),
                                     e->d_ctl.as<uint32_t>(), e->ctl_epoch, st), "unit table");
         n_units = n_docs; text_lo = 0; text_hi = ~0ull;
-        e->deferred = true; e->deferred_single = true; e->deferred_epoch = e->ctl_epoch;
-        e->deferred_unit_cap = n_docs; e->deferred_n_docs = n_docs;
+        L.deferred = L.single = true; L.epoch = e->ctl_epoch;
+        L.unit_cap = L.n_docs = n_docs;
     } else {
         {
             ProfScope ps(e, "aux");
@@ -624,12 +841,11 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         }
         // No read-back when the caller checks afterwards: the tables keep the size the last batch gave them (a document
         // is one unit unless it is longer than unit_max), units beyond the table are dropped and every index is clamped
-        // into it -- deferred_check sees the true count and has the batch run again
-        const uint64_t cap_units = std::min(std::min(e->d_units.cap / sizeof(Unit), e->d_unit_start.cap / 8), e->d_unit_count.cap / 4);
-        e->deferred = defer_ok && !need_csr && cap_units >= n_docs && e->pool_cap > 0;
-        if (e->deferred) {
+        // into it -- deferred_interpret sees the true count and has the batch run again
+        L.deferred = defer && !need_csr && cap_units >= n_docs && e->pool_cap > 0;
+        if (L.deferred) {
             n_units = cap_units; text_lo = 0; text_hi = ~0ull;       // (the text blob is readable 64 bytes past its end: gft.h)
-            e->deferred_unit_cap = cap_units; e->deferred_n_docs = n_docs;
+            L.unit_cap = cap_units; L.n_docs = n_docs;
         } else {
             uint64_t rb[7] = {0, 0, 0, 0, 0, 0, 0};
             HIP_TRY(hipMemcpyAsync(rb, e->d_ctl.p, sizeof rb, hipMemcpyDeviceToHost, st), "readback");
@@ -642,7 +858,7 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         }
     }
 
-    if (!e->deferred) { e->last_text_lo = text_lo; e->last_text_hi = text_hi; }
+    if (!L.deferred) { e->last_text_lo = text_lo; e->last_text_hi = text_hi; }
     HIP_TRY(e->d_units.ensure(n_units * sizeof(Unit)), "unit alloc");
     HIP_TRY(e->d_unit_start.ensure(n_units * 8), "unit alloc");
     HIP_TRY(e->d_unit_count.ensure(n_units * 4), "unit alloc");
@@ -652,9 +868,9 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         ProfScope ps(e, "aux");
         if (host_units) {
             if (n_units) HIP_TRY(hipMemcpyAsync(e->d_units.p, hun.data(), n_units * sizeof(Unit), hipMemcpyHostToDevice, st), "unit upload");
-        } else if (e->deferred_single) {
+        } else if (L.single) {
             // (k_units_single has filled the table)
-        } else if (e->deferred) {
+        } else if (L.deferred) {
             HIP_TRY(hipMemsetAsync(e->d_units.p, 0, n_units * sizeof(Unit), st), "memset");      // empty units behind the real ones
             HIP_TRY(launch_unit_fill(d_doc_off, n_docs, e->d_unit_base.as<uint64_t>(), e->d_units.as<Unit>(), unit_max, st, n_units), "unit_fill");
             HIP_TRY(launch_clamp_u64(e->d_unit_base.as<uint64_t>(), n_docs + 1, n_units, st), "unit clamp");
@@ -664,237 +880,39 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     }
 
     // 2. automaton walk into the slab pool; grow the pool and re-run if it overflowed (never truncate)
-    if (e->deferred) e->deferred_pool_cap = e->pool_cap;
-    int rc = e->deferred ? GFT_OK : ensure_pool(e, std::max<uint64_t>(1u << 20, (text_hi - text_lo) / 16));
-    if (!rc && !e->deferred && (e->use_scan2 || e->use_scan3)) {
+    const ScanKernel k = e->kernel;
+    if (L.deferred) L.pool_cap = e->pool_cap;
+    int rc = L.deferred ? GFT_OK : ensure_pool(e, std::max<uint64_t>(1u << 20, (text_hi - text_lo) / 16));
+    if (!rc && !L.deferred && counts_slabs(k)) {
         // (every wave of the grid owns a slab from the start: the pool holds those twice over, or a small batch on a fresh
         // engine would overflow it before it had written a match)
         // (scan4: a slab holds at least one chunk's regions -- up to eight units of unit_max bytes at 1.6 x the density seen)
-        const uint64_t wpw = e->use_scan3 ? e->scan3_waves : e->use_scan4 ? e->scan4_waves : e->use_scan5 ? kScan5Waves : e->scan2_k2_waves;
-        const uint64_t min_slab = e->use_scan3 ? 2 * kScan3MinRoom
-                                  : e->use_scan4 ? kScan4ChunkUnits * ((uint64_t)(unit_max * e->scan4_density * 1.6) + 49) : 64;
-        const uint64_t waves = std::min<uint64_t>(std::max<uint64_t>((n_units + wpw - 1) / wpw, 1), e->n_cus) * wpw;
-        rc = ensure_pool(e, 2 * waves * min_slab);
+        const uint64_t min_slab = k == ScanKernel::scan4 ? kScan4ChunkUnits * ((uint64_t)(unit_max * e->scan4_density * 1.6) + 49) : slab_floor(k);
+        rc = ensure_pool(e, 2 * grid_waves(e, n_units) * min_slab);
     }
     if (rc) return rc;
+    const ScanBatch batch{d_text, d_doc_off, n_docs, n_units, text_hi, flags, unit_max, need_csr};
     uint64_t total = 0;
-    for (int attempt = 0; attempt < 3 && e->use_scan3; attempt++) {
+    for (int attempt = 0; attempt < 3; attempt++) {
         if (attempt) HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint8_t>() + 8, 0, 16, st), "memset");
-        Scan3Params P;
-        P.text = d_text; P.doc_off = d_doc_off; P.units = e->d_units.as<Unit>(); P.n_units = n_units; P.text_bytes = text_hi;
-        P.fold = (flags & GFT_FOLD_ASCII) ? 1 : 0;
-        P.cls = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
-        P.filter = e->d_s3_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s3.filter.size();
-        P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
-        P.srec = e->d_s3_srec.as<uint32_t>(); P.srec_words = (uint32_t)e->s3.srec.size();
-        P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
-        P.srec_big = e->d_s3_srec_big.as<uint32_t>();
-        P.bloom = e->d_s3_bloom.as<uint32_t>(); P.bloom_lg = e->s3.bloom_lg; P.bloom_lds = e->s3.bloom_lg <= kScan3BloomLdsLg ? 1 : 0;
-        P.slots = e->d_s3_slots.as<Scan2Slot>(); P.slot_shift = e->s3.slot_shift; P.slot_seed = e->s3.slot_seed;
-        P.more = e->d_s3_more.as<Scan2Slot>();
-        P.term_blob = e->d_s3_term_blob.as<uint8_t>(); P.term_off = e->d_s3_term_off.as<uint32_t>();
-        P.G = e->s3.G; P.grouped = e->s3.grouped ? 1 : 0;
-        P.pos_end = (e->build_flags & GFT_POS_END) ? 1 : 0;
-        // presence-only mode: positions are only read by INORD groups (and by CSR callers)
-        P.want_pos = (need_csr || e->n_inord_groups > 0) ? 1 : 0;
-        P.prio = e->opt_scan_prio;
-        P.dbg = e->opt_scan_dbg;
-        P.nonascii = e->d_ctl.as<uint32_t>() + 6;
-        P.cand_cap = e->scan3_cand_cap;
-        P.cursor = e->d_ctl.as<uint64_t>() + 1; P.pool_cap = e->pool_cap;
-        P.pool_term = e->d_pool_term.as<uint32_t>(); P.pool_pos = e->d_pool_pos.as<uint32_t>();
-        P.unit_start = e->d_unit_start.as<uint64_t>(); P.unit_count = e->d_unit_count.as<uint32_t>();
-        P.n_matches = e->d_ctl.as<uint64_t>() + 2;
-        // slab slack is at most one slab per resident wave: keep it below half the pool
-        const uint64_t n_waves = (uint64_t)e->n_cus * e->scan3_waves;
-        P.slab = (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(2 * kScan3MinRoom, e->pool_cap / (2 * n_waves)));
-        // every wave of the grid owns one slab from the start; the cursor counts what is taken behind those
-        e->last_static_slabs = std::min<uint64_t>(std::max<uint64_t>((n_units + e->scan3_waves - 1) / e->scan3_waves, 1), e->n_cus) * e->scan3_waves * P.slab;
-        {
-            ProfScope ps(e, "scan");
-            HIP_TRY(launch_scan3(P, e->scan3_waves, e->n_cus, st), "scan kernel launch");
-        }
-        if (e->deferred) return GFT_OK;                       // (deferred_check reads the cursor after the solver)
-        uint64_t ct[3] = {0, 0, 0};
+        if ((rc = enqueue_scan(e, batch, L))) return rc;
+        if (L.deferred) { *defer = L; return GFT_OK; }         // (the caller reads the cursor back after the solver)
+        uint64_t ct[3] = {0, 0, 0};                            // cursor, exact match count (the DFA kernel: none, its cursor is that), non-ASCII bits
         HIP_TRY(hipMemcpyAsync(ct, e->d_ctl.as<uint8_t>() + 8, 24, hipMemcpyDeviceToHost, st), "readback");
         HIP_TRY(hipStreamSynchronize(st), "scan kernel");
-        const uint64_t cursor = ct[0] + e->last_static_slabs;
-        total = ct[1];
+        const uint64_t cursor = ct[0] + L.static_slabs;
+        total = counts_slabs(k) ? ct[1] : ct[0];
         e->last_nonascii_bits = (uint32_t)ct[2]; e->last_nonascii = e->last_nonascii_bits != 0;
-        if (cursor <= e->pool_cap) break;
-        if (attempt == 2) return fail(e, GFT_E_HIP, "match pool overflow persisted");
-        rc = ensure_pool(e, cursor + cursor / 16);
-        if (rc) return rc;
-    }
-    for (int attempt = 0; attempt < 3 && e->use_scan2 && !e->use_scan3; attempt++) {
-        if (attempt) HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint8_t>() + 8, 0, 16, st), "memset");
-        Scan2Params P;
-        P.text = d_text; P.doc_off = d_doc_off; P.units = e->d_units.as<Unit>(); P.n_units = n_units;
-        P.filter = e->d_s2_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s2.filter.size();
-        P.hashed = e->s2.hashed ? 1 : 0; P.hash_shift = e->s2.hash_shift;
-        P.short3 = e->d_s2_short3.as<uint8_t>(); P.short3_bytes = e->scan2_short3_bytes;
-        P.fpt = e->d_s2_fpt.as<uint8_t>(); P.fpt_lg = e->s2.fpt_lg;
-        P.shorts_packed = e->d_s2_shorts_packed.as<uint32_t>(); P.shorts_words = (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
-        P.short3_big = e->s2.short3_big.empty() ? nullptr : e->d_s2_short3_big.as<uint32_t>();
-        P.cand_cap = e->scan2_cand_cap;
-        P.slots = e->d_s2_slots.as<Scan2Slot>(); P.slot_shift = e->s2.slot_shift; P.slot_seed = e->s2.slot_seed;
-        P.more = e->d_s2_more.as<Scan2Slot>();
-        P.text_bytes = text_hi;
-        P.fold = (flags & GFT_FOLD_ASCII) ? 1 : 0;
-        P.cls = P.fold ? e->d_s2_cls_fold.as<uint8_t>() : e->d_s2_cls.as<uint8_t>();
-        P.term_blob = e->d_s2_term_blob.as<uint8_t>(); P.term_off = e->d_s2_term_off.as<uint32_t>();
-        P.kp = e->s2.kp; P.pad_class = e->s2.pad_class;
-        P.pos_end = (e->build_flags & GFT_POS_END) ? 1 : 0;
-        P.cursor = e->d_ctl.as<uint64_t>() + 1; P.pool_cap = e->pool_cap;
-        P.pool_term = e->d_pool_term.as<uint32_t>(); P.pool_pos = e->d_pool_pos.as<uint32_t>();
-        P.unit_start = e->d_unit_start.as<uint64_t>(); P.unit_count = e->d_unit_count.as<uint32_t>();
-        P.n_matches = e->d_ctl.as<uint64_t>() + 2;
-        // slab slack is at most one slab per resident wave: keep it below half the pool
-        const uint64_t n_waves = (uint64_t)e->n_cus * e->scan2_k2_waves;
-        P.slab = (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(64, e->pool_cap / (2 * n_waves)));
-        // every wave of the grid owns one slab from the start; the cursor counts what is taken behind those
-        e->last_static_slabs = std::min<uint64_t>(std::max<uint64_t>((n_units + e->scan2_k2_waves - 1) / e->scan2_k2_waves, 1), e->n_cus) * e->scan2_k2_waves * P.slab;
-        // the balanced path serves both callers: the solver reads presence / successor positions in any order, and
-        // CSR results are put into emission order by the gather (k_gather_sorted).  GFT_SCAN_ORDERED=1 sends every unit
-        // through the kernel's per-lane staging path (normally the fallback for units whose matches overflow the LDS
-        // fifo): a second implementation of the verification, kept as a cross-check
-        P.ordered = (need_csr && e->opt_scan_ordered) ? 1 : 0;
-        // presence-only mode: positions are only read by INORD groups (and by CSR callers)
-        P.want_pos = (need_csr || e->n_inord_groups > 0) ? 1 : 0;
-        P.dbg = e->opt_scan_dbg;
-        P.nonascii = e->d_ctl.as<uint32_t>() + 6;
-        // wave priorities: the latency-bound verification stages overtake the filter phase of the other waves (5 % on
-        // the benchmark; GFT_SCAN_PRIO=0 switches it off)
-        P.prio = e->opt_scan_prio;
-        P.dbg_counters = nullptr;
-        if (P.dbg & (2 | 64)) {
-            HIP_TRY(e->d_dbg.ensure(128), "debug alloc");
-            HIP_TRY(hipMemsetAsync(e->d_dbg.p, 0, 128, st), "memset");
-            P.dbg_counters = e->d_dbg.as<uint64_t>();
-        }
-        if (e->use_scan4) {
-            // the streaming form: chunks of up to eight units (fewer when the batch is small: every wave should get several
-            // chunks), a fifo in place of the candidate list, per-unit regions sized from the density seen so far
-            const uint64_t n_waves4 = (uint64_t)e->n_cus * e->scan4_waves;
-            P.chunk_units = (uint32_t)std::min<uint64_t>(kScan4ChunkUnits, std::max<uint64_t>(1, n_docs / (n_waves4 * 4)));
-            if (e->opt_scan4_chunk) P.chunk_units = std::min<uint32_t>(e->opt_scan4_chunk, kScan4ChunkUnits);      // (GFT_SCAN4_CHUNK: tests)
-            P.cand_cap = e->scan4_fifo[P.want_pos ? 1 : 0];
-            P.bound_q16 = (uint32_t)std::min<double>(e->scan4_density * 1.6 * 65536.0 + 1.0, 4.0e9);
-            P.bound_add = 48;
-            P.round_c = e->opt_scan4_round ? std::min<uint32_t>(64, std::max<uint32_t>(16, e->opt_scan4_round & ~15u)) : 64;   // (GFT_SCAN4_ROUND: timing studies)
-            // a slab should hold a few chunks' regions (the rest of a slab that the next chunk does not fit is lost)
-            const uint64_t chunk_need = (uint64_t)P.chunk_units * (((uint64_t)unit_max * P.bound_q16 >> 16) + P.bound_add);
-            P.slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kScan2Slab, 4 * chunk_need), std::max<uint64_t>(chunk_need, e->pool_cap / (2 * n_waves4)));
-            const uint64_t n_chunks = (n_units + P.chunk_units - 1) / P.chunk_units;
-            e->last_static_slabs = std::min<uint64_t>(std::max<uint64_t>((n_chunks + e->scan4_waves - 1) / e->scan4_waves, 1), e->n_cus) * e->scan4_waves * P.slab;
-            ProfScope ps(e, "scan");
-            HIP_TRY(launch_scan4(P, e->scan4_waves, e->n_cus, st), "scan kernel launch");
-        } else if (e->use_scan5) {
-            // one filter probe per two bytes: scan2's tables behind the 3-gram filter over merged classes
-            P.s5_filter = e->d_s5_filter.as<uint64_t>(); P.s5_dual = (uint32_t)e->s5.filter.size();
-            P.s5_grp = P.fold ? e->d_s5_grp_fold.as<uint8_t>() : e->d_s5_grp.as<uint8_t>();
-            P.s5_G = e->s5.G; P.s5_pad_g = e->s5.pad_group;
-            P.s5_fifo_cap = e->s5plan.fifo_cap; P.cand_cap = e->s5plan.cand_cap;
-            P.s5_sG = 0; P.s5_sgrp = nullptr; P.s5_srec_big = nullptr;
-            if (e->s5_short_groups) {
-                // more than 32 byte classes: the short terms through the group-indexed tables of the stride-2 kernel's set
-                P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
-                P.shorts_packed = e->d_s3_srec.as<uint32_t>(); P.shorts_words = (uint32_t)e->s3.srec.size();
-                P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
-                P.s5_srec_big = e->d_s3_srec_big.as<uint32_t>();
-                P.s5_sgrp = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
-                P.s5_sG = e->s3.G;
-            }
-            P.s5_term_bits = e->s5_term_bits; P.s5_pos_bias = e->s5_pos_bias;
-            P.s5_bloom = e->s5_bloom_lg ? e->d_s5_bloom.as<uint32_t>() : nullptr; P.s5_bloom_lg = e->s5_bloom_lg;
-            const uint64_t n_waves5 = (uint64_t)e->n_cus * kScan5Waves;
-            P.slab = (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(64, e->pool_cap / (2 * n_waves5)));
-            e->last_static_slabs = std::min<uint64_t>(std::max<uint64_t>((n_units + kScan5Waves - 1) / kScan5Waves, 1), e->n_cus) * kScan5Waves * P.slab;
-            ProfScope ps(e, "scan");
-            HIP_TRY(launch_scan5(P, e->n_cus, st), "scan kernel launch");
-        } else {
-            ProfScope ps(e, "scan");
-            // gft_scan2 serves both paths (ordered for CSR results, unordered + balanced for the solver)
-            HIP_TRY(launch_scan2(P, e->scan2_k2_waves, e->n_cus, st), "scan kernel launch");
-        }
-        if (P.dbg & 64) {
-            // phase clocks: a wave's cycles per unit (0 first bytes, 1 filter, 2 candidate list, 3 stage A, 4 stage B, 5 flush,
-            // 7 unit record), averaged over all units
-            uint64_t t[16];
-            HIP_TRY(hipMemcpyAsync(t, e->d_dbg.p, sizeof t, hipMemcpyDeviceToHost, st), "debug read-back");
-            HIP_TRY(hipStreamSynchronize(st), "debug read-back");
-            if (e->use_scan5) fprintf(stderr, "[gft scan debug] scan5 (G=%u, list %u):\n", e->s5.G, e->s5plan.cand_cap);
-            if (e->use_scan4)
-                fprintf(stderr, "[gft scan debug] scan4 wave cycles per unit: chunk set-up %.0f, filter %.0f, queue push %.0f, stage A issue %.0f, stage A %.0f, stage B %.0f, flush %.0f, unit records %.0f\n",
-                        (double)t[4] / n_units, (double)t[5] / n_units, (double)t[6] / n_units, (double)t[7] / n_units, (double)t[8] / n_units,
-                        (double)t[9] / n_units, (double)t[10] / n_units, (double)t[11] / n_units);
-            else
-            fprintf(stderr, "[gft scan debug] wave cycles per unit: first bytes %.0f, filter %.0f, list %.0f, stage A %.0f (scan5: trips %.0f + stage-B issue and short-term trips %.0f), stage B %.0f, flush %.0f, unit record %.0f\n",
-                    (double)t[4] / n_units, (double)t[5] / n_units, (double)t[6] / n_units, (double)(t[7] + t[10]) / n_units, (double)t[10] / n_units, (double)t[7] / n_units,
-                    (double)t[8] / n_units, (double)t[9] / n_units, (double)t[11] / n_units);
-            double sum = 0;
-            for (int k = 4; k < 12; k++) sum += (double)t[k];
-            if (t[13]) fprintf(stderr, "[gft scan debug] %llu waves: mean %.0f cycles in all, the slowest %.0f (+%.1f %%)\n", (unsigned long long)t[13],
-                               sum / (double)t[13], (double)t[12], 100.0 * ((double)t[12] * (double)t[13] / sum - 1.0));
-        }
-        if (e->deferred) return GFT_OK;                       // (deferred_check reads the cursor after the solver)
-        uint64_t ct[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(ct, e->d_ctl.as<uint8_t>() + 8, 24, hipMemcpyDeviceToHost, st), "readback");
-        HIP_TRY(hipStreamSynchronize(st), "scan kernel");
-        const uint64_t cursor = ct[0] + e->last_static_slabs;
-        total = ct[1];
-        e->last_nonascii_bits = (uint32_t)ct[2]; e->last_nonascii = e->last_nonascii_bits != 0;
-        if (P.dbg & 2) {
+        if (on_scan2_tables(k) && (e->opt_scan_dbg & 2)) {
             uint64_t c4[4] = {0, 0, 0, 0};
             HIP_TRY(hipMemcpy(c4, e->d_dbg.p, 32, hipMemcpyDeviceToHost), "debug readback");
             fprintf(stderr, "[gft scan debug] units=%llu flagged=%llu sum_of_per_unit_max_lane=%llu to_bucket_table=%llu matches=%llu\n",
                     (unsigned long long)n_units, (unsigned long long)c4[0], (unsigned long long)c4[1],
                     (unsigned long long)c4[2], (unsigned long long)total);
         }
-        if (cursor <= e->pool_cap) {
-            if (e->use_scan4 && text_hi > text_lo) e->scan4_density = std::max(0.002, (double)total / (double)(text_hi - text_lo));
-            if (P.ordered == 0 && text_hi > text_lo) {
-                // a unit of maximal size should fill ~75 % of the fifo
-                const double per_byte = (double)total / (double)(text_hi - text_lo);
-                const double want = per_byte > 0 ? 0.75 * (e->use_scan5 ? e->s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
-                uint32_t um = want >= kScan2UnitMax ? kScan2UnitMax : (uint32_t)want & ~255u;
-                e->scan2_unit_max = std::max<uint32_t>(512, um);
-            }
-            break;
-        }
+        if (cursor <= e->pool_cap) { learn_from_batch(e, L, total, text_lo, text_hi); break; }
         if (attempt == 2) return fail(e, GFT_E_HIP, "match pool overflow persisted");
         rc = ensure_pool(e, cursor + cursor / 16);
-        if (rc) return rc;
-    }
-    for (int attempt = 0; attempt < 3 && !e->use_scan2 && !e->use_scan3; attempt++) {
-        if (attempt) HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint8_t>() + 8, 0, 16, st), "memset");
-        ScanParams P;
-        P.text = d_text; P.doc_off = d_doc_off; P.units = e->d_units.as<Unit>(); P.n_units = n_units;
-        P.byte_class = e->d_byte_class.as<uint8_t>(); P.delta = e->d_delta.as<uint32_t>();
-        P.out_term = e->d_out_term.as<uint32_t>(); P.out_link = e->d_out_link.as<uint32_t>();
-        P.term_len = e->d_term_len.as<uint32_t>();
-        P.n_classes = e->tab.n_classes; P.n_states = e->tab.n_states; P.n_lds_states = e->n_lds_states;
-        P.max_term_len = e->tab.max_term_len;
-        P.pos_end = (e->build_flags & GFT_POS_END) ? 1 : 0;
-        P.fold = (flags & GFT_FOLD_ASCII) ? 1 : 0;
-        P.nonascii = e->d_ctl.as<uint32_t>() + 6;
-        P.cursor = e->d_ctl.as<uint64_t>() + 1; P.pool_cap = e->pool_cap;
-        P.pool_term = e->d_pool_term.as<uint32_t>(); P.pool_pos = e->d_pool_pos.as<uint32_t>();
-        P.unit_start = e->d_unit_start.as<uint64_t>(); P.unit_count = e->d_unit_count.as<uint32_t>();
-        e->last_static_slabs = 0;                                // (this kernel's cursor counts matches)
-        {
-            ProfScope ps(e, "scan");
-            HIP_TRY(launch_scan_units(P, e->n_cus, st), "scan kernel launch");
-        }
-        if (e->deferred) return GFT_OK;
-        uint64_t ct[3] = {0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(ct, e->d_ctl.as<uint8_t>() + 8, 24, hipMemcpyDeviceToHost, st), "readback");
-        HIP_TRY(hipStreamSynchronize(st), "scan kernel");
-        total = ct[0];
-        e->last_nonascii_bits = (uint32_t)ct[2]; e->last_nonascii = e->last_nonascii_bits != 0;
-        if (total <= e->pool_cap) break;
-        if (attempt == 2) return fail(e, GFT_E_HIP, "match pool overflow persisted");
-        rc = ensure_pool(e, total + total / 16);
         if (rc) return rc;
     }
 
@@ -904,56 +922,32 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     return csr_from_pool(e, n_docs);
 }
 
-// After the last kernel of a batch whose scan was launched blind (scan_pipeline, defer_ok): ONE read-back of the control
-// block -- the batch's only host synchronisation.  *again = the unit table or the match pool was too small (they have
-// been grown): the caller runs the batch once more, this time with the sizes known.
-// (what the launch of a deferred batch knew: the engine's fields at that time, or a pipelined batch's snapshot of them --
-// the pool may have grown since, for another batch, but the kernels of this one wrote nothing past pool_cap)
-struct DeferredLaunch { bool single; uint64_t n_docs, unit_cap, pool_cap, static_slabs; uint32_t epoch; };   // epoch: of a k_units_single batch (its flags)
-int deferred_interpret(gft_engine* e, const uint64_t* rb, const DeferredLaunch& dl, bool* again);
-
-int deferred_check(gft_engine* e, bool* again) {
+// The verdict on a deferred launch (scan_pipeline) from the read-back of the control block that its caller made after the
+// batch's last kernel -- the batch's only host synchronisation.  *again = the unit table or the match pool was too small
+// (they have been grown): the caller runs the batch once more, this time with the sizes known.
+int deferred_interpret(gft_engine* e, const uint64_t* rb, const ScanLaunch& L, bool* again) {
     *again = false;
-    if (!e->deferred) return GFT_OK;
-    e->deferred = false;
-    // (into pinned memory: a copy to pageable memory is staged by the runtime, ten microseconds on every batch)
-    if (!e->pin_rb) HIP_TRY(hipHostMalloc((void**)&e->pin_rb, 64, hipHostMallocDefault), "pinned alloc");
-    uint64_t* rb = e->pin_rb;
-    HIP_TRY(hipMemcpyAsync(rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
-    HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
-    return deferred_interpret(e, rb, DeferredLaunch{e->deferred_single, e->deferred_n_docs, e->deferred_unit_cap, e->deferred_pool_cap, e->last_static_slabs, e->deferred_single ? e->deferred_epoch : 0u}, again);
-}
-
-int deferred_interpret(gft_engine* e, const uint64_t* rb, const DeferredLaunch& dl, bool* again) {
-    *again = false;
-    const uint64_t cursor = rb[1] + dl.static_slabs, total = rb[2], n_units = rb[4], text_lo = rb[5], text_hi = rb[6];
+    const uint64_t cursor = rb[1] + L.static_slabs, total = rb[2], n_units = rb[4], text_lo = rb[5], text_hi = rb[6];
     e->last_nonascii_bits = (uint32_t)rb[3]; e->last_nonascii = e->last_nonascii_bits != 0;
     // (a k_units_single batch raises its flags to its epoch; what an earlier batch left there is smaller)
-    const bool flag_bad = dl.single ? (uint32_t)rb[0] == dl.epoch : (uint32_t)rb[0] != 0;
-    if (dl.single && (uint32_t)(rb[3] >> 32) == dl.epoch) {      // a document of more than one unit: the general path
+    const bool flag_bad = L.single ? (uint32_t)rb[0] == L.epoch : (uint32_t)rb[0] != 0;
+    if (L.single && (uint32_t)(rb[3] >> 32) == L.epoch) {      // a document of more than one unit: the general path
         e->single_streak = -8;
         *again = true;
         return GFT_OK;
     }
-    e->single_streak = n_units == dl.n_docs ? e->single_streak + 1 : std::min(e->single_streak, 0);
+    e->single_streak = n_units == L.n_docs ? e->single_streak + 1 : std::min(e->single_streak, 0);
     e->last_text_lo = text_lo; e->last_text_hi = text_hi;
     e->last_n_units = n_units; e->last_total = total;
     if (text_hi < text_lo) return fail(e, GFT_E_INVALID, "doc_off is not ascending");
     if (flag_bad) return fail(e, GFT_E_INVALID, "doc_off is not ascending, or a document is longer than 4 GiB - 1 bytes (positions are 32-bit)");
     // (the DFA kernel's cursor counts matches, the suffix-window kernels' slabs: both must fit the pool)
-    if (n_units > dl.unit_cap || cursor > dl.pool_cap) {
-        if (cursor > dl.pool_cap) { int rc = ensure_pool(e, cursor + cursor / 16); if (rc) return rc; }     // (a no-op when it has grown past the cursor since)
+    if (n_units > L.unit_cap || cursor > L.pool_cap) {
+        if (cursor > L.pool_cap) { int rc = ensure_pool(e, cursor + cursor / 16); if (rc) return rc; }     // (a no-op when it has grown past the cursor since)
         *again = true;
         return GFT_OK;
     }
-    if (e->use_scan4 && text_hi > text_lo) e->scan4_density = std::max(0.002, (double)total / (double)(text_hi - text_lo));
-    if (e->use_scan2 && !e->use_scan3 && !e->opt_scan_ordered && text_hi > text_lo) {
-        // scan2: a unit of maximal size should fill ~75 % of the fifo
-        const double per_byte = (double)total / (double)(text_hi - text_lo);
-        const double want = per_byte > 0 ? 0.75 * (e->use_scan5 ? e->s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
-        const uint32_t um = want >= kScan2UnitMax ? kScan2UnitMax : (uint32_t)want & ~255u;
-        e->scan2_unit_max = std::max<uint32_t>(512, um);
-    }
+    learn_from_batch(e, L, total, text_lo, text_hi);
     return GFT_OK;
 }
 
@@ -1445,7 +1439,101 @@ int gft_set_cu_margin(gft_engine* e, uint32_t margin) try {
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
-// e->tab / e->s2 hold compiled tables (from gft_build or gft_import_tables): check them against the device, upload
+// GFT_SCAN_KERNEL: the kernel the caller asks for ("auto", empty and unset: none)
+enum class Forced { none, dfa, scan2, scan3, scan4, scan5, unknown };
+static Forced forced_scan_kernel() {
+    const char* v = getenv("GFT_SCAN_KERNEL");
+    if (!v || !*v || !std::strcmp(v, "auto")) return Forced::none;
+    for (int k = 0; k < 5; k++)
+        if (!std::strcmp(v, kScanKernelName[k])) return (Forced)(k + 1);     // (ScanKernel's order)
+    return Forced::unknown;
+}
+
+// Does scan5 apply to the compiled tables?  It runs on scan2's long-term tables; a fifo entry of 32 bits holds term id and
+// relative position.  With more than 32 byte classes there is no direct short-term table
+// (Scan2Tables::short_direct): the group-indexed one of scan3's tables serves then (GFT_SCAN5_LARGE=0 leaves such
+// dictionaries to scan3).  Leaves its LDS plan and the shape of its fifo entries and Bloom level in the engine.
+static bool plan_scan5(gft_engine* e) {
+    const bool large = !e->s2.short_direct && e->s3.supported && e->opt_scan5_large;
+    if (!e->s2.long_ok || !(e->s2.supported || large)) return false;
+    uint32_t tb = 1;
+    while ((1ull << tb) < e->tab.terms.size()) tb++;
+    e->s5_term_bits = tb;
+    e->s5_pos_bias = e->tab.max_term_len + kScan2MaxOff;
+    const bool packs = (uint64_t)kScan2UnitMax + e->s5_pos_bias + 8 < (1ull << (32 - tb));
+    const uint32_t short_bytes = large ? (uint32_t)e->s3.short3.size() : (uint32_t)e->s2.short3.size();
+    const uint32_t rec_words = large ? (uint32_t)e->s3.srec.size() : (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
+    // a fingerprint table too large for LDS (fpt_lg != 0) gets a Bloom level there instead: 2^lg bits, as large as
+    // GFT_SCAN5_BLOOM_KB allows but not more than eight bits per item would take
+    e->s5_bloom_lg = 0;
+    if (e->s2.fpt_lg && e->opt_scan5_bloom_kb) {
+        uint32_t lg = 13;
+        while ((2u << lg) / 8 <= e->opt_scan5_bloom_kb * 1024u && (1ull << lg) < 8 * e->s2.n_keys) lg++;
+        e->s5_bloom_lg = lg;
+    }
+    bool fits = false;
+    for (int attempt = 0; attempt < 2 && packs && !fits; attempt++) {
+        const uint32_t in_lds = e->s2.fpt_lg ? (e->s5_bloom_lg ? (1u << e->s5_bloom_lg) / 8 : 0u) : kScan2FptSize;
+        fits = scan5_plan(e->s2.kp, short_bytes, rec_words, in_lds, e->lds_max - 512, e->opt_scan5_fifo ? e->opt_scan5_fifo : kScan2FifoCap, &e->s5plan);
+        if (!fits) e->s5_bloom_lg = 0;                      // (no room: without the Bloom level)
+    }
+    if (!fits) return false;
+    if (e->opt_scan5_groups && e->opt_scan5_groups < e->s5plan.G) {      // (tests: more merging than LDS asks for)
+        e->s5plan.G = std::max<uint32_t>(e->opt_scan5_groups, 2);
+        e->s5plan.dual_entries = e->s5plan.G * e->s5plan.G * e->s5plan.G;
+    }
+    e->s5_short_groups = large;
+    return true;
+}
+
+// The scan kernel for the compiled tables in e->tab / s2 / s3 (the table of DESIGN.md 4.7): sets e->kernel, its waves per
+// workgroup and what its LDS plan says; uploads nothing.  scan5 is the default wherever it applies, scan3 (any alphabet)
+// everywhere else; scan2 / scan4 (extra-kernels builds) and the DFA kernel are cross-checks that GFT_SCAN_KERNEL asks for.
+static int choose_scan_kernel(gft_engine* e) {
+    const Forced f = forced_scan_kernel();
+    if (!kExtraKernels && (f == Forced::scan2 || f == Forced::scan4))
+        return fail(e, GFT_E_UNSUPPORTED, std::string("GFT_SCAN_KERNEL=") + kScanKernelName[(int)f - 1] + ": this library was built without the cross-check kernels (GFT_EXTRA_KERNELS=1 python -m gofindthem_amd.build --force)");
+    const size_t lds = e->lds_max - 512;
+    const uint32_t s2_filter = (uint32_t)e->s2.filter.size(), s2_short3 = (uint32_t)e->s2.short3.size(),
+                   s2_recs = (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3), s2_fpt = e->s2.fpt_lg ? 0u : kScan2FptSize;
+    uint32_t w2 = 0, w3 = 0, w4[2] = {0, 0};
+    const bool k2_fits = e->s2.supported && scan2_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, &w2, &e->scan2_cand_cap);
+    // (scan4's fifo capacities belong to the smaller of the two wave counts; with fewer waves there is only more room)
+    const bool k4_fits = e->s2.supported && scan4_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, false, &w4[0], &e->scan4_fifo[0]) &&
+                         scan4_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, true, &w4[1], &e->scan4_fifo[1]);
+    e->scan4_density = 0.06;
+    e->s5_short_groups = false;
+    const bool k5_fits = (f == Forced::none || f == Forced::scan5) && plan_scan5(e);
+    const uint32_t bloom_lds_bytes = e->s3.supported && e->s3.bloom_lg <= kScan3BloomLdsLg ? 4u << e->s3.bloom_lg : 0u;
+    const bool k3_fits = e->s3.supported && scan3_plan((uint32_t)e->s3.filter.size(), (uint32_t)e->s3.short3.size(), (uint32_t)e->s3.srec.size(),
+                                                        bloom_lds_bytes, lds, &w3, &e->scan3_cand_cap);
+    // (scan5 asked for but not applicable: as by default)
+    auto chosen = [e](ScanKernel k, uint32_t waves) { e->kernel = k; e->scan_waves = waves; return GFT_OK; };
+    if (k3_fits && f != Forced::dfa && f != Forced::scan2 && f != Forced::scan4 && (f == Forced::scan3 || !(k5_fits || k2_fits)))
+        return chosen(ScanKernel::scan3, w3);
+    if (f == Forced::scan4 && k2_fits && k4_fits) return chosen(ScanKernel::scan4, std::min(w4[0], w4[1]));
+    if (k5_fits) return chosen(ScanKernel::scan5, kScan5Waves);
+    if (k2_fits && f != Forced::dfa) return chosen(ScanKernel::scan2, w2);
+    return chosen(ScanKernel::dfa, 0);
+}
+
+// scan3's short-term tables, which scan5 reads too over an alphabet too large for scan2's
+static int upload_scan3_short_tables(gft_engine* e) {
+    std::vector<uint8_t> s3v = e->s3.short3, g1(e->s3.cls, e->s3.cls + 256), g2(e->s3.cls_fold, e->s3.cls_fold + 256);
+    if (s3v.empty()) s3v.assign(16, 0);
+    SyncOnExit drained(e);                              // (the uploads read from these locals)
+    int rc;
+    if ((rc = upload(e, e->d_s3_short3, s3v, "table upload"))) return rc;
+    if ((rc = upload(e, e->d_s3_srec, e->s3.srec, "table upload"))) return rc;
+    if (!e->s3.short3_big.empty() && (rc = upload(e, e->d_s3_short3_big, e->s3.short3_big, "table upload"))) return rc;
+    if ((rc = upload(e, e->d_s3_srec_big, e->s3.srec_big, "table upload"))) return rc;
+    if ((rc = upload(e, e->d_s3_cls, g1, "table upload"))) return rc;
+    if ((rc = upload(e, e->d_s3_cls_fold, g2, "table upload"))) return rc;
+    return GFT_OK;
+}
+
+// e->tab / e->s2 / e->s3 hold compiled tables (from gft_build or gft_import_tables): check them against the device, choose
+// the scan kernel, upload what it reads
 static int install_tables(gft_engine* e, uint32_t flags) {
     if (e->tab.max_term_len + 1024 > kTextBuf)
         return fail(e, GFT_E_UNSUPPORTED, "keyword longer than " + std::to_string(kTextBuf - 1024) + " bytes");
@@ -1460,7 +1548,7 @@ static int install_tables(gft_engine* e, uint32_t flags) {
     size_t rows = (e->lds_max - fixed) / ((size_t)e->tab.n_classes * 4);
     e->n_lds_states = (uint32_t)std::min<size_t>(rows, e->tab.n_states);
 
-    std::vector<uint8_t> bc(e->tab.byte_class, e->tab.byte_class + 256), c1, c2, g1, g2, s3v, s5g, s5gf;
+    std::vector<uint8_t> bc(e->tab.byte_class, e->tab.byte_class + 256), c1, c2, s5g, s5gf;
     SyncOnExit drained(e);                              // (declared behind the temporaries the uploads read from: it goes first)
     int rc;
     if ((rc = upload(e, e->d_byte_class, bc, "table upload"))) return rc;
@@ -1468,142 +1556,34 @@ static int install_tables(gft_engine* e, uint32_t flags) {
     if ((rc = upload(e, e->d_out_term, e->tab.out_term, "table upload"))) return rc;
     if ((rc = upload(e, e->d_out_link, e->tab.out_link, "table upload"))) return rc;
     if ((rc = upload(e, e->d_term_len, e->tab.term_len, "table upload"))) return rc;
-    // GFT_SCAN_KERNEL=dfa forces the general two-tier DFA kernel
-    const char* force = getenv("GFT_SCAN_KERNEL");
-    if (!kExtraKernels && force && (std::string(force) == "scan2" || std::string(force) == "scan4"))
-        return fail(e, GFT_E_UNSUPPORTED, std::string("GFT_SCAN_KERNEL=") + force + ": this library was built without the cross-check kernels (GFT_EXTRA_KERNELS=1 python -m gofindthem_amd.build --force)");
-    const bool k2_fits = e->s2.supported && scan2_plan((uint32_t)e->s2.filter.size(), (uint32_t)e->s2.short3.size(),
-                                                        (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3),
-                                                        e->s2.fpt_lg ? 0u : kScan2FptSize, e->lds_max - 512,
-                                                        &e->scan2_k2_waves, &e->scan2_cand_cap);
-    e->use_scan2 = k2_fits && !(force && std::string(force) == "dfa");
-    {
-        uint32_t w0 = 0, w1 = 0;
-        const bool k4_fits = e->s2.supported &&
-                             scan4_plan((uint32_t)e->s2.filter.size(), (uint32_t)e->s2.short3.size(), (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3),
-                                        e->s2.fpt_lg ? 0u : kScan2FptSize, e->lds_max - 512, false, &w0, &e->scan4_fifo[0]) &&
-                             scan4_plan((uint32_t)e->s2.filter.size(), (uint32_t)e->s2.short3.size(), (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3),
-                                        e->s2.fpt_lg ? 0u : kScan2FptSize, e->lds_max - 512, true, &w1, &e->scan4_fifo[1]);
-        e->scan4_waves = std::min(w0, w1);
-        // (the fifo capacities belong to the smaller of the two wave counts; with fewer waves there is only more room)
-        e->use_scan4 = e->use_scan2 && k4_fits && force && std::string(force) == "scan4";
-        e->scan4_density = 0.06;
-    }
-    // The suffix-window kernel with one filter probe per two bytes: the default for every dictionary whose long-term tables
-    // exist (GFT_SCAN_KERNEL=scan2: the one-probe-per-byte kernel, scan3: the stride-2 kernel).  It runs on scan2's tables; a
-    // fifo entry of 32 bits holds term id and relative position.  With more than 32 byte classes there is no
-    // direct short-term table (Scan2Tables::short_direct): the group-indexed one of the stride-2 kernel's tables serves then
-    // (GFT_SCAN5_LARGE=0 leaves such dictionaries to the stride-2 kernel).
-    e->use_scan5 = false;
-    e->s5_short_groups = false;
-    const bool want5 = !force || std::string(force) == "scan5" || std::string(force) == "auto" || !*force;
-    const bool large5 = e->s2.long_ok && !e->s2.short_direct && e->s3.supported && e->opt_scan5_large;
-    // (the tables that kernel needs: the direct short-term table of small alphabets, or the group-indexed one)
-    const bool direct5 = e->s2.supported && !(force && std::string(force) == "dfa");
-    if ((direct5 || large5) && e->s2.long_ok && want5) {
-        uint32_t tb = 1;
-        while ((1ull << tb) < e->tab.terms.size()) tb++;
-        e->s5_term_bits = tb;
-        e->s5_pos_bias = e->tab.max_term_len + kScan2MaxOff;
-        const bool packs = (uint64_t)kScan2UnitMax + e->s5_pos_bias + 8 < (1ull << (32 - tb));
-        const uint32_t short_bytes = large5 ? (uint32_t)e->s3.short3.size() : (uint32_t)e->s2.short3.size();
-        const uint32_t rec_words = large5 ? (uint32_t)e->s3.srec.size() : (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
-        // a fingerprint table too large for LDS (fpt_lg != 0) gets a Bloom level there instead: 2^lg bits, as large as
-        // GFT_SCAN5_BLOOM_KB allows but not more than eight bits per item would take
-        e->s5_bloom_lg = 0;
-        e->s5_bloom.clear();
-        if (e->s2.fpt_lg && e->opt_scan5_bloom_kb) {
-            uint32_t lg = 13;
-            while ((2u << lg) / 8 <= e->opt_scan5_bloom_kb * 1024u && (1ull << lg) < 8 * e->s2.n_keys) lg++;
-            e->s5_bloom_lg = lg;
-        }
-        bool fits5 = false;
-        for (int attempt = 0; attempt < 2 && packs && !fits5; attempt++) {
-            const uint32_t in_lds = e->s2.fpt_lg ? (e->s5_bloom_lg ? (1u << e->s5_bloom_lg) / 8 : 0u) : kScan2FptSize;
-            fits5 = scan5_plan(e->s2.kp, short_bytes, rec_words, in_lds, e->lds_max - 512, e->opt_scan5_fifo ? e->opt_scan5_fifo : kScan2FifoCap, &e->s5plan);
-            if (!fits5) e->s5_bloom_lg = 0;                      // (no room: without the Bloom level)
-        }
-        if (fits5) {
-            if (e->opt_scan5_groups && e->opt_scan5_groups < e->s5plan.G) {      // (tests: more merging than LDS asks for)
-                e->s5plan.G = std::max<uint32_t>(e->opt_scan5_groups, 2);
-                e->s5plan.dual_entries = e->s5plan.G * e->s5plan.G * e->s5plan.G;
-            }
-            build_scan5_tables(e->tab, e->s2, e->s5plan.G, e->s5);
-            if (e->s5_bloom_lg) {
-                // one bit per owner of a fingerprint cell, read off the bucket table: (window key, byte in front of the
-                // window with its case bit cleared), or the window key alone where the window is the term's first four bytes
-                e->s5_bloom.assign((size_t)1 << (e->s5_bloom_lg - 5), 0u);
-                auto set = [&](uint32_t h) { e->s5_bloom[h >> 5] |= 1u << (h & 31); };
-                auto add = [&](const Scan2Slot& t) {
-                    if ((t.len & kScan2LenMask) == 4) set(scan5_bloom_x(t.key, e->s5_bloom_lg));
-                    else set(scan5_bloom_g(t.key, (t.front[0] >> 24) & 0xDFu, e->s5_bloom_lg));
-                };
-                for (const Scan2Slot& sl : e->s2.slots) {
-                    if (sl.key == kScan2EmptyKey) continue;
-                    if (!(sl.info & kScan2Multi)) { add(sl); continue; }
-                    for (uint32_t j = 0; j < sl.len; j++) add(e->s2.more[(sl.info & ~kScan2Multi) + j]);
-                }
-            }
-            e->use_scan5 = true;
-            e->s5_short_groups = large5;
-            e->use_scan2 = true;           // (the scan2 family's path through scan_pipeline; gft_scan2.hip itself runs only when s2.supported)
-            if (!k2_fits) { e->scan2_k2_waves = kScan5Waves; e->scan2_cand_cap = e->s5plan.cand_cap; }   // (what that path sizes slabs by)
-        }
-    }
-    // Kernel choice: the suffix-window kernel (scan2) where its direct tables apply -- small alphabets, the benchmark's
-    // shape --, the stride-2 kernel (scan3: any alphabet, merged filter groups) everywhere else; the DFA kernel only as
-    // a cross-check.  GFT_SCAN_KERNEL=scan2 / scan3 / dfa forces one (read here, i.e. by gft_build / gft_import_tables)
-    const uint32_t bloom_lds_bytes = e->s3.supported && e->s3.bloom_lg <= kScan3BloomLdsLg ? 4u << e->s3.bloom_lg : 0u;
-    const bool k3_fits = e->s3.supported && scan3_plan((uint32_t)e->s3.filter.size(), (uint32_t)e->s3.short3.size(), (uint32_t)e->s3.srec.size(),
-                                                        bloom_lds_bytes, e->lds_max - 512, &e->scan3_waves, &e->scan3_cand_cap);
-    const std::string forced = force ? force : "";
-    e->use_scan3 = k3_fits && forced != "dfa" && forced != "scan2" && forced != "scan4" && (forced == "scan3" || !e->use_scan2);   // (scan5 asked for but not applicable: the stride-2 kernel, as by default)
-    if (e->use_scan3) {
+    if ((rc = choose_scan_kernel(e))) return rc;
+    const ScanKernel k = e->kernel;
+    const bool build_dbg = getenv("GFT_SCAN_DEBUG") != nullptr;
+    if (k == ScanKernel::scan3) {
+        if ((rc = upload_scan3_short_tables(e))) return rc;
         if ((rc = upload(e, e->d_s3_filter, e->s3.filter, "table upload"))) return rc;
-        s3v = e->s3.short3;
-        if (s3v.empty()) s3v.assign(16, 0);
-        if ((rc = upload(e, e->d_s3_short3, s3v, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_srec, e->s3.srec, "table upload"))) return rc;
-        if (!e->s3.short3_big.empty() && (rc = upload(e, e->d_s3_short3_big, e->s3.short3_big, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_srec_big, e->s3.srec_big, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s3_bloom, e->s3.bloom, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s3_slots, e->s3.slots, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s3_more, e->s3.more, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s3_term_blob, e->s3.term_blob, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s3_term_off, e->s3.term_off, "table upload"))) return rc;
-        g1.assign(e->s3.cls, e->s3.cls + 256); g2.assign(e->s3.cls_fold, e->s3.cls_fold + 256);
-        if ((rc = upload(e, e->d_s3_cls, g1, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_cls_fold, g2, "table upload"))) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream), "table upload");      // g1 / g2 / s3v are locals
-        if (e->opt_scan_dbg || getenv("GFT_SCAN_DEBUG"))
+        if (build_dbg)
             fprintf(stderr, "[gft build debug] scan3: G=%u%s keys=%llu anchors=%llu slots=%zu more=%zu bloom 2^%u (%s) short cells: lds records %zu, big words %zu; waves=%u cand_cap=%u\n",
                     e->s3.G, e->s3.grouped ? " (merged classes)" : "", (unsigned long long)e->s3.n_keys, (unsigned long long)e->s3.n_anchors,
-                    e->s3.slots.size(), e->s3.more.size(), e->s3.bloom_lg, bloom_lds_bytes ? "LDS" : "global", e->s3.srec.size() / kScan3RecWords - 1,
-                    e->s3.srec_big.size(), e->scan3_waves, e->scan3_cand_cap);
+                    e->s3.slots.size(), e->s3.more.size(), e->s3.bloom_lg, e->s3.bloom_lg <= kScan3BloomLdsLg ? "LDS" : "global", e->s3.srec.size() / kScan3RecWords - 1,
+                    e->s3.srec_big.size(), e->scan_waves, e->scan3_cand_cap);
     }
-    if (e->use_scan2 && getenv("GFT_SCAN_DEBUG")) {
-        size_t n_ff = 0, n_used = 0, n_simple = 0, n_slots = 0;
-        for (uint8_t b : e->s2.fpt) { n_ff += b == 0xFF; n_used += b != 0; }
-        for (const auto& s : e->s2.slots) { n_slots += s.key != kScan2EmptyKey; n_simple += s.key != kScan2EmptyKey && !(s.info & kScan2Multi); }
-        fprintf(stderr, "[gft build debug] kp=%u keys=%zu (simple %zu) slots=%zu fpt: used=%zu always-pass=%zu of %u; shorts=%zu filter=%s %u bits waves=%u\n",
-                e->s2.kp, n_slots, n_simple, e->s2.slots.size(), n_used, n_ff, (unsigned)e->s2.fpt.size(), e->s2.shorts.size() - 1,
-                e->s2.hashed ? "hashed" : "direct", e->s2.filter_bits, e->scan2_k2_waves);
-        fprintf(stderr, "[gft build debug] candidate list capacity %u per wave\n", e->scan2_cand_cap);
-    }
-    if (e->use_scan5 && e->s5_short_groups && !e->use_scan3) {
-        // the short-term tables of the stride-2 kernel's set, which is not uploaded as a whole then
-        s3v = e->s3.short3;
-        if (s3v.empty()) s3v.assign(16, 0);
-        if ((rc = upload(e, e->d_s3_short3, s3v, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_srec, e->s3.srec, "table upload"))) return rc;
-        if (!e->s3.short3_big.empty() && (rc = upload(e, e->d_s3_short3_big, e->s3.short3_big, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_srec_big, e->s3.srec_big, "table upload"))) return rc;
-        g1.assign(e->s3.cls, e->s3.cls + 256); g2.assign(e->s3.cls_fold, e->s3.cls_fold + 256);
-        if ((rc = upload(e, e->d_s3_cls, g1, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_cls_fold, g2, "table upload"))) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream), "table upload");      // g1 / g2 / s3v are locals
-    }
-    if (e->use_scan2) {
+    if (on_scan2_tables(k)) {
+        if (build_dbg) {
+            size_t n_ff = 0, n_used = 0, n_simple = 0, n_slots = 0;
+            for (uint8_t b : e->s2.fpt) { n_ff += b == 0xFF; n_used += b != 0; }
+            for (const auto& s : e->s2.slots) { n_slots += s.key != kScan2EmptyKey; n_simple += s.key != kScan2EmptyKey && !(s.info & kScan2Multi); }
+            fprintf(stderr, "[gft build debug] kp=%u keys=%zu (simple %zu) slots=%zu fpt: used=%zu always-pass=%zu of %u; shorts=%zu filter=%s %u bits waves=%u\n",
+                    e->s2.kp, n_slots, n_simple, e->s2.slots.size(), n_used, n_ff, (unsigned)e->s2.fpt.size(), e->s2.shorts.size() - 1,
+                    e->s2.hashed ? "hashed" : "direct", e->s2.filter_bits, e->scan_waves);
+            fprintf(stderr, "[gft build debug] candidate list capacity %u per wave\n", k == ScanKernel::scan5 ? e->s5plan.cand_cap : e->scan2_cand_cap);
+        }
+        if (k == ScanKernel::scan5 && e->s5_short_groups && (rc = upload_scan3_short_tables(e))) return rc;
         e->scan2_short3_bytes = (uint32_t)e->s2.short3.size();
         if (e->s2.short3.empty()) e->s2.short3.assign(16, 0);   // placeholder upload; short3_bytes stays 0
         if ((rc = upload(e, e->d_s2_short3, e->s2.short3, "table upload"))) return rc;
@@ -1619,13 +1599,30 @@ static int install_tables(gft_engine* e, uint32_t flags) {
         if ((rc = upload(e, e->d_s2_term_blob, e->s2.term_blob, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s2_term_off, e->s2.term_off, "table upload"))) return rc;
     }
-    if (e->use_scan5) {
+    if (k == ScanKernel::scan5) {
+        build_scan5_tables(e->tab, e->s2, e->s5plan.G, e->s5);
+        e->s5_bloom.clear();
+        if (e->s5_bloom_lg) {
+            // one bit per owner of a fingerprint cell, read off the bucket table: (window key, byte in front of the
+            // window with its case bit cleared), or the window key alone where the window is the term's first four bytes
+            e->s5_bloom.assign((size_t)1 << (e->s5_bloom_lg - 5), 0u);
+            auto set = [&](uint32_t h) { e->s5_bloom[h >> 5] |= 1u << (h & 31); };
+            auto add = [&](const Scan2Slot& t) {
+                if ((t.len & kScan2LenMask) == 4) set(scan5_bloom_x(t.key, e->s5_bloom_lg));
+                else set(scan5_bloom_g(t.key, (t.front[0] >> 24) & 0xDFu, e->s5_bloom_lg));
+            };
+            for (const Scan2Slot& sl : e->s2.slots) {
+                if (sl.key == kScan2EmptyKey) continue;
+                if (!(sl.info & kScan2Multi)) { add(sl); continue; }
+                for (uint32_t j = 0; j < sl.len; j++) add(e->s2.more[(sl.info & ~kScan2Multi) + j]);
+            }
+        }
         s5g.assign(e->s5.grp, e->s5.grp + 256); s5gf.assign(e->s5.grp_fold, e->s5.grp_fold + 256);
         if ((rc = upload(e, e->d_s5_grp, s5g, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s5_grp_fold, s5gf, "table upload"))) return rc;
         if ((rc = upload(e, e->d_s5_filter, e->s5.filter, "table upload"))) return rc;
         if (e->s5_bloom_lg && (rc = upload(e, e->d_s5_bloom, e->s5_bloom, "table upload"))) return rc;
-        if (getenv("GFT_SCAN_DEBUG")) {
+        if (build_dbg) {
             size_t set_bits = 0;
             for (uint32_t w : e->s5_bloom) set_bits += (size_t)__builtin_popcount(w);
             fprintf(stderr, "[gft build debug] scan5: G=%u of %u classes, filter %zu entries, list %u, term bits %u; Bloom level 2^%u bits, %.1f %% set\n",
@@ -1669,7 +1666,7 @@ int gft_last_nonascii(const gft_engine* e) { return e && e->last_nonascii ? 1 : 
 const char* gft_build_info(void) { return kExtraKernels ? "gfx950 extra_kernels=1" : "gfx950 extra_kernels=0"; }
 const char* gft_scan_kernel(const gft_engine* e) {
     if (!e || !e->built) return "";
-    return e->use_scan3 ? "scan3" : e->use_scan4 ? "scan4" : e->use_scan5 ? "scan5" : e->use_scan2 ? "scan2" : "dfa";
+    return kScanKernelName[(int)e->kernel];
 }
 
 int gft_term(const gft_engine* e, uint32_t term_id, const uint8_t** ptr, uint32_t* len) try {
@@ -2157,14 +2154,18 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
     // this batch outgrew the unit table or the match pool the previous ones left behind
     for (int pass = 0; pass < 2; pass++) {
         uint64_t nm = 0;
-        int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, plan.all_docs, &nm, nullptr, pass == 0);
+        ScanLaunch launch;
+        int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, plan.all_docs, &nm, nullptr, pass == 0 ? &launch : nullptr);
         if (rc) return rc;
-        const bool was_deferred = e->deferred;
         rc = solve_pipeline(e, n_docs, d_extra, d_hit_bitmap);
         if (rc) return rc;
-        if (!was_deferred) break;
+        if (!launch.deferred) break;
+        // (into pinned memory: a copy to pageable memory is staged by the runtime, ten microseconds on every batch)
+        if (!e->pin_rb) HIP_TRY(hipHostMalloc((void**)&e->pin_rb, 64, hipHostMallocDefault), "pinned alloc");
+        HIP_TRY(hipMemcpyAsync(e->pin_rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
+        HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
         bool again = false;
-        rc = deferred_check(e, &again);
+        rc = deferred_interpret(e, e->pin_rb, launch, &again);
         if (rc) return rc;
         if (!again) break;
     }
@@ -2192,7 +2193,7 @@ void complete_pending(gft_engine* e, gft_engine::Pending& p, gft_engine::Pending
     if (p.done) return;
     if (hipEventSynchronize(p.ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
     bool again = false;
-    int rc = deferred_interpret(e, p.rb, DeferredLaunch{p.single, p.n_docs_cap, p.unit_cap, p.pool_cap, p.static_slabs, p.single ? p.epoch : 0u}, &again);
+    int rc = deferred_interpret(e, p.rb, p.launch, &again);
     if (!rc && again) {
         if (young && !young->done && hipEventSynchronize(young->ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
         const unsigned keep_count = e->pend_count;
@@ -2230,11 +2231,10 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
     }
     DeviceGuard g(e->device);
     uint64_t nm = 0;
-    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, false, &nm, nullptr, true);
+    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, false, &nm, nullptr, &pb.launch);
     if (rc) { keep_verdict(e, pb, rc); e->pend_count++; return GFT_OK; }
-    const bool was_deferred = e->deferred;
     rc = solve_pipeline(e, n_docs, nullptr, d_hit_bitmap);
-    if (rc || !was_deferred) {
+    if (rc || !pb.launch.deferred) {
         // (sizes were not known yet: this batch ran with its own synchronisations, like gft_process_device's first pass)
         if (!rc) { rc = hipStreamSynchronize(e->stream) == hipSuccess ? GFT_OK : fail(e, GFT_E_HIP, "process pipeline"); }
         if (!rc) rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags);
@@ -2242,11 +2242,8 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
         e->pend_count++;
         return GFT_OK;
     }
-    e->deferred = false;
     if (!pb.rb) HIP_TRY(hipHostMalloc((void**)&pb.rb, 64, hipHostMallocDefault), "pinned alloc");
     if (!pb.ev) HIP_TRY(hipEventCreateWithFlags(&pb.ev, hipEventDisableTiming), "event");
-    pb.single = e->deferred_single; pb.epoch = e->deferred_epoch; pb.n_docs_cap = e->deferred_n_docs; pb.unit_cap = e->deferred_unit_cap;
-    pb.pool_cap = e->deferred_pool_cap; pb.static_slabs = e->last_static_slabs;
     HIP_TRY(hipMemcpyAsync(pb.rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
     HIP_TRY(hipEventRecord(pb.ev, e->stream), "event");
     e->pend_count++;
