@@ -25,6 +25,7 @@
 #include "gft_guard.hpp"
 #include "gft_kernels.hpp"
 #include "host_solve.hpp"
+#include "program_set.hpp"
 #include "scan2_tables.hpp"
 #include "scan3_tables.hpp"
 
@@ -173,20 +174,17 @@ struct gft_engine {
     // programs
     bool have_programs = false;
     uint32_t n_exprs = 0, n_extra = 0;
-    // what the HOST solves (host_solve.hpp): expressions beyond the device solver's limits, and INORD expressions in the
-    // documents where one of their slots has a position list that is not ascending (a keyword and a regex with the same
-    // literal: finder/finder.go:181-196).  Host copy of the public programs + what gft_set_programs learnt about them.
-    std::vector<uint32_t> h_prog;
-    std::vector<uint64_t> h_prog_off;
-    std::vector<ProgramTraits> traits;
-    std::vector<uint32_t> host_only;       // expressions that are always solved on the host (over a device limit)
-    std::vector<uint32_t> inord_exprs;     // expressions with a multi-leaf INORD group (candidates for irregular documents)
-    std::vector<uint8_t> inord_slot;       // [n_slots]: 1 = the slot is read inside such a group
+    gft::ProgramSet progs;                 // the installed set (program_set.hpp) ...
+    struct ProgramBufs {                   // ... and the copies of its arrays that the solver kernel reads
+        DevBuf prog, prog_off;             // public postfix words (INORD group subtrees are read from these)
+        DevBuf fprog, fprog_off, groups;   // fused internal form + INORD group table
+        DevBuf order, blk_class, wave_blk; // evaluation order of the programs
+        DevBuf fprog_t, fblk_off;          // fused programs per sorted block of 64, transposed (read when they do not fit LDS)
+        DevBuf wide_list;
+    } d_progs;
     uint64_t last_n_units = 0, last_total = 0;   // of the last completed scan (csr_from_pool)
     bool csr_valid = false;                // d_match_off / d_term / d_pos hold the last scan's canonical CSR
     DevBuf d_patch;                        // bit patches of host-solved results for a device-resident bitmap
-    DevBuf d_prog, d_prog_off;            // public postfix words (INORD group subtrees are read from these)
-    DevBuf d_fprog, d_fprog_off, d_groups; // fused internal form + INORD group table
     DevBuf d_wide_slot, d_wide_theta;      // pairs of wide INORD groups, a region per wave of the solver's grid
     DevBuf d_solve_dbg;                    // GFT_SOLVE_DEBUG & 8: phase clocks
     // batches in a row that were one unit per document (k_units_single serves the next one from 2 on; a batch that took
@@ -207,15 +205,7 @@ struct gft_engine {
     };
     Pending pend[2];
     unsigned pend_head = 0, pend_count = 0;
-    DevBuf d_order, d_blk_class, d_wave_blk;            // evaluation order of the programs (gft_set_programs)
     uint32_t last_solve_group_docs = 64;   // documents per solver group of the last launch (0 = presence matrix in HBM)
-    DevBuf d_fprog_t, d_fblk_off;          // fused programs per sorted block of 64, transposed (read when they do not fit LDS)
-    uint32_t fprog_words = 0;
-    uint32_t n_inord_groups = 0;           // fused INORD ops: 0 = the solver never reads positions
-    uint32_t wide_pairs = 0;               // the widest INORD group the device solves through its scratch path (0: none); d_wide_*
-    uint32_t n_wide = 0;                   // expressions with such a group: answered by the solver's second phase (d_wide_list)
-    DevBuf d_wide_list;
-    uint32_t n_rare_words = 0;             // fused NOT + INORD ops: 0 = the solver variant without their slow path
     DevBuf d_pscratch;                    // HBM presence matrices when n_slots * 8 B does not fit LDS
 
     // workspace
@@ -316,208 +306,6 @@ int upload(gft_engine* e, DevBuf& buf, const std::vector<T>& v, const char* what
     return GFT_OK;
 }
 
-// validates one postfix program and measures its stack needs
-// traits != nullptr: a program beyond the device solver's limits is not refused but marked (it is solved on the host),
-// and the slots of its multi-leaf INORD groups are listed
-int check_program(const gft_engine* e, const uint32_t* w, uint64_t len, uint32_t n_slots, uint32_t idx, ProgramTraits* traits = nullptr) {
-    uint32_t sp = 0, psp = 0, g_tot = 0, g_psp = 0, max_sp = 0;   // g_*: the most pairs / the deepest pair stack of the group being read
-    std::vector<uint32_t> group_slots;
-    std::vector<uint32_t> pcnt;   // pair counts of the INORD operand stack
-    bool in_group = false;
-    auto bad = [&](const char* m) {
-        return fail(e, GFT_E_INVALID, "program " + std::to_string(idx) + ": " + m);
-    };
-    for (uint64_t pc = 0; pc < len; pc++) {
-        const uint32_t op = w[pc] >> 28;
-        const bool fl = (w[pc] & GFT_INORD_FLAG) != 0;
-        switch (op) {
-        case GFT_OP_UNIT:
-            if ((w[pc] & GFT_SLOT_MASK) >= n_slots) return bad("slot out of range");
-            sp++;
-            if (fl) { pcnt.push_back(1); in_group = true; group_slots.push_back(w[pc] & GFT_SLOT_MASK); }
-            break;
-        case GFT_OP_AND:
-        case GFT_OP_OR:
-            if (sp < 2) return bad("operand stack underflow");
-            sp--;
-            if (fl) {
-                if (pcnt.size() < 2) return bad("INORD operand stack underflow");
-                uint32_t r = pcnt.back(); pcnt.pop_back();
-                if (op == GFT_OP_AND) pcnt.back() = r; else pcnt.back() += r;
-            }
-            break;
-        case GFT_OP_NOT:
-            if (sp < 1) return bad("operand stack underflow");
-            if (in_group) return bad("NOT inside INORD");
-            break;
-        case GFT_OP_INORD:
-            if (sp < 1 || pcnt.size() != 1) return bad("malformed INORD group");
-            pcnt.clear(); in_group = false;
-            if (traits && (g_tot > kMaxPairs || g_psp > kMaxPairDepth) && g_tot <= kMaxPairsWide && g_psp <= kMaxPairDepthWide) {
-                traits->wide_pairs = std::max(traits->wide_pairs, g_tot);
-                traits->wide_groups.push_back(pc);
-            }
-            g_tot = g_psp = 0;
-            // (a group of ONE leaf is true exactly when the leaf is present: no position is ever compared)
-            if (traits && group_slots.size() > 1) traits->inord_slots.insert(traits->inord_slots.end(), group_slots.begin(), group_slots.end());
-            group_slots.clear();
-            break;
-        default:
-            return bad("unknown opcode");
-        }
-        // (the depth of the PUBLIC postfix form binds only a caller without traits; gft_set_programs judges the depth of the
-        // fused form, which is what the device interprets: operands are reordered there, a chain nested to one side is flat)
-        max_sp = std::max(max_sp, sp);
-        if (sp > kMaxBoolDepth && !traits)
-            return fail(e, GFT_E_UNSUPPORTED, "program " + std::to_string(idx) + ": operand stack deeper than " +
-                                                   std::to_string(kMaxBoolDepth));
-        uint32_t tot = 0;
-        for (uint32_t c : pcnt) tot += c;
-        psp = (uint32_t)pcnt.size();
-        g_tot = std::max(g_tot, tot); g_psp = std::max(g_psp, psp);
-        if (tot > kMaxPairs || psp > kMaxPairDepth) {
-            if (!traits) return fail(e, GFT_E_UNSUPPORTED, "program " + std::to_string(idx) + ": INORD group too wide for the device solver");
-            // (more than a pair per lane: the device's scratch path up to kMaxPairsWide, the host beyond)
-            if (tot > kMaxPairsWide || psp > kMaxPairDepthWide) traits->over_limit = true;
-        }
-    }
-    if (sp != 1 || !pcnt.empty()) return bad("program does not reduce to one value");
-    if (traits && traits->wide_pairs && max_sp > kMaxPairDepthWide) traits->over_limit = true;   // (the wide evaluator's boolean stack: a bit per entry)
-    if (traits) {
-        std::sort(traits->inord_slots.begin(), traits->inord_slots.end());
-        traits->inord_slots.erase(std::unique(traits->inord_slots.begin(), traits->inord_slots.end()), traits->inord_slots.end());
-    }
-    return GFT_OK;
-}
-
-// public postfix words -> fused internal form (gft_kernels.hpp FusedOp) + INORD group table.
-// `gbase` = offset of this program inside the uploaded public word array.
-// public postfix words -> fused words (gft_kernels.hpp FusedOp); returns the deepest the accumulator stack gets
-uint32_t fuse_program(const uint32_t* w, uint64_t len, uint64_t gbase, std::vector<uint32_t>& out,
-                      std::vector<uint32_t>& groups) {
-    // postfix -> tree (node = operator or leaf, with the range of public words it covers)
-    struct Node { uint32_t op, slot; int64_t l, r; uint64_t s, e; };
-    std::vector<Node> nodes;
-    std::vector<int64_t> st;
-    for (uint64_t i = 0; i < len; i++) {
-        const uint32_t op = w[i] >> 28;
-        switch (op) {
-        case GFT_OP_UNIT:
-            nodes.push_back(Node{op, w[i] & GFT_SLOT_MASK, -1, -1, i, i});
-            st.push_back((int64_t)nodes.size() - 1);
-            break;
-        case GFT_OP_AND:
-        case GFT_OP_OR: {
-            const int64_t r = st.back(); st.pop_back();
-            const int64_t l = st.back(); st.pop_back();
-            nodes.push_back(Node{op, 0, l, r, nodes[l].s, i});
-            st.push_back((int64_t)nodes.size() - 1);
-            break;
-        }
-        case GFT_OP_NOT:
-        case GFT_OP_INORD: {
-            const int64_t c = st.back(); st.pop_back();
-            nodes.push_back(Node{op, 0, c, -1, nodes[c].s, i});
-            st.push_back((int64_t)nodes.size() - 1);
-            break;
-        }
-        default:
-            break;
-        }
-    }
-    if (st.empty()) return 0;
-    const size_t out0 = out.size();
-    // Code generation with an explicit job stack (left-deep chains of 10 000 leaves must not recurse).
-    //  * NOT is pushed down to the leaves (De Morgan; every node is evaluated anyway, the reference does not
-    //    short-circuit), so it only survives on top of an INORD group;
-    //  * AND / OR commute: the operand that is a leaf goes second and folds into the operator word;
-    //  * the accumulator is pushed only between two operands that are both subtrees -- and of those the one that needs
-    //    the deeper stack goes FIRST (Sethi-Ullman), so a chain of parentheses nested to the right stays one entry deep
-    //    and only a balanced tree of 2^k subtrees gets k deep: real rule sets fit the interpreter's register stack.
-    auto strip = [&](int64_t n, bool& neg) {        // skip NOT chains
-        while (nodes[n].op == GFT_OP_NOT) { neg = !neg; n = nodes[n].l; }
-        return n;
-    };
-    std::vector<uint32_t> need(nodes.size(), 0);    // stack entries the subtree's code needs (children come before parents)
-    for (size_t n = 0; n < nodes.size(); n++) {
-        const Node& nd = nodes[n];
-        bool dummy = false;
-        if (nd.op == GFT_OP_NOT || nd.op == GFT_OP_INORD) need[n] = need[nd.l];
-        else if (nd.op == GFT_OP_AND || nd.op == GFT_OP_OR) {
-            const int64_t l = strip(nd.l, dummy), r = strip(nd.r, dummy);
-            if (nodes[r].op == GFT_OP_UNIT) need[n] = need[nd.l];
-            else if (nodes[l].op == GFT_OP_UNIT) need[n] = need[nd.r];
-            else need[n] = need[nd.l] == need[nd.r] ? need[nd.l] + 1 : std::max(need[nd.l], need[nd.r]);
-        }
-    }
-    struct Job { int64_t n; int phase; bool neg; };
-    std::vector<Job> jobs{{st.back(), 0, false}};
-    uint32_t depth = 0, max_depth = 0;
-    while (!jobs.empty()) {
-        Job j = jobs.back(); jobs.pop_back();
-        bool neg = j.neg;
-        const int64_t n = j.phase == 0 ? strip(j.n, neg) : j.n;
-        const Node& nd = nodes[n];
-        switch (nd.op) {
-        case GFT_OP_UNIT:
-            out.push_back((neg ? kFopSetN : kFopSet) << 28 | nd.slot);
-            break;
-        case GFT_OP_INORD:
-            if (j.phase == 0) { jobs.push_back({n, 1, neg}); jobs.push_back({nd.l, 0, false}); }
-            else {
-                // (a group with a single leaf has a non-empty position list exactly when the leaf is present: every
-                // reported key carries >= 1 position, so no position check is needed)
-                if (nodes[nd.l].op != GFT_OP_UNIT) {
-                    out.push_back(kFopInord << 28 | (uint32_t)(groups.size() / 2));
-                    groups.push_back((uint32_t)(gbase + nodes[nd.l].s));
-                    groups.push_back((uint32_t)(nodes[nd.l].e - nodes[nd.l].s + 1));
-                }
-                if (neg) out.push_back(kFopNot << 28);
-            }
-            break;
-        case GFT_OP_AND:
-        case GFT_OP_OR: {
-            const bool is_and = (nd.op == GFT_OP_AND) != neg;        // not (a and b) == not a or not b
-            if (j.phase == 0) {
-                bool ln = neg, rn = neg;
-                const int64_t l = strip(nd.l, ln), r = strip(nd.r, rn);
-                if (nodes[r].op == GFT_OP_UNIT) { jobs.push_back({n, 1, neg}); jobs.push_back({nd.l, 0, neg}); }
-                else if (nodes[l].op == GFT_OP_UNIT) { jobs.push_back({n, 2, neg}); jobs.push_back({nd.r, 0, neg}); }
-                else {
-                    const bool left_first = need[nd.l] >= need[nd.r];
-                    jobs.push_back({n, 4, neg}); jobs.push_back({left_first ? nd.r : nd.l, 0, neg});
-                    jobs.push_back({n, 3, neg}); jobs.push_back({left_first ? nd.l : nd.r, 0, neg});
-                }
-            } else if (j.phase == 1 || j.phase == 2) {
-                bool ln = neg;
-                const int64_t leaf = strip(j.phase == 1 ? nd.r : nd.l, ln);
-                out.push_back((is_and ? (ln ? kFopAndNS : kFopAndS) : (ln ? kFopOrNS : kFopOrS)) << 28 | nodes[leaf].slot);
-            } else if (j.phase == 3) {
-                out.push_back(kFopPush << 28);
-                max_depth = std::max(max_depth, ++depth);
-            } else {
-                out.push_back((is_and ? kFopAndPop : kFopOrPop) << 28);
-                depth--;
-            }
-            break;
-        }
-        default:
-            break;
-        }
-    }
-    // a push is always followed by the first leaf of the next subtree: one word does both
-    size_t k = out0;
-    for (size_t i = out0; i < out.size(); i++) {
-        const uint32_t op = out[i] >> 28, nx = i + 1 < out.size() ? out[i + 1] >> 28 : 0u;
-        if (op == kFopPush && (nx == kFopSet || nx == kFopSetN)) {
-            out[k++] = (nx == kFopSet ? kFopPushSet : kFopPushSetN) << 28 | (out[i + 1] & 0x0FFFFFFFu);
-            i++;
-        } else out[k++] = out[i];
-    }
-    out.resize(k);
-    return max_depth;
-}
-
 int ensure_pool(gft_engine* e, uint64_t entries) {
     if (entries <= e->pool_cap) return GFT_OK;
     HIP_TRY(e->d_pool_term.ensure(entries * 4), "pool alloc");
@@ -579,7 +367,7 @@ void fill_window(const gft_engine* e, const ScanBatch& b, Params& P) {
     P.text_bytes = b.text_hi;
     P.n_matches = e->d_ctl.as<uint64_t>() + 2;
     // presence-only mode: positions are only read by INORD groups (and by CSR callers)
-    P.want_pos = (b.need_csr || e->n_inord_groups > 0) ? 1 : 0;
+    P.want_pos = (b.need_csr || e->progs.n_inord_groups > 0) ? 1 : 0;
     // wave priorities: the latency-bound verification stages overtake the filter phase of the other waves (5 % on
     // the benchmark; GFT_SCAN_PRIO=0 switches it off)
     P.prio = e->opt_scan_prio;
@@ -1041,17 +829,18 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     S.doc_unit_base = e->d_unit_base.as<uint64_t>();
     S.unit_start = e->d_unit_start.as<uint64_t>(); S.unit_count = e->d_unit_count.as<uint32_t>();
     S.units = e->d_units.as<Unit>();
-    S.has_rare = e->n_rare_words > 0 ? 1u : 0u;
+    S.has_rare = e->progs.n_rare_words > 0 ? 1u : 0u;
     S.pos_back = (e->build_flags & GFT_POS_END) ? 0u : (e->tab.max_term_len ? e->tab.max_term_len - 1 : 0u);
     S.term = e->d_pool_term.as<uint32_t>(); S.pos = e->d_pool_pos.as<uint32_t>();
     S.x_off = d_extra ? d_extra->off : nullptr;
     S.x_slot = d_extra ? d_extra->slot : nullptr;
     S.x_pos = d_extra ? d_extra->pos : nullptr;
     S.n_docs = n_docs;
-    S.fprog = e->d_fprog.as<uint32_t>(); S.fprog_off = e->d_fprog_off.as<uint64_t>();
-    S.gprog = e->d_prog.as<uint32_t>(); S.groups = e->d_groups.as<uint32_t>();
-    S.order = e->d_order.as<uint32_t>(); S.blk_class = e->d_blk_class.as<uint32_t>(); S.wave_blk = e->d_wave_blk.as<uint32_t>();
-    S.fprog_t = e->d_fprog_t.as<uint32_t>(); S.fblk_off = e->d_fblk_off.as<uint32_t>();
+    const gft_engine::ProgramBufs& d = e->d_progs;
+    S.fprog = d.fprog.as<uint32_t>(); S.fprog_off = d.fprog_off.as<uint64_t>();
+    S.gprog = d.prog.as<uint32_t>(); S.groups = d.groups.as<uint32_t>();
+    S.order = d.order.as<uint32_t>(); S.blk_class = d.blk_class.as<uint32_t>(); S.wave_blk = d.wave_blk.as<uint32_t>();
+    S.fprog_t = d.fprog_t.as<uint32_t>(); S.fblk_off = d.fblk_off.as<uint32_t>();
     S.n_exprs = e->n_exprs;
     S.n_slots = (uint32_t)e->tab.terms.size() + e->n_extra + 1;
     S.tile_words = std::min<uint32_t>(kSolveTileWords, (e->n_exprs + 31) / 32);
@@ -1066,7 +855,7 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     }
     // Presence matrix in LDS next to the output tile: G documents per group = G / 8 bytes per slot, the widest G of
     // 64 / 32 / 16 / 8 that fits (GFT_SOLVE_GROUP_DOCS forces one, for tests); beyond that in HBM (served by L2), G = 64
-    S.fprog_words = e->fprog_words;
+    S.fprog_words = e->progs.fprog_words;
     uint32_t group_docs = 64;
     bool p_in_lds = false;
     for (uint32_t G : {64u, 32u, 16u, 8u}) {
@@ -1075,7 +864,7 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     }
     // ... and the fused programs too, if there is room left (the interpreter fetches them word after word)
     // (a set with a wide INORD group runs the kernel variant that reads its programs from L2: launch_g)
-    const bool prog_in_lds = !e->wide_pairs && solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, true) + 1024 <= e->lds_max;
+    const bool prog_in_lds = !e->progs.wide_pairs && solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, true) + 1024 <= e->lds_max;
     const uint64_t n_groups = (n_docs + group_docs - 1) / group_docs;
     const size_t lds_need = solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, prog_in_lds) + 512;
     const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, e->lds_max / lds_need));
@@ -1085,15 +874,15 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
         S.p_scratch = e->d_pscratch.as<uint64_t>();
     }
     S.wide_slot = nullptr; S.wide_theta = nullptr; S.wide_cap = 0; S.wide_list = nullptr; S.n_wide = 0;
-    if (e->wide_pairs) {
+    if (e->progs.wide_pairs) {
         // (a region per wave of the grid; 12 bytes per pair: 8 192 pairs x 4 096 waves = 400 MB at the very most)
         const uint64_t n_waves = (uint64_t)grid * (kSolveBlockThreads / 64);
-        S.wide_cap = (e->wide_pairs + 63u) & ~63u;
+        S.wide_cap = (e->progs.wide_pairs + 63u) & ~63u;
         HIP_TRY(e->d_wide_slot.ensure(n_waves * S.wide_cap * 4), "INORD scratch alloc");
         HIP_TRY(e->d_wide_theta.ensure(n_waves * S.wide_cap * 8), "INORD scratch alloc");
         S.wide_slot = e->d_wide_slot.as<uint32_t>();
         S.wide_theta = e->d_wide_theta.as<long long>();
-        S.wide_list = e->d_wide_list.as<uint32_t>(); S.n_wide = e->n_wide;
+        S.wide_list = d.wide_list.as<uint32_t>(); S.n_wide = e->progs.n_wide;
     }
     e->last_solve_group_docs = p_in_lds ? group_docs : 0;
     ProfScope ps(e, "solve");
@@ -1126,9 +915,9 @@ struct HostPlan {
 // of order when the caller's matches name a dictionary term (a regex with the text of a keyword), or are themselves not
 // ascending (a foreign engine's keyword hits followed by the regex engine's for the same literal).
 void plan_host(const gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, HostPlan& plan) {
-    plan.all_docs = !e->host_only.empty();
+    plan.all_docs = !e->progs.host_only.empty();
     plan.irregular.clear();
-    if (!extra || !extra->off || e->inord_exprs.empty() || !n_docs) return;
+    if (!extra || !extra->off || e->progs.inord_exprs.empty() || !n_docs) return;
     const uint32_t n_terms = (uint32_t)e->tab.terms.size();
     std::vector<std::pair<uint32_t, uint32_t>> seen;          // (slot, last position) of this document: a handful
     for (uint64_t d = 0; d < n_docs; d++) {
@@ -1136,7 +925,7 @@ void plan_host(const gft_engine* e, const gft_extra_matches* extra, uint64_t n_d
         bool irr = false;
         for (uint64_t i = extra->off[d]; i < extra->off[d + 1] && !irr; i++) {
             const uint32_t sl = extra->slot[i];
-            if (sl >= e->inord_slot.size() || !e->inord_slot[sl]) continue;      // (range errors are upload_extra's to report)
+            if (sl >= e->progs.inord_slot.size() || !e->progs.inord_slot[sl]) continue;      // (range errors are upload_extra's to report)
             if (sl < n_terms) { irr = true; break; }
             size_t k = 0;
             while (k < seen.size() && seen[k].first != sl) k++;
@@ -1195,14 +984,14 @@ int host_eval(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, co
         if (extra && extra->off)
             for (uint64_t i = extra->off[d]; i < extra->off[d + 1]; i++) lists[extra->slot[i]].push_back((int64_t)extra->pos[i]);
         auto solve_one = [&](uint32_t x) {
-            const bool hit = host_solve(e->h_prog.data() + e->h_prog_off[x], e->h_prog_off[x + 1] - e->h_prog_off[x], lists);
+            const bool hit = host_solve(e->progs.prog.data() + e->progs.prog_off[x], e->progs.prog_off[x + 1] - e->progs.prog_off[x], lists);
             const uint64_t w = d * words + (x >> 5);
             const uint32_t bit = 1u << (x & 31);
             if (h_bitmap) h_bitmap[w] = hit ? h_bitmap[w] | bit : h_bitmap[w] & ~bit;
             else { pw.push_back(w); pclr.push_back(hit ? 0u : bit); pset.push_back(hit ? bit : 0u); }
         };
-        for (uint32_t x : e->host_only) solve_one(x);
-        if (irregular) for (uint32_t x : e->inord_exprs) solve_one(x);
+        for (uint32_t x : e->progs.host_only) solve_one(x);
+        if (irregular) for (uint32_t x : e->progs.inord_exprs) solve_one(x);
     }
     if (!h_bitmap && !pw.empty()) {
         if (!d_bitmap) return fail(e, GFT_E_INVALID, "null bitmap");
@@ -1386,8 +1175,9 @@ void gft_engine_destroy(gft_engine* e) {
         for (auto& kv : e->prof)
             for (auto& p : kv.second.ev) { e->prof_pool.push_back(p.first); e->prof_pool.push_back(p.second); }
         for (hipEvent_t ev : e->prof_pool) (void)hipEventDestroy(ev);
-        DevBuf* all[] = {&e->d_byte_class, &e->d_delta, &e->d_out_term, &e->d_out_link, &e->d_term_len, &e->d_prog,
-                         &e->d_prog_off, &e->d_fprog, &e->d_fprog_off, &e->d_groups, &e->d_wide_slot, &e->d_wide_theta, &e->d_wide_list, &e->d_order, &e->d_blk_class, &e->d_wave_blk, &e->d_fprog_t, &e->d_fblk_off, &e->d_pscratch, &e->d_solve_dbg, &e->d_s2_filter,
+        DevBuf* all[] = {&e->d_byte_class, &e->d_delta, &e->d_out_term, &e->d_out_link, &e->d_term_len, &e->d_progs.prog,
+                         &e->d_progs.prog_off, &e->d_progs.fprog, &e->d_progs.fprog_off, &e->d_progs.groups, &e->d_progs.order, &e->d_progs.blk_class, &e->d_progs.wave_blk,
+                         &e->d_progs.fprog_t, &e->d_progs.fblk_off, &e->d_progs.wide_list, &e->d_wide_slot, &e->d_wide_theta, &e->d_pscratch, &e->d_solve_dbg, &e->d_s2_filter,
                          &e->d_s2_slots, &e->d_s2_more, &e->d_s2_cls, &e->d_s2_cls_fold, &e->d_s2_term_blob,
                          &e->d_s2_term_off, &e->d_ctl, &e->d_dbg, &e->d_s2_short3, &e->d_s2_shorts_packed, &e->d_s2_short3_big, &e->d_s2_fpt,
                          &e->d_s3_filter, &e->d_s3_short3, &e->d_s3_srec, &e->d_s3_short3_big, &e->d_s3_srec_big, &e->d_s3_bloom, &e->d_s3_slots,
@@ -1661,7 +1451,7 @@ int gft_build(gft_engine* e, const uint8_t* terms_blob, const uint64_t* term_off
 uint32_t gft_n_terms(const gft_engine* e) { return e ? (uint32_t)e->tab.terms.size() : 0; }
 uint32_t gft_n_states(const gft_engine* e) { return e ? e->tab.n_states : 0; }
 uint32_t gft_n_exprs(const gft_engine* e) { return e ? e->n_exprs : 0; }
-uint32_t gft_n_host_exprs(const gft_engine* e) { return e ? (uint32_t)e->host_only.size() : 0; }
+uint32_t gft_n_host_exprs(const gft_engine* e) { return e ? (uint32_t)e->progs.host_only.size() : 0; }
 int gft_last_nonascii(const gft_engine* e) { return e && e->last_nonascii ? 1 : 0; }
 const char* gft_build_info(void) { return kExtraKernels ? "gfx950 extra_kernels=1" : "gfx950 extra_kernels=0"; }
 const char* gft_scan_kernel(const gft_engine* e) {
@@ -1933,183 +1723,34 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
     if (!e->peers.empty() && !e->in_multi) return multi_set_programs(e, prog_words, prog_off, n_exprs, n_extra);
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
-    const uint32_t n_slots = (uint32_t)e->tab.terms.size() + n_extra;
-    // (slot n_slots itself is the solver's never-present slot: it must fit a program word's field too)
-    if (n_slots > GFT_SLOT_MASK || n_slots >= (1u << kDwFieldBits)) return fail(e, GFT_E_UNSUPPORTED, "too many slots");
-    std::vector<ProgramTraits> traits(n_exprs);
-    for (uint32_t i = 0; i < n_exprs; i++) {
-        if (prog_off[i + 1] < prog_off[i]) return fail(e, GFT_E_INVALID, "prog_off is not ascending");
-        int rc = check_program(e, prog_words + prog_off[i], prog_off[i + 1] - prog_off[i], n_slots, i, &traits[i]);
-        if (rc) return rc;
-    }
+    ProgramSet ps;              // (declared before `drained`: the uploads below read it until the stream has drained)
+    int rc = compile_programs(prog_words, prog_off, n_exprs, (uint32_t)e->tab.terms.size() + n_extra, ps, e->err);
+    if (rc) return rc;          // the handle is untouched: the set installed before, if any, still is
+    refresh_options(e);
+    if (e->opt_solve_dbg) print_program_stats(ps);
     DeviceGuard g(e->device);
     SyncOnExit drained(e);      // host buffers are read by asynchronous copies: drained on every way out
-    std::vector<uint32_t> w(prog_words, prog_words + (n_exprs ? prog_off[n_exprs] : 0));
-    std::vector<uint64_t> o(prog_off, prog_off + (n_exprs ? n_exprs + 1 : 0));
-    if (o.empty()) o.push_back(0);
-    int rc;
-    if ((rc = upload(e, e->d_prog, w, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_prog_off, o, "program upload"))) return rc;
-    std::vector<uint32_t> fw, groups, fdepth;
-    std::vector<uint64_t> fo(1, 0);
-    for (uint32_t i = 0; i < n_exprs; i++) {
-        if (traits[i].over_limit || traits[i].wide_pairs) {
-            // beyond a limit of the device solver: the device evaluates a stand-in (one leaf on the never-present slot), the
-            // expression itself is solved on the host from the scan's matches (host_solve.hpp) and its bit patched in.
-            // An expression with a WIDE INORD group gets the same stand-in in the fused form: the solver's second phase
-            // (gft_solve.hip wide_expr_doc) answers it from its public words, a document per wave
-            const uint32_t stub = GFT_OP_UNIT << 28 | n_slots;
-            fdepth.push_back(fuse_program(&stub, 1, 0, fw, groups));
-        } else {
-            const size_t fw0 = fw.size(), g0 = groups.size();
-            uint32_t depth = fuse_program(prog_words + prog_off[i], prog_off[i + 1] - prog_off[i], prog_off[i], fw, groups);
-            if (depth > kMaxBoolDepth) {
-                // the fused form still nests deeper than the interpreter's stack (a balanced tree of 2^128 sub-trees would):
-                // the host's
-                fw.resize(fw0); groups.resize(g0);
-                traits[i].over_limit = true;
-                const uint32_t stub = GFT_OP_UNIT << 28 | n_slots;
-                depth = fuse_program(&stub, 1, 0, fw, groups);
-            }
-            fdepth.push_back(depth);
-        }
-        while (fw.size() % 4) fw.push_back((uint32_t)kFopNop << 28);       // the interpreter reads 4-word chunks
-        fo.push_back(fw.size());
-    }
-    // Evaluation order: inside every output tile (kSolveTileWords * 32 expressions) the programs are sorted by the
-    // interpreter they need -- 2: nest deeper than its register stack, 1: use the stack, 0: flat (no push / pop at all,
-    // half the work per word) -- and by length, and handed to the waves 64 at a time, so that the lanes of a wave run
-    // loops of similar length on the cheapest interpreter that serves them all (longest first inside classes 2 and 1,
-    // shortest first inside class 0: the block on the border mixes short programs of both).
-    // order[i] = expression evaluated at sorted position i; blk_class[b] = the interpreter of block b.
-    std::vector<uint32_t> order(n_exprs), blk_class, fprog_t, fblk_off, wave_blk;
-    for (uint32_t i = 0; i < n_exprs; i++) order[i] = i;
-    auto klass = [&](uint32_t x) { return fdepth[x] > kSolveRegStack ? 2u : fdepth[x] > 0 ? 1u : 0u; };
-    auto plen = [&](uint32_t x) { return fo[x + 1] - fo[x]; };
-    const uint32_t tile_exprs = kSolveTileWords * 32;
-    constexpr uint32_t kWaves = kSolveBlockThreads / 64;
-    for (uint32_t t0 = 0; t0 < n_exprs; t0 += tile_exprs) {
-        const uint32_t t1 = std::min(n_exprs, t0 + tile_exprs);
-        std::stable_sort(order.begin() + t0, order.begin() + t1, [&](uint32_t a, uint32_t b) {
-            if (klass(a) != klass(b)) return klass(a) > klass(b);
-            return klass(a) ? plen(a) > plen(b) : plen(a) < plen(b);
-        });
-        std::vector<uint64_t> cost;              // VALU work of a block, for the deal below
-        for (uint32_t b0 = t0; b0 < t1; b0 += 64) {
-            uint32_t cls = 0;
-            uint64_t maxlen = 0;
-            for (uint32_t i = b0; i < std::min(t1, b0 + 64); i++) {
-                cls = std::max(cls, klass(order[i]));
-                maxlen = std::max(maxlen, plen(order[i]));
-            }
-            blk_class.push_back(cls);
-            cost.push_back(maxlen * (cls == 2 ? 40 : cls == 1 ? 26 : 14) + 160);
-            // the block's chunks transposed: words 4c..4c+3 of lane l at off + (c * 64 + l) * 4
-            if (fprog_t.size() + maxlen * 64 > 0xFFFFFFFFull) return fail(e, GFT_E_UNSUPPORTED, "program set too large");
-            fblk_off.push_back((uint32_t)fprog_t.size());
-            fprog_t.resize(fprog_t.size() + maxlen * 64, kDwNop);
-            for (uint32_t i = b0; i < std::min(t1, b0 + 64); i++) {
-                const uint64_t p0 = fo[order[i]], len = fo[order[i] + 1] - p0;
-                for (uint64_t pc = 0; pc < len; pc++)
-                    fprog_t[fblk_off.back() + ((pc / 4) * 64 + (i - b0)) * 4 + pc % 4] = fused_to_device(fw[p0 + pc]);
-            }
-        }
-        // The deal: the tile's blocks go to the workgroup's waves sixteen at a time.  Wave w runs on SIMD w % 4 and the
-        // four waves of a SIMD share its issue slots, so every round's blocks are dealt by cost, the most expensive
-        // first, to the SIMD with the least work so far that still has a wave free (its lowest wave: the oldest wave of
-        // a SIMD is served first, which suits the block everybody else ends up waiting for).
-        // wave_blk[tile's first block + round * 16 + wave] = block (relative to the tile) or ~0.
-        // (a full tile is 32 blocks = two rounds, so a tile's entries start at its first block's index)
-        const uint32_t nblk = (uint32_t)cost.size();
-        std::vector<uint32_t> by_cost(nblk);
-        for (uint32_t b = 0; b < nblk; b++) by_cost[b] = b;
-        for (uint32_t r0 = 0; r0 < nblk; r0 += kWaves) {
-            const uint32_t r1 = std::min(nblk, r0 + kWaves);
-            std::stable_sort(by_cost.begin() + r0, by_cost.begin() + r1, [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-            uint64_t load[4] = {0, 0, 0, 0};
-            uint32_t used[4] = {0, 0, 0, 0};
-            uint32_t deal[kWaves];
-            for (uint32_t w = 0; w < kWaves; w++) deal[w] = 0xFFFFFFFFu;
-            for (uint32_t k = r0; k < r1; k++) {
-                int best = -1;
-                for (int q = 0; q < 4; q++)
-                    if (used[q] < kWaves / 4 && (best < 0 || load[q] < load[best])) best = q;
-                deal[used[best] * 4 + best] = by_cost[k];
-                used[best]++;
-                load[best] += cost[by_cost[k]];
-            }
-            for (uint32_t w = 0; w < kWaves; w++) wave_blk.push_back(deal[w]);
-        }
-    }
-    if (order.empty()) order.push_back(0);
-    if (blk_class.empty()) blk_class.push_back(0);
-    if (wave_blk.empty()) wave_blk.push_back(0xFFFFFFFFu);
-    if (fblk_off.empty()) fblk_off.push_back(0);
-    if (fprog_t.empty()) fprog_t.push_back(0);
-    refresh_options(e);
-    if (e->opt_solve_dbg) {
-        uint64_t hist[16] = {0}, with_rare = 0, maxlen = 0;
-        for (uint32_t i = 0; i < n_exprs; i++) {
-            bool rare = false;
-            for (uint64_t k = fo[i]; k < fo[i + 1]; k++) { hist[fw[k] >> 28]++; rare |= (fw[k] >> 28) >= kFopAndPop; }
-            with_rare += rare;
-            maxlen = std::max<uint64_t>(maxlen, fo[i + 1] - fo[i]);
-        }
-        fprintf(stderr, "[gft solve debug] %u programs, %zu fused words (max %llu); programs with stack/not/inord ops: %llu; ops:",
-                n_exprs, fw.size(), (unsigned long long)maxlen, (unsigned long long)with_rare);
-        for (int k = 1; k <= 15; k++) fprintf(stderr, " %d:%llu", k, (unsigned long long)hist[k]);
-        fprintf(stderr, "\n");
-    }
-    if (groups.size() / 2 > (1u << kDwFieldBits)) return fail(e, GFT_E_UNSUPPORTED, "too many INORD groups");
-    // the kernel reads control bits, not opcodes (gft_kernels.hpp fused_to_device)
-    std::vector<uint32_t> dw(fw.size());
-    for (size_t i = 0; i < fw.size(); i++) dw[i] = fused_to_device(fw[i]);
-    if (dw.empty()) dw.push_back(kDwNop);
-    if (groups.empty()) groups.assign(2, 0);
-    if ((rc = upload(e, e->d_fprog, dw, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_fprog_off, fo, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_groups, groups, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_order, order, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_blk_class, blk_class, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_wave_blk, wave_blk, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_fprog_t, fprog_t, "program upload"))) return rc;
-    if ((rc = upload(e, e->d_fblk_off, fblk_off, "program upload"))) return rc;
+    // from here on the device holds a mixture of two sets until the last upload has landed: an error on the way leaves a
+    // handle that answers GFT_E_NOT_BUILT, as after gft_build
+    e->have_programs = false;
+    e->n_exprs = 0;
+    gft_engine::ProgramBufs& d = e->d_progs;
+    if ((rc = upload(e, d.prog, ps.prog, "program upload"))) return rc;
+    if ((rc = upload(e, d.prog_off, ps.prog_off, "program upload"))) return rc;
+    if ((rc = upload(e, d.fprog, ps.fprog, "program upload"))) return rc;
+    if ((rc = upload(e, d.fprog_off, ps.fprog_off, "program upload"))) return rc;
+    if ((rc = upload(e, d.groups, ps.groups, "program upload"))) return rc;
+    if ((rc = upload(e, d.order, ps.order, "program upload"))) return rc;
+    if ((rc = upload(e, d.blk_class, ps.blk_class, "program upload"))) return rc;
+    if ((rc = upload(e, d.wave_blk, ps.wave_blk, "program upload"))) return rc;
+    if ((rc = upload(e, d.fprog_t, ps.fprog_t, "program upload"))) return rc;
+    if ((rc = upload(e, d.fblk_off, ps.fblk_off, "program upload"))) return rc;
+    if (ps.n_wide && (rc = upload(e, d.wide_list, ps.wide_list, "program upload"))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream), "program upload");
+    e->progs = std::move(ps);
     e->n_exprs = n_exprs; e->n_extra = n_extra; e->have_programs = true;
     e->scan_valid_docs = ~0ull;          // positions may not have been written for the old program set
     e->csr_valid = false;
-    // what the host may have to solve (host_solve.hpp)
-    e->h_prog.swap(w); e->h_prog_off.swap(o);
-    e->host_only.clear(); e->inord_exprs.clear();
-    e->inord_slot.assign((size_t)n_slots + 1, 0);
-    for (uint32_t i = 0; i < n_exprs; i++) {
-        if (traits[i].over_limit) e->host_only.push_back(i);
-        else if (!traits[i].inord_slots.empty()) {
-            e->inord_exprs.push_back(i);
-            for (uint32_t sl : traits[i].inord_slots) e->inord_slot[sl] = 1;
-        }
-    }
-    e->wide_pairs = 0;
-    std::vector<uint32_t> wide_list;                     // per wide expression: index, offset and length of its public words
-    for (uint32_t i = 0; i < n_exprs; i++)
-        if (!traits[i].over_limit && traits[i].wide_pairs) {
-            e->wide_pairs = std::max(e->wide_pairs, traits[i].wide_pairs);
-            if (prog_off[i + 1] > 0xFFFFFFFFull) return fail(e, GFT_E_UNSUPPORTED, "program set too large");
-            wide_list.push_back(i); wide_list.push_back((uint32_t)prog_off[i]); wide_list.push_back((uint32_t)(prog_off[i + 1] - prog_off[i]));
-        }
-    e->n_wide = (uint32_t)(wide_list.size() / 3);
-    if (e->n_wide) {
-        if ((rc = upload(e, e->d_wide_list, wide_list, "program upload"))) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream), "program upload");        // (wide_list is a local)
-    }
-    e->traits.swap(traits);
-    e->fprog_words = (uint32_t)fw.size();
-    e->n_inord_groups = e->n_rare_words = 0;
-    for (uint32_t w : fw) {
-        e->n_inord_groups += (w >> 28) == kFopInord;
-        e->n_rare_words += (w >> 28) == kFopInord || (w >> 28) == kFopNot;
-    }
-    e->n_inord_groups += e->n_wide;                      // (their groups read positions too: the scan must write them)
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
@@ -2130,7 +1771,7 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
     std::vector<uint64_t> xo;
     std::vector<uint32_t> xs, xp;
     gft_extra_matches hx{nullptr, nullptr, nullptr};
-    const bool want_hx = d_extra && d_extra->off && n_docs && (!e->host_only.empty() || !e->inord_exprs.empty());
+    const bool want_hx = d_extra && d_extra->off && n_docs && (!e->progs.host_only.empty() || !e->progs.inord_exprs.empty());
     if (want_hx) {
         xo.resize(n_docs + 1);
         HIP_TRY(hipMemcpy(xo.data(), d_extra->off, (n_docs + 1) * 8, hipMemcpyDeviceToHost), "extra read-back");
@@ -2217,7 +1858,7 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
     gft_engine::Pending& pb = e->pend[k];
     pb.done = false; pb.rc = GFT_OK;
     pb.d_text = d_text_blob; pb.d_doc_off = d_doc_off; pb.n_docs = n_docs; pb.flags = flags; pb.d_bitmap = d_hit_bitmap;
-    const bool simple = n_docs && e->device >= 0 && e->built && e->have_programs && !(d_extra && d_extra->off) && e->host_only.empty() &&
+    const bool simple = n_docs && e->device >= 0 && e->built && e->have_programs && !(d_extra && d_extra->off) && e->progs.host_only.empty() &&
                         (!e->n_exprs || d_hit_bitmap);
     if (!simple) {
         // (whatever cannot be deferred -- caller-supplied matches, host-solved expressions, the first batches of an engine,
@@ -2615,19 +2256,25 @@ int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, 
 int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_slots,
                             const uint8_t* present, uint8_t* out_hit, uint32_t* out_depth) try {
     if (!prog_words || !prog_off || !out_hit || (n_slots && !present) || n_slots > (1u << kDwFieldBits)) return GFT_E_INVALID;
-    gft_engine scratch;                              // (only its error string is used, by check_program)
+    ProgramSet ps;
+    std::string err;
+    const int rc = compile_programs(prog_words, prog_off, n_exprs, n_slots, ps, err);
+    if (rc) return rc;
+    std::vector<uint8_t> elsewhere(n_exprs, 0);      // answered by the host, or by the solver's second phase: a stand-in here
+    for (uint32_t x : ps.host_only) elsewhere[x] = 1;
+    for (uint32_t k = 0; k < ps.n_wide; k++) elsewhere[ps.wide_list[3 * k]] = 1;
     for (uint32_t i = 0; i < n_exprs; i++) {
-        if (prog_off[i + 1] < prog_off[i]) return GFT_E_INVALID;
-        const int rc = check_program(&scratch, prog_words + prog_off[i], prog_off[i + 1] - prog_off[i], n_slots, i);
-        if (rc) return rc;
-        std::vector<uint32_t> fw, groups;
-        const uint32_t depth = fuse_program(prog_words + prog_off[i], prog_off[i + 1] - prog_off[i], prog_off[i], fw, groups);
-        if (out_depth) out_depth[i] = depth;
+        // expression ex the way its lane reads it (gft_solve.hip run_program_far): sorted position i = lane i % 64 of block i / 64
+        const uint32_t ex = ps.order[i], b = i / 64, lane = i % 64;
+        if (elsewhere[ex]) return GFT_E_UNSUPPORTED;
+        const uint32_t depth = ps.fdepth[ex];
+        if (out_depth) out_depth[ex] = depth;
         // the device's data flow on one document (gft_kernels.hpp "What the kernel reads", gft_solve.hip run_program)
         bool acc = false;
         std::vector<bool> stack;
-        for (uint32_t f : fw) {
-            const uint32_t w = fused_to_device(f);
+        size_t reached = 0;
+        for (uint64_t pc = 0; pc < ps.fprog_off[ex + 1] - ps.fprog_off[ex]; pc++) {
+            const uint32_t w = ps.fprog_t[ps.fblk_off[b] + ((pc / 4) * 64 + lane) * 4 + pc % 4];
             if (w & kDwRare) {
                 if (!(w & kDwNeg)) return GFT_E_UNSUPPORTED;         // an INORD group: needs positions
                 acc = !acc;
@@ -2642,9 +2289,12 @@ int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off
             if (w & kDwPop) stack.pop_back();
             if (w & kDwPush) stack.push_back(before);
             if (stack.size() > depth) return GFT_E_INVALID;           // fuse_program's own depth figure must hold
+            reached = std::max(reached, stack.size());
         }
         if (!stack.empty()) return GFT_E_INVALID;
-        out_hit[i] = acc ? 1 : 0;
+        // ... and fits the interpreter its block was given
+        if (reached > (ps.blk_class[b] == 0 ? 0u : ps.blk_class[b] == 1 ? kSolveRegStack : kMaxBoolDepth)) return GFT_E_INTERNAL;
+        out_hit[ex] = acc ? 1 : 0;
     }
     return GFT_OK;
 } GFT_CATCH(nullptr)
@@ -2652,12 +2302,12 @@ int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off
 int gft_debug_host_solve(const uint32_t* words, uint64_t len, const uint32_t* slots, const uint64_t* list_off,
                          const int64_t* positions, uint32_t n_lists, int* out) try {
     if (!words || !out || (n_lists && (!slots || !list_off))) return GFT_E_INVALID;
-    gft_engine scratch;                              // (only its error string is used, by check_program)
     uint32_t n_slots = 0;
     for (uint64_t i = 0; i < len; i++)
         if ((words[i] >> 28) == GFT_OP_UNIT) n_slots = std::max(n_slots, (words[i] & GFT_SLOT_MASK) + 1);
     ProgramTraits tr;
-    const int rc = check_program(&scratch, words, len, n_slots, 0, &tr);
+    std::string err;
+    const int rc = check_program(words, len, n_slots, 0, tr, err);
     if (rc) return rc;
     SlotLists m;
     for (uint32_t k = 0; k < n_lists; k++) {

@@ -1,4 +1,5 @@
-// Kernel parameter blocks + launcher prototypes shared by gft_kernels.hip and gft_api.cpp.
+// Kernel parameter blocks + launcher prototypes shared by the kernels (*.hip) and gft_api.cpp; the solver's limits and
+// program word formats, shared with the program compiler (program_set.cpp) as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

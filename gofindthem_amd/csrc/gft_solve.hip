@@ -6,7 +6,7 @@
 //      scan kernel's match slabs with ds_or (UNIT truth == key presence, dsl/expression.go:68-72);
 //   2. every lane interprets ONE expression over 64-bit masks, so each AND/OR/NOT evaluates 64 documents at once
 //      (the reference evaluates every node, no short-circuit, so this is the same function, expression.go:74-127);
-//      programs are fused at gft_set_programs time (gft_api.cpp fuse_program), staged in LDS and handed to the waves
+//      programs are fused at gft_set_programs time (program_set.cpp fuse_program), staged in LDS and handed to the waves
 //      sorted by length;
 //   3. INORD(...) groups: the boolean value of the group's subtree gives the candidate documents; only for those
 //      the position algebra runs, per document, on (slot, theta) pairs with successor queries;

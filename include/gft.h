@@ -137,13 +137,17 @@ int gft_scan_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d
 #define GFT_INORD_FLAG (1u << 27)
 #define GFT_SLOT_MASK ((1u << 27) - 1u)
 
-/* Limits of the DEVICE solver that the reference does not have: an INORD group with more than 64 leaves-with-thresholds
- * alive at once or nested deeper than 32, an operand stack deeper than 128 (left-deep chains of any length are fine: they
- * need no stack).  An expression beyond them is accepted all the same: gft_process* solve it on the host from the scan's
- * matches (csrc/host_solve.cpp, the reference's recursion restated -- dsl/expression.go:66-142 has no such limits) and put
- * its bit into the bitmap; every other expression of the set still runs on the device.
+/* Limits of the DEVICE solver that the reference does not have: an INORD group with more than 8 192 (slot, threshold) pairs
+ * alive at once or a pair stack deeper than 64, a fused form that nests deeper than 128 (chains nested to one side, of any
+ * length, are fine: they need no stack).  An expression beyond them is accepted all the same: gft_process* solve it on the
+ * host from the scan's matches (csrc/host_solve.cpp, the reference's recursion restated -- dsl/expression.go:66-142 has no
+ * such limits) and put its bit into the bitmap; every other expression of the set still runs on the device.
  * Refused with GFT_E_UNSUPPORTED: 2^25 slots or more (terms + extra literals; the solver's program words carry a 25-bit
- * slot), keywords longer than 7 424 bytes (gft_build). */
+ * slot), keywords longer than 7 424 bytes (gft_build).
+ * What an error leaves behind: the set is compiled on the host first (csrc/program_set.cpp), and a refusal there -- a
+ * malformed program, a limit above -- returns with the handle untouched: the set installed before, if any, stays installed
+ * and gft_process* go on answering from it.  An error after that, while the new set is copied to the device, leaves a handle
+ * without programs: gft_process* answer GFT_E_NOT_BUILT until a gft_set_programs call succeeds. */
 int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs,
                      uint32_t n_extra);
 uint32_t gft_n_exprs(const gft_engine* e);
@@ -418,12 +422,16 @@ int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, 
                            uint32_t lane_start, uint32_t scan_flags, uint32_t groups, uint8_t* out_exact, uint8_t* out_dual,
                            uint32_t* groups_used);
 
-/* The solver's program compiler alone, on the host: every program goes through the same steps as in gft_set_programs
- * (check, fusion with Sethi-Ullman operand order, control-bit device words) and its device words are then interpreted for
- * ONE document whose presence set is `present` (one byte per slot, non-zero = the slot's term occurs).  out_hit[i] = the
- * expression's truth value, out_depth[i] (nullable) = the accumulator-stack depth its fused form needs.  Programs with an
- * INORD group of more than one leaf need positions: GFT_E_UNSUPPORTED.  No HIP device is needed; tests use it to check the
- * compiler against the oracle's tree evaluation. */
+/* The solver's program compiler alone, on the host: the set is compiled by the very function gft_set_programs calls
+ * (csrc/program_set.cpp: check, fusion with Sethi-Ullman operand order, control-bit device words, evaluation order, blocks of
+ * 64 transposed) and every expression is then interpreted, from the transposed array the kernel reads, for ONE document
+ * whose presence set is `present` (one byte per slot, non-zero = the slot's term occurs).  out_hit[i] = the expression's
+ * truth value, out_depth[i] (nullable) = the accumulator-stack depth its fused form needs.  An expression that the device
+ * does not answer from presence alone is GFT_E_UNSUPPORTED: an INORD group of more than one leaf (it needs positions), a
+ * wide INORD group, an expression the host solves.  A program whose PUBLIC postfix form is deeper than 128 but whose fused
+ * form is not is evaluated, as gft_set_programs accepts it.  GFT_E_INTERNAL: a program reaches a stack depth that the
+ * interpreter chosen for its block does not have.  No HIP device is needed; tests use it to check the compiler against the
+ * oracle's tree evaluation. */
 int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_slots,
                             const uint8_t* present, uint8_t* out_hit, uint32_t* out_depth);
 

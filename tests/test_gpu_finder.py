@@ -483,6 +483,38 @@ def test_expressions_beyond_the_device_solver_limits_are_solved_on_the_host():
         assert np.array_equal(bm.cpu().numpy().astype(np.uint32), want)
 
 
+def test_a_refused_program_set_leaves_the_installed_one_in_place():
+    """gft_set_programs compiles a set before it touches the handle: a set with a malformed program is refused and the set
+    installed before goes on answering -- its fused programs, its INORD group table and the public words that table points
+    into (a refused set must not have replaced them) included."""
+    from gofindthem_amd.engine import Engine, GftError
+    U, AND, OR, NOT, INORD, FL = 1 << 28, 2 << 28, 3 << 28, 4 << 28, 5 << 28, 1 << 27
+    e = Engine()
+    try:
+        e.build(["a", "b", "c"])
+        a, b, c = (e.term_id(t) for t in "abc")
+        set_a = [[U | a, U | b, AND],                                     # "a" and "b"
+                 [U | FL | a, U | FL | b, AND | FL, INORD],               # inord("a" and "b")
+                 [U | c, NOT, U | a, OR]]                                 # not "c" or "a"
+        blob, off = pack_strings(["ab", "ba", "c", "", "bca"])
+        e.set_programs(set_a)
+        want = e.process(blob, off)
+        assert [int(x) for x in want[:, 0]] == [0b111, 0b101, 0b000, 0b100, 0b101]
+        # set B: other public words, more of them, the fourth program does not reduce to one value
+        set_b = [[U | c], [U | FL | c, U | FL | a, AND | FL, INORD, U | b, OR], [U | b, NOT], [U | a, U | b], [U | a]]
+        with pytest.raises(GftError) as err:
+            e.set_programs(set_b)
+        assert err.value.code == _lib.GFT_E_INVALID and "program 3" in err.value.msg
+        assert e.n_exprs == 3
+        assert np.array_equal(e.process(blob, off), want)
+        with pytest.raises(GftError) as err:                              # ... nor a slot that no term or extra literal has
+            e.set_programs([[U | 3]])
+        assert err.value.code == _lib.GFT_E_INVALID
+        assert np.array_equal(e.process(blob, off), want)
+    finally:
+        e.close()
+
+
 @pytest.mark.parametrize("k", [100, 10000])
 def test_inord_chains_of_the_reference_benchmarks(k):
     """benchmarks/benchmark_test.go:55-56, 132-134, 182-184, 438-462: exp100 / exp10000 are ONE `INORD` of 100 / 10 000 AND-ed

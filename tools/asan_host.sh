@@ -15,13 +15,13 @@ for f in gft_kernels.hip gft_solve.hip gft_scan3.hip gft_scan5.hip gft_compact.h
   [ $o -nt $CS/$f ] || hipcc --offload-arch=gfx950 -O1 -std=c++17 -fPIC -c $CS/$f -o $o
   objs="$objs $o"
 done
-for f in gft_api.cpp ac_tables.cpp scan2_tables.cpp scan3_tables.cpp dsl_compile.cpp finder_host.cpp json_mini.cpp group_host.cpp host_solve.cpp compact_host.cpp; do
+for f in gft_api.cpp ac_tables.cpp scan2_tables.cpp scan3_tables.cpp dsl_compile.cpp finder_host.cpp json_mini.cpp group_host.cpp host_solve.cpp compact_host.cpp program_set.cpp; do
   o=$OUT/$f.o
   hipcc -x hip --offload-arch=gfx950 -O1 -std=c++17 -fPIC $SAN -c $CS/$f -o $o
   objs="$objs $o"
 done
 hipcc -shared $SAN -shared-libsan -o $OUT/libgft.so $objs
 RT=$(dirname $(hipcc -print-file-name=libclang_rt.asan-x86_64.so))
-GFT_LIBRARY=$PWD/$OUT/libgft.so LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \
+GFT_LIBRARY=$PWD/$OUT/libgft.so LD_PRELOAD=$RT/libclang_rt.asan-x86_64.so${LD_PRELOAD:+:$LD_PRELOAD} ASAN_OPTIONS=detect_leaks=0:abort_on_error=1 \
   UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 LD_LIBRARY_PATH=$RT:$LD_LIBRARY_PATH \
   python -m pytest tests -x -q -m "not gpu" -p no:cacheprovider "$@"
