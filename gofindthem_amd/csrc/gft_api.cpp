@@ -19,15 +19,13 @@
 
 #include <cstdlib>
 
-#include "ac_tables.hpp"
 #include "compact_host.hpp"
 #include "copy_pool.hpp"
 #include "gft_guard.hpp"
 #include "gft_kernels.hpp"
 #include "host_solve.hpp"
 #include "program_set.hpp"
-#include "scan2_tables.hpp"
-#include "scan3_tables.hpp"
+#include "table_set.hpp"
 
 using namespace gft;
 
@@ -51,14 +49,6 @@ struct DevBuf {
 struct ProfCat {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
 };
-
-// The kernel that scans the text: the two-tier DFA kernel (gft_kernels.hip: an independent algorithm, the cross-check) or
-// one of the suffix-window kernels.  Those count the slabs of the match pool that their waves take, the DFA kernel counts
-// its matches.
-enum class ScanKernel { dfa, scan2, scan3, scan4, scan5 };
-constexpr const char* kScanKernelName[] = {"dfa", "scan2", "scan3", "scan4", "scan5"};
-constexpr bool counts_slabs(ScanKernel k) { return k != ScanKernel::dfa; }     // ... and leaves a unit's matches unsorted
-constexpr bool on_scan2_tables(ScanKernel k) { return k == ScanKernel::scan2 || k == ScanKernel::scan4 || k == ScanKernel::scan5; }
 
 // What a scan launch knew.  A deferred launch (scan_pipeline) ran without a read-back of the unit count or the pool need:
 // its caller judges it against these numbers after its last kernel -- the engine's own may have changed by then, for a
@@ -103,49 +93,29 @@ struct gft_engine {
     size_t lds_max = 65536;
     mutable std::string err;
 
-    // automaton
-    AcTables tab;
+    // the dictionary (table_set.hpp): the compiled tables, the scan kernel chosen for them on this device with its LDS plan
+    // and what scan5 derives from them; d_tabs: the copies on the device of what the DFA kernel, the gather (term_len) and
+    // the chosen kernel read
+    gft::TableSet tables;
+    gft::ScanPlan plan;
+    Scan5Tables s5;
     bool built = false;
     uint32_t build_flags = 0;
-    uint32_t n_lds_states = 0;
-    DevBuf d_byte_class, d_delta, d_out_term, d_out_link, d_term_len;
-    // the scan kernel of the built dictionary (choose_scan_kernel) and its waves per workgroup (dfa: 0, it owns no slabs)
-    ScanKernel kernel = ScanKernel::dfa;
-    uint32_t scan_waves = 0;
+    struct TableBufs {
+        struct { DevBuf byte_class, delta, out_term, out_link, term_len; } dfa;
+        struct { DevBuf filter, slots, more, cls, cls_fold, term_blob, term_off, short3, shorts_packed, short3_big, fpt; } s2;
+        struct { DevBuf filter, short3, srec, short3_big, srec_big, bloom, slots, more, cls, cls_fold, term_blob, term_off; } s3;
+        struct { DevBuf grp, grp_fold, filter, bloom; } s5;
+    } d_tabs;
     // control block (64 B): [0] u32 bad-offsets flag, [8] u64 pool cursor, [16] u64 exact match count, [24] u32 a folded scan
     // saw a byte >= 0x80, [32] u64 n_units,
     // [40] u64 first text offset, [48] u64 last text offset -- one memset per batch, one read-back per synchronisation
     DevBuf d_ctl, d_dbg;
     uint64_t scan_valid_docs = ~0ull;                   // documents of the last gft_process scan still in the pool (~0: none)
-    // scan3 (gft_scan3.hip): the stride-2 suffix-window kernel, any alphabet
-    Scan3Tables s3;
-    DevBuf d_s3_filter, d_s3_short3, d_s3_srec, d_s3_short3_big, d_s3_srec_big, d_s3_bloom, d_s3_slots, d_s3_more, d_s3_cls,
-        d_s3_cls_fold, d_s3_term_blob, d_s3_term_off;
-    uint32_t scan3_cand_cap = 0;                        // scan3_plan
-    // scan2's tables: what scan2, scan4 and scan5 run on
-    Scan2Tables s2;
-    DevBuf d_s2_filter, d_s2_slots, d_s2_more, d_s2_cls, d_s2_cls_fold, d_s2_term_blob, d_s2_term_off;
-    DevBuf d_s2_short3, d_s2_shorts_packed, d_s2_short3_big, d_s2_fpt;
-    uint32_t scan2_short3_bytes = 0;
-    uint32_t scan2_unit_max = kScan2UnitMax;            // bytes per work unit of these three (adapts to the match density)
-    // scan2 (gft_scan2.hip): the suffix-window kernel, one filter probe per byte
-    uint32_t scan2_cand_cap = 0;                        // scan2_plan
-    // scan4 (gft_scan4.hip): its streaming form, with an LDS plan of its own; a unit's region of the match pool is sized
-    // from the match density (matches per text byte) of the batches before
-    uint32_t scan4_fifo[2] = {0, 0};                    // fifo entries without / with positions
+    // what the batches teach the kernels on scan2's tables (learn_from_batch; not plan): the bytes per work unit follow the
+    // match density, and scan4 sizes a unit's region of the match pool from the matches per text byte of the batches before
+    uint32_t scan2_unit_max = kScan2UnitMax;
     double scan4_density = 0.06;
-    // scan5 (gft_scan5.hip): the unit's text in LDS, a filter over merged classes in front of scan2's tables
-    Scan5Plan s5plan{0, 0, 0, 0};
-    Scan5Tables s5;
-    DevBuf d_s5_grp, d_s5_grp_fold, d_s5_filter, d_s5_bloom;
-    std::vector<uint32_t> s5_bloom;                     // the Bloom level in front of a global fingerprint table (gft_kernels.hpp scan5_bloom_g)
-    uint32_t s5_bloom_lg = 0;                           // 2^lg bits; 0: none
-    uint32_t s5_term_bits = 0, s5_pos_bias = 0;
-    bool s5_short_groups = false;                       // its short terms come from scan3's tables (> 32 byte classes)
-    uint32_t opt_scan5_bloom_kb = 32;                   // GFT_SCAN5_BLOOM_KB: the Bloom level's size in LDS (0: none; a power of two up to 64)
-    uint32_t opt_scan5_large = 1;                       // GFT_SCAN5_LARGE=0: dictionaries over more than 32 byte classes stay on scan3
-    uint32_t opt_scan5_fifo = 0;                        // GFT_SCAN5_FIFO: entries of a wave's match fifo (0: 256; timing study)
-    uint32_t opt_scan5_groups = 0;                      // GFT_SCAN5_GROUPS: forced number of filter groups (tests)
     uint32_t last_nonascii_bits = 0;                    // what the scan kernels said: 1 = bytes >= 0x80 seen, not judged; 2 = judged unsafe
     bool last_nonascii = false;                         // the last GFT_FOLD_ASCII scan ran over text that ASCII folding does not
                                                         // lower-case the way strings.ToLower does (gft_last_nonascii)
@@ -234,19 +204,28 @@ struct gft_engine {
 
 namespace {
 
+long env_num(const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; }
+
 void refresh_options(gft_engine* e) {
-    auto num = [](const char* name, long dflt) { const char* v = getenv(name); return v ? atol(v) : dflt; };
+    const auto num = env_num;
     e->opt_scan_dbg = (uint32_t)num("GFT_SCAN_DEBUG", 0);
     e->opt_scan_prio = num("GFT_SCAN_PRIO", 1) ? 1u : 0u;
     e->opt_scan_ordered = getenv("GFT_SCAN_ORDERED") ? 1u : 0u;
     e->opt_scan4_chunk = (uint32_t)num("GFT_SCAN4_CHUNK", 0);
     e->opt_scan4_round = (uint32_t)num("GFT_SCAN4_ROUND", 0);
-    e->opt_scan5_groups = (uint32_t)num("GFT_SCAN5_GROUPS", 0);
-    e->opt_scan5_large = num("GFT_SCAN5_LARGE", 1) ? 1u : 0u;
-    e->opt_scan5_bloom_kb = (uint32_t)std::min<long>(std::max<long>(num("GFT_SCAN5_BLOOM_KB", 32), 0), 64);
-    e->opt_scan5_fifo = (uint32_t)std::min<long>(std::max<long>(num("GFT_SCAN5_FIFO", 0), 0), 4096) & ~63u;
     e->opt_solve_dbg = (uint32_t)num("GFT_SOLVE_DEBUG", 0);
     e->opt_solve_group = (int)num("GFT_SOLVE_GROUP_DOCS", -1);
+}
+// what plan_scan is told (table_set.hpp): GFT_SCAN_KERNEL and the GFT_SCAN5_* switches, read by gft_build / gft_import_tables
+ScanOptions scan_options() {
+    const auto num = env_num;
+    ScanOptions o;
+    o.forced = parse_forced(getenv("GFT_SCAN_KERNEL"));
+    o.scan5_groups = (uint32_t)num("GFT_SCAN5_GROUPS", 0);
+    o.scan5_large = num("GFT_SCAN5_LARGE", 1) ? 1u : 0u;
+    o.scan5_bloom_kb = (uint32_t)std::min<long>(std::max<long>(num("GFT_SCAN5_BLOOM_KB", 32), 0), 64);
+    o.scan5_fifo = (uint32_t)std::min<long>(std::max<long>(num("GFT_SCAN5_FIFO", 0), 0), 4096) & ~63u;
+    return o;
 }
 #define GFT_LOCK(e) std::lock_guard<std::recursive_mutex> _gft_lock((e)->mu)
 
@@ -329,13 +308,13 @@ int csr_from_pool(gft_engine* e, uint64_t n_docs) {
                                   e->d_partial.as<uint64_t>(), st), "unit_out scan");
     // (the suffix-window kernels leave a unit's matches in any order -- shifted anchors report a term from another position
     // than its end, also on scan2's per-lane path: the gather sorts them)
-    const bool sort_units = counts_slabs(e->kernel);
+    const bool sort_units = counts_slabs(e->plan.kernel);
     HIP_TRY(launch_gather(e->d_unit_start.as<uint64_t>(), e->d_unit_count.as<uint32_t>(),
                           e->d_unit_out.as<uint64_t>(), n_units, e->d_pool_term.as<uint32_t>(),
                           e->d_pool_pos.as<uint32_t>(), e->d_term.as<uint32_t>(), e->d_pos.as<uint32_t>(),
                           e->d_unit_base.as<uint64_t>(), n_docs, e->d_match_off.as<uint64_t>(), e->n_cus, st,
                           sort_units ? e->d_units.as<Unit>() : nullptr,
-                          e->d_term_len.as<uint32_t>(), (e->build_flags & GFT_POS_END) ? 1u : 0u),
+                          e->d_tabs.dfa.term_len.as<uint32_t>(), (e->build_flags & GFT_POS_END) ? 1u : 0u),
             "gather");
     e->csr_valid = true;
     return GFT_OK;
@@ -376,43 +355,47 @@ void fill_window(const gft_engine* e, const ScanBatch& b, Params& P) {
 
 // The waves of a launch over `work` items (units; chunks for scan4): every wave of the grid owns a slab from the start
 uint64_t grid_waves(const gft_engine* e, uint64_t work) {
-    const uint64_t wpw = e->scan_waves;
+    const uint64_t wpw = e->plan.scan_waves;
     return std::min<uint64_t>(std::max<uint64_t>((work + wpw - 1) / wpw, 1), e->n_cus) * wpw;
 }
 // the smallest slab of scan2 / scan3 / scan5 (scan4 sizes its slabs from a chunk's need)
 constexpr uint64_t slab_floor(ScanKernel k) { return k == ScanKernel::scan3 ? 2 * kScan3MinRoom : 64; }
 // ... and their slab: the slack is at most one slab per resident wave, keep it below half the pool
 uint32_t slab_size(const gft_engine* e) {
-    const uint64_t n_waves = (uint64_t)e->n_cus * e->scan_waves;
-    return (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(slab_floor(e->kernel), e->pool_cap / (2 * n_waves)));
+    const uint64_t n_waves = (uint64_t)e->n_cus * e->plan.scan_waves;
+    return (uint32_t)std::min<uint64_t>(kScan2Slab, std::max<uint64_t>(slab_floor(e->plan.kernel), e->pool_cap / (2 * n_waves)));
 }
 
 ScanParams dfa_params(const gft_engine* e, const ScanBatch& b) {
     ScanParams P;
     fill_common(e, b, P);
-    P.byte_class = e->d_byte_class.as<uint8_t>(); P.delta = e->d_delta.as<uint32_t>();
-    P.out_term = e->d_out_term.as<uint32_t>(); P.out_link = e->d_out_link.as<uint32_t>();
-    P.term_len = e->d_term_len.as<uint32_t>();
-    P.n_classes = e->tab.n_classes; P.n_states = e->tab.n_states; P.n_lds_states = e->n_lds_states;
-    P.max_term_len = e->tab.max_term_len;
+    const AcTables& tab = e->tables.tab;
+    const auto& d = e->d_tabs.dfa;
+    P.byte_class = d.byte_class.as<uint8_t>(); P.delta = d.delta.as<uint32_t>();
+    P.out_term = d.out_term.as<uint32_t>(); P.out_link = d.out_link.as<uint32_t>();
+    P.term_len = d.term_len.as<uint32_t>();
+    P.n_classes = tab.n_classes; P.n_states = tab.n_states; P.n_lds_states = e->plan.n_lds_states;
+    P.max_term_len = tab.max_term_len;
     return P;
 }
 
 Scan3Params scan3_params(const gft_engine* e, const ScanBatch& b) {
     Scan3Params P;
     fill_window(e, b, P);
-    P.cls = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
-    P.filter = e->d_s3_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s3.filter.size();
-    P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
-    P.srec = e->d_s3_srec.as<uint32_t>(); P.srec_words = (uint32_t)e->s3.srec.size();
-    P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
-    P.srec_big = e->d_s3_srec_big.as<uint32_t>();
-    P.bloom = e->d_s3_bloom.as<uint32_t>(); P.bloom_lg = e->s3.bloom_lg; P.bloom_lds = e->s3.bloom_lg <= kScan3BloomLdsLg ? 1 : 0;
-    P.slots = e->d_s3_slots.as<Scan2Slot>(); P.slot_shift = e->s3.slot_shift; P.slot_seed = e->s3.slot_seed;
-    P.more = e->d_s3_more.as<Scan2Slot>();
-    P.term_blob = e->d_s3_term_blob.as<uint8_t>(); P.term_off = e->d_s3_term_off.as<uint32_t>();
-    P.G = e->s3.G; P.grouped = e->s3.grouped ? 1 : 0;
-    P.cand_cap = e->scan3_cand_cap;
+    const Scan3Tables& s3 = e->tables.s3;
+    const auto& d = e->d_tabs.s3;
+    P.cls = P.fold ? d.cls_fold.as<uint8_t>() : d.cls.as<uint8_t>();
+    P.filter = d.filter.as<uint32_t>(); P.filter_words = (uint32_t)s3.filter.size();
+    P.short3 = d.short3.as<uint8_t>(); P.short3_bytes = (uint32_t)s3.short3.size();
+    P.srec = d.srec.as<uint32_t>(); P.srec_words = (uint32_t)s3.srec.size();
+    P.short3_big = s3.short3_big.empty() ? nullptr : d.short3_big.as<uint32_t>();
+    P.srec_big = d.srec_big.as<uint32_t>();
+    P.bloom = d.bloom.as<uint32_t>(); P.bloom_lg = s3.bloom_lg; P.bloom_lds = s3.bloom_lg <= kScan3BloomLdsLg ? 1 : 0;
+    P.slots = d.slots.as<Scan2Slot>(); P.slot_shift = s3.slot_shift; P.slot_seed = s3.slot_seed;
+    P.more = d.more.as<Scan2Slot>();
+    P.term_blob = d.term_blob.as<uint8_t>(); P.term_off = d.term_off.as<uint32_t>();
+    P.G = s3.G; P.grouped = s3.grouped ? 1 : 0;
+    P.cand_cap = e->plan.scan3_cand_cap;
     P.slab = slab_size(e);
     return P;
 }
@@ -421,18 +404,21 @@ Scan3Params scan3_params(const gft_engine* e, const ScanBatch& b) {
 Scan2Params scan2_params(const gft_engine* e, const ScanBatch& b) {
     Scan2Params P;
     fill_window(e, b, P);
-    P.filter = e->d_s2_filter.as<uint32_t>(); P.filter_words = (uint32_t)e->s2.filter.size();
-    P.hashed = e->s2.hashed ? 1 : 0; P.hash_shift = e->s2.hash_shift;
-    P.short3 = e->d_s2_short3.as<uint8_t>(); P.short3_bytes = e->scan2_short3_bytes;
-    P.fpt = e->d_s2_fpt.as<uint8_t>(); P.fpt_lg = e->s2.fpt_lg;
-    P.shorts_packed = e->d_s2_shorts_packed.as<uint32_t>(); P.shorts_words = (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
-    P.short3_big = e->s2.short3_big.empty() ? nullptr : e->d_s2_short3_big.as<uint32_t>();
-    P.cand_cap = e->scan2_cand_cap;
-    P.slots = e->d_s2_slots.as<Scan2Slot>(); P.slot_shift = e->s2.slot_shift; P.slot_seed = e->s2.slot_seed;
-    P.more = e->d_s2_more.as<Scan2Slot>();
-    P.cls = P.fold ? e->d_s2_cls_fold.as<uint8_t>() : e->d_s2_cls.as<uint8_t>();
-    P.term_blob = e->d_s2_term_blob.as<uint8_t>(); P.term_off = e->d_s2_term_off.as<uint32_t>();
-    P.kp = e->s2.kp; P.pad_class = e->s2.pad_class;
+    const Scan2Tables& s2 = e->tables.s2;
+    const Scan3Tables& s3 = e->tables.s3;
+    const gft_engine::TableBufs& d = e->d_tabs;
+    P.filter = d.s2.filter.as<uint32_t>(); P.filter_words = (uint32_t)s2.filter.size();
+    P.hashed = s2.hashed ? 1 : 0; P.hash_shift = s2.hash_shift;
+    P.short3 = d.s2.short3.as<uint8_t>(); P.short3_bytes = (uint32_t)s2.short3.size();
+    P.fpt = d.s2.fpt.as<uint8_t>(); P.fpt_lg = s2.fpt_lg;
+    P.shorts_packed = d.s2.shorts_packed.as<uint32_t>(); P.shorts_words = (uint32_t)std::min<size_t>(s2.shorts_packed.size(), 255 * 3);
+    P.short3_big = s2.short3_big.empty() ? nullptr : d.s2.short3_big.as<uint32_t>();
+    P.cand_cap = e->plan.scan2_cand_cap;
+    P.slots = d.s2.slots.as<Scan2Slot>(); P.slot_shift = s2.slot_shift; P.slot_seed = s2.slot_seed;
+    P.more = d.s2.more.as<Scan2Slot>();
+    P.cls = P.fold ? d.s2.cls_fold.as<uint8_t>() : d.s2.cls.as<uint8_t>();
+    P.term_blob = d.s2.term_blob.as<uint8_t>(); P.term_off = d.s2.term_off.as<uint32_t>();
+    P.kp = s2.kp; P.pad_class = s2.pad_class;
     // the balanced path serves both callers: the solver reads presence / successor positions in any order, and
     // CSR results are put into emission order by the gather (k_gather_sorted).  GFT_SCAN_ORDERED=1 sends every unit
     // through the kernel's per-lane staging path (normally the fallback for units whose matches overflow the LDS
@@ -440,37 +426,37 @@ Scan2Params scan2_params(const gft_engine* e, const ScanBatch& b) {
     P.ordered = (b.need_csr && e->opt_scan_ordered) ? 1 : 0;
     P.dbg_counters = (P.dbg & (2 | 64)) ? e->d_dbg.as<uint64_t>() : nullptr;
     P.slab = slab_size(e);
-    if (e->kernel == ScanKernel::scan4) {
+    if (e->plan.kernel == ScanKernel::scan4) {
         // the streaming form: chunks of up to eight units (fewer when the batch is small: every wave should get several
         // chunks), a fifo in place of the candidate list, per-unit regions sized from the density seen so far
-        const uint64_t n_waves = (uint64_t)e->n_cus * e->scan_waves;
+        const uint64_t n_waves = (uint64_t)e->n_cus * e->plan.scan_waves;
         P.chunk_units = (uint32_t)std::min<uint64_t>(kScan4ChunkUnits, std::max<uint64_t>(1, b.n_docs / (n_waves * 4)));
         if (e->opt_scan4_chunk) P.chunk_units = std::min<uint32_t>(e->opt_scan4_chunk, kScan4ChunkUnits);      // (GFT_SCAN4_CHUNK: tests)
-        P.cand_cap = e->scan4_fifo[P.want_pos ? 1 : 0];
+        P.cand_cap = e->plan.scan4_fifo[P.want_pos ? 1 : 0];
         P.bound_q16 = (uint32_t)std::min<double>(e->scan4_density * 1.6 * 65536.0 + 1.0, 4.0e9);
         P.bound_add = 48;
         P.round_c = e->opt_scan4_round ? std::min<uint32_t>(64, std::max<uint32_t>(16, e->opt_scan4_round & ~15u)) : 64;   // (GFT_SCAN4_ROUND: timing studies)
         // a slab should hold a few chunks' regions (the rest of a slab that the next chunk does not fit is lost)
         const uint64_t chunk_need = (uint64_t)P.chunk_units * (((uint64_t)b.unit_max * P.bound_q16 >> 16) + P.bound_add);
         P.slab = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(kScan2Slab, 4 * chunk_need), std::max<uint64_t>(chunk_need, e->pool_cap / (2 * n_waves)));
-    } else if (e->kernel == ScanKernel::scan5) {
+    } else if (e->plan.kernel == ScanKernel::scan5) {
         // one filter probe per two bytes: scan2's tables behind the 3-gram filter over merged classes
-        P.s5_filter = e->d_s5_filter.as<uint64_t>(); P.s5_dual = (uint32_t)e->s5.filter.size();
-        P.s5_grp = P.fold ? e->d_s5_grp_fold.as<uint8_t>() : e->d_s5_grp.as<uint8_t>();
+        P.s5_filter = d.s5.filter.as<uint64_t>(); P.s5_dual = (uint32_t)e->s5.filter.size();
+        P.s5_grp = P.fold ? d.s5.grp_fold.as<uint8_t>() : d.s5.grp.as<uint8_t>();
         P.s5_G = e->s5.G; P.s5_pad_g = e->s5.pad_group;
-        P.s5_fifo_cap = e->s5plan.fifo_cap; P.cand_cap = e->s5plan.cand_cap;
+        P.s5_fifo_cap = e->plan.s5plan.fifo_cap; P.cand_cap = e->plan.s5plan.cand_cap;
         P.s5_sG = 0; P.s5_sgrp = nullptr; P.s5_srec_big = nullptr;
-        if (e->s5_short_groups) {
+        if (e->plan.s5_short_groups) {
             // more than 32 byte classes: the short terms through the group-indexed tables of scan3's set
-            P.short3 = e->d_s3_short3.as<uint8_t>(); P.short3_bytes = (uint32_t)e->s3.short3.size();
-            P.shorts_packed = e->d_s3_srec.as<uint32_t>(); P.shorts_words = (uint32_t)e->s3.srec.size();
-            P.short3_big = e->s3.short3_big.empty() ? nullptr : e->d_s3_short3_big.as<uint32_t>();
-            P.s5_srec_big = e->d_s3_srec_big.as<uint32_t>();
-            P.s5_sgrp = P.fold ? e->d_s3_cls_fold.as<uint8_t>() : e->d_s3_cls.as<uint8_t>();
-            P.s5_sG = e->s3.G;
+            P.short3 = d.s3.short3.as<uint8_t>(); P.short3_bytes = (uint32_t)s3.short3.size();
+            P.shorts_packed = d.s3.srec.as<uint32_t>(); P.shorts_words = (uint32_t)s3.srec.size();
+            P.short3_big = s3.short3_big.empty() ? nullptr : d.s3.short3_big.as<uint32_t>();
+            P.s5_srec_big = d.s3.srec_big.as<uint32_t>();
+            P.s5_sgrp = P.fold ? d.s3.cls_fold.as<uint8_t>() : d.s3.cls.as<uint8_t>();
+            P.s5_sG = s3.G;
         }
-        P.s5_term_bits = e->s5_term_bits; P.s5_pos_bias = e->s5_pos_bias;
-        P.s5_bloom = e->s5_bloom_lg ? e->d_s5_bloom.as<uint32_t>() : nullptr; P.s5_bloom_lg = e->s5_bloom_lg;
+        P.s5_term_bits = e->plan.s5_term_bits; P.s5_pos_bias = e->plan.s5_pos_bias;
+        P.s5_bloom = e->plan.s5_bloom_lg ? d.s5.bloom.as<uint32_t>() : nullptr; P.s5_bloom_lg = e->plan.s5_bloom_lg;
     }
     return P;
 }
@@ -478,7 +464,7 @@ Scan2Params scan2_params(const gft_engine* e, const ScanBatch& b) {
 // Puts the engine's scan kernel on the stream once, over the whole pool as it is now; L learns what the launch owned.
 int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
     hipStream_t st = e->stream;
-    const ScanKernel k = e->kernel;
+    const ScanKernel k = e->plan.kernel;
     ScanParams Pd; Scan3Params P3; Scan2Params P2;
     uint64_t work = b.n_units, slab = 0;
     L.ordered = false;
@@ -499,9 +485,9 @@ int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
     {
         ProfScope ps(e, "scan");
         HIP_TRY(k == ScanKernel::dfa     ? launch_scan_units(Pd, e->n_cus, st)
-                : k == ScanKernel::scan2 ? launch_scan2(P2, e->scan_waves, e->n_cus, st)
-                : k == ScanKernel::scan3 ? launch_scan3(P3, e->scan_waves, e->n_cus, st)
-                : k == ScanKernel::scan4 ? launch_scan4(P2, e->scan_waves, e->n_cus, st)
+                : k == ScanKernel::scan2 ? launch_scan2(P2, e->plan.scan_waves, e->n_cus, st)
+                : k == ScanKernel::scan3 ? launch_scan3(P3, e->plan.scan_waves, e->n_cus, st)
+                : k == ScanKernel::scan4 ? launch_scan4(P2, e->plan.scan_waves, e->n_cus, st)
                                          : launch_scan5(P2, e->n_cus, st), "scan kernel launch");
     }
     if (on_scan2_tables(k) && (e->opt_scan_dbg & 64)) {
@@ -511,7 +497,7 @@ int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
         uint64_t t[16];
         HIP_TRY(hipMemcpyAsync(t, e->d_dbg.p, sizeof t, hipMemcpyDeviceToHost, st), "debug read-back");
         HIP_TRY(hipStreamSynchronize(st), "debug read-back");
-        if (k == ScanKernel::scan5) fprintf(stderr, "[gft scan debug] scan5 (G=%u, list %u):\n", e->s5.G, e->s5plan.cand_cap);
+        if (k == ScanKernel::scan5) fprintf(stderr, "[gft scan debug] scan5 (G=%u, list %u):\n", e->s5.G, e->plan.s5plan.cand_cap);
         if (k == ScanKernel::scan4)
             fprintf(stderr, "[gft scan debug] scan4 wave cycles per unit: chunk set-up %.0f, filter %.0f, queue push %.0f, stage A issue %.0f, stage A %.0f, stage B %.0f, flush %.0f, unit records %.0f\n",
                     (double)t[4] / n_units, (double)t[5] / n_units, (double)t[6] / n_units, (double)t[7] / n_units, (double)t[8] / n_units,
@@ -532,11 +518,11 @@ int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
 void learn_from_batch(gft_engine* e, const ScanLaunch& L, uint64_t total, uint64_t text_lo, uint64_t text_hi) {
     if (text_hi <= text_lo) return;
     const double per_byte = (double)total / (double)(text_hi - text_lo);
-    if (e->kernel == ScanKernel::scan4) e->scan4_density = std::max(0.002, per_byte);
-    if (on_scan2_tables(e->kernel) && !L.ordered) {
+    if (e->plan.kernel == ScanKernel::scan4) e->scan4_density = std::max(0.002, per_byte);
+    if (on_scan2_tables(e->plan.kernel) && !L.ordered) {
         // a unit's matches should fit the wave's LDS fifo: a unit of maximal size should fill ~75 % of it (dense
         // dictionaries -> smaller units; results do not depend on the unit size)
-        const double want = per_byte > 0 ? 0.75 * (e->kernel == ScanKernel::scan5 ? e->s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
+        const double want = per_byte > 0 ? 0.75 * (e->plan.kernel == ScanKernel::scan5 ? e->plan.s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
         const uint32_t um = want >= kScan2UnitMax ? kScan2UnitMax : (uint32_t)want & ~255u;
         e->scan2_unit_max = std::max<uint32_t>(512, um);
     }
@@ -569,11 +555,11 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         e->last_text_lo = e->last_text_hi = 0;
         return GFT_OK;
     }
-    const uint32_t warm = e->tab.max_term_len ? e->tab.max_term_len - 1 : 0;
+    const uint32_t warm = e->tables.tab.max_term_len ? e->tables.tab.max_term_len - 1 : 0;
     // gft_scan2: a unit's matches should fit the wave's LDS fifo (kScan2FifoCap), so the unit size follows the match
     // density the previous call saw (dense dictionaries -> smaller units); results do not depend on it
-    const uint32_t unit_max = e->kernel == ScanKernel::scan3 ? kScan3UnitMax : e->kernel == ScanKernel::scan4 ? kScan4UnitMax
-                              : on_scan2_tables(e->kernel) ? e->scan2_unit_max : kTextBuf - warm;
+    const uint32_t unit_max = e->plan.kernel == ScanKernel::scan3 ? kScan3UnitMax : e->plan.kernel == ScanKernel::scan4 ? kScan4UnitMax
+                              : on_scan2_tables(e->plan.kernel) ? e->scan2_unit_max : kTextBuf - warm;
 
     // 1. work units
     HIP_TRY(e->d_ctl.ensure(64), "control alloc");
@@ -668,7 +654,7 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     }
 
     // 2. automaton walk into the slab pool; grow the pool and re-run if it overflowed (never truncate)
-    const ScanKernel k = e->kernel;
+    const ScanKernel k = e->plan.kernel;
     if (L.deferred) L.pool_cap = e->pool_cap;
     int rc = L.deferred ? GFT_OK : ensure_pool(e, std::max<uint64_t>(1u << 20, (text_hi - text_lo) / 16));
     if (!rc && !L.deferred && counts_slabs(k)) {
@@ -772,7 +758,7 @@ bool pend_settled(const gft_engine* e) {
 int unique_pipeline(gft_engine* e, uint64_t n_docs, uint64_t* n_matches) {
     if (!n_docs) return GFT_OK;
     hipStream_t st = e->stream;
-    const uint32_t n_terms = std::max<uint32_t>((uint32_t)e->tab.terms.size(), 1);
+    const uint32_t n_terms = std::max<uint32_t>((uint32_t)e->tables.tab.terms.size(), 1);
     // as many workgroups as 256 MB of first-occurrence rows allow, at most 4 per CU
     const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(n_docs, (uint64_t)e->n_cus * 4), (256ull << 20) / ((uint64_t)n_terms * 4)));
     HIP_TRY(e->d_uq_first.ensure((size_t)grid * n_terms * 4), "unique alloc");
@@ -830,7 +816,7 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     S.unit_start = e->d_unit_start.as<uint64_t>(); S.unit_count = e->d_unit_count.as<uint32_t>();
     S.units = e->d_units.as<Unit>();
     S.has_rare = e->progs.n_rare_words > 0 ? 1u : 0u;
-    S.pos_back = (e->build_flags & GFT_POS_END) ? 0u : (e->tab.max_term_len ? e->tab.max_term_len - 1 : 0u);
+    S.pos_back = (e->build_flags & GFT_POS_END) ? 0u : (e->tables.tab.max_term_len ? e->tables.tab.max_term_len - 1 : 0u);
     S.term = e->d_pool_term.as<uint32_t>(); S.pos = e->d_pool_pos.as<uint32_t>();
     S.x_off = d_extra ? d_extra->off : nullptr;
     S.x_slot = d_extra ? d_extra->slot : nullptr;
@@ -842,7 +828,7 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     S.order = d.order.as<uint32_t>(); S.blk_class = d.blk_class.as<uint32_t>(); S.wave_blk = d.wave_blk.as<uint32_t>();
     S.fprog_t = d.fprog_t.as<uint32_t>(); S.fblk_off = d.fblk_off.as<uint32_t>();
     S.n_exprs = e->n_exprs;
-    S.n_slots = (uint32_t)e->tab.terms.size() + e->n_extra + 1;
+    S.n_slots = (uint32_t)e->tables.tab.terms.size() + e->n_extra + 1;
     S.tile_words = std::min<uint32_t>(kSolveTileWords, (e->n_exprs + 31) / 32);
     S.bitmap = d_bitmap;
     S.p_scratch = nullptr;
@@ -918,7 +904,7 @@ void plan_host(const gft_engine* e, const gft_extra_matches* extra, uint64_t n_d
     plan.all_docs = !e->progs.host_only.empty();
     plan.irregular.clear();
     if (!extra || !extra->off || e->progs.inord_exprs.empty() || !n_docs) return;
-    const uint32_t n_terms = (uint32_t)e->tab.terms.size();
+    const uint32_t n_terms = (uint32_t)e->tables.tab.terms.size();
     std::vector<std::pair<uint32_t, uint32_t>> seen;          // (slot, last position) of this document: a handful
     for (uint64_t d = 0; d < n_docs; d++) {
         seen.clear();
@@ -1010,111 +996,7 @@ int host_eval(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, co
 
 }  // namespace
 
-// ---- compiled tables as one blob (BuildEngine for a large dictionary is paid once) -----------------
 namespace {
-constexpr uint32_t kTablesMagic = 0x54544647u;   // "GFTT"
-constexpr uint32_t kTablesVersion = 9;           // bump when a table layout or a hash function changes
-
-struct Writer {
-    std::vector<uint8_t> b;
-    void raw(const void* p, size_t n) { const uint8_t* q = (const uint8_t*)p; b.insert(b.end(), q, q + n); }
-    void u32(uint32_t v) { raw(&v, 4); }
-    void u64(uint64_t v) { raw(&v, 8); }
-    template <class T> void vec(const std::vector<T>& v) { u64(v.size()); if (!v.empty()) raw(v.data(), v.size() * sizeof(T)); }
-};
-struct Reader {
-    const uint8_t* p; uint64_t n, i = 0; bool ok = true;
-    bool raw(void* d, size_t k) { if (!ok || k > n - i) { ok = false; return false; } memcpy(d, p + i, k); i += k; return true; }
-    uint32_t u32() { uint32_t v = 0; raw(&v, 4); return v; }
-    uint64_t u64() { uint64_t v = 0; raw(&v, 8); return v; }
-    template <class T> void vec(std::vector<T>& v) {
-        const uint64_t k = u64();
-        if (!ok || k > (n - i) / sizeof(T)) { ok = false; return; }
-        v.resize((size_t)k);
-        if (k) raw(v.data(), (size_t)k * sizeof(T));
-    }
-};
-// Every index a kernel follows must stay inside the table it indexes: a blob that passes the checksum may still be stale
-// (another library build) or crafted.  Returns what is wrong, or nullptr.
-const char* validate_tables(const AcTables& a, const Scan2Tables& t, const Scan3Tables& u) {
-    const size_t n_terms = a.terms.size();
-    if (a.n_classes == 0 || a.n_classes > 256) return "class count";
-    for (int b = 0; b < 256; b++) if (a.byte_class[b] >= a.n_classes) return "byte class";
-    for (uint32_t d : a.delta) if ((d & ~kOutFlag) >= a.n_states) return "DFA target";
-    for (uint32_t x : a.out_term) if (x != kNoTerm && x >= n_terms) return "DFA output term";
-    for (uint32_t x : a.out_link) if (x >= a.n_states) return "DFA output link";
-    for (size_t i = 0; i < n_terms; i++) if (a.term_len[i] != a.terms[i].size()) return "term length";
-    auto slots_ok = [&](const std::vector<Scan2Slot>& slots, const std::vector<Scan2Slot>& more, uint32_t shift, const std::vector<uint8_t>& blob,
-                        const std::vector<uint32_t>& off) -> const char* {
-        if (shift < 1 || shift > 31 || slots.size() != ((size_t)1 << (32 - shift))) return "bucket table size";
-        if (off.size() != n_terms + 1) return "term offsets";
-        for (size_t i = 0; i < n_terms; i++)
-            if (off[i] < 4 || (uint64_t)off[i] + a.terms[i].size() + 8 > blob.size()) return "term offset";
-        auto entry_ok = [&](const Scan2Slot& s) {
-            const uint32_t len1 = s.len & kScan2LenMask;
-            const int off8 = (int)(int8_t)(s.len >> 24);
-            return s.info < n_terms && off8 >= -1 && off8 <= (int)kScan2MaxOff && (int64_t)len1 + off8 == (int64_t)a.terms[s.info].size() && len1 >= 4;
-        };
-        for (const Scan2Slot& s : slots) {
-            if (s.key == kScan2EmptyKey) continue;
-            if (s.info & kScan2Multi) {
-                const uint64_t at = s.info & ~kScan2Multi;
-                if (at + s.len > more.size() || s.len == 0) return "bucket list";
-            } else if (!entry_ok(s)) return "bucket entry";
-        }
-        for (const Scan2Slot& s : more) if (s.key != kScan2EmptyKey && !entry_ok(s)) return "bucket list entry";
-        return nullptr;
-    };
-    if (t.supported) {
-        if (t.kp == 0 || t.kp > 256 || t.pad_class >= t.kp) return "scan2 classes";
-        for (int b = 0; b < 256; b++) if (t.cls[b] >= t.kp || t.cls_fold[b] >= t.kp) return "scan2 byte class";
-        // build_scan5_tables (run on imported tables too) indexes its class counters by the automaton's byte classes and splits
-        // every bucket key into four classes: the two class maps must be one, and a key must be four classes
-        if (t.kp != a.n_classes) return "scan2 class count differs from the automaton's";
-        for (int b = 0; b < 256; b++) if (t.cls[b] != a.byte_class[b]) return "scan2 byte class differs from the automaton's";
-        // (a key lives in ITS pair of the bucket table and nowhere else: the kernels look nowhere else)
-        if (t.slot_shift < 1 || t.slot_shift > 31) return "bucket table size";
-        for (size_t i = 0; i < t.slots.size(); i++)
-            if (t.slots[i].key != kScan2EmptyKey && (scan2_pair_slot(t.slots[i].key, 0, t.slot_shift, t.slot_seed) | 1u) != ((uint32_t)i | 1u)) return "bucket placement";
-        {
-            const uint64_t kp4 = (uint64_t)t.kp * t.kp * t.kp * t.kp;
-            for (const Scan2Slot& s : t.slots) if (s.key != kScan2EmptyKey && s.key >= kp4) return "bucket key";
-            for (const Scan2Slot& s : t.more) if (s.key != kScan2EmptyKey && s.key >= kp4) return "bucket list key";
-        }
-        if (t.hashed ? (t.hash_shift < 1 || t.hash_shift > 31 || t.filter_bits != (1u << (32 - t.hash_shift)))
-                     : (uint64_t)t.kp * t.kp * t.kp * t.kp > t.filter_bits) return "scan2 filter size";
-        if (!t.short3.empty() && t.short3.size() < (uint64_t)t.kp * t.kp * t.kp) return "scan2 short3 size";
-        if (!t.short3_big.empty() && t.short3_big.size() != t.short3.size()) return "scan2 short3_big size";
-        if (t.shorts_packed.size() != t.shorts.size() * 3) return "scan2 short records";
-        for (uint8_t id : t.short3) if (id != 255 && id >= t.shorts.size()) return "scan2 short record id";
-        for (uint32_t id : t.short3_big) if (id >= t.shorts.size()) return "scan2 short record id";
-        for (uint32_t w : t.shorts_packed) if (w && ((w & 0x0FFFFFFFu) >= n_terms || (w >> 28) > 3)) return "scan2 short record";
-        if (const char* why = slots_ok(t.slots, t.more, t.slot_shift, t.term_blob, t.term_off)) return why;
-    }
-    if (u.supported) {
-        if (u.G == 0 || u.G > kScan3Groups) return "scan3 groups";
-        const uint64_t G3 = (uint64_t)u.G * u.G * u.G;
-        for (int b = 0; b < 256; b++) if (u.cls[b] >= u.G || u.cls_fold[b] >= u.G) return "scan3 byte group";
-        if (u.filter.size() != (size_t)((G3 * u.G + 31) / 32)) return "scan3 filter size";
-        if (!u.short3.empty() && (u.short3.size() < G3 || u.short3.size() % 16)) return "scan3 short3 size";
-        if (!u.short3_big.empty() && u.short3_big.size() != u.short3.size()) return "scan3 short3_big size";
-        if (u.srec.size() % kScan3RecWords || u.srec.empty() || u.srec.size() / kScan3RecWords > kScan3RecLds + 1) return "scan3 records";
-        for (uint8_t id : u.short3) if (id != 255 && id >= u.srec.size() / kScan3RecWords) return "scan3 record id";
-        for (size_t i = 0; i < u.short3.size(); i++) if (u.short3[i] == 255 && (u.short3_big.empty() || u.short3_big[i] >= u.srec_big.size())) return "scan3 big record";
-        for (size_t i = 0; i < u.srec.size(); i += 2) if (u.srec[i] && ((u.srec[i] & 0x0FFFFFFFu) >= n_terms || (u.srec[i] >> 28) > 3)) return "scan3 record entry";
-        for (size_t at = 0; at < u.srec_big.size();) {
-            const uint64_t n = u.srec_big[at];
-            if (at + 1 + 2 * n > u.srec_big.size()) return "scan3 big record length";
-            for (uint64_t j = 0; j < n; j++) { const uint32_t w = u.srec_big[at + 1 + 2 * j]; if (w && ((w & 0x0FFFFFFFu) >= n_terms || (w >> 28) > 3)) return "scan3 big record entry"; }
-            at += 1 + 2 * n;
-        }
-        if (u.bloom_lg < 1 || u.bloom_lg > 28 || u.bloom.size() != ((size_t)1 << u.bloom_lg)) return "scan3 bloom size";
-        if (const char* why = slots_ok(u.slots, u.more, u.slot_shift, u.term_blob, u.term_off)) return why;
-    }
-    return nullptr;
-}
-
-
 void destroy_multi(gft_engine* e);
 // multi-device dispatch (definitions behind the single-device entry points)
 int multi_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
@@ -1175,15 +1057,16 @@ void gft_engine_destroy(gft_engine* e) {
         for (auto& kv : e->prof)
             for (auto& p : kv.second.ev) { e->prof_pool.push_back(p.first); e->prof_pool.push_back(p.second); }
         for (hipEvent_t ev : e->prof_pool) (void)hipEventDestroy(ev);
-        DevBuf* all[] = {&e->d_byte_class, &e->d_delta, &e->d_out_term, &e->d_out_link, &e->d_term_len, &e->d_progs.prog,
+        gft_engine::TableBufs& t = e->d_tabs;
+        DevBuf* all[] = {&t.dfa.byte_class, &t.dfa.delta, &t.dfa.out_term, &t.dfa.out_link, &t.dfa.term_len, &e->d_progs.prog,
                          &e->d_progs.prog_off, &e->d_progs.fprog, &e->d_progs.fprog_off, &e->d_progs.groups, &e->d_progs.order, &e->d_progs.blk_class, &e->d_progs.wave_blk,
-                         &e->d_progs.fprog_t, &e->d_progs.fblk_off, &e->d_progs.wide_list, &e->d_wide_slot, &e->d_wide_theta, &e->d_pscratch, &e->d_solve_dbg, &e->d_s2_filter,
-                         &e->d_s2_slots, &e->d_s2_more, &e->d_s2_cls, &e->d_s2_cls_fold, &e->d_s2_term_blob,
-                         &e->d_s2_term_off, &e->d_ctl, &e->d_dbg, &e->d_s2_short3, &e->d_s2_shorts_packed, &e->d_s2_short3_big, &e->d_s2_fpt,
-                         &e->d_s3_filter, &e->d_s3_short3, &e->d_s3_srec, &e->d_s3_short3_big, &e->d_s3_srec_big, &e->d_s3_bloom, &e->d_s3_slots,
-                         &e->d_s3_more, &e->d_s3_cls, &e->d_s3_cls_fold, &e->d_s3_term_blob, &e->d_s3_term_off,
-                         &e->d_s5_grp, &e->d_s5_grp_fold, &e->d_s5_filter, &e->d_s5_bloom,
-&e->d_unit_cnt, &e->d_unit_base, &e->d_units, &e->d_partial,
+                         &e->d_progs.fprog_t, &e->d_progs.fblk_off, &e->d_progs.wide_list, &e->d_wide_slot, &e->d_wide_theta, &e->d_pscratch, &e->d_solve_dbg, &t.s2.filter,
+                         &t.s2.slots, &t.s2.more, &t.s2.cls, &t.s2.cls_fold, &t.s2.term_blob,
+                         &t.s2.term_off, &e->d_ctl, &e->d_dbg, &t.s2.short3, &t.s2.shorts_packed, &t.s2.short3_big, &t.s2.fpt,
+                         &t.s3.filter, &t.s3.short3, &t.s3.srec, &t.s3.short3_big, &t.s3.srec_big, &t.s3.bloom, &t.s3.slots,
+                         &t.s3.more, &t.s3.cls, &t.s3.cls_fold, &t.s3.term_blob, &t.s3.term_off,
+                         &t.s5.grp, &t.s5.grp_fold, &t.s5.filter, &t.s5.bloom,
+                         &e->d_unit_cnt, &e->d_unit_base, &e->d_units, &e->d_partial,
                          &e->d_pool_term, &e->d_pool_pos, &e->d_unit_start, &e->d_unit_count, &e->d_unit_out,
                          &e->d_term, &e->d_pos, &e->d_match_off, &e->d_text, &e->d_doc_off, &e->d_bitmap, &e->d_xoff,
                          &e->d_xslot, &e->d_xpos, &e->d_uq_first, &e->d_uq_cnt, &e->d_uq_off, &e->d_uq_term, &e->d_patch, &e->d_rn_cnt, &e->d_rn_base, &e->d_rn_starts, &e->d_rn_prefix,
@@ -1229,203 +1112,113 @@ int gft_set_cu_margin(gft_engine* e, uint32_t margin) try {
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
-// GFT_SCAN_KERNEL: the kernel the caller asks for ("auto", empty and unset: none)
-enum class Forced { none, dfa, scan2, scan3, scan4, scan5, unknown };
-static Forced forced_scan_kernel() {
-    const char* v = getenv("GFT_SCAN_KERNEL");
-    if (!v || !*v || !std::strcmp(v, "auto")) return Forced::none;
-    for (int k = 0; k < 5; k++)
-        if (!std::strcmp(v, kScanKernelName[k])) return (Forced)(k + 1);     // (ScanKernel's order)
-    return Forced::unknown;
-}
-
-// Does scan5 apply to the compiled tables?  It runs on scan2's long-term tables; a fifo entry of 32 bits holds term id and
-// relative position.  With more than 32 byte classes there is no direct short-term table
-// (Scan2Tables::short_direct): the group-indexed one of scan3's tables serves then (GFT_SCAN5_LARGE=0 leaves such
-// dictionaries to scan3).  Leaves its LDS plan and the shape of its fifo entries and Bloom level in the engine.
-static bool plan_scan5(gft_engine* e) {
-    const bool large = !e->s2.short_direct && e->s3.supported && e->opt_scan5_large;
-    if (!e->s2.long_ok || !(e->s2.supported || large)) return false;
-    uint32_t tb = 1;
-    while ((1ull << tb) < e->tab.terms.size()) tb++;
-    e->s5_term_bits = tb;
-    e->s5_pos_bias = e->tab.max_term_len + kScan2MaxOff;
-    const bool packs = (uint64_t)kScan2UnitMax + e->s5_pos_bias + 8 < (1ull << (32 - tb));
-    const uint32_t short_bytes = large ? (uint32_t)e->s3.short3.size() : (uint32_t)e->s2.short3.size();
-    const uint32_t rec_words = large ? (uint32_t)e->s3.srec.size() : (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3);
-    // a fingerprint table too large for LDS (fpt_lg != 0) gets a Bloom level there instead: 2^lg bits, as large as
-    // GFT_SCAN5_BLOOM_KB allows but not more than eight bits per item would take
-    e->s5_bloom_lg = 0;
-    if (e->s2.fpt_lg && e->opt_scan5_bloom_kb) {
-        uint32_t lg = 13;
-        while ((2u << lg) / 8 <= e->opt_scan5_bloom_kb * 1024u && (1ull << lg) < 8 * e->s2.n_keys) lg++;
-        e->s5_bloom_lg = lg;
-    }
-    bool fits = false;
-    for (int attempt = 0; attempt < 2 && packs && !fits; attempt++) {
-        const uint32_t in_lds = e->s2.fpt_lg ? (e->s5_bloom_lg ? (1u << e->s5_bloom_lg) / 8 : 0u) : kScan2FptSize;
-        fits = scan5_plan(e->s2.kp, short_bytes, rec_words, in_lds, e->lds_max - 512, e->opt_scan5_fifo ? e->opt_scan5_fifo : kScan2FifoCap, &e->s5plan);
-        if (!fits) e->s5_bloom_lg = 0;                      // (no room: without the Bloom level)
-    }
-    if (!fits) return false;
-    if (e->opt_scan5_groups && e->opt_scan5_groups < e->s5plan.G) {      // (tests: more merging than LDS asks for)
-        e->s5plan.G = std::max<uint32_t>(e->opt_scan5_groups, 2);
-        e->s5plan.dual_entries = e->s5plan.G * e->s5plan.G * e->s5plan.G;
-    }
-    e->s5_short_groups = large;
-    return true;
-}
-
-// The scan kernel for the compiled tables in e->tab / s2 / s3 (the table of DESIGN.md 4.7): sets e->kernel, its waves per
-// workgroup and what its LDS plan says; uploads nothing.  scan5 is the default wherever it applies, scan3 (any alphabet)
-// everywhere else; scan2 / scan4 (extra-kernels builds) and the DFA kernel are cross-checks that GFT_SCAN_KERNEL asks for.
-static int choose_scan_kernel(gft_engine* e) {
-    const Forced f = forced_scan_kernel();
-    if (!kExtraKernels && (f == Forced::scan2 || f == Forced::scan4))
-        return fail(e, GFT_E_UNSUPPORTED, std::string("GFT_SCAN_KERNEL=") + kScanKernelName[(int)f - 1] + ": this library was built without the cross-check kernels (GFT_EXTRA_KERNELS=1 python -m gofindthem_amd.build --force)");
-    const size_t lds = e->lds_max - 512;
-    const uint32_t s2_filter = (uint32_t)e->s2.filter.size(), s2_short3 = (uint32_t)e->s2.short3.size(),
-                   s2_recs = (uint32_t)std::min<size_t>(e->s2.shorts_packed.size(), 255 * 3), s2_fpt = e->s2.fpt_lg ? 0u : kScan2FptSize;
-    uint32_t w2 = 0, w3 = 0, w4[2] = {0, 0};
-    const bool k2_fits = e->s2.supported && scan2_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, &w2, &e->scan2_cand_cap);
-    // (scan4's fifo capacities belong to the smaller of the two wave counts; with fewer waves there is only more room)
-    const bool k4_fits = e->s2.supported && scan4_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, false, &w4[0], &e->scan4_fifo[0]) &&
-                         scan4_plan(s2_filter, s2_short3, s2_recs, s2_fpt, lds, true, &w4[1], &e->scan4_fifo[1]);
-    e->scan4_density = 0.06;
-    e->s5_short_groups = false;
-    const bool k5_fits = (f == Forced::none || f == Forced::scan5) && plan_scan5(e);
-    const uint32_t bloom_lds_bytes = e->s3.supported && e->s3.bloom_lg <= kScan3BloomLdsLg ? 4u << e->s3.bloom_lg : 0u;
-    const bool k3_fits = e->s3.supported && scan3_plan((uint32_t)e->s3.filter.size(), (uint32_t)e->s3.short3.size(), (uint32_t)e->s3.srec.size(),
-                                                        bloom_lds_bytes, lds, &w3, &e->scan3_cand_cap);
-    // (scan5 asked for but not applicable: as by default)
-    auto chosen = [e](ScanKernel k, uint32_t waves) { e->kernel = k; e->scan_waves = waves; return GFT_OK; };
-    if (k3_fits && f != Forced::dfa && f != Forced::scan2 && f != Forced::scan4 && (f == Forced::scan3 || !(k5_fits || k2_fits)))
-        return chosen(ScanKernel::scan3, w3);
-    if (f == Forced::scan4 && k2_fits && k4_fits) return chosen(ScanKernel::scan4, std::min(w4[0], w4[1]));
-    if (k5_fits) return chosen(ScanKernel::scan5, kScan5Waves);
-    if (k2_fits && f != Forced::dfa) return chosen(ScanKernel::scan2, w2);
-    return chosen(ScanKernel::dfa, 0);
-}
-
 // scan3's short-term tables, which scan5 reads too over an alphabet too large for scan2's
-static int upload_scan3_short_tables(gft_engine* e) {
-    std::vector<uint8_t> s3v = e->s3.short3, g1(e->s3.cls, e->s3.cls + 256), g2(e->s3.cls_fold, e->s3.cls_fold + 256);
-    if (s3v.empty()) s3v.assign(16, 0);
+static int upload_scan3_short_tables(gft_engine* e, const Scan3Tables& s3) {
+    const std::vector<uint8_t> none(16, 0), g1(s3.cls, s3.cls + 256), g2(s3.cls_fold, s3.cls_fold + 256);
     SyncOnExit drained(e);                              // (the uploads read from these locals)
+    auto& d = e->d_tabs.s3;
     int rc;
-    if ((rc = upload(e, e->d_s3_short3, s3v, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_s3_srec, e->s3.srec, "table upload"))) return rc;
-    if (!e->s3.short3_big.empty() && (rc = upload(e, e->d_s3_short3_big, e->s3.short3_big, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_s3_srec_big, e->s3.srec_big, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_s3_cls, g1, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_s3_cls_fold, g2, "table upload"))) return rc;
+    if ((rc = upload(e, d.short3, s3.short3.empty() ? none : s3.short3, "table upload"))) return rc;
+    if ((rc = upload(e, d.srec, s3.srec, "table upload"))) return rc;
+    if (!s3.short3_big.empty() && (rc = upload(e, d.short3_big, s3.short3_big, "table upload"))) return rc;
+    if ((rc = upload(e, d.srec_big, s3.srec_big, "table upload"))) return rc;
+    if ((rc = upload(e, d.cls, g1, "table upload"))) return rc;
+    if ((rc = upload(e, d.cls_fold, g2, "table upload"))) return rc;
     return GFT_OK;
 }
 
-// e->tab / e->s2 / e->s3 hold compiled tables (from gft_build or gft_import_tables): check them against the device, choose
-// the scan kernel, upload what it reads
-static int install_tables(gft_engine* e, uint32_t flags) {
-    if (e->tab.max_term_len + 1024 > kTextBuf)
-        return fail(e, GFT_E_UNSUPPORTED, "keyword longer than " + std::to_string(kTextBuf - 1024) + " bytes");
-    if (e->tab.n_states >= 0x7FFFFFFFu) return fail(e, GFT_E_UNSUPPORTED, "automaton too large");
-    e->build_flags = flags;
-    refresh_options(e);
-
-    DeviceGuard g(e->device);
-    const size_t fixed = 256 + (size_t)(kScanBlockThreads / 64) * kTextBuf + 1024;
-    if (e->lds_max < fixed + (size_t)e->tab.n_classes * 4)
-        return fail(e, GFT_E_UNSUPPORTED, "device LDS too small for the scan kernel");
-    size_t rows = (e->lds_max - fixed) / ((size_t)e->tab.n_classes * 4);
-    e->n_lds_states = (uint32_t)std::min<size_t>(rows, e->tab.n_states);
-
-    std::vector<uint8_t> bc(e->tab.byte_class, e->tab.byte_class + 256), c1, c2, s5g, s5gf;
-    SyncOnExit drained(e);                              // (declared behind the temporaries the uploads read from: it goes first)
-    int rc;
-    if ((rc = upload(e, e->d_byte_class, bc, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_delta, e->tab.delta, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_out_term, e->tab.out_term, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_out_link, e->tab.out_link, "table upload"))) return rc;
-    if ((rc = upload(e, e->d_term_len, e->tab.term_len, "table upload"))) return rc;
-    if ((rc = choose_scan_kernel(e))) return rc;
-    const ScanKernel k = e->kernel;
+// Installs a compiled set (gft_build's, gft_import_tables', or a copy of the first device's): chooses the scan kernel for
+// this device, derives what it needs on top, uploads what it reads -- all from `set`, which nothing edits -- and commits.
+// A refusal comes before the first upload and leaves the handle as it was; from the first upload until the last has landed
+// the handle is not built, so an upload error gives GFT_E_NOT_BUILT and never a mixture of two dictionaries.
+static int install_tables(gft_engine* e, TableSet&& set, uint32_t flags) {
+    const AcTables& tab = set.tab;
+    const Scan2Tables& s2 = set.s2;
+    const Scan3Tables& s3 = set.s3;
+    ScanPlan plan;
+    int rc = plan_scan(set, scan_options(), e->lds_max, kExtraKernels, plan, e->err);
+    if (rc) return rc;
+    const ScanKernel k = plan.kernel;
+    Scan5Tables s5;
+    std::vector<uint32_t> s5_bloom;
+    if (k == ScanKernel::scan5) derive_scan5(set, plan, s5, s5_bloom);
     const bool build_dbg = getenv("GFT_SCAN_DEBUG") != nullptr;
-    if (k == ScanKernel::scan3) {
-        if ((rc = upload_scan3_short_tables(e))) return rc;
-        if ((rc = upload(e, e->d_s3_filter, e->s3.filter, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_bloom, e->s3.bloom, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_slots, e->s3.slots, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_more, e->s3.more, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_term_blob, e->s3.term_blob, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s3_term_off, e->s3.term_off, "table upload"))) return rc;
-        if (build_dbg)
-            fprintf(stderr, "[gft build debug] scan3: G=%u%s keys=%llu anchors=%llu slots=%zu more=%zu bloom 2^%u (%s) short cells: lds records %zu, big words %zu; waves=%u cand_cap=%u\n",
-                    e->s3.G, e->s3.grouped ? " (merged classes)" : "", (unsigned long long)e->s3.n_keys, (unsigned long long)e->s3.n_anchors,
-                    e->s3.slots.size(), e->s3.more.size(), e->s3.bloom_lg, e->s3.bloom_lg <= kScan3BloomLdsLg ? "LDS" : "global", e->s3.srec.size() / kScan3RecWords - 1,
-                    e->s3.srec_big.size(), e->scan_waves, e->scan3_cand_cap);
+    if (build_dbg && k == ScanKernel::scan3)
+        fprintf(stderr, "[gft build debug] scan3: G=%u%s keys=%llu anchors=%llu slots=%zu more=%zu bloom 2^%u (%s) short cells: lds records %zu, big words %zu; waves=%u cand_cap=%u\n",
+                s3.G, s3.grouped ? " (merged classes)" : "", (unsigned long long)s3.n_keys, (unsigned long long)s3.n_anchors,
+                s3.slots.size(), s3.more.size(), s3.bloom_lg, s3.bloom_lg <= kScan3BloomLdsLg ? "LDS" : "global", s3.srec.size() / kScan3RecWords - 1,
+                s3.srec_big.size(), plan.scan_waves, plan.scan3_cand_cap);
+    if (build_dbg && on_scan2_tables(k)) {
+        size_t n_ff = 0, n_used = 0, n_simple = 0, n_slots = 0;
+        for (uint8_t b : s2.fpt) { n_ff += b == 0xFF; n_used += b != 0; }
+        for (const auto& s : s2.slots) { n_slots += s.key != kScan2EmptyKey; n_simple += s.key != kScan2EmptyKey && !(s.info & kScan2Multi); }
+        fprintf(stderr, "[gft build debug] kp=%u keys=%zu (simple %zu) slots=%zu fpt: used=%zu always-pass=%zu of %u; shorts=%zu filter=%s %u bits waves=%u\n",
+                s2.kp, n_slots, n_simple, s2.slots.size(), n_used, n_ff, (unsigned)s2.fpt.size(), s2.shorts.size() - 1,
+                s2.hashed ? "hashed" : "direct", s2.filter_bits, plan.scan_waves);
+        fprintf(stderr, "[gft build debug] candidate list capacity %u per wave\n", k == ScanKernel::scan5 ? plan.s5plan.cand_cap : plan.scan2_cand_cap);
     }
-    if (on_scan2_tables(k)) {
-        if (build_dbg) {
-            size_t n_ff = 0, n_used = 0, n_simple = 0, n_slots = 0;
-            for (uint8_t b : e->s2.fpt) { n_ff += b == 0xFF; n_used += b != 0; }
-            for (const auto& s : e->s2.slots) { n_slots += s.key != kScan2EmptyKey; n_simple += s.key != kScan2EmptyKey && !(s.info & kScan2Multi); }
-            fprintf(stderr, "[gft build debug] kp=%u keys=%zu (simple %zu) slots=%zu fpt: used=%zu always-pass=%zu of %u; shorts=%zu filter=%s %u bits waves=%u\n",
-                    e->s2.kp, n_slots, n_simple, e->s2.slots.size(), n_used, n_ff, (unsigned)e->s2.fpt.size(), e->s2.shorts.size() - 1,
-                    e->s2.hashed ? "hashed" : "direct", e->s2.filter_bits, e->scan_waves);
-            fprintf(stderr, "[gft build debug] candidate list capacity %u per wave\n", k == ScanKernel::scan5 ? e->s5plan.cand_cap : e->scan2_cand_cap);
-        }
-        if (k == ScanKernel::scan5 && e->s5_short_groups && (rc = upload_scan3_short_tables(e))) return rc;
-        e->scan2_short3_bytes = (uint32_t)e->s2.short3.size();
-        if (e->s2.short3.empty()) e->s2.short3.assign(16, 0);   // placeholder upload; short3_bytes stays 0
-        if ((rc = upload(e, e->d_s2_short3, e->s2.short3, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_shorts_packed, e->s2.shorts_packed, "table upload"))) return rc;
-        if (!e->s2.short3_big.empty() && (rc = upload(e, e->d_s2_short3_big, e->s2.short3_big, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_fpt, e->s2.fpt, "table upload"))) return rc;
-        c1.assign(e->s2.cls, e->s2.cls + 256); c2.assign(e->s2.cls_fold, e->s2.cls_fold + 256);
-        if ((rc = upload(e, e->d_s2_cls, c1, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_cls_fold, c2, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_filter, e->s2.filter, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_slots, e->s2.slots, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_more, e->s2.more, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_term_blob, e->s2.term_blob, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s2_term_off, e->s2.term_off, "table upload"))) return rc;
+    if (build_dbg && k == ScanKernel::scan5) {
+        size_t set_bits = 0;
+        for (uint32_t w : s5_bloom) set_bits += (size_t)__builtin_popcount(w);
+        fprintf(stderr, "[gft build debug] scan5: G=%u of %u classes, filter %zu entries, list %u, term bits %u; Bloom level 2^%u bits, %.1f %% set\n",
+                s5.G, s2.kp, s5.filter.size(), plan.s5plan.cand_cap, plan.s5_term_bits, plan.s5_bloom_lg,
+                plan.s5_bloom_lg ? 100.0 * (double)set_bits / (double)(1ull << plan.s5_bloom_lg) : 0.0);
     }
-    if (k == ScanKernel::scan5) {
-        build_scan5_tables(e->tab, e->s2, e->s5plan.G, e->s5);
-        e->s5_bloom.clear();
-        if (e->s5_bloom_lg) {
-            // one bit per owner of a fingerprint cell, read off the bucket table: (window key, byte in front of the
-            // window with its case bit cleared), or the window key alone where the window is the term's first four bytes
-            e->s5_bloom.assign((size_t)1 << (e->s5_bloom_lg - 5), 0u);
-            auto set = [&](uint32_t h) { e->s5_bloom[h >> 5] |= 1u << (h & 31); };
-            auto add = [&](const Scan2Slot& t) {
-                if ((t.len & kScan2LenMask) == 4) set(scan5_bloom_x(t.key, e->s5_bloom_lg));
-                else set(scan5_bloom_g(t.key, (t.front[0] >> 24) & 0xDFu, e->s5_bloom_lg));
-            };
-            for (const Scan2Slot& sl : e->s2.slots) {
-                if (sl.key == kScan2EmptyKey) continue;
-                if (!(sl.info & kScan2Multi)) { add(sl); continue; }
-                for (uint32_t j = 0; j < sl.len; j++) add(e->s2.more[(sl.info & ~kScan2Multi) + j]);
-            }
-        }
-        s5g.assign(e->s5.grp, e->s5.grp + 256); s5gf.assign(e->s5.grp_fold, e->s5.grp_fold + 256);
-        if ((rc = upload(e, e->d_s5_grp, s5g, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s5_grp_fold, s5gf, "table upload"))) return rc;
-        if ((rc = upload(e, e->d_s5_filter, e->s5.filter, "table upload"))) return rc;
-        if (e->s5_bloom_lg && (rc = upload(e, e->d_s5_bloom, e->s5_bloom, "table upload"))) return rc;
-        if (build_dbg) {
-            size_t set_bits = 0;
-            for (uint32_t w : e->s5_bloom) set_bits += (size_t)__builtin_popcount(w);
-            fprintf(stderr, "[gft build debug] scan5: G=%u of %u classes, filter %zu entries, list %u, term bits %u; Bloom level 2^%u bits, %.1f %% set\n",
-                    e->s5.G, e->s2.kp, e->s5.filter.size(), e->s5plan.cand_cap, e->s5_term_bits, e->s5_bloom_lg,
-                    e->s5_bloom_lg ? 100.0 * (double)set_bits / (double)(1ull << e->s5_bloom_lg) : 0.0);
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream), "table upload");
-    e->built = true;
-    e->scan_valid_docs = ~0ull;
-    e->scan2_unit_max = kScan2UnitMax;
+
+    refresh_options(e);
+    DeviceGuard g(e->device);
+    // (an empty short3 is uploaded as 16 zero bytes; the kernel is told 0 bytes)
+    const std::vector<uint8_t> none(16, 0), bc(tab.byte_class, tab.byte_class + 256), c1(s2.cls, s2.cls + 256), c2(s2.cls_fold, s2.cls_fold + 256);
+    std::vector<uint8_t> s5g, s5gf;
+    if (k == ScanKernel::scan5) { s5g.assign(s5.grp, s5.grp + 256); s5gf.assign(s5.grp_fold, s5.grp_fold + 256); }
+    SyncOnExit drained(e);                              // (declared behind the temporaries the uploads read from: it goes first)
+    e->built = false;
     e->have_programs = false;   // slots refer to the dictionary: programs must be set again
     e->n_exprs = 0;
+    gft_engine::TableBufs& d = e->d_tabs;
+    if ((rc = upload(e, d.dfa.byte_class, bc, "table upload"))) return rc;
+    if ((rc = upload(e, d.dfa.delta, tab.delta, "table upload"))) return rc;
+    if ((rc = upload(e, d.dfa.out_term, tab.out_term, "table upload"))) return rc;
+    if ((rc = upload(e, d.dfa.out_link, tab.out_link, "table upload"))) return rc;
+    if ((rc = upload(e, d.dfa.term_len, tab.term_len, "table upload"))) return rc;
+    if (k == ScanKernel::scan3) {
+        if ((rc = upload_scan3_short_tables(e, s3))) return rc;
+        if ((rc = upload(e, d.s3.filter, s3.filter, "table upload"))) return rc;
+        if ((rc = upload(e, d.s3.bloom, s3.bloom, "table upload"))) return rc;
+        if ((rc = upload(e, d.s3.slots, s3.slots, "table upload"))) return rc;
+        if ((rc = upload(e, d.s3.more, s3.more, "table upload"))) return rc;
+        if ((rc = upload(e, d.s3.term_blob, s3.term_blob, "table upload"))) return rc;
+        if ((rc = upload(e, d.s3.term_off, s3.term_off, "table upload"))) return rc;
+    }
+    if (on_scan2_tables(k)) {
+        if (k == ScanKernel::scan5 && plan.s5_short_groups && (rc = upload_scan3_short_tables(e, s3))) return rc;
+        if ((rc = upload(e, d.s2.short3, s2.short3.empty() ? none : s2.short3, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.shorts_packed, s2.shorts_packed, "table upload"))) return rc;
+        if (!s2.short3_big.empty() && (rc = upload(e, d.s2.short3_big, s2.short3_big, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.fpt, s2.fpt, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.cls, c1, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.cls_fold, c2, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.filter, s2.filter, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.slots, s2.slots, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.more, s2.more, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.term_blob, s2.term_blob, "table upload"))) return rc;
+        if ((rc = upload(e, d.s2.term_off, s2.term_off, "table upload"))) return rc;
+    }
+    if (k == ScanKernel::scan5) {
+        if ((rc = upload(e, d.s5.grp, s5g, "table upload"))) return rc;
+        if ((rc = upload(e, d.s5.grp_fold, s5gf, "table upload"))) return rc;
+        if ((rc = upload(e, d.s5.filter, s5.filter, "table upload"))) return rc;
+        if (plan.s5_bloom_lg && (rc = upload(e, d.s5.bloom, s5_bloom, "table upload"))) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream), "table upload");
+    e->tables = std::move(set);
+    e->plan = plan;
+    e->s5 = std::move(s5);
+    e->build_flags = flags;
+    e->scan_valid_docs = ~0ull;
+    e->scan2_unit_max = kScan2UnitMax;
+    e->scan4_density = 0.06;
+    e->built = true;
     return GFT_OK;
 }
 
@@ -1441,38 +1234,36 @@ int gft_build(gft_engine* e, const uint8_t* terms_blob, const uint64_t* term_off
         if (term_off[i + 1] < term_off[i]) return fail(e, GFT_E_INVALID, "term_off is not ascending");
         terms.emplace_back((const char*)terms_blob + term_off[i], (size_t)(term_off[i + 1] - term_off[i]));
     }
-    e->built = false;
-    build_ac_tables(std::move(terms), e->tab);
-    build_scan2_tables(e->tab, e->s2);     // suffix-window tables (scan2, kept as a cross-check)
-    build_scan3_tables(e->tab, e->s3);     // stride-2 suffix-window tables (the fast path)
-    return install_tables(e, flags);
+    TableSet set;
+    compile_tables(std::move(terms), set);
+    return install_tables(e, std::move(set), flags);
 } GFT_CATCH((e ? &e->err : nullptr))
 
-uint32_t gft_n_terms(const gft_engine* e) { return e ? (uint32_t)e->tab.terms.size() : 0; }
-uint32_t gft_n_states(const gft_engine* e) { return e ? e->tab.n_states : 0; }
+uint32_t gft_n_terms(const gft_engine* e) { return e ? (uint32_t)e->tables.tab.terms.size() : 0; }
+uint32_t gft_n_states(const gft_engine* e) { return e ? e->tables.tab.n_states : 0; }
 uint32_t gft_n_exprs(const gft_engine* e) { return e ? e->n_exprs : 0; }
 uint32_t gft_n_host_exprs(const gft_engine* e) { return e ? (uint32_t)e->progs.host_only.size() : 0; }
 int gft_last_nonascii(const gft_engine* e) { return e && e->last_nonascii ? 1 : 0; }
 const char* gft_build_info(void) { return kExtraKernels ? "gfx950 extra_kernels=1" : "gfx950 extra_kernels=0"; }
 const char* gft_scan_kernel(const gft_engine* e) {
     if (!e || !e->built) return "";
-    return kScanKernelName[(int)e->kernel];
+    return kScanKernelName[(int)e->plan.kernel];
 }
 
 int gft_term(const gft_engine* e, uint32_t term_id, const uint8_t** ptr, uint32_t* len) try {
     if (!e || !ptr || !len) return GFT_E_INVALID;
-    if (term_id >= e->tab.terms.size()) return fail(e, GFT_E_INVALID, "term id out of range");
-    *ptr = (const uint8_t*)e->tab.terms[term_id].data();
-    *len = (uint32_t)e->tab.terms[term_id].size();
+    if (term_id >= e->tables.tab.terms.size()) return fail(e, GFT_E_INVALID, "term id out of range");
+    *ptr = (const uint8_t*)e->tables.tab.terms[term_id].data();
+    *len = (uint32_t)e->tables.tab.terms[term_id].size();
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int64_t gft_term_id(const gft_engine* e, const uint8_t* term, uint32_t len) try {
     if (!e) return -1;
     std::string s((const char*)term, len);
-    auto it = std::lower_bound(e->tab.terms.begin(), e->tab.terms.end(), s);
-    if (it == e->tab.terms.end() || *it != s) return -1;
-    return (int64_t)(it - e->tab.terms.begin());
+    auto it = std::lower_bound(e->tables.tab.terms.begin(), e->tables.tab.terms.end(), s);
+    if (it == e->tables.tab.terms.end() || *it != s) return -1;
+    return (int64_t)(it - e->tables.tab.terms.begin());
 } GFT_CATCH_VALUE(-1)
 
 
@@ -1480,30 +1271,11 @@ int gft_export_tables(const gft_engine* e, uint8_t* out, uint64_t cap, uint64_t*
     if (!e) return GFT_E_INVALID;
     GFT_LOCK(e);
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
-    Writer w;
-    w.u32(kTablesMagic); w.u32(kTablesVersion); w.u32((uint32_t)sizeof(Scan2Slot)); w.u32(kScan2FptSize); w.u32(e->build_flags);
-    const AcTables& a = e->tab;
-    w.u64(a.terms.size());
-    for (const auto& t : a.terms) { w.u64(t.size()); w.raw(t.data(), t.size()); }
-    w.u32(a.n_classes); w.raw(a.byte_class, 256); w.u32(a.n_states); w.u32(a.max_term_len);
-    w.vec(a.delta); w.vec(a.out_term); w.vec(a.out_link); w.vec(a.term_len); w.vec(a.depth); w.vec(a.fail);
-    w.vec(a.child_begin); w.vec(a.in_class);
-    const Scan2Tables& t = e->s2;
-    w.u32(t.supported ? 1 : 0); w.u32(t.kp); w.u32(t.pad_class); w.u32(t.hashed ? 1 : 0); w.u32(t.filter_bits); w.u32(t.hash_shift);
-    w.vec(t.filter); w.vec(t.short3); w.vec(t.shorts); w.vec(t.short3_big); w.vec(t.shorts_packed); w.u32(t.fpt_lg); w.vec(t.fpt);
-    w.u32(t.slot_shift); w.u32(t.slot_seed); w.vec(t.slots); w.vec(t.more);
-    w.raw(t.cls, 256); w.raw(t.cls_fold, 256); w.vec(t.term_blob); w.vec(t.term_off); w.u64(t.n_keys);
-    const Scan3Tables& u = e->s3;
-    w.u32(u.supported ? 1 : 0); w.u32(u.G); w.u32(u.grouped ? 1 : 0); w.raw(u.cls, 256); w.raw(u.cls_fold, 256);
-    w.vec(u.filter); w.vec(u.short3); w.vec(u.srec); w.vec(u.short3_big); w.vec(u.srec_big); w.u32(u.bloom_lg); w.vec(u.bloom);
-    w.u32(u.slot_shift); w.u32(u.slot_seed); w.vec(u.slots); w.vec(u.more); w.vec(u.term_blob); w.vec(u.term_off);
-    w.u64(u.n_keys); w.u64(u.n_anchors);
-    uint64_t sum = 1469598103934665603ull;          // FNV-1a over everything before it
-    for (uint8_t c : w.b) { sum ^= c; sum *= 1099511628211ull; }
-    w.u64(sum);
-    if (needed) *needed = w.b.size();
-    if (!out || cap < w.b.size()) return GFT_E_INVALID;
-    memcpy(out, w.b.data(), w.b.size());
+    std::vector<uint8_t> b;
+    write_tables(e->tables, e->build_flags, b);
+    if (needed) *needed = b.size();
+    if (!out || cap < b.size()) return GFT_E_INVALID;
+    memcpy(out, b.data(), b.size());
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
@@ -1511,58 +1283,12 @@ int gft_import_tables(gft_engine* e, const uint8_t* blob, uint64_t len) try {
     if (!e || !blob) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
     GFT_LOCK(e);
     if (!e->peers.empty() && !e->in_multi) return multi_import_tables(e, blob, len);
-    if (len < 28) return fail(e, GFT_E_INVALID, "table blob too short");
-    uint64_t sum = 1469598103934665603ull, stored;
-    for (uint64_t i = 0; i + 8 < len; i++) { sum ^= blob[i]; sum *= 1099511628211ull; }
-    memcpy(&stored, blob + len - 8, 8);
-    if (sum != stored) return fail(e, GFT_E_INVALID, "table blob is corrupt (checksum)");
-    Reader r{blob, len - 8};
-    if (r.u32() != kTablesMagic) return fail(e, GFT_E_INVALID, "not a gft table blob");
-    if (r.u32() != kTablesVersion || r.u32() != sizeof(Scan2Slot) || r.u32() != kScan2FptSize)
-        return fail(e, GFT_E_UNSUPPORTED, "table blob was written by another library version");
-    const uint32_t flags = r.u32();
-    AcTables a;
-    const uint64_t nt = r.u64();
-    if (!r.ok || nt > len) return fail(e, GFT_E_INVALID, "table blob is truncated");
-    a.terms.resize((size_t)nt);
-    for (auto& t : a.terms) {
-        const uint64_t k = r.u64();
-        if (!r.ok || k > r.n - r.i) return fail(e, GFT_E_INVALID, "table blob is truncated");
-        t.assign((const char*)r.p + r.i, (size_t)k);
-        r.i += k;
-    }
-    a.n_classes = r.u32(); r.raw(a.byte_class, 256); a.n_states = r.u32(); a.max_term_len = r.u32();
-    r.vec(a.delta); r.vec(a.out_term); r.vec(a.out_link); r.vec(a.term_len); r.vec(a.depth); r.vec(a.fail);
-    r.vec(a.child_begin); r.vec(a.in_class);
-    Scan2Tables t;
-    t.supported = r.u32() != 0; t.kp = r.u32(); t.pad_class = r.u32(); t.hashed = r.u32() != 0; t.filter_bits = r.u32(); t.hash_shift = r.u32();
-    r.vec(t.filter); r.vec(t.short3); r.vec(t.shorts); r.vec(t.short3_big); r.vec(t.shorts_packed); t.fpt_lg = r.u32(); r.vec(t.fpt);
-    t.slot_shift = r.u32(); t.slot_seed = r.u32(); r.vec(t.slots); r.vec(t.more);
-    r.raw(t.cls, 256); r.raw(t.cls_fold, 256); r.vec(t.term_blob); r.vec(t.term_off); t.n_keys = r.u64();
-    Scan3Tables u;
-    u.supported = r.u32() != 0; u.G = r.u32(); u.grouped = r.u32() != 0; r.raw(u.cls, 256); r.raw(u.cls_fold, 256);
-    r.vec(u.filter); r.vec(u.short3); r.vec(u.srec); r.vec(u.short3_big); r.vec(u.srec_big); u.bloom_lg = r.u32(); r.vec(u.bloom);
-    u.slot_shift = r.u32(); u.slot_seed = r.u32(); r.vec(u.slots); r.vec(u.more); r.vec(u.term_blob); r.vec(u.term_off);
-    u.n_keys = r.u64(); u.n_anchors = r.u64();
-    if (!r.ok || r.i != r.n) return fail(e, GFT_E_INVALID, "table blob is truncated");
-    // shape checks first: validate_tables indexes the tables by each other's sizes
-    if (a.n_classes == 0 || a.n_classes > 256 || a.delta.size() != (size_t)a.n_states * a.n_classes || a.out_term.size() != a.n_states ||
-        a.out_link.size() != a.n_states || a.term_len.size() != a.terms.size() ||
-        (t.supported && (t.fpt_lg > 28 || t.fpt.size() != (t.fpt_lg ? (size_t)1 << t.fpt_lg : (size_t)kScan2FptSize) || t.slots.size() != ((size_t)1 << (32 - t.slot_shift)) || t.term_off.size() != a.terms.size() + 1 ||
-                         t.filter.size() * 32 != t.filter_bits)))
-        return fail(e, GFT_E_INVALID, "table blob is inconsistent");
-    if (const char* why = validate_tables(a, t, u)) return fail(e, GFT_E_INVALID, std::string("table blob is inconsistent: ") + why);
-    if (!t.supported) t.why_not = "not supported by the suffix-window kernel (imported tables)";
+    TableSet set;
+    uint32_t flags = 0;
+    const int rc = read_tables(blob, len, set, flags, e->err);
+    if (rc) return rc;          // the handle is untouched: the dictionary installed before, if any, still is
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
-    e->built = false;
-    e->tab = std::move(a);
-    e->s2 = std::move(t);
-    e->s3 = std::move(u);
-    // (a dictionary whose suffix-window set is not serialised as complete -- more than 32 byte classes -- gets its long-term
-    // tables from the compiler again: a blob only ever holds what validate_tables checks)
-    if (!e->s2.supported) build_scan2_tables(e->tab, e->s2);
-    else e->s2.long_ok = true;
-    return install_tables(e, flags);
+    return install_tables(e, std::move(set), flags);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_scan_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
@@ -1724,7 +1450,7 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     ProgramSet ps;              // (declared before `drained`: the uploads below read it until the stream has drained)
-    int rc = compile_programs(prog_words, prog_off, n_exprs, (uint32_t)e->tab.terms.size() + n_extra, ps, e->err);
+    int rc = compile_programs(prog_words, prog_off, n_exprs, (uint32_t)e->tables.tab.terms.size() + n_extra, ps, e->err);
     if (rc) return rc;          // the handle is untouched: the set installed before, if any, still is
     refresh_options(e);
     if (e->opt_solve_dbg) print_program_stats(ps);
@@ -1784,7 +1510,7 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
         if (xo[n_docs]) {
             HIP_TRY(hipMemcpy(xs.data(), d_extra->slot, xo[n_docs] * 4, hipMemcpyDeviceToHost), "extra read-back");
             HIP_TRY(hipMemcpy(xp.data(), d_extra->pos, xo[n_docs] * 4, hipMemcpyDeviceToHost), "extra read-back");
-            const uint64_t n_slots = e->tab.terms.size() + e->n_extra;
+            const uint64_t n_slots = e->tables.tab.terms.size() + e->n_extra;
             for (uint64_t i = xo[0]; i < xo[n_docs]; i++)
                 if (xs[i] >= n_slots) return fail(e, GFT_E_INVALID, "extra slot out of range");
         }
@@ -1935,7 +1661,7 @@ int upload_extra(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs,
     HIP_TRY(hipMemcpyAsync(e->d_xoff.p, extra->off, (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream), "extra upload");
     if (nx) {
         for (uint64_t i = 0; i < nx; i++)
-            if (extra->slot[i] >= e->tab.terms.size() + e->n_extra) return fail(e, GFT_E_INVALID, "extra slot out of range");
+            if (extra->slot[i] >= e->tables.tab.terms.size() + e->n_extra) return fail(e, GFT_E_INVALID, "extra slot out of range");
         HIP_TRY(hipMemcpyAsync(e->d_xslot.p, extra->slot, nx * 4, hipMemcpyHostToDevice, e->stream), "extra upload");
         HIP_TRY(hipMemcpyAsync(e->d_xpos.p, extra->pos, nx * 4, hipMemcpyHostToDevice, e->stream), "extra upload");
     }
@@ -2299,6 +2025,46 @@ int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off
     return GFT_OK;
 } GFT_CATCH(nullptr)
 
+int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
+                     uint64_t lds_max, const char* forced_kernel, const char** kernel, uint8_t* out, uint64_t cap, uint64_t* needed,
+                     char* err_out, uint64_t err_cap) try {
+    if (!kernel || !needed || (!blob && n_terms && (!terms_blob || !term_off))) return GFT_E_INVALID;
+    *kernel = "";
+    *needed = 0;
+    std::string err;
+    auto done = [&](int rc) {
+        if (err_out && err_cap) { const size_t n = std::min<size_t>(err.size(), err_cap - 1); memcpy(err_out, err.data(), n); err_out[n] = 0; }
+        return rc;
+    };
+    TableSet set;
+    uint32_t flags = 0;
+    int rc;
+    if (blob) {
+        if ((rc = read_tables(blob, blob_len, set, flags, err))) return done(rc);
+    } else {
+        std::vector<std::string> terms;
+        for (uint32_t i = 0; i < n_terms; i++) terms.emplace_back((const char*)terms_blob + term_off[i], (size_t)(term_off[i + 1] - term_off[i]));
+        compile_tables(std::move(terms), set);
+    }
+    ScanOptions opt = scan_options();
+    if (forced_kernel) opt.forced = parse_forced(forced_kernel);
+    ScanPlan plan;
+    if ((rc = plan_scan(set, opt, lds_max, kExtraKernels, plan, err))) return done(rc);
+    *kernel = kScanKernelName[(int)plan.kernel];
+    if (plan.kernel == ScanKernel::scan5) {              // (what gft_build would go on to derive: it must not fault on these tables)
+        Scan5Tables s5;
+        std::vector<uint32_t> bloom;
+        derive_scan5(set, plan, s5, bloom);
+    }
+    std::vector<uint8_t> b;
+    write_tables(set, flags, b);
+    *needed = b.size();
+    if (!out) return done(GFT_OK);
+    if (cap < b.size()) return done(GFT_E_INVALID);
+    memcpy(out, b.data(), b.size());
+    return done(GFT_OK);
+} GFT_CATCH(nullptr)
+
 int gft_debug_host_solve(const uint32_t* words, uint64_t len, const uint32_t* slots, const uint64_t* list_off,
                          const int64_t* positions, uint32_t n_lists, int* out) try {
     if (!words || !out || (n_lists && (!slots || !list_off))) return GFT_E_INVALID;
@@ -2467,9 +2233,8 @@ int replicate_tables(gft_engine* e, uint32_t flags) {
                 gft_engine* p = e->peers[i];
                 try {
                     GFT_LOCK(p);
-                    p->built = false;
-                    p->tab = e->tab; p->s2 = e->s2; p->s3 = e->s3;
-                    rc[i] = install_tables(p, flags);
+                    TableSet copy = e->tables;
+                    rc[i] = install_tables(p, std::move(copy), flags);
                 } catch (...) { rc[i] = translate_exception(&p->err); }
             });
     }

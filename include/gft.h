@@ -85,7 +85,14 @@ int gft_set_cu_margin(gft_engine* e, uint32_t margin);
 
 /* ---- SubstringEngine.BuildEngine (finder/substringEngine.go:98-106) ----------------------------------- */
 /* Receives the full keyword set (already lower-cased by the DSL parser when case-insensitive,
- * dsl/parser.go:79-81).  Copies, sorts, de-duplicates, compiles the automaton and uploads it. */
+ * dsl/parser.go:79-81).  Copies, sorts, de-duplicates, compiles the automaton and uploads it.
+ * What an error leaves behind: the tables are compiled on the host first and the scan kernel is chosen for them
+ * (csrc/table_set.cpp), and a refusal there -- a null argument, a term_off that does not ascend, a keyword longer than 7 424
+ * bytes, an automaton too large, a GFT_SCAN_KERNEL that this library was built without -- returns with the handle untouched:
+ * the dictionary installed before, if any, stays installed with its programs, and gft_scan* / gft_process* go on answering
+ * from it.  An error after that, while the new tables are copied to the device, leaves a handle without a dictionary:
+ * gft_scan* / gft_process* answer GFT_E_NOT_BUILT until a gft_build or gft_import_tables call succeeds.  A successful call
+ * drops the programs (slots refer to the dictionary): gft_set_programs must be called again. */
 int gft_build(gft_engine* e, const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, uint32_t flags);
 uint32_t gft_n_terms(const gft_engine* e);  /* unique terms */
 uint32_t gft_n_states(const gft_engine* e); /* automaton states incl. root */
@@ -97,7 +104,10 @@ int64_t gft_term_id(const gft_engine* e, const uint8_t* term, uint32_t len);
 /* Compiled tables of the current dictionary as one blob (compiling a 100 k-term dictionary costs
  * ~0.6 s of host time; a blob is installed with a copy and an upload).  gft_export_tables writes into out (cap bytes) and
  * the size into *needed (GFT_E_INVALID when cap is too small); gft_import_tables is equivalent to the gft_build call that
- * produced the blob (same terms, ids and flags).  Blobs are tied to the library version that wrote them. */
+ * produced the blob (same terms, ids and flags), and what an error leaves behind is the same: a blob that is refused -- null,
+ * truncated, corrupt, written by another library version, inconsistent in itself, or one of gft_build's refusals -- returns
+ * with the handle untouched, an error while the tables are copied to the device leaves a handle that answers
+ * GFT_E_NOT_BUILT.  Blobs are tied to the library version that wrote them; the library reads back every blob it writes. */
 int gft_export_tables(const gft_engine* e, uint8_t* out, uint64_t cap, uint64_t* needed);
 int gft_import_tables(gft_engine* e, const uint8_t* blob, uint64_t len);
 
@@ -421,6 +431,18 @@ int gft_debug_emulate_scan(const uint8_t* terms_blob, const uint64_t* term_off, 
 int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* text, uint32_t len,
                            uint32_t lane_start, uint32_t scan_flags, uint32_t groups, uint8_t* out_exact, uint8_t* out_dual,
                            uint32_t* groups_used);
+
+/* The table set alone, on the host (csrc/table_set.cpp): compiles `terms` with the function gft_build calls -- or, when
+ * `blob` is not NULL, reads that blob with the function gft_import_tables calls (the terms are ignored) --, chooses the scan
+ * kernel the way both do for a device with `lds_max` bytes of LDS per workgroup (160 KiB on gfx950) and writes the set with
+ * the function gft_export_tables calls.  forced_kernel: what GFT_SCAN_KERNEL would say (NULL: the environment's own value);
+ * the GFT_SCAN5_* switches are read from the environment as usual.  *kernel = the chosen kernel's name (a static string),
+ * *needed = the size of the written blob, copied into out when out is not NULL (GFT_E_INVALID when cap is too small);
+ * err (nullable, err_cap bytes) receives the text of a refusal, whose status is returned.  No HIP device is needed and no
+ * handle is built; tests use it to check the blob format, its validation and the table of DESIGN.md 4.7. */
+int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
+                     uint64_t lds_max, const char* forced_kernel, const char** kernel, uint8_t* out, uint64_t cap, uint64_t* needed,
+                     char* err, uint64_t err_cap);
 
 /* The solver's program compiler alone, on the host: the set is compiled by the very function gft_set_programs calls
  * (csrc/program_set.cpp: check, fusion with Sethi-Ullman operand order, control-bit device words, evaluation order, blocks of

@@ -65,6 +65,8 @@ def test_engine_over_two_devices_equals_one():
         for e in (one, two):
             e.build(terms)
         assert two.terms() == one.terms()
+        L = _lib.load()
+        assert {L.gft_scan_kernel(L.gft_device_engine(two._h, i)) for i in range(L.gft_n_devices(two._h))} == {L.gft_scan_kernel(one._h)}
         # FindSubstrings: the shards' CSRs come back as one
         assert_csr_equal(two.scan(text, off, fold=True), o.scan(text, off, fold=True))
         assert_csr_equal(two.scan(text[:0], off[:1]), one.scan(text[:0], off[:1]))

@@ -359,6 +359,51 @@ def test_table_export_import_roundtrip(eng, scan_kernel):
         e2.close()
 
 
+def test_export_import_of_a_dictionary_without_short_terms(eng, scan_kernel):
+    """few byte classes, every term at least 4 bytes long: scan2's short3 table is EMPTY.  The installer uploads 16 zero
+    bytes in its place; a handle whose own tables held that placeholder exported a blob that gft_import_tables refused
+    ("scan2 short3 size": 16 < kp^3)"""
+    import random
+    from gofindthem_amd.engine import Engine
+    rng = random.Random(11)
+    terms = sorted({bytes(rng.choice(b"abcde") for _ in range(rng.randint(4, 12))) for _ in range(300)})
+    o = both(eng, terms)
+    blob, off = docs([bytes(rng.choice(b"abcde ") for _ in range(n)) for n in (0, 3, 4, 500, 9000, 70000)] + [b" ".join(terms)])
+    want = o.scan(blob, off)
+    assert want[1].size > len(terms)
+    assert_csr_equal(eng.scan(blob, off), want)
+    e2 = Engine()
+    try:
+        e2.import_tables(eng.export_tables())
+        from gofindthem_amd import _lib
+        L = _lib.load()
+        assert e2.terms() == eng.terms() and L.gft_scan_kernel(e2._h) == L.gft_scan_kernel(eng._h)
+        assert_csr_equal(e2.scan(blob, off), want)
+        assert e2.export_tables() == eng.export_tables()
+    finally:
+        e2.close()
+
+
+def test_refused_build_leaves_the_dictionary_and_its_programs_installed(eng):
+    """a gft_build that is refused before anything is uploaded -- here a keyword beyond the length limit -- leaves the
+    handle as it was: the dictionary installed before and its programs keep answering"""
+    from gofindthem_amd.engine import GftError
+    from gofindthem_amd.workload import Workload, make_expressions
+    w = Workload(1000)
+    terms = w.terms()
+    o = both(eng, terms)
+    exprs = make_expressions(terms, 120, inord_fraction=0.4)
+    o.set_expressions(exprs, False)
+    progs, _ = _programs(o, eng, exprs, False)
+    eng.set_programs(progs)
+    text, off = w.docs_host(0, 300)
+    with pytest.raises(GftError, match="keyword longer than"):
+        eng.build([b"abc", b"x" * 7425])
+    assert eng.terms() == o.terms() and eng.n_states == o.n_states
+    assert_csr_equal(eng.scan(text, off, fold=True), o.scan(text, off, fold=True))
+    assert np.array_equal(eng.process(text, off, fold=True), o.process(text, off, fold=True))
+
+
 def test_large_dictionary_spill_path(eng):
     """30 000 terms: more long terms than the LDS fingerprint table holds, so it moves to global memory
     (kScan2FptLdsItems; BASELINE configs[4] "LDS-tile spill path"); dense matches shrink the work units"""
