@@ -19,6 +19,7 @@
 
 #include <cstdlib>
 
+#include "batch_verdict.hpp"
 #include "compact_host.hpp"
 #include "copy_pool.hpp"
 #include "gft_guard.hpp"
@@ -50,16 +51,11 @@ struct ProfCat {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
 };
 
-// What a scan launch knew.  A deferred launch (scan_pipeline) ran without a read-back of the unit count or the pool need:
-// its caller judges it against these numbers after its last kernel -- the engine's own may have changed by then, for a
-// younger batch, but the kernels of this launch wrote nothing beyond unit_cap and pool_cap.
-struct ScanLaunch {
-    bool deferred = false;
-    bool single = false;                   // the unit table came from k_units_single ...
-    uint32_t epoch = 0;                    // ... which raises the batch's control-block flags to this number
-    bool ordered = false;                  // every unit went through scan2's per-lane staging path (GFT_SCAN_ORDERED)
-    uint64_t n_docs = 0, unit_cap = 0, pool_cap = 0;
-    uint64_t static_slabs = 0;             // pool entries that the waves of the grid owned from the start (the cursor counts behind them)
+// What the unit table, the match pool and the result buffers hold now
+struct PoolState {
+    uint64_t n_units = 0, total = 0;       // of the last completed scan (csr_from_pool)
+    uint64_t valid_docs = ~0ull;           // documents of the last gft_process scan still in the pool (~0: none)
+    bool csr_valid = false;                // d_match_off / d_term / d_pos hold that scan's canonical CSR
 };
 
 }  // namespace
@@ -107,19 +103,12 @@ struct gft_engine {
         struct { DevBuf filter, short3, srec, short3_big, srec_big, bloom, slots, more, cls, cls_fold, term_blob, term_off; } s3;
         struct { DevBuf grp, grp_fold, filter, bloom; } s5;
     } d_tabs;
-    // control block (64 B): [0] u32 bad-offsets flag, [8] u64 pool cursor, [16] u64 exact match count, [24] u32 a folded scan
-    // saw a byte >= 0x80, [32] u64 n_units,
-    // [40] u64 first text offset, [48] u64 last text offset -- one memset per batch, one read-back per synchronisation
-    DevBuf d_ctl, d_dbg;
-    uint64_t scan_valid_docs = ~0ull;                   // documents of the last gft_process scan still in the pool (~0: none)
-    // what the batches teach the kernels on scan2's tables (learn_from_batch; not plan): the bytes per work unit follow the
-    // match density, and scan4 sizes a unit's region of the match pool from the matches per text byte of the batches before
-    uint32_t scan2_unit_max = kScan2UnitMax;
-    double scan4_density = 0.06;
-    uint32_t last_nonascii_bits = 0;                    // what the scan kernels said: 1 = bytes >= 0x80 seen, not judged; 2 = judged unsafe
-    bool last_nonascii = false;                         // the last GFT_FOLD_ASCII scan ran over text that ASCII folding does not
-                                                        // lower-case the way strings.ToLower does (gft_last_nonascii)
-    uint64_t last_text_lo = 0, last_text_hi = 0;        // text range of the last scan
+    DevBuf d_ctl, d_dbg;                                // the control block (batch_verdict.hpp); GFT_SCAN_DEBUG counters
+    // batch_verdict.hpp: what the batches taught the next ones; the verdict of the batch whose entry point returned last
+    // (gft_last_nonascii) -- the public entry points assign it as their last act, nothing else does
+    gft::Learned learned;
+    gft::BatchVerdict reported;
+    PoolState pool;
     // Environment switches (cross-checks and timing studies) are read when the handle is created and again
     // by gft_build / gft_import_tables / gft_set_programs -- never on the per-batch path
     uint32_t opt_scan_dbg = 0;                          // GFT_SCAN_DEBUG (timing studies)
@@ -152,15 +141,9 @@ struct gft_engine {
         DevBuf fprog_t, fblk_off;          // fused programs per sorted block of 64, transposed (read when they do not fit LDS)
         DevBuf wide_list;
     } d_progs;
-    uint64_t last_n_units = 0, last_total = 0;   // of the last completed scan (csr_from_pool)
-    bool csr_valid = false;                // d_match_off / d_term / d_pos hold the last scan's canonical CSR
     DevBuf d_patch;                        // bit patches of host-solved results for a device-resident bitmap
     DevBuf d_wide_slot, d_wide_theta;      // pairs of wide INORD groups, a region per wave of the solver's grid
     DevBuf d_solve_dbg;                    // GFT_SOLVE_DEBUG & 8: phase clocks
-    // batches in a row that were one unit per document (k_units_single serves the next one from 2 on; a batch that took
-    // that path and held a longer document after all sets it well below zero, so that a corpus whose batches alternate does
-    // not pay for the miss every other time)
-    int single_streak = 0;
     uint32_t ctl_epoch = 1;                // k_units_single batches are numbered from 2 (their control-block flags)
     // gft_process_device_begin / _end: up to two batches enqueued, their read-backs landing in pinned slots of their own
     struct Pending {
@@ -170,8 +153,7 @@ struct gft_engine {
         uint32_t* d_bitmap = nullptr;
         ScanLaunch launch;
         uint64_t* rb = nullptr; hipEvent_t ev = nullptr;
-        // the batch's verdict once it is complete (gft_last_nonascii for its _end: a younger batch may be judged in between)
-        bool nonascii = false; uint32_t nonascii_bits = 0; uint64_t text_lo = 0, text_hi = 0;
+        gft::BatchVerdict verdict;         // the batch's own, complete when `done` or judged: what its _end reports
     };
     Pending pend[2];
     unsigned pend_head = 0, pend_count = 0;
@@ -295,10 +277,10 @@ int ensure_pool(gft_engine* e, uint64_t entries) {
 
 // slabs of the last completed scan -> canonical CSR in e->d_match_off / d_term / d_pos (document order, the reference's
 // emission order inside a document).  The unit table, the slabs and the counts of that scan are still in the engine
-// (last_n_units, last_total); positions must have been written (want_pos).
+// (e->pool); positions must have been written (want_pos).
 int csr_from_pool(gft_engine* e, uint64_t n_docs) {
     hipStream_t st = e->stream;
-    const uint64_t n_units = e->last_n_units, total = e->last_total;
+    const uint64_t n_units = e->pool.n_units, total = e->pool.total;
     HIP_TRY(e->d_term.ensure(std::max<uint64_t>(total, 1) * 4), "result alloc");
     HIP_TRY(e->d_pos.ensure(std::max<uint64_t>(total, 1) * 4), "result alloc");
     HIP_TRY(e->d_unit_out.ensure((n_units + 1) * 8), "unit alloc");
@@ -316,7 +298,7 @@ int csr_from_pool(gft_engine* e, uint64_t n_docs) {
                           sort_units ? e->d_units.as<Unit>() : nullptr,
                           e->d_tabs.dfa.term_len.as<uint32_t>(), (e->build_flags & GFT_POS_END) ? 1u : 0u),
             "gather");
-    e->csr_valid = true;
+    e->pool.csr_valid = true;
     return GFT_OK;
 }
 
@@ -328,14 +310,18 @@ struct ScanBatch {
     bool need_csr;
 };
 
+// where the kernels and the copies find a field of the control block (byte offsets: batch_verdict.hpp)
+template <class T>
+T* ctl_at(const gft_engine* e, size_t byte_off) { return reinterpret_cast<T*>(e->d_ctl.as<uint8_t>() + byte_off); }
+
 // the fields that every scan kernel's parameter struct has
 template <class Params>
 void fill_common(const gft_engine* e, const ScanBatch& b, Params& P) {
     P.text = b.d_text; P.doc_off = b.d_doc_off; P.units = e->d_units.as<Unit>(); P.n_units = b.n_units;
     P.pos_end = (e->build_flags & GFT_POS_END) ? 1 : 0;
     P.fold = (b.flags & GFT_FOLD_ASCII) ? 1 : 0;
-    P.nonascii = e->d_ctl.as<uint32_t>() + 6;
-    P.cursor = e->d_ctl.as<uint64_t>() + 1; P.pool_cap = e->pool_cap;
+    P.nonascii = ctl_at<uint32_t>(e, kCtlNonascii);
+    P.cursor = ctl_at<uint64_t>(e, kCtlCursor); P.pool_cap = e->pool_cap;
     P.pool_term = e->d_pool_term.as<uint32_t>(); P.pool_pos = e->d_pool_pos.as<uint32_t>();
     P.unit_start = e->d_unit_start.as<uint64_t>(); P.unit_count = e->d_unit_count.as<uint32_t>();
 }
@@ -344,7 +330,7 @@ template <class Params>
 void fill_window(const gft_engine* e, const ScanBatch& b, Params& P) {
     fill_common(e, b, P);
     P.text_bytes = b.text_hi;
-    P.n_matches = e->d_ctl.as<uint64_t>() + 2;
+    P.n_matches = ctl_at<uint64_t>(e, kCtlTotal);
     // presence-only mode: positions are only read by INORD groups (and by CSR callers)
     P.want_pos = (b.need_csr || e->progs.n_inord_groups > 0) ? 1 : 0;
     // wave priorities: the latency-bound verification stages overtake the filter phase of the other waves (5 % on
@@ -433,7 +419,7 @@ Scan2Params scan2_params(const gft_engine* e, const ScanBatch& b) {
         P.chunk_units = (uint32_t)std::min<uint64_t>(kScan4ChunkUnits, std::max<uint64_t>(1, b.n_docs / (n_waves * 4)));
         if (e->opt_scan4_chunk) P.chunk_units = std::min<uint32_t>(e->opt_scan4_chunk, kScan4ChunkUnits);      // (GFT_SCAN4_CHUNK: tests)
         P.cand_cap = e->plan.scan4_fifo[P.want_pos ? 1 : 0];
-        P.bound_q16 = (uint32_t)std::min<double>(e->scan4_density * 1.6 * 65536.0 + 1.0, 4.0e9);
+        P.bound_q16 = (uint32_t)std::min<double>(e->learned.scan4_density * 1.6 * 65536.0 + 1.0, 4.0e9);
         P.bound_add = 48;
         P.round_c = e->opt_scan4_round ? std::min<uint32_t>(64, std::max<uint32_t>(16, e->opt_scan4_round & ~15u)) : 64;   // (GFT_SCAN4_ROUND: timing studies)
         // a slab should hold a few chunks' regions (the rest of a slab that the next chunk does not fit is lost)
@@ -514,55 +500,40 @@ int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
     return GFT_OK;
 }
 
-// What a completed batch teaches the next ones: scan4's match density, and the unit size of the kernels on scan2's tables
-void learn_from_batch(gft_engine* e, const ScanLaunch& L, uint64_t total, uint64_t text_lo, uint64_t text_hi) {
-    if (text_hi <= text_lo) return;
-    const double per_byte = (double)total / (double)(text_hi - text_lo);
-    if (e->plan.kernel == ScanKernel::scan4) e->scan4_density = std::max(0.002, per_byte);
-    if (on_scan2_tables(e->plan.kernel) && !L.ordered) {
-        // a unit's matches should fit the wave's LDS fifo: a unit of maximal size should fill ~75 % of it (dense
-        // dictionaries -> smaller units; results do not depend on the unit size)
-        const double want = per_byte > 0 ? 0.75 * (e->plan.kernel == ScanKernel::scan5 ? e->plan.s5plan.fifo_cap : kScan2FifoCap) / per_byte : (double)kScan2UnitMax;
-        const uint32_t um = want >= kScan2UnitMax ? kScan2UnitMax : (uint32_t)want & ~255u;
-        e->scan2_unit_max = std::max<uint32_t>(512, um);
-    }
+// What a completed batch teaches the next ones (batch_verdict.hpp)
+void learn_from_batch(gft_engine* e, const ScanLaunch& L, const BatchVerdict& v) {
+    const ScanKernel k = e->plan.kernel;
+    learn(e->learned, k, k == ScanKernel::scan5 ? e->plan.s5plan.fifo_cap : kScan2FifoCap, L.ordered, v.total, v.text_lo, v.text_hi);
 }
 
-// The device pipeline shared by scan and process.  On success the canonical CSR sits in e->d_match_off /
-// d_term / d_pos and *n_matches is set.
+// The device pipeline shared by scan and process.  On success the canonical CSR sits in e->d_match_off / d_term / d_pos
+// (need_csr) and `v` says what the scan established -- unless the launch was deferred: deferred_interpret then does.
 constexpr uint64_t kHostUnitDocs = 1024;   // batches up to this many documents get their unit table from the host
 
 // defer != nullptr: the launch may be deferred -- the caller reads the control block back itself after its last kernel
 // (deferred_interpret), the unit table and the match pool are sized from the previous batch, and a batch that outgrew them is
 // run again.  *defer says whether it was, and what the launch knew.
 int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
-                  bool need_csr, uint64_t* n_matches, const uint64_t* h_doc_off = nullptr, ScanLaunch* defer = nullptr) {
+                  bool need_csr, BatchVerdict& v, const uint64_t* h_doc_off = nullptr, ScanLaunch* defer = nullptr) {
     hipStream_t st = e->stream;
-    *n_matches = 0;
+    v = BatchVerdict();                   // (an empty batch: nothing scanned, no range for refine_nonascii to judge)
     ScanLaunch L;
     if (defer) *defer = L;
-    e->scan_valid_docs = ~0ull;           // the pool is about to be overwritten
-    e->csr_valid = false;
+    e->pool = PoolState();                // the pool is about to be overwritten
     HIP_TRY(e->d_match_off.ensure((n_docs + 1) * 8), "match_off alloc");
     if (n_docs == 0) {
         HIP_TRY(hipMemsetAsync(e->d_match_off.p, 0, 8, st), "memset");
         HIP_TRY(hipStreamSynchronize(st), "sync");
-        e->last_n_units = e->last_total = 0;
-        // (nothing was scanned: the verdict and the text range of the batch BEFORE must not be judged against this one's
-        // pointers -- refine_nonascii would launch k_fold_safe over a stale range of a text that may be NULL)
-        e->last_nonascii = false;
-        e->last_nonascii_bits = 0;
-        e->last_text_lo = e->last_text_hi = 0;
         return GFT_OK;
     }
     const uint32_t warm = e->tables.tab.max_term_len ? e->tables.tab.max_term_len - 1 : 0;
     // gft_scan2: a unit's matches should fit the wave's LDS fifo (kScan2FifoCap), so the unit size follows the match
     // density the previous call saw (dense dictionaries -> smaller units); results do not depend on it
     const uint32_t unit_max = e->plan.kernel == ScanKernel::scan3 ? kScan3UnitMax : e->plan.kernel == ScanKernel::scan4 ? kScan4UnitMax
-                              : on_scan2_tables(e->plan.kernel) ? e->scan2_unit_max : kTextBuf - warm;
+                              : on_scan2_tables(e->plan.kernel) ? e->learned.unit_max : kTextBuf - warm;
 
     // 1. work units
-    HIP_TRY(e->d_ctl.ensure(64), "control alloc");
+    HIP_TRY(e->d_ctl.ensure(kCtlBytes), "control alloc");
     HIP_TRY(e->d_unit_cnt.ensure(n_docs * 4), "unit alloc");
     HIP_TRY(e->d_unit_base.ensure((n_docs + 1) * 8), "unit alloc");
     HIP_TRY(e->d_partial.ensure(scan_partials_needed(n_docs) * 8), "unit alloc");
@@ -575,9 +546,9 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     // also clears the control block (its two flags are raised to the batch's EPOCH, a number no earlier batch wrote there,
     // so they need no clearing): one node less on the stream of every batch
     const uint64_t cap_units = std::min(std::min(e->d_units.cap / sizeof(Unit), e->d_unit_start.cap / 8), e->d_unit_count.cap / 4);
-    bool units_single = !host_units && defer && !need_csr && e->single_streak >= 2 && e->pool_cap > 0 && cap_units >= n_docs;
+    bool units_single = !host_units && defer && !need_csr && e->learned.single_streak >= 2 && e->pool_cap > 0 && cap_units >= n_docs;
     if (units_single && ++e->ctl_epoch < 2) { e->ctl_epoch = 1; units_single = false; }      // (wrapped: this batch the general way)
-    if (!units_single) HIP_TRY(hipMemsetAsync(e->d_ctl.p, 0, 32, st), "memset");     // flag, cursor, match count, non-ASCII flag
+    if (!units_single) HIP_TRY(hipMemsetAsync(e->d_ctl.p, 0, kCtlBatchClear, st), "memset");
     std::vector<uint64_t> hub;
     std::vector<Unit> hun;
     struct DrainIf { gft_engine* e; bool on; ~DrainIf() { if (on && e->stream) (void)hipStreamSynchronize(e->stream); } } drain_units{e, host_units};
@@ -601,17 +572,17 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     } else if (units_single) {
         ProfScope ps(e, "aux");
         HIP_TRY(launch_units_single(d_doc_off, n_docs, unit_max, e->d_units.as<Unit>(), e->d_unit_base.as<uint64_t>(),
-                                    e->d_ctl.as<uint32_t>(), e->ctl_epoch, st), "unit table");
+                                    ctl_at<uint32_t>(e, kCtlBad), e->ctl_epoch, st), "unit table");
         n_units = n_docs; text_lo = 0; text_hi = ~0ull;
         L.deferred = L.single = true; L.epoch = e->ctl_epoch;
         L.unit_cap = L.n_docs = n_docs;
     } else {
         {
             ProfScope ps(e, "aux");
-            HIP_TRY(launch_unit_count(d_doc_off, n_docs, unit_max, e->d_unit_cnt.as<uint32_t>(), e->d_ctl.as<uint32_t>(), st), "unit_count");
+            HIP_TRY(launch_unit_count(d_doc_off, n_docs, unit_max, e->d_unit_cnt.as<uint32_t>(), ctl_at<uint32_t>(e, kCtlBad), st), "unit_count");
             HIP_TRY(launch_exclusive_scan(e->d_unit_cnt.as<uint32_t>(), n_docs, e->d_unit_base.as<uint64_t>(),
                                           e->d_partial.as<uint64_t>(), st), "unit scan");
-            HIP_TRY(launch_pack_ctl(e->d_unit_base.as<uint64_t>(), d_doc_off, n_docs, e->d_ctl.as<uint64_t>() + 4, st), "unit scan");
+            HIP_TRY(launch_pack_ctl(e->d_unit_base.as<uint64_t>(), d_doc_off, n_docs, ctl_at<uint64_t>(e, kCtlUnits), st), "unit scan");
         }
         // No read-back when the caller checks afterwards: the tables keep the size the last batch gave them (a document
         // is one unit unless it is longer than unit_max), units beyond the table are dropped and every index is clamped
@@ -621,18 +592,18 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
             n_units = cap_units; text_lo = 0; text_hi = ~0ull;       // (the text blob is readable 64 bytes past its end: gft.h)
             L.unit_cap = cap_units; L.n_docs = n_docs;
         } else {
-            uint64_t rb[7] = {0, 0, 0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(rb, e->d_ctl.p, sizeof rb, hipMemcpyDeviceToHost, st), "readback");
+            uint64_t raw[kCtlWords] = {};
+            HIP_TRY(hipMemcpyAsync(raw, e->d_ctl.p, sizeof raw, hipMemcpyDeviceToHost, st), "readback");
             HIP_TRY(hipStreamSynchronize(st), "sync");
-            n_units = rb[4]; text_lo = rb[5]; text_hi = rb[6];
-            e->single_streak = n_units == n_docs ? e->single_streak + 1 : std::min(e->single_streak, 0);
-            const uint32_t bad_doc = (uint32_t)rb[0];
+            const CtlBlock c = decode_ctl(raw);
+            n_units = c.n_units; text_lo = c.text_lo; text_hi = c.text_hi;
+            count_streak(e->learned, n_units, n_docs);
             if (text_hi < text_lo) return fail(e, GFT_E_INVALID, "doc_off is not ascending");
-            if (bad_doc) return fail(e, GFT_E_INVALID, "doc_off is not ascending, or a document is longer than 4 GiB - 1 bytes (positions are 32-bit)");
+            if (c.bad) return fail(e, GFT_E_INVALID, "doc_off is not ascending, or a document is longer than 4 GiB - 1 bytes (positions are 32-bit)");
         }
     }
 
-    if (!L.deferred) { e->last_text_lo = text_lo; e->last_text_hi = text_hi; }
+    if (!L.deferred) { v.text_lo = text_lo; v.text_hi = text_hi; }
     HIP_TRY(e->d_units.ensure(n_units * sizeof(Unit)), "unit alloc");
     HIP_TRY(e->d_unit_start.ensure(n_units * 8), "unit alloc");
     HIP_TRY(e->d_unit_count.ensure(n_units * 4), "unit alloc");
@@ -661,22 +632,23 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
         // (every wave of the grid owns a slab from the start: the pool holds those twice over, or a small batch on a fresh
         // engine would overflow it before it had written a match)
         // (scan4: a slab holds at least one chunk's regions -- up to eight units of unit_max bytes at 1.6 x the density seen)
-        const uint64_t min_slab = k == ScanKernel::scan4 ? kScan4ChunkUnits * ((uint64_t)(unit_max * e->scan4_density * 1.6) + 49) : slab_floor(k);
+        const uint64_t min_slab = k == ScanKernel::scan4 ? kScan4ChunkUnits * ((uint64_t)(unit_max * e->learned.scan4_density * 1.6) + 49) : slab_floor(k);
         rc = ensure_pool(e, 2 * grid_waves(e, n_units) * min_slab);
     }
     if (rc) return rc;
     const ScanBatch batch{d_text, d_doc_off, n_docs, n_units, text_hi, flags, unit_max, need_csr};
     uint64_t total = 0;
     for (int attempt = 0; attempt < 3; attempt++) {
-        if (attempt) HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint8_t>() + 8, 0, 16, st), "memset");
+        if (attempt) HIP_TRY(hipMemsetAsync(ctl_at<uint8_t>(e, kCtlCursor), 0, kCtlRetryClear, st), "memset");
         if ((rc = enqueue_scan(e, batch, L))) return rc;
         if (L.deferred) { *defer = L; return GFT_OK; }         // (the caller reads the cursor back after the solver)
-        uint64_t ct[3] = {0, 0, 0};                            // cursor, exact match count (the DFA kernel: none, its cursor is that), non-ASCII bits
-        HIP_TRY(hipMemcpyAsync(ct, e->d_ctl.as<uint8_t>() + 8, 24, hipMemcpyDeviceToHost, st), "readback");
+        uint64_t raw[kCtlWords] = {};                          // (the words behind the scan alone: cursor, match count, non-ASCII bits)
+        HIP_TRY(hipMemcpyAsync(raw + kCtlCursor / 8, ctl_at<uint8_t>(e, kCtlCursor), kCtlScanRead, hipMemcpyDeviceToHost, st), "readback");
         HIP_TRY(hipStreamSynchronize(st), "scan kernel");
-        const uint64_t cursor = ct[0] + L.static_slabs;
-        total = counts_slabs(k) ? ct[1] : ct[0];
-        e->last_nonascii_bits = (uint32_t)ct[2]; e->last_nonascii = e->last_nonascii_bits != 0;
+        const CtlBlock c = decode_ctl(raw);
+        const uint64_t cursor = c.cursor + L.static_slabs;
+        total = counts_slabs(k) ? c.total : c.cursor;          // (the DFA kernel keeps no count of its own: its cursor is that)
+        v.nonascii_bits = c.nonascii_bits; v.nonascii = c.nonascii_bits != 0;
         if (on_scan2_tables(k) && (e->opt_scan_dbg & 2)) {
             uint64_t c4[4] = {0, 0, 0, 0};
             HIP_TRY(hipMemcpy(c4, e->d_dbg.p, 32, hipMemcpyDeviceToHost), "debug readback");
@@ -684,65 +656,54 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
                     (unsigned long long)n_units, (unsigned long long)c4[0], (unsigned long long)c4[1],
                     (unsigned long long)c4[2], (unsigned long long)total);
         }
-        if (cursor <= e->pool_cap) { learn_from_batch(e, L, total, text_lo, text_hi); break; }
+        v.n_units = n_units; v.total = total;
+        if (cursor <= e->pool_cap) { learn_from_batch(e, L, v); break; }
         if (attempt == 2) return fail(e, GFT_E_HIP, "match pool overflow persisted");
         rc = ensure_pool(e, cursor + cursor / 16);
         if (rc) return rc;
     }
 
-    *n_matches = total;
-    e->last_n_units = n_units; e->last_total = total;
+    e->pool.n_units = n_units; e->pool.total = total;
     if (!need_csr) return GFT_OK;   // the solver reads the slabs in place (doc -> units -> pool)
     return csr_from_pool(e, n_docs);
 }
 
 // The verdict on a deferred launch (scan_pipeline) from the read-back of the control block that its caller made after the
-// batch's last kernel -- the batch's only host synchronisation.  *again = the unit table or the match pool was too small
-// (they have been grown): the caller runs the batch once more, this time with the sizes known.
-int deferred_interpret(gft_engine* e, const uint64_t* rb, const ScanLaunch& L, bool* again) {
-    *again = false;
-    const uint64_t cursor = rb[1] + L.static_slabs, total = rb[2], n_units = rb[4], text_lo = rb[5], text_hi = rb[6];
-    e->last_nonascii_bits = (uint32_t)rb[3]; e->last_nonascii = e->last_nonascii_bits != 0;
-    // (a k_units_single batch raises its flags to its epoch; what an earlier batch left there is smaller)
-    const bool flag_bad = L.single ? (uint32_t)rb[0] == L.epoch : (uint32_t)rb[0] != 0;
-    if (L.single && (uint32_t)(rb[3] >> 32) == L.epoch) {      // a document of more than one unit: the general path
-        e->single_streak = -8;
-        *again = true;
-        return GFT_OK;
-    }
-    e->single_streak = n_units == L.n_docs ? e->single_streak + 1 : std::min(e->single_streak, 0);
-    e->last_text_lo = text_lo; e->last_text_hi = text_hi;
-    e->last_n_units = n_units; e->last_total = total;
-    if (text_hi < text_lo) return fail(e, GFT_E_INVALID, "doc_off is not ascending");
-    if (flag_bad) return fail(e, GFT_E_INVALID, "doc_off is not ascending, or a document is longer than 4 GiB - 1 bytes (positions are 32-bit)");
-    // (the DFA kernel's cursor counts matches, the suffix-window kernels' slabs: both must fit the pool)
-    if (n_units > L.unit_cap || cursor > L.pool_cap) {
-        if (cursor > L.pool_cap) { int rc = ensure_pool(e, cursor + cursor / 16); if (rc) return rc; }     // (a no-op when it has grown past the cursor since)
-        *again = true;
-        return GFT_OK;
-    }
-    learn_from_batch(e, L, total, text_lo, text_hi);
+// batch's last kernel: judge_deferred says it, this applies it.  *again = the unit table or the match pool was too small
+// (the pool has been grown): the caller runs the batch once more, this time with the sizes known.
+int deferred_interpret(gft_engine* e, const uint64_t* raw, const ScanLaunch& L, BatchVerdict& v, bool* again) {
+    const CtlBlock c = decode_ctl(raw);
+    const Judgement j = judge_deferred(c, L);
+    v = j.verdict;
+    *again = j.kind == Judgement::again_general || j.kind == Judgement::again_grow;
+    if (single_miss(c, L)) { e->learned.single_streak = kSingleMissStreak; return GFT_OK; }
+    count_streak(e->learned, v.n_units, L.n_docs);
+    e->pool.n_units = v.n_units; e->pool.total = v.total;
+    if (j.kind == Judgement::invalid) return fail(e, GFT_E_INVALID, j.err);
+    if (j.kind == Judgement::again_grow) return ensure_pool(e, j.pool_need);     // (a no-op when it has grown past the need since)
+    if (j.kind == Judgement::accept) learn_from_batch(e, L, v);
     return GFT_OK;
 }
 
 // A folded scan that met bytes >= 0x80: is ASCII folding still the whole of strings.ToLower for this text (k_fold_safe)?
 // One more pass over the text and one more read-back, for such batches only.
-int refine_nonascii(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags) {
-    if (!(flags & GFT_FOLD_ASCII)) { e->last_nonascii = false; return GFT_OK; }
-    if (!e->last_nonascii) return GFT_OK;
+int refine_nonascii(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags, BatchVerdict& v) {
+    if (!(flags & GFT_FOLD_ASCII)) { v.nonascii = false; return GFT_OK; }
+    if (!v.nonascii) return GFT_OK;
     // (gft_scan3 / gft_scan5 judge the pieces that hold high bytes themselves -- gft_foldsafe_dev.hpp -- and say "unsafe"
     // or nothing; the other kernels only say that they saw some)
-    if (!(e->last_nonascii_bits & 1u)) { e->last_nonascii = (e->last_nonascii_bits & 2u) != 0; return GFT_OK; }
+    if (!(v.nonascii_bits & 1u)) { v.nonascii = (v.nonascii_bits & 2u) != 0; return GFT_OK; }
     uint32_t flag = 0;
+    uint32_t* d_flag = ctl_at<uint32_t>(e, kCtlNonascii);
     {
         ProfScope ps(e, "aux");
         // (the word starts at zero: a younger batch in flight may have left its own bits there since this batch's scan)
-        HIP_TRY(hipMemsetAsync(e->d_ctl.as<uint32_t>() + 6, 0, 4, e->stream), "memset");
-        HIP_TRY(launch_fold_safe(d_text, e->last_text_lo, e->last_text_hi, d_doc_off, n_docs, e->d_ctl.as<uint32_t>() + 6, e->stream), "fold check");
+        HIP_TRY(hipMemsetAsync(d_flag, 0, 4, e->stream), "memset");
+        HIP_TRY(launch_fold_safe(d_text, v.text_lo, v.text_hi, d_doc_off, n_docs, d_flag, e->stream), "fold check");
     }
-    HIP_TRY(hipMemcpyAsync(&flag, e->d_ctl.as<uint32_t>() + 6, 4, hipMemcpyDeviceToHost, e->stream), "readback");
+    HIP_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, e->stream), "readback");
     HIP_TRY(hipStreamSynchronize(e->stream), "fold check");
-    e->last_nonascii = (flag & 2u) != 0;
+    v.nonascii = (flag & 2u) != 0;
     return GFT_OK;
 }
 
@@ -928,7 +889,7 @@ int host_eval(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, co
               uint32_t* d_bitmap) {
     if (plan.empty() || !n_docs || !e->n_exprs) return GFT_OK;
     hipStream_t st = e->stream;
-    if (!e->csr_valid) { int rc = csr_from_pool(e, n_docs); if (rc) return rc; }
+    if (!e->pool.csr_valid) { int rc = csr_from_pool(e, n_docs); if (rc) return rc; }
     std::vector<uint64_t> mo(n_docs + 1);
     HIP_TRY(hipMemcpyAsync(mo.data(), e->d_match_off.p, (n_docs + 1) * 8, hipMemcpyDeviceToHost, st), "download");
     HIP_TRY(hipStreamSynchronize(st), "host solve");
@@ -1215,9 +1176,9 @@ static int install_tables(gft_engine* e, TableSet&& set, uint32_t flags) {
     e->plan = plan;
     e->s5 = std::move(s5);
     e->build_flags = flags;
-    e->scan_valid_docs = ~0ull;
-    e->scan2_unit_max = kScan2UnitMax;
-    e->scan4_density = 0.06;
+    e->pool.valid_docs = ~0ull;
+    e->learned.unit_max = kScan2UnitMax;
+    e->learned.scan4_density = 0.06;
     e->built = true;
     return GFT_OK;
 }
@@ -1243,7 +1204,7 @@ uint32_t gft_n_terms(const gft_engine* e) { return e ? (uint32_t)e->tables.tab.t
 uint32_t gft_n_states(const gft_engine* e) { return e ? e->tables.tab.n_states : 0; }
 uint32_t gft_n_exprs(const gft_engine* e) { return e ? e->n_exprs : 0; }
 uint32_t gft_n_host_exprs(const gft_engine* e) { return e ? (uint32_t)e->progs.host_only.size() : 0; }
-int gft_last_nonascii(const gft_engine* e) { return e && e->last_nonascii ? 1 : 0; }
+int gft_last_nonascii(const gft_engine* e) { return e && e->reported.nonascii ? 1 : 0; }
 const char* gft_build_info(void) { return kExtraKernels ? "gfx950 extra_kernels=1" : "gfx950 extra_kernels=0"; }
 const char* gft_scan_kernel(const gft_engine* e) {
     if (!e || !e->built) return "";
@@ -1291,6 +1252,24 @@ int gft_import_tables(gft_engine* e, const uint8_t* blob, uint64_t len) try {
     return install_tables(e, std::move(set), flags);
 } GFT_CATCH((e ? &e->err : nullptr))
 
+// What gft_scan / gft_scan_device do behind the scan itself: GFT_SCAN_UNIQUE, GFT_POS_RUNES, the non-ASCII verdict
+static int scan_post(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags, uint64_t& nm,
+                     BatchVerdict& v) {
+    int rc;
+    if ((flags & GFT_SCAN_UNIQUE) && (rc = unique_pipeline(e, n_docs, &nm))) return rc;
+    if ((flags & GFT_POS_RUNES) && !(flags & GFT_SCAN_UNIQUE)) {
+        if (e->build_flags & GFT_POS_END) return fail(e, GFT_E_UNSUPPORTED, "GFT_POS_RUNES needs a GFT_POS_START engine (AnknownEngine reports where a match begins)");
+        if ((rc = rune_pipeline(e, d_text, d_doc_off, n_docs, nm))) return rc;
+    }
+    return refine_nonascii(e, d_text, d_doc_off, n_docs, flags, v);
+}
+
+// a scan entry point's last act on every way out behind its scan: the batch's verdict becomes the handle's
+struct Publish {
+    gft_engine* e; const BatchVerdict& v;
+    ~Publish() { e->reported = v; }
+};
+
 int gft_scan_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                     uint32_t flags, gft_matches* out_dev) try {
     if (!e || !out_dev || (n_docs && (!d_text_blob || !d_doc_off))) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
@@ -1298,15 +1277,12 @@ int gft_scan_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     DeviceGuard g(e->device);
-    uint64_t nm = 0;
-    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, true, &nm);
+    BatchVerdict v;
+    Publish publish{e, v};
+    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, true, v);
     if (rc) return rc;
-    if ((flags & GFT_SCAN_UNIQUE) && (rc = unique_pipeline(e, n_docs, &nm))) return rc;
-    if ((flags & GFT_POS_RUNES) && !(flags & GFT_SCAN_UNIQUE)) {
-        if (e->build_flags & GFT_POS_END) return fail(e, GFT_E_UNSUPPORTED, "GFT_POS_RUNES needs a GFT_POS_START engine (AnknownEngine reports where a match begins)");
-        if ((rc = rune_pipeline(e, d_text_blob, d_doc_off, n_docs, nm))) return rc;
-    }
-    if ((rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags))) return rc;
+    uint64_t nm = v.total;
+    if ((rc = scan_post(e, d_text_blob, d_doc_off, n_docs, flags, nm, v))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream), "scan pipeline");
     out_dev->n_docs = n_docs; out_dev->n_matches = nm;
     out_dev->match_off = e->d_match_off.as<uint64_t>();
@@ -1338,17 +1314,23 @@ static unsigned pin_threads() {
     return n;
 }
 
+// the two pinned bounce buffers with their events, and the threads that fill / empty them
+static int ensure_bounce(gft_engine* e) {
+    for (int k = 0; k < 2; k++) {
+        if (!e->pin[k]) HIP_TRY(hipHostMalloc(&e->pin[k], kPinBuf, hipHostMallocDefault), "pinned alloc");
+        if (!e->pin_ev[k]) HIP_TRY(hipEventCreateWithFlags(&e->pin_ev[k], hipEventDisableTiming), "event");
+    }
+    if (!e->copy_pool) e->copy_pool.reset(new gft::CopyPool(pin_threads() - 1));
+    return GFT_OK;
+}
+
 // pageable host memory -> device through the pinned bounce buffers
 static int h2d_staged(gft_engine* e, void* dst, const void* src, size_t bytes) {
     if (bytes < (8u << 20)) {
         HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, e->stream), "upload");
         return GFT_OK;
     }
-    for (int k = 0; k < 2; k++) {
-        if (!e->pin[k]) HIP_TRY(hipHostMalloc(&e->pin[k], kPinBuf, hipHostMallocDefault), "pinned alloc");
-        if (!e->pin_ev[k]) HIP_TRY(hipEventCreateWithFlags(&e->pin_ev[k], hipEventDisableTiming), "event");
-    }
-    if (!e->copy_pool) e->copy_pool.reset(new gft::CopyPool(pin_threads() - 1));
+    if (int rc = ensure_bounce(e)) return rc;
     size_t done = 0;
     // (the first chunks are small and double: the link idles while the very first one is filled)
     size_t chunk = std::min<size_t>(kPinChunk, 4u << 20);
@@ -1371,11 +1353,7 @@ static int d2h_staged(gft_engine* e, void* dst, const void* src, size_t bytes) {
         HIP_TRY(hipStreamSynchronize(e->stream), "download");
         return GFT_OK;
     }
-    for (int k = 0; k < 2; k++) {
-        if (!e->pin[k]) HIP_TRY(hipHostMalloc(&e->pin[k], kPinBuf, hipHostMallocDefault), "pinned alloc");
-        if (!e->pin_ev[k]) HIP_TRY(hipEventCreateWithFlags(&e->pin_ev[k], hipEventDisableTiming), "event");
-    }
-    if (!e->copy_pool) e->copy_pool.reset(new gft::CopyPool(pin_threads() - 1));
+    if (int rc = ensure_bounce(e)) return rc;
     size_t issued = 0, done = 0;
     size_t len[2] = {0, 0};
     int ki = 0, kd = 0;
@@ -1417,15 +1395,12 @@ int gft_scan(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, u
     SyncOnExit drained(e);      // host buffers are read by asynchronous copies: drained on every way out
     int rc = stage_docs(e, text_blob, doc_off, n_docs);
     if (rc) return rc;
-    uint64_t nm = 0;
-    rc = scan_pipeline(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, true, &nm, doc_off);
+    BatchVerdict v;
+    Publish publish{e, v};
+    rc = scan_pipeline(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, true, v, doc_off);
     if (rc) return rc;
-    if ((flags & GFT_SCAN_UNIQUE) && (rc = unique_pipeline(e, n_docs, &nm))) return rc;
-    if ((flags & GFT_POS_RUNES) && !(flags & GFT_SCAN_UNIQUE)) {
-        if (e->build_flags & GFT_POS_END) return fail(e, GFT_E_UNSUPPORTED, "GFT_POS_RUNES needs a GFT_POS_START engine (AnknownEngine reports where a match begins)");
-        if ((rc = rune_pipeline(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, nm))) return rc;
-    }
-    if ((rc = refine_nonascii(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags))) return rc;
+    uint64_t nm = v.total;
+    if ((rc = scan_post(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, nm, v))) return rc;
     e->h_match_off.assign(n_docs + 1, 0);
     e->h_term.assign(nm, 0);
     e->h_pos.assign(nm, 0);
@@ -1475,20 +1450,29 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
     HIP_TRY(hipStreamSynchronize(e->stream), "program upload");
     e->progs = std::move(ps);
     e->n_exprs = n_exprs; e->n_extra = n_extra; e->have_programs = true;
-    e->scan_valid_docs = ~0ull;          // positions may not have been written for the old program set
-    e->csr_valid = false;
+    e->pool.valid_docs = ~0ull;          // positions may not have been written for the old program set
+    e->pool.csr_valid = false;
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
-int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
-                       uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap) try {
-    if (!e || (n_docs && (!d_text_blob || !d_doc_off))) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
-    GFT_LOCK(e);
+namespace {
+// the seven-word read-back of the control block into a pinned slot, enqueued behind a batch's last kernel (into pinned
+// memory: a copy to pageable memory is staged by the runtime, ten microseconds on every batch)
+int enqueue_ctl_readback(gft_engine* e, uint64_t** slot) {
+    if (!*slot) HIP_TRY(hipHostMalloc((void**)slot, kCtlBytes, hipHostMallocDefault), "pinned alloc");
+    HIP_TRY(hipMemcpyAsync(*slot, e->d_ctl.p, kCtlWords * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
+    return GFT_OK;
+}
+
+// gft_process_device behind its lock and its in-flight guard: one batch from start to end, with its own synchronisations;
+// `v` = its verdict.  It reuses the control block, so its callers inside _begin / _end / _complete have every older
+// deferred batch's read-back on the host before they call.  They keep a status per batch: the function-try-block.
+int process_device_sync(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
+                        const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap, BatchVerdict& v) try {
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built) return fail(e, GFT_E_NOT_BUILT, "gft_build has not been called");
     if (!e->have_programs) return fail(e, GFT_E_NOT_BUILT, "gft_set_programs has not been called");
     if (n_docs && e->n_exprs && !d_hit_bitmap) return fail(e, GFT_E_INVALID, "null bitmap");
-    if (!pend_settled(e)) return fail(e, GFT_E_INVALID, "batches of gft_process_device_begin are in flight: gft_process_device_end (or _complete) first");
     DeviceGuard g(e->device);
     // what the host solves (normally nothing): expressions beyond the device solver's limits, and INORD expressions in
     // documents where the caller's matches make a slot's list non-ascending -- for that the caller's (device) arrays are
@@ -1520,57 +1504,57 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
     // units -> scan -> solve without a host round trip in between; one read-back at the end, and a second pass only when
     // this batch outgrew the unit table or the match pool the previous ones left behind
     for (int pass = 0; pass < 2; pass++) {
-        uint64_t nm = 0;
         ScanLaunch launch;
-        int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, plan.all_docs, &nm, nullptr, pass == 0 ? &launch : nullptr);
+        int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, plan.all_docs, v, nullptr, pass == 0 ? &launch : nullptr);
         if (rc) return rc;
         rc = solve_pipeline(e, n_docs, d_extra, d_hit_bitmap);
         if (rc) return rc;
         if (!launch.deferred) break;
-        // (into pinned memory: a copy to pageable memory is staged by the runtime, ten microseconds on every batch)
-        if (!e->pin_rb) HIP_TRY(hipHostMalloc((void**)&e->pin_rb, 64, hipHostMallocDefault), "pinned alloc");
-        HIP_TRY(hipMemcpyAsync(e->pin_rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
+        if ((rc = enqueue_ctl_readback(e, &e->pin_rb))) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
         bool again = false;
-        rc = deferred_interpret(e, e->pin_rb, launch, &again);
+        rc = deferred_interpret(e, e->pin_rb, launch, v, &again);
         if (rc) return rc;
         if (!again) break;
     }
     HIP_TRY(hipStreamSynchronize(e->stream), "process pipeline");
-    int rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags);
+    int rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags, v);
     if (rc) return rc;
     return host_eval(e, want_hx ? &hx : nullptr, n_docs, plan, nullptr, d_hit_bitmap);
+} GFT_CATCH(&e->err)
+}  // namespace
+
+int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                       uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap) try {
+    if (!e || (n_docs && (!d_text_blob || !d_doc_off))) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
+    GFT_LOCK(e);
+    if (!pend_settled(e)) return fail(e, GFT_E_INVALID, "batches of gft_process_device_begin are in flight: gft_process_device_end (or _complete) first");
+    BatchVerdict v;
+    const int rc = process_device_sync(e, d_text_blob, d_doc_off, n_docs, flags, d_extra, d_hit_bitmap, v);
+    e->reported = v;
+    return rc;
 } GFT_CATCH((e ? &e->err : nullptr))
 
 // ---- two batches in flight (at 125 000 documents -- one GPU's share of 1 M over 8 -- a step is 0.5 ms of
 // kernels, and the read-back of the control block plus the launches of the next step are a tenth of it) -----------------------
 namespace {
-// a batch in flight is complete: its status and its verdict (gft_last_nonascii) are kept in its slot until its _end
-void keep_verdict(const gft_engine* e, gft_engine::Pending& p, int rc) {
-    p.rc = rc; p.done = true;
-    p.nonascii = e->last_nonascii; p.nonascii_bits = e->last_nonascii_bits; p.text_lo = e->last_text_lo; p.text_hi = e->last_text_hi;
-}
-void restore_verdict(gft_engine* e, const gft_engine::Pending& p) {
-    e->last_nonascii = p.nonascii; e->last_nonascii_bits = p.nonascii_bits; e->last_text_lo = p.text_lo; e->last_text_hi = p.text_hi;
-}
+// a batch in flight is complete: its status is kept in its slot, beside its verdict, until its _end
+void settle(gft_engine::Pending& p, int rc) { p.rc = rc; p.done = true; }
 // Completes a deferred batch in place: the wait for its read-back, its verdict, and a second run when it outgrew the unit
 // table or the match pool it was launched with.  `young`: the batch begun after it, still in flight behind it on the stream
 // -- its read-back must have landed before a second run reuses the control block.
 void complete_pending(gft_engine* e, gft_engine::Pending& p, gft_engine::Pending* young) {
     if (p.done) return;
-    if (hipEventSynchronize(p.ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
+    if (hipEventSynchronize(p.ev) != hipSuccess) { settle(p, fail(e, GFT_E_HIP, "event wait")); return; }
     bool again = false;
-    int rc = deferred_interpret(e, p.rb, p.launch, &again);
+    int rc = deferred_interpret(e, p.rb, p.launch, p.verdict, &again);
     if (!rc && again) {
-        if (young && !young->done && hipEventSynchronize(young->ev) != hipSuccess) { keep_verdict(e, p, fail(e, GFT_E_HIP, "event wait")); return; }
-        const unsigned keep_count = e->pend_count;
-        e->pend_count = 0;                                      // (the synchronous entry point refuses to run beside batches in flight)
-        rc = gft_process_device(e, p.d_text, p.d_doc_off, p.n_docs, p.flags, nullptr, p.d_bitmap);
-        e->pend_count = keep_count;
+        if (young && !young->done && hipEventSynchronize(young->ev) != hipSuccess) { settle(p, fail(e, GFT_E_HIP, "event wait")); return; }
+        rc = process_device_sync(e, p.d_text, p.d_doc_off, p.n_docs, p.flags, nullptr, p.d_bitmap, p.verdict);
     } else if (!rc) {
-        rc = refine_nonascii(e, p.d_text, p.d_doc_off, p.n_docs, p.flags);
+        rc = refine_nonascii(e, p.d_text, p.d_doc_off, p.n_docs, p.flags, p.verdict);
     }
-    keep_verdict(e, p, rc);
+    settle(p, rc);
 }
 }  // namespace
 
@@ -1582,7 +1566,7 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
     if (e->pend_count == 2) return fail(e, GFT_E_INVALID, "gft_process_device_begin: two batches are in flight already (gft_process_device_end first)");
     const unsigned k = (e->pend_head + e->pend_count) % 2;
     gft_engine::Pending& pb = e->pend[k];
-    pb.done = false; pb.rc = GFT_OK;
+    pb.done = false; pb.rc = GFT_OK; pb.verdict = BatchVerdict();
     pb.d_text = d_text_blob; pb.d_doc_off = d_doc_off; pb.n_docs = n_docs; pb.flags = flags; pb.d_bitmap = d_hit_bitmap;
     const bool simple = n_docs && e->device >= 0 && e->built && e->have_programs && !(d_extra && d_extra->off) && e->progs.host_only.empty() &&
                         (!e->n_exprs || d_hit_bitmap);
@@ -1591,27 +1575,24 @@ int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const ui
         // an empty batch -- completes here; _end then only hands its status and verdict back.  A batch before it is
         // completed first: the synchronous path reuses the control block it is still to read)
         if (e->pend_count) { DeviceGuard g2(e->device); complete_pending(e, e->pend[e->pend_head], nullptr); }
-        const int rc = gft_process_device(e, d_text_blob, d_doc_off, n_docs, flags, d_extra, d_hit_bitmap);
-        keep_verdict(e, pb, rc);
+        settle(pb, process_device_sync(e, d_text_blob, d_doc_off, n_docs, flags, d_extra, d_hit_bitmap, pb.verdict));
         e->pend_count++;
         return GFT_OK;
     }
     DeviceGuard g(e->device);
-    uint64_t nm = 0;
-    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, false, &nm, nullptr, &pb.launch);
-    if (rc) { keep_verdict(e, pb, rc); e->pend_count++; return GFT_OK; }
+    int rc = scan_pipeline(e, d_text_blob, d_doc_off, n_docs, flags, false, pb.verdict, nullptr, &pb.launch);
+    if (rc) { settle(pb, rc); e->pend_count++; return GFT_OK; }
     rc = solve_pipeline(e, n_docs, nullptr, d_hit_bitmap);
     if (rc || !pb.launch.deferred) {
         // (sizes were not known yet: this batch ran with its own synchronisations, like gft_process_device's first pass)
         if (!rc) { rc = hipStreamSynchronize(e->stream) == hipSuccess ? GFT_OK : fail(e, GFT_E_HIP, "process pipeline"); }
-        if (!rc) rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags);
-        keep_verdict(e, pb, rc);
+        if (!rc) rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags, pb.verdict);
+        settle(pb, rc);
         e->pend_count++;
         return GFT_OK;
     }
-    if (!pb.rb) HIP_TRY(hipHostMalloc((void**)&pb.rb, 64, hipHostMallocDefault), "pinned alloc");
     if (!pb.ev) HIP_TRY(hipEventCreateWithFlags(&pb.ev, hipEventDisableTiming), "event");
-    HIP_TRY(hipMemcpyAsync(pb.rb, e->d_ctl.p, 7 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream), "readback");
+    if ((rc = enqueue_ctl_readback(e, &pb.rb))) return rc;
     HIP_TRY(hipEventRecord(pb.ev, e->stream), "event");
     e->pend_count++;
     return GFT_OK;
@@ -1628,7 +1609,7 @@ int gft_process_device_end(gft_engine* e) try {
         DeviceGuard g(e->device);
         complete_pending(e, pb, e->pend_count == 2 ? &e->pend[(e->pend_head + 1) % 2] : nullptr);
     }
-    restore_verdict(e, pb);
+    e->reported = pb.verdict;
     const int rc = pb.rc;
     e->pend_head = (e->pend_head + 1) % 2;
     e->pend_count--;
@@ -1640,12 +1621,9 @@ int gft_process_device_complete(gft_engine* e) try {
     GFT_LOCK(e);
     if (pend_settled(e)) return GFT_OK;
     DeviceGuard g(e->device);
-    // (what gft_last_nonascii says -- the verdict of the batch ended last -- stays)
-    gft_engine::Pending last;
-    keep_verdict(e, last, GFT_OK);
+    // (every batch keeps its status and its verdict for its own _end; what gft_last_nonascii says stays)
     for (unsigned i = 0; i < e->pend_count; i++)
         complete_pending(e, e->pend[(e->pend_head + i) % 2], i + 1 < e->pend_count ? &e->pend[(e->pend_head + i + 1) % 2] : nullptr);
-    restore_verdict(e, last);
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
@@ -1677,7 +1655,7 @@ int gft_process_again(gft_engine* e, uint64_t n_docs, const gft_extra_matches* e
     if (!e->peers.empty() && !e->in_multi) return multi_process_again(e, n_docs, extra, hit_bitmap);
     if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
     if (!e->built || !e->have_programs) return fail(e, GFT_E_NOT_BUILT, "engine not ready");
-    if (e->scan_valid_docs != n_docs || !n_docs) return fail(e, GFT_E_INVALID, "gft_process_again: no scan of these documents to reuse");
+    if (e->pool.valid_docs != n_docs || !n_docs) return fail(e, GFT_E_INVALID, "gft_process_again: no scan of these documents to reuse");
     DeviceGuard g(e->device);
     SyncOnExit drained(e);      // host buffers are read by asynchronous copies: drained on every way out
     gft_extra_matches dx;
@@ -1824,14 +1802,15 @@ int process_host(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_of
     HIP_TRY(e->d_bitmap.ensure(std::max<uint64_t>(n_docs * words, 1) * 4), "bitmap alloc");
     HostPlan plan;                        // the (expression, document) pairs the host solves (normally none)
     plan_host(e, pdx ? extra : nullptr, n_docs, plan);
-    uint64_t nm = 0;
+    BatchVerdict v;
+    Publish publish{e, v};
     // (expressions beyond the device solver's limits need every match with its position: the scan then leaves the CSR too)
-    rc = scan_pipeline(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, plan.all_docs, &nm, doc_off);
+    rc = scan_pipeline(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, plan.all_docs, v, doc_off);
     if (rc) return rc;
-    e->scan_valid_docs = n_docs;          // gft_process_again may reuse this scan
+    e->pool.valid_docs = n_docs;          // gft_process_again may reuse this scan
     rc = solve_pipeline(e, n_docs, pdx, e->d_bitmap.as<uint32_t>());
     if (rc) return rc;
-    if ((rc = refine_nonascii(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags))) return rc;
+    if ((rc = refine_nonascii(e, e->d_text.as<uint8_t>(), e->d_doc_off.as<uint64_t>(), n_docs, flags, v))) return rc;
     since("scanned and solved");
     if (sparse && plan.empty()) {
         // the rows are complete where they are: compacted on the device, only the CSR comes down
@@ -2174,6 +2153,11 @@ std::vector<gft_engine*> all_engines(gft_engine* e) {
     return v;
 }
 
+// behind a call that every device ran its share of: device 0's own verdict is this handle's, the peers' are OR-ed in
+void or_peer_verdicts(gft_engine* e) {
+    for (gft_engine* g : e->peers) e->reported.nonascii = e->reported.nonascii || g->reported.nonascii;
+}
+
 // contiguous document ranges of near-equal text bytes: device i owns documents [cut[i], cut[i+1])
 void split_by_bytes(const uint64_t* doc_off, uint64_t n_docs, size_t n, std::vector<uint64_t>& cut) {
     cut.assign(n + 1, n_docs);
@@ -2284,7 +2268,7 @@ int multi_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_o
     if (n_docs == 0) doc_off = kNoDocs;
     split_by_bytes(doc_off, n_docs, n, e->shard_cut);
     const uint64_t words = (e->n_exprs + 31) / 32;
-    e->last_nonascii = false;
+    e->reported.nonascii = false;
     const int rc = fan_out(e, [&](size_t i, gft_engine* g) {
         const uint64_t a = e->shard_cut[i], b = e->shard_cut[i + 1];
         std::vector<uint64_t> off(doc_off + a, doc_off + b + 1);        // this shard's documents, offsets from its first byte
@@ -2294,7 +2278,7 @@ int multi_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_o
         xs.set(extra, a, b);
         return gft_process(g, text_blob + base, off.data(), b - a, flags, xs.ptr, hit_bitmap ? hit_bitmap + a * words : nullptr);
     });
-    for (gft_engine* g : e->peers) e->last_nonascii = e->last_nonascii || g->last_nonascii;
+    or_peer_verdicts(e);
     return rc;
 }
 
@@ -2343,8 +2327,7 @@ int multi_scan(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off,
         at += part[i].n_matches;
     }
     e->h_match_off.swap(mo); e->h_term.swap(ti); e->h_pos.swap(po);
-    // (device 0's own flag is this handle's: it stays, the peers' are OR-ed in)
-    for (gft_engine* g : e->peers) e->last_nonascii = e->last_nonascii || g->last_nonascii;
+    or_peer_verdicts(e);
     out->n_docs = n_docs; out->n_matches = total;
     out->match_off = e->h_match_off.data(); out->term_id = e->h_term.data(); out->pos = e->h_pos.data();
     return GFT_OK;
@@ -2481,7 +2464,7 @@ int gft_process_device_multi(gft_engine* e, const uint8_t* const* d_text, const 
             HIP_TRY(hipStreamSynchronize(e->stream), "bitmap gather");
         }
     }
-    for (gft_engine* g : e->peers) e->last_nonascii = e->last_nonascii || g->last_nonascii;   // (device 0's own flag stays)
+    or_peer_verdicts(e);
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 

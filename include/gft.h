@@ -213,9 +213,11 @@ int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t
  * table holds) completes inside _begin; _end then only hands its status and its verdict back.  A batch is run again when
  * its scan overflowed the match pool IT was launched with, even if another batch has grown the pool since.  Single-device
  * handles.  Between _begin and _end no other entry point of the handle, except: _complete completes every batch in flight
- * in place (each keeps its status and verdict for its own _end; gft_last_nonascii keeps saying what it said), after which
+ * in place (each keeps its status and verdict for its own _end), after which
  * the synchronous entry points (gft_process, gft_process_device) may run -- the finder repeats a batch that leaves ASCII
- * through them while a younger batch is in flight; gft_compact_device with total == NULL only enqueues (below). */
+ * through them while a younger batch is in flight; gft_compact_device with total == NULL only enqueues (below).
+ * gft_last_nonascii is the verdict of the batch whose _end, or whose synchronous call, returned last: _begin and _complete
+ * do not touch it. */
 int gft_process_device_begin(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                              uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap);
 int gft_process_device_end(gft_engine* e);
@@ -443,6 +445,20 @@ int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, 
 int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
                      uint64_t lds_max, const char* forced_kernel, const char** kernel, uint8_t* out, uint64_t cap, uint64_t* needed,
                      char* err, uint64_t err_cap);
+
+/* The judgement on a batch alone, on the host (csrc/batch_verdict.cpp): decodes the seven 64-bit words of a control-block
+ * read-back and judges them against what a deferred scan launch knew -- single / epoch (its unit table came from the
+ * one-launch path, which raises the block's flags to that number), n_docs, and the unit_cap, pool_cap and static_slabs IT
+ * ran with -- by the very functions gft_process_device and _end call.  *kind = 0 accept, 1 run again the general way, 2 run
+ * again with a match pool of *pool_need entries (0 otherwise), 3 invalid (its text in err, nullable, err_cap bytes);
+ * verdict[6] = nonascii, nonascii bits, text_lo, text_hi, n_units, total.  No HIP device is needed and no handle. */
+int gft_debug_judge_batch(const uint64_t* ctl_words, int single, uint32_t epoch, uint64_t n_docs, uint64_t unit_cap, uint64_t pool_cap,
+                          uint64_t static_slabs, int* kind, uint64_t* pool_need, uint64_t* verdict, char* err, uint64_t err_cap);
+/* ... and what a completed batch of `total` matches over the text range [text_lo, text_hi) teaches the next ones under
+ * `kernel` ("dfa" .. "scan5"; fifo_cap: entries of a wave's LDS match fifo, ordered: the GFT_SCAN_ORDERED path): *unit_max
+ * (bytes per work unit on scan2's tables) and *scan4_density go in as they were and come out as learnt. */
+int gft_debug_learn(const char* kernel, uint32_t fifo_cap, int ordered, uint64_t total, uint64_t text_lo, uint64_t text_hi,
+                    uint32_t* unit_max, double* scan4_density);
 
 /* The solver's program compiler alone, on the host: the set is compiled by the very function gft_set_programs calls
  * (csrc/program_set.cpp: check, fusion with Sethi-Ullman operand order, control-bit device words, evaluation order, blocks of

@@ -289,6 +289,36 @@ def test_each_end_reports_its_own_verdict(setup, host_set):
         eng.close()
 
 
+def test_synchronous_batch_between_complete_and_the_ends():
+    """begin(A: upper-case non-ASCII), begin(B: ASCII), _complete, gft_process_device(C: lower-case Latin-1), end, end -- what
+    the finder does when it repeats a batch beside younger ones in flight.  gft_last_nonascii right after the synchronous call
+    is C's verdict; A and B kept theirs in their slots while C was judged, and each _end hands its own back."""
+    L = _lib()
+    kw = _keywords(SMALL_EXPRS)
+    o = Oracle(kw)
+    o.set_expressions(SMALL_EXPRS, False)
+    words = 1
+    a, b, c = (_class_batch(k, 4, o) for k in ("upper", "ascii", "latin1"))
+    assert (a.verdict, b.verdict, c.verdict) == (1, 0, 0)
+    eng = _engine(kw, SMALL_EXPRS)
+    bma, bmb, bmc = a.bitmap(words), b.bitmap(words), c.bitmap(words)
+    for _ in range(3):                      # sizes learnt: A and B are deferred
+        eng.process_device(b.t.data_ptr(), b.o.data_ptr(), b.n, bmb.data_ptr(), fold=True)
+    bmb.zero_()
+    for x, bm in ((a, bma), (b, bmb)):
+        assert L.gft_process_device_begin(eng._h, x.t.data_ptr(), x.o.data_ptr(), x.n, FOLD, None, bm.data_ptr()) == 0
+    assert L.gft_process_device_complete(eng._h) == 0
+    assert L.gft_process_device(eng._h, c.t.data_ptr(), c.o.data_ptr(), c.n, FOLD, None, bmc.data_ptr()) == 0
+    assert L.gft_last_nonascii(eng._h) == c.verdict, "after the synchronous call"
+    assert L.gft_process_device_end(eng._h) == 0
+    assert L.gft_last_nonascii(eng._h) == a.verdict, "end of A"
+    assert L.gft_process_device_end(eng._h) == 0
+    assert L.gft_last_nonascii(eng._h) == b.verdict, "end of B"
+    for x, bm in ((a, bma), (b, bmb), (c, bmc)):
+        _check(bm, x)
+    eng.close()
+
+
 # ---- a pipelined Finder over text that leaves ASCII ------------------------------------------------------------------------
 def test_pipelined_finder_over_mixed_text():
     """bench.py's step(): two result buffers, always one batch begun ahead of the one that ends.  A batch with upper-case
