@@ -111,6 +111,12 @@ def one_process(eng, seed, it):
     if all(32 <= c < 127 and c not in b'"\\' for t in tl for c in t):
         extra = [nested(int(rng.choice([1, 2, 3, 6, 20])), int(rng.integers(2))) for _ in range(int(rng.integers(0, 40)))]
         extra += [nested(int(rng.integers(1, 6)), 2) for _ in range(int(rng.integers(0, 6)))]
+        # ... and INORD groups that are random AND/OR trees (tests/inord_trees.py), the ones with a pair per lane
+        import inord_trees
+        for _ in range(int(rng.integers(0, 8))):
+            e = inord_trees.gen_expr(rng, tl, lambda: int(rng.integers(2, 13)), p_or=float(rng.choice([0.2, 0.5, 0.8])))
+            if inord_trees.classify(inord_trees.words_of(e)) == inord_trees.NARROW:
+                extra.append(e)
         for e in extra:
             exprs.insert(int(rng.integers(len(exprs) + 1)), e)
         n_exprs = len(exprs)
