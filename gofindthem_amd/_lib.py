@@ -113,6 +113,10 @@ SYMBOLS = {
     "gft_regex_required_literals": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_dsl_tokens": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_to_lower": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "gft_to_lower_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_debug_lower_rune": (_u32, [_u32]),
+    "gft_debug_emulate_to_lower": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_finder_lowered_batches": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_tables": (_i, [_vp, _vp, _u32, _vp, _u64, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp, _u64, C.POINTER(_u64), _vp, _u64]),
     "gft_debug_judge_batch": (_i, [_vp, _i, _u32, _u64, _u64, _u64, _u64, C.POINTER(_i), C.POINTER(_u64), _vp, _vp, _u64]),

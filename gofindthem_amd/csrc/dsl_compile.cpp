@@ -58,7 +58,6 @@ void encode_rune(int32_t cp, std::string& out) {
     }
 }
 
-struct LowerPair { int32_t from, to; };
 const LowerPair kLower[] = {
 #include "unicode_lower.inc"
 };
@@ -75,6 +74,7 @@ std::string rune_str(int32_t cp) { std::string s; encode_rune(cp, s); return s; 
 }  // namespace
 
 int32_t DecodeRune(const std::string& s, size_t i, size_t* adv) { return decode_rune(s, i, adv); }
+const LowerPair* LowerPairs(size_t* n) { *n = sizeof(kLower) / sizeof(kLower[0]); return kLower; }
 void EncodeRune(int32_t cp, std::string& out) { encode_rune(cp, out); }
 
 // ---- regex prefilter literals ---------------------------------------------------------------------------------------

@@ -63,6 +63,10 @@ std::vector<std::string> RegexRequiredLiterals(const std::string& pattern, size_
 // strings.ToLower for the parser's literals and for document text (Unicode simple case mapping)
 std::string ToLower(const std::string& s);
 bool IsAscii(const std::string& s);
+// the mapping behind it: the (code point, lower-case form) pairs of unicode_lower.inc, ascending by code point, ASCII not
+// among them -- what the device's two-level table is derived from (lower_table.hpp)
+struct LowerPair { int32_t from, to; };
+const LowerPair* LowerPairs(size_t* n);
 
 // tree -> postfix words of include/gft.h; slot_of maps a literal to its slot
 void CompileProgram(const Expression& e, const std::function<uint32_t(const std::string&)>& slot_of,

@@ -4,11 +4,13 @@
 
 #include <mutex>
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <thread>
 
 #include "compact_host.hpp"
 #include "gft_guard.hpp"
+#include "gft_tolower.hpp"
 
 namespace gft {
 
@@ -97,7 +99,10 @@ Error CallbackRgxEngine::FindRegexes(const std::string& t, std::vector<Match>& m
 // ---- Finder ----------------------------------------------------------------------------------------------
 Finder::Finder(SubstringEngine* subEng, RegexEngine* rgxEng, bool caseSensitive, GpuEngine* gpu)
     : subEng_(subEng), rgxEng_(rgxEng), caseSensitive_(caseSensitive), gpu_(gpu),
-      gpu_sub_(static_cast<SubstringEngine*>(gpu) == subEng) {}
+      gpu_sub_(static_cast<SubstringEngine*>(gpu) == subEng) {
+    const char* v = getenv("GFT_DEVICE_TOLOWER");
+    device_tolower_ = !(v && atoi(v) == 0);
+}
 
 void Finder::debug_add_literal(int which, const std::string& lit) {
     if ((which ? rgx_set_ : kw_set_).insert(lit).second) (which ? regexes_ : keywords_).push_back(lit);
@@ -528,23 +533,35 @@ Error Finder::ProcessDeviceEnd() {
 }
 
 Error Finder::repeat_if_not_ascii(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
-    if (!caseSensitive_ && n_docs && gft_last_nonascii(gpu_->handle())) {
-        // The kernels lower-case A-Z only; the reference runs strings.ToLower (finder.go:140-142), which also maps
-        // non-ASCII upper-case letters, rewrites invalid UTF-8 and may change byte lengths.  A batch that holds bytes
-        // >= 0x80 is therefore repeated through the host path: text back to the host, ToLower per document, bitmap up.
-        std::vector<uint64_t> off(n_docs + 1);
-        if (hipMemcpy(off.data(), d_doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { last_code_ = GFT_E_HIP; return "device-to-host copy failed"; }
-        std::vector<uint8_t> text((size_t)(off[n_docs] - off[0]) + 1);
-        if (off[n_docs] > off[0] &&
-            hipMemcpy(text.data(), d_blob + off[0], (size_t)(off[n_docs] - off[0]), hipMemcpyDeviceToHost) != hipSuccess) { last_code_ = GFT_E_HIP; return "device-to-host copy failed"; }
-        const uint64_t base = off[0];
-        for (auto& o : off) o -= base;
-        const size_t words = (expressions_.size() + 31) / 32;
-        std::vector<uint32_t> bm((size_t)n_docs * words + 1);
-        Error err = ProcessTexts(text.data(), off.data(), n_docs, bm.data());
-        if (!err.empty()) return err;
-        if (words && hipMemcpy(d_bitmap, bm.data(), (size_t)n_docs * words * 4, hipMemcpyHostToDevice) != hipSuccess) { last_code_ = GFT_E_HIP; return "host-to-device copy failed"; }
+    if (caseSensitive_ || !n_docs || !gft_last_nonascii(gpu_->handle())) return "";
+    // The scan kernels lower-case A-Z only; the reference runs strings.ToLower (finder.go:140-142), which also maps
+    // non-ASCII upper-case letters, rewrites invalid UTF-8 and may change byte lengths.  A batch that holds such text is
+    // therefore lowered in full and scanned again.
+    if (device_tolower_ && gft_n_devices(gpu_->handle()) == 1) {
+        // on the device (gft_tolower.hip), into buffers of the engine: no text and no bitmap crosses the link
+        const uint8_t* d_low = nullptr;
+        const uint64_t* d_low_off = nullptr;
+        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
+        if (rc) return fail_gft(rc);
+        rc = gft_process_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, nullptr, d_bitmap);
+        if (rc) return fail_gft(rc);
+        lowered_on_device++;
+        return "";
     }
+    // on the host (GFT_DEVICE_TOLOWER=0, handles over several devices): text back to the host, ToLower per document, bitmap up
+    std::vector<uint64_t> off(n_docs + 1);
+    if (hipMemcpy(off.data(), d_doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost) != hipSuccess) { last_code_ = GFT_E_HIP; return "device-to-host copy failed"; }
+    std::vector<uint8_t> text((size_t)(off[n_docs] - off[0]) + 1);
+    if (off[n_docs] > off[0] &&
+        hipMemcpy(text.data(), d_blob + off[0], (size_t)(off[n_docs] - off[0]), hipMemcpyDeviceToHost) != hipSuccess) { last_code_ = GFT_E_HIP; return "device-to-host copy failed"; }
+    const uint64_t base = off[0];
+    for (auto& o : off) o -= base;
+    const size_t words = (expressions_.size() + 31) / 32;
+    std::vector<uint32_t> bm((size_t)n_docs * words + 1);
+    Error err = ProcessTexts(text.data(), off.data(), n_docs, bm.data());
+    if (!err.empty()) return err;
+    if (words && hipMemcpy(d_bitmap, bm.data(), (size_t)n_docs * words * 4, hipMemcpyHostToDevice) != hipSuccess) { last_code_ = GFT_E_HIP; return "host-to-device copy failed"; }
+    lowered_on_host++;
     return "";
 }
 
@@ -762,6 +779,13 @@ int gft_finder_process_device_end(gft_finder* f) try {
     if (!f) return GFT_E_INVALID;
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->ProcessDeviceEnd(), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_lowered_batches(const gft_finder* f, uint64_t* on_device, uint64_t* on_host) try {
+    if (!f || !f->finder || !on_device || !on_host) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    *on_device = f->finder->lowered_on_device; *on_host = f->finder->lowered_on_host;
+    return GFT_OK;
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_debug_add_literal(gft_finder* f, int which, const uint8_t* lit, uint32_t len) try {

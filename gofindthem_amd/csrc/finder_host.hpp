@@ -124,7 +124,7 @@ public:
     const std::vector<std::string>& tags() const { return tags_; }
     const std::vector<uint32_t>& tag_ids() const { return tag_ids_; }
     Error ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
-    // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, host ToLower repeat included
+    // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();
     Error ForceBuild();
@@ -139,6 +139,7 @@ public:
     const std::vector<ExprWrapper>& expressions() const { return expressions_; }
     int last_code() const { return last_code_; }
     uint64_t last_regex_docs = 0;        // documents the host regex engine saw in the last prefiltered ProcessTexts
+    uint64_t lowered_on_device = 0, lowered_on_host = 0;   // batches of ProcessDevice / ProcessDeviceEnd repeated, by path
     bool force_host_lower_ = false;      // ProcessTexts is repeating a batch whose text the device cannot fold (finder_host.cpp)
 
     // test hooks (finder_test.go pokes the struct fields directly)
@@ -191,6 +192,7 @@ private:
     struct Begun { const uint8_t* d_blob; const uint64_t* d_doc_off; uint64_t n_docs; uint32_t* d_bitmap; };
     Begun begun_[2] = {};                // batches of ProcessDeviceBegin that ProcessDeviceEnd has not completed yet
     unsigned first_begun_ = 0, n_begun_ = 0;
+    bool device_tolower_;                // GFT_DEVICE_TOLOWER (read at creation; 0: a batch that leaves ASCII is lowered on the host)
     Error repeat_if_not_ascii(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
 };
 

@@ -24,6 +24,7 @@
 #include "copy_pool.hpp"
 #include "gft_guard.hpp"
 #include "gft_kernels.hpp"
+#include "gft_tolower.hpp"
 #include "host_solve.hpp"
 #include "program_set.hpp"
 #include "table_set.hpp"
@@ -177,6 +178,11 @@ struct gft_engine {
     DevBuf d_labels, d_cp_cnt, d_cp_partial, d_cp_row_off, d_cp_idx, d_cp_label;
     std::vector<uint64_t> h_row_off;
     std::vector<uint32_t> h_expr_idx, h_label, h_sparse_bm;
+    // strings.ToLower on the device (gft_tolower.hip): the mapping table (uploaded with the first call), a unit table, counts
+    // and scan partials of its own, and the lowered batch the finder scans again (gft_lower_owned)
+    bool lower_table_up = false;
+    DevBuf d_lw_page, d_lw_delta, d_lw_doc_units, d_lw_unit_base, d_lw_units, d_lw_partial, d_lw_unit_cnt, d_lw_unit_out, d_lw_ctl,
+        d_lw_text, d_lw_off;
 
     // profiling
     int profiling = 0;                     // gft_profile_enable: 0 off, 1 every category, 2 the scan kernel only
@@ -1031,7 +1037,9 @@ void gft_engine_destroy(gft_engine* e) {
                          &e->d_pool_term, &e->d_pool_pos, &e->d_unit_start, &e->d_unit_count, &e->d_unit_out,
                          &e->d_term, &e->d_pos, &e->d_match_off, &e->d_text, &e->d_doc_off, &e->d_bitmap, &e->d_xoff,
                          &e->d_xslot, &e->d_xpos, &e->d_uq_first, &e->d_uq_cnt, &e->d_uq_off, &e->d_uq_term, &e->d_patch, &e->d_rn_cnt, &e->d_rn_base, &e->d_rn_starts, &e->d_rn_prefix,
-                         &e->d_labels, &e->d_cp_cnt, &e->d_cp_partial, &e->d_cp_row_off, &e->d_cp_idx, &e->d_cp_label};
+                         &e->d_labels, &e->d_cp_cnt, &e->d_cp_partial, &e->d_cp_row_off, &e->d_cp_idx, &e->d_cp_label,
+                         &e->d_lw_page, &e->d_lw_delta, &e->d_lw_doc_units, &e->d_lw_unit_base, &e->d_lw_units, &e->d_lw_partial,
+                         &e->d_lw_unit_cnt, &e->d_lw_unit_out, &e->d_lw_ctl, &e->d_lw_text, &e->d_lw_off};
         for (DevBuf* b : all) b->release();
         for (int k = 0; k < 2; k++) {
             if (e->pin[k]) (void)hipHostFree(e->pin[k]);
@@ -1878,6 +1886,135 @@ int gft_compact_device(gft_engine* e, const uint32_t* d_hit_bitmap, uint64_t n_d
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
+
+namespace {
+
+// strings.ToLower of a batch, first half: the unit table, the count pass, the prefix sum and d_out_off (complete when this
+// returns GFT_OK; the stream has drained).  *n_units / *total: what lower_write needs and what the caller sizes its buffer by.
+// d_out / cap take part in the overlap check only.
+int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, const uint8_t* d_out, uint64_t cap,
+                uint64_t* d_out_off, uint64_t* n_units, uint64_t* total) {
+    hipStream_t st = e->stream;
+    *n_units = 0; *total = 0;
+    if (!n_docs) {
+        HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, st), "lower offsets");
+        HIP_TRY(hipStreamSynchronize(st), "lower offsets");
+        return GFT_OK;
+    }
+    if (!e->lower_table_up) {
+        const LowerTableHost& t = lower_table_host();
+        int rc = upload(e, e->d_lw_page, t.page, "lower table upload");
+        if (!rc) rc = upload(e, e->d_lw_delta, t.delta, "lower table upload");
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(st), "lower table upload");
+        e->lower_table_up = true;
+    }
+    const LowerTable T{e->d_lw_page.as<uint16_t>(), e->d_lw_delta.as<int32_t>(), (uint32_t)lower_table_host().page.size()};
+    // d_lw_ctl: [0] units, [1] first and [2] last text offset (k_pack_ctl), [3] flags: 1 a document of 4 GiB or more or
+    // descending offsets (k_unit_count), 2 a lowered document of 4 GiB or more (k_lower_offsets)
+    HIP_TRY(e->d_lw_ctl.ensure(32), "lower alloc");
+    HIP_TRY(e->d_lw_doc_units.ensure(n_docs * 4), "lower alloc");
+    HIP_TRY(e->d_lw_unit_base.ensure((n_docs + 1) * 8), "lower alloc");
+    HIP_TRY(e->d_lw_partial.ensure(scan_partials_needed(n_docs) * 8), "lower alloc");
+    uint64_t* ctl = e->d_lw_ctl.as<uint64_t>();
+    uint32_t* flags = reinterpret_cast<uint32_t*>(ctl + 3);
+    uint64_t h_ctl[4] = {0, 0, 0, 0};
+    {
+        ProfScope ps(e, "aux");
+        HIP_TRY(hipMemsetAsync(ctl, 0, 32, st), "lower units");
+        HIP_TRY(launch_unit_count(d_doc_off, n_docs, kLowerUnitMax, e->d_lw_doc_units.as<uint32_t>(), flags, st), "lower units");
+        HIP_TRY(launch_exclusive_scan(e->d_lw_doc_units.as<uint32_t>(), n_docs, e->d_lw_unit_base.as<uint64_t>(), e->d_lw_partial.as<uint64_t>(), st),
+                "lower units");
+        HIP_TRY(launch_pack_ctl(e->d_lw_unit_base.as<uint64_t>(), d_doc_off, n_docs, ctl, st), "lower units");
+    }
+    HIP_TRY(hipMemcpyAsync(h_ctl, ctl, 32, hipMemcpyDeviceToHost, st), "lower units");
+    HIP_TRY(hipStreamSynchronize(st), "lower units");
+    if (h_ctl[3] & 1) return fail(e, GFT_E_INVALID, "gft_to_lower_device: document offsets descend, or a document of 4 GiB or more");
+    if (lower_buffers_overlap(d_text, h_ctl[1], h_ctl[2], d_doc_off, n_docs, d_out, cap, d_out_off))
+        return fail(e, GFT_E_INVALID, "gft_to_lower_device: the output overlaps the input");
+    const uint64_t nu = h_ctl[0];
+    HIP_TRY(e->d_lw_units.ensure(nu * sizeof(Unit)), "lower alloc");
+    HIP_TRY(e->d_lw_unit_cnt.ensure(nu * 4), "lower alloc");
+    HIP_TRY(e->d_lw_unit_out.ensure((nu + 1) * 8), "lower alloc");
+    HIP_TRY(e->d_lw_partial.ensure(scan_partials_needed(nu) * 8), "lower alloc");
+    {
+        ProfScope ps(e, "aux");
+        HIP_TRY(launch_unit_fill(d_doc_off, n_docs, e->d_lw_unit_base.as<uint64_t>(), e->d_lw_units.as<Unit>(), kLowerUnitMax, st, nu), "lower units");
+    }
+    {
+        ProfScope ps(e, "lower_count");
+        HIP_TRY(launch_lower_count(d_text, d_doc_off, e->d_lw_units.as<Unit>(), nu, T, e->d_lw_unit_cnt.as<uint32_t>(), e->n_cus, st), "lower count");
+    }
+    {
+        ProfScope ps(e, "lower_scan");
+        HIP_TRY(launch_exclusive_scan(e->d_lw_unit_cnt.as<uint32_t>(), nu, e->d_lw_unit_out.as<uint64_t>(), e->d_lw_partial.as<uint64_t>(), st), "lower scan");
+        HIP_TRY(launch_lower_offsets(e->d_lw_unit_base.as<uint64_t>(), e->d_lw_unit_out.as<uint64_t>(), n_docs, d_out_off, flags, st), "lower scan");
+    }
+    HIP_TRY(hipMemcpyAsync(h_ctl, e->d_lw_unit_out.as<uint64_t>() + nu, 8, hipMemcpyDeviceToHost, st), "lower total");
+    HIP_TRY(hipMemcpyAsync(h_ctl + 3, ctl + 3, 8, hipMemcpyDeviceToHost, st), "lower total");
+    HIP_TRY(hipStreamSynchronize(st), "lower count");
+    if (h_ctl[3] & 2) return fail(e, GFT_E_INVALID, "gft_to_lower_device: the lower-case form of a document has 4 GiB or more");
+    *n_units = nu; *total = h_ctl[0];
+    return GFT_OK;
+}
+
+// ... second half: the write pass over the unit table and prefix sums lower_count left in the engine.  Nothing waits here.
+int lower_write(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_units, uint8_t* d_out, uint64_t cap) {
+    if (!n_units || !cap) return GFT_OK;
+    const LowerTable T{e->d_lw_page.as<uint16_t>(), e->d_lw_delta.as<int32_t>(), (uint32_t)lower_table_host().page.size()};
+    ProfScope ps(e, "lower_write");
+    HIP_TRY(launch_lower_write(d_text, d_doc_off, e->d_lw_units.as<Unit>(), n_units, T, e->d_lw_unit_out.as<uint64_t>(), d_out, cap, e->n_cus,
+                               e->stream), "lower write");
+    return GFT_OK;
+}
+
+int lower_entry_checks(gft_engine* e, const char* who) {
+    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, std::string(who) + ": single-device handles only");
+    if (e->device < 0) return fail(e, GFT_E_HIP, "no HIP device available");
+    if (!pend_settled(e))
+        return fail(e, GFT_E_INVALID, std::string(who) + ": batches of gft_process_device_begin are in flight: gft_process_device_end (or _complete) first");
+    return GFT_OK;
+}
+
+}  // namespace
+
+int gft_to_lower_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_out, uint64_t cap,
+                        uint64_t* d_out_off, uint64_t* total) try {
+    if (!e || !d_out_off || (n_docs && !d_doc_off)) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
+    GFT_LOCK(e);
+    if (cap && !d_out) return fail(e, GFT_E_INVALID, "gft_to_lower_device: cap bytes but no output buffer");
+    int rc = lower_entry_checks(e, "gft_to_lower_device");
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    uint64_t n_units = 0, n_total = 0;
+    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, d_out, cap, d_out_off, &n_units, &n_total))) return rc;
+    if (total) *total = n_total;
+    if ((rc = lower_write(e, d_text_blob, d_doc_off, n_units, d_out, cap))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream), "lower write");
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int gft_lower_owned(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint8_t** d_lowered,
+                    const uint64_t** d_lowered_off) try {
+    if (!e || !d_lowered || !d_lowered_off || (n_docs && !d_doc_off)) return e ? fail(e, GFT_E_INVALID, "null argument") : GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = lower_entry_checks(e, "lowering a batch");
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    auto room = [&](DevBuf& b, uint64_t bytes) {
+        const hipError_t h = b.ensure(bytes);
+        if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, "no device memory for the lowered batch"); }
+        return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, "lower alloc");
+    };
+    if ((rc = room(e->d_lw_off, (n_docs + 1) * 8))) return rc;
+    uint64_t n_units = 0, total = 0;
+    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, nullptr, 0, e->d_lw_off.as<uint64_t>(), &n_units, &total))) return rc;
+    if ((rc = room(e->d_lw_text, total + 64))) return rc;
+    if ((rc = lower_write(e, d_text_blob, d_doc_off, n_units, e->d_lw_text.as<uint8_t>(), total))) return rc;
+    *d_lowered = e->d_lw_text.as<uint8_t>();
+    *d_lowered_off = e->d_lw_off.as<uint64_t>();
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_emulate_scan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* text,
                            uint32_t len, uint32_t lo, uint32_t flags, uint32_t scan_flags, uint32_t* out_term,

@@ -179,6 +179,14 @@ class Engine:
                                                C.byref(total) if want_total else None))
         return int(total.value) if want_total else None
 
+    def to_lower_device(self, d_text_ptr, d_doc_off_ptr, n_docs, d_out_ptr, cap, d_out_off_ptr):
+        """strings.ToLower of a device-resident batch (gft_to_lower_device) -> the lowered size.  d_out_off (n_docs + 1 u64) is
+        always complete; bytes at output positions >= cap are not written; d_out_ptr None with cap 0 counts only"""
+        total = C.c_uint64(0)
+        self._check(self._L.gft_to_lower_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, d_out_ptr, cap, d_out_off_ptr,
+                                                C.byref(total)))
+        return int(total.value)
+
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""
         n_docs = len(doc_off) - 1

@@ -336,6 +336,13 @@ class Finder:
     def ProcessDeviceEnd(self):
         self._check(self._L.gft_finder_process_device_end(self._h))
 
+    def lowered_batches(self):
+        """-> (on_device, on_host): batches ProcessDevice / ProcessDeviceEnd repeated because their text left ASCII, by the
+        path that lowered them (the device's ToLower kernels; the host with GFT_DEVICE_TOLOWER=0 or several devices)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._check(self._L.gft_finder_lowered_batches(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
     def engine_handle(self):
         return self._L.gft_finder_engine(self._h)
 

@@ -53,7 +53,8 @@ typedef enum gft_status {
 /* gft_scan / gft_process flags */
 #define GFT_FOLD_ASCII 1u /* lower-case A-Z while reading the text (finder.go:140-142 for ASCII input).  This IS
                            * strings.ToLower only while the text is ASCII: the kernels notice bytes >= 0x80 on their way
-                           * (gft_last_nonascii), and the finder entry points then fold such a batch on the host instead */
+                           * (gft_last_nonascii), and the finder entry points then lower such a batch in full first
+                           * (gft_to_lower_device) and scan it again */
 
 #define GFT_SCAN_UNIQUE 2u /* gft_scan / gft_scan_device: CloudflareEngine's output instead of CloudflareForkEngine's
                             * (finder/substringEngine.go:77-86): every term that occurs in a document once, in the order
@@ -170,7 +171,8 @@ uint32_t gft_n_host_exprs(const gft_engine* e);
  * sequences C2 80..BF and C3 9F..BF / C3 97 (Latin-1 signs and LOWER-case letters) -- i.e. possibly an upper-case
  * non-ASCII letter, a rune whose lower-case form has another length, or invalid UTF-8.  The scan kernels notice high
  * bytes on their way; only such a batch pays one more pass over its text for this answer.
- * gft_finder_process_device checks it and repeats an unsafe batch through the host's ToLower. */
+ * gft_finder_process_device checks it, lowers an unsafe batch with gft_to_lower_device's kernels and scans the lowered text
+ * again; gft_to_lower_device does not touch it. */
 int gft_last_nonascii(const gft_engine* e);
 /* which scan kernel the built dictionary runs on: "scan5" (suffix-window kernel, one filter probe per two bytes: the
  * default wherever the long-term tables exist), "scan3" (stride-2 suffix-window kernel, any alphabet: the fallback) or
@@ -260,6 +262,31 @@ int gft_process_sparse(gft_engine* e, const uint8_t* text_blob, const uint64_t* 
 int gft_debug_compact_host(const uint32_t* bitmap, uint64_t n_docs, uint32_t n_exprs, const uint32_t* labels, uint64_t* row_off,
                            uint32_t* expr_idx, uint32_t* label, uint64_t cap, uint64_t* total);
 
+/* ---- strings.ToLower over a batch on the device (finder/finder.go:140-142; csrc/gft_tolower.hip) -------------------------
+ * (d_text_blob, d_doc_off [n_docs + 1]) -> (d_out, d_out_off [n_docs + 1]): byte for byte what gft_to_lower gives for every
+ * document, concatenated, d_out_off[0] = 0.  Go's decoder: an invalid byte -- a continuation byte out of place, C0 / C1,
+ * F5..FF, an overlong form, a surrogate, F4 90.., a lead byte that ITS DOCUMENT does not continue -- becomes one U+FFFD; the
+ * bytes of a neighbouring document never complete a rune.  Lengths change (U+0130, U+212A shrink, U+023A, U+023E grow, an
+ * invalid byte becomes three): the output has at most three times the input's bytes.  Three passes on the engine's stream
+ * (gft_profile_read: "lower_count", "lower_scan", "lower_write"); the contract mirrors gft_compact_device: d_out_off is always
+ * complete, a byte whose output position is >= cap is NOT written and nothing is stored at or past d_out + cap, GFT_OK is
+ * returned in both cases and *total (host, nullable) receives the lowered size -- the caller compares it with cap and calls
+ * again.  d_out == NULL with cap == 0 counts only.  The call waits for the stream.  d_text_blob must be readable for 64 bytes
+ * past d_doc_off[n_docs], as for the scans; the output (d_out, d_out_off) may not overlap the input: GFT_E_INVALID, as for
+ * offsets that descend and for a document, or the lower-case form of one, of 4 GiB or more.  n_docs == 0 is valid.  Handles
+ * over several devices: GFT_E_UNSUPPORTED.  Between gft_process_device_begin and _end only after _complete.  Needs no
+ * dictionary, leaves gft_last_nonascii alone, and the handle stays usable after any error. */
+int gft_to_lower_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_out,
+                        uint64_t cap, uint64_t* d_out_off, uint64_t* total);
+/* The same on the host, no HIP device needed (tests): the lower-case form of ONE code point looked up in the two-level table
+ * the kernels read (derived from the pairs behind gft_to_lower when first used) ... */
+uint32_t gft_debug_lower_rune(uint32_t cp);
+/* ... and gft_to_lower_device's count / prefix / write walk, unit by unit and 16-byte piece by piece through the source the
+ * kernels are compiled from (csrc/gft_tolower_piece.hpp).  All pointers host; same contract and refusals (the 64 bytes of
+ * slack are not asked for here). */
+int gft_debug_emulate_to_lower(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* out, uint64_t cap,
+                               uint64_t* out_off, uint64_t* total);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -320,13 +347,20 @@ int64_t gft_finder_expression_tag_id(const gft_finder* f, uint32_t expr_i);   /*
  * and only these arrays are downloaded (gft_process_sparse). */
 int gft_finder_process_texts_sparse(gft_finder* f, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs,
                                     const uint64_t** row_off, const uint32_t** expr_idx, const uint32_t** tag_id);
-/* Same with the corpus resident in HBM (GPU substring engine, no regex terms). */
+/* Same with the corpus resident in HBM (GPU substring engine, no regex terms).  A batch that leaves ASCII
+ * (gft_last_nonascii) is lowered on the device into a buffer of the engine (gft_to_lower_device's kernels) and scanned again
+ * from there: neither text nor bitmap crosses the link.  No device memory for that buffer: GFT_E_NOMEM.  GFT_DEVICE_TOLOWER=0
+ * in the environment when the finder is created (and every finder over several devices): such a batch goes to the host
+ * instead -- text down, ToLower per document, scan, bitmap up; the results are the same. */
 int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint32_t* d_hit_bitmap);
-/* ... pipelined (gft_process_device_begin / _end): _end also repeats a batch that left ASCII through the host's ToLower */
+/* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
+ * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                                     uint32_t* d_hit_bitmap);
 int gft_finder_process_device_end(gft_finder* f);
+/* batches that gft_finder_process_device / _end have repeated because they left ASCII, by path */
+int gft_finder_lowered_batches(const gft_finder* f, uint64_t* on_device, uint64_t* on_host);
 /* gft_compact_device on the finder's engine (d_tag_id: the tag id of every entry, or NULL): pairs with
  * gft_finder_process_device, and with _begin / _end in the total == NULL form -- after a batch's _end has returned. */
 int gft_finder_compact_device(gft_finder* f, const uint32_t* d_hit_bitmap, uint64_t n_docs, uint64_t* d_row_off,
