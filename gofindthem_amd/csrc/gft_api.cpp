@@ -117,8 +117,7 @@ struct gft_engine {
     uint32_t opt_scan_ordered = 0;                      // GFT_SCAN_ORDERED=1: scan2's per-lane staging path for every unit
     uint32_t opt_scan4_round = 0;                       // GFT_SCAN4_ROUND: bytes per lane and round of the streaming kernel (0: 64)
     uint32_t opt_scan4_chunk = 0;                       // GFT_SCAN4_CHUNK: units per chunk of the streaming kernel (0: by batch size)
-    uint32_t opt_solve_dbg = 0;                         // GFT_SOLVE_DEBUG (timing studies)
-    int opt_solve_group = -1;                           // GFT_SOLVE_GROUP_DOCS: forced group width (-1: the widest that fits)
+    gft::SolveOptions opt_solve;                        // GFT_SOLVE_GROUP_DOCS, GFT_SOLVE_PROG_LDS, GFT_SOLVE_DEBUG (solve_plan.hpp)
     // one caller at a time per handle: every entry point that touches the device state takes this
     mutable std::recursive_mutex mu;
     // multi-device handle (gft_engine_create_multi): this engine serves devices[0], `peers` the others.  Tables and
@@ -158,7 +157,6 @@ struct gft_engine {
     };
     Pending pend[2];
     unsigned pend_head = 0, pend_count = 0;
-    uint32_t last_solve_group_docs = 64;   // documents per solver group of the last launch (0 = presence matrix in HBM)
     DevBuf d_pscratch;                    // HBM presence matrices when n_slots * 8 B does not fit LDS
 
     // workspace
@@ -201,8 +199,9 @@ void refresh_options(gft_engine* e) {
     e->opt_scan_ordered = getenv("GFT_SCAN_ORDERED") ? 1u : 0u;
     e->opt_scan4_chunk = (uint32_t)num("GFT_SCAN4_CHUNK", 0);
     e->opt_scan4_round = (uint32_t)num("GFT_SCAN4_ROUND", 0);
-    e->opt_solve_dbg = (uint32_t)num("GFT_SOLVE_DEBUG", 0);
-    e->opt_solve_group = (int)num("GFT_SOLVE_GROUP_DOCS", -1);
+    e->opt_solve.dbg = (uint32_t)num("GFT_SOLVE_DEBUG", 0);
+    e->opt_solve.forced_group = (int)num("GFT_SOLVE_GROUP_DOCS", -1);
+    e->opt_solve.prog_lds = num("GFT_SOLVE_PROG_LDS", 1) ? 1u : 0u;
 }
 // what plan_scan is told (table_set.hpp): GFT_SCAN_KERNEL and the GFT_SCAN5_* switches, read by gft_build / gft_import_tables
 ScanOptions scan_options() {
@@ -796,56 +795,44 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     S.fprog_t = d.fprog_t.as<uint32_t>(); S.fblk_off = d.fblk_off.as<uint32_t>();
     S.n_exprs = e->n_exprs;
     S.n_slots = (uint32_t)e->tables.tab.terms.size() + e->n_extra + 1;
-    S.tile_words = std::min<uint32_t>(kSolveTileWords, (e->n_exprs + 31) / 32);
     S.bitmap = d_bitmap;
     S.p_scratch = nullptr;
-    S.dbg = e->opt_solve_dbg;
+    S.dbg = e->opt_solve.dbg;
     S.dbg_out = nullptr;
     if (S.dbg & 8) {
         HIP_TRY(e->d_solve_dbg.ensure(128 * 8), "debug alloc");
         HIP_TRY(hipMemsetAsync(e->d_solve_dbg.p, 0, 128 * 8, e->stream), "memset");
         S.dbg_out = e->d_solve_dbg.as<unsigned long long>();
     }
-    // Presence matrix in LDS next to the output tile: G documents per group = G / 8 bytes per slot, the widest G of
-    // 64 / 32 / 16 / 8 that fits (GFT_SOLVE_GROUP_DOCS forces one, for tests); beyond that in HBM (served by L2), G = 64
     S.fprog_words = e->progs.fprog_words;
-    uint32_t group_docs = 64;
-    bool p_in_lds = false;
-    for (uint32_t G : {64u, 32u, 16u, 8u}) {
-        if (e->opt_solve_group >= 0 && (uint32_t)e->opt_solve_group != G) continue;
-        if (solve_lds_bytes(S.n_slots, S.tile_words, G, true, 0, 0, false) + 1024 <= e->lds_max) { group_docs = G; p_in_lds = true; break; }
-    }
-    // ... and the fused programs too, if there is room left (the interpreter fetches them word after word)
-    // (a set with a wide INORD group runs the kernel variant that reads its programs from L2: launch_g)
-    const bool prog_in_lds = !e->progs.wide_pairs && solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, true) + 1024 <= e->lds_max;
-    const uint64_t n_groups = (n_docs + group_docs - 1) / group_docs;
-    const size_t lds_need = solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, prog_in_lds) + 512;
-    const unsigned per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, e->lds_max / lds_need));
-    unsigned grid = (unsigned)std::min<uint64_t>(n_groups, (uint64_t)e->n_cus * per_cu);
-    if (!p_in_lds) {
-        HIP_TRY(e->d_pscratch.ensure((size_t)grid * S.n_slots * 8), "presence scratch alloc");
+    SolveShape shape;
+    shape.n_slots = S.n_slots; shape.n_exprs = S.n_exprs; shape.fprog_words = S.fprog_words;
+    shape.has_rare = S.has_rare; shape.wide_pairs = e->progs.wide_pairs;
+    const SolvePlan plan = plan_solve(shape, e->lds_max, e->n_cus, n_docs, e->opt_solve);
+    S.tile_words = plan.tile_words;
+    if (!plan.p_in_lds) {
+        HIP_TRY(e->d_pscratch.ensure((size_t)plan.grid * S.n_slots * 8), "presence scratch alloc");
         S.p_scratch = e->d_pscratch.as<uint64_t>();
     }
-    S.wide_slot = nullptr; S.wide_theta = nullptr; S.wide_cap = 0; S.wide_list = nullptr; S.n_wide = 0;
-    if (e->progs.wide_pairs) {
+    S.wide_slot = nullptr; S.wide_theta = nullptr; S.wide_cap = plan.wide_cap; S.wide_list = nullptr; S.n_wide = 0;
+    if (plan.wide_cap) {
         // (a region per wave of the grid; 12 bytes per pair: 8 192 pairs x 4 096 waves = 400 MB at the very most)
-        const uint64_t n_waves = (uint64_t)grid * (kSolveBlockThreads / 64);
-        S.wide_cap = (e->progs.wide_pairs + 63u) & ~63u;
+        const uint64_t n_waves = (uint64_t)plan.grid * (kSolveBlockThreads / 64);
         HIP_TRY(e->d_wide_slot.ensure(n_waves * S.wide_cap * 4), "INORD scratch alloc");
         HIP_TRY(e->d_wide_theta.ensure(n_waves * S.wide_cap * 8), "INORD scratch alloc");
         S.wide_slot = e->d_wide_slot.as<uint32_t>();
         S.wide_theta = e->d_wide_theta.as<long long>();
         S.wide_list = d.wide_list.as<uint32_t>(); S.n_wide = e->progs.n_wide;
     }
-    e->last_solve_group_docs = p_in_lds ? group_docs : 0;
     ProfScope ps(e, "solve");
-    HIP_TRY(launch_solve(S, group_docs, p_in_lds, prog_in_lds, grid, e->stream), "solve kernel launch");
+    HIP_TRY(launch_solve(S, plan, e->stream), "solve kernel launch");
     if (S.dbg & 8) {
         // phase clocks: cycles per group and wave (0 build, 1 barrier, 2 evaluation, 3 barrier, 4 transpose + wipe, 5 barrier,
         // 6 bitmap rows, 7 loop head), averaged over the workgroups
         unsigned long long t[128];
         HIP_TRY(hipMemcpyAsync(t, e->d_solve_dbg.p, sizeof t, hipMemcpyDeviceToHost, e->stream), "debug read-back");
         HIP_TRY(hipStreamSynchronize(e->stream), "debug read-back");
+        const uint64_t n_groups = (n_docs + plan.group_docs - 1) / plan.group_docs;
         fprintf(stderr, "[gft solve debug] cycles per group: wave | build bar eval bar transpose bar rows head\n");
         for (int w = 0; w < 16; w++) {
             fprintf(stderr, "[gft solve debug] %2d |", w);
@@ -1436,7 +1423,7 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
     int rc = compile_programs(prog_words, prog_off, n_exprs, (uint32_t)e->tables.tab.terms.size() + n_extra, ps, e->err);
     if (rc) return rc;          // the handle is untouched: the set installed before, if any, still is
     refresh_options(e);
-    if (e->opt_solve_dbg) print_program_stats(ps);
+    if (e->opt_solve.dbg) print_program_stats(ps);
     DeviceGuard g(e->device);
     SyncOnExit drained(e);      // host buffers are read by asynchronous copies: drained on every way out
     // from here on the device holds a mixture of two sets until the last upload has landed: an error on the way leaves a
@@ -2092,6 +2079,19 @@ int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, 
         const uint64_t ent = s5.filter[((size_t)gr(-3) * G + gr(-2)) * G + gr(-1)];
         if (len) out_dual[0] = (uint8_t)(ent >> (32 + gr(0)) & 1);
     }
+    return GFT_OK;
+} GFT_CATCH(nullptr)
+
+int gft_debug_program_shape(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_slots, uint32_t* out_shape,
+                            uint32_t shape_cap) try {
+    if (!prog_words || !prog_off || !out_shape || n_slots > (1u << kDwFieldBits)) return GFT_E_INVALID;
+    ProgramSet ps;
+    std::string err;
+    const int rc = compile_programs(prog_words, prog_off, n_exprs, n_slots, ps, err);
+    if (rc) return rc;
+    if (shape_cap < 3 + ps.blk_class.size()) return GFT_E_INVALID;
+    out_shape[0] = ps.fprog_words; out_shape[1] = ps.n_rare_words > 0; out_shape[2] = ps.wide_pairs;
+    std::copy(ps.blk_class.begin(), ps.blk_class.end(), out_shape + 3);
     return GFT_OK;
 } GFT_CATCH(nullptr)
 

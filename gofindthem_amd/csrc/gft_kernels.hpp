@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "solve_plan.hpp"
+
 namespace gft {
 
 constexpr uint32_t kScanBlockThreads = 512;      // 8 waves: one work unit per wave
@@ -100,7 +102,6 @@ inline uint32_t fused_to_device(uint32_t fw) {
     default: return kDwNop;
     }
 }
-constexpr uint32_t kSolveTileWords = 64;         // bitmap words (x32 expressions) evaluated per LDS output tile
 
 struct SolveParams {
     // matches: document d owns units [doc_unit_base[d], doc_unit_base[d+1]); unit u owns pool entries
@@ -444,9 +445,7 @@ hipError_t launch_rune_block_starts(const uint8_t* d_text, const uint64_t* d_doc
                                     uint64_t n_blocks, uint32_t* d_starts, hipStream_t st);
 hipError_t launch_pos_to_rune(const uint8_t* d_text, const uint64_t* d_doc_off, const uint64_t* d_blk_base, const uint64_t* d_blk_prefix,
                               const uint64_t* d_match_off, uint64_t n_docs, uint64_t n_matches, uint32_t* d_pos, hipStream_t st);
-size_t solve_lds_bytes(uint32_t n_slots, uint32_t tile_words, uint32_t group_docs, bool p_in_lds, uint32_t prog_words,
-                       uint32_t n_exprs, bool prog_in_lds);
-// group_docs: documents per group (64, 32, 16 or 8 = bits per presence-matrix element)
-hipError_t launch_solve(const SolveParams& S, uint32_t group_docs, bool p_in_lds, bool prog_in_lds, unsigned grid, hipStream_t st);
+// the kernel of `plan` (solve_plan.hpp) with the plan's grid and LDS; hipErrorInvalidValue: the library has no such kernel
+hipError_t launch_solve(const SolveParams& S, const SolvePlan& plan, hipStream_t st);
 
 }  // namespace gft

@@ -511,11 +511,15 @@ constexpr uint32_t bit_index(uint32_t m) { return m <= 1 ? 0 : 1 + bit_index(m >
 // The accumulator stack lives in R registers -- none for the blocks of flat programs (no push / pop: half the work per
 // word), 2 for the ordinary blocks, 4 for the blocks whose programs nest deeper, which also keep a depth counter and spill
 // to scratch beyond (a wave-uniform slow path, like the NOT / INORD words).
-// ALL 64 lanes of a wave call this together (lanes without a program pass chunks = 0): the trip count is the wave's
-// maximum, finished lanes run no-op words, so the INORD steps can use the whole wave.
+//
+// run_chunk is the interpreter's semantics, written once: ONE 4-word chunk `q` of one program against P, on the state
+// acc, s0..s3, sp, deep[] of the fetch schedule that calls it (run_program, run_program_far).  `q` is a copy of a register
+// set that its load has filled -- the schedules copy it out before they refill the set --, so nothing here touches a
+// register that a load is still filling.  Always inlined: the state is the caller's own locals, one reference each, which
+// are registers after inlining (state that reaches code that is NOT inlined by reference lives in scratch: DESIGN.md 4.1c).
 template <bool P_LDS, uint32_t R, int RARE, class PT, class AT>
-__device__ __forceinline__ AT run_program(const SolveParams& S, const PT* P, const uint4* prog, uint32_t stride, uint32_t chunks,
-                                          AT valid, uint64_t d0) {
+__device__ __forceinline__ void run_chunk(const SolveParams& S, const PT* P, const uint4 q, AT& acc, AT& s0, AT& s1, AT& s2, AT& s3,
+                                          AT (&deep)[R > kSolveRegStack ? kMaxBoolDepth : 1], uint32_t& sp, AT valid, uint64_t d0) {
     static_assert(R == 0 || R == kSolveRegStack || R == kSolveRegStackDeep, "three interpreters");
     constexpr bool DEEP = R > kSolveRegStack;
     // HBM-resident P was written with L2 atomics by other waves: read it past this CU's L1
@@ -527,87 +531,98 @@ __device__ __forceinline__ AT run_program(const SolveParams& S, const PT* P, con
         if (P_LDS) return (AT)*reinterpret_cast<const __attribute__((address_space(3))) PT*>((size_t)byte);
         return (AT)__hip_atomic_load(&P[byte / sizeof(PT)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
-    AT acc = AT(0), s0 = AT(0), s1 = AT(0), s2 = AT(0), s3 = AT(0), deep[DEEP ? kMaxBoolDepth : 1];
-    uint32_t sp = 0;                                            // DEEP: entries on the stack (registers + scratch)
-    uint4 nx = chunks ? prog[0] : make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);
-    uint4 nx2 = chunks > 1 ? prog[stride] : make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);   // two chunks ahead (programs in L2)
-    const uint32_t wchunks = wave_max_u32(chunks);
-    // four words per trip: the next two chunks and this chunk's four presence reads are in flight together, so a trip
+    // four words per trip: the chunks in front and this chunk's four presence reads are in flight together, so a trip
     // exposes one memory round trip instead of four (programs are padded to whole chunks with no-op words)
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    AT pv[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        pv[k] = ld(RARE && (int32_t)w[k] < 0 ? 0u : w[k]);            // (a rare word's field is a group, not a slot)
+    }
+    // wave-uniform: a NOT / INORD word in this chunk, or a lane whose stack leaves the registers in it
+    bool careful = RARE && __any((int32_t)(w[0] | w[1] | w[2] | w[3]) < 0);
+    if (DEEP) {
+        uint32_t high = sp;                                  // an upper bound of the depth inside this chunk
+#pragma unroll
+        for (int k = 0; k < 4; k++) high += (w[k] >> bit_index(kDwPush)) & 1u;
+        careful |= __any(high > R);
+    }
+    auto step = [&](const uint32_t wq, const AT pvq, const bool care) __attribute__((always_inline)) {
+        const AT neg = bit_mask<AT, bit_index(kDwNeg)>(wq), sel = bit_mask<AT, bit_index(kDwSel)>(wq);
+        const AT ones = bit_mask<AT, bit_index(kDwOnes)>(wq), orr = bit_mask<AT, bit_index(kDwOr)>(wq);
+        const AT pop = bit_mask<AT, bit_index(kDwPop)>(wq), push = bit_mask<AT, bit_index(kDwPush)>(wq);
+        const AT v = pvq ^ neg;                             // (bits past the group are never stored)
+        const AT x = R ? pick(pop, s0, v) : v;
+        const AT before = acc;
+        acc = (acc & pick(sel, x, ones)) | (x & orr);
+        if (R == 0) {
+            // flat programs: no push, no pop
+        } else if (!DEEP) {
+            const AT n0 = pick(push, before, pick(pop, s1, s0));
+            s1 = pick(push, s0, s1);
+            s0 = n0;
+        } else {
+            if (care && push && sp >= R) deep[sp - R] = s3;
+            const AT n0 = pick(push, before, pick(pop, s1, s0)), n1 = pick(push, s0, pick(pop, s2, s1));
+            const AT n2 = pick(push, s1, pick(pop, s3, s2)), n3 = pick(push, s2, s3);
+            s0 = n0; s1 = n1; s2 = n2; s3 = n3;
+            sp = sp - bit_mask<uint32_t, bit_index(kDwPush)>(wq) + bit_mask<uint32_t, bit_index(kDwPop)>(wq);   // 0 or ~0 == -1
+            if (care && pop && sp >= R) {
+                s3 = deep[sp - R];
+                // (waited for here: a scratch load left pending would have the compiler wait for ALL vector loads, the
+                // prefetch of the next group included, wherever the fast path touches the same register)
+                __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
+            }
+        }
+        if (RARE && care) {
+            const bool rare = (int32_t)wq < 0, is_not = rare && (wq & kDwNeg), is_inord = rare && !(wq & kDwNeg);
+            if (is_not) acc = ~acc;
+            // candidates: documents where the group's boolean value is true (rval, expression.go:137)
+            const AT in = AT(inord_wave(S, is_inord, (wq & kDwFieldMask) >> kDwFieldShift, (uint64_t)(acc & valid), d0));
+            if (is_inord) acc = in;
+        }
+    };
+    if (!careful) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) step(w[k], pv[k], false);
+    } else {
+        // one copy of the slow code: the chunk's words one after the other in a rolled loop.  The words rotate through
+        // fixed registers -- indexing w[] / pv[] with the loop counter would move both arrays to scratch memory, for
+        // the fast path above as well
+        uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+        AT p0 = pv[0], p1 = pv[1], p2 = pv[2], p3 = pv[3];
+#pragma nounroll
+        for (int k = 0; k < 4; k++) {
+            step(w0, p0, true);
+            w0 = w1; w1 = w2; w2 = w3;
+            p0 = p1; p1 = p2; p2 = p3;
+        }
+    }
+}
+
+// The near fetch schedule, for programs staged in LDS: two register sets, rotated -- the next two chunks are in flight
+// while this one is interpreted.
+// ALL 64 lanes of a wave call this together (lanes without a program pass chunks = 0): the trip count is the wave's
+// maximum, finished lanes run no-op words, so the INORD steps can use the whole wave.
+template <bool P_LDS, uint32_t R, int RARE, class PT, class AT>
+__device__ __forceinline__ AT run_program(const SolveParams& S, const PT* P, const uint4* prog, uint32_t stride, uint32_t chunks,
+                                          AT valid, uint64_t d0) {
+    AT acc = AT(0), s0 = AT(0), s1 = AT(0), s2 = AT(0), s3 = AT(0), deep[R > kSolveRegStack ? kMaxBoolDepth : 1];
+    uint32_t sp = 0;                                            // deep interpreter: entries on the stack (registers + scratch)
+    uint4 nx = chunks ? prog[0] : make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);
+    uint4 nx2 = chunks > 1 ? prog[stride] : make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);   // two chunks ahead
+    const uint32_t wchunks = wave_max_u32(chunks);
     for (uint32_t c = 0; c < wchunks; c++) {
-        const uint32_t w[4] = {nx.x, nx.y, nx.z, nx.w};
+        const uint4 q = nx;
         nx = nx2;
         nx2 = make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);
         if (c + 2 < chunks) nx2 = prog[(size_t)(c + 2) * stride];
-        AT pv[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            pv[q] = ld(RARE && (int32_t)w[q] < 0 ? 0u : w[q]);            // (a rare word's field is a group, not a slot)
-        }
-        // wave-uniform: a NOT / INORD word in this chunk, or a lane whose stack leaves the registers in it
-        bool careful = RARE && __any((int32_t)(w[0] | w[1] | w[2] | w[3]) < 0);
-        if (DEEP) {
-            uint32_t high = sp;                                  // an upper bound of the depth inside this chunk
-#pragma unroll
-            for (int q = 0; q < 4; q++) high += (w[q] >> bit_index(kDwPush)) & 1u;
-            careful |= __any(high > R);
-        }
-        auto step = [&](const uint32_t wq, const AT pvq, const bool care) __attribute__((always_inline)) {
-            const AT neg = bit_mask<AT, bit_index(kDwNeg)>(wq), sel = bit_mask<AT, bit_index(kDwSel)>(wq);
-            const AT ones = bit_mask<AT, bit_index(kDwOnes)>(wq), orr = bit_mask<AT, bit_index(kDwOr)>(wq);
-            const AT pop = bit_mask<AT, bit_index(kDwPop)>(wq), push = bit_mask<AT, bit_index(kDwPush)>(wq);
-            const AT v = pvq ^ neg;                             // (bits past the group are never stored)
-            const AT x = R ? pick(pop, s0, v) : v;
-            const AT before = acc;
-            acc = (acc & pick(sel, x, ones)) | (x & orr);
-            if (R == 0) {
-                // flat programs: no push, no pop
-            } else if (!DEEP) {
-                const AT n0 = pick(push, before, pick(pop, s1, s0));
-                s1 = pick(push, s0, s1);
-                s0 = n0;
-            } else {
-                if (care && push && sp >= R) deep[sp - R] = s3;
-                const AT n0 = pick(push, before, pick(pop, s1, s0)), n1 = pick(push, s0, pick(pop, s2, s1));
-                const AT n2 = pick(push, s1, pick(pop, s3, s2)), n3 = pick(push, s2, s3);
-                s0 = n0; s1 = n1; s2 = n2; s3 = n3;
-                sp = sp - bit_mask<uint32_t, bit_index(kDwPush)>(wq) + bit_mask<uint32_t, bit_index(kDwPop)>(wq);   // 0 or ~0 == -1
-                if (care && pop && sp >= R) {
-                    s3 = deep[sp - R];
-                    // (waited for here: a scratch load left pending would have the compiler wait for ALL vector loads, the
-                    // prefetch of the next group included, wherever the fast path touches the same register)
-                    __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
-                }
-            }
-            if (RARE && care) {
-                const bool rare = (int32_t)wq < 0, is_not = rare && (wq & kDwNeg), is_inord = rare && !(wq & kDwNeg);
-                if (is_not) acc = ~acc;
-                // candidates: documents where the group's boolean value is true (rval, expression.go:137)
-                const AT in = AT(inord_wave(S, is_inord, (wq & kDwFieldMask) >> kDwFieldShift, (uint64_t)(acc & valid), d0));
-                if (is_inord) acc = in;
-            }
-        };
-        if (!careful) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) step(w[q], pv[q], false);
-        } else {
-            // one copy of the slow code: the chunk's words one after the other in a rolled loop.  The words rotate through
-            // fixed registers -- indexing w[] / pv[] with the loop counter would move both arrays to scratch memory, for
-            // the fast path above as well
-            uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-            AT p0 = pv[0], p1 = pv[1], p2 = pv[2], p3 = pv[3];
-#pragma nounroll
-            for (int q = 0; q < 4; q++) {
-                step(w0, p0, true);
-                w0 = w1; w1 = w2; w2 = w3;
-                p0 = p1; p1 = p2; p2 = p3;
-            }
-        }
+        run_chunk<P_LDS, R, RARE, PT, AT>(S, P, q, acc, s0, s1, s2, s3, deep, sp, valid, d0);
     }
     return acc;
 }
 
-// The same interpreter for programs that are read from global memory (a 100 000-term dictionary's do not fit LDS): FOUR
+// The far fetch schedule, for programs that are read from global memory (a 100 000-term dictionary's do not fit LDS): FOUR
 // chunks are requested in front of the one being interpreted, each in a register set of its own that is loaded again as soon
 // as its words are copied out.  run_program's rotation (nx = nx2) copies a set that a load is still filling and so waits for
 // that load: its distance is one trip, which does not cover an L2 round trip -- the longest program of a group was a chain of
@@ -618,91 +633,17 @@ __device__ __forceinline__ AT run_program(const SolveParams& S, const PT* P, con
 template <bool P_LDS, uint32_t R, int RARE, class PT, class AT>
 __device__ __forceinline__ AT run_program_far(const SolveParams& S, const PT* P, const uint4* prog, uint32_t stride, uint32_t chunks,
                                               AT valid, uint64_t d0) {
-    static_assert(R == 0 || R == kSolveRegStack || R == kSolveRegStackDeep, "three interpreters");
-    constexpr bool DEEP = R > kSolveRegStack;
-    // HBM-resident P was written with L2 atomics by other waves: read it past this CU's L1
-    // (LDS: the field of a word is the slot's byte offset in a P of 8-byte elements, one v_and away)
-    auto ld = [&](uint32_t w) -> AT {
-        constexpr uint32_t kDown = sizeof(PT) == 8 ? 0 : sizeof(PT) == 4 ? 1 : sizeof(PT) == 2 ? 2 : 3;
-        const uint32_t byte = (w & kDwFieldMask) >> kDown;
-        // (P sits at LDS address 0 -- checked in the kernel --, so the byte offset IS the address: no add of the base)
-        if (P_LDS) return (AT)*reinterpret_cast<const __attribute__((address_space(3))) PT*>((size_t)byte);
-        return (AT)__hip_atomic_load(&P[byte / sizeof(PT)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    AT acc = AT(0), s0 = AT(0), s1 = AT(0), s2 = AT(0), s3 = AT(0), deep[DEEP ? kMaxBoolDepth : 1];
-    uint32_t sp = 0;                                            // DEEP: entries on the stack (registers + scratch)
+    AT acc = AT(0), s0 = AT(0), s1 = AT(0), s2 = AT(0), s3 = AT(0), deep[R > kSolveRegStack ? kMaxBoolDepth : 1];
+    uint32_t sp = 0;                                            // deep interpreter: entries on the stack (registers + scratch)
     const uint4 nops = make_uint4(kDwNop, kDwNop, kDwNop, kDwNop);
     uint4 q0 = chunks > 0 ? prog[0] : nops, q1 = chunks > 1 ? prog[stride] : nops;
     uint4 q2 = chunks > 2 ? prog[2 * (size_t)stride] : nops, q3 = chunks > 3 ? prog[3 * (size_t)stride] : nops;
     const uint32_t wchunks = wave_max_u32(chunks);
-    auto trip = [&](uint4& q, const uint32_t c) __attribute__((always_inline)) {
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        q = nops;
-        if (c + 4 < chunks) q = prog[(size_t)(c + 4) * stride];
-        AT pv[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            pv[q] = ld(RARE && (int32_t)w[q] < 0 ? 0u : w[q]);            // (a rare word's field is a group, not a slot)
-        }
-        // wave-uniform: a NOT / INORD word in this chunk, or a lane whose stack leaves the registers in it
-        bool careful = RARE && __any((int32_t)(w[0] | w[1] | w[2] | w[3]) < 0);
-        if (DEEP) {
-            uint32_t high = sp;                                  // an upper bound of the depth inside this chunk
-#pragma unroll
-            for (int q = 0; q < 4; q++) high += (w[q] >> bit_index(kDwPush)) & 1u;
-            careful |= __any(high > R);
-        }
-        auto step = [&](const uint32_t wq, const AT pvq, const bool care) __attribute__((always_inline)) {
-            const AT neg = bit_mask<AT, bit_index(kDwNeg)>(wq), sel = bit_mask<AT, bit_index(kDwSel)>(wq);
-            const AT ones = bit_mask<AT, bit_index(kDwOnes)>(wq), orr = bit_mask<AT, bit_index(kDwOr)>(wq);
-            const AT pop = bit_mask<AT, bit_index(kDwPop)>(wq), push = bit_mask<AT, bit_index(kDwPush)>(wq);
-            const AT v = pvq ^ neg;                             // (bits past the group are never stored)
-            const AT x = R ? pick(pop, s0, v) : v;
-            const AT before = acc;
-            acc = (acc & pick(sel, x, ones)) | (x & orr);
-            if (R == 0) {
-                // flat programs: no push, no pop
-            } else if (!DEEP) {
-                const AT n0 = pick(push, before, pick(pop, s1, s0));
-                s1 = pick(push, s0, s1);
-                s0 = n0;
-            } else {
-                if (care && push && sp >= R) deep[sp - R] = s3;
-                const AT n0 = pick(push, before, pick(pop, s1, s0)), n1 = pick(push, s0, pick(pop, s2, s1));
-                const AT n2 = pick(push, s1, pick(pop, s3, s2)), n3 = pick(push, s2, s3);
-                s0 = n0; s1 = n1; s2 = n2; s3 = n3;
-                sp = sp - bit_mask<uint32_t, bit_index(kDwPush)>(wq) + bit_mask<uint32_t, bit_index(kDwPop)>(wq);   // 0 or ~0 == -1
-                if (care && pop && sp >= R) {
-                    s3 = deep[sp - R];
-                    // (waited for here: a scratch load left pending would have the compiler wait for ALL vector loads, the
-                    // prefetch of the next group included, wherever the fast path touches the same register)
-                    __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
-                }
-            }
-            if (RARE && care) {
-                const bool rare = (int32_t)wq < 0, is_not = rare && (wq & kDwNeg), is_inord = rare && !(wq & kDwNeg);
-                if (is_not) acc = ~acc;
-                // candidates: documents where the group's boolean value is true (rval, expression.go:137)
-                const AT in = AT(inord_wave(S, is_inord, (wq & kDwFieldMask) >> kDwFieldShift, (uint64_t)(acc & valid), d0));
-                if (is_inord) acc = in;
-            }
-        };
-        if (!careful) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) step(w[q], pv[q], false);
-        } else {
-            // one copy of the slow code: the chunk's words one after the other in a rolled loop.  The words rotate through
-            // fixed registers -- indexing w[] / pv[] with the loop counter would move both arrays to scratch memory, for
-            // the fast path above as well
-            uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
-            AT p0 = pv[0], p1 = pv[1], p2 = pv[2], p3 = pv[3];
-#pragma nounroll
-            for (int q = 0; q < 4; q++) {
-                step(w0, p0, true);
-                w0 = w1; w1 = w2; w2 = w3;
-                p0 = p1; p1 = p2; p2 = p3;
-            }
-        }
+    auto trip = [&](uint4& set, const uint32_t c) __attribute__((always_inline)) {
+        const uint4 q = set;
+        set = nops;
+        if (c + 4 < chunks) set = prog[(size_t)(c + 4) * stride];
+        run_chunk<P_LDS, R, RARE, PT, AT>(S, P, q, acc, s0, s1, s2, s3, deep, sp, valid, d0);
     };
     for (uint32_t c = 0; c < wchunks; c += 4) {
         trip(q0, c);
@@ -748,6 +689,7 @@ __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const Solve
     constexpr uint32_t kWaves = kSolveBlockThreads / 64;
     const uint32_t tile_words = S.tile_words;                   // bitmap words covered by one pass (<= kSolveTileWords)
     const uint32_t bm_words = (S.n_exprs + 31) / 32;
+    // the LDS layout (host-side counterpart, which sizes the launch: solve_lds_bytes, solve_plan.cpp)
     PT* P = P_LDS ? reinterpret_cast<PT*>(smem) : reinterpret_cast<PT*>(S.p_scratch + (size_t)blockIdx.x * S.n_slots);
     uint32_t* O = reinterpret_cast<uint32_t*>(smem + (P_LDS ? (((size_t)S.n_slots * sizeof(PT) + 15) & ~(size_t)15) : 0));   // [64][tile_words | 1]
     uint32_t* Pw = reinterpret_cast<uint32_t*>(P);
@@ -1036,45 +978,19 @@ __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const Solve
 
 }  // namespace
 
-size_t solve_lds_bytes(uint32_t n_slots, uint32_t tile_words, uint32_t group_docs, bool p_in_lds, uint32_t prog_words,
-                       uint32_t n_exprs, bool prog_in_lds) {
-    return (p_in_lds ? (((size_t)n_slots * (group_docs / 8) + 15) & ~(size_t)15) : 0) + (size_t)64 * (tile_words | 1u) * 4 +
-           (size_t)tile_words * 32 * 8 + (prog_in_lds ? ((size_t)prog_words + 2 * (size_t)n_exprs + 1) * 4 : 0);
-}
-
-namespace {
-template <int G>
-hipError_t launch_g(const SolveParams& S, bool p_in_lds, bool prog_in_lds, unsigned grid, size_t lds, hipStream_t st) {
-    using Kern = void (*)(const SolveParams);
-    const bool io = S.has_rare != 0;
-    const Kern fn = p_in_lds ? (prog_in_lds ? (io ? k_solve_groups<true, true, G, 1> : k_solve_groups<true, true, G, 0>)
-                                            : (io ? k_solve_groups<true, false, G, 1> : k_solve_groups<true, false, G, 0>))
-                             : (prog_in_lds ? (io ? k_solve_groups<false, true, 64, 1> : k_solve_groups<false, true, 64, 0>)
-                                            : (io ? k_solve_groups<false, false, 64, 1> : k_solve_groups<false, false, 64, 0>));
-    Kern run = fn;
-    // a program set with a wide INORD group (SolveParams::wide_cap): the variant that can call the wide paths; its programs
-    // are read from L2 (the caller plans LDS accordingly)
-    if (S.wide_cap) run = p_in_lds ? k_solve_groups<true, false, G, 2> : k_solve_groups<false, false, 64, 2>;
-    // timing studies: the benchmark's shape only (presence matrix and programs in LDS, 64 documents per group)
-    if (S.dbg && !S.wide_cap && G == 64 && p_in_lds && prog_in_lds) run = io ? k_solve_groups<true, true, 64, 1, true> : k_solve_groups<true, true, 64, 0, true>;
-    // ... and the shape of a 100 000-term dictionary (8 documents per group, programs in L2)
-    if (S.dbg && !S.wide_cap && G == 8 && p_in_lds && !prog_in_lds) run = io ? k_solve_groups<true, false, 8, 1, true> : k_solve_groups<true, false, 8, 0, true>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(run), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    run<<<dim3(grid), dim3(kSolveBlockThreads), lds, st>>>(S);
-    return hipGetLastError();
-}
-}  // namespace
-
-hipError_t launch_solve(const SolveParams& S, uint32_t group_docs, bool p_in_lds, bool prog_in_lds, unsigned grid, hipStream_t st) {
+// The launch table: every instantiation the library carries (solve_plan.hpp GFT_SOLVE_KERNELS), keyed by the plan's fields.
+// The plan (plan_solve) has made every decision; a plan without a kernel is an error, never another variant.
+hipError_t launch_solve(const SolveParams& S, const SolvePlan& plan, hipStream_t st) {
     if (!S.n_docs || !S.n_exprs) return hipSuccess;
-    const size_t lds = solve_lds_bytes(S.n_slots, S.tile_words, group_docs, p_in_lds, S.fprog_words, S.n_exprs, prog_in_lds);
-    switch (p_in_lds ? group_docs : 64) {
-    case 64: return launch_g<64>(S, p_in_lds, prog_in_lds, grid, lds, st);
-    case 32: return launch_g<32>(S, p_in_lds, prog_in_lds, grid, lds, st);
-    case 16: return launch_g<16>(S, p_in_lds, prog_in_lds, grid, lds, st);
-    default: return launch_g<8>(S, p_in_lds, prog_in_lds, grid, lds, st);
-    }
+    void (*run)(const SolveParams) = nullptr;
+#define X(P_LDS, PROG_LDS, G, RARE, DBG) if (solve_kernel_is(plan, P_LDS, PROG_LDS, G, RARE, DBG)) run = k_solve_groups<P_LDS, PROG_LDS, G, RARE, DBG>;
+    GFT_SOLVE_KERNELS(X)
+#undef X
+    if (!run || !plan.grid) return hipErrorInvalidValue;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(run), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+    if (e != hipSuccess) return e;
+    run<<<dim3(plan.grid), dim3(kSolveBlockThreads), plan.lds_bytes, st>>>(S);
+    return hipGetLastError();
 }
 
 }  // namespace gft

@@ -506,6 +506,22 @@ int gft_debug_learn(const char* kernel, uint32_t fifo_cap, int ordered, uint64_t
  * oracle's tree evaluation. */
 int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_slots,
                             const uint8_t* present, uint8_t* out_hit, uint32_t* out_depth);
+/* ... and what the solver's plan reads of the set so compiled, without evaluating it (so also for sets with INORD groups):
+ * out_shape (shape_cap words; 3 + max(1, ceil(n_exprs / 64)) are written, GFT_E_INVALID if that is more) = words of the fused
+ * programs, 1 if some program holds a NOT or INORD word, pairs of the widest wide INORD group, then the interpreter class
+ * (0 flat, 1 two registers, 2 deep) of every block of 64 sorted programs (one entry for an empty set). */
+int gft_debug_program_shape(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_slots, uint32_t* out_shape,
+                            uint32_t shape_cap);
+
+/* The solver's launch plan alone, on the host (csrc/solve_plan.cpp): plan_solve -- the function every gft_process* calls -- for
+ * a program set of that shape (n_slots rows of the presence matrix, n_exprs, fprog_words, has_rare, wide_pairs: see
+ * gft_debug_program_shape) on a device of n_cus CUs and lds_max bytes of LDS per workgroup, for a batch of n_docs documents, under
+ * what GFT_SOLVE_GROUP_DOCS (forced_group, -1: unset), GFT_SOLVE_PROG_LDS (prog_lds) and GFT_SOLVE_DEBUG (dbg) would say.
+ * plan[11] = group_docs, p_in_lds, prog_in_lds, rare (0 / 1 / 2), dbg_variant, tile_words, wide_cap, lds_bytes, per_cu, grid,
+ * and 1 if the library carries the kernel of that plan (the launch table's own lookup).  No HIP device, no handle. */
+int gft_debug_plan_solve(uint32_t n_slots, uint32_t n_exprs, uint32_t fprog_words, int has_rare, uint32_t wide_pairs,
+                         uint64_t lds_max, uint32_t n_cus, uint64_t n_docs, int forced_group, int prog_lds, uint32_t dbg,
+                         uint64_t* plan);
 
 /* The host solver alone (csrc/host_solve.cpp: dsl/expression.go:66-142 restated over the postfix words, lists materialised):
  * Solve of ONE program over ONE document's map, given as n_lists keys -- slots[k] with the positions
