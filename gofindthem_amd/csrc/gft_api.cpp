@@ -2141,6 +2141,22 @@ int gft_debug_eval_programs(const uint32_t* prog_words, const uint64_t* prog_off
     return GFT_OK;
 } GFT_CATCH(nullptr)
 
+// what gft_debug_tables and gft_debug_scan_plan share: the table set (compiled from the terms, or read from `blob`) and the plan
+// that plan_scan makes for it
+static int debug_tables_and_plan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
+                                 uint64_t lds_max, const char* forced_kernel, TableSet& set, uint32_t& flags, ScanPlan& plan, std::string& err) {
+    if (blob) {
+        if (int rc = read_tables(blob, blob_len, set, flags, err)) return rc;
+    } else {
+        std::vector<std::string> terms;
+        for (uint32_t i = 0; i < n_terms; i++) terms.emplace_back((const char*)terms_blob + term_off[i], (size_t)(term_off[i + 1] - term_off[i]));
+        compile_tables(std::move(terms), set);
+    }
+    ScanOptions opt = scan_options();
+    if (forced_kernel) opt.forced = parse_forced(forced_kernel);
+    return plan_scan(set, opt, lds_max, kExtraKernels, plan, err);
+}
+
 int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
                      uint64_t lds_max, const char* forced_kernel, const char** kernel, uint8_t* out, uint64_t cap, uint64_t* needed,
                      char* err_out, uint64_t err_cap) try {
@@ -2155,17 +2171,8 @@ int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32
     TableSet set;
     uint32_t flags = 0;
     int rc;
-    if (blob) {
-        if ((rc = read_tables(blob, blob_len, set, flags, err))) return done(rc);
-    } else {
-        std::vector<std::string> terms;
-        for (uint32_t i = 0; i < n_terms; i++) terms.emplace_back((const char*)terms_blob + term_off[i], (size_t)(term_off[i + 1] - term_off[i]));
-        compile_tables(std::move(terms), set);
-    }
-    ScanOptions opt = scan_options();
-    if (forced_kernel) opt.forced = parse_forced(forced_kernel);
     ScanPlan plan;
-    if ((rc = plan_scan(set, opt, lds_max, kExtraKernels, plan, err))) return done(rc);
+    if ((rc = debug_tables_and_plan(terms_blob, term_off, n_terms, blob, blob_len, lds_max, forced_kernel, set, flags, plan, err))) return done(rc);
     *kernel = kScanKernelName[(int)plan.kernel];
     if (plan.kernel == ScanKernel::scan5) {              // (what gft_build would go on to derive: it must not fault on these tables)
         Scan5Tables s5;
@@ -2179,6 +2186,31 @@ int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32
     if (cap < b.size()) return done(GFT_E_INVALID);
     memcpy(out, b.data(), b.size());
     return done(GFT_OK);
+} GFT_CATCH(nullptr)
+
+int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fifo_cap) {
+    if (!e || !unit_max) return GFT_E_INVALID;
+    *unit_max = e->learned.unit_max;
+    if (fifo_cap) *fifo_cap = e->plan.kernel == ScanKernel::scan5 ? e->plan.s5plan.fifo_cap : kScan2FifoCap;
+    return GFT_OK;
+}
+
+int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, uint64_t lds_max, const char* forced_kernel,
+                        const char** kernel, uint32_t* plan_out) try {
+    if (!kernel || !plan_out || (n_terms && (!terms_blob || !term_off))) return GFT_E_INVALID;
+    *kernel = "";
+    TableSet set;
+    uint32_t flags = 0;
+    ScanPlan plan;
+    std::string err;
+    if (int rc = debug_tables_and_plan(terms_blob, term_off, n_terms, nullptr, 0, lds_max, forced_kernel, set, flags, plan, err)) return rc;
+    *kernel = kScanKernelName[(int)plan.kernel];
+    const bool s5 = plan.kernel == ScanKernel::scan5;
+    plan_out[0] = set.tab.max_term_len;
+    plan_out[1] = s5 ? plan.s5_term_bits : 0u;
+    plan_out[2] = s5 ? plan.s5_pos_bias : 0u;
+    plan_out[3] = s5 ? plan.s5plan.fifo_cap : kScan2FifoCap;
+    return GFT_OK;
 } GFT_CATCH(nullptr)
 
 int gft_debug_host_solve(const uint32_t* words, uint64_t len, const uint32_t* slots, const uint64_t* list_off,

@@ -479,6 +479,16 @@ int gft_debug_scan5_filter(const uint8_t* terms_blob, const uint64_t* term_off, 
 int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, const uint8_t* blob, uint64_t blob_len,
                      uint64_t lds_max, const char* forced_kernel, const char** kernel, uint8_t* out, uint64_t cap, uint64_t* needed,
                      char* err, uint64_t err_cap);
+/* What the handle has learnt from the batches it completed (read-only): *unit_max = the bytes per work unit that the next
+ * call of a kernel on scan2's tables (scan2, scan5) runs with (8 192 after gft_build, down to 512 behind dense batches;
+ * the other kernels do not read it), *fifo_cap (nullable) = the fifo entries that `learn` sizes it by. */
+int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fifo_cap);
+/* ... and the numbers of the plan that plan_scan makes for `terms`, compiled the same way: *kernel as above,
+ * plan[0..3] = the longest keyword's bytes, then the shape of scan5's fifo entries (s5_term_bits, s5_pos_bias: term id and
+ * relative position in 32 bits; both 0 under another kernel) and the entries of a wave's LDS match fifo, which the unit size
+ * follows (gft_debug_learn's fifo_cap).  No HIP device is needed and no handle is built. */
+int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, uint64_t lds_max, const char* forced_kernel,
+                        const char** kernel, uint32_t* plan);
 
 /* The judgement on a batch alone, on the host (csrc/batch_verdict.cpp): decodes the seven 64-bit words of a control-block
  * read-back and judges them against what a deferred scan launch knew -- single / epoch (its unit table came from the

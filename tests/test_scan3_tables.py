@@ -10,6 +10,7 @@ import random
 import numpy as np
 import pytest
 
+import long_terms
 from gofindthem_amd import _lib
 from gofindthem_amd.workload import Workload
 from oracle.pyoracle import Oracle, pack_strings, POS_END, POS_START
@@ -135,3 +136,18 @@ def test_input_class_of_the_round_2_abort(seed):
                 assert emulate(terms, text, lo=lo, pos_end=pos_end) == oracle_pairs(terms, text, lo=lo, pos_end=pos_end), (n, lo)
     planted = b" ".join(terms[i] for i in rng.integers(0, len(terms), 400))
     assert emulate(terms, planted) == oracle_pairs(terms, planted)
+
+
+@pytest.mark.parametrize("L", [513, 7424])
+@pytest.mark.parametrize("name", ["planted", "shared_suffix"])
+def test_keywords_of_513_and_7424_bytes(name, L):
+    """tests/long_terms.py: the second anchor and the stride-2 walk with a keyword that starts up to 7 423 bytes in front of the
+    unit it ends in -- units that begin at the 507- and 8 000-byte slices of a 40 000-byte document, one byte into the
+    document and on its last byte, both probe parities"""
+    terms, docs, _ = long_terms.family(name, L)
+    for text in docs:
+        n = len(text)
+        for lo in sorted({0, min(n, 1), min(n, 507 * 15), min(n, 8000), min(n, 8001), n // 2, max(n - 1, 0)}):
+            for pos_end in ((False, True) if lo in (0, n // 2) else (False,)):
+                got, want = emulate(terms, text, lo=lo, pos_end=pos_end), oracle_pairs(terms, text, lo=lo, pos_end=pos_end)
+                assert got == want, (n, lo, pos_end, [x for x in got if x not in want][:5], [x for x in want if x not in got][:5])

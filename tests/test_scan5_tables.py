@@ -12,6 +12,7 @@ import random
 import numpy as np
 import pytest
 
+import long_terms
 from gofindthem_amd import _lib
 from gofindthem_amd.workload import Workload
 from oracle.pyoracle import Oracle, pack_strings, POS_END
@@ -114,3 +115,28 @@ def test_input_edges():
     assert ex.tolist() == du.tolist() == [1]
     ex, du, _ = flags([b"abcd"], b"xabcd")
     assert ex.tolist() == du.tolist() == [0, 0, 0, 0, 1]
+
+
+@pytest.mark.parametrize("L", [513, 7424])
+@pytest.mark.parametrize("name", ["planted", "shared_suffix"])
+def test_keywords_of_513_and_7424_bytes(name, L):
+    """tests/long_terms.py: the anchor window of a keyword of up to 7 424 bytes is flagged by the exact filter within four bytes
+    of every place where the keyword ends, and whatever the exact filter flags the two-positions-per-probe filter flags too --
+    unmerged and with the classes merged into four groups, for every parity of a lane's first byte; with and without the
+    short keywords of the dictionary"""
+    terms, docs, _ = long_terms.family(name, L)
+    # with the one-byte keywords a, b, c three text bytes in eight are flagged anyway: the coverage of the anchor windows is
+    # also checked on the long keywords alone, where a flag can only come from a bucket key
+    for kws in (terms, [t for t in terms if len(t) > 300]):
+        for text in docs:
+            ends = match_ends(kws, text)
+            for groups in (0, 4):
+                for start in range(min(len(text), 3) + 1):
+                    ex, du, g = flags(kws, text, lane_start=start, groups=groups)
+                    assert not (ex & ~du & 1).any(), (len(text), groups, start)
+                    if not groups:
+                        assert np.array_equal(ex, du)
+                    for p, length in ends:
+                        assert ex[max(p - 4, 0):p + 1].any(), (p, length)
+        if kws is not terms:
+            assert ends and ex.sum() < len(text) // 8               # (the last document holds a long match; few flags)

@@ -5,7 +5,6 @@ calls --, chooses the scan kernel the way both do for a device with a given LDS 
 gft_export_tables calls.  So the blob format, its validation and the decision table of DESIGN.md 4.7 are checked here; the
 GPU suite keeps the checks that the installed tables scan like the oracle (tests/test_gpu_parity.py).
 """
-import ctypes as C
 import random
 import struct
 
@@ -13,34 +12,7 @@ import pytest
 
 from gofindthem_amd import _lib
 from gofindthem_amd.workload import Workload
-from oracle.pyoracle import pack_strings
-
-LDS_GFX950 = 160 * 1024          # what gft_engine_create sets on gfx950
-
-
-class Refused(Exception):
-    def __init__(self, code, msg):
-        super().__init__("gft error %d: %s" % (code, msg))
-        self.code = code
-
-
-def tables(terms=None, blob=None, forced="auto", lds_max=LDS_GFX950):
-    """-> (chosen kernel's name, written blob); Refused with the status and the text of a refusal"""
-    L = _lib.load()
-    tb, to = pack_strings(terms or [])
-    kernel, needed, err = C.c_char_p(), C.c_uint64(0), C.create_string_buffer(512)
-    out = C.create_string_buffer(4 << 20)
-    for _ in range(2):
-        rc = L.gft_debug_tables(tb.ctypes.data, to.ctypes.data, len(terms or []), blob, len(blob) if blob is not None else 0, lds_max,
-                                forced.encode() if forced is not None else None, C.byref(kernel), C.addressof(out), len(out),
-                                C.byref(needed), C.addressof(err), len(err))
-        if rc == _lib.GFT_E_INVALID and needed.value > len(out):
-            out = C.create_string_buffer(needed.value)
-            continue
-        break
-    if rc:
-        raise Refused(rc, err.value.decode())
-    return kernel.value.decode(), out.raw[:needed.value]
+from helpers import Refused, tables
 
 
 def lower_terms():

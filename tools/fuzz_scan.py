@@ -71,7 +71,9 @@ def one_process(eng, seed, it):
     alpha = [b"ab", b"abc", b"abcdefgh", b"abcdefghijklmnopqrstuvwxyz"][int(rng.integers(4))]
     A = np.frombuffer(alpha, dtype=np.uint8)
     n_terms = int(rng.choice([3, 20, 200, 3000]))
-    maxlen = int(rng.choice([3, 6, 12, 40]))
+    maxlen = int(rng.choice([3, 6, 12, 40, 1000]))
+    if maxlen >= 1000:
+        n_terms = min(n_terms, 400_000 // maxlen)      # (long keywords: an automaton of a few hundred thousand states at most)
     terms = set()
     for _ in range(n_terms):
         terms.add(A[rng.integers(0, len(alpha), int(rng.integers(1, maxlen + 1)))].tobytes())
@@ -153,7 +155,9 @@ def one(eng, seed, it):
     alpha = ALPHAS[int(rng.integers(len(ALPHAS)))]
     A = np.frombuffer(alpha, dtype=np.uint8)
     n_terms = int(rng.choice([1, 3, 20, 200, 2000, 8000]))
-    maxlen = int(rng.choice([3, 5, 8, 12, 30, 300]))
+    maxlen = int(rng.choice([3, 5, 8, 12, 30, 300, 1000, 7424]))      # (7 424: the longest keyword gft_build accepts)
+    if maxlen >= 1000:
+        n_terms = min(n_terms, 400_000 // maxlen)      # (long keywords: an automaton of a few hundred thousand states at most)
     minlen = int(rng.choice([1, 1, 2, 4, 5]))
     terms = set()
     for _ in range(n_terms):
