@@ -107,6 +107,13 @@ SYMBOLS = {
     "gft_group_last_result": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_evaluate": (_i, [_vp, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_last_batch": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_group_set_schema": (_i, [_vp, _vp, _vp, _u32, C.c_char_p, _u64, C.c_char_p, _u64]),
+    "gft_group_n_rule_exprs": (_u32, [_vp]),
+    "gft_group_rule_expr": (_i, [_vp, _u32, C.POINTER(_vp), C.POINTER(_u32), C.POINTER(_vp), C.POINTER(_u32)]),
+    "gft_group_process_records_device": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "gft_group_process_records": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
+    "gft_debug_eval_rules": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp]),
+    "gft_debug_eval_rules_device": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp]),
     "gft_group_dsl_parse": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_dsl_tokens": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_dsl_parse": (_i, [C.c_char_p, _u64, _i, _vp, _u64, C.POINTER(_u64)]),

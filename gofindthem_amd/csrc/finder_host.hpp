@@ -138,6 +138,10 @@ public:
     };
     const std::vector<ExprWrapper>& expressions() const { return expressions_; }
     int last_code() const { return last_code_; }
+    // the engine behind ProcessDevice (nullptr: none), and whether ProcessDevice would take a batch: the GPU substring engine
+    // and no regex terms
+    gft_engine* device_engine() const { return gpu_ ? gpu_->handle() : nullptr; }
+    bool device_resident_ok() const { return device_engine() && gpu_sub_ && regexes_.empty(); }
     uint64_t last_regex_docs = 0;        // documents the host regex engine saw in the last prefiltered ProcessTexts
     uint64_t lowered_on_device = 0, lowered_on_host = 0;   // batches of ProcessDevice / ProcessDeviceEnd repeated, by path
     bool force_host_lower_ = false;      // ProcessTexts is repeating a batch whose text the device cannot fold (finder_host.cpp)

@@ -10,6 +10,8 @@
 #include <unordered_map>
 
 #include "gft_guard.hpp"
+#include "gft_rules.hpp"
+#include "rule_set.hpp"
 
 namespace gft {
 namespace gdsl {
@@ -367,6 +369,7 @@ Error GroupFinder::AddRule(const std::string& ruleName, const std::vector<std::s
         w.ExpressionString = raw;
         w.Expression = std::move(pr.expr);
         rules_[ruleName].push_back(std::move(w));
+        rules_version_++;
         for (const auto& t : pr.tags) tags_.insert(t);
         for (const auto& f : pr.fields) fields_.insert(f);
     }
@@ -563,6 +566,161 @@ Error GroupFinder::EvaluateRules(const gdsl::TagMap& m, RuleResult& out) const {
     return "";
 }
 
+// ---- records (rule_set.hpp, gft_rules.hip) ---------------------------------------------------------------------------
+struct GroupFinder::Records {
+    std::vector<std::string> schema, inc, exc;
+    RuleSet set;
+    uint64_t rules_version = 0;            // what `set` was compiled from
+    size_t n_exprs = 0;
+    uint64_t serial = 0;                   // its copy on the engine (rules_install), 0: not uploaded
+};
+
+const std::vector<GroupFinder::RuleExpr>& GroupFinder::RuleExprs() {
+    if (rule_exprs_version_ != rules_version_) {
+        rule_exprs_.clear();
+        for (const auto& kv : rules_)
+            for (const auto& ew : kv.second) rule_exprs_.push_back(RuleExpr{&kv.first, &ew.ExpressionString});
+        rule_exprs_version_ = rules_version_;
+    }
+    return rule_exprs_;
+}
+
+int GroupFinder::SetSchema(const std::vector<std::string>& paths, const std::vector<std::string>& includePaths,
+                           const std::vector<std::string>& excludePaths, Error& err) {
+    std::set<std::string> seen;
+    for (const auto& p : paths)
+        if (!seen.insert(p).second) { err = "record schema: field path '" + p + "' is listed twice"; return GFT_E_INVALID; }
+    auto next = std::make_shared<Records>();
+    int rc = compile_rules(rules_, findthem_->tags(), findthem_->tag_ids(), paths, includePaths, excludePaths, next->set, err);
+    if (rc) return rc;
+    next->schema = paths; next->inc = includePaths; next->exc = excludePaths;
+    next->rules_version = rules_version_;
+    next->n_exprs = findthem_->expressions().size();
+    rec_ = std::move(next);
+    return GFT_OK;
+}
+
+int GroupFinder::compile_current(Error& err) {
+    if (!rec_) { err = "record batch: no schema set (gft_group_set_schema)"; return GFT_E_INVALID; }
+    if (rec_->rules_version == rules_version_ && rec_->n_exprs == findthem_->expressions().size()) return GFT_OK;
+    RuleSet fresh;
+    int rc = compile_rules(rules_, findthem_->tags(), findthem_->tag_ids(), rec_->schema, rec_->inc, rec_->exc, fresh, err);
+    if (rc) return rc;
+    rec_->set = std::move(fresh);
+    rec_->rules_version = rules_version_;
+    rec_->n_exprs = findthem_->expressions().size();
+    rec_->serial = 0;
+    return GFT_OK;
+}
+
+int GroupFinder::install_current(gft_engine* e, Error& err) {
+    if (rec_->serial && rules_serial(e) == rec_->serial) return GFT_OK;
+    int rc = rules_install(e, rec_->set, &rec_->serial);
+    if (rc) { rec_->serial = 0; err = gft_last_error(e); }
+    return rc;
+}
+
+int GroupFinder::DebugEvalRules(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                                uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap, Error& err) {
+    int rc = compile_current(err);
+    if (rc) return rc;
+    const RuleSet& rs = rec_->set;
+    if (n_exprs != rs.n_exprs) { err = "gft_debug_eval_rules: n_exprs is not the finder's number of expressions"; return GFT_E_INVALID; }
+    err = validate_records(rs.n_fields, leaf_field, rec_off, n_records, n_leaves);
+    if (!err.empty()) return GFT_E_INVALID;
+    if (!n_records || !rs.n_rules) return GFT_OK;
+    if (!rule_bitmap || (n_leaves && n_exprs && !hit_bitmap)) { err = "gft_debug_eval_rules: null argument"; return GFT_E_INVALID; }
+    eval_rules_host(rs, hit_bitmap, leaf_field, rec_off, n_records, rule_bitmap);
+    return GFT_OK;
+}
+
+int GroupFinder::DebugEvalRulesDevice(const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                                      uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err) {
+    int rc = compile_current(err);
+    if (rc) return rc;
+    if (n_exprs != rec_->set.n_exprs) { err = "gft_debug_eval_rules_device: n_exprs is not the finder's number of expressions"; return GFT_E_INVALID; }
+    gft_engine* e = findthem_->device_engine();
+    if (!e) { err = "no GPU engine"; return GFT_E_HIP; }
+    RulesLock whole_call(e);
+    if ((rc = install_current(e, err))) return rc;
+    if ((rc = rules_eval_device(e, d_hit_bitmap, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap))) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::ProcessRecordsDevice(const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                                      uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err) {
+    int rc = compile_current(err);
+    if (rc) return rc;
+    gft_engine* e = findthem_->device_engine();
+    if (!findthem_->device_resident_ok()) { err = "device-resident records need the GPU substring engine and no regex terms"; return GFT_E_UNSUPPORTED; }
+    if (gft_n_devices(e) != 1) { err = "record batches: single-device handles only"; return GFT_E_UNSUPPORTED; }
+    // one state of the engine from the set's install to the read of the flags: another group on the same finder, called from
+    // another thread, installs its own set and uses the same work buffers
+    RulesLock whole_call(e);
+    if ((rc = install_current(e, err))) return rc;
+    const RuleSet& rs = rec_->set;
+    uint32_t* d_hit = nullptr;
+    if (n_leaves && rs.n_exprs) {
+        if (!d_text || !d_leaf_off) { err = "record batch: null argument"; return GFT_E_INVALID; }
+        if ((rc = rules_leaf_bitmap(e, n_leaves, (rs.n_exprs + 31) / 32, &d_hit))) { err = gft_last_error(e); return rc; }
+        err = findthem_->ProcessDevice(d_text, d_leaf_off, n_leaves, d_hit);
+        if (!err.empty()) return findthem_->last_code() ? findthem_->last_code() : GFT_E_ENGINE;
+        // (the finder may have rebuilt its programs, never its expressions: the set installed above still fits)
+    }
+    if ((rc = rules_eval_device(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap))) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::ProcessRecords(const uint8_t* text, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off,
+                                uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap, Error& err) {
+    int rc = compile_current(err);
+    if (rc) return rc;
+    const RuleSet& rs = rec_->set;
+    err = validate_records(rs.n_fields, leaf_field, rec_off, n_records, n_leaves);
+    if (!err.empty()) return GFT_E_INVALID;
+    if (n_leaves && (!text || !leaf_off)) { err = "record batch: null argument"; return GFT_E_INVALID; }
+    for (uint64_t l = 0; l < n_leaves; l++)
+        if (leaf_off[l] > leaf_off[l + 1]) { err = "record batch: leaf_off descends at leaf " + std::to_string(l); return GFT_E_INVALID; }
+    const uint64_t RW = (rs.n_rules + 31) / 32, EW = (rs.n_exprs + 31) / 32;
+    if (!n_records || !RW) return GFT_OK;
+    if (!rule_bitmap) { err = "record batch: null argument"; return GFT_E_INVALID; }
+    gft_engine* e = findthem_->device_engine();
+    if (!e) { err = "no GPU engine"; return GFT_E_HIP; }
+    if (gft_n_devices(e) != 1) { err = "record batches: single-device handles only"; return GFT_E_UNSUPPORTED; }
+    RulesLock whole_call(e);              // (staging buffers, set and work buffers: see ProcessRecordsDevice)
+    static const uint64_t none = 0;
+    void* d[5] = {};
+    if (findthem_->device_resident_ok()) {
+        const uint64_t text_bytes = n_leaves ? leaf_off[n_leaves] : 0;
+        const void* src[5] = {text, n_leaves ? (const void*)leaf_off : &none, leaf_field, rec_off, nullptr};
+        const uint64_t bytes[5] = {text_bytes, (n_leaves + 1) * 8, n_leaves * 4, (n_records + 1) * 8, 0};
+        const uint64_t slack[5] = {64, 0, 0, 0, n_records * RW * 4};
+        if ((rc = rules_stage(e, 5, src, bytes, slack, d))) { err = gft_last_error(e); return rc; }
+        rc = ProcessRecordsDevice((const uint8_t*)d[0], (const uint64_t*)d[1], (const uint32_t*)d[2], (const uint64_t*)d[3], n_records, n_leaves,
+                                  (uint32_t*)d[4], err);
+        if (rc) return rc;
+    } else {
+        // regex terms, the prefilter, injected engines: the finder's own batch path gives the leaf bitmap
+        std::vector<uint32_t> hit((size_t)(n_leaves * EW) + 1, 0);
+        if (n_leaves && EW) {
+            err = findthem_->ProcessTexts(text, leaf_off, n_leaves, hit.data());
+            if (!err.empty()) return findthem_->last_code() ? findthem_->last_code() : GFT_E_ENGINE;
+        }
+        if ((rc = install_current(e, err))) return rc;
+        const void* src[4] = {hit.data(), leaf_field, rec_off, nullptr};
+        const uint64_t bytes[4] = {n_leaves * EW * 4, n_leaves * 4, (n_records + 1) * 8, 0};
+        const uint64_t slack[4] = {0, 0, 0, n_records * RW * 4};
+        if ((rc = rules_stage(e, 4, src, bytes, slack, d))) { err = gft_last_error(e); return rc; }
+        if ((rc = rules_eval_device(e, (const uint32_t*)d[0], (const uint32_t*)d[1], (const uint64_t*)d[2], n_records, n_leaves, (uint32_t*)d[3]))) {
+            err = gft_last_error(e);
+            return rc;
+        }
+        d[4] = d[3];
+    }
+    if ((rc = rules_fetch(e, rule_bitmap, d[4], n_records * RW * 4))) err = gft_last_error(e);
+    return rc;
+}
+
 }  // namespace gft
 
 // ---- C ABI (include/gft.h) --------------------------------------------------------------------------------------
@@ -755,6 +913,65 @@ int gft_group_evaluate(gft_group* g, const uint8_t* tagmap, uint64_t len, char* 
     rules_json(rr, o);
     return put(o, out, cap, needed);
 } GFT_CATCH((g ? &const_cast<gft_group*>(g)->err : nullptr))
+
+int gft_group_set_schema(gft_group* g, const uint8_t* paths_blob, const uint64_t* path_off, uint32_t n_fields, const uint8_t* include_json,
+                         uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len) try {
+    if (!g || (n_fields && !path_off)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> inc, exc, paths;
+    if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
+    for (uint32_t f = 0; f < n_fields; f++) {
+        if (path_off[f] > path_off[f + 1] || (path_off[f + 1] > path_off[f] && !paths_blob)) { g->err = "record schema: broken path offsets"; return GFT_E_INVALID; }
+        paths.emplace_back(paths_blob ? (const char*)paths_blob + path_off[f] : "", (size_t)(path_off[f + 1] - path_off[f]));
+    }
+    return g->g->SetSchema(paths, inc, exc, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+uint32_t gft_group_n_rule_exprs(gft_group* g) try {
+    if (!g) return 0;
+    GFT_GLOCK(g);
+    return (uint32_t)g->g->RuleExprs().size();
+} GFT_CATCH_VALUE(0)
+
+int gft_group_rule_expr(gft_group* g, uint32_t i, const uint8_t** name, uint32_t* name_len, const uint8_t** expr, uint32_t* expr_len) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    const auto& v = g->g->RuleExprs();
+    if (i >= v.size()) { g->err = "gft_group_rule_expr: index out of range"; return GFT_E_INVALID; }
+    if (name) *name = (const uint8_t*)v[i].name->data();
+    if (name_len) *name_len = (uint32_t)v[i].name->size();
+    if (expr) *expr = (const uint8_t*)v[i].expr->data();
+    if (expr_len) *expr_len = (uint32_t)v[i].expr->size();
+    return GFT_OK;
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_process_records_device(gft_group* g, const uint8_t* d_text_blob, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field,
+                                     const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->ProcessRecordsDevice(d_text_blob, d_leaf_off, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_process_records(gft_group* g, const uint8_t* text_blob, const uint64_t* leaf_off, const uint32_t* leaf_field,
+                              const uint64_t* rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->ProcessRecords(text_blob, leaf_off, leaf_field, rec_off, n_records, n_leaves, rule_bitmap, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_eval_rules(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                         uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugEvalRules(hit_bitmap, n_exprs, leaf_field, rec_off, n_records, n_leaves, rule_bitmap, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_eval_rules_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
+                                const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugEvalRulesDevice(d_hit_bitmap, n_exprs, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
 
 int gft_group_last_batch(const gft_group* g, uint64_t* leaves, uint64_t* bytes) try {
     if (!g) return GFT_E_INVALID;

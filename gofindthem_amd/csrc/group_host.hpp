@@ -117,6 +117,29 @@ public:
     // EvaluateRules (finder.go:118-137)
     Error EvaluateRules(const gdsl::TagMap& m, RuleResult& out) const;
 
+    // ---- records: a batch of (field, string) leaves under a schema of field paths, rules evaluated on the device
+    // (rule_set.hpp, gft_rules.hip).  Every function returns a gft_status and leaves the text of a failure in `err`.
+    // Stores the schema after compiling the rules against it: a refusal leaves the previous schema and set answering.
+    int SetSchema(const std::vector<std::string>& paths, const std::vector<std::string>& includePaths,
+                  const std::vector<std::string>& excludePaths, Error& err);
+    // rule expression i in the order of the rule bitmap's bits: ascending rule name, AddRule order inside a name
+    struct RuleExpr { const std::string* name; const std::string* expr; };
+    const std::vector<RuleExpr>& RuleExprs();
+    // device pointers; the leaves go through Finder::ProcessDevice into an engine-owned bitmap, then the two kernels
+    int ProcessRecordsDevice(const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                             uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err);
+    // host pointers: upload + ProcessRecordsDevice when the finder qualifies, else Finder::ProcessTexts and the bitmap uploaded
+    int ProcessRecords(const uint8_t* text, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
+                       uint64_t n_leaves, uint32_t* rule_bitmap, Error& err);
+    // the compiled device words interpreted on the host over a caller-supplied leaf bitmap: no device
+    int DebugEvalRules(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
+                       uint64_t n_leaves, uint32_t* rule_bitmap, Error& err);
+
+    // the two kernels over a caller-supplied leaf bitmap on the device (the device half of the proof: what the kernels make of
+    // rows the finder did not write, bits at and above n_exprs included)
+    int DebugEvalRulesDevice(const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                             uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err);
+
     const std::map<std::string, std::vector<ExpressionWrapper>>& rules() const { return rules_; }
     const std::set<std::string>& fields() const { return fields_; }
     const std::set<std::string>& tags() const { return tags_; }
@@ -127,6 +150,14 @@ private:
     Finder* findthem_;
     std::map<std::string, std::vector<ExpressionWrapper>> rules_;
     std::set<std::string> fields_, tags_;
+
+    struct Records;                        // schema, compiled RuleSet and what it was compiled from (group_host.cpp)
+    std::shared_ptr<Records> rec_;
+    uint64_t rules_version_ = 0;           // counts AddRule calls that changed rules_
+    std::vector<RuleExpr> rule_exprs_;
+    uint64_t rule_exprs_version_ = ~0ull;
+    int compile_current(Error& err);       // the set for the stored schema, redone when rules / finder expressions changed
+    int install_current(gft_engine* e, Error& err);
 };
 
 // isValidateFieldPath (internal.go:99-119)

@@ -9,6 +9,8 @@ attributes with an upper-case first letter are visible, like exported Go struct 
 import ctypes as C
 import json
 
+import numpy as np
+
 from . import _lib
 from .engine import pack
 from .finder import Finder
@@ -167,6 +169,127 @@ class GroupFinder:
 
     def ProcessText(self, data):                                                   # finder.go:186-196
         return self.ProcessObject(data)
+
+    # -- records: columns of strings instead of JSON documents, rules evaluated on the device -----------------
+    def SetSchema(self, paths, includePaths=None, excludePaths=None):
+        """the field paths of the record form ("Body", "Meta.Notes", "items.index(2)", "" for TagText), unique"""
+        raws = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in paths]
+        blob, off = pack(raws)
+        inc = json.dumps(list(includePaths)).encode() if includePaths else None
+        exc = json.dumps(list(excludePaths)).encode() if excludePaths else None
+        rc = self._L.gft_group_set_schema(self._h, blob.ctypes.data, off.ctypes.data, len(raws), inc, len(inc) if inc else 0,
+                                          exc, len(exc) if exc else 0)
+        if rc != 0:
+            raise self._err(rc)
+        self._schema = {p: i for i, p in enumerate(raws)}
+
+    def rule_exprs(self):
+        """[(rule name, expression string)] in the order of the rule bitmap's bits"""
+        out = []
+        name, expr, nl, el = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
+        for i in range(self._L.gft_group_n_rule_exprs(self._h)):
+            rc = self._L.gft_group_rule_expr(self._h, i, C.byref(name), C.byref(nl), C.byref(expr), C.byref(el))
+            if rc != 0:
+                raise self._err(rc)
+            out.append((C.string_at(name.value, nl.value).decode("utf-8", "replace") if nl.value else "",
+                        C.string_at(expr.value, el.value).decode("utf-8", "replace") if el.value else ""))
+        return out
+
+    def rule_words(self):
+        return (self._L.gft_group_n_rule_exprs(self._h) + 31) // 32
+
+    def pack_records(self, records):
+        """[[(path or field index, str)]] -> (text_blob with slack, leaf_off, leaf_field, rec_off)"""
+        schema = getattr(self, "_schema", None)
+        if schema is None:
+            raise GroupFinderError(_lib.GFT_E_INVALID, "no schema set (SetSchema)")
+        texts, fields, rec_off = [], [], [0]
+        for rec in records:
+            for field, text in rec:
+                if not isinstance(field, (int, np.integer)):
+                    key = field.encode("utf-8") if isinstance(field, str) else bytes(field)
+                    if key not in schema:
+                        raise GroupFinderError(_lib.GFT_E_INVALID, "field path %r is not in the schema" % (field,))
+                    field = schema[key]
+                fields.append(int(field))
+                texts.append(text.encode("utf-8") if isinstance(text, str) else bytes(text))
+            rec_off.append(len(texts))
+        blob, off = pack(texts)
+        blob = np.concatenate([blob, np.zeros(64, dtype=np.uint8)])          # the readable slack every scan wants
+        return blob, off, np.asarray(fields, dtype=np.uint32), np.asarray(rec_off, dtype=np.uint64)
+
+    def ProcessRecordsBitmap(self, blob, leaf_off, leaf_field, rec_off):
+        """host arrays of the record form -> the dense rule bitmap u32[n_records, ceil(R / 32)]"""
+        n_records, n_leaves = len(rec_off) - 1, len(leaf_field)
+        out = np.zeros((n_records, self.rule_words()), dtype=np.uint32)
+        rc = self._L.gft_group_process_records(self._h, blob.ctypes.data, leaf_off.ctypes.data, leaf_field.ctypes.data, rec_off.ctypes.data,
+                                               n_records, n_leaves, out.ctypes.data)
+        if rc != 0:
+            raise self._err(rc)
+        return out
+
+    def rules_from_bitmap(self, bitmap):
+        """rows of the rule bitmap -> one expressionsByRule dict per record"""
+        names = self.rule_exprs()
+        res = []
+        for row in np.asarray(bitmap):
+            d = {}
+            for w, word in enumerate(row):
+                word = int(word)
+                while word:
+                    b = (word & -word).bit_length() - 1
+                    word &= word - 1
+                    name, expr = names[w * 32 + b]
+                    d.setdefault(name, []).append(expr)
+            res.append(d)
+        return res
+
+    def ProcessRecords(self, records):
+        """records: a list of lists of (path or field index, str).  One expressionsByRule dict per record, what ProcessObject
+        gives for an object with exactly those leaves."""
+        return self.rules_from_bitmap(self.ProcessRecordsBitmap(*self.pack_records(records)))
+
+    def ProcessRecordsDevice(self, text, leaf_off, leaf_field, rec_off):
+        """torch device tensors (uint8 text with 64 bytes of slack, leaf_off / rec_off as 64-bit, leaf_field as 32-bit integers) ->
+        the rule bitmap as a device tensor int32[n_records, ceil(R / 32)] (the bits of the u32 words)"""
+        import torch
+        n_records, n_leaves = int(rec_off.numel()) - 1, int(leaf_field.numel())
+        for t, size in ((text, 1), (leaf_off, 8), (leaf_field, 4), (rec_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "ProcessRecordsDevice takes contiguous device tensors of 1, 8, 4 and 8 byte integers")
+        out = torch.zeros((max(n_records, 0), self.rule_words()), dtype=torch.int32, device=text.device)
+        torch.cuda.current_stream(text.device).synchronize()          # (the library runs on the engine's own stream)
+        rc = self._L.gft_group_process_records_device(self._h, text.data_ptr(), leaf_off.data_ptr(), leaf_field.data_ptr(), rec_off.data_ptr(),
+                                                      n_records, n_leaves, out.data_ptr())
+        if rc != 0:
+            raise self._err(rc)
+        return out
+
+    def debug_eval_rules_device(self, hit_bitmap, n_exprs, leaf_field, rec_off):
+        """gft_debug_eval_rules_device: the two rule kernels over a caller-supplied leaf bitmap (torch device tensors, int32 rows,
+        int32 fields, int64 offsets) -> the rule bitmap as a device tensor"""
+        import torch
+        n_records, n_leaves = int(rec_off.numel()) - 1, int(leaf_field.numel())
+        out = torch.zeros((max(n_records, 0), self.rule_words()), dtype=torch.int32, device=rec_off.device)
+        torch.cuda.current_stream(rec_off.device).synchronize()
+        rc = self._L.gft_debug_eval_rules_device(self._h, hit_bitmap.data_ptr(), n_exprs, leaf_field.data_ptr(), rec_off.data_ptr(),
+                                                 n_records, n_leaves, out.data_ptr())
+        if rc != 0:
+            raise self._err(rc)
+        return out
+
+    def debug_eval_rules(self, hit_bitmap, n_exprs, leaf_field, rec_off):
+        """gft_debug_eval_rules: the compiled device words on the host over a caller-supplied leaf bitmap (no device)"""
+        hit_bitmap = np.ascontiguousarray(hit_bitmap, dtype=np.uint32)
+        leaf_field = np.ascontiguousarray(leaf_field, dtype=np.uint32)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        n_records, n_leaves = len(rec_off) - 1, len(leaf_field)
+        out = np.zeros((n_records, self.rule_words()), dtype=np.uint32)
+        rc = self._L.gft_debug_eval_rules(self._h, hit_bitmap.ctypes.data, n_exprs, leaf_field.ctypes.data, rec_off.ctypes.data,
+                                          n_records, n_leaves, out.ctypes.data)
+        if rc != 0:
+            raise self._err(rc)
+        return out
 
     def last_batch(self):
         """(string leaves, text bytes) the last call sent through the finder"""

@@ -394,6 +394,46 @@ int gft_group_last_result(const gft_group* g, char* out, uint64_t cap, uint64_t*
 int gft_group_evaluate(gft_group* g, const uint8_t* tagmap_json, uint64_t len, char* out, uint64_t cap, uint64_t* needed);
 /* string leaves and text bytes the last gft_group_process_jsons call sent through the finder (measurement) */
 int gft_group_last_batch(const gft_group* g, uint64_t* leaves, uint64_t* bytes);
+/* ---- Records: a batch that is columns of strings already, rules evaluated on the device (gft_rules.hip) ------------
+ * A schema is F unique field paths, byte strings as the object walk builds them ("Body", "Meta.Notes", "items.index(2)",
+ * "" for the TagText case); include / exclude as in gft_group_process_jsons, exclude wins.  A batch is N records in CSR
+ * form over leaves: record r owns the leaves rec_off[r] .. rec_off[r + 1], leaf l lies in field leaf_field[l] of the
+ * schema and holds the bytes leaf_off[l] .. leaf_off[l + 1] of text_blob (64 readable bytes behind the text, as for every
+ * scan).  A record may have no leaves and may name a field more than once; an empty string is a leaf.  The result is
+ * rule_bitmap[r * ceil(R / 32) + (i >> 5)] bit (i & 31) = rule expression i is true for record r -- what EvaluateRules of
+ * TagObject gives for an object with exactly those (path, string) leaves.  Rule expressions are numbered by ascending rule
+ * name (byte order), AddRule order inside a name.
+ * The rules are compiled against the schema here (a refusal leaves the previous schema and its set answering) and again,
+ * lazily, once rules or finder expressions have been added.  GFT_E_UNSUPPORTED names the limit: more than 65535 fields,
+ * more than 8192 distinct (tag, field path) units, an expression that needs an operand stack deeper than 32. */
+int gft_group_set_schema(gft_group* g, const uint8_t* paths_blob, const uint64_t* path_off, uint32_t n_fields,
+                         const uint8_t* include_json, uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len);
+uint32_t gft_group_n_rule_exprs(gft_group* g);
+/* rule name and expression string of bit i; the pointers stay valid until the next gft_group_add_rule */
+int gft_group_rule_expr(gft_group* g, uint32_t i, const uint8_t** name, uint32_t* name_len, const uint8_t** expr, uint32_t* expr_len);
+/* Every pointer is a device pointer.  The leaves go through gft_finder_process_device (its limits apply: GPU substring
+ * engine, no regex terms, one device; a batch that leaves ASCII is lowered and scanned again on the device) into a bitmap
+ * the engine owns, then the two rule kernels run on the engine's stream; only the status crosses the link.  GFT_E_INVALID:
+ * no schema, a leaf_field entry >= F, rec_off that descends or does not end at n_leaves, leaves but no records (also for a
+ * group without rules: both calls check the same things).  GFT_E_NOMEM: no room for the work buffers.  n_records == 0,
+ * n_leaves == 0 and a group without rules are valid.  Groups that share a finder may be called from several threads: a
+ * call holds the engine from the install of its rule set to the end. */
+int gft_group_process_records_device(gft_group* g, const uint8_t* d_text_blob, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field,
+                                     const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap);
+/* Host pointers.  A finder that qualifies for the call above: upload, that call, the rule bitmap back.  Any other finder
+ * (regex terms, injected engines): the leaf bitmap comes from gft_finder_process_texts and is uploaded to the same kernels.
+ * Both routes give the same rows; a finder error is the call's error. */
+int gft_group_process_records(gft_group* g, const uint8_t* text_blob, const uint64_t* leaf_off, const uint32_t* leaf_field,
+                              const uint64_t* rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap);
+/* The compiled device words (field masks, units, postfix programs) interpreted on the host over a caller-supplied leaf
+ * bitmap [n_leaves][ceil(n_exprs / 32)]; n_exprs must be the finder's number of expressions.  Needs no device. */
+int gft_debug_eval_rules(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                         uint64_t n_records, uint64_t n_leaves, uint32_t* rule_bitmap);
+/* The same two kernels that gft_group_process_records_device runs, over a caller-supplied leaf bitmap on the device (every
+ * pointer is a device pointer): what the kernels make of rows the finder did not write.  Bits at and above n_exprs in a
+ * row's last word are ignored.  One device; validation as for the call above. */
+int gft_debug_eval_rules_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
+                                const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap);
 /* group DSL alone (host only): {"tree":..,"tags":[..],"fields":[..]} or {"error":..}; token list as gft_dsl_tokens */
 int gft_group_dsl_parse(const uint8_t* expr, uint64_t len, char* out, uint64_t cap, uint64_t* needed);
 int gft_group_dsl_tokens(const uint8_t* expr, uint64_t len, char* out, uint64_t cap, uint64_t* needed);
