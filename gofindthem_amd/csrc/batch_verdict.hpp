@@ -1,6 +1,6 @@
 // batch_verdict.hpp -- what a batch reports back, as values: the control block the kernels of a batch write and the host
 // reads once, the verdict a scan established, what a scan launch knew, the judgement on a launch that ran without knowing
-// its sizes, and what batches teach the next ones.  Host arithmetic only: no device, no handle -- gft_api.cpp reads the
+// its sizes, and what batches teach the next ones.  Host arithmetic only: no device, no handle -- gft_pipeline.cpp reads the
 // block back and applies the judgement, gft_debug_judge_batch / gft_debug_learn run the same functions on the CPU.
 #pragma once
 #include <algorithm>

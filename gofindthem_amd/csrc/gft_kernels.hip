@@ -67,13 +67,8 @@ __global__ void __launch_bounds__(256) k_unit_fill(const uint64_t* __restrict__ 
     uint64_t b = unit_base[d];
     uint32_t k = (uint32_t)(unit_base[d + 1] - b);
     if (k == 0) return;
-    uint64_t per = (n + k - 1) / k;
-    if (per > unit_max) per = unit_max;                 // (never taken when cnt came from k_unit_count with the same unit_max)
-    for (uint32_t i = 0; i < k; i++) {
-        uint64_t lo = (uint64_t)i * per, hi = lo + per < n ? lo + per : n;
-        if (lo > n) lo = n;
-        if (b + i < max_units) units[b + i] = Unit{(uint32_t)d, (uint32_t)lo, (uint32_t)hi};
-    }
+    for (uint32_t i = 0; i < k; i++)
+        if (b + i < max_units) units[b + i] = unit_slice((uint32_t)d, n, k, i, unit_max);
 }
 
 // The whole unit table in one launch for the batch in which every document is ONE unit (the common shape: documents up to

@@ -1,5 +1,6 @@
-// Kernel parameter blocks + launcher prototypes shared by the kernels (*.hip) and gft_api.cpp; the solver's limits and
-// program word formats, shared with the program compiler (program_set.cpp) as well.
+// Kernel parameter blocks + launcher prototypes shared by the kernels (*.hip) and the orchestration (gft_pipeline.cpp and
+// its neighbours: gft_engine.hpp); the solver's limits and program word formats, shared with the program compiler
+// (program_set.cpp) as well.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,6 +26,14 @@ constexpr uint32_t kMaxPairDepthWide = 64;       // (a stack entry per lane)
 
 // a work unit: matches whose END offset lies in [lo, hi) of document `doc`
 struct Unit { uint32_t doc, lo, hi; };
+// Unit i of the k equal slices of document `doc` (n bytes): per = ceil(n / k) bytes each, clamped to unit_max -- never taken
+// when k = ceil(n / unit_max), k_unit_count's figure --, the last one shorter.  k_unit_fill and the host's unit table.
+__host__ __device__ inline Unit unit_slice(uint32_t doc, uint64_t n, uint64_t k, uint64_t i, uint32_t unit_max) {
+    uint64_t per = (n + k - 1) / k;
+    if (per > unit_max) per = unit_max;
+    const uint64_t lo = i * per < n ? i * per : n, hi = lo + per < n ? lo + per : n;
+    return Unit{doc, (uint32_t)lo, (uint32_t)hi};
+}
 
 struct ScanParams {
     const uint8_t* text;

@@ -1,6 +1,6 @@
 // solve_plan.hpp -- which solver kernel a program set runs, and with what: the presence matrix's place and width, the
 // programs' place, the kernel variant, the LDS need and the grid, decided by ONE function from a few numbers.  Host
-// arithmetic only: no device, no handle, no environment -- solve_pipeline (gft_api.cpp) sizes its buffers from the plan and
+// arithmetic only: no device, no handle, no environment -- solve_pipeline (gft_pipeline.cpp) sizes its buffers from the plan and
 // hands it to launch_solve (gft_solve.hip), which looks the kernel up and decides nothing; gft_debug_plan_solve runs the
 // same function on the CPU.
 #pragma once

@@ -30,7 +30,7 @@ E_ACUTE = "é".encode("utf-8")
 
 
 def unit_slice(n, unit_max):
-    """bytes per work unit of a document of n bytes (k_unit_fill, and the host's unit table in gft_api.cpp): equal slices"""
+    """bytes per work unit of a document of n bytes (unit_slice of gft_kernels.hpp: k_unit_fill, and the host's unit table in gft_pipeline.cpp): equal slices"""
     k = 1 if n <= unit_max else (n + unit_max - 1) // unit_max
     return (n + k - 1) // k if n else 0
 

@@ -644,7 +644,7 @@ def test_process_device_begin_end_pipelines_two_batches():
 
 def test_steady_state_batches_are_scanned_once():
     """A sequence of equal batches settles on ONE scan launch and ONE solver launch per batch: the
-    deferred verdict (gft_api.cpp deferred_interpret) must not send a batch of single-unit documents around again, on the
+    deferred verdict (gft_pipeline.cpp deferred_interpret) must not send a batch of single-unit documents around again, on the
     synchronous entry point and with two batches in flight alike -- a rerun is invisible in the results, so the profile
     counters (gft_profile_read) are what this test reads."""
     import ctypes as C
