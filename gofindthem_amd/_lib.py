@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("GFT_LIBRARY") or os.path.join(HERE, "libgft.so")   # 
 GFT_OK, GFT_E_INVALID, GFT_E_NOT_BUILT, GFT_E_HIP, GFT_E_UNSUPPORTED, GFT_E_PARSE, GFT_E_ENGINE = 0, -1, -2, -3, -4, -5, -6
 GFT_E_NOMEM, GFT_E_INTERNAL, GFT_W_NO_RCCL = -7, -8, 1
 GFT_POS_START, GFT_POS_END = 0, 1
+GFT_JSON_OK, GFT_JSON_SYNTAX, GFT_JSON_DEPTH, GFT_JSON_PATH, GFT_JSON_KEY, GFT_JSON_DUP, GFT_JSON_TEXT = range(7)
 GFT_FOLD_ASCII = 1
 GFT_SCAN_UNIQUE = 2
 GFT_POS_RUNES = 4
@@ -114,6 +115,13 @@ SYMBOLS = {
     "gft_group_process_records": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp]),
     "gft_debug_eval_rules": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp]),
     "gft_debug_eval_rules_device": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp]),
+    "gft_group_json_leaves_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "gft_group_process_jsons_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "gft_group_process_jsons_schema": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "gft_group_json_last": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_json_leaves_ref": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "gft_debug_emulate_json_leaves": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
+    "gft_debug_json_schema_find": (C.c_int64, [_vp, C.c_int64, C.c_char_p, _u32, C.POINTER(C.c_int64)]),
     "gft_group_dsl_parse": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_dsl_tokens": (_i, [C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_dsl_parse": (_i, [C.c_char_p, _u64, _i, _vp, _u64, C.POINTER(_u64)]),

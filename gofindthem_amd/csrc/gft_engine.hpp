@@ -186,6 +186,14 @@ struct gft_engine {
         DevBuf expr_tag, masks, units, prog, prog_off, leaf_bitmap, tag_rows, flags, stage[6];
     } d_rules;
 
+    // JSON documents decoded on the device (gft_json.hip): the installed schema trie, the counts and prefix sums of a batch, the
+    // record arrays of gft_group_process_jsons_device, staging for the host-pointer entry point
+    struct JsonBufs {
+        uint64_t serial = 0;               // 0: no trie installed
+        uint32_t n_nodes = 0, table_mask = 0, max_key_len = 0;
+        DevBuf nodes, keys, table, cnt_leaves, cnt_text, text_off, partial, flags, rec_off, leaf_field, leaf_off, text, blob, doc_off, status, rows;
+    } d_json;
+
     // profiling
     int profiling = 0;                     // gft_profile_enable: 0 off, 1 every category, 2 the scan kernel only
     std::vector<hipEvent_t> prof_pool;     // events given back by gft_profile_reset

@@ -1,0 +1,173 @@
+// gft_json_api.cpp -- JSON documents decoded on the device into the record form (gft_json.hpp): the engine's side, which
+// group_host.cpp drives.
+#include "gft_engine.hpp"
+
+#include <atomic>
+
+#include "gft_json.hpp"
+#include "json_schema.hpp"
+
+using namespace gft;
+using namespace gft::api;
+
+namespace {
+int json_entry_checks(gft_engine* e) {
+    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, "JSON batches: single-device handles only");
+    return check_ready(e, kNeedDevice | kNeedSettled, "JSON batches");
+}
+int json_room(gft_engine* e, gft_engine::DevBuf& b, uint64_t bytes) {
+    const hipError_t h = b.ensure(std::max<uint64_t>(bytes, 16));
+    if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, "no device memory for the JSON batch's work buffers"); }
+    return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, "JSON batch alloc");
+}
+bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    if (!a || !b || !a_bytes || !b_bytes) return false;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + b_bytes && y < x + a_bytes;
+}
+}  // namespace
+
+namespace gft {
+
+int json_install(gft_engine* e, const JsonSchema& s, uint64_t* serial) try {
+    if (!e || !serial) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    auto& J = e->d_json;
+    J.serial = 0;                          // (a failed upload leaves no trie)
+    if ((rc = upload(e, J.nodes, s.nodes, "JSON schema upload"))) return rc;
+    if ((rc = upload(e, J.keys, s.keys, "JSON schema upload"))) return rc;
+    if ((rc = upload(e, J.table, s.table, "JSON schema upload"))) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream), "JSON schema upload");
+    J.n_nodes = (uint32_t)s.nodes.size(); J.table_mask = (uint32_t)s.table.size() - 1; J.max_key_len = s.max_key_len;
+    static std::atomic<uint64_t> next_serial{1};
+    *serial = J.serial = next_serial.fetch_add(1);
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+uint64_t json_serial(gft_engine* e) {
+    if (!e) return 0;
+    GFT_LOCK(e);
+    return e->d_json.serial;
+}
+
+int json_leaves_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint64_t* d_rec_off,
+                       uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text, uint64_t text_cap, uint64_t* totals) try {
+    if (!e) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    auto& J = e->d_json;
+    if (!J.serial) return fail(e, GFT_E_INVALID, "JSON batch: no schema installed");
+    if (!d_rec_off || (n_docs && (!d_blob || !d_doc_off || !d_status))) return fail(e, GFT_E_INVALID, "JSON batch: null argument");
+    if ((leaf_cap && (!d_leaf_field || !d_leaf_off)) || (text_cap && !d_text)) return fail(e, GFT_E_INVALID, "JSON batch: a cap but no array");
+    DeviceGuard g(e->device);
+    hipStream_t st = e->stream;
+    if (totals) totals[0] = totals[1] = 0;
+    if (!n_docs) {
+        HIP_TRY(hipMemsetAsync(d_rec_off, 0, 8, st), "JSON offsets");
+        if (d_leaf_off) HIP_TRY(hipMemsetAsync(d_leaf_off, 0, 8, st), "JSON offsets");
+        HIP_TRY(hipStreamSynchronize(st), "JSON offsets");
+        return GFT_OK;
+    }
+    uint64_t ends[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_doc_off, 8, hipMemcpyDeviceToHost, st), "JSON offsets");
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_doc_off + n_docs, 8, hipMemcpyDeviceToHost, st), "JSON offsets");
+    HIP_TRY(hipStreamSynchronize(st), "JSON offsets");
+    if (ends[1] < ends[0]) return fail(e, GFT_E_INVALID, "gft_group_json_leaves_device: document offsets descend");
+    const struct { const void* p; uint64_t bytes; } in[2] = {{d_blob + ends[0], ends[1] - ends[0] + 64}, {d_doc_off, (n_docs + 1) * 8}},
+        outs[5] = {{d_status, n_docs}, {d_rec_off, (n_docs + 1) * 8}, {d_leaf_field, leaf_cap * 4}, {d_leaf_off, d_leaf_off ? (leaf_cap + 1) * 8 : 0},
+                   {d_text, text_cap}};
+    for (const auto& i : in)
+        for (const auto& o : outs)
+            if (overlap(i.p, i.bytes, o.p, o.bytes)) return fail(e, GFT_E_INVALID, "gft_group_json_leaves_device: the output overlaps the input");
+    if ((rc = json_room(e, J.cnt_leaves, n_docs * 4)) || (rc = json_room(e, J.cnt_text, n_docs * 4)) || (rc = json_room(e, J.text_off, (n_docs + 1) * 8)) ||
+        (rc = json_room(e, J.partial, scan_partials_needed(n_docs) * 8)) || (rc = json_room(e, J.flags, 16)))
+        return rc;
+    JsonParams P{};
+    P.blob = d_blob; P.doc_off = d_doc_off; P.n_docs = n_docs;
+    P.T = JsonTrie{J.nodes.as<JsonTrieNode>(), J.keys.as<uint8_t>(), J.table.as<uint32_t>(), J.table_mask, J.n_nodes, J.max_key_len};
+    P.status = d_status; P.cnt_leaves = J.cnt_leaves.as<uint32_t>(); P.cnt_text = J.cnt_text.as<uint32_t>(); P.flags = J.flags.as<uint32_t>();
+    P.rec_off = d_rec_off; P.text_off = J.text_off.as<uint64_t>();
+    P.leaf_field = d_leaf_field; P.leaf_off = d_leaf_off; P.text = d_text; P.leaf_cap = leaf_cap; P.text_cap = text_cap;
+    HIP_TRY(hipMemsetAsync(P.flags, 0, 8, st), "JSON count");
+    {
+        ProfScope ps(e, "json_count");
+        HIP_TRY(launch_json_count(P, e->n_cus, st), "JSON count kernel launch");
+    }
+    {
+        ProfScope ps(e, "json_scan");
+        HIP_TRY(launch_exclusive_scan(P.cnt_leaves, n_docs, d_rec_off, J.partial.as<uint64_t>(), st), "JSON scan");
+        HIP_TRY(launch_exclusive_scan(P.cnt_text, n_docs, J.text_off.as<uint64_t>(), J.partial.as<uint64_t>(), st), "JSON scan");
+    }
+    uint64_t h_tot[2] = {0, 0};
+    uint32_t h_flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&h_tot[0], d_rec_off + n_docs, 8, hipMemcpyDeviceToHost, st), "JSON totals");
+    HIP_TRY(hipMemcpyAsync(&h_tot[1], J.text_off.as<uint64_t>() + n_docs, 8, hipMemcpyDeviceToHost, st), "JSON totals");
+    HIP_TRY(hipMemcpyAsync(h_flags, P.flags, 8, hipMemcpyDeviceToHost, st), "JSON totals");
+    HIP_TRY(hipStreamSynchronize(st), "JSON count");
+    if (h_flags[0]) return fail(e, GFT_E_INVALID, "gft_group_json_leaves_device: document offsets descend, or a document of 4 GiB or more");
+    if (totals) { totals[0] = h_tot[0]; totals[1] = h_tot[1]; }
+    if (d_leaf_off || d_text) {
+        ProfScope ps(e, "json_write");
+        HIP_TRY(launch_json_write(P, e->n_cus, st), "JSON write kernel launch");
+    }
+    HIP_TRY(hipStreamSynchronize(st), "JSON write");
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int json_leaves_owned(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                      const uint64_t** d_rec_off, const uint32_t** d_leaf_field, const uint64_t** d_leaf_off, const uint8_t** d_text,
+                      uint64_t* totals) try {
+    if (!e || !d_rec_off || !d_leaf_field || !d_leaf_off || !d_text || !totals) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    auto& J = e->d_json;
+    if ((rc = json_room(e, J.rec_off, (n_docs + 1) * 8)) || (rc = json_room(e, J.leaf_field, 16)) || (rc = json_room(e, J.leaf_off, 16)) ||
+        (rc = json_room(e, J.text, 64)))
+        return rc;
+    for (int round = 0;; round++) {
+        const uint64_t leaf_cap = std::min<uint64_t>(J.leaf_field.cap / 4, J.leaf_off.cap / 8 - 1), text_cap = J.text.cap - 64;
+        if ((rc = json_leaves_device(e, d_blob, d_doc_off, n_docs, d_status, J.rec_off.as<uint64_t>(), J.leaf_field.as<uint32_t>(),
+                                     J.leaf_off.as<uint64_t>(), leaf_cap, J.text.as<uint8_t>(), text_cap, totals)))
+            return rc;
+        if (totals[0] <= leaf_cap && totals[1] <= text_cap) break;
+        if (round) return fail(e, GFT_E_INTERNAL, "JSON batch: the record arrays do not fit the buffers grown for them");
+        if ((rc = json_room(e, J.leaf_field, totals[0] * 4)) || (rc = json_room(e, J.leaf_off, (totals[0] + 1) * 8)) ||
+            (rc = json_room(e, J.text, totals[1] + 64)))
+            return rc;
+    }
+    HIP_TRY(hipMemsetAsync(J.text.as<uint8_t>() + totals[1], 0, 64, e->stream), "JSON text slack");
+    HIP_TRY(hipStreamSynchronize(e->stream), "JSON text slack");
+    *d_rec_off = J.rec_off.as<uint64_t>(); *d_leaf_field = J.leaf_field.as<uint32_t>();
+    *d_leaf_off = J.leaf_off.as<uint64_t>(); *d_text = J.text.as<uint8_t>();
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int json_stage(gft_engine* e, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint64_t row_bytes, const uint8_t** d_blob,
+               const uint64_t** d_doc_off, uint8_t** d_status, uint32_t** d_rows) try {
+    if (!e || !doc_off || !d_blob || !d_doc_off || !d_status || !d_rows) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    SyncOnExit drain(e);
+    auto& J = e->d_json;
+    const uint64_t lo = doc_off[0], bytes = doc_off[n_docs] - lo;
+    if ((rc = json_room(e, J.blob, lo + bytes + 64)) || (rc = json_room(e, J.doc_off, (n_docs + 1) * 8)) || (rc = json_room(e, J.status, n_docs)) ||
+        (rc = json_room(e, J.rows, n_docs * row_bytes)))
+        return rc;
+    // (the offsets stay as the caller gave them: the blob keeps its place in the buffer)
+    if (bytes) HIP_TRY(hipMemcpyAsync(J.blob.as<uint8_t>() + lo, blob + lo, bytes, hipMemcpyHostToDevice, e->stream), "JSON batch upload");
+    HIP_TRY(hipMemsetAsync(J.blob.as<uint8_t>() + lo + bytes, 0, 64, e->stream), "JSON batch upload");
+    HIP_TRY(hipMemcpyAsync(J.doc_off.p, doc_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, e->stream), "JSON batch upload");
+    HIP_TRY(hipStreamSynchronize(e->stream), "JSON batch upload");
+    *d_blob = J.blob.as<uint8_t>(); *d_doc_off = J.doc_off.as<uint64_t>(); *d_status = J.status.as<uint8_t>(); *d_rows = J.rows.as<uint32_t>();
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+}  // namespace gft

@@ -10,7 +10,9 @@
 #include <unordered_map>
 
 #include "gft_guard.hpp"
+#include "gft_json.hpp"
 #include "gft_rules.hpp"
+#include "json_schema.hpp"
 #include "rule_set.hpp"
 
 namespace gft {
@@ -573,6 +575,10 @@ struct GroupFinder::Records {
     uint64_t rules_version = 0;            // what `set` was compiled from
     size_t n_exprs = 0;
     uint64_t serial = 0;                   // its copy on the engine (rules_install), 0: not uploaded
+    JsonSchema json;                       // the schema's component trie (json_schema.hpp) ...
+    int json_rc = GFT_OK;                  // ... or why there is none: the JSON calls answer this
+    Error json_err;
+    uint64_t json_serial = 0;              // its copy on the engine (json_install)
 };
 
 const std::vector<GroupFinder::RuleExpr>& GroupFinder::RuleExprs() {
@@ -596,6 +602,7 @@ int GroupFinder::SetSchema(const std::vector<std::string>& paths, const std::vec
     next->schema = paths; next->inc = includePaths; next->exc = excludePaths;
     next->rules_version = rules_version_;
     next->n_exprs = findthem_->expressions().size();
+    next->json_rc = compile_json_schema(paths, next->json, next->json_err);
     rec_ = std::move(next);
     return GFT_OK;
 }
@@ -721,6 +728,127 @@ int GroupFinder::ProcessRecords(const uint8_t* text, const uint64_t* leaf_off, c
     return rc;
 }
 
+// ---- JSON decoded on the device (json_schema.hpp, gft_json.hip) ---------------------------------------------------------
+int GroupFinder::json_current(gft_engine* e, Error& err) {
+    if (!rec_) { err = "JSON batch: no schema set (gft_group_set_schema)"; return GFT_E_INVALID; }
+    if (rec_->json_rc) { err = rec_->json_err; return rec_->json_rc; }
+    if (!e || (rec_->json_serial && json_serial(e) == rec_->json_serial)) return GFT_OK;
+    int rc = json_install(e, rec_->json, &rec_->json_serial);
+    if (rc) { rec_->json_serial = 0; err = gft_last_error(e); }
+    return rc;
+}
+
+int GroupFinder::JsonLeavesDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint64_t* d_rec_off,
+                                  uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text, uint64_t text_cap,
+                                  uint64_t* totals, Error& err) {
+    int rc = json_current(nullptr, err);
+    if (rc) return rc;
+    gft_engine* e = findthem_->device_engine();
+    if (!e) { err = "no GPU engine"; return GFT_E_HIP; }
+    if (gft_n_devices(e) != 1) { err = "JSON batches: single-device handles only"; return GFT_E_UNSUPPORTED; }
+    RulesLock whole_call(e);               // (another group on the same finder installs its own trie)
+    if ((rc = json_current(e, err))) return rc;
+    if ((rc = json_leaves_device(e, d_blob, d_doc_off, n_docs, d_status, d_rec_off, d_leaf_field, d_leaf_off, leaf_cap, d_text, text_cap, totals)))
+        err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::ProcessJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
+                                    Error& err) {
+    int rc = json_current(nullptr, err);
+    if (rc) return rc;
+    if ((rc = compile_current(err))) return rc;
+    gft_engine* e = findthem_->device_engine();
+    if (!findthem_->device_resident_ok()) { err = "device-resident JSON batches need the GPU substring engine and no regex terms"; return GFT_E_UNSUPPORTED; }
+    if (gft_n_devices(e) != 1) { err = "JSON batches: single-device handles only"; return GFT_E_UNSUPPORTED; }
+    RulesLock whole_call(e);
+    if ((rc = json_current(e, err))) return rc;
+    const uint64_t* d_rec_off = nullptr; const uint32_t* d_leaf_field = nullptr; const uint64_t* d_leaf_off = nullptr; const uint8_t* d_text = nullptr;
+    uint64_t totals[2] = {0, 0};
+    if ((rc = json_leaves_owned(e, d_blob, d_doc_off, n_docs, d_status, &d_rec_off, &d_leaf_field, &d_leaf_off, &d_text, totals))) {
+        err = gft_last_error(e);
+        return rc;
+    }
+    last_leaves = totals[0];
+    last_bytes = totals[1];
+    return ProcessRecordsDevice(d_text, d_leaf_off, d_leaf_field, d_rec_off, n_docs, totals[0], d_rule_bitmap, err);
+}
+
+int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
+    int rc = json_current(nullptr, err);
+    if (rc) return rc;
+    if ((rc = compile_current(err))) return rc;
+    if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
+    gft_engine* e = findthem_->device_engine();
+    json_last_device = json_last_host = 0;
+    if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) {
+        // regex terms, injected engines, several devices: the walk on host threads, for every document
+        err = ProcessJsons(blob, doc_off, n_docs, rec_->inc, rec_->exc, false, out);
+        json_last_host = n_docs;
+        return err.empty() ? GFT_OK : GFT_E_ENGINE;
+    }
+    out.assign(n_docs, DocResult());
+    if (!n_docs) return GFT_OK;
+    const uint64_t RW = (rec_->set.n_rules + 31) / 32;
+    std::vector<uint8_t> status(n_docs);
+    std::vector<uint32_t> rows((size_t)(n_docs * RW) + 1, 0);
+    {
+        RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
+        const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
+        if ((rc = json_stage(e, blob, doc_off, n_docs, RW * 4, &d_blob, &d_doc_off, &d_status, &d_rows))) { err = gft_last_error(e); return rc; }
+        if ((rc = ProcessJsonsDevice(d_blob, d_doc_off, n_docs, d_status, d_rows, err))) return rc;
+        if ((rc = rules_fetch(e, status.data(), d_status, n_docs)) || (rc = rules_fetch(e, rows.data(), d_rows, n_docs * RW * 4))) {
+            err = gft_last_error(e);
+            return rc;
+        }
+    }
+    // what the device did not decide: one sub-batch through the host route
+    std::vector<uint64_t> host_docs;
+    for (uint64_t d = 0; d < n_docs; d++)
+        if (status[d]) host_docs.push_back(d);
+    if (!host_docs.empty()) {
+        std::vector<uint64_t> off(host_docs.size() + 1, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) off[k + 1] = off[k] + (doc_off[host_docs[k] + 1] - doc_off[host_docs[k]]);
+        std::vector<uint8_t> sub(off.back() + 64, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) memcpy(sub.data() + off[k], blob + doc_off[host_docs[k]], (size_t)(off[k + 1] - off[k]));
+        std::vector<DocResult> res;
+        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), rec_->inc, rec_->exc, false, res);
+        if (!err.empty()) return GFT_E_ENGINE;
+        for (size_t k = 0; k < host_docs.size(); k++) out[host_docs[k]] = std::move(res[k]);
+    }
+    const auto& names = RuleExprs();
+    parallel_for(n_docs, [&](uint64_t d, unsigned) {
+        if (status[d]) return;
+        const uint32_t* row = rows.data() + d * RW;
+        for (uint32_t w = 0; w < RW; w++)
+            for (uint32_t bits = row[w]; bits; bits &= bits - 1) {
+                const RuleExpr& re = names[w * 32 + (uint32_t)__builtin_ctz(bits)];
+                out[d].rules[*re.name].push_back(*re.expr);
+            }
+    });
+    json_last_host = host_docs.size();
+    json_last_device = n_docs - host_docs.size();
+    return GFT_OK;
+}
+
+int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {
+    if (field) *field = -1;
+    if (!rec_ || rec_->json_rc || parent < 0 || parent >= (int64_t)rec_->json.nodes.size() || (key_len && !key)) return -1;
+    const uint32_t c = key_len ? json_schema_find(rec_->json, (uint32_t)parent, key, key_len) : (uint32_t)parent;
+    if (c == kJsonNone) return -1;
+    if (field && rec_->json.nodes[c].field != kJsonNone) *field = rec_->json.nodes[c].field;
+    return c;
+}
+
+int GroupFinder::DebugJsonLeaves(bool emulate, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
+                                 uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals,
+                                 Error& err) {
+    int rc = json_current(nullptr, err);
+    if (rc) return rc;
+    const JsonLeavesOut out{status, rec_off, leaf_field, leaf_off, leaf_cap, text, text_cap, totals};
+    return emulate ? json_leaves_emulate(rec_->json, blob, doc_off, n_docs, out, err) : json_leaves_ref(rec_->schema, blob, doc_off, n_docs, out, err);
+}
+
 }  // namespace gft
 
 // ---- C ABI (include/gft.h) --------------------------------------------------------------------------------------
@@ -801,6 +929,26 @@ bool string_list(const uint8_t* p, uint64_t n, std::vector<std::string>& out, st
     return true;
 }
 
+// the result document of a JSON batch into g->result (what: 0 rules, 1 tags)
+void result_document(gft_group* g, const std::vector<GroupFinder::DocResult>& res, int what) {
+    std::vector<std::string> parts(res.size());
+    parallel_for(res.size(), [&](uint64_t d, unsigned) {
+        std::string& o = parts[d];
+        if (!res[d].err.empty()) { o = "{\"error\":"; dsl::json_str(res[d].err, o); o += "}"; return; }
+        o = what == 0 ? "{\"rules\":" : "{\"tags\":";
+        if (what == 0) rules_json(res[d].rules, o); else tagmap_json(res[d].tags, o);
+        o += "}";
+    });
+    size_t total = 2;
+    for (const auto& p : parts) total += p.size() + 1;
+    std::string& o = g->result;
+    o.clear();
+    o.reserve(total);
+    o = "[";
+    for (size_t d = 0; d < parts.size(); d++) { if (d) o += ","; o += parts[d]; }
+    o += "]";
+}
+
 bool tagmap_from_json(const json::Value& v, gdsl::TagMap& m, std::string& err) {
     if (v.kind != json::Value::Object) { err = "expected {tag: {field: [expressions]}}"; return false; }
     for (const auto& t : v.obj) {
@@ -874,24 +1022,66 @@ int gft_group_process_jsons(gft_group* g, const uint8_t* json_blob, const uint64
     std::vector<GroupFinder::DocResult> res;
     g->err = g->g->ProcessJsons(json_blob, doc_off, n_docs, inc, exc, what != 0, res);
     if (!g->err.empty()) return GFT_E_ENGINE;
-    std::vector<std::string> parts(res.size());
-    parallel_for(res.size(), [&](uint64_t d, unsigned) {
-        std::string& o = parts[d];
-        if (!res[d].err.empty()) { o = "{\"error\":"; dsl::json_str(res[d].err, o); o += "}"; return; }
-        o = what == 0 ? "{\"rules\":" : "{\"tags\":";
-        if (what == 0) rules_json(res[d].rules, o); else tagmap_json(res[d].tags, o);
-        o += "}";
-    });
-    size_t total = 2;
-    for (const auto& p : parts) total += p.size() + 1;
-    std::string& o = g->result;
-    o.clear();
-    o.reserve(total);
-    o = "[";
-    for (size_t d = 0; d < parts.size(); d++) { if (d) o += ","; o += parts[d]; }
-    o += "]";
-    return put(o, out, cap, needed);
+    result_document(g, res, what);
+    return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &const_cast<gft_group*>(g)->err : nullptr))
+
+int gft_group_process_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
+                                   uint64_t* needed) try {
+    if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<GroupFinder::DocResult> res;
+    int rc = g->g->ProcessJsonsSchema(json_blob, doc_off, n_docs, res, g->err);
+    if (rc) return rc;
+    result_document(g, res, 0);
+    return put(g->result, out, cap, needed);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_json_last(const gft_group* g, uint64_t* n_device, uint64_t* n_host) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    if (n_device) *n_device = g->g->json_last_device;
+    if (n_host) *n_host = g->g->json_last_host;
+    return GFT_OK;
+} GFT_CATCH((g ? &const_cast<gft_group*>(g)->err : nullptr))
+
+int gft_group_json_leaves_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                                 uint64_t* d_rec_off, uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text,
+                                 uint64_t text_cap, uint64_t* totals) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->JsonLeavesDevice(d_json_blob, d_doc_off, n_docs, d_status, d_rec_off, d_leaf_field, d_leaf_off, leaf_cap, d_text, text_cap, totals,
+                                  g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_process_jsons_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                                   uint32_t* d_rule_bitmap) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->ProcessJsonsDevice(d_json_blob, d_doc_off, n_docs, d_status, d_rule_bitmap, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_json_leaves_ref(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
+                              uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugJsonLeaves(false, json_blob, doc_off, n_docs, status, rec_off, leaf_field, leaf_off, leaf_cap, text, text_cap, totals, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_emulate_json_leaves(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status,
+                                  uint64_t* rec_off, uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap,
+                                  uint64_t* totals) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugJsonLeaves(true, json_blob, doc_off, n_docs, status, rec_off, leaf_field, leaf_off, leaf_cap, text, text_cap, totals, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int64_t gft_debug_json_schema_find(gft_group* g, int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) try {
+    if (!g) return -2;
+    GFT_GLOCK(g);
+    return g->g->DebugJsonFind(parent, key, key_len, field);
+} GFT_CATCH_VALUE(-2)
+
 
 int gft_group_last_result(const gft_group* g, char* out, uint64_t cap, uint64_t* needed) try {
     if (!g) return GFT_E_INVALID;

@@ -131,6 +131,28 @@ public:
     // host pointers: upload + ProcessRecordsDevice when the finder qualifies, else Finder::ProcessTexts and the bitmap uploaded
     int ProcessRecords(const uint8_t* text, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
                        uint64_t n_leaves, uint32_t* rule_bitmap, Error& err);
+    // ---- JSON decoded on the device (json_schema.hpp, gft_json.hip) against the schema's trie.  GFT_E_UNSUPPORTED names the
+    // trie's limit when the schema is beyond it (SetSchema itself accepts such a schema).
+    // device pointers: the record arrays of a batch of raw JSON documents (gft_group_json_leaves_device)
+    int JsonLeavesDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint64_t* d_rec_off,
+                         uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text, uint64_t text_cap, uint64_t* totals,
+                         Error& err);
+    // ... into engine-owned arrays, then ProcessRecordsDevice: rows of documents with status != 0 are those of an empty record
+    int ProcessJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
+                           Error& err);
+    // host pointers: upload, ProcessJsonsDevice, status and rows down; documents the device did not decide go through
+    // ProcessJsons as one sub-batch.  The include / exclude lists are the schema's.  A finder that does not qualify for the
+    // device record route takes ProcessJsons for the whole batch.  out: as ProcessJsons with want_tags = false.
+    int ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err);
+    // no device: the reference classification and the kernels' walker on the host (json_schema.hpp), against the stored schema
+    int DebugJsonLeaves(bool emulate, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
+                        uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals, Error& err);
+    // the trie's lookup (tests): the child of node `parent` under a component, or `parent` itself for key_len == 0; -1: none.
+    // *field: the node's field index, or -1
+    int64_t DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field);
+    // documents of the last ProcessJsonsSchema batch decided on the device / handed to ProcessJsons
+    uint64_t json_last_device = 0, json_last_host = 0;
+
     // the compiled device words interpreted on the host over a caller-supplied leaf bitmap: no device
     int DebugEvalRules(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
                        uint64_t n_leaves, uint32_t* rule_bitmap, Error& err);
@@ -158,6 +180,7 @@ private:
     uint64_t rule_exprs_version_ = ~0ull;
     int compile_current(Error& err);       // the set for the stored schema, redone when rules / finder expressions changed
     int install_current(gft_engine* e, Error& err);
+    int json_current(gft_engine* e, Error& err);   // the schema's trie, refused or installed on e (e == nullptr: checked only)
 };
 
 // isValidateFieldPath (internal.go:99-119)

@@ -15,6 +15,7 @@ struct Reader {
     const char* p;
     size_t n, i = 0;
     std::string err;
+    uint8_t str_flags = 0;                              // Value::kRaw* of the string read last
 
     static std::string show(unsigned char c) {          // quoteChar of encoding/json
         if (c == '\'') return "'\\''";
@@ -51,12 +52,14 @@ struct Reader {
     bool string(std::string& out) {                    // p[i] == '"'
         i++;
         std::string raw;
+        str_flags = 0;
         for (;;) {
             if (i >= n) return eof();
             const unsigned char c = (unsigned char)p[i];
             if (c == '"') { i++; break; }
             if (c < 0x20) return fail_char("in string literal");
             if (c != '\\') { raw.push_back((char)c); i++; continue; }
+            str_flags |= Value::kRawEscape;
             i++;
             if (i >= n) return eof();
             const char e = p[i];
@@ -73,6 +76,7 @@ struct Reader {
                 i++;
                 int32_t cp;
                 if (!u4(cp)) return false;
+                if (cp >= 0xD800 && cp <= 0xDFFF) str_flags |= Value::kRawSurrogate;
                 if (cp >= 0xD800 && cp <= 0xDBFF) {    // high surrogate: needs \uDC00..\uDFFF right behind it
                     int32_t lo = -1;
                     if (i + 1 < n && p[i] == '\\' && p[i + 1] == 'u') {
@@ -100,7 +104,9 @@ struct Reader {
         if (ascii) { out = raw; return true; }
         for (size_t k = 0; k < raw.size();) {
             size_t adv;
-            dsl::EncodeRune(dsl::DecodeRune(raw, k, &adv), out);
+            const int32_t cp = dsl::DecodeRune(raw, k, &adv);
+            if (cp == 0xFFFD && adv == 1) str_flags |= Value::kRawInvalidUtf8;   // (escapes only give whole runes: a raw byte)
+            dsl::EncodeRune(cp, out);
             k += adv;
         }
         return true;
@@ -142,7 +148,7 @@ struct Reader {
     // caller's thread may have a small stack); depth is capped like encoding/json caps it
     bool scalar(Value& v) {
         const char c = p[i];
-        if (c == '"') { v.kind = Value::String; return string(v.str); }
+        if (c == '"') { v.kind = Value::String; const bool ok = string(v.str); v.str_flags = str_flags; return ok; }
         if (c == 't') { v.kind = Value::Bool; v.b = true; return literal("true", "in literal true (expecting 'r')"); }
         if (c == 'f') { v.kind = Value::Bool; v.b = false; return literal("false", "in literal false (expecting 'a')"); }
         if (c == 'n') { v.kind = Value::Null; return literal("null", "in literal null (expecting 'u')"); }
@@ -195,8 +201,10 @@ struct Reader {
                     if (i >= n) return eof();
                     if (p[i] != ':') return fail_char("after object key");
                     i++;
+                    const uint8_t kf = str_flags;
                     top->obj.emplace_back(std::move(key), Value());
                     v = &top->obj.back().second;
+                    v->key_flags = kf;
                 } else {
                     top->arr.emplace_back();
                     v = &top->arr.back();

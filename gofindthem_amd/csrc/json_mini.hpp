@@ -15,6 +15,10 @@ struct Value {
     enum Kind { Null, Bool, Number, String, Array, Object } kind = Null;
     bool b = false;
     std::string str;                                   // String: decoded text; Number: its literal
+    // what the raw text of a String (str_flags) and of the key this member sits under (key_flags) held: the device JSON
+    // walker hands such strings back (gft_json_walk.hpp), and its reference classifier reads these (json_schema.cpp)
+    enum : uint8_t { kRawEscape = 1, kRawSurrogate = 2, kRawInvalidUtf8 = 4 };
+    uint8_t str_flags = 0, key_flags = 0;
     std::vector<Value> arr;
     std::vector<std::pair<std::string, Value>> obj;    // in document order; duplicate keys are kept (last one wins
                                                        // for a Go map: see last_wins())

@@ -291,6 +291,113 @@ class GroupFinder:
             raise self._err(rc)
         return out
 
+    # -- JSON decoded on the device against the schema (csrc/gft_json.hip) -----------------------------------------------
+    def _json_leaves_host(self, fn, docs, leaf_cap=None, text_cap=None):
+        """gft_debug_json_leaves_ref / gft_debug_emulate_json_leaves over a list of byte strings -> (status, rec_off, leaf_field,
+        leaf_off, text, (leaves, text bytes)); caps given: arrays of exactly that size behind which nothing may be stored"""
+        docs = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs]
+        blob, off = pack(docs)
+        blob = np.concatenate([blob, np.zeros(64, dtype=np.uint8)])
+        n = len(docs)
+        status, rec_off, totals = np.zeros(n, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64), np.zeros(2, dtype=np.uint64)
+        if leaf_cap is None:
+            rc = fn(self._h, blob.ctypes.data, off.ctypes.data, n, status.ctypes.data, rec_off.ctypes.data, None, None, 0, None, 0, totals.ctypes.data)
+            if rc != 0:
+                raise self._err(rc)
+            leaf_cap, text_cap = int(totals[0]), int(totals[1])
+        guard = 8
+        leaf_field = np.full(leaf_cap + guard, 0xA5A5A5A5, dtype=np.uint32)
+        leaf_off = np.full(leaf_cap + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        text = np.full(text_cap + guard, 0xA5, dtype=np.uint8)
+        rc = fn(self._h, blob.ctypes.data, off.ctypes.data, n, status.ctypes.data, rec_off.ctypes.data, leaf_field.ctypes.data,
+                leaf_off.ctypes.data, leaf_cap, text.ctypes.data, text_cap, totals.ctypes.data)
+        if rc != 0:
+            raise self._err(rc)
+        return status, rec_off, leaf_field, leaf_off, text, (int(totals[0]), int(totals[1]))
+
+    def debug_json_leaves_ref(self, docs, leaf_cap=None, text_cap=None):
+        return self._json_leaves_host(self._L.gft_debug_json_leaves_ref, docs, leaf_cap, text_cap)
+
+    def debug_emulate_json_leaves(self, docs, leaf_cap=None, text_cap=None):
+        return self._json_leaves_host(self._L.gft_debug_emulate_json_leaves, docs, leaf_cap, text_cap)
+
+    def debug_json_schema_find(self, parent, key):
+        """(child node or -1, its field index or -1) of trie node `parent` under the component `key` (b"": the node itself)"""
+        field = C.c_int64(-1)
+        node = self._L.gft_debug_json_schema_find(self._h, parent, key, len(key), C.byref(field))
+        return int(node), int(field.value)
+
+    def JsonLeavesDevice(self, blob, doc_off, leaf_cap=None, text_cap=None):
+        """torch device tensors (uint8 JSON text with 64 bytes of slack, doc_off as 64-bit integers) -> the record form as device
+        tensors (status uint8[n], rec_off int64[n + 1], leaf_field int32[L], leaf_off int64[L + 1], text uint8[T + 64]) and
+        (L, T).  Without caps the batch is counted first and the arrays are sized by the totals."""
+        import torch
+        n = int(doc_off.numel()) - 1
+        for t, size in ((blob, 1), (doc_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "JsonLeavesDevice takes contiguous device tensors of 1 and 8 byte integers")
+        dev = blob.device
+        status = torch.zeros(max(n, 0), dtype=torch.uint8, device=dev)
+        rec_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=dev)
+        totals = np.zeros(2, dtype=np.uint64)
+        torch.cuda.current_stream(dev).synchronize()
+        if leaf_cap is None:
+            rc = self._L.gft_group_json_leaves_device(self._h, blob.data_ptr(), doc_off.data_ptr(), n, status.data_ptr(), rec_off.data_ptr(),
+                                                      None, None, 0, None, 0, totals.ctypes.data)
+            if rc != 0:
+                raise self._err(rc)
+            leaf_cap, text_cap = int(totals[0]), int(totals[1])
+        guard = 8                                              # (behind the caps: nothing may be stored there)
+        leaf_field = torch.full((leaf_cap + guard,), -1, dtype=torch.int32, device=dev)
+        leaf_off = torch.full((leaf_cap + 1 + guard,), -1, dtype=torch.int64, device=dev)
+        text = torch.zeros(text_cap + 64, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self._L.gft_group_json_leaves_device(self._h, blob.data_ptr(), doc_off.data_ptr(), n, status.data_ptr(), rec_off.data_ptr(),
+                                                  leaf_field.data_ptr(), leaf_off.data_ptr(), leaf_cap, text.data_ptr(), text_cap,
+                                                  totals.ctypes.data)
+        if rc != 0:
+            raise self._err(rc)
+        return status, rec_off, leaf_field, leaf_off, text, (int(totals[0]), int(totals[1]))
+
+    def ProcessJsonsDevice(self, blob, doc_off):
+        """torch device tensors as for JsonLeavesDevice -> (rule bitmap int32[n, ceil(R / 32)], status uint8[n]) on the device; the
+        row of a document whose status is not 0 is that of an empty record"""
+        import torch
+        n = int(doc_off.numel()) - 1
+        for t, size in ((blob, 1), (doc_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "ProcessJsonsDevice takes contiguous device tensors of 1 and 8 byte integers")
+        out = torch.zeros((max(n, 0), self.rule_words()), dtype=torch.int32, device=blob.device)
+        status = torch.zeros(max(n, 0), dtype=torch.uint8, device=blob.device)
+        torch.cuda.current_stream(blob.device).synchronize()
+        rc = self._L.gft_group_process_jsons_device(self._h, blob.data_ptr(), doc_off.data_ptr(), n, status.data_ptr(), out.data_ptr())
+        if rc != 0:
+            raise self._err(rc)
+        return out, status
+
+    def ProcessJsonsSchema(self, rawJsons):
+        """ProcessJsons(rawJsons, include, exclude of SetSchema) with the documents decoded on the device where it decides them"""
+        raws = [r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in rawJsons]
+        blob, off = pack(raws)
+        need = C.c_uint64(0)
+        cap = max(1 << 16, 2 * int(blob.size))
+        buf = C.create_string_buffer(cap)
+        rc = self._L.gft_group_process_jsons_schema(self._h, blob.ctypes.data, off.ctypes.data, len(raws), C.cast(buf, C.c_void_p), cap,
+                                                    C.byref(need))
+        if rc == _lib.GFT_E_INVALID and need.value > cap:      # the library kept the document: fetch it, no second run
+            cap = int(need.value)
+            buf = C.create_string_buffer(cap)
+            rc = self._L.gft_group_last_result(self._h, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc != 0:
+            raise self._err(rc)
+        return json.loads(buf.value.decode("utf-8", "replace"))
+
+    def json_last(self):
+        """(documents decided on the device, documents handed to the host route) of the last ProcessJsonsSchema batch"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._L.gft_group_json_last(self._h, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
     def last_batch(self):
         """(string leaves, text bytes) the last call sent through the finder"""
         a, b = C.c_uint64(), C.c_uint64()

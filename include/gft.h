@@ -434,6 +434,69 @@ int gft_debug_eval_rules(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_ex
  * row's last word are ignored.  One device; validation as for the call above. */
 int gft_debug_eval_rules_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap);
+/* ---- JSON decoded on the device (gft_json.hip): raw documents in HBM -> the record form above ----------------------------
+ * The schema of gft_group_set_schema is compiled into a trie of path components (split at '.', the root is the path "");
+ * a wave walks a document in 64-byte pieces and resolves every object key and array element ("index(<i>)") in that trie,
+ * exactly: a hash hit is confirmed by comparing the bytes; a key that contains '.' resolves to nothing.  The walker is exact
+ * for every document it decides, and says which ones it did not decide -- one status byte per document: */
+enum gft_json_status {
+    GFT_JSON_OK = 0,     /* decided on the device: its leaves are those of the host route, byte for byte, in document order */
+    GFT_JSON_SYNTAX = 1, /* the walker did not accept the text (the host route has the error text) */
+    GFT_JSON_DEPTH = 2,  /* more than 32 containers open at once */
+    GFT_JSON_PATH = 3,   /* a string value at a path that is not a schema path */
+    GFT_JSON_KEY = 4,    /* an object key that is empty, contains a backslash or is not valid UTF-8 */
+    GFT_JSON_DUP = 5,    /* a node of the trie was reached twice: a duplicate key at or above a schema path */
+    GFT_JSON_TEXT = 6    /* a string value at a schema path with a \uD800..\uDFFF escape or a byte that is not valid UTF-8 */
+};
+/* A document with a status other than 0 contributes no leaves: its record is empty.  When several conditions hold the lowest
+ * status is reported.  Status 0 is guaranteed for a document that is valid JSON (every number form, literal, escape; no
+ * control byte in a string; nothing behind the top-level value), has at most 32 containers open at any point, whose keys are
+ * non-empty valid UTF-8 without backslashes and do not repeat inside one object, whose string values all lie at schema paths
+ * and consist of valid UTF-8, the escapes \" \\ \/ \b \f \n \r \t and \uXXXX outside D800..DFFF (\u0000 becomes a NUL byte
+ * of the leaf).  Numbers, literals, and containers under keys the schema does not know carry no leaf: they are checked and
+ * skipped.  A document that is not valid JSON never gets status 0.
+ * Limits, answered by the calls of this section only (gft_group_set_schema accepts such schemas): GFT_E_UNSUPPORTED for a
+ * schema with more than 16384 trie nodes (distinct path prefixes), or a path component longer than 65535 bytes.
+ *
+ * Every pointer is a device pointer except totals.  Three launches on the engine's stream (gft_profile_read: "json_count",
+ * "json_scan", "json_write"); the contract mirrors gft_to_lower_device: d_status [n_docs] and d_rec_off [n_docs + 1] are always
+ * complete; leaf l is written to d_leaf_field [leaf_cap] and d_leaf_off [leaf_cap + 1] when l < leaf_cap, a text byte when its
+ * position is < text_cap, and nothing is stored past the caps (d_leaf_off[n_leaves] = the text's size is written when
+ * n_leaves <= leaf_cap); GFT_OK is returned in both cases and totals[2] (host, nullable) receives the number of leaves and of
+ * text bytes -- the caller compares and calls again.  NULL arrays with zero caps count only.  The decoded text is never
+ * longer than the raw documents; the caller leaves 64 readable bytes behind it before handing it to a scan.  d_json_blob must
+ * be readable for 64 bytes past d_doc_off[n_docs].  GFT_E_INVALID: no schema, offsets that descend, a document of 4 GiB or
+ * more, output that overlaps the input.  Handles over several devices: GFT_E_UNSUPPORTED.  n_docs == 0 is valid. */
+int gft_group_json_leaves_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                                 uint64_t* d_rec_off, uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text,
+                                 uint64_t text_cap, uint64_t* totals);
+/* The call above into buffers the engine owns (grown until the batch fits), then gft_group_process_records_device over them
+ * (its limits apply): only the status and the totals cross the link.  d_rule_bitmap [n_docs][ceil(R / 32)]: the row of a
+ * document whose status is not 0 is that of an empty record -- the caller consults d_status [n_docs]. */
+int gft_group_process_jsons_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                                   uint32_t* d_rule_bitmap);
+/* Host pointers; the same result document as gft_group_process_jsons(..., what = 0) with the include / exclude lists given to
+ * gft_group_set_schema: upload, the call above, status and rows down; a document of status 0 gets {"rules": ..} from its row,
+ * all others go through gft_group_process_jsons' route as one sub-batch and take its "rules" or "error".  A finder that does
+ * not qualify for the device record route (regex terms, injected engines, several devices) takes that route for the whole
+ * batch.  gft_group_last_result serves this call too. */
+int gft_group_process_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
+                                   uint64_t* needed);
+/* documents of the last gft_group_process_jsons_schema batch decided on the device / handed to the host route */
+int gft_group_json_last(const gft_group* g, uint64_t* n_device, uint64_t* n_host);
+/* No device needed (tests), host pointers, the array contract of gft_group_json_leaves_device: the reference -- the host
+ * route's JSON reader and a walk of the decoded value against the schema, classified into the statuses above by code that
+ * shares nothing with the walker -- ... */
+int gft_debug_json_leaves_ref(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
+                              uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals);
+/* ... and the kernels' walker on the host, 64-byte piece by piece through the source the kernels are compiled from
+ * (csrc/gft_json_walk.hpp): count, prefix sums, write */
+int gft_debug_emulate_json_leaves(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status,
+                                  uint64_t* rec_off, uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap,
+                                  uint64_t* totals);
+/* the trie's lookup: the child of node `parent` (0: the root) under one path component, or `parent` itself for key_len == 0;
+ * -1: none.  *field (nullable): the node's field index, or -1 */
+int64_t gft_debug_json_schema_find(gft_group* g, int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field);
 /* group DSL alone (host only): {"tree":..,"tags":[..],"fields":[..]} or {"error":..}; token list as gft_dsl_tokens */
 int gft_group_dsl_parse(const uint8_t* expr, uint64_t len, char* out, uint64_t cap, uint64_t* needed);
 int gft_group_dsl_tokens(const uint8_t* expr, uint64_t len, char* out, uint64_t cap, uint64_t* needed);
