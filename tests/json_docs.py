@@ -235,8 +235,8 @@ def gen_value(schema, rng, words=None, density=0.6):
 _KIND = "\0kind"                                   # True: the container's children are array elements
 
 
-def gen_doc(schema, rng, words=None):
-    return dumps(gen_value(schema, rng, words), rng).encode("utf-8")
+def gen_doc(schema, rng, words=None, density=0.6):
+    return dumps(gen_value(schema, rng, words, density), rng).encode("utf-8")
 
 
 def mutate(raw, rng):
@@ -287,6 +287,33 @@ def leaves_of(status, rec_off, leaf_field, leaf_off, text):
         a, b = int(rec_off[d]), int(rec_off[d + 1])
         out.append((int(status[d]), [(int(leaf_field[l]), bytes(text[int(leaf_off[l]):int(leaf_off[l + 1])])) for l in range(a, b)]))
     return out
+
+
+def to_device(docs):
+    """documents -> (blob with 64 bytes of slack, doc_off) as device tensors"""
+    import torch
+    from gofindthem_amd.engine import pack
+    blob, off = pack([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
+    blob = np.concatenate([blob, np.zeros(64, dtype=np.uint8)])
+    return torch.from_numpy(blob).cuda(), torch.from_numpy(off.astype(np.int64)).cuda()
+
+
+def check_leaves(g, docs, caps=None):
+    """JsonLeavesDevice == gft_debug_json_leaves_ref in every array; nothing stored behind the caps"""
+    ref = g.debug_json_leaves_ref(docs, *(caps or ()))
+    got = g.JsonLeavesDevice(*to_device(docs), *(caps or ()))
+    n_leaves, n_text = ref[5]
+    assert got[5] == ref[5]
+    status, rec_off, leaf_field, leaf_off, text = (t.cpu().numpy() for t in got[:5])
+    assert np.array_equal(status, ref[0]) and np.array_equal(rec_off.astype(np.uint64), ref[1])
+    leaf_cap, text_cap = caps or ref[5]
+    k, t = min(leaf_cap, n_leaves), min(text_cap, n_text)
+    assert np.array_equal(leaf_field[:k].astype(np.uint32), ref[2][:k]) and np.all(leaf_field[leaf_cap:] == -1)
+    end = k + 1 if n_leaves <= leaf_cap else k
+    assert np.array_equal(leaf_off[:end].astype(np.uint64), ref[3][:end]) and np.all(leaf_off[max(leaf_cap + 1, end):] == -1)
+    assert n_leaves <= leaf_cap or leaf_off[leaf_cap] == -1
+    assert np.array_equal(text[:t], ref[4][:t]) and not text[text_cap:].any()
+    return ref
 
 
 def write_table(path):

@@ -10,8 +10,8 @@ import torch  # noqa: F401  (before libgft.so is loaded: one HIP runtime)
 
 import json_docs as J
 import records as R
+from json_docs import check_leaves, to_device
 from gofindthem_amd import _lib, group
-from gofindthem_amd.engine import pack
 from gofindthem_amd.finder import EmptyRgxEngine, Finder, GpuEngine, PyRegexpEngine
 
 pytestmark = pytest.mark.gpu
@@ -37,30 +37,6 @@ def plain_group(schema):
     if key not in _PLAIN:
         _PLAIN[key] = make_group(['"x"'], ["t"], {}, schema)
     return _PLAIN[key]
-
-
-def to_device(docs):
-    blob, off = pack([d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs])
-    blob = np.concatenate([blob, np.zeros(64, dtype=np.uint8)])
-    return torch.from_numpy(blob).cuda(), torch.from_numpy(off.astype(np.int64)).cuda()
-
-
-def check_leaves(g, docs, caps=None):
-    """JsonLeavesDevice == gft_debug_json_leaves_ref in every array; nothing stored behind the caps"""
-    ref = g.debug_json_leaves_ref(docs, *(caps or ()))
-    got = g.JsonLeavesDevice(*to_device(docs), *(caps or ()))
-    n_leaves, n_text = ref[5]
-    assert got[5] == ref[5]
-    status, rec_off, leaf_field, leaf_off, text = (t.cpu().numpy() for t in got[:5])
-    assert np.array_equal(status, ref[0]) and np.array_equal(rec_off.astype(np.uint64), ref[1])
-    leaf_cap, text_cap = caps or ref[5]
-    k, t = min(leaf_cap, n_leaves), min(text_cap, n_text)
-    assert np.array_equal(leaf_field[:k].astype(np.uint32), ref[2][:k]) and np.all(leaf_field[leaf_cap:] == -1)
-    end = k + 1 if n_leaves <= leaf_cap else k
-    assert np.array_equal(leaf_off[:end].astype(np.uint64), ref[3][:end]) and np.all(leaf_off[max(leaf_cap + 1, end):] == -1)
-    assert n_leaves <= leaf_cap or leaf_off[leaf_cap] == -1
-    assert np.array_equal(text[:t], ref[4][:t]) and not text[text_cap:].any()
-    return ref
 
 
 TABLE = J.table()
