@@ -119,6 +119,11 @@ SYMBOLS = {
     "gft_group_process_jsons_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "gft_group_process_jsons_schema": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_json_last": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_group_json_paths_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_group_process_jsons_auto": (_i, [_vp, _vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "gft_group_json_auto_last": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_emulate_json_paths": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64), C.POINTER(_u64), _vp, _u64, C.POINTER(_u64)]),
+    "gft_debug_json_paths_ref": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
     "gft_debug_json_leaves_ref": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "gft_debug_emulate_json_leaves": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "gft_debug_json_schema_find": (C.c_int64, [_vp, C.c_int64, C.c_char_p, _u32, C.POINTER(C.c_int64)]),

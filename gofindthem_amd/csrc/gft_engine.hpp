@@ -192,6 +192,7 @@ struct gft_engine {
         uint64_t serial = 0;               // 0: no trie installed
         uint32_t n_nodes = 0, table_mask = 0, max_key_len = 0;
         DevBuf nodes, keys, table, cnt_leaves, cnt_text, text_off, partial, flags, rec_off, leaf_field, leaf_off, text, blob, doc_off, status, rows;
+        DevBuf paths;                      // discovery (k_json_paths): counters, hash set, path offsets, pool; allocated once
     } d_json;
 
     // profiling

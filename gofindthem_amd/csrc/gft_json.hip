@@ -7,6 +7,9 @@
 //   k_json<true>    the same walk again over the documents of status 0: every leaf's field and offset, its bytes copied with a
 //                   per-lane prefix count as the output position
 //
+//   k_json_paths    discovery, no trie: the distinct paths of the batch's string values into a set of path hashes and a pool
+//                   (gft_group_json_paths_device; the host compiles them into the schema of gft_group_process_jsons_auto)
+//
 // A wave owns a document at a time and reads it in pieces of 64 bytes, a byte per lane; workgroups of four waves stride over
 // the batch.  What a piece means is decided by gft_json_walk.hpp, which the host compiles too: here its lane operations are
 // ballots, a shuffle reduction and v_readlane, its per-wave memory (visited bitset, container stack) is LDS.  The walk is
@@ -76,6 +79,52 @@ __global__ void __launch_bounds__(kJsonBlock) k_json(const JsonParams P) {
     }
 }
 
+// the wave of k_json_paths: what discovery needs on top (gft_json_walk.hpp).  One lane issues an atomic, every lane gets
+// its answer; the set's slot is read by a load of device scope, which sees what another wave's compare-and-swap put there.
+struct DevPathWave : DevWave {
+    __device__ uint64_t uni64(uint64_t x) const { return (uint64_t)uni((uint32_t)(x >> 32)) << 32 | uni((uint32_t)x); }
+    template <class F> __device__ uint64_t sum64(F&& f) {
+        const uint64_t v = f(lane);
+        uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
+        for (int o = 32; o; o >>= 1) {                                       // (64-bit adds: the carry goes with the halves)
+            const uint64_t other = (uint64_t)(uint32_t)__shfl_xor((int)hi, o, 64) << 32 | (uint32_t)__shfl_xor((int)lo, o, 64);
+            const uint64_t s = ((uint64_t)hi << 32 | lo) + other;
+            lo = (uint32_t)s; hi = (uint32_t)(s >> 32);
+        }
+        return uni64((uint64_t)hi << 32 | lo);
+    }
+    __device__ uint64_t load64(const uint64_t* p) const { return uni64(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
+    __device__ uint64_t cas64(uint64_t* p, uint64_t v) const {
+        unsigned long long old = 0;
+        if (lane == 0) old = atomicCAS(reinterpret_cast<unsigned long long*>(p), 0ull, (unsigned long long)v);
+        return uni64(old);
+    }
+    __device__ uint32_t add32(uint32_t* p, uint32_t v) const {
+        uint32_t old = 0;
+        if (lane == 0) old = atomicAdd(p, v);
+        return uni(old);
+    }
+};
+
+__global__ void __launch_bounds__(kJsonBlock) k_json_paths(const JsonPathParams P) {
+    __shared__ JsonWaveMem s_mem[kJsonBlock / 64];
+    __shared__ JsonPathMem s_pm[kJsonBlock / 64];
+    DevPathWave w;
+    w.lane = threadIdx.x & 63u;
+    w.m = &s_mem[threadIdx.x >> 6];
+    JsonPaths dsc{&s_pm[threadIdx.x >> 6], P.set};
+    const uint64_t wave = ((uint64_t)blockIdx.x * kJsonBlock + threadIdx.x) >> 6;
+    const uint64_t n_waves = ((uint64_t)gridDim.x * kJsonBlock) >> 6;
+    for (uint64_t d = wave; d < P.n_docs; d += n_waves) {
+        const uint64_t a = P.doc_off[d], z = P.doc_off[d + 1];
+        if (z < a || z - a > 0xFFFFFFFFull) {
+            if (w.lane == 0) atomicOr(P.flags, 1u);
+            continue;
+        }
+        json_walk_paths(w, dsc, P.blob + a, (uint32_t)(z - a));
+    }
+}
+
 unsigned json_grid(uint64_t n_docs, unsigned n_cus) {
     const uint64_t blocks = (n_docs + kJsonBlock / 64 - 1) / (kJsonBlock / 64);
     return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, (uint64_t)std::max(n_cus, 1u) * 8));   // 32 waves per CU
@@ -92,6 +141,12 @@ hipError_t launch_json_count(const JsonParams& P, unsigned n_cus, hipStream_t st
 hipError_t launch_json_write(const JsonParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
     k_json<true><<<dim3(json_grid(P.n_docs, n_cus)), dim3(kJsonBlock), 0, st>>>(P);
+    return hipGetLastError();
+}
+
+hipError_t launch_json_paths(const JsonPathParams& P, unsigned n_cus, hipStream_t st) {
+    if (!P.n_docs) return hipSuccess;
+    k_json_paths<<<dim3(json_grid(P.n_docs, n_cus)), dim3(kJsonBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 

@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
 #include "../../include/gft.h"
 #include "gft_json_walk.hpp"
 
@@ -27,10 +30,21 @@ struct JsonParams {
     uint64_t leaf_cap, text_cap;
 };
 
+struct JsonPathParams {
+    const uint8_t* blob;
+    const uint64_t* doc_off;     // [n_docs + 1]
+    uint64_t n_docs;
+    JsonPathSet set;             // device pointers; cleared by the caller
+    uint32_t* flags;             // as JsonParams
+};
+
 // status, leaves and decoded bytes per document
 hipError_t launch_json_count(const JsonParams& P, unsigned n_cus, hipStream_t st);
 // the arrays, for the documents of status 0; leaf_off[total leaves] = total text when it lies inside leaf_cap
 hipError_t launch_json_write(const JsonParams& P, unsigned n_cus, hipStream_t st);
+
+// discovery: the paths of the batch's string values into P.set
+hipError_t launch_json_paths(const JsonPathParams& P, unsigned n_cus, hipStream_t st);
 
 // ---- the engine's side (gft_json_api.cpp); single-device handles only, the calls take the engine's lock (RulesLock around
 // several of them, as for the rule kernels)
@@ -44,6 +58,9 @@ int json_leaves_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_d
 int json_leaves_owned(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
                       const uint64_t** d_rec_off, const uint32_t** d_leaf_field, const uint64_t** d_leaf_off, const uint8_t** d_text,
                       uint64_t* totals);
+// gft_group_json_paths_device: the distinct paths of the batch's string values, sorted bytewise; needs no trie.
+int json_paths_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths,
+                      uint64_t* dropped);
 // a batch from host memory into engine-owned buffers (64 zero bytes behind the blob), with room for its status bytes and
 // rule bitmap rows
 int json_stage(gft_engine* e, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint64_t row_bytes, const uint8_t** d_blob,

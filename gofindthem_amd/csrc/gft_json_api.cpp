@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "gft_json.hpp"
+#include "json_paths.hpp"
 #include "json_schema.hpp"
 
 using namespace gft;
@@ -145,6 +146,58 @@ int json_leaves_owned(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_do
     HIP_TRY(hipStreamSynchronize(e->stream), "JSON text slack");
     *d_rec_off = J.rec_off.as<uint64_t>(); *d_leaf_field = J.leaf_field.as<uint32_t>();
     *d_leaf_off = J.leaf_off.as<uint64_t>(); *d_text = J.text.as<uint8_t>();
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
+int json_paths_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths,
+                      uint64_t* dropped) try {
+    if (!e) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    paths.clear();
+    if (dropped) *dropped = 0;
+    if (n_docs && (!d_blob || !d_doc_off)) return fail(e, GFT_E_INVALID, "JSON batch: null argument");
+    if (!n_docs) return GFT_OK;
+    DeviceGuard g(e->device);
+    SyncOnExit drain(e);                   // (the copies below land in vectors of this call)
+    hipStream_t st = e->stream;
+    uint64_t ends[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&ends[0], d_doc_off, 8, hipMemcpyDeviceToHost, st), "JSON offsets");
+    HIP_TRY(hipMemcpyAsync(&ends[1], d_doc_off + n_docs, 8, hipMemcpyDeviceToHost, st), "JSON offsets");
+    HIP_TRY(hipStreamSynchronize(st), "JSON offsets");
+    if (ends[1] < ends[0]) return fail(e, GFT_E_INVALID, "gft_group_json_paths_device: document offsets descend");
+    // counters (count, dropped, cursor, -) | slots | path_off | pool: one allocation of a fixed size
+    constexpr uint64_t kHead = 16, kSlots = (uint64_t)kJsonPathSlots * 8, kOffs = (uint64_t)kJsonPathCap * 4;
+    auto& J = e->d_json;
+    if ((rc = json_room(e, J.paths, kHead + kSlots + kOffs + kJsonPathPool)) || (rc = json_room(e, J.flags, 16))) return rc;
+    uint8_t* base = J.paths.as<uint8_t>();
+    JsonPathParams P{};
+    P.blob = d_blob; P.doc_off = d_doc_off; P.n_docs = n_docs; P.flags = J.flags.as<uint32_t>();
+    uint32_t* head = reinterpret_cast<uint32_t*>(base);
+    P.set = JsonPathSet{reinterpret_cast<uint64_t*>(base + kHead), head, head + 1, head + 2, reinterpret_cast<uint32_t*>(base + kHead + kSlots),
+                        base + kHead + kSlots + kOffs, kJsonPathPool};
+    HIP_TRY(hipMemsetAsync(base, 0, kHead + kSlots, st), "JSON paths");
+    HIP_TRY(hipMemsetAsync(P.set.path_off, 0xFF, kOffs, st), "JSON paths");
+    HIP_TRY(hipMemsetAsync(P.flags, 0, 8, st), "JSON paths");
+    {
+        ProfScope ps(e, "json_paths");
+        HIP_TRY(launch_json_paths(P, e->n_cus, st), "JSON paths kernel launch");
+    }
+    uint32_t h_head[4] = {0, 0, 0, 0}, h_flags[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h_head, head, 16, hipMemcpyDeviceToHost, st), "JSON paths");
+    HIP_TRY(hipMemcpyAsync(h_flags, P.flags, 8, hipMemcpyDeviceToHost, st), "JSON paths");
+    HIP_TRY(hipStreamSynchronize(st), "JSON paths");
+    if (h_flags[0]) return fail(e, GFT_E_INVALID, "gft_group_json_paths_device: document offsets descend, or a document of 4 GiB or more");
+    const uint32_t n = std::min(h_head[0], kJsonPathCap);
+    const uint64_t pool_valid = std::min<uint64_t>(h_head[2], kJsonPathPool);
+    std::vector<uint32_t> offs(n);
+    std::vector<uint8_t> pool(pool_valid);
+    if (n) HIP_TRY(hipMemcpyAsync(offs.data(), P.set.path_off, (size_t)n * 4, hipMemcpyDeviceToHost, st), "JSON paths");
+    if (pool_valid) HIP_TRY(hipMemcpyAsync(pool.data(), P.set.pool, pool_valid, hipMemcpyDeviceToHost, st), "JSON paths");
+    HIP_TRY(hipStreamSynchronize(st), "JSON paths");
+    json_paths_collect(h_head[0], offs.data(), pool.data(), pool_valid, paths);
+    if (dropped) *dropped = h_head[1];
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 

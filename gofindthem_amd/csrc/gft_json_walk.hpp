@@ -17,6 +17,18 @@
 //     uni(x)                    x, which is the same in every lane (the device moves it to a scalar register)
 //     mem()                     JsonWaveMem of the wave (LDS on the device)
 //
+// Three ways to run the walk, chosen at compile time by the policy class D (json_walk_doc):
+//     JsonNoPaths     against the schema trie: count pass and write pass (json_walk_doc)
+//     JsonPaths       discovery: no trie.  The wave remembers where it is -- per tracked container the member key that is open
+//                     (JsonPathMem) -- and hands the path of every string value to a set of 64-bit path hashes
+//                     (json_path_found); the wave that puts a hash in first writes the path's bytes into a pool.
+// A path is spelled as getRulesInfo spells it (internal.go:46-47, 68-69, 82-84): components joined by '.', a key as its raw
+// bytes, an array element as "index(<i>)", the root as "".  No path is produced below a key that raises kJsKey, below
+// container depth 32, or when the path is longer than 65 535 bytes.  A value under a key that contains '.' IS reported, with
+// the key's bytes as one component: the path then reads like that of a nested member, which is harmless -- such a key resolves
+// to nothing in the trie, and the document ends as GFT_JSON_PATH on the host route (the two spellings of one path string hash
+// differently; the host removes the duplicate).
+//
 // Statuses and the class of documents that is decided here: include/gft.h (gft_json_status).  A document is walked to its end
 // also after a condition other than GFT_JSON_SYNTAX was met: every condition sets its bit, the lowest status wins, so that
 // the answer does not depend on the order in which a walker meets them.  Nothing outside [0, len) of the document is read.
@@ -87,6 +99,67 @@ struct JsonKeyIndex {                              // "index(<i>)", the componen
         return '0' + v % 10;
     }
 };
+
+// ---- discovery: the paths of a batch's string values (k_json_paths, json_paths_emulate) ---------------------------------
+constexpr uint32_t kJsonPathSlots = 1u << 16;      // the set of path hashes: open addressing, linear probing, 0: empty
+constexpr uint32_t kJsonPathProbes = 128;          // ... given up behind this many slots (a full table: the path is dropped)
+constexpr uint32_t kJsonPathCap = 16384;           // paths kept: more never compile into a trie (kJsonMaxNodes)
+constexpr uint32_t kJsonPathPool = 8u << 20;       // bytes of the path pool
+constexpr uint32_t kJsonPathMax = 65535;           // bytes of one path
+constexpr uint64_t kJsonPathRoot = 0x243F6A8885A308D3ull;    // the hash of the path ""
+
+// what a wave remembers of the containers it tracks, besides JsonWaveMem's kinds and count: allocated by discovery only
+struct JsonPathMem {
+    uint64_t pre_hash[kJsonMaxDepth];              // the hash of the container's own path ...
+    uint32_t pre_len[kJsonMaxDepth];               // ... and its length in bytes, kJsonNone: it has none
+    uint64_t cur_hash[kJsonMaxDepth];              // an object: the path of the member whose key was closed last
+    uint32_t cur_len[kJsonMaxDepth];
+    uint32_t key_off[kJsonMaxDepth];               // ... and where that key's bytes lie in the document
+    uint32_t key_len[kJsonMaxDepth];
+};
+// the state of a batch: one allocation, cleared per call (the pool needs no clearing)
+struct JsonPathSet {
+    uint64_t* slots;                               // [kJsonPathSlots]
+    uint32_t* count;                               // hashes that were new (may pass kJsonPathCap: the first kJsonPathCap own a number)
+    uint32_t* dropped;                             // paths that were found and not written: cap, pool, probe limit
+    uint32_t* cursor;                              // bytes of the pool handed out
+    uint32_t* path_off;                            // [kJsonPathCap] where path n lies in the pool, kJsonNone: nowhere
+    uint8_t* pool;                                 // per path: u32 length, the bytes, padded to 4
+    uint32_t pool_bytes;
+};
+
+// A component's hash is a sum of per-byte terms, so that the lanes can add their shares in any order and host and device agree.
+// The terms are 64 bits, mixed per (byte, position): json_key_term's sums collide by construction -- "1221" and "2112" give the
+// same sum under its odd multipliers --, which the trie settles by comparing bytes and a set of hashes cannot.
+GFT_JHD inline uint64_t json_path_term(uint32_t b, uint32_t j) {
+    uint64_t x = (uint64_t)(b + 1u) * 0x9E3779B97F4A7C15ull + (uint64_t)(j + 1u) * 0xC2B2AE3D27D4EB4Full;
+    x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 32;
+    return x;
+}
+template <class W, class KB>
+GFT_JHD inline uint64_t json_path_sum(W& w, const KB& kb, uint32_t len) {
+    return w.sum64([&](uint32_t lane) {
+        uint64_t s = 0;
+        for (uint32_t j = lane; j < len; j += 64) s += json_path_term(kb(j), j);
+        return s;
+    });
+}
+// the path of a member under a container
+GFT_JHD inline uint64_t json_path_mix(uint64_t parent, uint64_t h, uint32_t len) {
+    uint64_t x = parent * 0x9E3779B97F4A7C15ull + h + (uint64_t)(len + 1u) * 0xC2B2AE3D27D4EB4Full;
+    x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 29; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 32;
+    return x;
+}
+// (pre_hash, pre_len) + component -> (hash, len); len == kJsonNone: no path
+template <class W, class KB>
+GFT_JHD inline void json_path_child(W& w, uint64_t pre_hash, uint32_t pre_len, const KB& kb, uint32_t len, uint64_t& hash, uint32_t& plen) {
+    plen = kJsonNone; hash = 0;
+    if (pre_len == kJsonNone || len > kJsonPathMax) return;
+    const uint32_t total = pre_len ? pre_len + 1 + len : len;          // (only the root's path is empty: components are not)
+    if (total > kJsonPathMax) return;
+    plen = total;
+    hash = json_path_mix(pre_hash, json_path_sum(w, kb, len), len);
+}
 
 // child of `parent` under the component kb[0, len), or kJsonNone.  A hit is a node whose parent, length and bytes agree.
 template <class W, class KB>
@@ -307,9 +380,67 @@ GFT_JHD inline uint32_t json_value_node(W& w, const JsonTrie& T, JsonWalk& S) {
     return node;
 }
 
-// One event: byte c at offset pos of the document, outside every string or one of its quotes.  false: not JSON.
+// ---- discovery -------------------------------------------------------------------------------------------------------------
+struct JsonNoPaths { static constexpr bool on = false; };
+struct JsonPaths {                                 // what discovery reads and fills
+    static constexpr bool on = true;
+    JsonPathMem* pm;
+    JsonPathSet set;
+};
+
+// the path of the value that begins now
+template <class W, class D>
+GFT_JHD inline void json_value_path(W& w, D& dsc, const JsonWalk& S, uint64_t& hash, uint32_t& plen) {
+    if (!S.depth) { hash = kJsonPathRoot; plen = 0; return; }
+    hash = 0; plen = kJsonNone;
+    if (S.depth > kJsonMaxDepth) return;
+    const uint32_t d = S.depth - 1;
+    JsonPathMem& pm = *dsc.pm;
+    if (json_top_is_object(w, S)) { hash = w.uni64(pm.cur_hash[d]); plen = w.uni(pm.cur_len[d]); return; }
+    const JsonKeyIndex kb(w.uni(w.mem().count[d]));
+    json_path_child(w, w.uni64(pm.pre_hash[d]), w.uni(pm.pre_len[d]), kb, kb.len(), hash, plen);
+}
+
+// A string value at the path (hash, plen), whose components the wave still holds.  The slot is read with a plain load first:
+// a path that is in the set already -- the common case -- costs no atomic.  The wave whose compare-and-swap put the hash in
+// takes a path number and pool space and writes the bytes with all its lanes; when the cap or the pool is exhausted the slot
+// keeps the hash and nothing is written.  Nothing at or behind pool + pool_bytes is stored.
 template <class W>
-GFT_JHD inline bool json_event(W& w, const JsonTrie& T, const uint8_t* doc, const JsonDocOut& O, JsonWalk& S, uint32_t pos, uint32_t c) {
+GFT_JHD inline void json_path_found(W& w, const JsonPathSet& G, JsonPathMem& pm, const uint8_t* doc, const JsonWalk& S, uint64_t hash, uint32_t plen) {
+    if (!hash) hash = 1;
+    uint32_t slot = (uint32_t)(hash >> 40) & (kJsonPathSlots - 1);
+    for (uint32_t probe = 0; probe < kJsonPathProbes; probe++, slot = (slot + 1) & (kJsonPathSlots - 1)) {
+        uint64_t v = w.load64(G.slots + slot);
+        if (v == hash) return;
+        if (v) continue;
+        v = w.cas64(G.slots + slot, hash);                                     // (one lane; the slot's value before it)
+        if (v == hash) return;
+        if (v) continue;
+        const uint32_t n = w.add32(G.count, 1);
+        const uint32_t need = 4 + ((plen + 3) & ~3u);
+        if (n >= kJsonPathCap) { (void)w.add32(G.dropped, 1); return; }
+        const uint32_t off = w.add32(G.cursor, need);                          // (at most kJsonPathCap times: no wrap)
+        if ((uint64_t)off + need > G.pool_bytes) { (void)w.add32(G.dropped, 1); return; }
+        const uint32_t end = off + 4 + plen;
+        uint32_t at = off + 4;
+        for (uint32_t d = 0; d < S.depth; d++) {
+            if (d) { w.once([&]() { if (at < end) G.pool[at] = '.'; }); at++; }
+            auto put = [&](const auto& kb, uint32_t len) {
+                w.each([&](uint32_t l) { for (uint32_t j = l; j < len; j += 64) if (at + j < end) G.pool[at + j] = (uint8_t)kb(j); });
+                at += len;
+            };
+            if (w.uni(w.mem().kinds[d >> 5]) >> (d & 31) & 1) put(JsonKeyMem{doc + w.uni(pm.key_off[d])}, w.uni(pm.key_len[d]));
+            else { const JsonKeyIndex kb(w.uni(w.mem().count[d])); put(kb, kb.len()); }
+        }
+        w.once([&]() { *reinterpret_cast<uint32_t*>(G.pool + off) = plen; G.path_off[n] = off; });   // (off is a multiple of 4)
+        return;
+    }
+    (void)w.add32(G.dropped, 1);
+}
+
+// One event: byte c at offset pos of the document, outside every string or one of its quotes.  false: not JSON.
+template <class W, class D>
+GFT_JHD inline bool json_event(W& w, D& dsc, const JsonTrie& T, const uint8_t* doc, const JsonDocOut& O, JsonWalk& S, uint32_t pos, uint32_t c) {
     const uint32_t prev = S.prev_pos;
     S.prev_pos = pos;
     if (S.state == kJwNumber) {
@@ -327,21 +458,36 @@ GFT_JHD inline bool json_event(W& w, const JsonTrie& T, const uint8_t* doc, cons
     case kJwValueOrClose:
         if (c == ']' && S.state == kJwValueOrClose) { S.depth--; S.state = kJwAfter; return true; }
         if (c == '"') {
-            const uint32_t node = json_value_node(w, T, S);
-            const uint32_t field = node == kJsonNone ? kJsonNone : w.uni(T.nodes[node].field);
-            if (field == kJsonNone) { S.cond |= 1u << kJsPath; S.mode = kJmOther; }
-            else {
-                S.mode = kJmLeaf;
-                const uint64_t l = O.leaf_base + S.n_leaves;
-                if (O.leaf_off && l < O.leaf_cap) w.once([&]() { O.leaf_field[l] = field; O.leaf_off[l] = O.text_base + S.n_text; });
-                S.n_leaves++;
+            if constexpr (D::on) {
+                uint64_t hash; uint32_t plen;
+                json_value_path(w, dsc, S, hash, plen);
+                if (plen != kJsonNone) json_path_found(w, dsc.set, *dsc.pm, doc, S, hash, plen);
+                S.mode = kJmOther;
+            } else {
+                const uint32_t node = json_value_node(w, T, S);
+                const uint32_t field = node == kJsonNone ? kJsonNone : w.uni(T.nodes[node].field);
+                if (field == kJsonNone) { S.cond |= 1u << kJsPath; S.mode = kJmOther; }
+                else {
+                    S.mode = kJmLeaf;
+                    const uint64_t l = O.leaf_base + S.n_leaves;
+                    if (O.leaf_off && l < O.leaf_cap) w.once([&]() { O.leaf_field[l] = field; O.leaf_off[l] = O.text_base + S.n_text; });
+                    S.n_leaves++;
+                }
             }
             S.state = kJwInString;
             return true;
         }
         if (c == '{' || c == '[') {
             if (S.depth >= kJsonHardDepth) return false;                        // json_mini: "exceeded max depth"
-            const uint32_t node = S.depth < kJsonMaxDepth ? json_value_node(w, T, S) : kJsonNone;
+            if constexpr (D::on) {
+                if (S.depth < kJsonMaxDepth) {                                  // the container's own path, before it is pushed
+                    uint64_t hash; uint32_t plen;
+                    json_value_path(w, dsc, S, hash, plen);
+                    dsc.pm->pre_hash[S.depth] = hash; dsc.pm->pre_len[S.depth] = plen; dsc.pm->cur_len[S.depth] = kJsonNone;
+                }
+            }
+            uint32_t node = kJsonNone;
+            if constexpr (!D::on) node = S.depth < kJsonMaxDepth ? json_value_node(w, T, S) : kJsonNone;
             const uint32_t kw = w.uni(w.mem().kinds[S.depth >> 5]);
             w.mem().kinds[S.depth >> 5] = c == '{' ? kw | 1u << (S.depth & 31) : kw & ~(1u << (S.depth & 31));
             if (S.depth < kJsonMaxDepth) { w.mem().node[S.depth] = node; w.mem().count[S.depth] = 0; }
@@ -379,8 +525,18 @@ GFT_JHD inline bool json_event(W& w, const JsonTrie& T, const uint8_t* doc, cons
         if (S.mode == kJmKey) {
             const uint32_t len = pos - S.key_start;
             if (!len) { S.cond |= 1u << kJsKey; S.key_bad = 1; }
-            S.key_node = S.key_bad ? kJsonNone : json_trie_find(w, T, json_parent(w, S), JsonKeyMem{doc + S.key_start}, len);
-            json_mark(w, S, S.key_node);
+            if constexpr (D::on) {
+                if (S.depth <= kJsonMaxDepth) {
+                    const uint32_t d = S.depth - 1;
+                    JsonPathMem& pm = *dsc.pm;
+                    uint64_t hash = 0; uint32_t plen = kJsonNone;
+                    if (!S.key_bad) json_path_child(w, w.uni64(pm.pre_hash[d]), w.uni(pm.pre_len[d]), JsonKeyMem{doc + S.key_start}, len, hash, plen);
+                    pm.cur_hash[d] = hash; pm.cur_len[d] = plen; pm.key_off[d] = S.key_start; pm.key_len[d] = len;
+                }
+            } else {
+                S.key_node = S.key_bad ? kJsonNone : json_trie_find(w, T, json_parent(w, S), JsonKeyMem{doc + S.key_start}, len);
+                json_mark(w, S, S.key_node);
+            }
             S.state = kJwColon;
         } else {
             S.state = kJwAfter;
@@ -414,12 +570,14 @@ GFT_JHD inline void json_segment(W& w, const JsonMasks& M, const JsonDocOut& O, 
 }
 
 // One document.  Returns its status; *n_leaves / *n_text: what it gives (0 unless the status is 0).
-template <class W>
+template <class W, class D = JsonNoPaths>
 GFT_JHD inline uint32_t json_walk_doc(W& w, const JsonTrie& T, const uint8_t* doc, uint32_t len, const JsonDocOut& O, uint32_t* n_leaves,
-                                      uint32_t* n_text) {
+                                      uint32_t* n_text, D dsc = D()) {
     *n_leaves = 0; *n_text = 0;
-    const uint32_t words = (T.n_nodes + 31) / 32;
-    w.each([&](uint32_t l) { for (uint32_t k = l; k < words; k += 64) w.mem().visited[k] = 0; });
+    if constexpr (!D::on) {
+        const uint32_t words = (T.n_nodes + 31) / 32;
+        w.each([&](uint32_t l) { for (uint32_t k = l; k < words; k += 64) w.mem().visited[k] = 0; });
+    }
     JsonWalk S;
     JsonCarry C{0, 0, 0};
     JsonMasks M;
@@ -431,7 +589,7 @@ GFT_JHD inline uint32_t json_walk_doc(W& w, const JsonTrie& T, const uint8_t* do
         for (uint64_t ev = M.events; ev; ev &= ev - 1) {
             const uint32_t k = (uint32_t)__builtin_ctzll(ev);
             if (S.state == kJwInString) json_segment(w, M, O, S, json_range(seg_lo, k));
-            if (!json_event(w, T, doc, O, S, (uint32_t)base + k, w.byte_at(k))) return kJsSyntax;
+            if (!json_event(w, dsc, T, doc, O, S, (uint32_t)base + k, w.byte_at(k))) return kJsSyntax;
             seg_lo = k + 1;
         }
         if (S.state == kJwInString) json_segment(w, M, O, S, json_range(seg_lo, 64) & M.valid);
@@ -441,6 +599,14 @@ GFT_JHD inline uint32_t json_walk_doc(W& w, const JsonTrie& T, const uint8_t* do
     if (S.cond) return (uint32_t)__builtin_ctz(S.cond);
     *n_leaves = S.n_leaves; *n_text = S.n_text;
     return kJsOk;
+}
+// discovery: the paths of the document's string values go into dsc.set
+template <class W>
+GFT_JHD inline void json_walk_paths(W& w, const JsonPaths& dsc, const uint8_t* doc, uint32_t len) {
+    const JsonTrie no_trie{nullptr, nullptr, nullptr, 0, 0, 0};
+    const JsonDocOut none{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    uint32_t a, b;
+    (void)json_walk_doc(w, no_trie, doc, len, none, &a, &b, dsc);
 }
 
 }  // namespace gft

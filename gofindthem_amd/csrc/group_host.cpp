@@ -12,6 +12,7 @@
 #include "gft_guard.hpp"
 #include "gft_json.hpp"
 #include "gft_rules.hpp"
+#include "json_paths.hpp"
 #include "json_schema.hpp"
 #include "rule_set.hpp"
 
@@ -774,34 +775,20 @@ int GroupFinder::ProcessJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc
     return ProcessRecordsDevice(d_text, d_leaf_off, d_leaf_field, d_rec_off, n_docs, totals[0], d_rule_bitmap, err);
 }
 
-int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
-    int rc = json_current(nullptr, err);
-    if (rc) return rc;
-    if ((rc = compile_current(err))) return rc;
-    if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
-    gft_engine* e = findthem_->device_engine();
-    json_last_device = json_last_host = 0;
-    if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) {
-        // regex terms, injected engines, several devices: the walk on host threads, for every document
-        err = ProcessJsons(blob, doc_off, n_docs, rec_->inc, rec_->exc, false, out);
-        json_last_host = n_docs;
-        return err.empty() ? GFT_OK : GFT_E_ENGINE;
-    }
-    out.assign(n_docs, DocResult());
-    if (!n_docs) return GFT_OK;
+int GroupFinder::json_staged_rows(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rows,
+                                  std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err) {
     const uint64_t RW = (rec_->set.n_rules + 31) / 32;
-    std::vector<uint8_t> status(n_docs);
-    std::vector<uint32_t> rows((size_t)(n_docs * RW) + 1, 0);
-    {
-        RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
-        const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
-        if ((rc = json_stage(e, blob, doc_off, n_docs, RW * 4, &d_blob, &d_doc_off, &d_status, &d_rows))) { err = gft_last_error(e); return rc; }
-        if ((rc = ProcessJsonsDevice(d_blob, d_doc_off, n_docs, d_status, d_rows, err))) return rc;
-        if ((rc = rules_fetch(e, status.data(), d_status, n_docs)) || (rc = rules_fetch(e, rows.data(), d_rows, n_docs * RW * 4))) {
-            err = gft_last_error(e);
-            return rc;
-        }
-    }
+    status.assign(n_docs, 0);
+    rows.assign((size_t)(n_docs * RW) + 1, 0);
+    int rc = ProcessJsonsDevice(d_blob, d_doc_off, n_docs, d_status, d_rows, err);
+    if (rc) return rc;
+    if ((rc = rules_fetch(e, status.data(), d_status, n_docs)) || (rc = rules_fetch(e, rows.data(), d_rows, n_docs * RW * 4))) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::json_results(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                              const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err) {
+    const uint64_t RW = (rec_->set.n_rules + 31) / 32;
     // what the device did not decide: one sub-batch through the host route
     std::vector<uint64_t> host_docs;
     for (uint64_t d = 0; d < n_docs; d++)
@@ -829,6 +816,132 @@ int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off
     json_last_host = host_docs.size();
     json_last_device = n_docs - host_docs.size();
     return GFT_OK;
+}
+
+int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
+    int rc = json_current(nullptr, err);
+    if (rc) return rc;
+    if ((rc = compile_current(err))) return rc;
+    if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
+    gft_engine* e = findthem_->device_engine();
+    json_last_device = json_last_host = 0;
+    if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) {
+        // regex terms, injected engines, several devices: the walk on host threads, for every document
+        err = ProcessJsons(blob, doc_off, n_docs, rec_->inc, rec_->exc, false, out);
+        json_last_host = n_docs;
+        return err.empty() ? GFT_OK : GFT_E_ENGINE;
+    }
+    out.assign(n_docs, DocResult());
+    if (!n_docs) return GFT_OK;
+    const uint64_t RW = (rec_->set.n_rules + 31) / 32;
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> rows;
+    {
+        RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
+        const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
+        if ((rc = json_stage(e, blob, doc_off, n_docs, RW * 4, &d_blob, &d_doc_off, &d_status, &d_rows))) { err = gft_last_error(e); return rc; }
+        if ((rc = json_staged_rows(e, d_blob, d_doc_off, n_docs, d_status, d_rows, status, rows, err))) return rc;
+    }
+    return json_results(blob, doc_off, n_docs, status, rows, out, err);
+}
+
+// ---- the schema discovered from the batch ------------------------------------------------------------------------------------
+int GroupFinder::JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths,
+                                 uint64_t* dropped, Error& err) {
+    gft_engine* e = findthem_->device_engine();
+    if (!e) { err = "no GPU engine"; return GFT_E_HIP; }
+    if (gft_n_devices(e) != 1) { err = "JSON batches: single-device handles only"; return GFT_E_UNSUPPORTED; }
+    RulesLock whole_call(e);               // (the set and the pool are the engine's)
+    int rc = json_paths_device(e, d_blob, d_doc_off, n_docs, paths, dropped);
+    if (rc) err = gft_last_error(e);
+    return rc;
+}
+
+// auto_ in rec_'s place for the length of a call: compile_current, install_current, json_current and the routes on top of
+// them answer against it; the serials re-install whichever set and trie the engine does not hold
+struct GroupFinder::UseAuto {
+    GroupFinder& g;
+    explicit UseAuto(GroupFinder& g_) : g(g_) { std::swap(g.rec_, g.auto_); }
+    ~UseAuto() { std::swap(g.rec_, g.auto_); }
+};
+
+int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                                  const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err) {
+    int rc = json_check_offsets(doc_off, n_docs, err);
+    if (rc) return rc;
+    gft_engine* e = findthem_->device_engine();
+    json_last_device = json_last_host = 0;
+    auto_last_paths = auto_last_dropped = auto_last_recompiled = 0;
+    auto by_host = [&]() {
+        err = ProcessJsons(blob, doc_off, n_docs, includePaths, excludePaths, false, out);
+        json_last_device = 0;
+        json_last_host = n_docs;
+        return err.empty() ? GFT_OK : GFT_E_ENGINE;
+    };
+    // regex terms, injected engines, several devices: the walk on host threads, for every document
+    if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) return by_host();
+    out.assign(n_docs, DocResult());
+    if (!n_docs) return GFT_OK;
+    const uint64_t RW = (RuleExprs().size() + 31) / 32;      // (a bit per rule expression, whatever the schema)
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> rows;
+    bool refused = false;                  // a limit of the schema's compilers: the host route, for every document
+    {
+        RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
+        const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
+        if ((rc = json_stage(e, blob, doc_off, n_docs, RW * 4, &d_blob, &d_doc_off, &d_status, &d_rows))) { err = gft_last_error(e); return rc; }
+        std::vector<std::string> found;
+        if ((rc = json_paths_device(e, d_blob, d_doc_off, n_docs, found, &auto_last_dropped))) { err = gft_last_error(e); return rc; }
+        auto_last_paths = found.size();
+        // the kept schema answers when it covers the batch and was made for these lists
+        const bool same_lists = auto_ && auto_->inc == includePaths && auto_->exc == excludePaths;
+        bool covered = same_lists;
+        if (covered) {
+            const std::set<std::string> kept(auto_->schema.begin(), auto_->schema.end());
+            for (const auto& p : found) covered = covered && kept.count(p);
+        }
+        if (!covered) {
+            // what was kept stays in when the whole still compiles, so that batches of alternating shapes settle
+            std::vector<std::vector<std::string>> tries;
+            if (same_lists) {
+                std::set<std::string> all(auto_->schema.begin(), auto_->schema.end());
+                all.insert(found.begin(), found.end());
+                if (all.size() <= kJsonPathCap) tries.emplace_back(all.begin(), all.end());
+            }
+            tries.push_back(found);
+            std::shared_ptr<Records> next;
+            for (const auto& paths : tries) {
+                auto r = std::make_shared<Records>();
+                Error why;
+                rc = compile_rules(rules_, findthem_->tags(), findthem_->tag_ids(), paths, includePaths, excludePaths, r->set, why);
+                if (!rc) rc = r->json_rc = compile_json_schema(paths, r->json, r->json_err);
+                if (rc == GFT_E_UNSUPPORTED) continue;         // a limit: never the caller's error
+                if (rc) { err = why.empty() ? r->json_err : why; return rc; }
+                r->schema = paths; r->inc = includePaths; r->exc = excludePaths;
+                r->rules_version = rules_version_;
+                r->n_exprs = findthem_->expressions().size();
+                next = std::move(r);
+                break;
+            }
+            if (!next) { refused = true; }
+            else auto_ = std::move(next);
+            auto_last_recompiled = 1;
+        } else if (auto_->rules_version != rules_version_ || auto_->n_exprs != findthem_->expressions().size()) {
+            auto_last_recompiled = 1;      // (compile_current, below)
+        }
+        if (!refused) {
+            UseAuto swapped(*this);
+            rc = compile_current(err);                         // (rules or expressions were added since)
+            if (rc == GFT_E_UNSUPPORTED) { err.clear(); refused = true; }
+            else if (rc) return rc;
+            else if ((uint64_t)(rec_->set.n_rules + 31) / 32 != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; return GFT_E_INTERNAL; }
+            else if ((rc = json_staged_rows(e, d_blob, d_doc_off, n_docs, d_status, d_rows, status, rows, err))) return rc;
+            if (refused) rec_.reset();                         // (auto_, behind the swap: its rules no longer compile)
+        }
+    }
+    if (refused) return by_host();
+    UseAuto swapped(*this);
+    return json_results(blob, doc_off, n_docs, status, rows, out, err);
 }
 
 int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {
@@ -1044,6 +1157,86 @@ int gft_group_json_last(const gft_group* g, uint64_t* n_device, uint64_t* n_host
     if (n_host) *n_host = g->g->json_last_host;
     return GFT_OK;
 } GFT_CATCH((g ? &const_cast<gft_group*>(g)->err : nullptr))
+
+namespace {
+// sorted paths -> blob + offsets under the cap / needed convention: needed[0] bytes, needed[1] paths; path_off [path_cap + 1]
+int put_paths(const std::vector<std::string>& paths, uint8_t* blob, uint64_t blob_cap, uint64_t* path_off, uint64_t path_cap, uint64_t* needed,
+              uint64_t* n_paths) {
+    uint64_t bytes = 0;
+    for (const auto& p : paths) bytes += p.size();
+    if (needed) { needed[0] = bytes; needed[1] = paths.size(); }
+    if (n_paths) *n_paths = paths.size();
+    if (bytes > blob_cap || paths.size() > path_cap || !path_off || (bytes && !blob)) return GFT_E_INVALID;
+    uint64_t at = 0;
+    for (size_t i = 0; i < paths.size(); i++) {
+        path_off[i] = at;
+        if (!paths[i].empty()) memcpy(blob + at, paths[i].data(), paths[i].size());
+        at += paths[i].size();
+    }
+    path_off[paths.size()] = at;
+    return GFT_OK;
+}
+}  // namespace
+
+int gft_group_json_paths_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* paths_blob,
+                                uint64_t blob_cap, uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths, uint64_t* dropped) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> paths;
+    int rc = g->g->JsonPathsDevice(d_json_blob, d_doc_off, n_docs, paths, dropped, g->err);
+    if (rc) return rc;
+    if ((rc = put_paths(paths, paths_blob, blob_cap, path_off, path_cap, needed, n_paths))) g->err = "gft_group_json_paths_device: the paths do not fit the caps";
+    return rc;
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_process_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* include_json,
+                                 uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap,
+                                 uint64_t* needed) try {
+    if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> inc, exc;
+    if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
+    std::vector<GroupFinder::DocResult> res;
+    int rc = g->g->ProcessJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err);
+    if (rc) return rc;
+    result_document(g, res, 0);
+    return put(g->result, out, cap, needed);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_json_auto_last(const gft_group* g, uint64_t* n_paths, uint64_t* dropped, uint64_t* recompiled) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    if (n_paths) *n_paths = g->g->auto_last_paths;
+    if (dropped) *dropped = g->g->auto_last_dropped;
+    if (recompiled) *recompiled = g->g->auto_last_recompiled;
+    return GFT_OK;
+} GFT_CATCH((g ? &const_cast<gft_group*>(g)->err : nullptr))
+
+int gft_debug_emulate_json_paths(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* paths_blob,
+                                 uint64_t blob_cap, uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths, uint64_t* dropped,
+                                 uint64_t* hashes, uint64_t hash_cap, uint64_t* n_hashes) try {
+    if (!g || (n_docs && !doc_off)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> paths;
+    std::vector<uint64_t> set;
+    int rc = json_paths_emulate(json_blob, doc_off, n_docs, paths, &set, dropped, g->err);
+    if (rc) return rc;
+    if (n_hashes) *n_hashes = set.size();
+    if (hashes) memcpy(hashes, set.data(), (size_t)std::min<uint64_t>(hash_cap, set.size()) * 8);
+    if ((rc = put_paths(paths, paths_blob, blob_cap, path_off, path_cap, needed, n_paths))) g->err = "gft_debug_emulate_json_paths: the paths do not fit the caps";
+    return rc;
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_json_paths_ref(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* paths_blob, uint64_t blob_cap,
+                             uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths) try {
+    if (!g || (n_docs && !doc_off)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> paths;
+    int rc = json_paths_ref(json_blob, doc_off, n_docs, paths, g->err);
+    if (rc) return rc;
+    if ((rc = put_paths(paths, paths_blob, blob_cap, path_off, path_cap, needed, n_paths))) g->err = "gft_debug_json_paths_ref: the paths do not fit the caps";
+    return rc;
+} GFT_CATCH((g ? &g->err : nullptr))
 
 int gft_group_json_leaves_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
                                  uint64_t* d_rec_off, uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text,

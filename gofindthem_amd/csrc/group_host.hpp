@@ -144,13 +144,24 @@ public:
     // ProcessJsons as one sub-batch.  The include / exclude lists are the schema's.  A finder that does not qualify for the
     // device record route takes ProcessJsons for the whole batch.  out: as ProcessJsons with want_tags = false.
     int ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err);
+    // ---- the schema discovered from the batch (k_json_paths): what ProcessJson means without SetSchema
+    // device pointers: the distinct paths of the batch's string values, sorted bytewise; needs no schema
+    int JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths, uint64_t* dropped,
+                        Error& err);
+    // host pointers: upload once, discover the paths, compile them into a schema of its own (kept between calls, apart from
+    // SetSchema's) and run ProcessJsonsSchema's route on the staged batch.  out: as ProcessJsons with want_tags = false, for
+    // every batch; a finder that does not qualify, or a discovered schema beyond a limit, sends the batch through ProcessJsons.
+    int ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                         const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err);
+    // what the last ProcessJsonsAuto found: paths, paths found and not kept, whether it compiled a schema
+    uint64_t auto_last_paths = 0, auto_last_dropped = 0, auto_last_recompiled = 0;
     // no device: the reference classification and the kernels' walker on the host (json_schema.hpp), against the stored schema
     int DebugJsonLeaves(bool emulate, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
                         uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals, Error& err);
     // the trie's lookup (tests): the child of node `parent` under a component, or `parent` itself for key_len == 0; -1: none.
     // *field: the node's field index, or -1
     int64_t DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field);
-    // documents of the last ProcessJsonsSchema batch decided on the device / handed to ProcessJsons
+    // documents of the last ProcessJsonsSchema / ProcessJsonsAuto batch decided on the device / handed to ProcessJsons
     uint64_t json_last_device = 0, json_last_host = 0;
 
     // the compiled device words interpreted on the host over a caller-supplied leaf bitmap: no device
@@ -175,6 +186,15 @@ private:
 
     struct Records;                        // schema, compiled RuleSet and what it was compiled from (group_host.cpp)
     std::shared_ptr<Records> rec_;
+    std::shared_ptr<Records> auto_;        // ProcessJsonsAuto's: stands in for rec_ while that call runs (UseAuto)
+    struct UseAuto;
+    // ProcessJsonsSchema behind the upload, for whichever schema rec_ is.  Under the caller's RulesLock: ProcessJsonsDevice over
+    // the staged batch, status and rows down ...
+    int json_staged_rows(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rows,
+                         std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err);
+    // ... and behind it: the documents the device did not decide through ProcessJsons as one sub-batch, the others from their rows
+    int json_results(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                     const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err);
     uint64_t rules_version_ = 0;           // counts AddRule calls that changed rules_
     std::vector<RuleExpr> rule_exprs_;
     uint64_t rule_exprs_version_ = ~0ull;

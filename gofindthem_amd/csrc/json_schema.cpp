@@ -7,32 +7,12 @@
 #include <memory>
 #include <set>
 
+#include "json_host_wave.hpp"
 #include "json_mini.hpp"
 
 namespace gft {
 
 namespace {
-
-// the lanes of a wave as loops (gft_json_walk.hpp)
-struct HostWave {
-    uint8_t bytes[64];
-    uint32_t fl[64];
-    JsonLaneOut lo[64];
-    JsonWaveMem* m;
-    void load(const uint8_t* doc, uint32_t base, uint32_t len) {
-        for (uint32_t l = 0; l < 64; l++) bytes[l] = (uint64_t)base + l < len ? doc[base + l] : 0;
-    }
-    uint32_t lane_byte(uint32_t l) const { return bytes[l]; }
-    uint32_t byte_at(uint32_t k) const { return bytes[k]; }
-    template <class F> uint64_t ballot(F&& f) { uint64_t r = 0; for (uint32_t l = 0; l < 64; l++) if (f(l)) r |= 1ull << l; return r; }
-    template <class F> uint32_t sum(F&& f) { uint32_t r = 0; for (uint32_t l = 0; l < 64; l++) r += f(l); return r; }
-    template <class F> void each(F&& f) { for (uint32_t l = 0; l < 64; l++) f(l); }
-    template <class F> void once(F&& f) { f(); }
-    JsonLaneOut& out(uint32_t l) { return lo[l]; }
-    uint32_t& flags(uint32_t l) { return fl[l]; }
-    template <class T> T uni(T x) const { return x; }
-    JsonWaveMem& mem() { return *m; }
-};
 
 std::vector<std::string> split_path(const std::string& p) {
     std::vector<std::string> out;

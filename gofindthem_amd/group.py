@@ -392,8 +392,90 @@ class GroupFinder:
             raise self._err(rc)
         return json.loads(buf.value.decode("utf-8", "replace"))
 
+    # -- the schema discovered from the batch (csrc/gft_json.hip: k_json_paths) ----------------------------------------------
+    PATH_CAP, PATH_POOL = 16384, 8 << 20                     # what the device keeps at most: the caps that always suffice
+
+    def _paths_call(self, fn, *args):
+        """the paths_blob / path_off / needed / n_paths part of the three path calls -> a sorted list of byte strings"""
+        blob_cap, path_cap = self.PATH_POOL, self.PATH_CAP
+        needed = np.zeros(2, dtype=np.uint64)
+        n = C.c_uint64(0)
+        head, tail = args
+        while True:
+            blob = np.zeros(blob_cap, dtype=np.uint8)
+            off = np.zeros(path_cap + 1, dtype=np.uint64)
+            rc = fn(self._h, *head, blob.ctypes.data, blob_cap, off.ctypes.data, path_cap, needed.ctypes.data, C.byref(n), *tail)
+            if rc == _lib.GFT_E_INVALID and (needed[0] > blob_cap or needed[1] > path_cap):     # (the reference knows no cap)
+                blob_cap, path_cap = max(blob_cap, int(needed[0])), max(path_cap, int(needed[1]))
+                continue
+            break
+        if rc != 0:
+            raise self._err(rc)
+        raw = blob[:int(needed[0])].tobytes()
+        return [raw[int(off[i]):int(off[i + 1])] for i in range(int(n.value))]
+
+    def JsonPathsDevice(self, blob, doc_off):
+        """torch device tensors as for JsonLeavesDevice -> (the distinct paths of the batch's string values as byte strings, sorted
+        bytewise, each once; the number of paths found and not kept).  Needs no schema."""
+        import torch
+        n = int(doc_off.numel()) - 1
+        for t, size in ((blob, 1), (doc_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "JsonPathsDevice takes contiguous device tensors of 1 and 8 byte integers")
+        torch.cuda.current_stream(blob.device).synchronize()
+        dropped = C.c_uint64(0)
+        paths = self._paths_call(self._L.gft_group_json_paths_device, (blob.data_ptr(), doc_off.data_ptr(), n), (C.byref(dropped),))
+        return paths, int(dropped.value)
+
+    def _paths_host(self, docs):
+        docs = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in docs]
+        blob, off = pack(docs)
+        blob = np.concatenate([blob, np.zeros(64, dtype=np.uint8)])
+        return blob, off, len(docs)
+
+    def debug_emulate_json_paths(self, docs):
+        """gft_debug_emulate_json_paths over a list of byte strings -> (paths, dropped, the hashes in the set, ascending)"""
+        blob, off, n = self._paths_host(docs)
+        hashes = np.zeros(1 << 16, dtype=np.uint64)
+        dropped, n_hashes = C.c_uint64(0), C.c_uint64(0)
+        paths = self._paths_call(self._L.gft_debug_emulate_json_paths, (blob.ctypes.data, off.ctypes.data, n),
+                                 (C.byref(dropped), hashes.ctypes.data, hashes.size, C.byref(n_hashes)))
+        return paths, int(dropped.value), [int(h) for h in hashes[:int(n_hashes.value)]]
+
+    def debug_json_paths_ref(self, docs):
+        """gft_debug_json_paths_ref: the paths of the string values of the documents that the host route's reader accepts"""
+        blob, off, n = self._paths_host(docs)
+        return self._paths_call(self._L.gft_debug_json_paths_ref, (blob.ctypes.data, off.ctypes.data, n), ())
+
+    def ProcessJsonsAuto(self, rawJsons, includePaths=None, excludePaths=None):
+        """ProcessJsons(rawJsons, includePaths, excludePaths) with the schema discovered from the batch on the device and the
+        documents decoded there where the device decides them"""
+        raws = [r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in rawJsons]
+        blob, off = pack(raws)
+        inc = json.dumps(list(includePaths)).encode() if includePaths else None
+        exc = json.dumps(list(excludePaths)).encode() if excludePaths else None
+        need = C.c_uint64(0)
+        cap = max(1 << 16, 2 * int(blob.size))
+        buf = C.create_string_buffer(cap)
+        rc = self._L.gft_group_process_jsons_auto(self._h, blob.ctypes.data, off.ctypes.data, len(raws), inc, len(inc) if inc else 0,
+                                                  exc, len(exc) if exc else 0, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc == _lib.GFT_E_INVALID and need.value > cap:      # the library kept the document: fetch it, no second run
+            cap = int(need.value)
+            buf = C.create_string_buffer(cap)
+            rc = self._L.gft_group_last_result(self._h, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc != 0:
+            raise self._err(rc)
+        return json.loads(buf.value.decode("utf-8", "replace"))
+
+    def json_auto_last(self):
+        """(distinct paths, paths found and not kept, 1 if a schema was compiled) of the last ProcessJsonsAuto batch"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._L.gft_group_json_auto_last(self._h, C.byref(a), C.byref(b), C.byref(c))
+        return int(a.value), int(b.value), int(c.value)
+
     def json_last(self):
-        """(documents decided on the device, documents handed to the host route) of the last ProcessJsonsSchema batch"""
+        """(documents decided on the device, documents handed to the host route) of the last ProcessJsonsSchema / ProcessJsonsAuto
+        batch"""
         a, b = C.c_uint64(), C.c_uint64()
         self._L.gft_group_json_last(self._h, C.byref(a), C.byref(b))
         return int(a.value), int(b.value)

@@ -482,8 +482,48 @@ int gft_group_process_jsons_device(gft_group* g, const uint8_t* d_json_blob, con
  * batch.  gft_group_last_result serves this call too. */
 int gft_group_process_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
                                    uint64_t* needed);
-/* documents of the last gft_group_process_jsons_schema batch decided on the device / handed to the host route */
+/* documents of the last gft_group_process_jsons_schema / _auto batch decided on the device / handed to the host route */
 int gft_group_json_last(const gft_group* g, uint64_t* n_device, uint64_t* n_host);
+/* ---- The schema discovered from the batch (gft_json.hip: k_json_paths) ------------------------------------------------------
+ * One more pass of the same walker, without a trie, collects the distinct paths of the batch's string values on the device:
+ * a set of 2^16 64-bit path hashes (linear probing), at most 16384 paths, a pool of 8 MiB for their bytes.  A path is spelled
+ * as the object walk spells it ("Body", "Meta.Notes", "items.index(2)", "" for a top-level string); none is produced below a
+ * key that is empty, contains a backslash or is not valid UTF-8, below 32 open containers, or when it is longer than 65535
+ * bytes.  A value under a key that contains '.' is reported, its key as one component.  A path that the pass misses -- a hash
+ * collision, a full set, the cap, the pool: *dropped counts the paths found and not kept -- only makes the documents that use
+ * it GFT_JSON_PATH under the resulting schema: a miss costs time, never a result.  A document that is not valid JSON may
+ * have contributed the paths in front of its error.
+ *
+ * Device pointers in (no byte outside the documents is read), host memory out: paths_blob [blob_cap] and
+ * path_off [path_cap + 1] receive the paths sorted bytewise, each once; needed[2] (nullable): bytes, paths; GFT_E_INVALID when a
+ * cap is too small (8 MiB and 16384 always suffice).  One launch on the engine's stream (gft_profile_read: "json_paths").  Needs
+ * no schema.  GFT_E_INVALID: offsets that descend, a document of 4 GiB or more, a null argument.  Handles over several
+ * devices: GFT_E_UNSUPPORTED.  n_docs == 0 is valid and gives no paths. */
+int gft_group_json_paths_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* paths_blob,
+                                uint64_t blob_cap, uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths, uint64_t* dropped);
+/* ProcessJson as the reference has it: no schema.  Host pointers; the same result document as gft_group_process_jsons(...,
+ * what = 0) with the same lists, for every batch.  The batch is uploaded once, its paths are discovered (the call above),
+ * compiled into a schema of the group's own -- kept between calls and apart from gft_group_set_schema's, which goes on
+ * answering its calls -- and gft_group_process_jsons_schema's route runs on the staged batch.  A later call compiles again only
+ * when it found a path the kept schema lacks, when the lists changed, or when rules or finder expressions were added.  The
+ * whole batch takes gft_group_process_jsons' route when the finder does not qualify (regex terms, injected engines, several
+ * devices) or when the discovered schema is beyond a limit (16384 trie nodes, 65535 fields, ...): never an error of the
+ * caller.  gft_group_last_result and gft_group_json_last serve this call too. */
+int gft_group_process_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* include_json,
+                                 uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap,
+                                 uint64_t* needed);
+/* what the last gft_group_process_jsons_auto found: distinct paths, paths found and not kept, 1 when it compiled a schema */
+int gft_group_json_auto_last(const gft_group* g, uint64_t* n_paths, uint64_t* dropped, uint64_t* recompiled);
+/* No device needed (tests), host pointers, the output contract of gft_group_json_paths_device: the discovery mode of the
+ * kernels' walker on the host, 64-byte piece by piece, with the set and the pool as plain arrays (hashes [hash_cap], nullable:
+ * the values in the set, ascending; *n_hashes: how many there are) -- ... */
+int gft_debug_emulate_json_paths(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* paths_blob,
+                                 uint64_t blob_cap, uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths, uint64_t* dropped,
+                                 uint64_t* hashes, uint64_t hash_cap, uint64_t* n_hashes);
+/* ... and the reference: the host route's JSON reader plus a walk that collects every string value's path as a list of
+ * components, joined at the end, by code that shares nothing with the walker.  Only documents that the reader accepts count. */
+int gft_debug_json_paths_ref(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* paths_blob, uint64_t blob_cap,
+                             uint64_t* path_off, uint64_t path_cap, uint64_t* needed, uint64_t* n_paths);
 /* No device needed (tests), host pointers, the array contract of gft_group_json_leaves_device: the reference -- the host
  * route's JSON reader and a walk of the decoded value against the schema, classified into the statuses above by code that
  * shares nothing with the walker -- ... */

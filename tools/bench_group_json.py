@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Measurement of the group finder's three ways through a batch of JSON documents, in one process, on the shape of
+"""Measurement of the group finder's four ways through a batch of JSON documents, in one process, on the shape of
 tools/bench_group.py (50 000 documents of about 4.2 KB with 8 string leaves, 1 000 finder expressions in 50 tags, 100 rules):
 
     ProcessJsons         the JSON reader and the walk on host threads (the baseline)
     ProcessJsonsSchema   host memory in, the documents decoded on the device (csrc/gft_json.hip)
+    ProcessJsonsAuto     as ProcessJsonsSchema without SetSchema: the schema is discovered from the batch on the device
     ProcessJsonsDevice   the same with the blob resident in HBM; status and rule bitmap stay there
 
 Identical rule results are asserted.  One warm-up call each, then the median of --reps calls; the json_* kernel times come
@@ -74,6 +75,11 @@ def schema_route():
     assert rc == 0, L.gft_group_last_error(g._h)
 
 
+def auto_route():
+    rc = L.gft_group_process_jsons_auto(g._h, blob.ctypes.data, boff.ctypes.data, len(raws), None, 0, None, 0, C.cast(buf, C.c_void_p), cap, C.byref(need))
+    assert rc == 0, L.gft_group_last_error(g._h)
+
+
 d_blob = torch.from_numpy(np.concatenate([blob, np.zeros(64, dtype=np.uint8)])).cuda()
 d_off = torch.from_numpy(boff.astype(np.int64)).cuda()
 d_rows = torch.zeros((len(raws), g.rule_words()), dtype=torch.int32, device="cuda")
@@ -102,6 +108,11 @@ schema_s, schema_all = timed(schema_route)
 got = json.loads(buf.value.decode())
 split = g.json_last()
 assert got == want, "ProcessJsonsSchema differs from ProcessJsons"
+auto_s, auto_all = timed(auto_route)
+got = json.loads(buf.value.decode())
+auto_split, auto_last = g.json_last(), g.json_auto_last()
+assert got == want, "ProcessJsonsAuto differs from ProcessJsons"
+assert auto_s < host_s, "ProcessJsonsAuto (median %.3f s) is not faster than ProcessJsons (%.3f s)" % (auto_s, host_s)
 device_s, device_all = timed(device_route)
 assert not bool(d_status.any().item())
 assert g.rules_from_bitmap(d_rows.cpu().numpy().view(np.uint32)) == [r["rules"] for r in want], "ProcessJsonsDevice differs from ProcessJsons"
@@ -119,16 +130,28 @@ for _ in range(args.reps):
         a, n = C.c_double(), C.c_uint64()
         L.gft_profile_read(eh, name.encode(), C.byref(a), C.byref(n))
         kern[name].append(a.value)
+paths_ms = []
+for _ in range(args.reps):
+    L.gft_profile_reset(eh)
+    g.JsonPathsDevice(d_blob, d_off)
+    a, n = C.c_double(), C.c_uint64()
+    L.gft_profile_read(eh, b"json_paths", C.byref(a), C.byref(n))
+    paths_ms.append(a.value)
 L.gft_profile_enable(eh, 0)
 kern_ms = {k: statistics.median(v) for k, v in kern.items()}
+kern_ms["json_paths"] = statistics.median(paths_ms)
 
 print(json.dumps({
     "row": "group finder: JSON batches", "docs": args.docs, "json_bytes": json_bytes, "leaves": leaves, "leaf_bytes": leaf_bytes,
     "rules": len(rules) * 2, "finder_expressions": len(exprs), "reps": args.reps,
     "ProcessJsons": {"median_s": host_s, "docs_per_s": args.docs / host_s, "all_s": host_all},
     "ProcessJsonsSchema": {"median_s": schema_s, "docs_per_s": args.docs / schema_s, "all_s": schema_all, "json_last": split},
+    "ProcessJsonsAuto": {"median_s": auto_s, "docs_per_s": args.docs / auto_s, "all_s": auto_all, "json_last": auto_split, "auto_last": auto_last},
+    "auto_faster_than_host": auto_s < host_s,
     "ProcessJsonsDevice": {"median_s": device_s, "docs_per_s": args.docs / device_s, "all_s": device_all},
     "schema_not_slower_than_host": schema_s <= host_s,
     "kernels_ms": kern_ms,
+    "kernels_all_ms": {"json_count": kern["json_count"], "json_write": kern["json_write"], "json_paths": paths_ms},
+    "json_paths_GBps": json_bytes / (kern_ms["json_paths"] * 1e-3) / 1e9 if kern_ms["json_paths"] else None,
     "json_count_GBps": json_bytes / (kern_ms["json_count"] * 1e-3) / 1e9 if kern_ms["json_count"] else None,
     "json_write_GBps": json_bytes / (kern_ms["json_write"] * 1e-3) / 1e9 if kern_ms["json_write"] else None}))
