@@ -599,7 +599,7 @@ struct gft_finder {
 };
 #define GFT_FLOCK(f) std::lock_guard<std::recursive_mutex> _gft_flock((f)->mu)
 
-// for group_host.cpp: the C++ object behind the handle
+// for group_api.cpp: the C++ object behind the handle
 gft::Finder* gft_finder_impl(gft_finder* f) { return f ? f->finder.get() : nullptr; }
 
 extern "C" {

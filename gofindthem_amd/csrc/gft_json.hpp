@@ -1,5 +1,5 @@
 // gft_json.hpp -- JSON documents decoded on the device into the record form (gft_json.hip): parameter block, launchers, and the
-// engine's side of it (gft_json_api.cpp) that group_host.cpp drives.
+// engine's side of it (gft_json_api.cpp) that group_json.cpp drives.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // gft_json_api.cpp -- JSON documents decoded on the device into the record form (gft_json.hpp): the engine's side, which
-// group_host.cpp drives.
+// group_json.cpp drives.
 #include "gft_engine.hpp"
 
 #include <atomic>

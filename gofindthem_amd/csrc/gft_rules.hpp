@@ -1,5 +1,5 @@
 // gft_rules.hpp -- rule evaluation for records on the device (gft_rules.hip): parameter block, launchers, and the engine's
-// side of it (gft_rules_api.cpp) that group_host.cpp drives.
+// side of it (gft_rules_api.cpp) that group_records.cpp drives.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -34,7 +34,7 @@ hipError_t launch_record_rules(const RulesParams& P, size_t lds_max, hipStream_t
 
 }  // namespace gft
 
-// ---- for group_host.cpp: the engine's side (gft_rules_api.cpp).  Single-device handles only (GFT_E_UNSUPPORTED otherwise); every
+// ---- for group_records.cpp and group_json.cpp: the engine's side (gft_rules_api.cpp).  Single-device handles only (GFT_E_UNSUPPORTED otherwise); every
 // call takes the engine's lock, which is recursive: a caller that needs several of them to see one state -- a group's call
 // from set install to the read of the flags, next to another group on the same finder -- holds RulesLock around them.
 namespace gft {

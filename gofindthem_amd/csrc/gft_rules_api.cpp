@@ -1,4 +1,4 @@
-// gft_rules_api.cpp -- rule evaluation for records (gft_rules.hpp): the engine's side, which group_host.cpp drives.
+// gft_rules_api.cpp -- rule evaluation for records (gft_rules.hpp): the engine's side, which group_records.cpp drives.
 #include "gft_engine.hpp"
 
 #include <atomic>

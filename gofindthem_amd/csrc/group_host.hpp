@@ -4,6 +4,7 @@
 // one document of ONE Finder::ProcessTexts call, instead of one ProcessText per leaf (internal.go:28-31).
 #pragma once
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <set>
@@ -11,96 +12,15 @@
 #include <vector>
 
 #include "finder_host.hpp"
+#include "group_dsl.hpp"
 #include "json_mini.hpp"
 
 namespace gft {
-namespace gdsl {
-
-// group/dsl/scanner.go:12-35
-enum Token { ILLEGAL = 0, END_OF_INPUT, WS, TAG, FIELD_PATH, QUOTATION, OPPAR, CLPAR, AND, OR, NOT };
-const char* token_name(Token t);
-
-// group/dsl/expression.go:11-17
-enum ExprType { UNSET_EXPR = 0, AND_EXPR, OR_EXPR, NOT_EXPR, UNIT_EXPR };
-const char* expr_type_name(ExprType t);
-
-struct TagInfo { std::string Name, FieldPath; };            // expression.go:39-42
-
-struct Expression {                                         // expression.go:46-51
-    std::unique_ptr<Expression> LExpr, RExpr;
-    ExprType Type = UNSET_EXPR;
-    TagInfo Tag;
-    mutable int32_t tag_id = -1;                            // batch evaluation: index of Tag.Name among the finder's tags
-};
-
-struct ScanResult { Token tok = ILLEGAL; std::string lit; std::string err; };
-
-class Scanner {                                             // scanner.go:67-263
-public:
-    explicit Scanner(const std::string& src) : s_(src) {}
-    ScanResult Scan();
-private:
-    int32_t read();
-    void unread();
-    ScanResult scan_whitespace();
-    ScanResult scan_operators();
-    ScanResult scan_tag();
-    ScanResult scan_field_path();
-    const std::string& s_;
-    size_t i_ = 0, last_ = 0;
-};
-
-struct ParseResult {
-    std::unique_ptr<Expression> expr;      // null on error
-    std::vector<std::string> tags, fields; // unique, first-seen order (GetTags / GetFields, parser.go:281-297)
-    std::string err;
-};
-ParseResult Parse(const std::string& src);                  // parser.go:35-175
-
-// tag -> field path -> set of expression strings (the reference's map[string]map[string]map[string]struct{})
-using TagMap = std::map<std::string, std::map<std::string, std::set<std::string>>>;
-
-// Expression.Solve (expression.go:61-125); err = "" when fine
-bool Solve(const Expression& e, const TagMap& m, std::string& err);
-
-// the same recursion over a caller-supplied UNIT predicate (batch evaluation keeps tags as ids, not map keys)
-template <class UnitPred>
-bool SolveWith(const Expression& e, UnitPred&& unit, std::string& err) {
-    switch (e.Type) {
-    case UNIT_EXPR:
-        return unit(e);
-    case AND_EXPR:
-    case OR_EXPR: {
-        if (!e.LExpr || !e.RExpr) {
-            err = std::string(e.Type == AND_EXPR ? "AND" : "OR") + " statement do not have right or left expression";
-            return false;
-        }
-        const bool l = SolveWith(*e.LExpr, unit, err);
-        if (!err.empty()) return false;
-        const bool r = SolveWith(*e.RExpr, unit, err);
-        if (!err.empty()) return false;
-        return e.Type == AND_EXPR ? (l && r) : (l || r);
-    }
-    case NOT_EXPR: {
-        if (!e.RExpr) { err = "NOT statement do not have expression"; return false; }
-        const bool r = SolveWith(*e.RExpr, unit, err);
-        if (!err.empty()) return false;
-        return !r;
-    }
-    default:
-        err = "unable to process expression type " + std::to_string((int)e.Type);
-        return false;
-    }
-}
-
-std::string ToJson(const Expression& e);                    // {"Type":"AND","LExpr":..,"RExpr":..} / {"Type":"UNIT","Tag":{..}}
-
-}  // namespace gdsl
 
 // group/finder/finder.go:12-17
 class GroupFinder {
 public:
-    struct ExpressionWrapper { std::string ExpressionString; std::unique_ptr<gdsl::Expression> Expression; };
+    using ExpressionWrapper = gft::ExpressionWrapper;
     using RuleResult = std::map<std::string, std::vector<std::string>>;   // expressionsByRule
 
     explicit GroupFinder(Finder* findthem) : findthem_(findthem) {}
@@ -173,7 +93,7 @@ public:
     int DebugEvalRulesDevice(const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
                              uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err);
 
-    const std::map<std::string, std::vector<ExpressionWrapper>>& rules() const { return rules_; }
+    const RuleMap& rules() const { return rules_; }
     const std::set<std::string>& fields() const { return fields_; }
     const std::set<std::string>& tags() const { return tags_; }
     // leaves and bytes of the last TagJsons call (measurement)
@@ -181,30 +101,43 @@ public:
 
 private:
     Finder* findthem_;
-    std::map<std::string, std::vector<ExpressionWrapper>> rules_;
+    RuleMap rules_;
     std::set<std::string> fields_, tags_;
 
-    struct Records;                        // schema, compiled RuleSet and what it was compiled from (group_host.cpp)
-    std::shared_ptr<Records> rec_;
-    std::shared_ptr<Records> auto_;        // ProcessJsonsAuto's: stands in for rec_ while that call runs (UseAuto)
-    struct UseAuto;
-    // ProcessJsonsSchema behind the upload, for whichever schema rec_ is.  Under the caller's RulesLock: ProcessJsonsDevice over
-    // the staged batch, status and rows down ...
-    int json_staged_rows(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rows,
-                         std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err);
-    // ... and behind it: the documents the device did not decide through ProcessJsons as one sub-batch, the others from their rows
-    int json_results(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
-                     const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err);
     uint64_t rules_version_ = 0;           // counts AddRule calls that changed rules_
     std::vector<RuleExpr> rule_exprs_;
     uint64_t rule_exprs_version_ = ~0ull;
-    int compile_current(Error& err);       // the set for the stored schema, redone when rules / finder expressions changed
-    int install_current(gft_engine* e, Error& err);
-    int json_current(gft_engine* e, Error& err);   // the schema's trie, refused or installed on e (e == nullptr: checked only)
-};
 
-// isValidateFieldPath (internal.go:99-119)
-bool IsValidFieldPath(const std::string& fieldPath, const std::vector<std::string>& includePaths,
-                      const std::vector<std::string>& excludePaths);
+    // ---- a schema with what was compiled from it (group_records.hpp).  Every helper names the Records it works on: rec_ is
+    // SetSchema's, auto_ the one ProcessJsonsAuto keeps between its calls, and neither route touches the other's.
+    struct Records;
+    std::shared_ptr<Records> rec_, auto_;
+    Records* schema_records(const char* what, Error& err);   // rec_, or "<what>: no schema set (gft_group_set_schema)"
+    // the one way to a Records: the rule set (compile_set), then the trie into json / json_rc / json_err.  Returns the rule
+    // compiler's status; what a refused trie means is the caller's to say
+    int make_records(const std::vector<std::string>& paths, const std::vector<std::string>& includePaths,
+                     const std::vector<std::string>& excludePaths, Records& out, Error& err);
+    int compile_set(Records& r, Error& err);               // r.set from r's schema and lists, stamped; untouched on a refusal
+    int compile(Records& r, Error& err);                   // ... when rules or finder expressions were added since
+    int install(gft_engine* e, Records& r, Error& err);    // r.set on the engine, unless it is the one the engine holds
+    int json_ready(gft_engine* e, Records& r, Error& err); // r's trie: refused, or installed on e (e == nullptr: checked only)
+    int records_device(Records& r, const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                       uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err);          // ProcessRecordsDevice
+    int jsons_device(Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
+                     Error& err);                                                                            // ProcessJsonsDevice
+    // ---- a JSON batch from host memory, for ProcessJsonsSchema and ProcessJsonsAuto: a finder that does not qualify sends it
+    // through ProcessJsons (with the lists given); else the batch is uploaded with rows of row_words words and, under the
+    // engine's lock, `choose` names the Records that answer it -- null with rc == 0: ProcessJsons after all.
+    using ChooseRecords = std::function<std::shared_ptr<Records>(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc)>;
+    int json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                   const std::vector<std::string>& excludePaths, uint64_t row_words, const ChooseRecords& choose, std::vector<DocResult>& out,
+                   Error& err);
+    // under the caller's RulesLock: jsons_device over the staged batch, status and rows down ...
+    int json_staged_rows(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                         uint32_t* d_rows, std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err);
+    // ... and behind it: the documents the device did not decide through ProcessJsons as one sub-batch, the others from their rows
+    int json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                     const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err);
+};
 
 }  // namespace gft

@@ -1,0 +1,235 @@
+// group_json.cpp -- the group finder's JSON routes on the device (json_schema.hpp, gft_json.hip): documents decoded into the
+// record form against a schema's trie and sent down the record route (group_records.cpp), for the schema of SetSchema and for
+// the one discovered from the batch (json_paths.hpp: k_json_paths).
+#include <cstring>
+#include <set>
+
+#include "group_records.hpp"
+#include "host_parallel.hpp"
+#include "json_paths.hpp"
+
+namespace gft {
+
+int GroupFinder::json_ready(gft_engine* e, Records& r, Error& err) {
+    if (r.json_rc) { err = r.json_err; return r.json_rc; }
+    if (!e || (r.json_serial && json_serial(e) == r.json_serial)) return GFT_OK;
+    int rc = json_install(e, r.json, &r.json_serial);
+    if (rc) { r.json_serial = 0; err = gft_last_error(e); }
+    return rc;
+}
+
+int GroupFinder::JsonLeavesDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint64_t* d_rec_off,
+                                  uint32_t* d_leaf_field, uint64_t* d_leaf_off, uint64_t leaf_cap, uint8_t* d_text, uint64_t text_cap,
+                                  uint64_t* totals, Error& err) {
+    Records* r = schema_records("JSON batch", err);
+    if (!r) return GFT_E_INVALID;
+    int rc = json_ready(nullptr, *r, err);
+    if (rc) return rc;
+    gft_engine* e = nullptr;
+    if ((rc = single_device_engine(findthem_, "JSON batches", e, err))) return rc;
+    RulesLock whole_call(e);               // (another group on the same finder installs its own trie)
+    if ((rc = json_ready(e, *r, err))) return rc;
+    if ((rc = json_leaves_device(e, d_blob, d_doc_off, n_docs, d_status, d_rec_off, d_leaf_field, d_leaf_off, leaf_cap, d_text, text_cap, totals)))
+        err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::ProcessJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
+                                    Error& err) {
+    Records* r = schema_records("JSON batch", err);
+    return r ? jsons_device(*r, d_blob, d_doc_off, n_docs, d_status, d_rule_bitmap, err) : GFT_E_INVALID;
+}
+
+int GroupFinder::jsons_device(Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                              uint32_t* d_rule_bitmap, Error& err) {
+    int rc = json_ready(nullptr, r, err);
+    if (rc) return rc;
+    if ((rc = compile(r, err))) return rc;
+    if (!findthem_->device_resident_ok()) { err = "device-resident JSON batches need the GPU substring engine and no regex terms"; return GFT_E_UNSUPPORTED; }
+    gft_engine* e = nullptr;
+    if ((rc = single_device_engine(findthem_, "JSON batches", e, err))) return rc;
+    RulesLock whole_call(e);
+    if ((rc = json_ready(e, r, err))) return rc;
+    const uint64_t* d_rec_off = nullptr; const uint32_t* d_leaf_field = nullptr; const uint64_t* d_leaf_off = nullptr; const uint8_t* d_text = nullptr;
+    uint64_t totals[2] = {0, 0};
+    if ((rc = json_leaves_owned(e, d_blob, d_doc_off, n_docs, d_status, &d_rec_off, &d_leaf_field, &d_leaf_off, &d_text, totals))) {
+        err = gft_last_error(e);
+        return rc;
+    }
+    last_leaves = totals[0];
+    last_bytes = totals[1];
+    return records_device(r, d_text, d_leaf_off, d_leaf_field, d_rec_off, n_docs, totals[0], d_rule_bitmap, err);
+}
+
+int GroupFinder::json_staged_rows(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                                  uint32_t* d_rows, std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err) {
+    const uint64_t RW = r.row_words();
+    status.assign(n_docs, 0);
+    rows.assign((size_t)(n_docs * RW) + 1, 0);
+    int rc = jsons_device(r, d_blob, d_doc_off, n_docs, d_status, d_rows, err);
+    if (rc) return rc;
+    if ((rc = rules_fetch(e, status.data(), d_status, n_docs)) || (rc = rules_fetch(e, rows.data(), d_rows, n_docs * RW * 4))) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                              const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err) {
+    const uint64_t RW = r.row_words();
+    // what the device did not decide: one sub-batch through the host route
+    std::vector<uint64_t> host_docs;
+    for (uint64_t d = 0; d < n_docs; d++)
+        if (status[d]) host_docs.push_back(d);
+    if (!host_docs.empty()) {
+        std::vector<uint64_t> off(host_docs.size() + 1, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) off[k + 1] = off[k] + (doc_off[host_docs[k] + 1] - doc_off[host_docs[k]]);
+        std::vector<uint8_t> sub(off.back() + 64, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) memcpy(sub.data() + off[k], blob + doc_off[host_docs[k]], (size_t)(off[k + 1] - off[k]));
+        std::vector<DocResult> res;
+        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), r.inc, r.exc, false, res);
+        if (!err.empty()) return GFT_E_ENGINE;
+        for (size_t k = 0; k < host_docs.size(); k++) out[host_docs[k]] = std::move(res[k]);
+    }
+    const auto& names = RuleExprs();
+    parallel_for(n_docs, [&](uint64_t d, unsigned) {
+        if (status[d]) return;
+        const uint32_t* row = rows.data() + d * RW;
+        for (uint32_t w = 0; w < RW; w++)
+            for (uint32_t bits = row[w]; bits; bits &= bits - 1) {
+                const RuleExpr& re = names[w * 32 + (uint32_t)__builtin_ctz(bits)];
+                out[d].rules[*re.name].push_back(*re.expr);
+            }
+    });
+    json_last_host = host_docs.size();
+    json_last_device = n_docs - host_docs.size();
+    return GFT_OK;
+}
+
+int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                            const std::vector<std::string>& excludePaths, uint64_t row_words, const ChooseRecords& choose,
+                            std::vector<DocResult>& out, Error& err) {
+    gft_engine* e = findthem_->device_engine();
+    json_last_device = json_last_host = 0;
+    auto by_host = [&]() {
+        err = ProcessJsons(blob, doc_off, n_docs, includePaths, excludePaths, false, out);
+        json_last_host = n_docs;
+        return err.empty() ? GFT_OK : GFT_E_ENGINE;
+    };
+    // regex terms, injected engines, several devices: the walk on host threads, for every document
+    if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) return by_host();
+    out.assign(n_docs, DocResult());
+    if (!n_docs) return GFT_OK;
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> rows;
+    std::shared_ptr<Records> r;            // (held to the end: the call's own, whatever becomes of the member it came from)
+    {
+        RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
+        const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
+        int rc = json_stage(e, blob, doc_off, n_docs, row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows);
+        if (rc) { err = gft_last_error(e); return rc; }
+        r = choose(e, d_blob, d_doc_off, rc);
+        if (rc) return rc;
+        if (r && (rc = json_staged_rows(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, status, rows, err))) return rc;
+    }
+    if (!r) return by_host();
+    return json_results(*r, blob, doc_off, n_docs, status, rows, out, err);
+}
+
+int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
+    Records* r = schema_records("JSON batch", err);
+    if (!r) return GFT_E_INVALID;
+    int rc = json_ready(nullptr, *r, err);
+    if (rc) return rc;
+    if ((rc = compile(*r, err))) return rc;
+    if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
+    // (the schema's own lists; it is compiled already, whatever the batch holds)
+    return json_batch(blob, doc_off, n_docs, r->inc, r->exc, r->row_words(), [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; },
+                      out, err);
+}
+
+// ---- the schema discovered from the batch ------------------------------------------------------------------------------------
+int GroupFinder::JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths,
+                                 uint64_t* dropped, Error& err) {
+    gft_engine* e = nullptr;
+    int rc = single_device_engine(findthem_, "JSON batches", e, err);
+    if (rc) return rc;
+    RulesLock whole_call(e);               // (the set and the pool are the engine's)
+    rc = json_paths_device(e, d_blob, d_doc_off, n_docs, paths, dropped);
+    if (rc) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                                  const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err) {
+    int rc = json_check_offsets(doc_off, n_docs, err);
+    if (rc) return rc;
+    auto_last_paths = auto_last_dropped = auto_last_recompiled = 0;
+    const uint64_t RW = (RuleExprs().size() + 31) / 32;      // (a bit per rule expression, whatever the schema)
+    // auto_ for the staged batch, or null: a limit of the schema's compilers, the host route for every document
+    auto discover = [&](gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc) -> std::shared_ptr<Records> {
+        std::vector<std::string> found;
+        if ((rc = json_paths_device(e, d_blob, d_doc_off, n_docs, found, &auto_last_dropped))) { err = gft_last_error(e); return nullptr; }
+        auto_last_paths = found.size();
+        // the kept schema answers when it covers the batch and was made for these lists
+        const bool same_lists = auto_ && auto_->inc == includePaths && auto_->exc == excludePaths;
+        bool covered = same_lists;
+        if (covered) {
+            const std::set<std::string> kept(auto_->schema.begin(), auto_->schema.end());
+            for (const auto& p : found) covered = covered && kept.count(p);
+        }
+        if (!covered) {
+            // what was kept stays in when the whole still compiles, so that batches of alternating shapes settle
+            std::vector<std::vector<std::string>> tries;
+            if (same_lists) {
+                std::set<std::string> all(auto_->schema.begin(), auto_->schema.end());
+                all.insert(found.begin(), found.end());
+                if (all.size() <= kJsonPathCap) tries.emplace_back(all.begin(), all.end());
+            }
+            tries.push_back(found);
+            std::shared_ptr<Records> next;
+            for (const auto& paths : tries) {
+                auto r = std::make_shared<Records>();
+                Error why;
+                rc = make_records(paths, includePaths, excludePaths, *r, why);
+                if (!rc) rc = r->json_rc;                      // (here a schema without a trie is no schema)
+                if (rc == GFT_E_UNSUPPORTED) continue;         // a limit: never the caller's error
+                if (rc) { err = why.empty() ? r->json_err : why; return nullptr; }
+                next = std::move(r);
+                break;
+            }
+            rc = GFT_OK;
+            auto_last_recompiled = 1;
+            if (!next) return nullptr;
+            auto_ = std::move(next);
+        } else if (auto_->rules_version != rules_version_ || auto_->n_exprs != findthem_->expressions().size()) {
+            auto_last_recompiled = 1;      // (compile, below)
+        }
+        rc = compile(*auto_, err);                             // (rules or expressions were added since)
+        if (rc == GFT_E_UNSUPPORTED) { err.clear(); rc = GFT_OK; auto_.reset(); return nullptr; }   // (its rules no longer compile)
+        if (rc) return nullptr;
+        if (auto_->row_words() != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; rc = GFT_E_INTERNAL; return nullptr; }
+        return auto_;
+    };
+    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, RW, discover, out, err);
+}
+
+int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {
+    if (field) *field = -1;
+    if (!rec_ || rec_->json_rc || parent < 0 || parent >= (int64_t)rec_->json.nodes.size() || (key_len && !key)) return -1;
+    const uint32_t c = key_len ? json_schema_find(rec_->json, (uint32_t)parent, key, key_len) : (uint32_t)parent;
+    if (c == kJsonNone) return -1;
+    if (field && rec_->json.nodes[c].field != kJsonNone) *field = rec_->json.nodes[c].field;
+    return c;
+}
+
+int GroupFinder::DebugJsonLeaves(bool emulate, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* status, uint64_t* rec_off,
+                                 uint32_t* leaf_field, uint64_t* leaf_off, uint64_t leaf_cap, uint8_t* text, uint64_t text_cap, uint64_t* totals,
+                                 Error& err) {
+    Records* r = schema_records("JSON batch", err);
+    if (!r) return GFT_E_INVALID;
+    int rc = json_ready(nullptr, *r, err);
+    if (rc) return rc;
+    const JsonLeavesOut out{status, rec_off, leaf_field, leaf_off, leaf_cap, text, text_cap, totals};
+    return emulate ? json_leaves_emulate(r->json, blob, doc_off, n_docs, out, err) : json_leaves_ref(r->schema, blob, doc_off, n_docs, out, err);
+}
+
+}  // namespace gft

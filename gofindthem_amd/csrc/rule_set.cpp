@@ -82,7 +82,7 @@ inline bool bit(const uint32_t* row, uint32_t i) { return row[i >> 5] >> (i & 31
 
 }  // namespace
 
-int compile_rules(const std::map<std::string, std::vector<GroupFinder::ExpressionWrapper>>& rules, const std::vector<std::string>& tags,
+int compile_rules(const RuleMap& rules, const std::vector<std::string>& tags,
                   const std::vector<uint32_t>& expr_tag, const std::vector<std::string>& schema,
                   const std::vector<std::string>& includePaths, const std::vector<std::string>& excludePaths, RuleSet& out, std::string& err) {
     if (schema.size() > kRuleMaxFields) {

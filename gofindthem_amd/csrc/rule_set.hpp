@@ -6,10 +6,12 @@
 // comes out, eval_rules_host interprets the same words on the CPU.
 #pragma once
 #include <cstdint>
+#include <map>
 #include <string>
 #include <vector>
 
-#include "group_host.hpp"
+#include "../../include/gft.h"
+#include "group_dsl.hpp"
 #include "rule_words.hpp"
 
 namespace gft {
@@ -33,7 +35,7 @@ struct RuleSet {
 // Compiles a whole set.  GFT_OK, or the status of the first refusal with its text in `err` -- `out` is then untouched.
 // rules: GroupFinder::rules() (ascending rule name, AddRule order inside a name); tags / expr_tag: Finder::tags() /
 // Finder::tag_ids(); schema: unique field paths as getRulesInfo builds them.
-int compile_rules(const std::map<std::string, std::vector<GroupFinder::ExpressionWrapper>>& rules, const std::vector<std::string>& tags,
+int compile_rules(const RuleMap& rules, const std::vector<std::string>& tags,
                   const std::vector<uint32_t>& expr_tag, const std::vector<std::string>& schema,
                   const std::vector<std::string>& includePaths, const std::vector<std::string>& excludePaths, RuleSet& out, std::string& err);
 

@@ -1,7 +1,7 @@
 """oracle/group_ref.py -- TEST INFRASTRUCTURE, NOT PRODUCT CODE.
 
 Pure-Python restatement of the reference's group package, the checker for
-gofindthem_amd/csrc/group_host.cpp.  Plain Python loops: rule sets and objects are small.
+gofindthem_amd/csrc/group_dsl.cpp and group_host.cpp.  Plain Python loops: rule sets and objects are small.
 
 Follows, statement by statement (paths relative to /root/reference):
   * group/dsl/scanner.go:12-263     tokens, Scan, scanWhitespace, scanOperators, scanTag, scanFieldPath

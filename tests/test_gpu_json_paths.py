@@ -292,6 +292,26 @@ def test_the_two_schemas_do_not_disturb_each_other():
     assert sum(1 for r in want_docs if r.get("rules")) > 10
 
 
+def test_two_groups_on_one_finder_take_turns_with_json_batches():
+    """one group with a schema, one that discovers its own, other rules, one engine: every call finds the other group's set and
+    trie installed and puts its own back"""
+    rng = np.random.default_rng(9)
+    schema, shape = R.make_schema(8), R.make_schema(16)[8:]
+    exprs, tags = R.make_expressions(40, 5, rng)
+    g = make_group(exprs, tags, R.make_rules(20, 5, schema, rng))
+    g.SetSchema(schema)
+    g2 = group.NewFinderWithRules(g.findthem, R.make_rules(12, 5, shape, rng))
+    V = R.vocabulary()
+    mine = [J.gen_doc(schema, rng, V) for _ in range(100)]
+    other = [J.gen_doc(shape, rng, V) for _ in range(50)]
+    want, want2 = g.ProcessJsons(mine), g2.ProcessJsons(other)
+    for turn in range(3):
+        assert g.ProcessJsonsSchema(mine) == want and g.json_last() == (100, 0)
+        assert g2.ProcessJsonsAuto(other) == want2 and g2.json_last() == (50, 0)
+        assert g2.json_auto_last()[2] == (1 if turn == 0 else 0)
+    assert min(sum(1 for r in res if r.get("rules")) for res in (want, want2)) > 10
+
+
 def test_recompilation():
     g, _, _ = nested_config(2)
     V = R.vocabulary()
