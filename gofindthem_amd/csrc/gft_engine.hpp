@@ -184,7 +184,14 @@ struct gft_engine {
         uint64_t serial = 0;               // 0: none installed
         uint32_t n_fields = 0, n_tags = 0, n_exprs = 0, n_rules = 0, n_units = 0, max_depth = 0, field_words = 0;
         DevBuf expr_tag, masks, units, prog, prog_off, leaf_bitmap, tag_rows, flags, stage[6];
+        DevBuf valid;                      // [field_words] the set's validity mask (gft_tags.hip)
     } d_rules;
+
+    // tag entries of a record batch (gft_tags.hip): counts, leaf offsets, scan partials and flag words of their own -- apart from
+    // the compaction's scratch and the rule kernels' buffers --, and the arrays of the owned form (rules_tag_entries_owned)
+    struct TagBufs {
+        DevBuf cnt, leaf_ent_off, partial, flags, row_off, ent_field, ent_expr;
+    } d_tags;
 
     // JSON documents decoded on the device (gft_json.hip): the installed schema trie, the counts and prefix sums of a batch, the
     // record arrays of gft_group_process_jsons_device, staging for the host-pointer entry point

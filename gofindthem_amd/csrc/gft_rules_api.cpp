@@ -41,6 +41,7 @@ int rules_install(gft_engine* e, const RuleSet& rs, uint64_t* serial) try {
     if ((rc = upload(e, R.units, rs.units, "rule set upload"))) return rc;
     if ((rc = upload(e, R.prog, rs.prog, "rule set upload"))) return rc;
     if ((rc = upload(e, R.prog_off, rs.prog_off, "rule set upload"))) return rc;
+    if ((rc = upload(e, R.valid, rs.valid, "rule set upload"))) return rc;
     HIP_TRY(R.flags.ensure(16), "rule set upload");
     HIP_TRY(hipStreamSynchronize(e->stream), "rule set upload");
     R.n_fields = rs.n_fields; R.n_tags = rs.n_tags; R.n_exprs = rs.n_exprs; R.n_rules = rs.n_rules;

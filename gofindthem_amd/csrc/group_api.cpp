@@ -397,6 +397,74 @@ int gft_debug_eval_rules_device(gft_group* g, const uint32_t* d_hit_bitmap, uint
     return g->g->DebugEvalRulesDevice(d_hit_bitmap, n_exprs, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap, g->err);
 } GFT_CATCH((g ? &g->err : nullptr))
 
+int gft_group_tag_records_device(gft_group* g, const uint8_t* d_text_blob, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field,
+                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint64_t* d_row_off, uint32_t* d_ent_field,
+                                 uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->TagRecordsDevice(d_text_blob, d_leaf_off, d_leaf_field, d_rec_off, n_records, n_leaves,
+                                  {d_row_off, d_ent_field, d_ent_expr, d_ent_tag, cap, total}, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_tag_records(gft_group* g, const uint8_t* text_blob, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off,
+                          uint64_t n_records, uint64_t n_leaves, uint64_t* row_off, uint32_t* ent_field, uint32_t* ent_expr, uint32_t* ent_tag,
+                          uint64_t cap, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->TagRecords(text_blob, leaf_off, leaf_field, rec_off, n_records, n_leaves, {row_off, ent_field, ent_expr, ent_tag, cap, total}, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_tag_jsons_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                               uint64_t* d_row_off, uint32_t* d_ent_field, uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap,
+                               uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->TagJsonsDevice(d_json_blob, d_doc_off, n_docs, d_status, {d_row_off, d_ent_field, d_ent_expr, d_ent_tag, cap, total}, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_tag_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
+                               uint64_t* needed) try {
+    if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<GroupFinder::DocResult> res;
+    int rc = g->g->TagJsonsSchema(json_blob, doc_off, n_docs, res, g->err);
+    if (rc) return rc;
+    result_document(g, res, 1);
+    return put(g->result, out, cap, needed);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_tag_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* include_json,
+                             uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap,
+                             uint64_t* needed) try {
+    if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> inc, exc;
+    if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
+    std::vector<GroupFinder::DocResult> res;
+    int rc = g->g->TagJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err);
+    if (rc) return rc;
+    result_document(g, res, 1);
+    return put(g->result, out, cap, needed);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_tag_entries(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                          uint64_t n_records, uint64_t n_leaves, uint64_t* row_off, uint32_t* ent_field, uint32_t* ent_expr, uint32_t* ent_tag,
+                          uint64_t cap, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugTagEntries(hit_bitmap, n_exprs, leaf_field, rec_off, n_records, n_leaves, {row_off, ent_field, ent_expr, ent_tag, cap, total},
+                                 g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_tag_entries_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
+                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint64_t* d_row_off, uint32_t* d_ent_field,
+                                 uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugTagEntriesDevice(d_hit_bitmap, n_exprs, d_leaf_field, d_rec_off, n_records, n_leaves,
+                                       {d_row_off, d_ent_field, d_ent_expr, d_ent_tag, cap, total}, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
 int gft_group_last_batch(const gft_group* g, uint64_t* leaves, uint64_t* bytes) try {
     if (!g) return GFT_E_INVALID;
     GFT_GLOCK(g);

@@ -84,6 +84,28 @@ public:
     // documents of the last ProcessJsonsSchema / ProcessJsonsAuto batch decided on the device / handed to ProcessJsons
     uint64_t json_last_device = 0, json_last_host = 0;
 
+    // ---- tag entries: TagObject's map of every record as a sparse list of (field, expression) pairs (gft_tags.hip, include/gft.h).
+    // The arrays of one result; device pointers in the *Device calls (total is always host memory)
+    struct TagEntries { uint64_t* row_off; uint32_t* ent_field; uint32_t* ent_expr; uint32_t* ent_tag; uint64_t cap; uint64_t* total; };
+    // device pointers; the leaves go through Finder::ProcessDevice into the engine's leaf bitmap, then the three launches
+    int TagRecordsDevice(const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                         uint64_t n_records, uint64_t n_leaves, const TagEntries& d_out, Error& err);
+    // host pointers: upload + the call above + the arrays down when the finder qualifies, else Finder::ProcessTexts and
+    // tag_entries_host; both routes give the same arrays
+    int TagRecords(const uint8_t* text, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
+                   uint64_t n_leaves, const TagEntries& out, Error& err);
+    // device pointers: JsonLeavesDevice into engine-owned arrays, then TagRecordsDevice; a document with status != 0 has an empty row
+    int TagJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, const TagEntries& d_out, Error& err);
+    // ProcessJsonsSchema / ProcessJsonsAuto for tags: out as ProcessJsons with want_tags = true
+    int TagJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err);
+    int TagJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                     const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err);
+    // tag_entries_host, and the three launches, over a caller-supplied leaf bitmap (host / device pointers)
+    int DebugTagEntries(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
+                        uint64_t n_leaves, const TagEntries& out, Error& err);
+    int DebugTagEntriesDevice(const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                              uint64_t n_records, uint64_t n_leaves, const TagEntries& d_out, Error& err);
+
     // the compiled device words interpreted on the host over a caller-supplied leaf bitmap: no device
     int DebugEvalRules(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
                        uint64_t n_leaves, uint32_t* rule_bitmap, Error& err);
@@ -121,23 +143,32 @@ private:
     int compile(Records& r, Error& err);                   // ... when rules or finder expressions were added since
     int install(gft_engine* e, Records& r, Error& err);    // r.set on the engine, unless it is the one the engine holds
     int json_ready(gft_engine* e, Records& r, Error& err); // r's trie: refused, or installed on e (e == nullptr: checked only)
+    // What a device call over records is to produce (group_records.hpp): rule rows, or tag entries
+    struct RecordsOut;
     int records_device(Records& r, const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
-                       uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err);          // ProcessRecordsDevice
-    int jsons_device(Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
-                     Error& err);                                                                            // ProcessJsonsDevice
-    // ---- a JSON batch from host memory, for ProcessJsonsSchema and ProcessJsonsAuto: a finder that does not qualify sends it
-    // through ProcessJsons (with the lists given); else the batch is uploaded with rows of row_words words and, under the
-    // engine's lock, `choose` names the Records that answer it -- null with rc == 0: ProcessJsons after all.
+                       uint64_t n_records, uint64_t n_leaves, const RecordsOut& out, Error& err);    // ProcessRecordsDevice, TagRecordsDevice
+    int jsons_device(Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, const RecordsOut& out,
+                     Error& err);                                                                    // ProcessJsonsDevice, TagJsonsDevice
+    // ---- a JSON batch from host memory, for ProcessJsonsSchema / ProcessJsonsAuto (want_tags == false: rule rows) and
+    // TagJsonsSchema / TagJsonsAuto (want_tags == true: tag entries): a finder that does not qualify sends it through ProcessJsons
+    // (with the lists given); else the batch is uploaded (rule rows: with rows of row_words words) and, under the engine's lock,
+    // `choose` names the Records that answer it -- null with rc == 0: ProcessJsons after all.
     using ChooseRecords = std::function<std::shared_ptr<Records>(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc)>;
     int json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                   const std::vector<std::string>& excludePaths, uint64_t row_words, const ChooseRecords& choose, std::vector<DocResult>& out,
-                   Error& err);
-    // under the caller's RulesLock: jsons_device over the staged batch, status and rows down ...
-    int json_staged_rows(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
-                         uint32_t* d_rows, std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err);
+                   const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
+                   std::vector<DocResult>& out, Error& err);
+    // what came down from the device for a staged batch: the status bytes, and the rule rows or the tag entries
+    struct JsonStaged;
+    // under the caller's RulesLock: jsons_device over the staged batch, status and rows / entries down ...
+    int json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                    uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err);
     // ... and behind it: the documents the device did not decide through ProcessJsons as one sub-batch, the others from their rows
-    int json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
-                     const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err);
+    // or entries, a document per task
+    int json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const JsonStaged& s, bool want_tags,
+                     std::vector<DocResult>& out, Error& err);
+    int jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err);
+    int jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                   const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err);
 };
 
 }  // namespace gft

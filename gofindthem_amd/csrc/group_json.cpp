@@ -37,11 +37,13 @@ int GroupFinder::JsonLeavesDevice(const uint8_t* d_blob, const uint64_t* d_doc_o
 int GroupFinder::ProcessJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, uint32_t* d_rule_bitmap,
                                     Error& err) {
     Records* r = schema_records("JSON batch", err);
-    return r ? jsons_device(*r, d_blob, d_doc_off, n_docs, d_status, d_rule_bitmap, err) : GFT_E_INVALID;
+    RecordsOut out;
+    out.d_rule_bitmap = d_rule_bitmap;
+    return r ? jsons_device(*r, d_blob, d_doc_off, n_docs, d_status, out, err) : GFT_E_INVALID;
 }
 
 int GroupFinder::jsons_device(Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
-                              uint32_t* d_rule_bitmap, Error& err) {
+                              const RecordsOut& out, Error& err) {
     int rc = json_ready(nullptr, r, err);
     if (rc) return rc;
     if ((rc = compile(r, err))) return rc;
@@ -58,23 +60,42 @@ int GroupFinder::jsons_device(Records& r, const uint8_t* d_blob, const uint64_t*
     }
     last_leaves = totals[0];
     last_bytes = totals[1];
-    return records_device(r, d_text, d_leaf_off, d_leaf_field, d_rec_off, n_docs, totals[0], d_rule_bitmap, err);
+    return records_device(r, d_text, d_leaf_off, d_leaf_field, d_rec_off, n_docs, totals[0], out, err);
 }
 
-int GroupFinder::json_staged_rows(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
-                                  uint32_t* d_rows, std::vector<uint8_t>& status, std::vector<uint32_t>& rows, Error& err) {
+int GroupFinder::json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                             uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err) {
+    s.status.assign(n_docs, 0);
+    RecordsOut out;
+    RecordsOut::Owned own;
     const uint64_t RW = r.row_words();
-    status.assign(n_docs, 0);
-    rows.assign((size_t)(n_docs * RW) + 1, 0);
-    int rc = jsons_device(r, d_blob, d_doc_off, n_docs, d_status, d_rows, err);
+    if (want_tags) {
+        out.owned = &own;
+    } else {
+        s.rows.assign((size_t)(n_docs * RW) + 1, 0);
+        out.d_rule_bitmap = d_rows;
+    }
+    int rc = jsons_device(r, d_blob, d_doc_off, n_docs, d_status, out, err);
     if (rc) return rc;
-    if ((rc = rules_fetch(e, status.data(), d_status, n_docs)) || (rc = rules_fetch(e, rows.data(), d_rows, n_docs * RW * 4))) err = gft_last_error(e);
+    if ((rc = rules_fetch(e, s.status.data(), d_status, n_docs))) { err = gft_last_error(e); return rc; }
+    if (want_tags) {
+        // only the sparse result crosses the link: the offsets and the two entry columns (the tag is the expression's)
+        s.row_off.assign(n_docs + 1, 0);
+        s.ent_field.assign((size_t)own.total + 1, 0);
+        s.ent_expr.assign((size_t)own.total + 1, 0);
+        if ((rc = rules_fetch(e, s.row_off.data(), own.row_off, (n_docs + 1) * 8)) || (rc = rules_fetch(e, s.ent_field.data(), own.ent_field, own.total * 4)) ||
+            (rc = rules_fetch(e, s.ent_expr.data(), own.ent_expr, own.total * 4)))
+            err = gft_last_error(e);
+    } else if ((rc = rules_fetch(e, s.rows.data(), d_rows, n_docs * RW * 4))) {
+        err = gft_last_error(e);
+    }
     return rc;
 }
 
-int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
-                              const std::vector<uint32_t>& rows, std::vector<DocResult>& out, Error& err) {
+int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const JsonStaged& s, bool want_tags,
+                              std::vector<DocResult>& out, Error& err) {
     const uint64_t RW = r.row_words();
+    const std::vector<uint8_t>& status = s.status;
     // what the device did not decide: one sub-batch through the host route
     std::vector<uint64_t> host_docs;
     for (uint64_t d = 0; d < n_docs; d++)
@@ -85,10 +106,25 @@ int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint6
         std::vector<uint8_t> sub(off.back() + 64, 0);
         for (size_t k = 0; k < host_docs.size(); k++) memcpy(sub.data() + off[k], blob + doc_off[host_docs[k]], (size_t)(off[k + 1] - off[k]));
         std::vector<DocResult> res;
-        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), r.inc, r.exc, false, res);
+        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), r.inc, r.exc, want_tags, res);
         if (!err.empty()) return GFT_E_ENGINE;
         for (size_t k = 0; k < host_docs.size(); k++) out[host_docs[k]] = std::move(res[k]);
     }
+    json_last_host = host_docs.size();
+    json_last_device = n_docs - host_docs.size();
+    if (want_tags) {
+        // a document's entries -> its tag map; the set's insert drops what a repeated field says twice
+        const auto& exprs = findthem_->expressions();
+        parallel_for(n_docs, [&](uint64_t d, unsigned) {
+            if (status[d]) return;
+            for (uint64_t k = s.row_off[d]; k < s.row_off[d + 1]; k++) {
+                const auto& x = exprs[s.ent_expr[k]];
+                out[d].tags[x.tag][r.schema[s.ent_field[k]]].insert(x.exprString);
+            }
+        });
+        return GFT_OK;
+    }
+    const std::vector<uint32_t>& rows = s.rows;
     const auto& names = RuleExprs();
     parallel_for(n_docs, [&](uint64_t d, unsigned) {
         if (status[d]) return;
@@ -99,18 +135,16 @@ int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint6
                 out[d].rules[*re.name].push_back(*re.expr);
             }
     });
-    json_last_host = host_docs.size();
-    json_last_device = n_docs - host_docs.size();
     return GFT_OK;
 }
 
 int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                            const std::vector<std::string>& excludePaths, uint64_t row_words, const ChooseRecords& choose,
+                            const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
                             std::vector<DocResult>& out, Error& err) {
     gft_engine* e = findthem_->device_engine();
     json_last_device = json_last_host = 0;
     auto by_host = [&]() {
-        err = ProcessJsons(blob, doc_off, n_docs, includePaths, excludePaths, false, out);
+        err = ProcessJsons(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, out);
         json_last_host = n_docs;
         return err.empty() ? GFT_OK : GFT_E_ENGINE;
     };
@@ -118,23 +152,26 @@ int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64
     if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) return by_host();
     out.assign(n_docs, DocResult());
     if (!n_docs) return GFT_OK;
-    std::vector<uint8_t> status;
-    std::vector<uint32_t> rows;
+    JsonStaged staged;
     std::shared_ptr<Records> r;            // (held to the end: the call's own, whatever becomes of the member it came from)
     {
         RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
         const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
-        int rc = json_stage(e, blob, doc_off, n_docs, row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows);
+        int rc = json_stage(e, blob, doc_off, n_docs, want_tags ? 0 : row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows);
         if (rc) { err = gft_last_error(e); return rc; }
         r = choose(e, d_blob, d_doc_off, rc);
         if (rc) return rc;
-        if (r && (rc = json_staged_rows(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, status, rows, err))) return rc;
+        if (r && (rc = json_staged(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, want_tags, staged, err))) return rc;
     }
     if (!r) return by_host();
-    return json_results(*r, blob, doc_off, n_docs, status, rows, out, err);
+    return json_results(*r, blob, doc_off, n_docs, staged, want_tags, out, err);
 }
 
 int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
+    return jsons_schema(blob, doc_off, n_docs, false, out, err);
+}
+
+int GroupFinder::jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err) {
     Records* r = schema_records("JSON batch", err);
     if (!r) return GFT_E_INVALID;
     int rc = json_ready(nullptr, *r, err);
@@ -142,8 +179,8 @@ int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off
     if ((rc = compile(*r, err))) return rc;
     if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
     // (the schema's own lists; it is compiled already, whatever the batch holds)
-    return json_batch(blob, doc_off, n_docs, r->inc, r->exc, r->row_words(), [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; },
-                      out, err);
+    return json_batch(blob, doc_off, n_docs, r->inc, r->exc, want_tags, r->row_words(),
+                      [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; }, out, err);
 }
 
 // ---- the schema discovered from the batch ------------------------------------------------------------------------------------
@@ -160,6 +197,11 @@ int GroupFinder::JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_of
 
 int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                                   const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err) {
+    return jsons_auto(blob, doc_off, n_docs, includePaths, excludePaths, false, out, err);
+}
+
+int GroupFinder::jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
+                            const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err) {
     int rc = json_check_offsets(doc_off, n_docs, err);
     if (rc) return rc;
     auto_last_paths = auto_last_dropped = auto_last_recompiled = 0;
@@ -206,10 +248,10 @@ int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, 
         rc = compile(*auto_, err);                             // (rules or expressions were added since)
         if (rc == GFT_E_UNSUPPORTED) { err.clear(); rc = GFT_OK; auto_.reset(); return nullptr; }   // (its rules no longer compile)
         if (rc) return nullptr;
-        if (auto_->row_words() != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; rc = GFT_E_INTERNAL; return nullptr; }
+        if (!want_tags && auto_->row_words() != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; rc = GFT_E_INTERNAL; return nullptr; }
         return auto_;
     };
-    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, RW, discover, out, err);
+    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, RW, discover, out, err);
 }
 
 int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {

@@ -1,5 +1,6 @@
 // group_records.cpp -- the group finder's record route (rule_set.hpp, gft_rules.hip): a schema and what is compiled from it
-// (Records), the one function that makes one, and a batch of (field, string) leaves through the finder and the two rule kernels.
+// (Records), the one function that makes one, and a batch of (field, string) leaves through the finder and the two rule kernels
+// -- or, for the tag calls (group_tags.cpp), the three tag kernels.
 #include "group_records.hpp"
 
 #include <set>
@@ -89,11 +90,13 @@ int GroupFinder::DebugEvalRulesDevice(const uint32_t* d_hit_bitmap, uint32_t n_e
 int GroupFinder::ProcessRecordsDevice(const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
                                       uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err) {
     Records* r = schema_records("record batch", err);
-    return r ? records_device(*r, d_text, d_leaf_off, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap, err) : GFT_E_INVALID;
+    RecordsOut out;
+    out.d_rule_bitmap = d_rule_bitmap;
+    return r ? records_device(*r, d_text, d_leaf_off, d_leaf_field, d_rec_off, n_records, n_leaves, out, err) : GFT_E_INVALID;
 }
 
 int GroupFinder::records_device(Records& r, const uint8_t* d_text, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
-                                uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap, Error& err) {
+                                uint64_t n_records, uint64_t n_leaves, const RecordsOut& out, Error& err) {
     int rc = compile(r, err);
     if (rc) return rc;
     if (!findthem_->device_resident_ok()) { err = "device-resident records need the GPU substring engine and no regex terms"; return GFT_E_UNSUPPORTED; }
@@ -112,7 +115,17 @@ int GroupFinder::records_device(Records& r, const uint8_t* d_text, const uint64_
         if (!err.empty()) return findthem_->last_code() ? findthem_->last_code() : GFT_E_ENGINE;
         // (the finder may have rebuilt its programs, never its expressions: the set installed above still fits)
     }
-    if ((rc = rules_eval_device(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, d_rule_bitmap))) err = gft_last_error(e);
+    if (out.owned) {
+        rc = rules_tag_entries_owned(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, &out.owned->row_off, &out.owned->ent_field,
+                                     &out.owned->ent_expr, &out.owned->total);
+    } else if (out.d_entries) {
+        const TagEntries& t = *out.d_entries;
+        rc = rules_tag_entries_device(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, t.row_off, t.ent_field, t.ent_expr, t.ent_tag, t.cap,
+                                      t.total);
+    } else {
+        rc = rules_eval_device(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, out.d_rule_bitmap);
+    }
+    if (rc) err = gft_last_error(e);
     return rc;
 }
 
@@ -142,8 +155,10 @@ int GroupFinder::ProcessRecords(const uint8_t* text, const uint64_t* leaf_off, c
         const uint64_t bytes[5] = {text_bytes, (n_leaves + 1) * 8, n_leaves * 4, (n_records + 1) * 8, 0};
         const uint64_t slack[5] = {64, 0, 0, 0, n_records * RW * 4};
         if ((rc = rules_stage(e, 5, src, bytes, slack, d))) { err = gft_last_error(e); return rc; }
-        rc = records_device(*r, (const uint8_t*)d[0], (const uint64_t*)d[1], (const uint32_t*)d[2], (const uint64_t*)d[3], n_records, n_leaves,
-                            (uint32_t*)d[4], err);
+        RecordsOut rows;
+        rows.d_rule_bitmap = (uint32_t*)d[4];
+        rc = records_device(*r, (const uint8_t*)d[0], (const uint64_t*)d[1], (const uint32_t*)d[2], (const uint64_t*)d[3], n_records, n_leaves, rows,
+                            err);
         if (rc) return rc;
     } else {
         // regex terms, the prefilter, injected engines: the finder's own batch path gives the leaf bitmap

@@ -1,8 +1,10 @@
-// group_records.hpp -- GroupFinder::Records, for the two files that work on one: group_records.cpp (the record route) and
-// group_json.cpp (the JSON routes on top of it).  Not for other includers.
+// group_records.hpp -- GroupFinder::Records, for the three files that work on one: group_records.cpp (the record route),
+// group_json.cpp (the JSON routes on top of it) and group_tags.cpp (the tag calls, which ask both for entries instead of rule
+// rows).  Not for other includers.
 #pragma once
 #include "gft_json.hpp"
 #include "gft_rules.hpp"
+#include "gft_tags.hpp"
 #include "group_host.hpp"
 #include "json_schema.hpp"
 #include "rule_set.hpp"
@@ -20,6 +22,23 @@ struct GroupFinder::Records {
     Error json_err;
     uint64_t json_serial = 0;              // its copy on the engine (json_install)
     uint64_t row_words() const { return (uint64_t)(set.n_rules + 31) / 32; }    // of a rule bitmap row
+};
+
+// One of: rule rows [n_records][row_words]; tag entries into the caller's device arrays; tag entries into the engine's own
+// arrays (rules_tag_entries_owned), which `owned` then names
+struct GroupFinder::RecordsOut {
+    uint32_t* d_rule_bitmap = nullptr;
+    const TagEntries* d_entries = nullptr;
+    struct Owned { const uint64_t* row_off = nullptr; const uint32_t* ent_field = nullptr; const uint32_t* ent_expr = nullptr; uint64_t total = 0; };
+    Owned* owned = nullptr;
+    bool tags() const { return d_entries || owned; }
+};
+
+struct GroupFinder::JsonStaged {
+    std::vector<uint8_t> status;           // [n_docs]
+    std::vector<uint32_t> rows;            // rule rows [n_docs][row_words] ...
+    std::vector<uint64_t> row_off;         // ... or tag entries: [n_docs + 1], [total], [total]
+    std::vector<uint32_t> ent_field, ent_expr;
 };
 
 // the finder's engine for a batch on the device, or why there is none (what: "record batches", "JSON batches")

@@ -291,6 +291,143 @@ class GroupFinder:
             raise self._err(rc)
         return out
 
+    # -- tag entries: TagObject's map of every record as sparse (field, expression) lists (csrc/gft_tags.hip) -------------------
+    GUARD = 8                                                  # words behind a cap in which nothing may be stored
+
+    def tags_from_entries(self, row_off, ent_field, ent_expr):
+        """the three columns of a tag result -> one {tag: {field path: [expression strings, sorted]}} per record: what TagObject
+        gives for an object with exactly the record's (path, string) leaves"""
+        schema = getattr(self, "_schema", None)
+        if schema is None:
+            raise GroupFinderError(_lib.GFT_E_INVALID, "no schema set (SetSchema)")
+        paths = [p.decode("utf-8", "surrogateescape") for p in sorted(schema, key=schema.get)]
+        pairs = self.findthem._pairs()
+        row_off = [int(x) for x in np.asarray(row_off).reshape(-1)]
+        ent_field, ent_expr = np.asarray(ent_field).reshape(-1), np.asarray(ent_expr).reshape(-1)
+        out = []
+        for r in range(len(row_off) - 1):
+            sets = {}
+            for k in range(row_off[r], row_off[r + 1]):
+                expr, tag = pairs[int(ent_expr[k])]
+                sets.setdefault(tag, {}).setdefault(paths[int(ent_field[k])], set()).add(expr)
+            out.append({t: {f: sorted(v) for f, v in fs.items()} for t, fs in sets.items()})
+        return out
+
+    def _entries_host(self, fn, head, n_records, cap, want_tag):
+        """the row_off / ent_* / cap / total part of the host-pointer tag calls -> (row_off, ent_field, ent_expr, ent_tag, total);
+        cap None: counted first, the arrays sized by the total; the arrays are GUARD words longer than cap, filled with 0xA5"""
+        row_off, total = np.zeros(n_records + 1, dtype=np.uint64), C.c_uint64(0)
+        if cap is None:
+            rc = fn(self._h, *head, row_off.ctypes.data, None, None, None, 0, C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        cols = [np.full(cap + self.GUARD, 0xA5A5A5A5, dtype=np.uint32) for _ in range(3)]
+        rc = fn(self._h, *head, row_off.ctypes.data, cols[0].ctypes.data, cols[1].ctypes.data, cols[2].ctypes.data if want_tag else None, cap,
+                C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return row_off, cols[0], cols[1], cols[2] if want_tag else None, int(total.value)
+
+    def _entries_device(self, fn, head, n_records, cap, want_tag, dev):
+        """... and of the device-pointer calls: device tensors int64[n_records + 1], int32[cap + GUARD] (the guard words hold -1)"""
+        import torch
+        row_off = torch.zeros(n_records + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64(0)
+        torch.cuda.current_stream(dev).synchronize()          # (the library runs on the engine's own stream)
+        if cap is None:
+            rc = fn(self._h, *head, row_off.data_ptr(), None, None, None, 0, C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        cols = [torch.full((cap + self.GUARD,), -1, dtype=torch.int32, device=dev) for _ in range(3)]
+        torch.cuda.current_stream(dev).synchronize()
+        rc = fn(self._h, *head, row_off.data_ptr(), cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr() if want_tag else None, cap,
+                C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return row_off, cols[0], cols[1], cols[2] if want_tag else None, int(total.value)
+
+    def debug_tag_entries(self, hit_bitmap, n_exprs, leaf_field, rec_off, cap=None, want_tag=True):
+        """gft_debug_tag_entries: the contract of the tag kernels in plain loops on the host over a caller-supplied leaf bitmap (no
+        device) -> (row_off u64[n + 1], ent_field, ent_expr, ent_tag u32[cap + GUARD], total)"""
+        hit_bitmap = np.ascontiguousarray(hit_bitmap, dtype=np.uint32)
+        leaf_field = np.ascontiguousarray(leaf_field, dtype=np.uint32)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        n_records, n_leaves = len(rec_off) - 1, len(leaf_field)
+        head = (hit_bitmap.ctypes.data, n_exprs, leaf_field.ctypes.data, rec_off.ctypes.data, n_records, n_leaves)
+        return self._entries_host(self._L.gft_debug_tag_entries, head, max(n_records, 0), cap, want_tag)
+
+    def debug_tag_entries_device(self, hit_bitmap, n_exprs, leaf_field, rec_off, cap=None, want_tag=True):
+        """gft_debug_tag_entries_device: the three tag launches over a caller-supplied leaf bitmap (torch device tensors, int32 rows,
+        int32 fields, int64 offsets) -> device tensors as _entries_device, and the total"""
+        n_records, n_leaves = int(rec_off.numel()) - 1, int(leaf_field.numel())
+        head = (hit_bitmap.data_ptr(), n_exprs, leaf_field.data_ptr(), rec_off.data_ptr(), n_records, n_leaves)
+        return self._entries_device(self._L.gft_debug_tag_entries_device, head, max(n_records, 0), cap, want_tag, rec_off.device)
+
+    def TagRecordsEntries(self, blob, leaf_off, leaf_field, rec_off, cap=None, want_tag=True):
+        """host arrays of the record form -> (row_off, ent_field, ent_expr, ent_tag, total) as debug_tag_entries"""
+        n_records, n_leaves = len(rec_off) - 1, len(leaf_field)
+        head = (blob.ctypes.data, leaf_off.ctypes.data, leaf_field.ctypes.data, rec_off.ctypes.data, n_records, n_leaves)
+        return self._entries_host(self._L.gft_group_tag_records, head, max(n_records, 0), cap, want_tag)
+
+    def TagRecords(self, records):
+        """records: a list of lists of (path or field index, str).  One {tag: {field: [expressions]}} per record, what TagObject
+        gives for an object with exactly those leaves."""
+        row_off, ent_field, ent_expr, _, total = self.TagRecordsEntries(*self.pack_records(records), want_tag=False)
+        return self.tags_from_entries(row_off, ent_field[:total], ent_expr[:total])
+
+    def TagRecordsDevice(self, text, leaf_off, leaf_field, rec_off, cap=None, want_tag=True):
+        """torch device tensors as for ProcessRecordsDevice -> (row_off int64[n + 1], ent_field, ent_expr, ent_tag int32[cap + GUARD],
+        total) on the device; without a cap the batch is counted first and the arrays are sized by the total"""
+        n_records, n_leaves = int(rec_off.numel()) - 1, int(leaf_field.numel())
+        for t, size in ((text, 1), (leaf_off, 8), (leaf_field, 4), (rec_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "TagRecordsDevice takes contiguous device tensors of 1, 8, 4 and 8 byte integers")
+        head = (text.data_ptr(), leaf_off.data_ptr(), leaf_field.data_ptr(), rec_off.data_ptr(), n_records, n_leaves)
+        return self._entries_device(self._L.gft_group_tag_records_device, head, max(n_records, 0), cap, want_tag, text.device)
+
+    def TagJsonsDevice(self, blob, doc_off, cap=None, want_tag=True):
+        """torch device tensors as for JsonLeavesDevice -> ((row_off, ent_field, ent_expr, ent_tag, total) as TagRecordsDevice, status
+        uint8[n]); the row of a document whose status is not 0 is empty"""
+        import torch
+        n = int(doc_off.numel()) - 1
+        for t, size in ((blob, 1), (doc_off, 8)):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "TagJsonsDevice takes contiguous device tensors of 1 and 8 byte integers")
+        status = torch.zeros(max(n, 0), dtype=torch.uint8, device=blob.device)
+        head = (blob.data_ptr(), doc_off.data_ptr(), n, status.data_ptr())
+        return self._entries_device(self._L.gft_group_tag_jsons_device, head, max(n, 0), cap, want_tag, blob.device), status
+
+    def _result_call(self, fn, rawJsons, *lists):
+        """a JSON batch through an entry point that leaves a result document (fetched again, not run again, when it is larger than
+        the buffer)"""
+        raws = [r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in rawJsons]
+        blob, off = pack(raws)
+        need = C.c_uint64(0)
+        cap = max(1 << 16, 2 * int(blob.size))
+        buf = C.create_string_buffer(cap)
+        extra = []
+        for lst in lists:
+            j = json.dumps(list(lst)).encode() if lst else None
+            extra += [j, len(j) if j else 0]
+        rc = fn(self._h, blob.ctypes.data, off.ctypes.data, len(raws), *extra, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc == _lib.GFT_E_INVALID and need.value > cap:
+            cap = int(need.value)
+            buf = C.create_string_buffer(cap)
+            rc = self._L.gft_group_last_result(self._h, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc != 0:
+            raise self._err(rc)
+        return json.loads(buf.value.decode("utf-8", "replace"))
+
+    def TagJsonsSchema(self, rawJsons):
+        """TagJsons(rawJsons, include, exclude of SetSchema) with the documents decoded and tagged on the device where it decides them"""
+        return self._result_call(self._L.gft_group_tag_jsons_schema, rawJsons)
+
+    def TagJsonsAuto(self, rawJsons, includePaths=None, excludePaths=None):
+        """TagJsons(rawJsons, includePaths, excludePaths) with the schema discovered from the batch on the device"""
+        return self._result_call(self._L.gft_group_tag_jsons_auto, rawJsons, includePaths, excludePaths)
+
     # -- JSON decoded on the device against the schema (csrc/gft_json.hip) -----------------------------------------------
     def _json_leaves_host(self, fn, docs, leaf_cap=None, text_cap=None):
         """gft_debug_json_leaves_ref / gft_debug_emulate_json_leaves over a list of byte strings -> (status, rec_off, leaf_field,

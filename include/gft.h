@@ -434,6 +434,69 @@ int gft_debug_eval_rules(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_ex
  * row's last word are ignored.  One device; validation as for the call above. */
 int gft_debug_eval_rules_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint32_t* d_rule_bitmap);
+/* ---- Tag entries: TagObject / TagJson on the device as sparse (field, expression) lists (gft_tags.hip) ----------------------
+ * For a record batch under the schema, the tag map of every record -- tag -> field path -> {expression}, finder.go:87-110 -- comes
+ * back as three columns:
+ *     row_off   u64 [n_records + 1]   record r owns the entries row_off[r] .. row_off[r + 1]
+ *     ent_field u32 [total]           schema index of the leaf's field
+ *     ent_expr  u32 [total]           finder expression index
+ *     ent_tag   u32 [total]           nullable: the tag id of expression ent_expr (gft_finder_expression_tag_id)
+ * Inside a record the leaves come in record order (rec_off[r] .. rec_off[r + 1]), inside a leaf the expression index ascends.
+ * A leaf contributes one entry per set bit e < n_exprs of its hit row (bits at and above n_exprs in a row's last word are
+ * ignored), and only when its field is valid: isValidateFieldPath under the schema's include / exclude lists, exclude wins.
+ * (The host route drops invalid leaves before the finder sees them; the device decoder keeps them, the mask is applied here.)
+ * A record that names a field twice contributes twice: nothing is de-duplicated or sorted on the device.  The tag map is a map
+ * of sets, so the consumer's insert removes the duplicate, and records decoded from JSON never repeat a field (GFT_JSON_DUP).
+ * {(tag of ent_expr, schema[ent_field], ExpresionStr of ent_expr)} over a record's entries is TagObject's map for an object with
+ * exactly those (path, string) leaves.  A group without rules is valid; a finder without expressions gives total = 0.
+ * Cap protocol, as for gft_compact_device and gft_group_json_leaves_device: row_off is always complete; an entry at a position
+ * >= cap is not stored and nothing is stored past the caps; the status is GFT_OK either way; *total (host memory, nullable)
+ * receives row_off[n_records]; NULL arrays with cap == 0 count only.
+ * Validation, as for gft_group_process_records_device: GFT_E_INVALID for no schema, a leaf_field entry >= F, rec_off that
+ * descends or does not end at n_leaves, leaves but no records -- such leaves and records are skipped on the device, never
+ * dereferenced, and the handle goes on answering.  Handles over several devices: GFT_E_UNSUPPORTED from the device-pointer
+ * calls.  GFT_E_NOMEM: no room for the work buffers (counts, offsets and scan partials of their own, grown on demand).
+ *
+ * Every pointer is a device pointer except total.  The leaves go through gft_finder_process_device into the engine's leaf
+ * bitmap (the limits of gft_group_process_records_device), then three launches run on the engine's stream (gft_profile_read:
+ * "tags_count", "tags_scan", "tags_fill"); only the status and the total cross the link. */
+int gft_group_tag_records_device(gft_group* g, const uint8_t* d_text_blob, const uint64_t* d_leaf_off, const uint32_t* d_leaf_field,
+                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint64_t* d_row_off, uint32_t* d_ent_field,
+                                 uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap, uint64_t* total);
+/* Host pointers.  A finder that qualifies for the call above: upload, that call into arrays the engine owns, the arrays down.
+ * Any other finder (regex terms, injected engines, several devices): the leaf bitmap comes from gft_finder_process_texts and
+ * the entries are made on the host.  Both routes give the same arrays; a finder error is the call's error. */
+int gft_group_tag_records(gft_group* g, const uint8_t* text_blob, const uint64_t* leaf_off, const uint32_t* leaf_field, const uint64_t* rec_off,
+                          uint64_t n_records, uint64_t n_leaves, uint64_t* row_off, uint32_t* ent_field, uint32_t* ent_expr, uint32_t* ent_tag,
+                          uint64_t cap, uint64_t* total);
+/* Device pointers: gft_group_json_leaves_device into buffers the engine owns, then gft_group_tag_records_device over them, a
+ * document a record.  d_status [n_docs] as in gft_group_process_jsons_device: a document whose status is not 0 has an empty row. */
+int gft_group_tag_jsons_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
+                               uint64_t* d_row_off, uint32_t* d_ent_field, uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap,
+                               uint64_t* total);
+/* Host pointers; the same result document as gft_group_process_jsons(..., what = 1) with the include / exclude lists given to
+ * gft_group_set_schema: upload, the call above into arrays the engine owns, status and entries down; a document of status 0 gets
+ * {"tags": ..} from its entries (on host threads, a document per task), all others go through gft_group_process_jsons' route as
+ * one sub-batch and take its "tags" or "error".  A finder that does not qualify takes that route for the whole batch.
+ * gft_group_last_result and gft_group_json_last serve this call too. */
+int gft_group_tag_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
+                               uint64_t* needed);
+/* TagJson as the reference has it: no schema.  As gft_group_process_jsons_auto -- the schema discovered from the batch, kept
+ * between calls (one kept schema serves both calls) -- with the result document of gft_group_process_jsons(..., what = 1).  A
+ * limit that refuses the discovered schema is never the caller's error: the batch takes the host route. */
+int gft_group_tag_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* include_json,
+                             uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap,
+                             uint64_t* needed);
+/* The contract above stated in plain loops on the host over a caller-supplied leaf bitmap [n_leaves][ceil(n_exprs / 32)]; n_exprs
+ * must be the finder's number of expressions.  Needs no device.  It is also the second route of gft_group_tag_records. */
+int gft_debug_tag_entries(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                          uint64_t n_records, uint64_t n_leaves, uint64_t* row_off, uint32_t* ent_field, uint32_t* ent_expr, uint32_t* ent_tag,
+                          uint64_t cap, uint64_t* total);
+/* The three launches of gft_group_tag_records_device over a caller-supplied leaf bitmap on the device (every pointer is a device
+ * pointer except total): what the kernels make of rows the finder did not write. */
+int gft_debug_tag_entries_device(gft_group* g, const uint32_t* d_hit_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field,
+                                 const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves, uint64_t* d_row_off, uint32_t* d_ent_field,
+                                 uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap, uint64_t* total);
 /* ---- JSON decoded on the device (gft_json.hip): raw documents in HBM -> the record form above ----------------------------
  * The schema of gft_group_set_schema is compiled into a trie of path components (split at '.', the root is the path "");
  * a wave walks a document in 64-byte pieces and resolves every object key and array element ("index(<i>)") in that trie,
