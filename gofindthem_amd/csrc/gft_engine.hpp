@@ -227,6 +227,15 @@ inline int fail_hip(const gft_engine* e, hipError_t h, const char* what) {
     return GFT_E_HIP;
 }
 
+// a work buffer grown on demand to at least `bytes` (and 16); the texts of its two failures: GFT_E_NOMEM's message, and what
+// fail_hip names for any other error
+struct RoomTexts { const char* nomem; const char* alloc; };
+inline int room(const gft_engine* e, DevBuf& b, uint64_t bytes, const RoomTexts& t) {
+    const hipError_t h = b.ensure(std::max<uint64_t>(bytes, 16));
+    if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, t.nomem); }
+    return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, t.alloc);
+}
+
 struct DeviceGuard {
     int prev = -1;
     bool ok = true;

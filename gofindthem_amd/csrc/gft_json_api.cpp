@@ -16,11 +16,7 @@ int json_entry_checks(gft_engine* e) {
     if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, "JSON batches: single-device handles only");
     return check_ready(e, kNeedDevice | kNeedSettled, "JSON batches");
 }
-int json_room(gft_engine* e, gft_engine::DevBuf& b, uint64_t bytes) {
-    const hipError_t h = b.ensure(std::max<uint64_t>(bytes, 16));
-    if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, "no device memory for the JSON batch's work buffers"); }
-    return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, "JSON batch alloc");
-}
+constexpr RoomTexts kJsonRoom{"no device memory for the JSON batch's work buffers", "JSON batch alloc"};
 bool overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
     if (!a || !b || !a_bytes || !b_bytes) return false;
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -84,8 +80,8 @@ int json_leaves_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_d
     for (const auto& i : in)
         for (const auto& o : outs)
             if (overlap(i.p, i.bytes, o.p, o.bytes)) return fail(e, GFT_E_INVALID, "gft_group_json_leaves_device: the output overlaps the input");
-    if ((rc = json_room(e, J.cnt_leaves, n_docs * 4)) || (rc = json_room(e, J.cnt_text, n_docs * 4)) || (rc = json_room(e, J.text_off, (n_docs + 1) * 8)) ||
-        (rc = json_room(e, J.partial, scan_partials_needed(n_docs) * 8)) || (rc = json_room(e, J.flags, 16)))
+    if ((rc = room(e, J.cnt_leaves, n_docs * 4, kJsonRoom)) || (rc = room(e, J.cnt_text, n_docs * 4, kJsonRoom)) || (rc = room(e, J.text_off, (n_docs + 1) * 8, kJsonRoom)) ||
+        (rc = room(e, J.partial, scan_partials_needed(n_docs) * 8, kJsonRoom)) || (rc = room(e, J.flags, 16, kJsonRoom)))
         return rc;
     JsonParams P{};
     P.blob = d_blob; P.doc_off = d_doc_off; P.n_docs = n_docs;
@@ -128,8 +124,8 @@ int json_leaves_owned(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_do
     if (rc) return rc;
     DeviceGuard g(e->device);
     auto& J = e->d_json;
-    if ((rc = json_room(e, J.rec_off, (n_docs + 1) * 8)) || (rc = json_room(e, J.leaf_field, 16)) || (rc = json_room(e, J.leaf_off, 16)) ||
-        (rc = json_room(e, J.text, 64)))
+    if ((rc = room(e, J.rec_off, (n_docs + 1) * 8, kJsonRoom)) || (rc = room(e, J.leaf_field, 16, kJsonRoom)) || (rc = room(e, J.leaf_off, 16, kJsonRoom)) ||
+        (rc = room(e, J.text, 64, kJsonRoom)))
         return rc;
     for (int round = 0;; round++) {
         const uint64_t leaf_cap = std::min<uint64_t>(J.leaf_field.cap / 4, J.leaf_off.cap / 8 - 1), text_cap = J.text.cap - 64;
@@ -138,8 +134,8 @@ int json_leaves_owned(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_do
             return rc;
         if (totals[0] <= leaf_cap && totals[1] <= text_cap) break;
         if (round) return fail(e, GFT_E_INTERNAL, "JSON batch: the record arrays do not fit the buffers grown for them");
-        if ((rc = json_room(e, J.leaf_field, totals[0] * 4)) || (rc = json_room(e, J.leaf_off, (totals[0] + 1) * 8)) ||
-            (rc = json_room(e, J.text, totals[1] + 64)))
+        if ((rc = room(e, J.leaf_field, totals[0] * 4, kJsonRoom)) || (rc = room(e, J.leaf_off, (totals[0] + 1) * 8, kJsonRoom)) ||
+            (rc = room(e, J.text, totals[1] + 64, kJsonRoom)))
             return rc;
     }
     HIP_TRY(hipMemsetAsync(J.text.as<uint8_t>() + totals[1], 0, 64, e->stream), "JSON text slack");
@@ -170,7 +166,7 @@ int json_paths_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_do
     // counters (count, dropped, cursor, -) | slots | path_off | pool: one allocation of a fixed size
     constexpr uint64_t kHead = 16, kSlots = (uint64_t)kJsonPathSlots * 8, kOffs = (uint64_t)kJsonPathCap * 4;
     auto& J = e->d_json;
-    if ((rc = json_room(e, J.paths, kHead + kSlots + kOffs + kJsonPathPool)) || (rc = json_room(e, J.flags, 16))) return rc;
+    if ((rc = room(e, J.paths, kHead + kSlots + kOffs + kJsonPathPool, kJsonRoom)) || (rc = room(e, J.flags, 16, kJsonRoom))) return rc;
     uint8_t* base = J.paths.as<uint8_t>();
     JsonPathParams P{};
     P.blob = d_blob; P.doc_off = d_doc_off; P.n_docs = n_docs; P.flags = J.flags.as<uint32_t>();
@@ -211,8 +207,8 @@ int json_stage(gft_engine* e, const uint8_t* blob, const uint64_t* doc_off, uint
     SyncOnExit drain(e);
     auto& J = e->d_json;
     const uint64_t lo = doc_off[0], bytes = doc_off[n_docs] - lo;
-    if ((rc = json_room(e, J.blob, lo + bytes + 64)) || (rc = json_room(e, J.doc_off, (n_docs + 1) * 8)) || (rc = json_room(e, J.status, n_docs)) ||
-        (rc = json_room(e, J.rows, n_docs * row_bytes)))
+    if ((rc = room(e, J.blob, lo + bytes + 64, kJsonRoom)) || (rc = room(e, J.doc_off, (n_docs + 1) * 8, kJsonRoom)) || (rc = room(e, J.status, n_docs, kJsonRoom)) ||
+        (rc = room(e, J.rows, n_docs * row_bytes, kJsonRoom)))
         return rc;
     // (the offsets stay as the caller gave them: the blob keeps its place in the buffer)
     if (bytes) HIP_TRY(hipMemcpyAsync(J.blob.as<uint8_t>() + lo, blob + lo, bytes, hipMemcpyHostToDevice, e->stream), "JSON batch upload");

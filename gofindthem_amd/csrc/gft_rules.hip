@@ -24,20 +24,20 @@ namespace gft {
 
 namespace {
 
-constexpr uint32_t kTagsBlock = 256;
+constexpr uint32_t kLeafTagsBlock = 256;
 
-__global__ void __launch_bounds__(kTagsBlock) k_leaf_tags(const uint32_t* __restrict__ hit, uint32_t EW, uint32_t n_exprs,
+__global__ void __launch_bounds__(kLeafTagsBlock) k_leaf_tags(const uint32_t* __restrict__ hit, uint32_t EW, uint32_t n_exprs,
                                                           const uint32_t* __restrict__ expr_tag, const uint32_t* __restrict__ leaf_field,
                                                           uint32_t n_fields, uint64_t n_leaves, uint32_t TW, uint32_t* __restrict__ tag_rows,
                                                           uint32_t* __restrict__ flags) {
-    const uint64_t stride = (uint64_t)gridDim.x * kTagsBlock;
+    const uint64_t stride = (uint64_t)gridDim.x * kLeafTagsBlock;
     if (TW == 0) {                                  // a finder without expressions: nothing to fold, the fields are still checked
-        for (uint64_t l = (uint64_t)blockIdx.x * kTagsBlock + threadIdx.x; l < n_leaves; l += stride)
+        for (uint64_t l = (uint64_t)blockIdx.x * kLeafTagsBlock + threadIdx.x; l < n_leaves; l += stride)
             if (leaf_field[l] >= n_fields) flags[0] = 1;
         return;
     }
     const uint64_t total = n_leaves * TW;
-    for (uint64_t idx = (uint64_t)blockIdx.x * kTagsBlock + threadIdx.x; idx < total; idx += stride) {
+    for (uint64_t idx = (uint64_t)blockIdx.x * kLeafTagsBlock + threadIdx.x; idx < total; idx += stride) {
         const uint64_t l = idx / TW;
         const uint32_t tw = (uint32_t)(idx - l * TW);
         if (tw == 0 && leaf_field[l] >= n_fields) flags[0] = 1;
@@ -164,8 +164,8 @@ hipError_t launch_leaf_tags(const uint32_t* d_hit, uint32_t n_exprs, const uint3
                             uint64_t n_leaves, uint32_t n_tags, uint32_t* d_tag_rows, uint32_t* d_flags, hipStream_t st) {
     const uint32_t TW = (n_tags + 31) / 32;
     if (!n_leaves) return hipSuccess;
-    const uint64_t blocks = (n_leaves * (TW ? TW : 1) + kTagsBlock - 1) / kTagsBlock;
-    k_leaf_tags<<<dim3((unsigned)std::min<uint64_t>(blocks, 1u << 20)), dim3(kTagsBlock), 0, st>>>(
+    const uint64_t blocks = (n_leaves * (TW ? TW : 1) + kLeafTagsBlock - 1) / kLeafTagsBlock;
+    k_leaf_tags<<<dim3((unsigned)std::min<uint64_t>(blocks, 1u << 20)), dim3(kLeafTagsBlock), 0, st>>>(
         d_hit, (n_exprs + 31) / 32, n_exprs, d_expr_tag, d_leaf_field, n_fields, n_leaves, TW, d_tag_rows, d_flags);
     return hipGetLastError();
 }

@@ -26,6 +26,9 @@ struct RulesParams {
     uint32_t* out;               // [n_records][RW]
 };
 
+// what the flag words of a record batch say, read back after its kernels: GFT_OK, or GFT_E_INVALID and its message
+int record_flags_rc(gft_engine* e, const uint32_t h_flags[2]);
+
 size_t rules_lds_bytes(uint32_t n_units, uint32_t max_depth);
 hipError_t launch_leaf_tags(const uint32_t* d_hit, uint32_t n_exprs, const uint32_t* d_expr_tag, const uint32_t* d_leaf_field, uint32_t n_fields,
                             uint64_t n_leaves, uint32_t n_tags, uint32_t* d_tag_rows, uint32_t* d_flags, hipStream_t st);

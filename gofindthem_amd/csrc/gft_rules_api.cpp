@@ -14,14 +14,16 @@ int rules_entry_checks(gft_engine* e) {
     if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, "record batches: single-device handles only");
     return check_ready(e, kNeedDevice | kNeedSettled, "record batches");
 }
-int rules_room(gft_engine* e, DevBuf& b, uint64_t bytes) {
-    const hipError_t h = b.ensure(std::max<uint64_t>(bytes, 16));
-    if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, "no device memory for the record batch's work buffers"); }
-    return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, "record batch alloc");
-}
+constexpr RoomTexts kRulesRoom{"no device memory for the record batch's work buffers", "record batch alloc"};
 }  // namespace
 
 namespace gft {
+
+int record_flags_rc(gft_engine* e, const uint32_t h_flags[2]) {
+    if (h_flags[1]) return fail(e, GFT_E_INVALID, "record batch: rec_off descends or does not end at n_leaves");
+    if (h_flags[0]) return fail(e, GFT_E_INVALID, "record batch: a leaf names a field outside the schema");
+    return GFT_OK;
+}
 
 void rules_lock(gft_engine* e) { e->mu.lock(); }
 void rules_unlock(gft_engine* e) { e->mu.unlock(); }
@@ -63,7 +65,7 @@ int rules_leaf_bitmap(gft_engine* e, uint64_t n_leaves, uint32_t words, uint32_t
     int rc = rules_entry_checks(e);
     if (rc) return rc;
     DeviceGuard g(e->device);
-    if ((rc = rules_room(e, e->d_rules.leaf_bitmap, n_leaves * words * 4))) return rc;
+    if ((rc = room(e, e->d_rules.leaf_bitmap, n_leaves * words * 4, kRulesRoom))) return rc;
     *d_bitmap = e->d_rules.leaf_bitmap.as<uint32_t>();
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
@@ -77,7 +79,7 @@ int rules_stage(gft_engine* e, int n, const void* const* src, const uint64_t* by
     SyncOnExit drain(e);
     for (int k = 0; k < n; k++) {
         DevBuf& b = e->d_rules.stage[k];
-        if ((rc = rules_room(e, b, bytes[k] + slack[k]))) return rc;
+        if ((rc = room(e, b, bytes[k] + slack[k], kRulesRoom))) return rc;
         if (bytes[k]) HIP_TRY(hipMemcpyAsync(b.p, src[k], bytes[k], hipMemcpyHostToDevice, e->stream), "record batch upload");
         if (slack[k]) HIP_TRY(hipMemsetAsync((uint8_t*)b.p + bytes[k], 0, slack[k], e->stream), "record batch upload");
         d_dst[k] = b.p;
@@ -111,7 +113,7 @@ int rules_eval_device(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
     const uint32_t TW = (R.n_tags + 31) / 32;
-    if ((rc = rules_room(e, R.tag_rows, n_leaves * TW * 4))) return rc;
+    if ((rc = room(e, R.tag_rows, n_leaves * TW * 4, kRulesRoom))) return rc;
     uint32_t* d_flags = R.flags.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(d_flags, 0, 8, st), "record rules");
     {
@@ -136,9 +138,7 @@ int rules_eval_device(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_
     uint32_t h_flags[2] = {0, 0};
     HIP_TRY(hipMemcpyAsync(h_flags, d_flags, 8, hipMemcpyDeviceToHost, st), "record rules");
     HIP_TRY(hipStreamSynchronize(st), "record rules");
-    if (h_flags[1]) return fail(e, GFT_E_INVALID, "record batch: rec_off descends or does not end at n_leaves");
-    if (h_flags[0]) return fail(e, GFT_E_INVALID, "record batch: a leaf names a field outside the schema");
-    return GFT_OK;
+    return record_flags_rc(e, h_flags);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 }  // namespace gft

@@ -7,17 +7,15 @@
 #include <stdint.h>
 
 #include "../../include/gft.h"
+#include "gft_bitrows_dev.hpp"
 
 namespace gft {
 
 struct TagParams {
-    const uint32_t* bitmap;      // [n_leaves][W] hit rows
+    BitRows rows;                // [n_leaves][W] hit rows: a row a leaf (bit_rows)
     const uint32_t* leaf_field;  // [n_leaves]
     const uint32_t* valid;       // [ceil(n_fields / 32)] RuleSet::valid
-    uint64_t n_leaves;
     uint32_t n_fields;
-    uint32_t W, lg;              // words per row; W <= 64: W' = 1 << lg
-    uint32_t tail;               // valid bits of a row's last word
     uint32_t* flags;             // [2]: a field index outside the schema; record offsets that descend or leave [0, n_leaves]
     uint32_t* cnt;               // count pass: [n_leaves]
     // fill pass
@@ -32,9 +30,6 @@ struct TagParams {
     uint64_t cap;
 };
 
-// the part of the block both passes read (W, lg, tail from n_exprs)
-TagParams tag_params(const uint32_t* d_bitmap, uint32_t n_exprs, const uint32_t* d_leaf_field, const uint32_t* d_valid, uint32_t n_fields,
-                     uint64_t n_leaves, uint32_t* d_flags);
 // cnt[l] = set bits < n_exprs of leaf l's row, 0 when its field is invalid or outside the schema (flags[0])
 hipError_t launch_tags_count(const TagParams& P, unsigned n_cus, hipStream_t st);
 // row_off[r] = leaf_ent_off[rec_off[r]] for r = 0 .. n_records (offsets checked first: flags[1]), then the entries below cap

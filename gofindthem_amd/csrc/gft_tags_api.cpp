@@ -1,6 +1,7 @@
 // gft_tags_api.cpp -- tag entries of a record batch (gft_tags.hpp): the engine's side, which group_tags.cpp drives.
 #include "gft_engine.hpp"
 
+#include "gft_rules.hpp"
 #include "gft_tags.hpp"
 
 using namespace gft;
@@ -8,11 +9,7 @@ using namespace gft::api;
 
 namespace {
 
-int tags_room(gft_engine* e, DevBuf& b, uint64_t bytes) {
-    const hipError_t h = b.ensure(std::max<uint64_t>(bytes, 16));
-    if (h == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(e, GFT_E_NOMEM, "no device memory for the tag entries' work buffers"); }
-    return h == hipSuccess ? (int)GFT_OK : fail_hip(e, h, "tag entries alloc");
-}
+constexpr RoomTexts kTagsRoom{"no device memory for the tag entries' work buffers", "tag entries alloc"};
 
 struct TagOut {
     uint64_t* row_off; uint32_t* ent_field; uint32_t* ent_expr; uint32_t* ent_tag; uint64_t cap;
@@ -31,7 +28,7 @@ int tag_entries(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_t* d_l
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
     if (owned) {
-        if ((rc = tags_room(e, T.row_off, (n_records + 1) * 8)) || (rc = tags_room(e, T.ent_field, 16)) || (rc = tags_room(e, T.ent_expr, 16))) return rc;
+        if ((rc = room(e, T.row_off, (n_records + 1) * 8, kTagsRoom)) || (rc = room(e, T.ent_field, 16, kTagsRoom)) || (rc = room(e, T.ent_expr, 16, kTagsRoom))) return rc;
         out = TagOut{T.row_off.as<uint64_t>(), T.ent_field.as<uint32_t>(), T.ent_expr.as<uint32_t>(), nullptr, 0};
     }
     if (!out.row_off) return fail(e, GFT_E_INVALID, "tag entries: null argument");
@@ -43,11 +40,13 @@ int tag_entries(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_t* d_l
         return GFT_OK;
     }
     if (!d_rec_off || (n_leaves && (!d_leaf_field || (R.n_exprs && !d_hit_bitmap)))) return fail(e, GFT_E_INVALID, "record batch: null argument");
-    if ((rc = tags_room(e, T.cnt, n_leaves * 4)) || (rc = tags_room(e, T.leaf_ent_off, (n_leaves + 1) * 8)) ||
-        (rc = tags_room(e, T.partial, scan_partials_needed(n_leaves) * 8)) || (rc = tags_room(e, T.flags, 16)))
+    if ((rc = room(e, T.cnt, n_leaves * 4, kTagsRoom)) || (rc = room(e, T.leaf_ent_off, (n_leaves + 1) * 8, kTagsRoom)) ||
+        (rc = room(e, T.partial, scan_partials_needed(n_leaves) * 8, kTagsRoom)) || (rc = room(e, T.flags, 16, kTagsRoom)))
         return rc;
-    TagParams P = tag_params(d_hit_bitmap, R.n_exprs, d_leaf_field, R.valid.as<uint32_t>(), R.n_fields, n_leaves, T.flags.as<uint32_t>());
-    P.cnt = T.cnt.as<uint32_t>();
+    TagParams P{};
+    P.rows = bit_rows(d_hit_bitmap, n_leaves, R.n_exprs);
+    P.leaf_field = d_leaf_field; P.valid = R.valid.as<uint32_t>(); P.n_fields = R.n_fields;
+    P.flags = T.flags.as<uint32_t>(); P.cnt = T.cnt.as<uint32_t>();
     HIP_TRY(hipMemsetAsync(P.flags, 0, 8, st), "tag entries");
     {
         ProfScope ps(e, "tags_count");
@@ -62,7 +61,7 @@ int tag_entries(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_t* d_l
         // (the one read that sizes the arrays; the caller's form reads the total with the flags, below)
         HIP_TRY(hipMemcpyAsync(&h_total, T.leaf_ent_off.as<uint64_t>() + n_leaves, 8, hipMemcpyDeviceToHost, st), "tag entries");
         HIP_TRY(hipStreamSynchronize(st), "tag entries");
-        if ((rc = tags_room(e, T.ent_field, h_total * 4)) || (rc = tags_room(e, T.ent_expr, h_total * 4))) return rc;
+        if ((rc = room(e, T.ent_field, h_total * 4, kTagsRoom)) || (rc = room(e, T.ent_expr, h_total * 4, kTagsRoom))) return rc;
         out.ent_field = T.ent_field.as<uint32_t>(); out.ent_expr = T.ent_expr.as<uint32_t>(); out.cap = h_total;
     }
     P.leaf_ent_off = T.leaf_ent_off.as<uint64_t>();
@@ -77,8 +76,7 @@ int tag_entries(gft_engine* e, const uint32_t* d_hit_bitmap, const uint32_t* d_l
     HIP_TRY(hipMemcpyAsync(h_flags, P.flags, 8, hipMemcpyDeviceToHost, st), "tag entries");
     HIP_TRY(hipMemcpyAsync(&h_total, T.leaf_ent_off.as<uint64_t>() + n_leaves, 8, hipMemcpyDeviceToHost, st), "tag entries");
     HIP_TRY(hipStreamSynchronize(st), "tag entries");
-    if (h_flags[1]) return fail(e, GFT_E_INVALID, "record batch: rec_off descends or does not end at n_leaves");
-    if (h_flags[0]) return fail(e, GFT_E_INVALID, "record batch: a leaf names a field outside the schema");
+    if ((rc = record_flags_rc(e, h_flags))) return rc;
     if (total) *total = h_total;           // (= row_off[n_records]: the offsets end at n_leaves)
     return GFT_OK;
 }
