@@ -193,6 +193,14 @@ struct gft_engine {
         DevBuf cnt, leaf_ent_off, partial, flags, row_off, ent_field, ent_expr;
     } d_tags;
 
+    // the result document of a batch's rule rows (gft_result.hip): the installed fragment table (rules_json.hpp), counts, prefix
+    // sums, scan partials and flag words of their own, the hole lengths and the text of the owned form (rules_json_owned)
+    struct ResultBufs {
+        uint64_t serial = 0;               // 0: no table installed
+        uint32_t n_exprs = 0;
+        DevBuf rule_first, name_off, name_len, expr_off, expr_len, blob, cnt, scan, partial, flags, hole_len, out_off, text;
+    } d_result;
+
     // JSON documents decoded on the device (gft_json.hip): the installed schema trie, the counts and prefix sums of a batch, the
     // record arrays of gft_group_process_jsons_device, staging for the host-pointer entry point
     struct JsonBufs {

@@ -8,6 +8,7 @@
 #include "group_host.hpp"
 #include "host_parallel.hpp"
 #include "json_paths.hpp"
+#include "rules_json.hpp"
 
 using namespace gft;
 
@@ -109,9 +110,10 @@ void result_document(gft_group* g, const std::vector<GroupFinder::DocResult>& re
     std::vector<std::string> parts(res.size());
     parallel_for(res.size(), [&](uint64_t d, unsigned) {
         std::string& o = parts[d];
+        if (what == 0) { rule_doc_text(res[d].err, res[d].rules, o); return; }     // (the text a hole of the device route gets, too)
         if (!res[d].err.empty()) { o = "{\"error\":"; dsl::json_str(res[d].err, o); o += "}"; return; }
-        o = what == 0 ? "{\"rules\":" : "{\"tags\":";
-        if (what == 0) rules_json(res[d].rules, o); else tagmap_json(res[d].tags, o);
+        o = "{\"tags\":";
+        tagmap_json(res[d].tags, o);
         o += "}";
     });
     size_t total = 2;
@@ -206,9 +208,10 @@ int gft_group_process_jsons_schema(gft_group* g, const uint8_t* json_blob, const
     if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
     GFT_GLOCK(g);
     std::vector<GroupFinder::DocResult> res;
-    int rc = g->g->ProcessJsonsSchema(json_blob, doc_off, n_docs, res, g->err);
+    GroupFinder::ResultText text{&g->result, false};
+    int rc = g->g->ProcessJsonsSchema(json_blob, doc_off, n_docs, res, g->err, &text);
     if (rc) return rc;
-    result_document(g, res, 0);
+    if (!text.written) result_document(g, res, 0);
     return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &g->err : nullptr))
 
@@ -239,9 +242,10 @@ int gft_group_process_jsons_auto(gft_group* g, const uint8_t* json_blob, const u
     std::vector<std::string> inc, exc;
     if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
     std::vector<GroupFinder::DocResult> res;
-    int rc = g->g->ProcessJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err);
+    GroupFinder::ResultText text{&g->result, false};
+    int rc = g->g->ProcessJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err, &text);
     if (rc) return rc;
-    result_document(g, res, 0);
+    if (!text.written) result_document(g, res, 0);
     return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &g->err : nullptr))
 
@@ -463,6 +467,20 @@ int gft_debug_tag_entries_device(gft_group* g, const uint32_t* d_hit_bitmap, uin
     GFT_GLOCK(g);
     return g->g->DebugTagEntriesDevice(d_hit_bitmap, n_exprs, d_leaf_field, d_rec_off, n_records, n_leaves,
                                        {d_row_off, d_ent_field, d_ent_expr, d_ent_tag, cap, total}, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_rules_json_device(gft_group* g, const uint32_t* d_rule_bitmap, uint64_t n_docs, const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap,
+                                uint64_t* d_out_off, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->RulesJsonDevice(d_rule_bitmap, n_docs, d_hole_len, d_out, cap, d_out_off, total, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_rules_json(gft_group* g, const uint32_t* rule_bitmap, uint64_t n_docs, const uint64_t* hole_len, uint8_t* out, uint64_t cap,
+                         uint64_t* out_off, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugRulesJson(rule_bitmap, n_docs, hole_len, out, cap, out_off, total, g->err);
 } GFT_CATCH((g ? &g->err : nullptr))
 
 int gft_group_last_batch(const gft_group* g, uint64_t* leaves, uint64_t* bytes) try {

@@ -17,13 +17,15 @@
 
 namespace gft {
 
+struct RuleFragments;                      // rules_json.hpp
+
 // group/finder/finder.go:12-17
 class GroupFinder {
 public:
     using ExpressionWrapper = gft::ExpressionWrapper;
     using RuleResult = std::map<std::string, std::vector<std::string>>;   // expressionsByRule
 
-    explicit GroupFinder(Finder* findthem) : findthem_(findthem) {}
+    explicit GroupFinder(Finder* findthem) : findthem_(findthem), device_result_(env_device_result()) {}
     Error AddRule(const std::string& ruleName, const std::vector<std::string>& expressions);
     std::vector<std::string> GetFieldNames() const { return {fields_.begin(), fields_.end()}; }
 
@@ -63,7 +65,12 @@ public:
     // host pointers: upload, ProcessJsonsDevice, status and rows down; documents the device did not decide go through
     // ProcessJsons as one sub-batch.  The include / exclude lists are the schema's.  A finder that does not qualify for the
     // device record route takes ProcessJsons for the whole batch.  out: as ProcessJsons with want_tags = false.
-    int ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err);
+    // text != nullptr: the caller wants the result document ('[' D0 ',' D1 ... ']', rules_json.hpp).  When the device route answers
+    // and writes it (gft_result.hip), text->written is set, the rows never cross the link and `out` stays empty; otherwise `out`
+    // is filled as without it and the caller serialises.
+    struct ResultText { std::string* text = nullptr; bool written = false; };
+    int ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err,
+                           ResultText* text = nullptr);
     // ---- the schema discovered from the batch (k_json_paths): what ProcessJson means without SetSchema
     // device pointers: the distinct paths of the batch's string values, sorted bytewise; needs no schema
     int JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, std::vector<std::string>& paths, uint64_t* dropped,
@@ -72,7 +79,7 @@ public:
     // SetSchema's) and run ProcessJsonsSchema's route on the staged batch.  out: as ProcessJsons with want_tags = false, for
     // every batch; a finder that does not qualify, or a discovered schema beyond a limit, sends the batch through ProcessJsons.
     int ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                         const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err);
+                         const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
     // what the last ProcessJsonsAuto found: paths, paths found and not kept, whether it compiled a schema
     uint64_t auto_last_paths = 0, auto_last_dropped = 0, auto_last_recompiled = 0;
     // no device: the reference classification and the kernels' walker on the host (json_schema.hpp), against the stored schema
@@ -83,6 +90,16 @@ public:
     int64_t DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field);
     // documents of the last ProcessJsonsSchema / ProcessJsonsAuto batch decided on the device / handed to ProcessJsons
     uint64_t json_last_device = 0, json_last_host = 0;
+
+    // ---- the result document of rule rows as text (rules_json.hpp, gft_result.hip): depends on the rules only, not on a schema.
+    // device pointers except total: rows [n_docs][ceil(R / 32)] as ProcessJsonsDevice / ProcessRecordsDevice leave them -> text
+    // and out_off [n_docs + 1] under the cap protocol; d_hole_len nullable.  GFT_E_UNSUPPORTED: rules whose fragment table the
+    // format cannot hold
+    int RulesJsonDevice(const uint32_t* d_rule_bitmap, uint64_t n_docs, const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap,
+                        uint64_t* d_out_off, uint64_t* total, Error& err);
+    // rules_json_host over the group's current rules: no device, no schema
+    int DebugRulesJson(const uint32_t* rule_bitmap, uint64_t n_docs, const uint64_t* hole_len, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                       uint64_t* total, Error& err);
 
     // ---- tag entries: TagObject's map of every record as a sparse list of (field, expression) pairs (gft_tags.hip, include/gft.h).
     // The arrays of one result; device pointers in the *Device calls (total is always host memory)
@@ -130,6 +147,15 @@ private:
     std::vector<RuleExpr> rule_exprs_;
     uint64_t rule_exprs_version_ = ~0ull;
 
+    // ---- the rules' fragment table (rules_json.hpp), rebuilt when rules_version_ changes; rec_ and auto_ share it
+    static bool env_device_result();       // GFT_DEVICE_RESULT=0: the result documents are serialised on the host (read at creation)
+    bool device_result_;
+    std::shared_ptr<RuleFragments> frags_; // null with frags_version_ current: refused, `frags_why_` says why
+    uint64_t frags_version_ = ~0ull, frags_serial_ = 0;
+    Error frags_why_;
+    const RuleFragments* fragments();      // the table for the current rules, or null
+    int result_ready(gft_engine* e, Error& err);   // ... installed on e, unless it is the one the engine holds (fragments() != null)
+
     // ---- a schema with what was compiled from it (group_records.hpp).  Every helper names the Records it works on: rec_ is
     // SetSchema's, auto_ the one ProcessJsonsAuto keeps between its calls, and neither route touches the other's.
     struct Records;
@@ -156,19 +182,29 @@ private:
     using ChooseRecords = std::function<std::shared_ptr<Records>(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc)>;
     int json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                    const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
-                   std::vector<DocResult>& out, Error& err);
+                   std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
     // what came down from the device for a staged batch: the status bytes, and the rule rows or the tag entries
     struct JsonStaged;
     // under the caller's RulesLock: jsons_device over the staged batch, status and rows / entries down ...
+    // (fetch_rows == false: the rule rows stay in d_rows)
     int json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
-                    uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err);
+                    uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err, bool fetch_rows = true);
+    // the documents the device did not decide (status != 0), through ProcessJsons as one sub-batch: res[k] is document host_docs[k]'s
+    int json_host_docs(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                       bool want_tags, std::vector<uint64_t>& host_docs, std::vector<DocResult>& res, Error& err);
+    // under the caller's RulesLock, behind json_staged without the rows: the undecided documents serialised on the host and left as
+    // holes, the text written on the device from d_rows, brought down into `text` and the holes copied in
+    int json_text(gft_engine* e, const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* d_rows,
+                  const JsonStaged& s, std::string& text, Error& err);
     // ... and behind it: the documents the device did not decide through ProcessJsons as one sub-batch, the others from their rows
     // or entries, a document per task
     int json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const JsonStaged& s, bool want_tags,
                      std::vector<DocResult>& out, Error& err);
-    int jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err);
+    int jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err,
+                     ResultText* text = nullptr);
     int jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                   const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err);
+                   const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err,
+                   ResultText* text = nullptr);
 };
 
 }  // namespace gft

@@ -1,12 +1,15 @@
 // group_json.cpp -- the group finder's JSON routes on the device (json_schema.hpp, gft_json.hip): documents decoded into the
 // record form against a schema's trie and sent down the record route (group_records.cpp), for the schema of SetSchema and for
 // the one discovered from the batch (json_paths.hpp: k_json_paths).
+#include <cstdlib>
 #include <cstring>
 #include <set>
 
+#include "gft_result.hpp"
 #include "group_records.hpp"
 #include "host_parallel.hpp"
 #include "json_paths.hpp"
+#include "rules_json.hpp"
 
 namespace gft {
 
@@ -64,7 +67,7 @@ int GroupFinder::jsons_device(Records& r, const uint8_t* d_blob, const uint64_t*
 }
 
 int GroupFinder::json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
-                             uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err) {
+                             uint32_t* d_rows, bool want_tags, JsonStaged& s, Error& err, bool fetch_rows) {
     s.status.assign(n_docs, 0);
     RecordsOut out;
     RecordsOut::Owned own;
@@ -72,7 +75,7 @@ int GroupFinder::json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, c
     if (want_tags) {
         out.owned = &own;
     } else {
-        s.rows.assign((size_t)(n_docs * RW) + 1, 0);
+        if (fetch_rows) s.rows.assign((size_t)(n_docs * RW) + 1, 0);
         out.d_rule_bitmap = d_rows;
     }
     int rc = jsons_device(r, d_blob, d_doc_off, n_docs, d_status, out, err);
@@ -86,10 +89,29 @@ int GroupFinder::json_staged(gft_engine* e, Records& r, const uint8_t* d_blob, c
         if ((rc = rules_fetch(e, s.row_off.data(), own.row_off, (n_docs + 1) * 8)) || (rc = rules_fetch(e, s.ent_field.data(), own.ent_field, own.total * 4)) ||
             (rc = rules_fetch(e, s.ent_expr.data(), own.ent_expr, own.total * 4)))
             err = gft_last_error(e);
-    } else if ((rc = rules_fetch(e, s.rows.data(), d_rows, n_docs * RW * 4))) {
+    } else if (fetch_rows && (rc = rules_fetch(e, s.rows.data(), d_rows, n_docs * RW * 4))) {
         err = gft_last_error(e);
     }
     return rc;
+}
+
+int GroupFinder::json_host_docs(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<uint8_t>& status,
+                                bool want_tags, std::vector<uint64_t>& host_docs, std::vector<DocResult>& res, Error& err) {
+    host_docs.clear();
+    res.clear();
+    for (uint64_t d = 0; d < n_docs; d++)
+        if (status[d]) host_docs.push_back(d);
+    if (!host_docs.empty()) {
+        std::vector<uint64_t> off(host_docs.size() + 1, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) off[k + 1] = off[k] + (doc_off[host_docs[k] + 1] - doc_off[host_docs[k]]);
+        std::vector<uint8_t> sub(off.back() + 64, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) memcpy(sub.data() + off[k], blob + doc_off[host_docs[k]], (size_t)(off[k + 1] - off[k]));
+        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), r.inc, r.exc, want_tags, res);
+        if (!err.empty()) return GFT_E_ENGINE;
+    }
+    json_last_host = host_docs.size();
+    json_last_device = n_docs - host_docs.size();
+    return GFT_OK;
 }
 
 int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const JsonStaged& s, bool want_tags,
@@ -98,20 +120,10 @@ int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint6
     const std::vector<uint8_t>& status = s.status;
     // what the device did not decide: one sub-batch through the host route
     std::vector<uint64_t> host_docs;
-    for (uint64_t d = 0; d < n_docs; d++)
-        if (status[d]) host_docs.push_back(d);
-    if (!host_docs.empty()) {
-        std::vector<uint64_t> off(host_docs.size() + 1, 0);
-        for (size_t k = 0; k < host_docs.size(); k++) off[k + 1] = off[k] + (doc_off[host_docs[k] + 1] - doc_off[host_docs[k]]);
-        std::vector<uint8_t> sub(off.back() + 64, 0);
-        for (size_t k = 0; k < host_docs.size(); k++) memcpy(sub.data() + off[k], blob + doc_off[host_docs[k]], (size_t)(off[k + 1] - off[k]));
-        std::vector<DocResult> res;
-        err = ProcessJsons(sub.data(), off.data(), host_docs.size(), r.inc, r.exc, want_tags, res);
-        if (!err.empty()) return GFT_E_ENGINE;
-        for (size_t k = 0; k < host_docs.size(); k++) out[host_docs[k]] = std::move(res[k]);
-    }
-    json_last_host = host_docs.size();
-    json_last_device = n_docs - host_docs.size();
+    std::vector<DocResult> res;
+    int rc = json_host_docs(r, blob, doc_off, n_docs, status, want_tags, host_docs, res, err);
+    if (rc) return rc;
+    for (size_t k = 0; k < host_docs.size(); k++) out[host_docs[k]] = std::move(res[k]);
     if (want_tags) {
         // a document's entries -> its tag map; the set's insert drops what a repeated field says twice
         const auto& exprs = findthem_->expressions();
@@ -138,9 +150,87 @@ int GroupFinder::json_results(const Records& r, const uint8_t* blob, const uint6
     return GFT_OK;
 }
 
+// ---- the result document written on the device ----------------------------------------------------------------------------------
+bool GroupFinder::env_device_result() {
+    const char* v = getenv("GFT_DEVICE_RESULT");
+    return !(v && v[0] == '0' && !v[1]);
+}
+
+const RuleFragments* GroupFinder::fragments() {
+    if (frags_version_ != rules_version_) {
+        auto next = std::make_shared<RuleFragments>();
+        frags_why_.clear();
+        frags_ = make_rule_fragments(RuleExprs(), *next, frags_why_) ? std::move(next) : nullptr;
+        frags_version_ = rules_version_;
+        frags_serial_ = 0;
+    }
+    return frags_.get();
+}
+
+int GroupFinder::result_ready(gft_engine* e, Error& err) {
+    const RuleFragments* fr = fragments();
+    if (!fr) { err = "result document: " + frags_why_; return GFT_E_UNSUPPORTED; }
+    if (frags_serial_ && rules_json_serial(e) == frags_serial_) return GFT_OK;
+    int rc = rules_json_install(e, *fr, &frags_serial_);
+    if (rc) { frags_serial_ = 0; err = gft_last_error(e); }
+    return rc;
+}
+
+int GroupFinder::RulesJsonDevice(const uint32_t* d_rule_bitmap, uint64_t n_docs, const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap,
+                                 uint64_t* d_out_off, uint64_t* total, Error& err) {
+    gft_engine* e = nullptr;
+    int rc = single_device_engine(findthem_, "result documents", e, err);
+    if (rc) return rc;
+    RulesLock whole_call(e);               // (another group on the same finder installs its own table)
+    if ((rc = result_ready(e, err))) return rc;
+    if ((rc = rules_json_device(e, d_rule_bitmap, n_docs, d_hole_len, d_out, cap, d_out_off, total))) err = gft_last_error(e);
+    return rc;
+}
+
+int GroupFinder::DebugRulesJson(const uint32_t* rule_bitmap, uint64_t n_docs, const uint64_t* hole_len, uint8_t* out, uint64_t cap,
+                                uint64_t* out_off, uint64_t* total, Error& err) {
+    const RuleFragments* fr = fragments();
+    if (!fr) { err = "gft_debug_rules_json: " + frags_why_; return GFT_E_UNSUPPORTED; }
+    if (!out_off || (cap && !out) || (n_docs && fr->n_exprs() && !rule_bitmap)) { err = "gft_debug_rules_json: null argument"; return GFT_E_INVALID; }
+    if (!rules_json_host(*fr, rule_bitmap, n_docs, hole_len, out, cap, out_off, total)) { err = "gft_debug_rules_json: a hole of 4 GiB or more"; return GFT_E_INVALID; }
+    return GFT_OK;
+}
+
+int GroupFinder::json_text(gft_engine* e, const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* d_rows,
+                           const JsonStaged& s, std::string& text, Error& err) {
+    // what the device did not decide: one sub-batch through the host route, every document to its final text
+    std::vector<uint64_t> host_docs;
+    std::vector<DocResult> res;
+    int rc = json_host_docs(r, blob, doc_off, n_docs, s.status, false, host_docs, res, err);
+    if (rc) return rc;
+    std::vector<std::string> hole_text(host_docs.size());
+    std::vector<uint64_t> hole_len;
+    if (!host_docs.empty()) {
+        hole_len.assign(n_docs, 0);
+        for (size_t k = 0; k < host_docs.size(); k++) {
+            rule_doc_text(res[k].err, res[k].rules, hole_text[k]);
+            hole_len[host_docs[k]] = hole_text[k].size();
+        }
+    }
+    const uint8_t* d_text = nullptr; const uint64_t* d_out_off = nullptr;
+    uint64_t total = 0;
+    if ((rc = rules_json_owned(e, d_rows, n_docs, hole_len.empty() ? nullptr : hole_len.data(), &d_text, &d_out_off, &total))) {
+        err = gft_last_error(e);
+        return rc;
+    }
+    text.resize((size_t)total);
+    if ((rc = rules_fetch(e, &text[0], d_text, total))) { err = gft_last_error(e); return rc; }
+    if (!host_docs.empty()) {
+        std::vector<uint64_t> out_off(n_docs + 1, 0);
+        if ((rc = rules_fetch(e, out_off.data(), d_out_off, (n_docs + 1) * 8))) { err = gft_last_error(e); return rc; }
+        for (size_t k = 0; k < host_docs.size(); k++) memcpy(&text[(size_t)out_off[host_docs[k]]], hole_text[k].data(), hole_text[k].size());
+    }
+    return GFT_OK;
+}
+
 int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                             const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
-                            std::vector<DocResult>& out, Error& err) {
+                            std::vector<DocResult>& out, Error& err, ResultText* text) {
     gft_engine* e = findthem_->device_engine();
     json_last_device = json_last_host = 0;
     auto by_host = [&]() {
@@ -161,17 +251,29 @@ int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64
         if (rc) { err = gft_last_error(e); return rc; }
         r = choose(e, d_blob, d_doc_off, rc);
         if (rc) return rc;
+        // the document from the rows where they are, unless the table was refused (the host serialisation is the route then)
+        const bool on_device = r && text && text->text && !want_tags && device_result_ && fragments();
+        if (on_device) {
+            if ((rc = result_ready(e, err))) return rc;
+            if ((rc = json_staged(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, false, staged, err, false))) return rc;
+            if ((rc = json_text(e, *r, blob, doc_off, n_docs, d_rows, staged, *text->text, err))) return rc;
+            text->written = true;
+            out.clear();
+            return GFT_OK;
+        }
         if (r && (rc = json_staged(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, want_tags, staged, err))) return rc;
     }
     if (!r) return by_host();
     return json_results(*r, blob, doc_off, n_docs, staged, want_tags, out, err);
 }
 
-int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err) {
-    return jsons_schema(blob, doc_off, n_docs, false, out, err);
+int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err,
+                                    ResultText* text) {
+    return jsons_schema(blob, doc_off, n_docs, false, out, err, text);
 }
 
-int GroupFinder::jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err) {
+int GroupFinder::jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err,
+                              ResultText* text) {
     Records* r = schema_records("JSON batch", err);
     if (!r) return GFT_E_INVALID;
     int rc = json_ready(nullptr, *r, err);
@@ -180,7 +282,7 @@ int GroupFinder::jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint
     if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
     // (the schema's own lists; it is compiled already, whatever the batch holds)
     return json_batch(blob, doc_off, n_docs, r->inc, r->exc, want_tags, r->row_words(),
-                      [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; }, out, err);
+                      [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; }, out, err, text);
 }
 
 // ---- the schema discovered from the batch ------------------------------------------------------------------------------------
@@ -196,12 +298,13 @@ int GroupFinder::JsonPathsDevice(const uint8_t* d_blob, const uint64_t* d_doc_of
 }
 
 int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                                  const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err) {
-    return jsons_auto(blob, doc_off, n_docs, includePaths, excludePaths, false, out, err);
+                                  const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text) {
+    return jsons_auto(blob, doc_off, n_docs, includePaths, excludePaths, false, out, err, text);
 }
 
 int GroupFinder::jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                            const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err) {
+                            const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err,
+                            ResultText* text) {
     int rc = json_check_offsets(doc_off, n_docs, err);
     if (rc) return rc;
     auto_last_paths = auto_last_dropped = auto_last_recompiled = 0;
@@ -251,7 +354,7 @@ int GroupFinder::jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64
         if (!want_tags && auto_->row_words() != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; rc = GFT_E_INTERNAL; return nullptr; }
         return auto_;
     };
-    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, RW, discover, out, err);
+    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, RW, discover, out, err, text);
 }
 
 int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {

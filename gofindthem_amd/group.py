@@ -399,6 +399,54 @@ class GroupFinder:
         head = (blob.data_ptr(), doc_off.data_ptr(), n, status.data_ptr())
         return self._entries_device(self._L.gft_group_tag_jsons_device, head, max(n, 0), cap, want_tag, blob.device), status
 
+    # -- the result document of rule rows as text (csrc/rules_json.cpp, csrc/gft_result.hip) --------------------------------------
+    TEXT_GUARD = 32                                            # bytes behind a cap in which nothing may be stored (they hold 0xA5)
+
+    def debug_rules_json(self, bitmap, hole_len=None, cap=None):
+        """gft_debug_rules_json: the contract of the result kernels in plain loops on the host (no device, no schema) over rule rows
+        u32[n_docs, ceil(R / 32)] -> (text uint8[cap + TEXT_GUARD], out_off u64[n_docs + 1], total); cap None: counted first"""
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint32)
+        n = int(bitmap.shape[0])
+        holes = None if hole_len is None else np.ascontiguousarray(hole_len, dtype=np.uint64)
+        out_off, total = np.zeros(n + 1, dtype=np.uint64), C.c_uint64(0)
+        head = (bitmap.ctypes.data, n, holes.ctypes.data if holes is not None else None)
+        if cap is None:
+            rc = self._L.gft_debug_rules_json(self._h, *head, None, 0, out_off.ctypes.data, C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        text = np.full(cap + self.TEXT_GUARD, 0xA5, dtype=np.uint8)
+        rc = self._L.gft_debug_rules_json(self._h, *head, text.ctypes.data, cap, out_off.ctypes.data, C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return text, out_off, int(total.value)
+
+    def RulesJsonDevice(self, rule_bitmap, hole_len=None, cap=None):
+        """torch device tensors: rule rows int32[n_docs, ceil(R / 32)] as ProcessJsonsDevice / ProcessRecordsDevice give them, hole
+        lengths int64[n_docs] or None -> (text uint8[cap + TEXT_GUARD] with 0xA5 behind the cap, out_off int64[n_docs + 1], total)
+        on the device; without a cap the batch is counted first and the text is sized by the total"""
+        import torch
+        dev = rule_bitmap.device
+        n = int(rule_bitmap.shape[0])
+        for t, size in ((rule_bitmap, 4),) + (((hole_len, 8),) if hole_len is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "RulesJsonDevice takes contiguous device tensors of 4 and 8 byte integers")
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64(0)
+        head = (rule_bitmap.data_ptr(), n, hole_len.data_ptr() if hole_len is not None else None)
+        torch.cuda.current_stream(dev).synchronize()           # (the library runs on the engine's own stream)
+        if cap is None:
+            rc = self._L.gft_group_rules_json_device(self._h, *head, None, 0, out_off.data_ptr(), C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        text = torch.full((cap + self.TEXT_GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self._L.gft_group_rules_json_device(self._h, *head, text.data_ptr(), cap, out_off.data_ptr(), C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return text, out_off, int(total.value)
+
     def _result_call(self, fn, rawJsons, *lists):
         """a JSON batch through an entry point that leaves a result document (fetched again, not run again, when it is larger than
         the buffer)"""

@@ -539,14 +539,41 @@ int gft_group_json_leaves_device(gft_group* g, const uint8_t* d_json_blob, const
 int gft_group_process_jsons_device(gft_group* g, const uint8_t* d_json_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status,
                                    uint32_t* d_rule_bitmap);
 /* Host pointers; the same result document as gft_group_process_jsons(..., what = 0) with the include / exclude lists given to
- * gft_group_set_schema: upload, the call above, status and rows down; a document of status 0 gets {"rules": ..} from its row,
- * all others go through gft_group_process_jsons' route as one sub-batch and take its "rules" or "error".  A finder that does
- * not qualify for the device record route (regex terms, injected engines, several devices) takes that route for the whole
- * batch.  gft_group_last_result serves this call too. */
+ * gft_group_set_schema: upload, the call above, the status down; the documents of status != 0 go through
+ * gft_group_process_jsons' route as one sub-batch and take its "rules" or "error"; the document itself is written on the device
+ * from the rows where they are (gft_group_rules_json_device, the host-decided documents as holes) and comes down as one piece of
+ * text.  GFT_DEVICE_RESULT=0, read when the group is created, or rules whose fragment table the format cannot hold: the rows
+ * come down instead and every document of status 0 gets {"rules": ..} from its row on host threads -- the same bytes.  A finder
+ * that does not qualify for the device record route (regex terms, injected engines, several devices) takes
+ * gft_group_process_jsons' route for the whole batch.  gft_group_last_result serves this call too. */
 int gft_group_process_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
                                    uint64_t* needed);
 /* documents of the last gft_group_process_jsons_schema / _auto batch decided on the device / handed to the host route */
 int gft_group_json_last(const gft_group* g, uint64_t* n_device, uint64_t* n_host);
+/* ---- The result document of rule rows, written on the device (gft_result.hip) ------------------------------------------------
+ * d_rule_bitmap [n_docs][ceil(R / 32)], as gft_group_process_jsons_device and gft_group_process_records_device leave it, ->
+ * the text '[' D0 ',' D1 ... ']' with Dd = {"rules":{"<rule>":["<expression>",..],..}}: a member per rule with a set bit, rules
+ * and expressions in bit order (gft_group_rule_expr), names and expressions escaped as gft_group_process_jsons escapes them; a
+ * row without bits gives {"rules":{}}; bits at and above R in a row's last word are ignored.  It is byte for byte the result
+ * document of gft_group_process_jsons(..., what = 0) for documents with those rule hits.  A caller with a resident blob gets
+ * the document without the rows crossing the link.  A group without rules is valid: every document is {"rules":{}}.
+ * d_out_off [n_docs + 1]: d_out_off[0] = 1, d_out_off[d + 1] = d_out_off[d] + len(d) + 1; the separator behind document d (','
+ * or the closing ']') is the byte at d_out_off[d + 1] - 1.  n_docs == 0: "[]", *total = 2.
+ * d_hole_len [n_docs], nullable: a value != 0 reserves exactly that many bytes for document d -- none of them is written and
+ * its row is not read (the caller fills in a text of its own, an {"error": ..} for instance; every real document has at least
+ * 12 bytes).  GFT_E_INVALID for a hole of 4 GiB or more.
+ * Cap protocol of gft_compact_device: d_out_off is always complete, a byte at a position >= cap is not stored and nothing is
+ * stored at or past d_out + cap, GFT_OK either way, *total (host memory, nullable) receives the text's size; d_out == NULL with
+ * cap == 0 counts only.  Every pointer but total is a device pointer.  Three launches on the engine's stream (gft_profile_read:
+ * "result_count", "result_scan", "result_fill"); the table of escaped names and expressions depends on the rules only -- no
+ * schema is needed -- and is uploaded again when rules were added.  Handles over several devices: GFT_E_UNSUPPORTED, also for
+ * rules whose escaped text does not fit 32-bit offsets.  GFT_E_NOMEM: no room for the work buffers. */
+int gft_group_rules_json_device(gft_group* g, const uint32_t* d_rule_bitmap, uint64_t n_docs, const uint64_t* d_hole_len, uint8_t* d_out,
+                                uint64_t cap, uint64_t* d_out_off, uint64_t* total);
+/* The contract above stated in plain loops on the host (host pointers) over the group's current rules.  Needs no device and no
+ * schema. */
+int gft_debug_rules_json(gft_group* g, const uint32_t* rule_bitmap, uint64_t n_docs, const uint64_t* hole_len, uint8_t* out, uint64_t cap,
+                         uint64_t* out_off, uint64_t* total);
 /* ---- The schema discovered from the batch (gft_json.hip: k_json_paths) ------------------------------------------------------
  * One more pass of the same walker, without a trie, collects the distinct paths of the batch's string values on the device:
  * a set of 2^16 64-bit path hashes (linear probing), at most 16384 paths, a pool of 8 MiB for their bytes.  A path is spelled
