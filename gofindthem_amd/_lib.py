@@ -124,6 +124,8 @@ SYMBOLS = {
     "gft_debug_tag_entries_device": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_group_rules_json_device": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "gft_debug_rules_json": (_i, [_vp, _vp, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_group_tags_json_device": (_i, [_vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_debug_tags_json": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u64, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
     "gft_group_json_leaves_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _u64, _vp]),
     "gft_group_process_jsons_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
     "gft_group_process_jsons_schema": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),

@@ -201,6 +201,19 @@ struct gft_engine {
         DevBuf rule_first, name_off, name_len, expr_off, expr_len, blob, cnt, scan, partial, flags, hole_len, out_off, text;
     } d_result;
 
+    // the tag result document of a record batch (gft_tagdoc.hip): the installed slot and field tables (tags_json.hpp), the slot
+    // rows of a batch, the staged leaf fields and record offsets (tags_json_stage), counts, prefix sums, scan partials and flag
+    // words of their own, the hole lengths and the text of the owned form (tags_json_owned)
+    struct TagDocBufs {
+        uint64_t slot_serial = 0, field_serial = 0;    // 0: no table installed
+        uint32_t n_exprs = 0, SW = 0, n_tags = 0, n_fields = 0;
+        DevBuf src_off, src_expr, slot_off, slot_len, tag_word, tag_words, tag_off, tag_len, slot_blob;
+        DevBuf field_rank, field_off, field_len, valid, field_blob;
+        DevBuf slot_rows, leaf_field, rec_off, cnt, scan, partial, flags, hole_len, out_off, text;
+        bool staged = false;                           // slot_rows, leaf_field and rec_off hold a batch of ...
+        uint64_t staged_records = 0, staged_leaves = 0;
+    } d_tagdoc;
+
     // JSON documents decoded on the device (gft_json.hip): the installed schema trie, the counts and prefix sums of a batch, the
     // record arrays of gft_group_process_jsons_device, staging for the host-pointer entry point
     struct JsonBufs {

@@ -9,6 +9,7 @@
 #include "host_parallel.hpp"
 #include "json_paths.hpp"
 #include "rules_json.hpp"
+#include "tags_json.hpp"
 
 using namespace gft;
 
@@ -56,27 +57,6 @@ void str_array(const std::vector<std::string>& v, std::string& o) {
     o += "]";
 }
 
-void tagmap_json(const gdsl::TagMap& m, std::string& o) {
-    o += "{";
-    bool f1 = true;
-    for (const auto& t : m) {
-        if (!f1) o += ",";
-        f1 = false;
-        dsl::json_str(t.first, o);
-        o += ":{";
-        bool f2 = true;
-        for (const auto& fp : t.second) {
-            if (!f2) o += ",";
-            f2 = false;
-            dsl::json_str(fp.first, o);
-            o += ":";
-            str_array({fp.second.begin(), fp.second.end()}, o);
-        }
-        o += "}";
-    }
-    o += "}";
-}
-
 void rules_json(const GroupFinder::RuleResult& r, std::string& o) {
     o += "{";
     bool first = true;
@@ -111,10 +91,7 @@ void result_document(gft_group* g, const std::vector<GroupFinder::DocResult>& re
     parallel_for(res.size(), [&](uint64_t d, unsigned) {
         std::string& o = parts[d];
         if (what == 0) { rule_doc_text(res[d].err, res[d].rules, o); return; }     // (the text a hole of the device route gets, too)
-        if (!res[d].err.empty()) { o = "{\"error\":"; dsl::json_str(res[d].err, o); o += "}"; return; }
-        o = "{\"tags\":";
-        tagmap_json(res[d].tags, o);
-        o += "}";
+        tag_doc_text(res[d].err, res[d].tags, o);
     });
     size_t total = 2;
     for (const auto& p : parts) total += p.size() + 1;
@@ -431,9 +408,10 @@ int gft_group_tag_jsons_schema(gft_group* g, const uint8_t* json_blob, const uin
     if (!g || !doc_off || (n_docs && !json_blob)) return GFT_E_INVALID;
     GFT_GLOCK(g);
     std::vector<GroupFinder::DocResult> res;
-    int rc = g->g->TagJsonsSchema(json_blob, doc_off, n_docs, res, g->err);
+    GroupFinder::ResultText text{&g->result, false};
+    int rc = g->g->TagJsonsSchema(json_blob, doc_off, n_docs, res, g->err, &text);
     if (rc) return rc;
-    result_document(g, res, 1);
+    if (!text.written) result_document(g, res, 1);
     return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &g->err : nullptr))
 
@@ -445,9 +423,10 @@ int gft_group_tag_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint6
     std::vector<std::string> inc, exc;
     if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
     std::vector<GroupFinder::DocResult> res;
-    int rc = g->g->TagJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err);
+    GroupFinder::ResultText text{&g->result, false};
+    int rc = g->g->TagJsonsAuto(json_blob, doc_off, n_docs, inc, exc, res, g->err, &text);
     if (rc) return rc;
-    result_document(g, res, 1);
+    if (!text.written) result_document(g, res, 1);
     return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &g->err : nullptr))
 
@@ -481,6 +460,21 @@ int gft_debug_rules_json(gft_group* g, const uint32_t* rule_bitmap, uint64_t n_d
     if (!g) return GFT_E_INVALID;
     GFT_GLOCK(g);
     return g->g->DebugRulesJson(rule_bitmap, n_docs, hole_len, out, cap, out_off, total, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_group_tags_json_device(gft_group* g, const uint32_t* d_hit_bitmap, const uint32_t* d_leaf_field, const uint64_t* d_rec_off, uint64_t n_records,
+                               uint64_t n_leaves, const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap, uint64_t* d_out_off, uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->TagsJsonDevice(d_hit_bitmap, d_leaf_field, d_rec_off, n_records, n_leaves, d_hole_len, d_out, cap, d_out_off, total, g->err);
+} GFT_CATCH((g ? &g->err : nullptr))
+
+int gft_debug_tags_json(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                        uint64_t n_records, uint64_t n_leaves, const uint64_t* hole_len, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                        uint64_t* total) try {
+    if (!g) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    return g->g->DebugTagsJson(hit_bitmap, n_exprs, leaf_field, rec_off, n_records, n_leaves, hole_len, out, cap, out_off, total, g->err);
 } GFT_CATCH((g ? &g->err : nullptr))
 
 int gft_group_last_batch(const gft_group* g, uint64_t* leaves, uint64_t* bytes) try {

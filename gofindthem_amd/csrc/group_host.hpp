@@ -18,6 +18,8 @@
 namespace gft {
 
 struct RuleFragments;                      // rules_json.hpp
+struct TagSlots;                           // tags_json.hpp
+struct TagFields;
 
 // group/finder/finder.go:12-17
 class GroupFinder {
@@ -113,10 +115,22 @@ public:
                    uint64_t n_leaves, const TagEntries& out, Error& err);
     // device pointers: JsonLeavesDevice into engine-owned arrays, then TagRecordsDevice; a document with status != 0 has an empty row
     int TagJsonsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint8_t* d_status, const TagEntries& d_out, Error& err);
-    // ProcessJsonsSchema / ProcessJsonsAuto for tags: out as ProcessJsons with want_tags = true
-    int TagJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err);
+    // ProcessJsonsSchema / ProcessJsonsAuto for tags: out as ProcessJsons with want_tags = true.  text != nullptr: the caller wants
+    // the result document ('[' D0 ',' D1 ... ']', tags_json.hpp); when the device route answers and writes it (gft_tagdoc.hip),
+    // text->written is set, the entries never cross the link and `out` stays empty
+    int TagJsonsSchema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, std::vector<DocResult>& out, Error& err,
+                       ResultText* text = nullptr);
     int TagJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
-                     const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err);
+                     const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
+    // ---- the tag result document as text (tags_json.hpp, gft_tagdoc.hip): depends on the finder's expressions and on the schema.
+    // device pointers except total: a leaf bitmap [n_leaves][ceil(E / 32)] with the record arrays of TagRecordsDevice -> text and
+    // out_off [n_records + 1] under the cap protocol; d_hole_len nullable.  GFT_E_UNSUPPORTED: tables the format cannot hold, and
+    // what the contract refuses of a batch (a field twice, a record beyond GFT_TAGS_JSON_MAX_LEAVES, a document of 4 GiB)
+    int TagsJsonDevice(const uint32_t* d_hit_bitmap, const uint32_t* d_leaf_field, const uint64_t* d_rec_off, uint64_t n_records, uint64_t n_leaves,
+                       const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap, uint64_t* d_out_off, uint64_t* total, Error& err);
+    // tags_json_host over the finder's current expressions and the schema: no device
+    int DebugTagsJson(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
+                      uint64_t n_leaves, const uint64_t* hole_len, uint8_t* out, uint64_t cap, uint64_t* out_off, uint64_t* total, Error& err);
     // tag_entries_host, and the three launches, over a caller-supplied leaf bitmap (host / device pointers)
     int DebugTagEntries(const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off, uint64_t n_records,
                         uint64_t n_leaves, const TagEntries& out, Error& err);
@@ -156,9 +170,24 @@ private:
     const RuleFragments* fragments();      // the table for the current rules, or null
     int result_ready(gft_engine* e, Error& err);   // ... installed on e, unless it is the one the engine holds (fragments() != null)
 
+    // ---- the tag document's tables (tags_json.hpp): the slot part is the group's, rebuilt when the finder has more expressions;
+    // the field part is a Records' (made once: a Records' schema and lists do not change)
+    std::shared_ptr<TagSlots> tslots_;     // null with tslots_n_exprs_ current: refused, `tslots_why_` says why
+    size_t tslots_n_exprs_ = ~(size_t)0;
+    uint64_t tslots_serial_ = 0;
+    Error tslots_why_;
+    const TagSlots* tag_slots();
+    struct Records;
+    const TagFields* tag_fields(Records& r);
+    // both tables for r, or GFT_E_UNSUPPORTED with the reason; e != nullptr: installed on e unless they are what the engine holds
+    int tagdoc_ready(gft_engine* e, Records& r, Error& err);
+    // under the caller's RulesLock: the staged JSON batch's tag document written on the device into `text`, the documents the
+    // device did not decide (or that are wider than GFT_TAGS_JSON_MAX_LEAVES) serialised on the host and copied into their holes
+    int json_tag_text(gft_engine* e, Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* d_blob,
+                      const uint64_t* d_doc_off, uint8_t* d_status, std::string& text, Error& err);
+
     // ---- a schema with what was compiled from it (group_records.hpp).  Every helper names the Records it works on: rec_ is
     // SetSchema's, auto_ the one ProcessJsonsAuto keeps between its calls, and neither route touches the other's.
-    struct Records;
     std::shared_ptr<Records> rec_, auto_;
     Records* schema_records(const char* what, Error& err);   // rec_, or "<what>: no schema set (gft_group_set_schema)"
     // the one way to a Records: the rule set (compile_set), then the trie into json / json_rc / json_err.  Returns the rule

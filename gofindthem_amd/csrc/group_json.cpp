@@ -261,6 +261,18 @@ int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64
             out.clear();
             return GFT_OK;
         }
+        // the tag document from the leaf rows where they are, unless a table was refused.  A batch the contract refuses, or a
+        // text the device has no room for, takes the entries route below: a call that succeeds there never fails here
+        if (r && text && text->text && want_tags && device_result_) {
+            if (!(rc = tagdoc_ready(nullptr, *r, err))) rc = json_tag_text(e, *r, blob, doc_off, n_docs, d_blob, d_doc_off, d_status, *text->text, err);
+            if (!rc) {
+                text->written = true;
+                out.clear();
+                return GFT_OK;
+            }
+            if (rc != GFT_E_NOMEM && rc != GFT_E_UNSUPPORTED) return rc;
+            err.clear();
+        }
         if (r && (rc = json_staged(e, *r, d_blob, d_doc_off, n_docs, d_status, d_rows, want_tags, staged, err))) return rc;
     }
     if (!r) return by_host();

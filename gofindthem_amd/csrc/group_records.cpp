@@ -115,7 +115,9 @@ int GroupFinder::records_device(Records& r, const uint8_t* d_text, const uint64_
         if (!err.empty()) return findthem_->last_code() ? findthem_->last_code() : GFT_E_ENGINE;
         // (the finder may have rebuilt its programs, never its expressions: the set installed above still fits)
     }
-    if (out.owned) {
+    if (out.tagdoc) {
+        rc = tags_json_stage(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, &out.tagdoc->d_rec_off);
+    } else if (out.owned) {
         rc = rules_tag_entries_owned(e, d_hit, d_leaf_field, d_rec_off, n_records, n_leaves, &out.owned->row_off, &out.owned->ent_field,
                                      &out.owned->ent_expr, &out.owned->total);
     } else if (out.d_entries) {

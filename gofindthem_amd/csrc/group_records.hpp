@@ -4,10 +4,12 @@
 #pragma once
 #include "gft_json.hpp"
 #include "gft_rules.hpp"
+#include "gft_tagdoc.hpp"
 #include "gft_tags.hpp"
 #include "group_host.hpp"
 #include "json_schema.hpp"
 #include "rule_set.hpp"
+#include "tags_json.hpp"
 
 namespace gft {
 
@@ -21,6 +23,10 @@ struct GroupFinder::Records {
     int json_rc = GFT_OK;                  // ... or why there is none: the JSON calls answer this
     Error json_err;
     uint64_t json_serial = 0;              // its copy on the engine (json_install)
+    std::shared_ptr<TagFields> tfields;    // the tag document's field table (tags_json.hpp), made on first use; null when made: refused
+    bool tfields_made = false;
+    Error tfields_why;
+    uint64_t tfields_serial = 0;           // its copy on the engine (tags_json_install)
     uint64_t row_words() const { return (uint64_t)(set.n_rules + 31) / 32; }    // of a rule bitmap row
 };
 
@@ -31,7 +37,10 @@ struct GroupFinder::RecordsOut {
     const TagEntries* d_entries = nullptr;
     struct Owned { const uint64_t* row_off = nullptr; const uint32_t* ent_field = nullptr; const uint32_t* ent_expr = nullptr; uint64_t total = 0; };
     Owned* owned = nullptr;
-    bool tags() const { return d_entries || owned; }
+    // ... or the batch staged for the tag document (tags_json_stage): `tagdoc` then names the kept copy of the record offsets
+    struct TagDoc { const uint64_t* d_rec_off = nullptr; };
+    TagDoc* tagdoc = nullptr;
+    bool tags() const { return d_entries || owned || tagdoc; }
 };
 
 struct GroupFinder::JsonStaged {

@@ -447,6 +447,56 @@ class GroupFinder:
             raise self._err(rc)
         return text, out_off, int(total.value)
 
+    # -- the tag result document as text (csrc/tags_json.cpp, csrc/gft_tagdoc.hip) ------------------------------------------------
+    def debug_tags_json(self, hit_bitmap, n_exprs, leaf_field, rec_off, hole_len=None, cap=None):
+        """gft_debug_tags_json: the contract of the tag document kernels in plain loops on the host (no device) over a leaf bitmap
+        u32[n_leaves, ceil(E / 32)] and the record arrays -> (text uint8[cap + TEXT_GUARD], out_off u64[n_records + 1], total);
+        cap None: counted first"""
+        hit_bitmap = np.ascontiguousarray(hit_bitmap, dtype=np.uint32)
+        leaf_field = np.ascontiguousarray(leaf_field, dtype=np.uint32)
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        n, n_leaves = len(rec_off) - 1, len(leaf_field)
+        holes = None if hole_len is None else np.ascontiguousarray(hole_len, dtype=np.uint64)
+        out_off, total = np.zeros(max(n, 0) + 1, dtype=np.uint64), C.c_uint64(0)
+        head = (hit_bitmap.ctypes.data, n_exprs, leaf_field.ctypes.data, rec_off.ctypes.data, n, n_leaves,
+                holes.ctypes.data if holes is not None else None)
+        if cap is None:
+            rc = self._L.gft_debug_tags_json(self._h, *head, None, 0, out_off.ctypes.data, C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        text = np.full(cap + self.TEXT_GUARD, 0xA5, dtype=np.uint8)
+        rc = self._L.gft_debug_tags_json(self._h, *head, text.ctypes.data, cap, out_off.ctypes.data, C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return text, out_off, int(total.value)
+
+    def TagsJsonDevice(self, hit_bitmap, leaf_field, rec_off, hole_len=None, cap=None):
+        """torch device tensors: a leaf bitmap int32[n_leaves, ceil(E / 32)], leaf fields int32[n_leaves], record offsets
+        int64[n_records + 1], hole lengths int64[n_records] or None -> (text uint8[cap + TEXT_GUARD] with 0xA5 behind the cap,
+        out_off int64[n_records + 1], total) on the device; without a cap the batch is counted first"""
+        import torch
+        dev = rec_off.device
+        n, n_leaves = int(rec_off.numel()) - 1, int(leaf_field.numel())
+        for t, size in ((hit_bitmap, 4), (leaf_field, 4), (rec_off, 8)) + (((hole_len, 8),) if hole_len is not None else ()):
+            if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+                raise GroupFinderError(_lib.GFT_E_INVALID, "TagsJsonDevice takes contiguous device tensors of 4, 4, 8 and 8 byte integers")
+        out_off = torch.zeros(max(n, 0) + 1, dtype=torch.int64, device=dev)
+        total = C.c_uint64(0)
+        head = (hit_bitmap.data_ptr(), leaf_field.data_ptr(), rec_off.data_ptr(), n, n_leaves, hole_len.data_ptr() if hole_len is not None else None)
+        torch.cuda.current_stream(dev).synchronize()           # (the library runs on the engine's own stream)
+        if cap is None:
+            rc = self._L.gft_group_tags_json_device(self._h, *head, None, 0, out_off.data_ptr(), C.byref(total))
+            if rc != 0:
+                raise self._err(rc)
+            cap = int(total.value)
+        text = torch.full((cap + self.TEXT_GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        rc = self._L.gft_group_tags_json_device(self._h, *head, text.data_ptr(), cap, out_off.data_ptr(), C.byref(total))
+        if rc != 0:
+            raise self._err(rc)
+        return text, out_off, int(total.value)
+
     def _result_call(self, fn, rawJsons, *lists):
         """a JSON batch through an entry point that leaves a result document (fetched again, not run again, when it is larger than
         the buffer)"""

@@ -475,10 +475,14 @@ int gft_group_tag_jsons_device(gft_group* g, const uint8_t* d_json_blob, const u
                                uint64_t* d_row_off, uint32_t* d_ent_field, uint32_t* d_ent_expr, uint32_t* d_ent_tag, uint64_t cap,
                                uint64_t* total);
 /* Host pointers; the same result document as gft_group_process_jsons(..., what = 1) with the include / exclude lists given to
- * gft_group_set_schema: upload, the call above into arrays the engine owns, status and entries down; a document of status 0 gets
- * {"tags": ..} from its entries (on host threads, a document per task), all others go through gft_group_process_jsons' route as
- * one sub-batch and take its "tags" or "error".  A finder that does not qualify takes that route for the whole batch.
- * gft_group_last_result and gft_group_json_last serve this call too. */
+ * gft_group_set_schema: upload, the documents decoded and tagged on the device, the status down; the documents of status != 0
+ * (and those of more than GFT_TAGS_JSON_MAX_LEAVES string values) go through gft_group_process_jsons' route as one sub-batch and
+ * take its "tags" or "error"; the document itself is written on the device from the leaf rows where they are
+ * (gft_group_tags_json_device, the host-decided documents as holes) and comes down as one piece of text: the entries never cross
+ * the link.  GFT_DEVICE_RESULT=0, read when the group is created, tables the format cannot hold, or no device memory for the
+ * text: the entries of gft_group_tag_jsons_device come down instead and every document of status 0 gets {"tags": ..} from them on
+ * host threads -- the same bytes.  A finder that does not qualify (regex terms, injected engines, several devices) takes
+ * gft_group_process_jsons' route for the whole batch.  gft_group_last_result and gft_group_json_last serve this call too. */
 int gft_group_tag_jsons_schema(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, char* out, uint64_t cap,
                                uint64_t* needed);
 /* TagJson as the reference has it: no schema.  As gft_group_process_jsons_auto -- the schema discovered from the batch, kept
@@ -574,6 +578,34 @@ int gft_group_rules_json_device(gft_group* g, const uint32_t* d_rule_bitmap, uin
  * schema. */
 int gft_debug_rules_json(gft_group* g, const uint32_t* rule_bitmap, uint64_t n_docs, const uint64_t* hole_len, uint8_t* out, uint64_t cap,
                          uint64_t* out_off, uint64_t* total);
+/* ---- The tag result document, written on the device (gft_tagdoc.hip) ----------------------------------------------------------
+ * A leaf bitmap d_hit_bitmap [n_leaves][ceil(E / 32)] (E = the finder's expressions, as gft_finder_process_device leaves it over
+ * the leaves as documents) with the record arrays of gft_group_tag_records_device -> the text '[' D0 ',' D1 ... ']' with
+ * Dd = {"tags":{"<tag>":{"<field path>":["<expression>",..],..},..}}: a member per tag matched in a valid field of record d, tags
+ * ascending bytewise; inside it a member per such field, paths ascending bytewise; inside that the distinct expression strings of
+ * the tag that are true in the field, ascending bytewise; everything escaped as gft_group_process_jsons escapes it.  A record
+ * without such a hit gives {"tags":{}}; bits at and above E are ignored; a leaf whose field the include / exclude lists take out
+ * contributes nothing.  It is byte for byte the result document of gft_group_process_jsons(..., what = 1) for documents with
+ * those leaves.  The order is compiled into tables once -- a slot per distinct (tag, expression string), a rank per field -- so no
+ * entry is sorted: four launches on the engine's stream (gft_profile_read: "tagdoc_slots", "tagdoc_count", "tagdoc_scan",
+ * "tagdoc_fill").  Needs a schema (gft_group_set_schema); the tables are uploaded again when expressions were added or the schema
+ * changed.
+ * d_out_off, d_hole_len, the cap protocol, n_records == 0 and total: exactly those of gft_group_rules_json_device (every real
+ * document has at least 11 bytes).
+ * GFT_E_INVALID: what gft_group_tag_records_device refuses of a batch, a hole of 4 GiB or more.  GFT_E_UNSUPPORTED -- "serialise
+ * on the host", the handle answers afterwards --: a record that names a valid field twice, a record of more than
+ * GFT_TAGS_JSON_MAX_LEAVES leaves that is not a hole, a document whose length + 1 does not fit 32 bits, tables whose escaped
+ * text does not fit 32-bit offsets, handles over several devices.  GFT_E_NOMEM: no room for the work buffers (n_leaves times the
+ * slot row's words among them). */
+#define GFT_TAGS_JSON_MAX_LEAVES 1024
+int gft_group_tags_json_device(gft_group* g, const uint32_t* d_hit_bitmap, const uint32_t* d_leaf_field, const uint64_t* d_rec_off,
+                               uint64_t n_records, uint64_t n_leaves, const uint64_t* d_hole_len, uint8_t* d_out, uint64_t cap,
+                               uint64_t* d_out_off, uint64_t* total);
+/* The contract above stated in plain loops on the host (host pointers); n_exprs must be the finder's number of expressions.
+ * Needs no device. */
+int gft_debug_tags_json(gft_group* g, const uint32_t* hit_bitmap, uint32_t n_exprs, const uint32_t* leaf_field, const uint64_t* rec_off,
+                        uint64_t n_records, uint64_t n_leaves, const uint64_t* hole_len, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                        uint64_t* total);
 /* ---- The schema discovered from the batch (gft_json.hip: k_json_paths) ------------------------------------------------------
  * One more pass of the same walker, without a trie, collects the distinct paths of the batch's string values on the device:
  * a set of 2^16 64-bit path hashes (linear probing), at most 16384 paths, a pool of 8 MiB for their bytes.  A path is spelled
