@@ -221,6 +221,12 @@ int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uin
     return GFT_OK;
 } GFT_CATCH(nullptr)
 
+int gft_debug_pool_entries(const gft_engine* e, uint64_t* entries) {
+    if (!e || !entries) return GFT_E_INVALID;
+    *entries = e->pool.total;
+    return GFT_OK;
+}
+
 int gft_debug_host_solve(const uint32_t* words, uint64_t len, const uint32_t* slots, const uint64_t* list_off,
                          const int64_t* positions, uint32_t n_lists, int* out) try {
     if (!words || !out || (n_lists && (!slots || !list_off))) return GFT_E_INVALID;

@@ -286,13 +286,15 @@ struct Scan2Params {
     uint32_t* pool_pos;
     uint64_t* unit_start;
     uint32_t* unit_count;
-    uint64_t* n_matches;         // exact number of matches (the cursor includes slab slack)
+    uint64_t* n_matches;         // exact number of pool entries written (the cursor includes slab slack): one per match -- on a
+                                 // presence-only launch k_scan5 writes the terms of a short-term record once per unit (short_trip)
     uint32_t slab;               // pool entries a wave reserves per global atomic (<= kScan2Slab)
     uint32_t ordered;            // 1: per-lane staging path for every unit (cross-check); 0: balanced path, staging only on overflow
     uint64_t text_bytes;         // size of the text blob (loads behind a window must not run past it)
     uint32_t prio;               // 1 (default): graded wave priorities (s_setprio) -- filter 0 < list build 1 < stage A 2 <
                                  // stage B 3; 0: off
-    uint32_t want_pos;           // 0: presence only -- no expression has an INORD group, pool_pos is not written
+    uint32_t want_pos;           // 0: presence only -- no expression has an INORD group, pool_pos is not written and a unit's
+                                 // entries are a SET of its terms (a term at least once; k_scan5 drops repeats of short terms)
     uint32_t dbg;                // GFT_SCAN_DEBUG bits (timing studies only): 1 = skip verification, 2 = count flags
     uint32_t* nonascii;          // fold only: *nonascii |= 1 when the text holds a byte >= 0x80 (nullptr: not wanted)
     uint64_t* dbg_counters;      // [4] when dbg & 2: flagged positions, table probes, entries compared, -
@@ -338,6 +340,7 @@ hipError_t launch_scan4(const Scan2Params& P, uint32_t waves, unsigned n_cus, hi
 constexpr uint32_t kScan5Waves = 16;             // waves per workgroup (one LDS copy of the tables per CU)
 constexpr uint32_t kScan5MaxGroups = 27;         // filter groups: G^3 x 8 bytes of LDS (G <= 32: a group is a bit of a 32-bit word)
 constexpr uint32_t kScan5SurvX = 64;              // stage A hands the window keys of a unit's first survivors to stage B through LDS
+constexpr uint32_t kScan5SeenWords = 8;          // presence-only launches: one bit per LDS short-term record id (< 255) that the unit has emitted
 constexpr uint32_t kScan5CandCapMin = 384;       // flagged positions of one unit listed in LDS at least (more when LDS is left)
 struct Scan5Plan { uint32_t G, dual_entries, cand_cap, fifo_cap; };
 // filter groups and list capacities that fit lds_max with kScan5Waves waves; false if nothing fits

@@ -46,6 +46,10 @@ struct Ctx5 {
     uint64_t dbase;              // ... at this entry
     uint32_t term_bits, pos_base;
 };
+// the short-term records (LDS ids, < 255) that this walk of the unit has emitted, one bit each: kScan5SeenWords words of the
+// wave's LDS region behind the fifo and the survivors' keys (presence-only launches, short_trip)
+typedef __attribute__((address_space(3))) uint32_t lds_w32;
+__device__ __forceinline__ lds_w32* scan5_seen(const Ctx5& o) { return (lds_w32*)(o.fifo + o.fifo_cap + kScan5SurvX); }
 
 __device__ __forceinline__ void out_append(const Scan2Params& P, Ctx5& o, bool em, uint32_t term, uint32_t pos) {
     const uint64_t mask = __ballot(em);
@@ -77,7 +81,17 @@ __device__ __forceinline__ void short_trip(const Ctx& c, Ctx5& o, uint32_t ubase
     const bool on = lane < n;
     const uint32_t job = o.fifo[o.fifo_cap - 1 - (o.npend - n) - (on ? lane : 0)];
     o.npend -= n;
-    const uint32_t p = ubase + (job & 0xFFFFu), sid = on ? job >> 16 : 0;
+    const uint32_t p = ubase + (job & 0xFFFFu);
+    uint32_t sid = on ? job >> 16 : 0;
+    // Presence only (no INORD group, no CSR: the one reader ORs a unit's entries into its presence matrix): a record's terms
+    // are written ONCE per walk of a unit.  The returning OR is serialised by the LDS unit, so of the lanes of this trip and
+    // of every earlier one that hold the same record exactly one finds its bit clear.  A job at p < 3 may stand in front of
+    // terms its record holds (L > p + 1): it emits as ever and leaves the bit alone, a later one then emits the whole record
+    // (measured and set aside: the same OR in park_short, so that a record seen is not parked again -- DESIGN.md 4.1c)
+    if (!c.P.want_pos && sid && p >= 3) {
+        const uint32_t bit = 1u << (sid & 31);
+        if (__hip_atomic_fetch_or(scan5_seen(o) + (sid >> 5), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) & bit) sid = 0;
+    }
     uint32_t r[3] = {0, 0, 0};
     if (sid) {
         const uint32_t* src = c.lrec + 3 * sid;
@@ -120,7 +134,9 @@ __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase
 // ---- short terms over an alphabet too large for the direct K^3 table (SG = true): the tables of the stride-2 kernel
 // (scan3_tables.hpp) -- a record id per 3-window of byte GROUPS, records of up to three {term | len << 28, the term's bytes
 // as text[e-3 .. e]} -- so a record's terms are verified against the text (gft_scan3.hip stage_s).  Stage A parks {position,
-// record id}; ids of 255 name cells whose records live in global memory (short3_big / srec_big) ------------------------------
+// record id}; ids of 255 name cells whose records live in global memory (short3_big / srec_big).  These trips emit every
+// occurrence on presence-only launches too: a record id names a 3-window of GROUPS here and its terms are verified against the
+// text, so two positions with one id can differ in what they emit -- short_trip's once-per-record rule does not carry over --
 __device__ __forceinline__ void short_trip_g(const Ctx& c, Ctx5& o, lds_u8* lsg, uint32_t ubase, uint32_t n) {
     const Scan2Params& P = c.P;
     const uint32_t lane = lane_id();
@@ -269,11 +285,12 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
     if (DBG && (P.dbg & 128)) return;                            // timing study: launch + table staging alone
 
     const uint32_t lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // per-wave LDS region: [fifo: fifo_cap x 4 B][window keys of the first survivors: kScan5SurvX x 4 B][candidate list: cand_cap x 2 B]
-    uint8_t* wave_lds = wave_lds_all + (size_t)wave * (P.s5_fifo_cap * 4 + kScan5SurvX * 4 + ((P.cand_cap * 2 + 15) & ~15u));
+    // per-wave LDS region (scan5_wave_lds): [fifo: fifo_cap x 4 B][window keys of the first survivors: kScan5SurvX x 4 B]
+    // [short-term records emitted: kScan5SeenWords x 4 B, scan5_seen][candidate list: cand_cap x 2 B]
+    uint8_t* wave_lds = wave_lds_all + (size_t)wave * (P.s5_fifo_cap * 4 + kScan5SurvX * 4 + kScan5SeenWords * 4 + ((P.cand_cap * 2 + 15) & ~15u));
     uint32_t* fifo = reinterpret_cast<uint32_t*>(wave_lds);
     uint32_t* survx = fifo + P.s5_fifo_cap;
-    uint16_t* cand = reinterpret_cast<uint16_t*>(survx + kScan5SurvX);
+    uint16_t* cand = reinterpret_cast<uint16_t*>(survx + kScan5SurvX + kScan5SeenWords);
     const uint32_t G = __builtin_amdgcn_readfirstlane(P.s5_G);
     const uint32_t kp = __builtin_amdgcn_readfirstlane(P.kp), kp2 = __builtin_amdgcn_readfirstlane(kp * kp);
     lds_u8* lgrp = (lds_u8*)0;
@@ -453,6 +470,9 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
         const uint32_t ftotal = lane_value(fincl, 63);
         for (uint32_t walk = 0; walk < 2 && ftotal; walk++) {
             o.nf = 0; o.npend = 0; o.lost = false;
+            // (every walk emits a record's terms again -- the second one counts from nf = 0 like the first; the list build's
+            // wave_lds_sync stands between this and the first short-term trip)
+            if (lane < kScan5SeenWords) scan5_seen(o)[lane] = 0;
             for (uint32_t l0 = 0; l0 < 64;) {
                 const uint32_t before = l0 ? lane_value(fincl, l0 - 1) : 0;
                 const bool fits = lane >= l0 && fincl - before <= P.cand_cap;
@@ -695,7 +715,7 @@ static size_t scan5_fixed_lds(uint32_t dual_entries, uint32_t short3_bytes, uint
     return ((768 + (size_t)dual_entries * 8 + short3_bytes + fpt_lds_bytes + (size_t)shorts_words * 4 + 15) & ~(size_t)15) + 16;
 }
 static size_t scan5_wave_lds(uint32_t fifo_cap, uint32_t cand_cap) {
-    return (size_t)fifo_cap * 4 + kScan5SurvX * 4 + (((size_t)cand_cap * 2 + 15) & ~(size_t)15);
+    return (size_t)fifo_cap * 4 + kScan5SurvX * 4 + kScan5SeenWords * 4 + (((size_t)cand_cap * 2 + 15) & ~(size_t)15);
 }
 
 bool scan5_plan(uint32_t kp, uint32_t short3_bytes, uint32_t shorts_words, uint32_t fpt_lds_bytes, size_t lds_max, uint32_t fifo_cap, Scan5Plan* out) {

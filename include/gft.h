@@ -754,6 +754,14 @@ int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fi
  * follows (gft_debug_learn's fifo_cap).  No HIP device is needed and no handle is built. */
 int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uint32_t n_terms, uint64_t lds_max, const char* forced_kernel,
                         const char** kernel, uint32_t* plan);
+/* The entries that the scan of the handle's last completed batch wrote to the match pool (the scan kernel's own count, as the
+ * batch's verdict read it back; a batch of gft_process_device_begin counts once its _end has returned).  With positions
+ * (gft_scan*, or any INORD group among the expressions) that is the number of matches.  Without them the pool is read as a
+ * set of terms per work unit, and k_scan5 writes the terms of a short-term record (the terms of one to three bytes that end
+ * at one 3-window; the direct table of alphabets of up to 32 byte classes) once per unit, however often the window occurs
+ * at end offsets >= 3 of the document; occurrences that end at offsets 0..2 and terms of four bytes or more are written
+ * every time. */
+int gft_debug_pool_entries(const gft_engine* e, uint64_t* entries);
 
 /* The judgement on a batch alone, on the host (csrc/batch_verdict.cpp): decodes the seven 64-bit words of a control-block
  * read-back and judges them against what a deferred scan launch knew -- single / epoch (its unit table came from the
