@@ -124,6 +124,9 @@ public:
     const std::vector<std::string>& tags() const { return tags_; }
     const std::vector<uint32_t>& tag_ids() const { return tag_ids_; }
     Error ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
+    // gft_split_lines_device on the finder's engine, for a blob that ProcessDevice is to take next: what ProcessDevice needs of the
+    // finder, refused in its words
+    Error SplitLinesDevice(const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap, uint64_t* n_docs);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

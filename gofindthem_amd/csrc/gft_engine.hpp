@@ -178,6 +178,10 @@ struct gft_engine {
         DevBuf page, delta, doc_units, unit_base, units, partial, unit_cnt, unit_out, ctl, text, off;
     } d_lw;
 
+    // a blob cut into line documents (gft_split.hip): tile summaries, the carry in front of every tile, counts, their prefix
+    // sums and scan partials of its own
+    struct SplitBufs { DevBuf sums, carry, cnt, base, partial; } d_split;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

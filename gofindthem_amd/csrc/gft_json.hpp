@@ -65,5 +65,10 @@ int json_paths_device(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_do
 // rule bitmap rows
 int json_stage(gft_engine* e, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint64_t row_bytes, const uint8_t** d_blob,
                const uint64_t** d_doc_off, uint8_t** d_status, uint32_t** d_rows);
+// ... and a blob of JSON Lines: uploaded once, cut into documents where it lies (gft_split_lines_device, GFT_SPLIT_JSON_LINES:
+// one call when the offsets fit the buffer kept from earlier batches, else a second one into a larger buffer); h_doc_off receives
+// the n_docs + 1 offsets, which the host route needs for the documents the device does not decide
+int json_stage_lines(gft_engine* e, const uint8_t* blob, uint64_t len, uint64_t row_bytes, const uint8_t** d_blob, const uint64_t** d_doc_off,
+                     uint8_t** d_status, uint32_t** d_rows, std::vector<uint64_t>& h_doc_off);
 
 }  // namespace gft

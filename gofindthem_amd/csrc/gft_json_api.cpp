@@ -219,4 +219,31 @@ int json_stage(gft_engine* e, const uint8_t* blob, const uint64_t* doc_off, uint
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))
 
+int json_stage_lines(gft_engine* e, const uint8_t* blob, uint64_t len, uint64_t row_bytes, const uint8_t** d_blob, const uint64_t** d_doc_off,
+                     uint8_t** d_status, uint32_t** d_rows, std::vector<uint64_t>& h_doc_off) try {
+    if (!e || (len && !blob) || !d_blob || !d_doc_off || !d_status || !d_rows) return GFT_E_INVALID;
+    GFT_LOCK(e);
+    int rc = json_entry_checks(e);
+    if (rc) return rc;
+    DeviceGuard g(e->device);
+    SyncOnExit drain(e);
+    auto& J = e->d_json;
+    if ((rc = room(e, J.blob, len + 64, kJsonRoom)) || (rc = room(e, J.doc_off, 16, kJsonRoom))) return rc;
+    if (len) HIP_TRY(hipMemcpyAsync(J.blob.p, blob, len, hipMemcpyHostToDevice, e->stream), "JSON batch upload");
+    HIP_TRY(hipMemsetAsync(J.blob.as<uint8_t>() + len, 0, 64, e->stream), "JSON batch upload");
+    uint64_t n = 0;
+    for (int round = 0;; round++) {
+        const uint64_t cap = J.doc_off.cap / 8;
+        if ((rc = gft_split_lines_device(e, J.blob.as<uint8_t>(), len, GFT_SPLIT_JSON_LINES, J.doc_off.as<uint64_t>(), cap, &n))) return rc;
+        if (n + 1 <= cap) break;
+        if (round) return fail(e, GFT_E_INTERNAL, "JSON Lines: the offsets do not fit the buffer grown for them");
+        if ((rc = room(e, J.doc_off, (n + 1) * 8, kJsonRoom))) return rc;
+    }
+    if ((rc = room(e, J.status, n, kJsonRoom)) || (rc = room(e, J.rows, n * row_bytes, kJsonRoom))) return rc;
+    h_doc_off.assign(n + 1, 0);
+    if ((rc = d2h_staged(e, h_doc_off.data(), J.doc_off.p, (n + 1) * 8))) return rc;
+    *d_blob = J.blob.as<uint8_t>(); *d_doc_off = J.doc_off.as<uint64_t>(); *d_status = J.status.as<uint8_t>(); *d_rows = J.rows.as<uint32_t>();
+    return GFT_OK;
+} GFT_CATCH((e ? &e->err : nullptr))
+
 }  // namespace gft

@@ -226,6 +226,20 @@ int gft_group_process_jsons_auto(gft_group* g, const uint8_t* json_blob, const u
     return put(g->result, out, cap, needed);
 } GFT_CATCH((g ? &g->err : nullptr))
 
+int gft_group_process_json_lines(gft_group* g, const uint8_t* blob, uint64_t len, const uint8_t* include_json, uint64_t include_len,
+                                 const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap, uint64_t* needed) try {
+    if (!g || (len && !blob)) return GFT_E_INVALID;
+    GFT_GLOCK(g);
+    std::vector<std::string> inc, exc;
+    if (!string_list(include_json, include_len, inc, g->err) || !string_list(exclude_json, exclude_len, exc, g->err)) return GFT_E_INVALID;
+    std::vector<GroupFinder::DocResult> res;
+    GroupFinder::ResultText text{&g->result, false};
+    int rc = g->g->ProcessJsonLines(blob, len, inc, exc, res, g->err, &text);
+    if (rc) return rc;
+    if (!text.written) result_document(g, res, 0);
+    return put(g->result, out, cap, needed);
+} GFT_CATCH((g ? &g->err : nullptr))
+
 int gft_group_json_auto_last(const gft_group* g, uint64_t* n_paths, uint64_t* dropped, uint64_t* recompiled) try {
     if (!g) return GFT_E_INVALID;
     GFT_GLOCK(g);

@@ -82,6 +82,12 @@ public:
     // every batch; a finder that does not qualify, or a discovered schema beyond a limit, sends the batch through ProcessJsons.
     int ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                          const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
+    // host pointers, JSON Lines: the blob is uploaded once and cut into documents where it lies (gft_split_lines_device,
+    // GFT_SPLIT_JSON_LINES), the offsets come down, and ProcessJsonsSchema's route (a schema is set: the lists must be empty,
+    // GFT_E_INVALID otherwise) or ProcessJsonsAuto's (none is set) continues from the resident blob.  A finder that does not
+    // qualify splits on the host (split_lines_host) and takes ProcessJsons.
+    int ProcessJsonLines(const uint8_t* blob, uint64_t len, const std::vector<std::string>& includePaths,
+                         const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
     // what the last ProcessJsonsAuto found: paths, paths found and not kept, whether it compiled a schema
     uint64_t auto_last_paths = 0, auto_last_dropped = 0, auto_last_recompiled = 0;
     // no device: the reference classification and the kernels' walker on the host (json_schema.hpp), against the stored schema
@@ -208,10 +214,13 @@ private:
     // TagJsonsSchema / TagJsonsAuto (want_tags == true: tag entries): a finder that does not qualify sends it through ProcessJsons
     // (with the lists given); else the batch is uploaded (rule rows: with rows of row_words words) and, under the engine's lock,
     // `choose` names the Records that answer it -- null with rc == 0: ProcessJsons after all.
-    using ChooseRecords = std::function<std::shared_ptr<Records>(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc)>;
+    // lines != nullptr: the batch is a blob of lines->len bytes of JSON Lines -- doc_off and n_docs are not read; the blob is cut
+    // where it is staged (or by split_lines_host on the host route) and lines->off receives the offsets the routes go on with.
+    struct JsonLines { uint64_t len = 0; std::vector<uint64_t> off; };
+    using ChooseRecords = std::function<std::shared_ptr<Records>(gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, int& rc)>;
     int json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                    const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
-                   std::vector<DocResult>& out, Error& err, ResultText* text = nullptr);
+                   std::vector<DocResult>& out, Error& err, ResultText* text = nullptr, JsonLines* lines = nullptr);
     // what came down from the device for a staged batch: the status bytes, and the rule rows or the tag entries
     struct JsonStaged;
     // under the caller's RulesLock: jsons_device over the staged batch, status and rows / entries down ...
@@ -230,10 +239,10 @@ private:
     int json_results(const Records& r, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const JsonStaged& s, bool want_tags,
                      std::vector<DocResult>& out, Error& err);
     int jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err,
-                     ResultText* text = nullptr);
+                     ResultText* text = nullptr, JsonLines* lines = nullptr);
     int jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                    const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err,
-                   ResultText* text = nullptr);
+                   ResultText* text = nullptr, JsonLines* lines = nullptr);
 };
 
 }  // namespace gft

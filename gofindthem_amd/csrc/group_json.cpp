@@ -6,6 +6,7 @@
 #include <set>
 
 #include "gft_result.hpp"
+#include "gft_split.hpp"
 #include "group_records.hpp"
 #include "host_parallel.hpp"
 #include "json_paths.hpp"
@@ -230,10 +231,20 @@ int GroupFinder::json_text(gft_engine* e, const Records& r, const uint8_t* blob,
 
 int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                             const std::vector<std::string>& excludePaths, bool want_tags, uint64_t row_words, const ChooseRecords& choose,
-                            std::vector<DocResult>& out, Error& err, ResultText* text) {
+                            std::vector<DocResult>& out, Error& err, ResultText* text, JsonLines* lines) {
     gft_engine* e = findthem_->device_engine();
     json_last_device = json_last_host = 0;
-    auto by_host = [&]() {
+    auto by_host = [&]() -> int {
+        if (lines && lines->off.empty()) {     // (not split on the device: the kernels' walk on the host)
+            uint64_t n = 0;
+            int rc = split_lines_host(blob, lines->len, GFT_SPLIT_JSON_LINES, nullptr, 0, &n);
+            lines->off.assign(n + 1, 0);
+            if (!rc) rc = split_lines_host(blob, lines->len, GFT_SPLIT_JSON_LINES, lines->off.data(), n + 1, &n);
+            if (rc) { err = "JSON Lines: the blob could not be split"; return rc; }
+            doc_off = lines->off.data();
+            n_docs = n;
+            if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
+        }
         err = ProcessJsons(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, out);
         json_last_host = n_docs;
         return err.empty() ? GFT_OK : GFT_E_ENGINE;
@@ -241,15 +252,22 @@ int GroupFinder::json_batch(const uint8_t* blob, const uint64_t* doc_off, uint64
     // regex terms, injected engines, several devices: the walk on host threads, for every document
     if (!e || !findthem_->device_resident_ok() || gft_n_devices(e) != 1) return by_host();
     out.assign(n_docs, DocResult());
-    if (!n_docs) return GFT_OK;
+    if (!n_docs && !(lines && lines->len)) return GFT_OK;
     JsonStaged staged;
     std::shared_ptr<Records> r;            // (held to the end: the call's own, whatever becomes of the member it came from)
     {
         RulesLock whole_call(e);           // (the staging buffers, from the upload to the read of the rows)
         const uint8_t* d_blob = nullptr; const uint64_t* d_doc_off = nullptr; uint8_t* d_status = nullptr; uint32_t* d_rows = nullptr;
-        int rc = json_stage(e, blob, doc_off, n_docs, want_tags ? 0 : row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows);
+        int rc = lines ? json_stage_lines(e, blob, lines->len, want_tags ? 0 : row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows, lines->off)
+                       : json_stage(e, blob, doc_off, n_docs, want_tags ? 0 : row_words * 4, &d_blob, &d_doc_off, &d_status, &d_rows);
         if (rc) { err = gft_last_error(e); return rc; }
-        r = choose(e, d_blob, d_doc_off, rc);
+        if (lines) {                           // the batch's shape is known only now
+            doc_off = lines->off.data();
+            n_docs = lines->off.size() - 1;
+            out.assign(n_docs, DocResult());
+            if (!n_docs) return GFT_OK;
+        }
+        r = choose(e, d_blob, d_doc_off, n_docs, rc);
         if (rc) return rc;
         // the document from the rows where they are, unless the table was refused (the host serialisation is the route then)
         const bool on_device = r && text && text->text && !want_tags && device_result_ && fragments();
@@ -285,16 +303,16 @@ int GroupFinder::ProcessJsonsSchema(const uint8_t* blob, const uint64_t* doc_off
 }
 
 int GroupFinder::jsons_schema(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, bool want_tags, std::vector<DocResult>& out, Error& err,
-                              ResultText* text) {
+                              ResultText* text, JsonLines* lines) {
     Records* r = schema_records("JSON batch", err);
     if (!r) return GFT_E_INVALID;
     int rc = json_ready(nullptr, *r, err);
     if (rc) return rc;
     if ((rc = compile(*r, err))) return rc;
-    if ((rc = json_check_offsets(doc_off, n_docs, err))) return rc;
+    if (!lines && (rc = json_check_offsets(doc_off, n_docs, err))) return rc;
     // (the schema's own lists; it is compiled already, whatever the batch holds)
     return json_batch(blob, doc_off, n_docs, r->inc, r->exc, want_tags, r->row_words(),
-                      [&](gft_engine*, const uint8_t*, const uint64_t*, int&) { return rec_; }, out, err, text);
+                      [&](gft_engine*, const uint8_t*, const uint64_t*, uint64_t, int&) { return rec_; }, out, err, text, lines);
 }
 
 // ---- the schema discovered from the batch ------------------------------------------------------------------------------------
@@ -316,13 +334,13 @@ int GroupFinder::ProcessJsonsAuto(const uint8_t* blob, const uint64_t* doc_off, 
 
 int GroupFinder::jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const std::vector<std::string>& includePaths,
                             const std::vector<std::string>& excludePaths, bool want_tags, std::vector<DocResult>& out, Error& err,
-                            ResultText* text) {
-    int rc = json_check_offsets(doc_off, n_docs, err);
+                            ResultText* text, JsonLines* lines) {
+    int rc = lines ? (int)GFT_OK : json_check_offsets(doc_off, n_docs, err);
     if (rc) return rc;
     auto_last_paths = auto_last_dropped = auto_last_recompiled = 0;
     const uint64_t RW = (RuleExprs().size() + 31) / 32;      // (a bit per rule expression, whatever the schema)
     // auto_ for the staged batch, or null: a limit of the schema's compilers, the host route for every document
-    auto discover = [&](gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, int& rc) -> std::shared_ptr<Records> {
+    auto discover = [&](gft_engine* e, const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, int& rc) -> std::shared_ptr<Records> {
         std::vector<std::string> found;
         if ((rc = json_paths_device(e, d_blob, d_doc_off, n_docs, found, &auto_last_dropped))) { err = gft_last_error(e); return nullptr; }
         auto_last_paths = found.size();
@@ -366,7 +384,20 @@ int GroupFinder::jsons_auto(const uint8_t* blob, const uint64_t* doc_off, uint64
         if (!want_tags && auto_->row_words() != RW) { err = "ProcessJsonsAuto: the rule set's rows are not those the batch was staged for"; rc = GFT_E_INTERNAL; return nullptr; }
         return auto_;
     };
-    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, RW, discover, out, err, text);
+    return json_batch(blob, doc_off, n_docs, includePaths, excludePaths, want_tags, RW, discover, out, err, text, lines);
+}
+
+// ---- JSON Lines: the batch arrives as one blob, a document a line ----------------------------------------------------------------
+int GroupFinder::ProcessJsonLines(const uint8_t* blob, uint64_t len, const std::vector<std::string>& includePaths,
+                                  const std::vector<std::string>& excludePaths, std::vector<DocResult>& out, Error& err, ResultText* text) {
+    JsonLines lines;
+    lines.len = len;
+    if (!rec_) return jsons_auto(blob, nullptr, 0, includePaths, excludePaths, false, out, err, text, &lines);
+    if (!includePaths.empty() || !excludePaths.empty()) {
+        err = "ProcessJsonLines: a schema is set, its include and exclude lists answer (pass none)";
+        return GFT_E_INVALID;
+    }
+    return jsons_schema(blob, nullptr, 0, false, out, err, text, &lines);
 }
 
 int64_t GroupFinder::DebugJsonFind(int64_t parent, const uint8_t* key, uint32_t key_len, int64_t* field) {

@@ -23,6 +23,51 @@ def pack(strs):
     return blob, off
 
 
+SPLIT_AFTER_NL, SPLIT_JSON_LINES = 0, 1      # gft_split_mode
+
+
+def split_lines_tensor(call, buf, length, mode):
+    """what Engine.split_lines_device and the finders' line calls share: `call(d_blob, len, mode, d_doc_off, cap, byref(n))` is
+    gft_split_lines_device on some handle and raises on an error.  Two calls: count only, then into a tensor of n + 1 entries"""
+    import torch
+    length = int(length)
+    if not buf.is_cuda or buf.dtype != torch.uint8 or not buf.is_contiguous() or length < 0 or buf.numel() < length + 64:
+        raise ValueError("split_lines_device takes a contiguous torch.uint8 device tensor of at least length + 64 bytes")
+    torch.cuda.current_stream(buf.device).synchronize()
+    n = C.c_uint64(0)
+    call(buf.data_ptr(), length, mode, None, 0, C.byref(n))
+    off = torch.empty(int(n.value) + 1, dtype=torch.int64, device=buf.device)
+    torch.cuda.current_stream(buf.device).synchronize()
+    call(buf.data_ptr(), length, mode, off.data_ptr(), off.numel(), C.byref(n))
+    return off
+
+
+def split_lines_host(data, mode, cap=None, guard=0):
+    """gft_debug_split_lines over a bytes object -> (n, doc_off uint64 [cap + guard]); no device needed.  cap=None: count first,
+    then n + 1 entries; the guard entries behind cap hold 0xA5.. and must come back untouched"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = C.c_uint64(0)
+
+    def call(off, cap):
+        rc = L.gft_debug_split_lines(a.ctypes.data if a.size else None, a.size, mode, off.ctypes.data if off is not None else None, cap, C.byref(n))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_split_lines")
+    if cap is None:
+        call(None, 0)
+        cap = int(n.value) + 1
+    off = np.full(cap + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    call(off, cap)
+    return int(n.value), off
+
+
+def split_shape():
+    """(tile bytes, tiles per trip of the carry pass) of the split kernels (gft_debug_split_shape)"""
+    t, k = C.c_uint32(0), C.c_uint32(0)
+    _lib.load().gft_debug_split_shape(C.byref(t), C.byref(k))
+    return int(t.value), int(k.value)
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
@@ -186,6 +231,14 @@ class Engine:
         self._check(self._L.gft_to_lower_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, d_out_ptr, cap, d_out_off_ptr,
                                                 C.byref(total)))
         return int(total.value)
+
+    def split_lines_device(self, buf, length, mode=SPLIT_AFTER_NL):
+        """a resident blob -> its documents' offsets, made on the device (gft_split_lines_device).  buf: a contiguous torch.uint8
+        device tensor with buf.numel() >= length + 64; mode: SPLIT_AFTER_NL (a document per line, the newline stays with it) or
+        SPLIT_JSON_LINES (a document per non-blank line, blank lines travel with the document in front).  Returns a torch.int64
+        device tensor of n + 1 offsets (one entry, 0, for n == 0) -- what every *_device batch call takes as doc_off.  The call
+        runs twice: count only, then into a tensor of exactly n + 1 entries"""
+        return split_lines_tensor(lambda *a: self._check(self._L.gft_split_lines_device(self._h, *a)), buf, length, mode)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

@@ -177,6 +177,7 @@ class Finder:
             self.close()
             raise FinderError(rc, msg)
         self.caseSensitive = caseSensitive
+        self._device = device if devices is None else devices[0]
         self._keep = []
         if subEng is not None and not isinstance(subEng, GpuEngine):
             b, f = _mk_build(subEng), _mk_find(subEng, "FindSubstrings")
@@ -327,6 +328,36 @@ class Finder:
 
     def ProcessDevice(self, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr):
         self._check(self._L.gft_finder_process_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr))
+
+    def SplitLinesDevice(self, buf, length, mode=0):
+        """Engine.split_lines_device on the finder's engine (gft_finder_split_lines_device): needs what ProcessDevice needs"""
+        from .engine import split_lines_tensor
+        return split_lines_tensor(lambda *a: self._check(self._L.gft_finder_split_lines_device(self._h, *a)), buf, length, mode)
+
+    def ProcessLinesDevice(self, buf, length):
+        """a resident blob of text lines (a torch.uint8 device tensor of at least length + 64 bytes) -> (doc_off int64 [n + 1],
+        bitmap int32 [n, ceil(E / 32)]) on the device: the blob is cut behind every newline on the device (SPLIT_AFTER_NL, Go's
+        strings.SplitAfter without a final empty piece), then ProcessDevice runs over the result; the rows are those of
+        ProcessTexts over the pieces.  Needs what ProcessDevice needs"""
+        import torch
+        off = self.SplitLinesDevice(buf, length, 0)
+        n = int(off.numel()) - 1
+        bm = torch.zeros((n, (self.n_expressions + 31) // 32), dtype=torch.int32, device=buf.device)
+        torch.cuda.current_stream(buf.device).synchronize()
+        self.ProcessDevice(buf.data_ptr(), off.data_ptr(), n, bm.data_ptr() if bm.numel() else None)
+        return off, bm
+
+    def ProcessLines(self, data):
+        """the host-memory form: bytes -> (doc_off uint64 [n + 1], bitmap uint32 [n, ceil(E / 32)]) as numpy arrays: the blob goes
+        up once with 64 bytes of slack, ProcessLinesDevice, offsets and rows come down"""
+        import torch
+        data = bytes(data)
+        dev = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+        buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+        if data:
+            buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        off, bm = self.ProcessLinesDevice(buf, len(data))
+        return off.cpu().numpy().astype(np.uint64), bm.cpu().numpy().view(np.uint32)
 
     def ProcessDeviceBegin(self, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr):
         """pipelined ProcessDevice: enqueue the batch and return; ProcessDeviceEnd() completes the oldest batch begun (at

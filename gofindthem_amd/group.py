@@ -610,6 +610,36 @@ class GroupFinder:
             raise self._err(rc)
         return out, status
 
+    def ProcessJsonLinesDevice(self, buf, length):
+        """a resident blob of JSON Lines (a torch.uint8 device tensor of at least length + 64 bytes) -> (doc_off int64 [n + 1], rule
+        bitmap int32 [n, ceil(R / 32)], status uint8 [n]) on the device: the blob is cut into a document per non-blank line on the
+        device (SPLIT_JSON_LINES), then ProcessJsonsDevice runs over the result.  A schema must be set.  The tag side needs
+        nothing of its own: TagJsonsDevice takes the offsets of split_lines_device as they are"""
+        off = self.findthem.SplitLinesDevice(buf, length, 1)
+        out, status = self.ProcessJsonsDevice(buf, off)
+        return off, out, status
+
+    def ProcessJsonLines(self, data, includePaths=None, excludePaths=None):
+        """JSON Lines from host memory (gft_group_process_json_lines): bytes, a document a line -> the result of
+        ProcessJsonsSchema over the lines when a schema is set (the lists must then be None), of ProcessJsonsAuto(lines,
+        includePaths, excludePaths) otherwise.  The blob goes up once and is cut on the device"""
+        data = bytes(data)
+        blob = np.frombuffer(data + b"\0" * 64, dtype=np.uint8)
+        inc = json.dumps(list(includePaths)).encode() if includePaths else None
+        exc = json.dumps(list(excludePaths)).encode() if excludePaths else None
+        need = C.c_uint64(0)
+        cap = max(1 << 16, 2 * len(data))
+        buf = C.create_string_buffer(cap)
+        rc = self._L.gft_group_process_json_lines(self._h, blob.ctypes.data, len(data), inc, len(inc) if inc else 0, exc, len(exc) if exc else 0,
+                                                  C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc == _lib.GFT_E_INVALID and need.value > cap:      # the library kept the document: fetch it, no second run
+            cap = int(need.value)
+            buf = C.create_string_buffer(cap)
+            rc = self._L.gft_group_last_result(self._h, C.cast(buf, C.c_void_p), cap, C.byref(need))
+        if rc != 0:
+            raise self._err(rc)
+        return json.loads(buf.value.decode("utf-8", "replace"))
+
     def ProcessJsonsSchema(self, rawJsons):
         """ProcessJsons(rawJsons, include, exclude of SetSchema) with the documents decoded on the device where it decides them"""
         raws = [r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in rawJsons]

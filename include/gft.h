@@ -287,6 +287,39 @@ uint32_t gft_debug_lower_rune(uint32_t cp);
 int gft_debug_emulate_to_lower(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* out, uint64_t cap,
                                uint64_t* out_off, uint64_t* total);
 
+/* ---- A resident blob cut into line documents on the device (csrc/gft_split.hip) -------------------------------------------
+ * (d_blob, len) -> d_doc_off [n + 1]: the offset array every batch entry point takes, made where the text lies.  Two modes: */
+enum gft_split_mode {
+    GFT_SPLIT_AFTER_NL = 0,   /* Go's strings.SplitAfter(blob, "\n") without a final empty piece: a document starts at 0 and at
+                               * every p + 1 with blob[p] == '\n' and p + 1 < len; a '\n' stays with the document it ends;
+                               * len == 0 gives no document */
+    GFT_SPLIT_JSON_LINES = 1  /* JSON Lines: a line begins at 0 and behind every '\n' and is blank when it holds nothing but the
+                               * JSON whitespace bytes 20 09 0A 0D.  Document 0 starts at 0, document i >= 1 where the i-th
+                               * non-blank line (counted from 0) starts: blank lines, '\r', indentation and the newline travel
+                               * with the document in front of them, those in front of the first non-blank line with document
+                               * 0.  A blob of whitespace gives no document.  Every document is one line's JSON value with
+                               * whitespace round it -- what the walker of the group finder's JSON calls and its host reader
+                               * accept unchanged */
+};
+/* d_doc_off[0..n] is written with d_doc_off[0] = 0 and d_doc_off[n] = len; n == 0 writes d_doc_off[0] = 0 only.  Three launches
+ * on the engine's stream (gft_profile_read: "split_count", "split_scan", "split_write"); the cap protocol is gft_compact_device's:
+ * cap counts entries of d_doc_off, an entry whose index is >= cap is NOT written and nothing is stored at or past
+ * d_doc_off + cap, GFT_OK is returned in both cases and *n_docs (host) receives n -- the caller compares n + 1 with cap and
+ * calls again.  d_doc_off == NULL with cap == 0 counts only.  The call waits for the stream.  d_blob must be readable for 64
+ * bytes past len, as for the scans (what those bytes hold never changes the answer), and needs no alignment.  Offsets and counts
+ * are 64-bit throughout: a document of 4 GiB or more is not refused here -- the calls that take the result refuse it.
+ * GFT_E_INVALID: an unknown mode, an output that overlaps the input.  Handles over several devices: GFT_E_UNSUPPORTED.  Between
+ * gft_process_device_begin and _end only after _complete.  Needs no dictionary, leaves gft_last_nonascii alone, and the handle
+ * stays usable after any error. */
+int gft_split_lines_device(gft_engine* e, const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap,
+                           uint64_t* n_docs);
+/* The same on the host, no HIP device needed: the kernels' walk tile by tile through the source they are compiled from
+ * (csrc/gft_split_piece.hpp), with the same carry resolution.  All pointers host; same contract; the 64 bytes of slack are not
+ * asked for here.  It is also what gft_group_process_json_lines splits with when the finder does not take the device route. */
+int gft_debug_split_lines(const uint8_t* blob, uint64_t len, uint32_t mode, uint64_t* doc_off, uint64_t cap, uint64_t* n_docs);
+/* where that walk's borders are: the bytes a wave owns (a tile), and the tiles one trip of the carry pass resolves */
+void gft_debug_split_shape(uint32_t* tile_bytes, uint32_t* tiles_per_carry_trip);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -354,6 +387,10 @@ int gft_finder_process_texts_sparse(gft_finder* f, const uint8_t* text_blob, con
  * instead -- text down, ToLower per document, scan, bitmap up; the results are the same. */
 int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                               uint32_t* d_hit_bitmap);
+/* gft_split_lines_device on the finder's engine: the offsets of a resident blob of lines, for the call above.  It asks of the
+ * finder what that call asks (the GPU substring engine, no regex terms) and refuses in its words. */
+int gft_finder_split_lines_device(gft_finder* f, const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap,
+                                  uint64_t* n_docs);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
@@ -634,6 +671,16 @@ int gft_group_json_paths_device(gft_group* g, const uint8_t* d_json_blob, const 
 int gft_group_process_jsons_auto(gft_group* g, const uint8_t* json_blob, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* include_json,
                                  uint64_t include_len, const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap,
                                  uint64_t* needed);
+/* JSON Lines from host memory: one blob, a document a line (gft_split_lines_device, GFT_SPLIT_JSON_LINES).  With a schema set
+ * (gft_group_set_schema) the result document of gft_group_process_jsons_schema -- the include / exclude arguments must then be
+ * empty: GFT_E_INVALID --, without one that of gft_group_process_jsons_auto with these lists; both over the documents of the
+ * split, byte for byte.  The blob is uploaded once and cut where it lies; the offsets come down at 8 bytes a document (the host
+ * route needs them for the documents whose status is not 0) and the schema / auto route continues from the resident blob.  A
+ * finder that does not qualify for the device route (regex terms, injected engines, several devices) splits on the host -- the
+ * code behind gft_debug_split_lines -- and takes gft_group_process_jsons' route.  A blob without a non-blank line gives "[]".
+ * gft_group_last_result and gft_group_json_last serve this call too. */
+int gft_group_process_json_lines(gft_group* g, const uint8_t* blob, uint64_t len, const uint8_t* include_json, uint64_t include_len,
+                                 const uint8_t* exclude_json, uint64_t exclude_len, char* out, uint64_t cap, uint64_t* needed);
 /* what the last gft_group_process_jsons_auto found: distinct paths, paths found and not kept, 1 when it compiled a schema */
 int gft_group_json_auto_last(const gft_group* g, uint64_t* n_paths, uint64_t* dropped, uint64_t* recompiled);
 /* No device needed (tests), host pointers, the output contract of gft_group_json_paths_device: the discovery mode of the
