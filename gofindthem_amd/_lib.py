@@ -152,6 +152,10 @@ SYMBOLS = {
     "gft_debug_split_lines": (_i, [_vp, _u64, _u32, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_split_shape": (None, [C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_split_lines_device": (_i, [_vp, _vp, _u64, _u32, _vp, _u64, C.POINTER(_u64)]),
+    "gft_select_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_select_docs": (_i, [_vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_select_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gft_finder_select_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_group_process_json_lines": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_tables": (_i, [_vp, _vp, _u32, _vp, _u64, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp, _u64, C.POINTER(_u64), _vp, _u64]),

@@ -509,6 +509,20 @@ Error Finder::SplitLinesDevice(const uint8_t* d_blob, uint64_t len, uint32_t mod
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                               uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
+                               uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes) {
+    last_code_ = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    int rc = gft_select_docs_device(gpu_->handle(), d_blob, d_doc_off, n_docs, d_bitmap, (uint32_t)expressions_.size(), want, mode, d_also, d_out,
+                                    cap_bytes, d_out_off, d_doc_idx, cap_docs, n_selected, total_bytes);
+    return rc ? fail_gft(rc) : Error();
+}
+
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
     if (!gpu_sub_ || !regexes_.empty()) {
@@ -784,6 +798,16 @@ int gft_finder_split_lines_device(gft_finder* f, const uint8_t* d_blob, uint64_t
     if (!f || !n_docs) return GFT_E_INVALID;
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->SplitLinesDevice(d_blob, len, mode, d_doc_off, cap, n_docs), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_select_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                  const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint8_t* d_out,
+                                  uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* n_selected,
+                                  uint64_t* total_bytes) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->SelectDocsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, mode, d_also, d_out, cap_bytes, d_out_off,
+                                                     d_doc_idx, cap_docs, n_selected, total_bytes), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

@@ -127,6 +127,11 @@ public:
     // gft_split_lines_device on the finder's engine, for a blob that ProcessDevice is to take next: what ProcessDevice needs of the
     // finder, refused in its words
     Error SplitLinesDevice(const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap, uint64_t* n_docs);
+    // gft_select_docs_device on the finder's engine over the rows ProcessDevice left (n_cols = the expressions): what ProcessDevice
+    // needs of the finder, refused in its words
+    Error SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                           uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
+                           uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

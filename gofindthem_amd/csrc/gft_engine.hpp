@@ -182,6 +182,10 @@ struct gft_engine {
     // sums and scan partials of its own
     struct SplitBufs { DevBuf sums, carry, cnt, base, partial; } d_split;
 
+    // the documents that matched, gathered into one blob (gft_select.hip): the mask, the lengths and marks of a batch, their
+    // prefix sums, scan partials and read-back words of its own, and the compact offsets the copy pass searches
+    struct SelectBufs { DevBuf want, len, sel, pos, rank, partial, ctl, c_off, c_src; } d_select;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

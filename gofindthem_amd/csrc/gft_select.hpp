@@ -1,0 +1,83 @@
+// gft_select.hpp -- the documents that matched, gathered into one blob (gft_select.hip): the launchers, and the same walk on the
+// host (select_host.cpp), which is also what a finder selects with when a batch's rows were completed on the host.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/gft.h"
+#include "gft_select_piece.hpp"
+
+namespace gft {
+
+// gft_select_docs_device's contract on host pointers: the mark pass, the two prefix sums, the place pass and the copy pass, tile
+// by tile through gft_select_piece.hpp.  Reads blob[doc_off[0], doc_off[n_docs]) only.  Returns a gft_status.
+int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
+                     const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
+                     uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
+
+// `want` as the mark pass reads it: W = ceil(n_cols / 32) words, NULL = every column, the bits at and above n_cols cleared
+inline void select_want_words(const uint32_t* want, uint32_t n_cols, uint32_t* dst) {
+    const uint32_t W = (n_cols + 31) / 32;
+    for (uint32_t j = 0; j < W; j++) dst[j] = want ? want[j] : 0xFFFFFFFFu;
+    if (W && (n_cols & 31)) dst[W - 1] &= (1u << (n_cols & 31)) - 1;
+}
+
+// two byte ranges meet (an empty one meets nothing)
+inline bool select_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return a && b && an && bn && x < y + bn && y < x + an;
+}
+// an output of the call overlaps one of its inputs (the text is [lo, hi) of the blob), or another output
+inline bool select_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs,
+                                   const uint32_t* bitmap, uint32_t n_cols, const uint8_t* also, const uint8_t* out, uint64_t cap_bytes,
+                                   const uint64_t* out_off, const uint64_t* doc_idx, uint64_t cap_docs) {
+    const void* outs[3] = {out, out_off, doc_idx};
+    const uint64_t out_n[3] = {cap_bytes, out_off ? (cap_docs + 1) * 8 : 0, cap_docs * 8};
+    const void* ins[4] = {text ? text + lo : nullptr, doc_off, bitmap, also};
+    const uint64_t in_n[4] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, n_docs * ((n_cols + 31) / 32) * 4, n_docs};
+    for (int o = 0; o < 3; o++) {
+        for (int i = 0; i < 4; i++)
+            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
+        for (int p = o + 1; p < 3; p++)
+            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
+    }
+    return false;
+}
+
+}  // namespace gft
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+namespace gft {
+
+struct SelectParams {
+    const uint8_t* text;
+    const uint64_t* doc_off;   // [n_docs + 1]
+    uint64_t n_docs;
+    const uint32_t* bitmap;    // [n_docs][W]
+    uint32_t W, lg;            // words per row; W <= 64: a row is a segment of 1 << lg lanes
+    uint32_t mode;
+    const uint32_t* want;      // [W]            the engine's copy, cut to n_cols
+    const uint8_t* also;       // [n_docs] or NULL
+    uint32_t* len;             // [n_docs]       mark: the document's length if selected, else 0
+    uint32_t* sel;             // [n_docs]       mark: 0 / 1
+    const uint64_t* pos;       // [n_docs + 1]   exclusive prefix sum of len
+    const uint64_t* rank;      // [n_docs + 1]   ... of sel
+    uint64_t* ctl;             // [5]            total, m, doc_off[0], doc_off[n_docs], flag (offsets descend / 4 GiB)
+    uint64_t* c_off;           // [m + 1]        place -> copy
+    uint64_t* c_src;           // [m]
+    uint64_t m, total;
+    uint8_t* out;
+    uint64_t* out_off;         // [cap_docs + 1] or NULL
+    uint64_t* doc_idx;         // [cap_docs]
+    uint64_t cap_docs;
+    SelGeom G;
+};
+
+hipError_t launch_select_mark(const SelectParams& P, unsigned n_cus, hipStream_t st);
+hipError_t launch_select_pack(const SelectParams& P, hipStream_t st);
+hipError_t launch_select_place(const SelectParams& P, hipStream_t st);
+hipError_t launch_select_copy(const SelectParams& P, hipStream_t st);
+
+}  // namespace gft
+#endif

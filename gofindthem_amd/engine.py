@@ -72,6 +72,95 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+SELECT_MODES = {"any": 0, "all": 1, "none": 2}      # gft_select_mode
+
+
+def _select_mode(mode):
+    return SELECT_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def _want_words(want, n_cols):
+    """the host mask of a select call: None, or ceil(n_cols / 32) uint32 words"""
+    if want is None:
+        return None
+    w = np.ascontiguousarray(want, dtype=np.uint32).reshape(-1)
+    if w.size != (n_cols + 31) // 32:
+        raise ValueError("want must have ceil(n_cols / 32) words")
+    return w if w.size else np.zeros(1, dtype=np.uint32)
+
+
+def select_docs_tensor(call, text, doc_off, bitmap, n_cols, want, mode, also):
+    """what Engine.select_docs_device and the finders' select calls share: `call(d_text, d_doc_off, n_docs, d_bitmap, n_cols, want,
+    mode, d_also, d_out, cap_bytes, d_out_off, d_doc_idx, cap_docs, byref(m), byref(total))` is gft_select_docs_device on some
+    handle and raises on an error.  Two calls: count only, then into tensors of exactly the sizes counted"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    W = (n_cols + 31) // 32
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
+            (((also, 1, "also"),) if also is not None else ()):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("select_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs):
+        raise ValueError("select_docs_device: doc_off, bitmap and also do not describe the same batch")
+    w = _want_words(want, n_cols)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), _select_mode(mode),
+            also.data_ptr() if also is not None else None)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, None, 0, None, None, 0, C.byref(m), C.byref(total))
+    nm, nb = int(m.value), int(total.value)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
+    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
+    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_idx.data_ptr() if nm else None, nm, C.byref(m), C.byref(total))
+    return buf[:nb], out_off, doc_idx
+
+
+def select_docs_host(blob, doc_off, rows, n_cols, want=None, mode="any", also=None, cap_bytes=None, cap_docs=None, guard=0, out_shift=0,
+                     count_only=False):
+    """gft_debug_select_docs over host arrays -> (m, total, out uint8 [cap_bytes + guard], out_off uint64 [cap_docs + 1 + guard],
+    doc_idx uint64 [cap_docs + guard]); no device needed.  Caps None: count first, then exactly what the result needs; the guard
+    entries behind the caps hold 0xA5 and must come back untouched.  out_shift: the output starts that many bytes into its
+    allocation's 16-byte grid.  out_off, with its cap_docs + 1 entries, is always passed; count_only: no array at all"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    n_docs = off.size - 1
+    W = (n_cols + 31) // 32
+    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
+    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    w = _want_words(want, n_cols)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cb, oo, di, cd):
+        rc = L.gft_debug_select_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), _select_mode(mode), _p(al),
+                                     out, cb, oo, di, cd, C.byref(m), C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_select_docs")
+    if cap_bytes is None or cap_docs is None:
+        call(None, 0, None, None, 0)
+        cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
+        cap_docs = int(m.value) if cap_docs is None else cap_docs
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 16 + out_shift
+    out = raw[at:at + cap_bytes + guard]
+    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    if count_only:
+        call(None, 0, None, None, 0)
+    else:
+        call(out.ctypes.data if cap_bytes or guard else None, cap_bytes, out_off.ctypes.data, doc_idx.ctypes.data if cap_docs or guard else None, cap_docs)
+    return int(m.value), int(total.value), out, out_off, doc_idx
+
+
+def select_shape():
+    """(chunk, trip, tile) bytes of the select's copy kernel (gft_debug_select_shape)"""
+    c, t, k = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _lib.load().gft_debug_select_shape(C.byref(c), C.byref(t), C.byref(k))
+    return int(c.value), int(t.value), int(k.value)
+
+
 class Engine:
     """Thin object wrapper of the C ABI (one gft_engine handle)."""
 
@@ -239,6 +328,16 @@ class Engine:
         device tensor of n + 1 offsets (one entry, 0, for n == 0) -- what every *_device batch call takes as doc_off.  The call
         runs twice: count only, then into a tensor of exactly n + 1 entries"""
         return split_lines_tensor(lambda *a: self._check(self._L.gft_split_lines_device(self._h, *a)), buf, length, mode)
+
+    def select_docs_device(self, text, doc_off, bitmap, n_cols, want=None, mode="any", also=None):
+        """the documents of a resident batch whose rows hit `want`, gathered on the device (gft_select_docs_device).  text: torch.uint8
+        with 64 readable bytes behind doc_off[-1]; doc_off: int64 [n + 1]; bitmap: int32 [n, ceil(n_cols / 32)] (not read for
+        n_cols == 0); want: None (every column) or ceil(n_cols / 32) host uint32 words; mode: "any", "all" or "none"; also: uint8 [n],
+        non-zero selects the document whatever its row says.  Returns device tensors (out uint8 [total] -- the selected documents
+        back to back in input order, a view with 64 zero bytes behind it --, out_off int64 [m + 1], doc_idx int64 [m]).  The call
+        runs twice: count only, then into tensors of exactly those sizes"""
+        return select_docs_tensor(lambda *a: self._check(self._L.gft_select_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, want,
+                                  mode, also)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

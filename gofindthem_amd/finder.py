@@ -359,6 +359,84 @@ class Finder:
         off, bm = self.ProcessLinesDevice(buf, len(data))
         return off.cpu().numpy().astype(np.uint64), bm.cpu().numpy().view(np.uint32)
 
+    # -- the documents that matched (csrc/gft_select.hip) ------------------------------------------------------------------
+    def want_mask(self, indices=None, tags=None):
+        """the host mask of the select calls: ceil(E / 32) uint32 words with the bits of the expressions named by index and / or
+        by tag (every expression registered under one of `tags`).  Both None: every expression.  An index out of range or a tag no
+        expression carries is a ValueError"""
+        E = self.n_expressions
+        w = np.zeros((E + 31) // 32, dtype=np.uint32)
+        if indices is None and tags is None:
+            indices = range(E)
+        picked = []
+        for i in indices or ():
+            i = int(i)
+            if not 0 <= i < E:
+                raise ValueError("want_mask: no expression %d" % i)
+            picked.append(i)
+        if tags is not None:
+            names = self.tags()
+            ids = set()
+            for t in [tags] if isinstance(tags, str) else tags:
+                if t not in names:
+                    raise ValueError("want_mask: no expression carries the tag %r" % (t,))
+                ids.add(names.index(t))
+            picked += [i for i in range(E) if self.expression_tag_id(i) in ids]
+        for i in picked:
+            w[i >> 5] |= np.uint32(1 << (i & 31))
+        return w
+
+    def SelectDevice(self, text, doc_off, bitmap, want=None, mode="any", also=None):
+        """Engine.select_docs_device on the finder's engine with n_cols = n_expressions (gft_finder_select_docs_device): the
+        documents whose rows -- as ProcessDevice left them -- hit `want` (want_mask(); None: any expression), as device tensors
+        (out uint8, out_off int64 [m + 1], doc_idx int64 [m]).  Needs what ProcessDevice needs"""
+        from .engine import select_docs_tensor
+
+        def call(d_text, d_off, n, d_bm, n_cols, w, m, d_also, *rest):
+            self._check(self._L.gft_finder_select_docs_device(self._h, d_text, d_off, n, d_bm, w, m, d_also, *rest))
+        return select_docs_tensor(call, text, doc_off, bitmap, self.n_expressions, want, mode, also)
+
+    def SelectLinesDevice(self, buf, length, want=None, mode="any"):
+        """a resident blob of text lines -> the lines that hit: ProcessLinesDevice (split behind every newline, ProcessDevice), then
+        SelectDevice over its rows.  Returns (out, out_off, doc_idx, doc_off, bitmap), all on the device; a line keeps its newline"""
+        off, bm = self.ProcessLinesDevice(buf, length)
+        out, out_off, doc_idx = self.SelectDevice(buf, off, bm, want, mode)
+        return out, out_off, doc_idx, off, bm
+
+    def SelectLines(self, data, want=None, mode="any"):
+        """the host-memory form: bytes -> (the selected lines as bytes, out_off uint64 [m + 1], doc_idx uint64 [m]).  One upload;
+        only the selected lines, their offsets and their indices come down.  A finder that does not take the device route (regex
+        terms, injected engines, several devices) splits, processes and selects on the host -- the kernels' walk behind
+        gft_debug_split_lines and gft_debug_select_docs --: the same result"""
+        import torch
+        data = bytes(data)
+        if self._takes_device_route():
+            dev = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+            buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+            if data:
+                buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+            out, out_off, doc_idx, _, _ = self.SelectLinesDevice(buf, len(data), want, mode)
+            return out.cpu().numpy().tobytes(), out_off.cpu().numpy().astype(np.uint64), doc_idx.cpu().numpy().astype(np.uint64)
+        from .engine import select_docs_host, split_lines_host
+        n, off = split_lines_host(data, 0)
+        off = off[:n + 1]
+        bm = self.ProcessTexts(blob=np.frombuffer(data + b"\0" * 64, dtype=np.uint8), doc_off=off)
+        m, total, out, out_off, doc_idx = select_docs_host(data, off, bm, self.n_expressions, want, mode)
+        return out[:total].tobytes(), out_off[:m + 1].copy(), doc_idx[:m].copy()
+
+    def _takes_device_route(self):
+        """asks the handle: the split of an empty blob (gft_finder_split_lines_device, count only) answers what ProcessDevice asks
+        of the finder -- the GPU substring engine, no regex terms, one device -- and whether there is a device at all.  Any other
+        refusal (batches in flight) is the caller's"""
+        if not self.engine_handle():                         # (a finder kept without a device has no engine handle)
+            return False
+        n = C.c_uint64(0)
+        rc = self._L.gft_finder_split_lines_device(self._h, None, 0, 0, None, 0, C.byref(n))
+        if rc in (_lib.GFT_E_UNSUPPORTED, _lib.GFT_E_HIP):
+            return False
+        self._check(rc)
+        return True
+
     def ProcessDeviceBegin(self, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr):
         """pipelined ProcessDevice: enqueue the batch and return; ProcessDeviceEnd() completes the oldest batch begun (at
         most two in flight; inputs and bitmap stay untouched until then)"""

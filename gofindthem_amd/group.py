@@ -619,6 +619,59 @@ class GroupFinder:
         out, status = self.ProcessJsonsDevice(buf, off)
         return off, out, status
 
+    # -- the documents whose rules fired (csrc/gft_select.hip) ----------------------------------------------------------------
+    def rule_mask(self, rules=None):
+        """the host mask of the select calls over rule rows: rule_words() uint32 words with the bits of rule_exprs() whose rule name
+        is in `rules` -- ANY over them means "one of these rules fired".  None: every rule.  A name no rule has is a ValueError"""
+        names = [r for r, _ in self.rule_exprs()]
+        w = np.zeros((len(names) + 31) // 32, dtype=np.uint32)
+        if rules is None:
+            wanted = set(names)
+        else:
+            wanted = set([rules] if isinstance(rules, str) else rules)
+            for r in wanted:
+                if r not in names:
+                    raise ValueError("rule_mask: no rule %r" % (r,))
+        for i, r in enumerate(names):
+            if r in wanted:
+                w[i >> 5] |= np.uint32(1 << (i & 31))
+        return w
+
+    def SelectJsonLinesDevice(self, buf, length, rules=None, mode="any", keep_undecided=True):
+        """a resident blob of JSON Lines -> the lines whose rules fired: ProcessJsonLinesDevice, then the select over the rule rows
+        with rule_mask(rules).  keep_undecided: a document whose status is not 0 -- the device did not decide it, its row is that
+        of an empty record -- is selected whatever its row says (its index in doc_idx tells which it was).  Returns (out uint8,
+        out_off int64 [m + 1], doc_idx int64 [m], status uint8 [n]) on the device; a document carries its trailing whitespace and
+        newline, so `out` is JSON Lines again.  A schema must be set"""
+        from .engine import select_docs_tensor
+        off, rows, status = self.ProcessJsonLinesDevice(buf, length)
+        n_cols = int(self._L.gft_group_n_rule_exprs(self._h))
+        eh = self.findthem.engine_handle()
+
+        def call(*a):
+            rc = self._L.gft_select_docs_device(eh, *a)
+            if rc != 0:
+                raise GroupFinderError(rc, self._L.gft_last_error(eh).decode("utf-8", "replace"))
+        out, out_off, doc_idx = select_docs_tensor(call, buf, off, rows, n_cols, self.rule_mask(rules), mode, status if keep_undecided else None)
+        return out, out_off, doc_idx, status
+
+    def SelectJsonLines(self, data, rules=None, mode="any"):
+        """the host-memory form: bytes -> (the selected lines as bytes, out_off uint64 [m + 1], doc_idx uint64 [m], undecided
+        uint64 [u]).  One upload; the lines the device decided come back selected by their rows, the ones it did not decide (status
+        not 0) come back too and `undecided` lists their input indices (a subset of doc_idx) -- the caller gives those to
+        ProcessJsons.  The bytes are JSON Lines again.  A schema must be set"""
+        import torch
+        data = bytes(data)
+        f = self.findthem
+        dev = torch.device("cuda", f._device if f._device >= 0 else torch.cuda.current_device())
+        buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+        if data:
+            buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        out, out_off, doc_idx, status = self.SelectJsonLinesDevice(buf, len(data), rules, mode, True)
+        undecided = torch.nonzero(status, as_tuple=False).reshape(-1)
+        return (out.cpu().numpy().tobytes(), out_off.cpu().numpy().astype(np.uint64), doc_idx.cpu().numpy().astype(np.uint64),
+                undecided.cpu().numpy().astype(np.uint64))
+
     def ProcessJsonLines(self, data, includePaths=None, excludePaths=None):
         """JSON Lines from host memory (gft_group_process_json_lines): bytes, a document a line -> the result of
         ProcessJsonsSchema over the lines when a schema is set (the lists must then be None), of ProcessJsonsAuto(lines,

@@ -320,6 +320,51 @@ int gft_debug_split_lines(const uint8_t* blob, uint64_t len, uint32_t mode, uint
 /* where that walk's borders are: the bytes a wave owns (a tile), and the tiles one trip of the carry pass resolves */
 void gft_debug_split_shape(uint32_t* tile_bytes, uint32_t* tiles_per_carry_trip);
 
+/* ---- The documents that matched, gathered into one blob on the device (csrc/gft_select.hip) -------------------------------
+ * (d_text_blob, d_doc_off [n_docs + 1], hit rows, a column mask) -> the selected documents' bytes back to back in input order,
+ * their offsets and their input indices: the filter step behind gft_process_device / gft_group_process_jsons_device, made where
+ * the text lies.  A document is selected by its row under one of three modes: */
+enum gft_select_mode {
+    GFT_SELECT_ANY = 0,   /* (row & want) != 0 */
+    GFT_SELECT_ALL = 1,   /* (row & want) == want  -- an empty want selects every document */
+    GFT_SELECT_NONE = 2   /* (row & want) == 0    -- the complement of ANY */
+};
+/* d_bitmap [n_docs][W], W = ceil(n_cols / 32), layout of gft_process; n_cols is explicit so that finder rows (gft_n_exprs) and
+ * the group finder's rule rows (gft_group_n_rule_exprs) go through one call.  Bits at and above n_cols in a row's last word are
+ * ignored, whatever they hold.  want: HOST memory, W words, copied by the call; NULL = every column; its bits at and above
+ * n_cols are ignored too.  n_cols == 0 is valid and needs no d_bitmap: ANY selects nothing, ALL and NONE every document.
+ * d_also (nullable) [n_docs] bytes: non-zero = the document is selected whatever its row says (the status bytes of
+ * gft_group_process_jsons_device: a document the device did not decide is never silently dropped; d_doc_idx tells which it was).
+ * With m selected documents of `total` bytes: d_out receives them back to back in input order, d_out_off[0..m] where each
+ * starts (d_out_off[0] = 0, d_out_off[m] = total), d_doc_idx[k] the input index of output document k.
+ * Cap protocol of gft_compact_device: cap_bytes counts bytes of d_out, cap_docs entries of d_doc_idx, and d_out_off has
+ * cap_docs + 1 entries.  A byte whose output position is >= cap_bytes, an index entry >= cap_docs and an offset entry > cap_docs
+ * are NOT written; nothing at all is stored at or past d_out + min(total, cap_bytes) -- byte-exactly, no rounding up to a store
+ * width --; GFT_OK is returned in both cases and *n_selected = m, *total_bytes = total (host, nullable) are always handed back
+ * -- the caller compares them with the caps and calls again.  d_out == NULL with cap_bytes == 0, and d_out_off == d_doc_idx ==
+ * NULL with cap_docs == 0, count only (a d_out_off that is not NULL always receives entry 0).  n_docs == 0 is valid.
+ * Four launches on the engine's stream (gft_profile_read: "select_mark", "select_scan", "select_place", "select_copy"); the call
+ * waits for the stream.  d_text_blob must be readable for 64 bytes past d_doc_off[n_docs], as for the scans (what those bytes
+ * hold never changes the answer), and needs no alignment; d_out needs none either.
+ * GFT_E_INVALID: an unknown mode; a cap without its array; offsets that descend or a document of 4 GiB or more (selected or
+ * not; found on the device as gft_to_lower_device finds them); an output that overlaps the text, the offsets, the bitmap, d_also
+ * or another output.  Handles over several devices: GFT_E_UNSUPPORTED.  GFT_E_NOMEM: no room for the work buffers (24 bytes a
+ * document and 16 a selected one).  Between gft_process_device_begin and _end only after _complete.  Needs no dictionary and no programs, leaves
+ * gft_last_nonascii alone, and the handle stays usable after any error. */
+int gft_select_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap,
+                           uint32_t n_cols, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,
+                           uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
+/* The same on the host, no HIP device needed: the kernels' walk tile by tile through the source they are compiled from
+ * (csrc/gft_select_piece.hpp).  All pointers host; same contract and refusals; only blob[doc_off[0], doc_off[n_docs]) is read:
+ * the 64 bytes of slack are not asked for here.  It is also what a finder selects with when a batch's rows were completed on
+ * the host. */
+int gft_debug_select_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
+                          const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
+                          uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
+/* where that walk's borders are: the bytes of the output a lane stores at once (a chunk, aligned to the output address), a
+ * wave's trip, and the bytes a wave owns (a tile) */
+void gft_debug_select_shape(uint32_t* chunk_bytes, uint32_t* trip_bytes, uint32_t* tile_bytes);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -391,6 +436,13 @@ int gft_finder_process_device(gft_finder* f, const uint8_t* d_text_blob, const u
  * finder what that call asks (the GPU substring engine, no regex terms) and refuses in its words. */
 int gft_finder_split_lines_device(gft_finder* f, const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap,
                                   uint64_t* n_docs);
+/* gft_select_docs_device on the finder's engine with n_cols = gft_finder_n_expressions: the documents of a resident batch whose
+ * rows -- as the calls above leave them -- hit `want`.  It asks of the finder what gft_finder_process_device asks and refuses in
+ * its words; no batch of gft_finder_process_device_begin may be in flight. */
+int gft_finder_select_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                  const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint8_t* d_out,
+                                  uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* n_selected,
+                                  uint64_t* total_bytes);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
