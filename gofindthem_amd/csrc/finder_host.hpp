@@ -132,6 +132,10 @@ public:
     Error SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
                            uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
                            uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
+    // gft_route_docs_device on the finder's engine (n_cols = the expressions): what SelectDocsDevice asks, refused in its words
+    Error RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* masks,
+                          uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,
+                          uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

@@ -186,6 +186,11 @@ struct gft_engine {
     // prefix sums, scan partials and read-back words of its own, and the compact offsets the copy pass searches
     struct SelectBufs { DevBuf want, len, sel, pos, rank, partial, ctl, c_off, c_src; } d_select;
 
+    // documents routed to per-bucket runs of one blob (gft_route.hip): the masks, the member words and lengths of a batch, the
+    // (bucket, tile) counts with their prefix sums, the tiles' bytes, scan partials and read-back words of its own, and the
+    // entries' lengths and compact offsets the select's copy pass searches
+    struct RouteBufs { DevBuf masks, member, len, cnt, tile_bytes, base, partial, ctl, ent_len, c_off, c_src; } d_route;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

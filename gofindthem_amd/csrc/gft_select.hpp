@@ -14,6 +14,9 @@ int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
                      const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
                      uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
 
+// the copy pass alone, every tile of G: the compact arrays c_off [m + 1] / c_src [m] in whatever order their entries come
+void select_copy_host(const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, const SelGeom& G, uint8_t* out);
+
 // `want` as the mark pass reads it: W = ceil(n_cols / 32) words, NULL = every column, the bits at and above n_cols cleared
 inline void select_want_words(const uint32_t* want, uint32_t n_cols, uint32_t* dst) {
     const uint32_t W = (n_cols + 31) / 32;

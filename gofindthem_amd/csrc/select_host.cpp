@@ -78,6 +78,10 @@ void copy_tile(const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src
 
 }  // namespace
 
+void select_copy_host(const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, const SelGeom& G, uint8_t* out) {
+    for (uint64_t tile = 0, n = sel_tiles(G); tile < n; tile++) copy_tile(text, c_off, c_src, m, G, tile, out);
+}
+
 int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
                      const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
                      uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes) {
@@ -131,7 +135,7 @@ int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
     }
     // k_select_copy
     const SelGeom G{std::min(total, cap_bytes), (uint32_t)((uintptr_t)out & 15u)};
-    for (uint64_t tile = 0, n = sel_tiles(G); tile < n; tile++) copy_tile(blob, c_off.data(), c_src.data(), m, G, tile, out);
+    select_copy_host(blob, c_off.data(), c_src.data(), m, G, out);
     return GFT_OK;
 }
 

@@ -161,6 +161,103 @@ def select_shape():
     return int(c.value), int(t.value), int(k.value)
 
 
+ROUTE_MODES = {"first": 0, "every": 1}              # gft_route_mode
+ROUTE_REST = 1                                      # GFT_ROUTE_REST
+ROUTE_MAX_BUCKETS = 64                              # GFT_ROUTE_MAX_BUCKETS
+
+
+def _route_mode(mode):
+    return ROUTE_MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def _mask_rows(masks, n_cols):
+    """the host masks of a route call: (K, the K x ceil(n_cols / 32) uint32 words); masks is a sequence of K rows"""
+    W = (n_cols + 31) // 32
+    K = len(masks)
+    if K and W:
+        w = np.ascontiguousarray(np.asarray([np.asarray(m, dtype=np.uint32).reshape(-1) for m in masks], dtype=np.uint32))
+        if w.shape != (K, W):
+            raise ValueError("every mask must have ceil(n_cols / 32) words")
+    else:
+        w = np.zeros((K, W), dtype=np.uint32)
+    return K, (w.reshape(-1) if w.size else np.zeros(1, dtype=np.uint32))
+
+
+def route_docs_tensor(call, text, doc_off, bitmap, n_cols, masks, mode, rest, also, count_only=False):
+    """what Engine.route_docs_device and the finders' route calls share: `call(d_text, d_doc_off, n_docs, d_bitmap, n_cols, masks,
+    n_buckets, mode, flags, d_also, d_out, cap_bytes, d_out_off, d_doc_idx, cap_docs, bucket_doc, bucket_byte)` is
+    gft_route_docs_device on some handle and raises on an error.  Two calls: count only, then into tensors of exactly the sizes
+    counted.  count_only: the first call alone -> (bucket_doc, bucket_byte)"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    W = (n_cols + 31) // 32
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
+            (((also, 1, "also"),) if also is not None else ()):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("route_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs):
+        raise ValueError("route_docs_device: doc_off, bitmap and also do not describe the same batch")
+    K, w = _mask_rows(masks, n_cols)
+    B = K + (1 if rest else 0)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), K, _route_mode(mode),
+            ROUTE_REST if rest else 0, also.data_ptr() if also is not None else None)
+    bucket_doc, bucket_byte = np.zeros(B + 1, dtype=np.uint64), np.zeros(B + 1, dtype=np.uint64)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, None, 0, None, None, 0, _p(bucket_doc), _p(bucket_byte))
+    if count_only:
+        return bucket_doc, bucket_byte
+    nm, nb = int(bucket_doc[B]), int(bucket_byte[B])
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
+    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
+    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_idx.data_ptr() if nm else None, nm, _p(bucket_doc), _p(bucket_byte))
+    return buf[:nb], out_off, doc_idx, bucket_doc, bucket_byte
+
+
+def route_docs_host(blob, doc_off, rows, n_cols, masks, mode="every", rest=False, also=None, cap_bytes=None, cap_docs=None, guard=0, out_shift=0,
+                    count_only=False):
+    """gft_debug_route_docs over host arrays -> (bucket_doc uint64 [B + 1], bucket_byte uint64 [B + 1], out uint8 [cap_bytes + guard],
+    out_off uint64 [cap_docs + 1 + guard], doc_idx uint64 [cap_docs + guard]); no device needed.  Caps None: count first, then
+    exactly what the result needs; the guard entries behind the caps hold 0xA5 and must come back untouched.  out_shift: the output
+    starts that many bytes into its allocation's 16-byte grid.  count_only: no array at all"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    n_docs = off.size - 1
+    W = (n_cols + 31) // 32
+    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
+    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    K, w = _mask_rows(masks, n_cols)
+    B = K + (1 if rest else 0)
+    bucket_doc, bucket_byte = np.zeros(B + 1, dtype=np.uint64), np.zeros(B + 1, dtype=np.uint64)
+
+    def call(out, cb, oo, di, cd):
+        rc = L.gft_debug_route_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), K, _route_mode(mode),
+                                    ROUTE_REST if rest else 0, _p(al), out, cb, oo, di, cd, _p(bucket_doc), _p(bucket_byte))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_route_docs")
+    if cap_bytes is None or cap_docs is None or count_only:
+        call(None, 0, None, None, 0)
+        cap_bytes = int(bucket_byte[B]) if cap_bytes is None else cap_bytes
+        cap_docs = int(bucket_doc[B]) if cap_docs is None else cap_docs
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 16 + out_shift
+    out = raw[at:at + cap_bytes + guard]
+    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    if not count_only:
+        call(out.ctypes.data if cap_bytes or guard else None, cap_bytes, out_off.ctypes.data, doc_idx.ctypes.data if cap_docs or guard else None, cap_docs)
+    return bucket_doc, bucket_byte, out, out_off, doc_idx
+
+
+def route_shape():
+    """the documents a counting tile of the route kernels holds (gft_debug_route_shape)"""
+    t = C.c_uint32(0)
+    _lib.load().gft_debug_route_shape(C.byref(t))
+    return int(t.value)
+
+
 class Engine:
     """Thin object wrapper of the C ABI (one gft_engine handle)."""
 
@@ -338,6 +435,23 @@ class Engine:
         runs twice: count only, then into tensors of exactly those sizes"""
         return select_docs_tensor(lambda *a: self._check(self._L.gft_select_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, want,
                                   mode, also)
+
+    def route_docs_device(self, text, doc_off, bitmap, n_cols, masks, mode="every", rest=False, also=None):
+        """the documents of a resident batch routed to one bucket per mask, on the device (gft_route_docs_device).  Tensors as for
+        select_docs_device; masks: a sequence of K rows of ceil(n_cols / 32) uint32 words (host).  mode "every": a document goes to
+        every bucket whose mask its row hits; "first": to the lowest-numbered one only.  rest: one more bucket, the last, for the
+        documents that hit no mask; also (needs rest): uint8 [n_docs], non-zero sends the document to the rest bucket alone.
+        Returns (out uint8 -- one blob, every bucket a contiguous run, input order inside a bucket --, out_off int64 [m + 1],
+        doc_idx int64 [m]) on the device and (bucket_doc, bucket_byte) uint64 [B + 1] on the host: bucket b is entries
+        bucket_doc[b]:bucket_doc[b + 1] and bytes bucket_byte[b]:bucket_byte[b + 1].  Counts first, then fills"""
+        return route_docs_tensor(lambda *a: self._check(self._L.gft_route_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, masks, mode,
+                                 rest, also)
+
+    def route_count_device(self, text, doc_off, bitmap, n_cols, masks, mode="every", rest=False, also=None):
+        """the count-only form of route_docs_device -> (bucket_doc, bucket_byte): how many documents and bytes every bucket gets,
+        with nothing but those 2 (B + 1) numbers crossing the link"""
+        return route_docs_tensor(lambda *a: self._check(self._L.gft_route_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, masks, mode,
+                                 rest, also, count_only=True)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

@@ -424,6 +424,95 @@ class Finder:
         m, total, out, out_off, doc_idx = select_docs_host(data, off, bm, self.n_expressions, want, mode)
         return out[:total].tobytes(), out_off[:m + 1].copy(), doc_idx[:m].copy()
 
+    # -- documents routed to one bucket per tag (csrc/gft_route.hip) -----------------------------------------------------------
+    def route_masks(self, buckets=None):
+        """the host masks of the route calls: a list of want_mask() rows, one per bucket.  None: one bucket per tag in tag-id order
+        (tags()).  Otherwise a list whose items are what want_mask takes: a tag or a list of tags, a list of expression indices, or a
+        dict of want_mask's keywords (indices=, tags=).  More than 64 buckets is a ValueError"""
+        from .engine import ROUTE_MAX_BUCKETS
+        if buckets is None:
+            buckets = list(self.tags())
+        if len(buckets) > ROUTE_MAX_BUCKETS:
+            raise ValueError("route_masks: %d buckets, the limit is %d (GFT_ROUTE_MAX_BUCKETS)" % (len(buckets), ROUTE_MAX_BUCKETS))
+        out = []
+        for b in buckets:
+            if isinstance(b, dict):
+                out.append(self.want_mask(**b))
+            elif isinstance(b, str):
+                out.append(self.want_mask(tags=[b]))
+            else:
+                b = list(b)
+                out.append(self.want_mask(tags=b) if b and all(isinstance(x, str) for x in b) else self.want_mask(indices=b))
+        return out
+
+    def _route_call(self):
+        def call(d_text, d_off, n, d_bm, n_cols, *rest):
+            self._check(self._L.gft_finder_route_docs_device(self._h, d_text, d_off, n, d_bm, *rest))
+        return call
+
+    def RouteDevice(self, text, doc_off, bitmap, masks, mode="every", rest=False, also=None):
+        """Engine.route_docs_device on the finder's engine with n_cols = n_expressions (gft_finder_route_docs_device) over the rows
+        ProcessDevice left; masks: route_masks().  Returns (out, out_off, doc_idx) on the device and (bucket_doc, bucket_byte) on the
+        host.  Needs what ProcessDevice needs"""
+        from .engine import route_docs_tensor
+        return route_docs_tensor(self._route_call(), text, doc_off, bitmap, self.n_expressions, masks, mode, rest, also)
+
+    def RouteLinesDevice(self, buf, length, buckets=None, mode="every", rest=False):
+        """a resident blob of text lines -> the lines of every bucket: ProcessLinesDevice, then RouteDevice over its rows with
+        route_masks(buckets).  Returns (out, out_off, doc_idx, bucket_doc, bucket_byte, doc_off, bitmap); a line keeps its newline"""
+        off, bm = self.ProcessLinesDevice(buf, length)
+        out, out_off, doc_idx, bucket_doc, bucket_byte = self.RouteDevice(buf, off, bm, self.route_masks(buckets), mode, rest)
+        return out, out_off, doc_idx, bucket_doc, bucket_byte, off, bm
+
+    def _resident(self, data):
+        import torch
+        dev = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+        buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+        if data:
+            buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        return buf
+
+    def _host_lines(self, data):
+        """(doc_off, rows) of a blob of lines by the host walk of the split and ProcessTexts"""
+        from .engine import split_lines_host
+        n, off = split_lines_host(data, 0)
+        off = off[:n + 1]
+        return off, self.ProcessTexts(blob=np.frombuffer(data + b"\0" * 64, dtype=np.uint8), doc_off=off)
+
+    def RouteLines(self, data, buckets=None, mode="every", rest=False):
+        """the host-memory form: bytes -> (parts, idx): parts a list of bytes, the lines of every bucket (the rest bucket last when
+        asked for), idx a list of uint64 arrays, their input line numbers.  One upload; one blob, its offsets and indices come down.
+        A finder that does not take the device route splits, processes and routes on the host -- the kernels' walk behind
+        gft_debug_split_lines and gft_debug_route_docs --: the same result"""
+        data = bytes(data)
+        if self._takes_device_route():
+            out, _, doc_idx, bucket_doc, bucket_byte, _, _ = self.RouteLinesDevice(self._resident(data), len(data), buckets, mode, rest)
+            out, doc_idx = out.cpu().numpy().tobytes(), doc_idx.cpu().numpy().astype(np.uint64)
+        else:
+            from .engine import route_docs_host
+            off, bm = self._host_lines(data)
+            bucket_doc, bucket_byte, out, _, doc_idx = route_docs_host(data, off, bm, self.n_expressions, self.route_masks(buckets), mode, rest)
+            out = out.tobytes()
+        B = len(bucket_doc) - 1
+        return ([out[int(bucket_byte[b]):int(bucket_byte[b + 1])] for b in range(B)],
+                [doc_idx[int(bucket_doc[b]):int(bucket_doc[b + 1])].copy() for b in range(B)])
+
+    def CountLines(self, data, buckets=None):
+        """the count-only form: bytes -> (documents, bytes) per bucket as uint64 arrays -- a tag histogram of the lines.  Neither rows
+        nor lines come down: the per-bucket counts are all that crosses the link"""
+        data = bytes(data)
+        masks = self.route_masks(buckets)
+        if self._takes_device_route():
+            from .engine import route_docs_tensor
+            buf = self._resident(data)
+            off, bm = self.ProcessLinesDevice(buf, len(data))
+            bucket_doc, bucket_byte = route_docs_tensor(self._route_call(), buf, off, bm, self.n_expressions, masks, "every", False, None, count_only=True)
+        else:
+            from .engine import route_docs_host
+            off, bm = self._host_lines(data)
+            bucket_doc, bucket_byte = route_docs_host(data, off, bm, self.n_expressions, masks, "every", False, count_only=True)[:2]
+        return np.diff(bucket_doc), np.diff(bucket_byte)
+
     def _takes_device_route(self):
         """asks the handle: the split of an empty blob (gft_finder_split_lines_device, count only) answers what ProcessDevice asks
         of the finder -- the GPU substring engine, no regex terms, one device -- and whether there is a device at all.  Any other

@@ -672,6 +672,55 @@ class GroupFinder:
         return (out.cpu().numpy().tobytes(), out_off.cpu().numpy().astype(np.uint64), doc_idx.cpu().numpy().astype(np.uint64),
                 undecided.cpu().numpy().astype(np.uint64))
 
+    # -- the documents of every rule (csrc/gft_route.hip) -------------------------------------------------------------------
+    def route_rule_names(self, rules=None):
+        """the buckets of the route calls over rule rows: the rule names in byte order (None: every rule; a name no rule has is a
+        ValueError -- rule_mask's)"""
+        names = sorted(set(r for r, _ in self.rule_exprs()) if rules is None else set([rules] if isinstance(rules, str) else rules),
+                       key=lambda r: r.encode("utf-8"))
+        for r in names:
+            self.rule_mask([r])
+        return names
+
+    def RouteJsonLinesDevice(self, buf, length, rules=None, mode="every"):
+        """a resident blob of JSON Lines -> the lines of every rule: ProcessJsonLinesDevice, then the route over the rule rows with
+        one bucket per rule name in byte order (route_rule_names(rules); rule_mask of each).  The rest bucket is always on and the
+        status bytes go in as `also`: a document the device did not decide lands in the last bucket, with the decided ones no rule
+        fired for.  Returns (out uint8, out_off int64 [m + 1], doc_idx int64 [m]) on the device, (bucket_doc, bucket_byte) uint64
+        [len(names) + 2] on the host, status uint8 [n] on the device and the names.  A schema must be set"""
+        from .engine import route_docs_tensor
+        names = self.route_rule_names(rules)
+        off, rows, status = self.ProcessJsonLinesDevice(buf, length)
+        n_cols = int(self._L.gft_group_n_rule_exprs(self._h))
+        eh = self.findthem.engine_handle()
+
+        def call(*a):
+            rc = self._L.gft_route_docs_device(eh, *a)
+            if rc != 0:
+                raise GroupFinderError(rc, self._L.gft_last_error(eh).decode("utf-8", "replace"))
+        out, out_off, doc_idx, bucket_doc, bucket_byte = route_docs_tensor(call, buf, off, rows, n_cols, [self.rule_mask([r]) for r in names], mode,
+                                                                           True, status)
+        return out, out_off, doc_idx, bucket_doc, bucket_byte, status, names
+
+    def RouteJsonLines(self, data, rules=None, mode="every"):
+        """the host-memory form: bytes -> (parts, idx, undecided): parts a list of bytes, the lines of every rule in the order of
+        route_rule_names(rules) and the rest last; idx a list of uint64 arrays, their input line numbers; undecided uint64 [u], the
+        lines the device did not decide (status not 0) -- all of them in the last part; the caller gives those to ProcessJsons.
+        Every part is JSON Lines again.  A schema must be set"""
+        import torch
+        data = bytes(data)
+        f = self.findthem
+        dev = torch.device("cuda", f._device if f._device >= 0 else torch.cuda.current_device())
+        buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+        if data:
+            buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+        out, _, doc_idx, bucket_doc, bucket_byte, status, _ = self.RouteJsonLinesDevice(buf, len(data), rules, mode)
+        out, doc_idx = out.cpu().numpy().tobytes(), doc_idx.cpu().numpy().astype(np.uint64)
+        undecided = torch.nonzero(status, as_tuple=False).reshape(-1).cpu().numpy().astype(np.uint64)
+        B = len(bucket_doc) - 1
+        return ([out[int(bucket_byte[b]):int(bucket_byte[b + 1])] for b in range(B)],
+                [doc_idx[int(bucket_doc[b]):int(bucket_doc[b + 1])].copy() for b in range(B)], undecided)
+
     def ProcessJsonLines(self, data, includePaths=None, excludePaths=None):
         """JSON Lines from host memory (gft_group_process_json_lines): bytes, a document a line -> the result of
         ProcessJsonsSchema over the lines when a schema is set (the lists must then be None), of ProcessJsonsAuto(lines,

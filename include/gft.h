@@ -365,6 +365,57 @@ int gft_debug_select_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t
  * wave's trip, and the bytes a wave owns (a tile) */
 void gft_debug_select_shape(uint32_t* chunk_bytes, uint32_t* trip_bytes, uint32_t* tile_bytes);
 
+/* ---- Documents routed to per-bucket runs of one blob on the device (csrc/gft_route.hip) ----------------------------------
+ * The K-way form of the select above: n_buckets column masks instead of one, and the output is ONE blob in which every bucket is
+ * a contiguous run -- a stable counting sort of (document, bucket) entries in front of the select's copy kernel. */
+enum gft_route_mode {
+    GFT_ROUTE_FIRST = 0,  /* a routing table: a document goes to the lowest-numbered bucket whose mask it hits, only there */
+    GFT_ROUTE_EVERY = 1   /* a document goes to every bucket whose mask it hits: one entry, and one copy of its bytes, per bucket */
+};
+#define GFT_ROUTE_REST 1u        /* flags: one more bucket, numbered n_buckets, for the documents that hit no mask */
+#define GFT_ROUTE_MAX_BUCKETS 64 /* n_buckets plus the rest bucket */
+/* d_text_blob, d_doc_off, d_bitmap and n_cols as for gft_select_docs_device (64 bytes of slack behind the text, no alignment,
+ * d_doc_off[0] may be non-zero; finder rows and the group finder's rule rows go through the one call).  masks: HOST memory,
+ * n_buckets x W words, W = ceil(n_cols / 32), copied by the call.  Document d hits bucket k when (row[d] & masks[k]) != 0, both
+ * cut to n_cols: bits at and above n_cols are ignored in rows and in masks, whatever they hold.  n_cols == 0 needs no d_bitmap
+ * and no masks: no document then hits any mask.  n_buckets == 0 is valid.
+ * B = n_buckets + (flags & GFT_ROUTE_REST ? 1 : 0) buckets; B > GFT_ROUTE_MAX_BUCKETS: GFT_E_UNSUPPORTED.  Without GFT_ROUTE_REST
+ * a document that hits no mask produces no entry.  d_also (nullable) [n_docs] bytes: non-zero = the document goes to the rest
+ * bucket and nowhere else, in both modes (the status bytes of gft_group_process_jsons_device: the device did not decide the
+ * document, its row means nothing and it must not be dropped); d_also without GFT_ROUTE_REST: GFT_E_INVALID.
+ * The result is a list of m entries (document, bucket) ordered by bucket first and by input index inside a bucket (stable):
+ * d_out holds the entries' documents back to back in that order, d_out_off[0..m] where each starts (d_out_off[0] = 0),
+ * d_doc_idx[r] the input index of entry r.  bucket_doc, bucket_byte: HOST arrays of B + 1 entries (nullable): bucket b's entries
+ * are [bucket_doc[b], bucket_doc[b + 1]) and its bytes d_out[bucket_byte[b] .. bucket_byte[b + 1]); bucket_doc[B] = m and
+ * bucket_byte[B] = the total.  When given they are always complete, whatever the caps: they take the place of the select's
+ * n_selected and total_bytes.  Empty documents are entries like any other.
+ * Cap protocol of gft_select_docs_device: cap_bytes counts bytes of d_out, cap_docs entries; nothing is stored at or past
+ * d_out + min(total, cap_bytes) -- byte-exactly --, at d_doc_idx[>= cap_docs] or at d_out_off[> cap_docs]; GFT_OK in both cases.
+ * All outputs NULL with both caps 0 counts only (a tag histogram: no bitmap crosses the link).  n_docs == 0 is valid:
+ * d_out_off[0] = 0 if given, the host arrays all zero.  The call waits for the stream; it synchronises with the host once in
+ * the middle (the entry count, the bucket borders and the total come back together).
+ * Launches on the engine's stream (gft_profile_read: "route_mark", "route_count", "route_scan", "route_place", "route_copy").
+ * GFT_E_INVALID: an unknown mode; unknown flag bits; a cap without its array; offsets that descend or a document of 4 GiB or more
+ * (found on the device); an output that overlaps an input or another output.  Handles over several devices: GFT_E_UNSUPPORTED.
+ * GFT_E_NOMEM: no room for the work buffers -- 12 bytes a document (member word, length), 12 bytes a (bucket, tile of 64
+ * documents) (count, base) and 8 a tile (its bytes), 20 bytes an entry (length, output offset, source offset), the masks and the
+ * scans' partials.  Between gft_process_device_begin and _end only after _complete.  Needs no dictionary and no programs, leaves
+ * gft_last_nonascii alone, and the handle stays usable after any error. */
+int gft_route_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                          const uint32_t* d_bitmap, uint32_t n_cols,
+                          const uint32_t* masks, uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also,
+                          uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs,
+                          uint64_t* bucket_doc, uint64_t* bucket_byte);
+/* The same on the host, no HIP device needed: the kernels' walk tile by tile through the source they are compiled from
+ * (csrc/gft_route_piece.hpp, and the select's copy walk).  All pointers host; same contract and refusals; only
+ * blob[doc_off[0], doc_off[n_docs]) is read.  It is also what a finder routes with when it does not take the device route. */
+int gft_debug_route_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
+                         const uint32_t* masks, uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* also,
+                         uint8_t* out, uint64_t cap_bytes, uint64_t* out_off, uint64_t* doc_idx, uint64_t cap_docs,
+                         uint64_t* bucket_doc, uint64_t* bucket_byte);
+/* where that walk's borders are: the documents a counting tile (a wave) holds */
+void gft_debug_route_shape(uint32_t* tile_docs);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -443,6 +494,12 @@ int gft_finder_select_docs_device(gft_finder* f, const uint8_t* d_text_blob, con
                                   const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint8_t* d_out,
                                   uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* n_selected,
                                   uint64_t* total_bytes);
+/* gft_route_docs_device on the finder's engine with n_cols = gft_finder_n_expressions.  It asks of the finder what
+ * gft_finder_select_docs_device asks and refuses in its words. */
+int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                 const uint32_t* d_hit_bitmap, const uint32_t* masks, uint32_t n_buckets, uint32_t mode, uint32_t flags,
+                                 const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
+                                 uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
