@@ -268,6 +268,7 @@ enum class UnitRoute {
     deferred,   // count + prefix sum + fill + clamp into the table as the last batch left it; the true count is read afterwards
     counted,    // count + prefix sum, a read-back of the count, fill
 };
+constexpr const char* kUnitRouteName[] = {"host", "single", "deferred", "counted"};      // (in UnitRoute's order)
 constexpr uint64_t kHostUnitDocs = 1024;   // batches up to this many documents get their unit table from the host
 
 // What build_unit_table says of the table it made: the units the scan is launched over and the text range they cover.  The
@@ -418,6 +419,7 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
                       : can_defer                                     ? UnitRoute::deferred
                                                                       : UnitRoute::counted;
     if (route == UnitRoute::single && ++e->ctl_epoch < 2) { e->ctl_epoch = 1; route = UnitRoute::deferred; }      // (wrapped: this batch the general way)
+    e->last_unit_route = kUnitRouteName[(int)route];
     UnitTable table(e);
     int rc = build_unit_table(e, route, d_doc_off, h_doc_off, n_docs, unit_max, cap_units, L, table);
     if (rc) return rc;

@@ -127,8 +127,13 @@ typedef struct gft_matches {
 int gft_scan(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
              gft_matches* out);
 /* Device-resident variant: text_blob / doc_off already live in HBM on the engine's device; the returned
- * pointers are DEVICE pointers (n_docs / n_matches are host values).  text_blob must be readable for 64 bytes
- * past doc_off[n_docs] (vector loads). */
+ * pointers are DEVICE pointers (n_docs / n_matches are host values).  Where the text lies: d_text_blob needs no alignment and
+ * d_doc_off[0] may be non-zero -- a caller's buffer at any address, a bucket's run inside the blob of gft_route_docs_device.  The
+ * bytes [0, d_doc_off[0]) in front of the first document must be readable, and d_text_blob must be readable for 64 bytes past
+ * d_doc_off[n_docs] (vector loads); what those bytes hold never changes the answer, neither the matches nor gft_last_nonascii --
+ * not the other half of a keyword that a document border cuts, not the other half of a rune, not a neighbouring bucket's text
+ * (tests/test_gpu_placement.py).  The same holds for gft_scan's host buffers: [0, doc_off[n_docs]) is uploaded as it is and
+ * nothing behind it is read. */
 int gft_scan_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                     uint32_t flags, gft_matches* out_dev);
 
@@ -201,15 +206,19 @@ int gft_process(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off
  * first pass without regex hits, host regex engine on the candidate documents only, second pass with their hits. */
 int gft_process_again(gft_engine* e, uint64_t n_docs, const gft_extra_matches* extra, uint32_t* hit_bitmap);
 /* Device-resident variant of gft_process (all pointers are device pointers, bitmap written in HBM).  As for
- * gft_scan_device, d_text_blob must be readable for 64 bytes past doc_off[n_docs] (vector loads); documents of 4 GiB
- * and more, and offsets that descend, are refused with GFT_E_INVALID. */
+ * gft_scan_device: d_text_blob needs no alignment, d_doc_off[0] may be non-zero, the bytes [0, d_doc_off[0]) and the 64 bytes
+ * past d_doc_off[n_docs] must be readable (vector loads) and what they hold never changes the answer -- on every way a batch
+ * gets its work units (gft_debug_last_unit_route), the deferred ones included, which tell the kernels nothing of the blob's end.
+ * Documents of 4 GiB and more, and offsets that descend, are refused with GFT_E_INVALID. */
 int gft_process_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                        uint32_t flags, const gft_extra_matches* d_extra, uint32_t* d_hit_bitmap);
 /* The same, pipelined: _begin enqueues the batch (units -> scan -> solve -> the read-back of its control block) on the
  * engine's stream and returns WITHOUT waiting; _end completes the oldest batch begun and returns ITS status (and sets
  * gft_last_nonascii for it).  At most two batches are in flight, so a caller that begins batch i + 1 before it ends
  * batch i keeps the device busy while the host reads batch i's verdict and launches the next one -- what a step of 0.5 ms
- * (125 000 documents: one GPU's share of 1 M over 8) needs.  Inputs and the bitmap of a batch must stay untouched until its
+ * (125 000 documents: one GPU's share of 1 M over 8) needs.  Where the text lies is as for gft_process_device: no alignment,
+ * d_doc_off[0] may be non-zero, the bytes in front of the first document and the 64 bytes of slack are readable and never
+ * change the answer; the two batches in flight may lie at different residues behind different lead bytes.  Inputs and the bitmap of a batch must stay untouched until its
  * _end has returned: a batch that outgrew the engine's unit table or match pool is run again there.  A batch that cannot be
  * deferred (caller-supplied matches, host-solved expressions, an engine's first batches, more documents than the unit
  * table holds) completes inside _begin; _end then only hands its status and its verdict back.  A batch is run again when
@@ -904,6 +913,12 @@ int gft_debug_tables(const uint8_t* terms_blob, const uint64_t* term_off, uint32
  * call of a kernel on scan2's tables (scan2, scan5) runs with (8 192 after gft_build, down to 512 behind dense batches;
  * the other kernels do not read it), *fifo_cap (nullable) = the fifo entries that `learn` sizes it by. */
 int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fifo_cap);
+/* How the last batch that the handle launched got its table of work units (read-only; *name is a static string): "host"
+ * (computed on the host and uploaded: up to 1 024 documents from host memory), "counted" (counted on the device and the count
+ * read back: a handle's first batches, gft_scan_device, a batch that is run again), "deferred" (filled into the table as the
+ * batch before left it, the count read afterwards) or "single" (one launch on the assumption of one unit per document, after
+ * two such batches); "" before the first batch.  A batch that was deferred and then run again reports the second run. */
+int gft_debug_last_unit_route(const gft_engine* e, const char** name);
 /* ... and the numbers of the plan that plan_scan makes for `terms`, compiled the same way: *kernel as above,
  * plan[0..3] = the longest keyword's bytes, then the shape of scan5's fifo entries (s5_term_bits, s5_pos_bias: term id and
  * relative position in 32 bits; both 0 under another kernel) and the entries of a wave's LDS match fifo, which the unit size
