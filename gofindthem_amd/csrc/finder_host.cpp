@@ -537,6 +537,40 @@ Error Finder::RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint64_t* d_row_idx,
+                             const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap,
+                             uint64_t* total, int* lowered) {
+    last_code_ = 0;
+    if (lowered) *lowered = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    std::vector<Record> none;
+    Error err = collect(std::string(), false, none);
+    if (!err.empty()) return err;
+    int rc = gft_hit_spans_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, d_row_idx, want, d_span_off,
+                                  d_span_start, d_span_len, d_span_term, cap, total);
+    if (rc) return fail_gft(rc);
+    if (caseSensitive_ || !n_docs || !gft_last_nonascii(gpu_->handle())) return "";
+    // as repeat_if_not_ascii: the batch is lowered in full on the device and scanned again from there; the spans then index the
+    // lowered text, whose lengths may differ from the caller's
+    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "hit spans of a batch that leaves ASCII need the device ToLower on a single device";
+    }
+    const uint8_t* d_low = nullptr;
+    const uint64_t* d_low_off = nullptr;
+    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
+    if (rc) return fail_gft(rc);
+    rc = gft_hit_spans_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, d_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
+                              d_span_term, cap, total);
+    if (rc) return fail_gft(rc);
+    if (lowered) *lowered = 1;
+    return "";
+}
+
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
     if (!gpu_sub_ || !regexes_.empty()) {
@@ -832,6 +866,15 @@ int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, cons
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->RouteDocsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, masks, n_buckets, mode, flags, d_also, d_out, cap_bytes,
                                                     d_out_off, d_doc_idx, cap_docs, bucket_doc, bucket_byte), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_hit_spans_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,
+                                const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len,
+                                uint32_t* d_span_term, uint64_t cap, uint64_t* total, int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->HitSpansDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
+                                                   d_span_term, cap, total, lowered), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

@@ -219,6 +219,7 @@ int install_tables(gft_engine* e, TableSet&& set, uint32_t flags) {
     SyncOnExit drained(e);                              // (declared behind the temporaries the uploads read from: it goes first)
     e->built = false;
     e->have_programs = false;   // slots refer to the dictionary: programs must be set again
+    e->d_spans.wit_ready = false;
     e->n_exprs = 0;
     gft_engine::TableBufs& d = e->d_tabs;
     if ((rc = upload(e, d.dfa.byte_class, bc, "table upload"))) return rc;
@@ -357,6 +358,7 @@ int gft_set_programs(gft_engine* e, const uint32_t* prog_words, const uint64_t* 
     // from here on the device holds a mixture of two sets until the last upload has landed: an error on the way leaves a
     // handle that answers GFT_E_NOT_BUILT, as after gft_build
     e->have_programs = false;
+    e->d_spans.wit_ready = false;
     e->n_exprs = 0;
     gft_engine::ProgramBufs& d = e->d_progs;
     if ((rc = upload(e, d.prog, ps.prog, "program upload"))) return rc;

@@ -192,6 +192,14 @@ struct gft_engine {
     // entries' lengths and compact offsets the select's copy pass searches
     struct RouteBufs { DevBuf masks, member, len, cnt, tile_bytes, base, partial, ctl, ent_len, c_off, c_src; } d_route;
 
+    // hit spans and redaction (gft_spans.hip): the witness table of the installed programs (witness_terms.hpp; compiled and
+    // uploaded by the first spans call after a gft_set_programs, dropped with the programs), the mask, the marks of a batch's
+    // matches with their prefix sums and scan partials; the redaction's span addresses and its flag word
+    struct SpanBufs {
+        bool wit_ready = false;
+        DevBuf wit_off, wit_expr, want, keep, rank, partial, dst, ctl;
+    } d_spans;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

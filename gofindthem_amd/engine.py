@@ -258,6 +258,124 @@ def route_shape():
     return int(t.value)
 
 
+def hit_spans_tensor(call, text, doc_off, bitmap, n_cols, want, row_idx):
+    """what Engine.hit_spans_device and Finder.SpansDevice share: `call(d_text, d_doc_off, n_docs, d_bitmap, d_row_idx, want, d_span_off,
+    d_span_start, d_span_len, d_span_term, cap, byref(total))` is gft_hit_spans_device on some handle and raises on an error.  Two
+    calls: count only, then into tensors of exactly the size counted.  Returns (span_off int64 [n + 1], start, len, term int32 [total])"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    W = (n_cols + 31) // 32
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
+            (((row_idx, 8, "row_idx"),) if row_idx is not None else ()):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("hit_spans_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or (row_idx is not None and row_idx.numel() != n_docs) or \
+            (row_idx is None and W and n_docs > 0 and bitmap.numel() != n_docs * W):
+        raise ValueError("hit_spans_device: doc_off, bitmap and row_idx do not describe the same batch")
+    w = _want_words(want, n_cols)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None,
+            row_idx.data_ptr() if row_idx is not None else None, _p(w))
+    total = C.c_uint64(0)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, None, None, None, None, 0, C.byref(total))
+    n = int(total.value)
+    span_off = torch.empty(n_docs + 1, dtype=torch.int64, device=text.device)
+    start, length, term = (torch.empty(n, dtype=torch.int32, device=text.device) for _ in range(3))
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, span_off.data_ptr(), start.data_ptr() if n else None, length.data_ptr() if n else None, term.data_ptr() if n else None, n,
+         C.byref(total))
+    return span_off, start, length, term
+
+
+def redact_spans_tensor(call, text, doc_off, span_off, start, length, mask):
+    """gft_redact_spans_device through `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, mask_byte)`, in place"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("redact_spans_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel():
+        raise ValueError("redact_spans_device: doc_off, span_off and the span arrays do not describe the same batch")
+    mask = mask[0] if isinstance(mask, (bytes, bytearray)) else int(mask)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
+         length.data_ptr() if length.numel() else None, mask)
+
+
+def witness_terms_host(programs, n_terms, n_slots):
+    """gft_debug_witness_terms over a list of postfix programs -> (off uint64 [n_terms + 1], expr uint32 []); no device needed"""
+    L = _lib.load()
+    words = np.asarray([w for p in programs for w in p], dtype=np.uint32)
+    poff = np.zeros(len(programs) + 1, dtype=np.uint64)
+    if programs:
+        poff[1:] = np.cumsum([len(p) for p in programs], dtype=np.uint64)
+    if words.size == 0:
+        words = np.zeros(1, dtype=np.uint32)
+    off = np.zeros(n_terms + 1, dtype=np.uint64)
+    needed = C.c_uint64(0)
+    rc = L.gft_debug_witness_terms(_p(words), _p(poff), len(programs), n_terms, n_slots, _p(off), None, 0, C.byref(needed))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_witness_terms")
+    expr = np.zeros(max(int(needed.value), 1), dtype=np.uint32)
+    rc = L.gft_debug_witness_terms(_p(words), _p(poff), len(programs), n_terms, n_slots, _p(off), _p(expr), int(needed.value), C.byref(needed))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_witness_terms")
+    return off, expr[:int(needed.value)]
+
+
+def hit_spans_host(match_off, term_id, pos, term_len, pos_end, wit_off, wit_expr, rows, n_exprs, row_idx=None, want=None, cap=None, guard=0,
+                   with_len=True, with_term=True):
+    """gft_debug_hit_spans over host arrays -> (total, span_off uint64 [n + 1 + guard], start, len, term uint32 [cap + guard]); no
+    device needed.  cap None: count first, then exactly the total; the guard entries behind the caps hold 0xA5.. and must come back
+    untouched.  with_len / with_term False: that array is not passed (None is returned for it)"""
+    L = _lib.load()
+    mo = np.ascontiguousarray(match_off, dtype=np.uint64)
+    n_docs = mo.size - 1
+    tid, ps = np.ascontiguousarray(term_id, dtype=np.uint32), np.ascontiguousarray(pos, dtype=np.uint32)
+    tl = np.ascontiguousarray(term_len, dtype=np.uint32)
+    wo, we = np.ascontiguousarray(wit_off, dtype=np.uint64), np.ascontiguousarray(wit_expr, dtype=np.uint32)
+    W = (n_exprs + 31) // 32
+    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W else None
+    ri = np.ascontiguousarray(row_idx, dtype=np.uint64) if row_idx is not None else None
+    w = _want_words(want, n_exprs)
+    total = C.c_uint64(0)
+
+    def call(so, a, b, c, cp):
+        rc = L.gft_debug_hit_spans(_p(mo), _p(tid) if tid.size else None, _p(ps) if ps.size else None, n_docs, _p(tl) if tl.size else None, int(pos_end),
+                                   _p(wo), _p(we) if we.size else None, _p(bm) if bm is not None and bm.size else None, n_exprs, _p(ri), _p(w),
+                                   _p(so), _p(a), _p(b), _p(c), cp, C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_hit_spans")
+    if cap is None:
+        call(None, None, None, None, 0)
+        cap = int(total.value)
+    span_off = np.full(n_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    arrs = [np.full(cap + guard, 0xA5A5A5A5, dtype=np.uint32) for _ in range(3)]
+    call(span_off, arrs[0] if cap or guard else None, arrs[1] if with_len and (cap or guard) else None,
+         arrs[2] if with_term and (cap or guard) else None, cap)
+    return int(total.value), span_off, arrs[0], arrs[1] if with_len else None, arrs[2] if with_term else None
+
+
+def redact_spans_host(blob, doc_off, span_off, start, length, mask=0x2A):
+    """gft_debug_redact_spans over a copy of `blob` -> the masked bytes (numpy uint8); no device needed"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8).copy() if not isinstance(blob, np.ndarray) else np.array(blob, dtype=np.uint8)
+    off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
+    st, ln = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(length, dtype=np.uint32)
+    rc = L.gft_debug_redact_spans(_p(a) if a.size else None, _p(off), off.size - 1, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None,
+                                  int(mask))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_redact_spans")
+    return a
+
+
+def spans_shape():
+    """(matches a workgroup of the mark pass takes per step, spans a wave of the fill owns) (gft_debug_spans_shape)"""
+    t, k = C.c_uint32(0), C.c_uint32(0)
+    _lib.load().gft_debug_spans_shape(C.byref(t), C.byref(k))
+    return int(t.value), int(k.value)
+
+
 class Engine:
     """Thin object wrapper of the C ABI (one gft_engine handle)."""
 
@@ -452,6 +570,22 @@ class Engine:
         with nothing but those 2 (B + 1) numbers crossing the link"""
         return route_docs_tensor(lambda *a: self._check(self._L.gft_route_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, masks, mode,
                                  rest, also, count_only=True)
+
+    def hit_spans_device(self, text, doc_off, bitmap, want=None, row_idx=None, fold=False):
+        """where the expressions matched (gft_hit_spans_device): for a resident batch and its hit rows -- as process_device left them
+        --, the byte spans of the keyword occurrences that belong to a true, wanted expression.  Tensors as for select_docs_device;
+        want: None (every expression) or ceil(n_exprs / 32) host uint32 words; row_idx: None, or int64 [n]: the row of document d
+        (the doc_idx of a select or a route of the processed batch).  Returns device tensors (span_off int64 [n + 1], start, len,
+        term int32 [total]): document d's spans are span_off[d]:span_off[d + 1], start relative to the document.  The call runs
+        twice: count only, then into tensors of exactly that size"""
+        flags = _lib.GFT_FOLD_ASCII if fold else 0
+        return hit_spans_tensor(lambda t, o, n, *a: self._check(self._L.gft_hit_spans_device(self._h, t, o, n, flags, *a)), text, doc_off, bitmap,
+                                self.n_exprs, want, row_idx)
+
+    def redact_spans_device(self, text, doc_off, span_off, start, length, mask=b"*"):
+        """overwrites, in place, the bytes of every span with the mask byte (gft_redact_spans_device); every other byte of `text`
+        keeps its value.  span_off, start, length: what hit_spans_device returned for (text, doc_off)"""
+        redact_spans_tensor(lambda *a: self._check(self._L.gft_redact_spans_device(self._h, *a)), text, doc_off, span_off, start, length, mask)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

@@ -425,6 +425,77 @@ int gft_debug_route_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t 
 /* where that walk's borders are: the documents a counting tile (a wave) holds */
 void gft_debug_route_shape(uint32_t* tile_docs);
 
+/* ---- Hit spans and redaction on the device: where the expressions matched (csrc/gft_spans.hip) ------------------------------
+ * The step behind gft_process_device, the select and the route: for a resident batch and its hit rows, the byte spans of the
+ * keyword occurrences that belong to a true, wanted expression -- and the overwrite of exactly those bytes with a mask byte.
+ * Witness terms: P(i), the witness terms of expression i, are the dictionary slots (slot < gft_n_terms) of the GFT_OP_UNIT words
+ * of its public postfix program that lie outside the operand of every GFT_OP_NOT.  A unit under a NOT is no witness, whatever
+ * the nesting -- one under two NOTs is not either: a NOT removes the units below it and nothing restores them.  INORD changes
+ * nothing.  Extra slots (>= n_terms: regex literals, caller-supplied matches) are never witnesses, the library has no length for
+ * them; an extra literal with the text of a keyword shares the keyword's term id and counts through it.  A slot that occurs twice
+ * in an expression is listed once.  This is the rule "highlight every query term of a matching query": in a true
+ * ("a" and "b") or "c" an occurrence of a is kept even if b is absent -- no minimal witness (which branch of an OR fired) is
+ * attempted.
+ * Kept matches: a match (document d, term t, pos) of the canonical CSR -- what gft_scan_device gives for the batch -- is kept
+ * when some expression i with t in P(i) has its bit set in `want` and in row r(d) of the hit bitmap (layout of gft_process,
+ * gft_n_exprs columns).  Bits at and above n_exprs are ignored in rows and in want, whatever they hold.  want: HOST memory,
+ * W = ceil(n_exprs / 32) words, copied by the call; NULL = every expression.  r(d) = d, or d_row_idx[d] with d_row_idx (nullable,
+ * uint64 [n_docs]): the blob a select or a route produced is explained against the bitmap of the batch it came from -- their
+ * d_doc_idx output is exactly this array; repeated indices (a document routed to two buckets) are valid.  Every index must name a
+ * row of d_hit_bitmap: the call cannot know how many it has.
+ * Spans: len = the term's byte length; start = pos on a GFT_POS_START engine, pos + 1 - len on a GFT_POS_END engine; both uint32,
+ * relative to the document's first byte.  term = the term id.  The kept matches of a document stay in the order gft_scan_device
+ * gives them (the compaction is stable): the spans of document d are [d_span_off[d], d_span_off[d + 1]), d_span_off[0] = 0,
+ * d_span_off[n_docs] = the total.
+ * The call runs the scan with positions and the canonical CSR, as gft_scan_device does, under its placement contract: no
+ * alignment, d_doc_off[0] may be non-zero, 64 readable bytes of slack behind d_doc_off[n_docs], and neither the slack nor the lead
+ * bytes ever change the answer.  Behind the scan three launches on the engine's stream (gft_profile_read: "span_mark",
+ * "span_scan", "span_place"); the call waits for the stream.  It counts as a scan: it publishes gft_last_nonascii for the batch
+ * and leaves the engine's scan state as gft_scan_device leaves it.  flags: GFT_FOLD_ASCII; GFT_SCAN_UNIQUE and GFT_POS_RUNES:
+ * GFT_E_INVALID.
+ * Cap protocol of gft_compact_device: cap counts span entries; an entry at or past cap is NOT written and nothing is stored at or
+ * past any array + cap; d_span_off (n_docs + 1 entries, nullable, always complete when given) is not capped; all span arrays NULL
+ * with cap == 0 counts only; GFT_OK in both cases and *total (host, nullable) is always handed back -- the caller compares it with
+ * cap and calls again.  d_span_len and d_span_term may each be NULL on their own.
+ * Needs a dictionary and programs (GFT_E_NOT_BUILT).  Handles over several devices: GFT_E_UNSUPPORTED.  Between
+ * gft_process_device_begin and _end only after _complete.  n_docs == 0 and n_exprs == 0 are valid and give no span.  An output
+ * that overlaps the text, the offsets, the bitmap (its first n_docs rows; with d_row_idx its first row), d_row_idx or another
+ * output: GFT_E_INVALID.  GFT_E_NOMEM: no room for the work buffers (12 bytes a match).  The handle stays usable after any error.
+ * Cost note: a term that stands in thousands of expressions makes the walk of one match that long when none of them is true and
+ * wanted (DESIGN.md 7 #2k). */
+int gft_hit_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
+                         const uint32_t* d_hit_bitmap, const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off,
+                         uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap, uint64_t* total);
+/* In place: byte d_doc_off[d] + start + k for k < len of every span (d_span_off [n_docs + 1], spans [d_span_off[0],
+ * d_span_off[n_docs]) of d_span_start / d_span_len) becomes mask_byte; every other byte of the buffer keeps its value,
+ * byte-exactly -- the lead bytes, the slack, the neighbours of a span's first and last byte: the fill stores single bytes.  Spans
+ * may overlap, nest and repeat.  mask_byte > 255: GFT_E_INVALID.  A span that reaches past its document's end is found on the
+ * device, before the fill, and refused with GFT_E_INVALID: nothing at all is written then, inside the documents or outside.
+ * gft_profile_read: "redact_fill" (the check pass that resolves every span's address and the fill pass run under that one name).
+ * Masking whole keyword occurrences byte by byte keeps valid UTF-8 valid when the mask is ASCII, and the result has the same
+ * length: the offsets stay good.  Needs no dictionary and no programs, leaves gft_last_nonascii alone; handles over several
+ * devices: GFT_E_UNSUPPORTED; between gft_process_device_begin and _end only after _complete; GFT_E_NOMEM: no room for the work
+ * buffer (8 bytes a span); n_docs == 0 and no spans are valid; the handle stays usable after any error. */
+int gft_redact_spans_device(gft_engine* e, uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                            const uint32_t* d_span_start, const uint32_t* d_span_len, uint32_t mask_byte);
+/* The host forms, no HIP device needed, same contracts, all pointers host.  The witness table of a set of programs as the
+ * term -> expressions CSR the kernels read (csrc/witness_terms.cpp): off [n_terms + 1] (nullable, always complete), expr (cap
+ * entries; NULL with cap 0 counts only) ascending per term, *needed = their number.  GFT_E_INVALID: a program that is no postfix
+ * expression, a slot >= n_slots. */
+int gft_debug_witness_terms(const uint32_t* prog_words, const uint64_t* prog_off, uint32_t n_exprs, uint32_t n_terms, uint32_t n_slots,
+                            uint64_t* off, uint32_t* expr, uint64_t cap, uint64_t* needed);
+/* gft_hit_spans_device behind its scan: the kernels' walk, match tile by match tile through the source they are compiled from
+ * (csrc/gft_spans_piece.hpp), over a match CSR (match_off[0] = 0), the terms' lengths and a witness table. */
+int gft_debug_hit_spans(const uint64_t* match_off, const uint32_t* term_id, const uint32_t* pos, uint64_t n_docs, const uint32_t* term_len,
+                        uint32_t pos_end, const uint64_t* wit_off, const uint32_t* wit_expr, const uint32_t* bitmap, uint32_t n_exprs,
+                        const uint64_t* row_idx, const uint32_t* want, uint64_t* span_off, uint32_t* span_start, uint32_t* span_len,
+                        uint32_t* span_term, uint64_t cap, uint64_t* total);
+/* gft_redact_spans_device: the check and the fill's walk, span tile by span tile and lane by lane through the same header. */
+int gft_debug_redact_spans(uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
+                           const uint32_t* span_len, uint32_t mask_byte);
+/* where those walks' borders are: the matches a workgroup of the mark pass takes per step, the spans a wave of the fill owns */
+void gft_debug_spans_shape(uint32_t* tile_matches, uint32_t* tile_spans);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -509,6 +580,16 @@ int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, cons
                                  const uint32_t* d_hit_bitmap, const uint32_t* masks, uint32_t n_buckets, uint32_t mode, uint32_t flags,
                                  const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
                                  uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte);
+/* gft_hit_spans_device on the finder's engine under the finder's case rule, over the rows the calls above left.  A
+ * case-insensitive finder passes GFT_FOLD_ASCII; when the batch is not fold-safe (gft_last_nonascii) it lowers the batch with the
+ * gft_to_lower_device kernels and scans the lowered text, as gft_finder_process_device does, and sets *lowered = 1 (else 0).  A
+ * LIMITATION: the spans then index the LOWERED text -- the bytes gft_to_lower_device gives for the batch, with its offsets --, not
+ * the caller's text: lower-casing can change lengths, and no mapping back is built.  It asks of the finder what
+ * gft_finder_process_device asks and refuses in its words; such a batch on a finder without the device ToLower
+ * (GFT_DEVICE_TOLOWER=0): GFT_E_UNSUPPORTED. */
+int gft_finder_hit_spans_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,
+                                const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len,
+                                uint32_t* d_span_term, uint64_t cap, uint64_t* total, int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
