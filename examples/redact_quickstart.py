@@ -15,18 +15,30 @@ f = Finder(GpuEngine(), EmptyRgxEngine(), False)
 f.AddExpressionWithTag('"error" and not "retry"', "alerts")
 f.AddExpressionWithTag('"timeout" or "refused"', "network")
 
-log = b"""09:00:01 service started
+log = """09:00:01 service started
 09:00:07 ERROR disk full on /var
 09:00:09 error sending mail, will retry
 09:01:12 connection refused by 10.0.0.7
 09:01:15 request served in 12 ms
 09:02:40 Timeout after 30 s, ERROR reported
-"""
+09:03:02 CAFÉ gateway in İstanbul: ERROR reported
+""".encode()
 
 idx, spans, lowered = f.SpansLines(log)
 masked, _ = f.RedactLines(log, mask=b"#")
 lines = masked.split(b"\n")
 print("lines that hit: %s%s" % (idx.tolist(), " (positions index the lower-cased text)" if lowered else ""))
+for k, d in enumerate(idx.tolist()):
+    print("    " + lines[d].decode())
+    for start, end, keyword in spans[k]:
+        print("        bytes %d..%d: %s" % (start, end, keyword.decode()))
+
+# The É and the İ make the finder lower the whole batch before it scans it (strings.ToLower; "İ" shrinks from two bytes to one): the
+# calls above answer in the lower-cased text.  source=True maps the spans back: the caller's own bytes, lengths and upper case
+idx, spans, lowered = f.SpansLines(log, source=True)
+masked, _ = f.RedactLines(log, mask=b"#", source=True)
+lines = masked.split(b"\n")
+print("the same with source=True (positions index the caller's text, lowered = %s):" % lowered)
 for k, d in enumerate(idx.tolist()):
     print("    " + lines[d].decode())
     for start, end, keyword in spans[k]:

@@ -167,6 +167,10 @@ SYMBOLS = {
     "gft_debug_redact_spans": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u32]),
     "gft_debug_spans_shape": (None, [C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_hit_spans_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_finder_hit_spans_source_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_map_spans_to_source_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "gft_debug_map_spans_to_source": (_i, [_vp, _vp, _u64, _vp, _vp, _vp]),
+    "gft_debug_lowermap_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_group_process_json_lines": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_tables": (_i, [_vp, _vp, _u32, _vp, _u64, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp, _u64, C.POINTER(_u64), _vp, _u64]),

@@ -10,6 +10,7 @@
 
 #include "compact_host.hpp"
 #include "gft_guard.hpp"
+#include "gft_lowermap.hpp"
 #include "gft_tolower.hpp"
 
 namespace gft {
@@ -539,9 +540,13 @@ Error Finder::RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
 
 Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint64_t* d_row_idx,
                              const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap,
-                             uint64_t* total, int* lowered) {
+                             uint64_t* total, int* lowered, bool source) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
+    if (source && cap && (!d_span_off || !d_span_len)) {
+        last_code_ = GFT_E_INVALID;
+        return "hit spans in source positions need the span offsets and the length array whenever spans are written";
+    }
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
@@ -568,6 +573,11 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
                               d_span_term, cap, total);
     if (rc) return fail_gft(rc);
     if (lowered) *lowered = 1;
+    // the spans that were written (those below the cap) index the lowered text: back to the caller's bytes, in place
+    if (source && cap) {
+        rc = gft_map_spans_limit(gpu_->handle(), d_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, cap);
+        if (rc) return fail_gft(rc);
+    }
     return "";
 }
 
@@ -874,7 +884,17 @@ int gft_finder_hit_spans_device(gft_finder* f, const uint8_t* d_text_blob, const
     if (!f) return GFT_E_INVALID;
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->HitSpansDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
-                                                   d_span_term, cap, total, lowered), GFT_E_ENGINE);
+                                                   d_span_term, cap, total, lowered, false), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_hit_spans_source_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                       const uint32_t* d_hit_bitmap, const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off,
+                                       uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap, uint64_t* total,
+                                       int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->HitSpansDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
+                                                   d_span_term, cap, total, lowered, true), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

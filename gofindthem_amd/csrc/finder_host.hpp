@@ -137,10 +137,12 @@ public:
                           uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,
                           uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte);
     // gft_hit_spans_device on the finder's engine under the finder's case rule: a batch that leaves ASCII is lowered on the device
-    // and scanned again from there -- *lowered = 1: the spans index the lowered text.  What ProcessDevice asks, refused in its words
+    // and scanned again from there -- *lowered = 1: the spans index the lowered text.  What ProcessDevice asks, refused in its words.
+    // source: the spans of a lowered batch are mapped back to the caller's bytes before the call returns (gft_map_spans_limit over
+    // the entries below cap); cap != 0 then needs d_span_off and d_span_len
     Error HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint64_t* d_row_idx,
                          const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap,
-                         uint64_t* total, int* lowered);
+                         uint64_t* total, int* lowered, bool source = false);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

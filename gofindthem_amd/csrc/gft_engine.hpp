@@ -200,6 +200,10 @@ struct gft_engine {
         DevBuf wit_off, wit_expr, want, keep, rank, partial, dst, ctl;
     } d_spans;
 
+    // lowered spans mapped back to the source text (gft_lowermap.hip): the pieces' offset table, the lowered offsets the count
+    // passes want, the mapped spans between the check and the write pass, the flag word
+    struct LowerMapBufs { DevBuf tab, off, mapped, ctl; } d_lmap;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {
@@ -356,6 +360,14 @@ struct HostPlan {
 };
 void plan_host(const gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, HostPlan& plan);
 int host_eval(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, const HostPlan& plan, uint32_t* h_bitmap, uint32_t* d_bitmap);
+
+// ---- gft_lower_api.cpp -------------------------------------------------------------------------------------------------
+// the unit table of a batch, the count pass and the prefix sum of gft_to_lower_device into e->d_lw (units, unit_base, unit_out) and
+// d_out_off; waits for the stream.  who: the entry point the refusals name; stage: NULL, or one gft_profile_read name for the
+// count and the prefix instead of "lower_count" / "lower_scan"; text_range: NULL, or [2] for doc_off[0] and doc_off[n_docs]
+int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, const uint8_t* d_out, uint64_t cap,
+                uint64_t* d_out_off, uint64_t* n_units, uint64_t* total, const char* who, const char* stage = nullptr,
+                uint64_t* text_range = nullptr);
 
 // ---- gft_staging.cpp ---------------------------------------------------------------------------------------------------
 // device -> pageable host memory through the bounce buffers; synchronous: returns when dst holds the bytes

@@ -5,15 +5,17 @@
 using namespace gft;
 using namespace gft::api;
 
-namespace {
+namespace gft::api {
 
 // strings.ToLower of a batch, first half: the unit table, the count pass, the prefix sum and d_out_off (complete when this
 // returns GFT_OK; the stream has drained).  *n_units / *total: what lower_write needs and what the caller sizes its buffer by.
-// d_out / cap take part in the overlap check only.
+// d_out / cap take part in the overlap check only.  (gft_engine.hpp: gft_lowermap_api.cpp builds its table on these passes.)
 int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, const uint8_t* d_out, uint64_t cap,
-                uint64_t* d_out_off, uint64_t* n_units, uint64_t* total) {
+                uint64_t* d_out_off, uint64_t* n_units, uint64_t* total, const char* who, const char* stage, uint64_t* text_range) {
     hipStream_t st = e->stream;
+    const std::string me(who);
     *n_units = 0; *total = 0;
+    if (text_range) text_range[0] = text_range[1] = 0;
     if (!n_docs) {
         HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, st), "lower offsets");
         HIP_TRY(hipStreamSynchronize(st), "lower offsets");
@@ -47,9 +49,10 @@ int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off,
     }
     HIP_TRY(hipMemcpyAsync(h_ctl, ctl, 32, hipMemcpyDeviceToHost, st), "lower units");
     HIP_TRY(hipStreamSynchronize(st), "lower units");
-    if (h_ctl[3] & 1) return fail(e, GFT_E_INVALID, "gft_to_lower_device: document offsets descend, or a document of 4 GiB or more");
+    if (h_ctl[3] & 1) return fail(e, GFT_E_INVALID, me + ": document offsets descend, or a document of 4 GiB or more");
     if (lower_buffers_overlap(d_text, h_ctl[1], h_ctl[2], d_doc_off, n_docs, d_out, cap, d_out_off))
-        return fail(e, GFT_E_INVALID, "gft_to_lower_device: the output overlaps the input");
+        return fail(e, GFT_E_INVALID, me + ": the output overlaps the input");
+    if (text_range) { text_range[0] = h_ctl[1]; text_range[1] = h_ctl[2]; }
     const uint64_t nu = h_ctl[0];
     HIP_TRY(e->d_lw.units.ensure(nu * sizeof(Unit)), "lower alloc");
     HIP_TRY(e->d_lw.unit_cnt.ensure(nu * 4), "lower alloc");
@@ -60,21 +63,25 @@ int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off,
         HIP_TRY(launch_unit_fill(d_doc_off, n_docs, e->d_lw.unit_base.as<uint64_t>(), e->d_lw.units.as<Unit>(), kLowerUnitMax, st, nu), "lower units");
     }
     {
-        ProfScope ps(e, "lower_count");
+        ProfScope ps(e, stage ? stage : "lower_count");
         HIP_TRY(launch_lower_count(d_text, d_doc_off, e->d_lw.units.as<Unit>(), nu, T, e->d_lw.unit_cnt.as<uint32_t>(), e->n_cus, st), "lower count");
     }
     {
-        ProfScope ps(e, "lower_scan");
+        ProfScope ps(e, stage ? stage : "lower_scan");
         HIP_TRY(launch_exclusive_scan(e->d_lw.unit_cnt.as<uint32_t>(), nu, e->d_lw.unit_out.as<uint64_t>(), e->d_lw.partial.as<uint64_t>(), st), "lower scan");
         HIP_TRY(launch_lower_offsets(e->d_lw.unit_base.as<uint64_t>(), e->d_lw.unit_out.as<uint64_t>(), n_docs, d_out_off, flags, st), "lower scan");
     }
     HIP_TRY(hipMemcpyAsync(h_ctl, e->d_lw.unit_out.as<uint64_t>() + nu, 8, hipMemcpyDeviceToHost, st), "lower total");
     HIP_TRY(hipMemcpyAsync(h_ctl + 3, ctl + 3, 8, hipMemcpyDeviceToHost, st), "lower total");
     HIP_TRY(hipStreamSynchronize(st), "lower count");
-    if (h_ctl[3] & 2) return fail(e, GFT_E_INVALID, "gft_to_lower_device: the lower-case form of a document has 4 GiB or more");
+    if (h_ctl[3] & 2) return fail(e, GFT_E_INVALID, me + ": the lower-case form of a document has 4 GiB or more");
     *n_units = nu; *total = h_ctl[0];
     return GFT_OK;
 }
+
+}  // namespace gft::api
+
+namespace {
 
 // ... second half: the write pass over the unit table and prefix sums lower_count left in the engine.  Nothing waits here.
 int lower_write(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_units, uint8_t* d_out, uint64_t cap) {
@@ -104,7 +111,7 @@ int gft_to_lower_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_
     if (rc) return rc;
     DeviceGuard g(e->device);
     uint64_t n_units = 0, n_total = 0;
-    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, d_out, cap, d_out_off, &n_units, &n_total))) return rc;
+    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, d_out, cap, d_out_off, &n_units, &n_total, "gft_to_lower_device"))) return rc;
     if (total) *total = n_total;
     if ((rc = lower_write(e, d_text_blob, d_doc_off, n_units, d_out, cap))) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream), "lower write");
@@ -125,7 +132,7 @@ int gft_lower_owned(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d
     };
     if ((rc = room(e->d_lw.off, (n_docs + 1) * 8))) return rc;
     uint64_t n_units = 0, total = 0;
-    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, nullptr, 0, e->d_lw.off.as<uint64_t>(), &n_units, &total))) return rc;
+    if ((rc = lower_count(e, d_text_blob, d_doc_off, n_docs, nullptr, 0, e->d_lw.off.as<uint64_t>(), &n_units, &total, "gft_to_lower_device"))) return rc;
     if ((rc = room(e->d_lw.text, total + 64))) return rc;
     if ((rc = lower_write(e, d_text_blob, d_doc_off, n_units, e->d_lw.text.as<uint8_t>(), total))) return rc;
     *d_lowered = e->d_lw.text.as<uint8_t>();

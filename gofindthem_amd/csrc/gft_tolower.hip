@@ -3,11 +3,13 @@
 //
 //   (text, doc_off [n_docs + 1])  ->  (out, out_off [n_docs + 1]): every document's lower-case form, concatenated
 //
-//   k_lower<false>    output bytes per work unit {doc, lo, hi} (the unit table of k_unit_count / k_unit_fill)  -> unit_cnt
+//   k_lower<kLowerCount>  output bytes per work unit {doc, lo, hi} (the unit table of k_unit_count / k_unit_fill)  -> unit_cnt
 //   (k_scan_* of gft_kernels.hip: unit_cnt -> unit_out)
 //   k_lower_offsets   out_off[d] = unit_out[first unit of document d]
-//   k_lower<true>     the same walk again: prefix of the pieces' lengths over the wave (DPP), carried from trip to trip,
+//   k_lower<kLowerWrite>  the same walk again: prefix of the pieces' lengths over the wave (DPP), carried from trip to trip,
 //                     every lane writes its piece at unit_out[unit] + prefix
+//   k_lower<kLowerTable>  that walk for gft_map_spans_to_source_device (gft_lowermap.hip): instead of the piece's bytes every
+//                     lane stores WHERE its piece's output begins in its document's lower-case form, one uint32 per piece
 //
 // A wave owns a unit and walks it in trips of 1 KiB, a lane owns 16 bytes of a trip; what a piece becomes is decided by
 // gft_tolower_piece.hpp, which the host compiles too.  Lengths change (U+0130 shrinks, U+023A grows, an invalid byte becomes
@@ -35,7 +37,12 @@ struct LowerParams {
     const uint64_t* unit_out;       // write pass
     uint8_t* out;
     uint64_t cap;
+    const uint64_t* unit_base;      // table pass: the first unit of every document
+    uint32_t* tab;                  //             the pieces' offsets, a slot each (lowermap_slot)
+    uint64_t text_lo;               //             doc_off[0]
 };
+
+enum : int { kLowerCount = 0, kLowerWrite = 1, kLowerTable = 2 };
 
 // inclusive prefix sum over the 64 lanes with DPP moves (as gft_scan2_dev.hpp)
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
@@ -48,8 +55,9 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
-template <bool WRITE>
+template <int MODE>
 __global__ void __launch_bounds__(kLowerBlock) k_lower(const LowerParams P) {
+    constexpr bool WRITE = MODE != kLowerCount;
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = ((uint64_t)blockIdx.x * kLowerBlock + threadIdx.x) >> 6;
     const uint64_t n_waves = ((uint64_t)gridDim.x * kLowerBlock) >> 6;
@@ -58,6 +66,11 @@ __global__ void __launch_bounds__(kLowerBlock) k_lower(const LowerParams P) {
         const uint64_t doc_abs = P.doc_off[un.doc];
         const uint64_t doc_len = P.doc_off[un.doc + 1] - doc_abs;
         uint64_t carry = WRITE ? P.unit_out[u] : 0;
+        uint64_t slot = 0;
+        if (MODE == kLowerTable) {
+            carry -= P.unit_out[P.unit_base[un.doc]];                            // relative to the document's lowered start
+            slot = lowermap_slot(doc_abs - P.text_lo + un.lo, u) + lane;
+        }
         uint32_t sum = 0;
         for (uint64_t base = un.lo; base < un.hi; base += kLowerChunk) {       // (the same in every lane)
             const uint64_t o = base + lane * kLowerPiece;                       // the piece's offset in its document
@@ -72,7 +85,11 @@ __global__ void __launch_bounds__(kLowerBlock) k_lower(const LowerParams P) {
                 sum += len;
             } else {
                 const uint32_t incl = wave_incl_scan(len);
-                if (n) tolower_piece<true>(P.T, w, n, P.out, carry + (incl - len), P.cap);
+                if (MODE == kLowerTable) {
+                    if (n) P.tab[slot + (base - un.lo) / kLowerPiece] = (uint32_t)(carry + (incl - len));
+                } else if (n) {
+                    tolower_piece<true>(P.T, w, n, P.out, carry + (incl - len), P.cap);
+                }
                 carry += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
             }
         }
@@ -107,7 +124,7 @@ hipError_t launch_lower_count(const uint8_t* d_text, const uint64_t* d_doc_off, 
     LowerParams P{};
     P.text = d_text; P.doc_off = d_doc_off; P.units = d_units; P.n_units = n_units; P.T = T;
     P.unit_cnt = d_unit_cnt;
-    k_lower<false><<<dim3(lower_grid(n_units, n_cus)), dim3(kLowerBlock), 0, st>>>(P);
+    k_lower<kLowerCount><<<dim3(lower_grid(n_units, n_cus)), dim3(kLowerBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 
@@ -123,7 +140,18 @@ hipError_t launch_lower_write(const uint8_t* d_text, const uint64_t* d_doc_off, 
     LowerParams P{};
     P.text = d_text; P.doc_off = d_doc_off; P.units = d_units; P.n_units = n_units; P.T = T;
     P.unit_out = d_unit_out; P.out = d_out; P.cap = cap;
-    k_lower<true><<<dim3(lower_grid(n_units, n_cus)), dim3(kLowerBlock), 0, st>>>(P);
+    k_lower<kLowerWrite><<<dim3(lower_grid(n_units, n_cus)), dim3(kLowerBlock), 0, st>>>(P);
+    return hipGetLastError();
+}
+
+hipError_t launch_lower_table(const uint8_t* d_text, const uint64_t* d_doc_off, const Unit* d_units, uint64_t n_units, const LowerTable& T,
+                              const uint64_t* d_unit_base, const uint64_t* d_unit_out, uint64_t text_lo, uint32_t* d_tab, unsigned n_cus,
+                              hipStream_t st) {
+    if (!n_units) return hipSuccess;
+    LowerParams P{};
+    P.text = d_text; P.doc_off = d_doc_off; P.units = d_units; P.n_units = n_units; P.T = T;
+    P.unit_out = d_unit_out; P.unit_base = d_unit_base; P.tab = d_tab; P.text_lo = text_lo;
+    k_lower<kLowerTable><<<dim3(lower_grid(n_units, n_cus)), dim3(kLowerBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 

@@ -9,6 +9,7 @@
 #include "../../include/gft.h"
 #include "gft_kernels.hpp"
 #include "gft_tolower_piece.hpp"
+#include "gft_lowermap_piece.hpp"
 
 namespace gft {
 
@@ -39,6 +40,16 @@ hipError_t launch_lower_offsets(const uint64_t* d_unit_base, const uint64_t* d_u
                                 uint32_t* d_bad, hipStream_t st);
 hipError_t launch_lower_write(const uint8_t* d_text, const uint64_t* d_doc_off, const Unit* d_units, uint64_t n_units, const LowerTable& T,
                               const uint64_t* d_unit_out, uint8_t* d_out, uint64_t cap, unsigned n_cus, hipStream_t st);
+
+// the walk of launch_lower_write with the table form of the kernel: d_tab[lowermap_slot(..)] = where the piece's output begins
+// in its document's lower-case form (gft_lowermap_piece.hpp); d_unit_base: the first unit of every document; text_lo: doc_off[0]
+hipError_t launch_lower_table(const uint8_t* d_text, const uint64_t* d_doc_off, const Unit* d_units, uint64_t n_units, const LowerTable& T,
+                              const uint64_t* d_unit_base, const uint64_t* d_unit_out, uint64_t text_lo, uint32_t* d_tab, unsigned n_cus,
+                              hipStream_t st);
+
+// the unit table as k_unit_count / k_unit_fill build it, on the host: unit_base [n_docs + 1] and the units.  GFT_E_INVALID for
+// descending offsets or a document of 4 GiB or more
+int lower_units_host(const uint64_t* doc_off, uint64_t n_docs, std::vector<uint64_t>& unit_base, std::vector<Unit>& units);
 
 }  // namespace gft
 

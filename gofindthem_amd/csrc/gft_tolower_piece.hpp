@@ -193,4 +193,40 @@ GFT_HD inline uint32_t tolower_piece(const LowerTable& T, const LowerWin& w, uin
     return total;
 }
 
+// The rune of the piece whose lower-case form holds byte t of the piece's output (t < tolower_piece<false>'s figure): returns
+// the index of its first byte among the piece's own bytes, src_len = the source bytes it takes -- 1 for an ASCII or an invalid
+// byte, 2..4 for a valid sequence, which may reach past the piece's end.  The walk of tolower_piece, without the stores: a
+// continuation byte that a lead in front of it covers has no output and is never the answer.  kLowerPiece when t is not below
+// the piece's output length.
+GFT_HD inline uint32_t tolower_piece_rune_at(const LowerTable& T, const LowerWin& w, uint32_t n, uint32_t t, uint32_t& src_len) {
+    src_len = 1;
+    if (tolower_piece_ascii(w, n)) return t < n ? t : kLowerPiece;
+    uint32_t total = 0, at = kLowerPiece;
+    uint32_t covered = 0;
+#pragma unroll
+    for (int j = -3; j < (int)kLowerPiece; j++) {
+        const uint32_t b = tolower_win_byte(w, j);
+        const bool own = j >= 0 && (uint32_t)j < n;
+        uint32_t bytes, len = 3, sl = 1;            // U+FFFD from one byte
+        if (b >= 0xC0u) {
+            uint32_t cp;
+            const uint32_t L = tolower_decode(b, tolower_win_byte(w, j + 1), tolower_win_byte(w, j + 2), tolower_win_byte(w, j + 3), cp);
+            if (L) {
+                covered |= ((1u << (L - 1)) - 1u) << (j + 4);
+                sl = L;
+                if (own) len = tolower_encode(tolower_rune(T, cp), bytes);
+            }
+        } else if (b >= 0x80u) {
+            if (covered >> (j + 3) & 1u) len = 0;
+        } else {
+            len = 1;
+        }
+        if (own) {
+            if (at == kLowerPiece && t - total < len) { at = (uint32_t)j; src_len = sl; }   // (t >= total while at is unset)
+            total += len;
+        }
+    }
+    return at;
+}
+
 }  // namespace gft

@@ -45,21 +45,28 @@ bool lower_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const 
            meet(doc_off, off_bytes, out_off, off_bytes) || meet(out, cap, out_off, off_bytes);
 }
 
-int lower_emulate(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* out, uint64_t cap, uint64_t* out_off,
-                  uint64_t* total) {
-    const LowerTable T = lower_table_host().view();
-    // the unit table (k_unit_count, the prefix sum, k_unit_fill)
-    std::vector<uint64_t> unit_base(n_docs + 1, 0);
+// the unit table (k_unit_count, the prefix sum, k_unit_fill)
+int lower_units_host(const uint64_t* doc_off, uint64_t n_docs, std::vector<uint64_t>& unit_base, std::vector<Unit>& units) {
+    unit_base.assign(n_docs + 1, 0);
     for (uint64_t d = 0; d < n_docs; d++) {
         if (doc_off[d + 1] < doc_off[d] || doc_off[d + 1] - doc_off[d] > 0xFFFFFFFFull) return GFT_E_INVALID;
         const uint64_t n = doc_off[d + 1] - doc_off[d];
         unit_base[d + 1] = unit_base[d] + (n <= kLowerUnitMax ? 1 : (n + kLowerUnitMax - 1) / kLowerUnitMax);
     }
-    std::vector<Unit> units(unit_base[n_docs]);
+    units.resize(unit_base[n_docs]);
     for (uint64_t d = 0; d < n_docs; d++) {
         const uint64_t n = doc_off[d + 1] - doc_off[d], k = unit_base[d + 1] - unit_base[d], per = (n + k - 1) / k;
         for (uint64_t i = 0; i < k; i++) units[unit_base[d] + i] = Unit{(uint32_t)d, (uint32_t)std::min(i * per, n), (uint32_t)std::min(i * per + per, n)};
     }
+    return GFT_OK;
+}
+
+int lower_emulate(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint8_t* out, uint64_t cap, uint64_t* out_off,
+                  uint64_t* total) {
+    const LowerTable T = lower_table_host().view();
+    std::vector<uint64_t> unit_base;
+    std::vector<Unit> units;
+    if (int rc = lower_units_host(doc_off, n_docs, unit_base, units)) return rc;
     // a unit's pieces in the kernel's order: trips of 64 pieces
     auto walk = [&](const Unit& un, auto&& piece) {
         const uint64_t doc_abs = doc_off[un.doc], doc_len = doc_off[un.doc + 1] - doc_abs;

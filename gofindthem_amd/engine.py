@@ -369,6 +369,43 @@ def redact_spans_host(blob, doc_off, span_off, start, length, mask=0x2A):
     return a
 
 
+def map_spans_to_source_tensor(call, text, doc_off, span_off, start, length):
+    """gft_map_spans_to_source_device through `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len)`, in place"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("map_spans_to_source_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel():
+        raise ValueError("map_spans_to_source_device: doc_off, span_off and the span arrays do not describe the same batch")
+    torch.cuda.current_stream(text.device).synchronize()
+    call(text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
+         length.data_ptr() if length.numel() else None)
+
+
+def map_spans_to_source_host(blob, doc_off, span_off, start, length):
+    """gft_debug_map_spans_to_source: the spans (span_off uint64 [n + 1]; start, length: contiguous numpy uint32 arrays) of the
+    lower-case form of the batch (blob, doc_off) become spans of the batch itself, IN PLACE; no device needed.  A refusal raises
+    GftError and leaves both arrays as they were"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
+    for t, what in ((start, "start"), (length, "length")):
+        if not isinstance(t, np.ndarray) or t.dtype != np.uint32 or not t.flags.c_contiguous or not t.flags.writeable:
+            raise ValueError("map_spans_to_source_host: %s must be a writable contiguous numpy uint32 array" % what)
+    rc = L.gft_debug_map_spans_to_source(_p(a) if a.size else None, _p(off), off.size - 1, _p(so), _p(start) if start.size else None,
+                                         _p(length) if length.size else None)
+    if rc != 0:
+        raise GftError(rc, "gft_debug_map_spans_to_source")
+
+
+def lowermap_shape():
+    """(bytes of a piece, of a wave's trip, of a work unit at most, spans of a wave's tile) (gft_debug_lowermap_shape)"""
+    v = [C.c_uint32(0) for _ in range(4)]
+    _lib.load().gft_debug_lowermap_shape(*(C.byref(x) for x in v))
+    return tuple(int(x.value) for x in v)
+
+
 def spans_shape():
     """(matches a workgroup of the mark pass takes per step, spans a wave of the fill owns) (gft_debug_spans_shape)"""
     t, k = C.c_uint32(0), C.c_uint32(0)
@@ -586,6 +623,14 @@ class Engine:
         """overwrites, in place, the bytes of every span with the mask byte (gft_redact_spans_device); every other byte of `text`
         keeps its value.  span_off, start, length: what hit_spans_device returned for (text, doc_off)"""
         redact_spans_tensor(lambda *a: self._check(self._L.gft_redact_spans_device(self._h, *a)), text, doc_off, span_off, start, length, mask)
+
+    def map_spans_to_source_device(self, text, doc_off, span_off, start, length):
+        """rewrites, in place, spans of the LOWER-CASE form of a resident batch -- what hit_spans_device gave for the output of
+        to_lower_device over (text, doc_off) -- to spans of the batch itself (gft_map_spans_to_source_device).  text, doc_off: the
+        SOURCE batch; the lowered text is not needed.  A span that begins or ends inside a rune's lower-case form covers the whole
+        source rune"""
+        map_spans_to_source_tensor(lambda *a: self._check(self._L.gft_map_spans_to_source_device(self._h, *a)), text, doc_off, span_off, start,
+                                   length)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

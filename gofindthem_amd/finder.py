@@ -425,25 +425,28 @@ class Finder:
         return out[:total].tobytes(), out_off[:m + 1].copy(), doc_idx[:m].copy()
 
     # -- where the expressions matched (csrc/gft_spans.hip) ----------------------------------------------------------------------
-    def SpansDevice(self, text, doc_off, bitmap, want=None, row_idx=None):
+    def SpansDevice(self, text, doc_off, bitmap, want=None, row_idx=None, source=False):
         """Engine.hit_spans_device on the finder's engine under the finder's case rule (gft_finder_hit_spans_device), over the rows
         ProcessDevice left: (span_off int64 [n + 1], start, len, term int32 [total], lowered).  lowered True: the batch left ASCII
         and was lowered on the device before it was scanned -- the spans index the LOWERED text (Engine.to_lower_device over the
-        batch gives its bytes and offsets), not the caller's.  Needs what ProcessDevice needs"""
+        batch gives its bytes and offsets), not the caller's.  source=True (gft_finder_hit_spans_source_device): the spans of such
+        a batch are mapped back on the device and always index `text`; lowered still says what happened.  Needs what ProcessDevice
+        needs"""
         from .engine import hit_spans_tensor
         lowered = C.c_int(0)
+        fn = self._L.gft_finder_hit_spans_source_device if source else self._L.gft_finder_hit_spans_device
 
         def call(*a):
-            self._check(self._L.gft_finder_hit_spans_device(self._h, *a, C.byref(lowered)))
+            self._check(fn(self._h, *a, C.byref(lowered)))
         out = hit_spans_tensor(call, text, doc_off, bitmap, self.n_expressions, want, row_idx)
         return out + (bool(lowered.value),)
 
-    def _spans_of_lines(self, buf, length, want):
+    def _spans_of_lines(self, buf, length, want, source=False):
         """split, process and spans of a resident blob of lines: (doc_off, bitmap, spans..., lowered)"""
         if not self._takes_device_route():
             raise FinderError(_lib.GFT_E_UNSUPPORTED, "hit spans need the device route: the GPU substring engine, no regex terms, one device")
         off, bm = self.ProcessLinesDevice(buf, length)
-        return (off, bm) + self.SpansDevice(buf, off, bm, want)
+        return (off, bm) + self.SpansDevice(buf, off, bm, want, source=source)
 
     def _lowered_clone(self, buf, off, lowered):
         """the text the spans index, as a buffer of its own: a copy of the batch, or its lower-case form (gft_to_lower_device)"""
@@ -466,15 +469,17 @@ class Finder:
         if rc != 0:
             raise FinderError(rc, self._L.gft_last_error(self.engine_handle()).decode())
 
-    def SpansLines(self, data, want=None):
+    def SpansLines(self, data, want=None, source=False):
         """bytes -> (idx, spans, lowered): idx the numbers of the lines that hit `want` (want_mask(); None: any expression), spans[k]
         the list of (start, end, keyword) of line idx[k] -- every occurrence of a keyword that is a witness of a true, wanted
         expression, in the scan's order, start / end relative to the line; a line that hit through negated keywords alone has an
         empty list.  One upload; only the rows and the spans come down.  lowered True: the batch left ASCII and the positions index
-        the lines' lower-case form (strings.ToLower), whose lengths may differ.  Device route only"""
+        the lines' lower-case form (strings.ToLower), whose lengths may differ -- unless source=True: the positions then always
+        index the caller's lines (a span covers whole source runes; the keyword in the tuple stays the dictionary's lowered one).
+        Device route only"""
         data = bytes(data)
         buf = self._resident(data)
-        off, bm, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want)
+        off, bm, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want, source)
         rows = bm.cpu().numpy().view(np.uint32).reshape(int(off.numel()) - 1, -1)
         w = self.want_mask() if want is None else np.ascontiguousarray(want, dtype=np.uint32)
         w = self.want_mask() & w
@@ -488,16 +493,17 @@ class Finder:
         spans = [[(int(st[k]), int(st[k]) + int(ln[k]), terms[int(tm[k])]) for k in range(int(so[d]), int(so[d + 1]))] for d in hit.tolist()]
         return hit.astype(np.uint64), spans, lowered
 
-    def RedactLines(self, data, want=None, mask=b"*"):
+    def RedactLines(self, data, want=None, mask=b"*", source=False):
         """bytes -> (bytes, lowered): the blob with every keyword occurrence that is a witness of a true, wanted expression
         overwritten by `mask`, byte for byte.  One upload, then split, process, spans and the redaction of a clone on the device,
         one download.  lowered True: the batch left ASCII -- the bytes are the lines' lower-case form (strings.ToLower) with the
-        masks in it.  Device route only"""
+        masks in it.  source=True: a clone of the CALLER's blob is redacted with the spans mapped back to it -- the result has
+        len(data) bytes and differs from data only inside the source spans, whatever lowered says.  Device route only"""
         from .engine import redact_spans_tensor
         data = bytes(data)
         buf = self._resident(data)
-        off, _, span_off, start, length, _, lowered = self._spans_of_lines(buf, len(data), want)
-        text, text_off = self._lowered_clone(buf, off, lowered)
+        off, _, span_off, start, length, _, lowered = self._spans_of_lines(buf, len(data), want, source)
+        text, text_off = self._lowered_clone(buf, off, lowered and not source)
         redact_spans_tensor(lambda *a: self._check_engine(self._L.gft_redact_spans_device(self.engine_handle(), *a)), text, text_off, span_off,
                             start, length, mask)
         n = int(text_off[-1].item()) if text_off.numel() else 0

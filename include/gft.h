@@ -496,6 +496,41 @@ int gft_debug_redact_spans(uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
 /* where those walks' borders are: the matches a workgroup of the mark pass takes per step, the spans a wave of the fill owns */
 void gft_debug_spans_shape(uint32_t* tile_matches, uint32_t* tile_spans);
 
+/* ---- Spans of a lowered batch mapped back to the source text (csrc/gft_lowermap.hip) ---------------------------------------------
+ * strings.ToLower changes lengths (U+0130 and U+212A shrink, U+023A grows, an invalid byte becomes the three bytes of U+FFFD), so
+ * the spans gft_hit_spans_device gives for the LOWERED form of a batch (gft_to_lower_device) do not index the text the caller
+ * holds.  This call rewrites them, in place, to positions in the SOURCE batch; it needs neither the lowered text nor its offsets:
+ * the map is a function of the source alone.
+ * Go's decoder cuts a document S into runes: a valid sequence of 1..4 bytes, or ONE byte that decodes to U+FFFD.  Rune i takes the
+ * source bytes [a_i, a_i + sl_i) and the lowered bytes [b_i, b_i + ll_i), ll_i >= 1; B = the lowered length.  A lowered span
+ * (start, len) with len >= 1 maps to [a_p, a_q + sl_q): p the rune whose lowered bytes hold byte start, q the one that holds byte
+ * start + len - 1 -- a span that cuts a lowered rune covers the whole source rune.  len == 0 maps to (a_p, 0), and at start == B to
+ * (the length of S, 0).  So: source spans begin and end on the source's rune cuts -- masking them with an ASCII byte keeps valid
+ * UTF-8 valid; a text masked through them has the caller's length and the caller's offsets; and on a fold-safe document the map
+ * is the identity.
+ * d_text_blob / d_doc_off: the source batch under the scans' placement contract (no alignment, d_doc_off[0] may be non-zero, 64
+ * readable bytes of slack; neither the slack nor the lead bytes ever change the answer; documents are judged one by one, as
+ * gft_to_lower_device judges them).  d_span_off [n_docs + 1] / d_span_start / d_span_len: what gft_hit_spans_device wrote for the
+ * lowered form of this batch -- the spans [d_span_off[0], d_span_off[n_docs]).  A span with start + len > B is found on the device,
+ * before anything is written, and refused with GFT_E_INVALID: nothing at all is written then.
+ * Two parts on the engine's stream (gft_profile_read): "lowermap_table" -- gft_to_lower_device's count pass and prefix sum, then
+ * its walk once more, storing where every 16-byte piece's output begins in its document's lowered form: 4 bytes per 16 source
+ * bytes -- and "lowermap_spans" -- a lane a span: a check pass (the span's document, two binary searches, the rune inside the piece
+ * found) and a write pass.  The call waits for the stream.  Needs no dictionary, leaves gft_last_nonascii alone.  Handles over
+ * several devices: GFT_E_UNSUPPORTED.  Between gft_process_device_begin and _end only after _complete.  n_docs == 0 and no spans
+ * are valid.  GFT_E_INVALID: a span array that overlaps the text, the offsets or the other span array; offsets that descend; a
+ * document, or the lower-case form of one, of 4 GiB or more.  GFT_E_NOMEM: no room for the work buffers (4 bytes per 16 of text,
+ * 8 bytes a span).  The handle stays usable after any error. */
+int gft_map_spans_to_source_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                   const uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len);
+/* The host form, no HIP device needed, same contract, all pointers host (the 64 bytes of slack are not asked for here): the table
+ * unit by unit and piece by piece, the map span by span, through the source the kernels are compiled from
+ * (csrc/gft_tolower_piece.hpp, csrc/gft_lowermap_piece.hpp). */
+int gft_debug_map_spans_to_source(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                                  uint32_t* span_start, uint32_t* span_len);
+/* where that walk's borders are: the bytes of a piece, of a wave's trip and of a work unit at most; the spans of a wave's tile */
+void gft_debug_lowermap_shape(uint32_t* piece_bytes, uint32_t* trip_bytes, uint32_t* unit_bytes, uint32_t* tile_spans);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -586,10 +621,18 @@ int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, cons
  * LIMITATION: the spans then index the LOWERED text -- the bytes gft_to_lower_device gives for the batch, with its offsets --, not
  * the caller's text: lower-casing can change lengths, and no mapping back is built.  It asks of the finder what
  * gft_finder_process_device asks and refuses in its words; such a batch on a finder without the device ToLower
- * (GFT_DEVICE_TOLOWER=0): GFT_E_UNSUPPORTED. */
+ * (GFT_DEVICE_TOLOWER=0): GFT_E_UNSUPPORTED.  gft_finder_hit_spans_source_device below has no such limitation. */
 int gft_finder_hit_spans_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,
                                 const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len,
                                 uint32_t* d_span_term, uint64_t cap, uint64_t* total, int* lowered);
+/* The same call, but the spans ALWAYS index the caller's text: when the batch was lowered, gft_map_spans_to_source_device runs over
+ * the spans the call kept before it returns; *lowered still reports what happened.  Under the cap protocol only the entries that
+ * were written (those below cap) are mapped and nothing is stored at or past cap.  The map reads the offsets and the lengths:
+ * cap != 0 without d_span_off or without d_span_len is GFT_E_INVALID, whatever the batch holds (cap == 0 counts only, as above). */
+int gft_finder_hit_spans_source_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                       const uint32_t* d_hit_bitmap, const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off,
+                                       uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap, uint64_t* total,
+                                       int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
