@@ -176,6 +176,7 @@ SYMBOLS = {
     "gft_debug_tables": (_i, [_vp, _vp, _u32, _vp, _u64, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp, _u64, C.POINTER(_u64), _vp, _u64]),
     "gft_debug_learned_unit": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_debug_last_unit_route": (_i, [_vp, C.POINTER(C.c_char_p)]),
+    "gft_debug_last_fold_bits": (_i, [_vp, C.POINTER(_u32)]),
     "gft_debug_scan_plan": (_i, [_vp, _vp, _u32, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp]),
     "gft_debug_pool_entries": (_i, [_vp, C.POINTER(_u64)]),
     "gft_debug_judge_batch": (_i, [_vp, _i, _u32, _u64, _u64, _u64, _u64, C.POINTER(_i), C.POINTER(_u64), _vp, _vp, _u64]),

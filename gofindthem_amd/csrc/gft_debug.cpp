@@ -1,5 +1,5 @@
 // gft_debug.cpp -- the gft_debug_* hooks of include/gft.h: host restatements and pure planners that the tests and tools
-// call without a device (gft_debug_learned_unit and gft_debug_last_unit_route alone read a handle).
+// call without a device (gft_debug_learned_unit, gft_debug_last_unit_route and gft_debug_last_fold_bits alone read a handle).
 #include "gft_engine.hpp"
 
 #include <unordered_set>
@@ -206,6 +206,12 @@ int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fi
 int gft_debug_last_unit_route(const gft_engine* e, const char** name) {
     if (!e || !name) return GFT_E_INVALID;
     *name = e->last_unit_route;
+    return GFT_OK;
+}
+
+int gft_debug_last_fold_bits(const gft_engine* e, uint32_t* bits) {
+    if (!e || !bits) return GFT_E_INVALID;
+    *bits = e->reported.nonascii_bits;
     return GFT_OK;
 }
 

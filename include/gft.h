@@ -1043,6 +1043,12 @@ int gft_debug_learned_unit(const gft_engine* e, uint32_t* unit_max, uint32_t* fi
  * batch before left it, the count read afterwards) or "single" (one launch on the assumption of one unit per document, after
  * two such batches); "" before the first batch.  A batch that was deferred and then run again reports the second run. */
 int gft_debug_last_unit_route(const gft_engine* e, const char** name);
+/* Who answered gft_last_nonascii for the batch whose entry point returned last (read-only): *bits = the word the scan kernels
+ * left in the control block.  0: no byte >= 0x80 in a folded scan (or no folded scan); 2: the scan kernel judged the pieces with
+ * high bytes itself and found the text unsafe (gft_scan3, gft_scan5); bit 0 set: high bytes were seen and not judged -- the DFA
+ * kernel always, the other two when a unit listed more pieces than its candidate list holds -- and the second pass over the
+ * text (k_fold_safe, k_fold_doc_edges) gave the verdict.  The tests use it to tell which of the judges they are testing. */
+int gft_debug_last_fold_bits(const gft_engine* e, uint32_t* bits);
 /* ... and the numbers of the plan that plan_scan makes for `terms`, compiled the same way: *kernel as above,
  * plan[0..3] = the longest keyword's bytes, then the shape of scan5's fifo entries (s5_term_bits, s5_pos_bias: term id and
  * relative position in 32 bits; both 0 under another kernel) and the entries of a wave's LDS match fifo, which the unit size
