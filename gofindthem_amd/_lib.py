@@ -179,11 +179,13 @@ SYMBOLS = {
     "gft_debug_last_fold_bits": (_i, [_vp, C.POINTER(_u32)]),
     "gft_debug_scan_plan": (_i, [_vp, _vp, _u32, _u64, C.c_char_p, C.POINTER(C.c_char_p), _vp]),
     "gft_debug_pool_entries": (_i, [_vp, C.POINTER(_u64)]),
+    "gft_debug_last_solve_pf": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_debug_judge_batch": (_i, [_vp, _i, _u32, _u64, _u64, _u64, _u64, C.POINTER(_i), C.POINTER(_u64), _vp, _vp, _u64]),
     "gft_debug_learn": (_i, [C.c_char_p, _u32, _i, _u64, _u64, _u64, C.POINTER(_u32), C.POINTER(C.c_double)]),
     "gft_debug_eval_programs": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "gft_debug_program_shape": (_i, [_vp, _vp, _u32, _u32, _vp, _u32]),
     "gft_debug_plan_solve": (_i, [_u32, _u32, _u32, _i, _u32, _u64, _u32, _u64, _i, _i, _u32, _vp]),
+    "gft_debug_plan_solve_pf": (_i, [_u32, _u32, _u32, _i, _u32, _u32, _u64, _u32, _u64, _i, _i, _u32, _u32, _vp]),
     "gft_debug_host_solve": (_i, [_vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_i)]),
     "gft_profile_enable": (_i, [_vp, _i]),
     "gft_profile_read": (_i, [_vp, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_u64)]),

@@ -79,6 +79,8 @@ struct Learned {
     int single_streak = 0;
     uint32_t unit_max = kScan2UnitMax;     // bytes per work unit of the kernels on scan2's tables: follows the match density
     double scan4_density = 0.06;           // matches per text byte: scan4 sizes a unit's region of the match pool from it
+    uint32_t unit_entries = 0;             // mean pool entries per unit of the last completed batch, rounded up (0: none yet, or
+                                           // none matched): the solver's prefetch depth follows it (solve_plan.hpp)
 };
 constexpr int kSingleMissStreak = -8;
 inline void count_streak(Learned& s, uint64_t n_units, uint64_t n_docs) {

@@ -25,6 +25,8 @@ void refresh_options(gft_engine* e) {
     e->opt_solve.dbg = (uint32_t)num("GFT_SOLVE_DEBUG", 0);
     e->opt_solve.forced_group = (int)num("GFT_SOLVE_GROUP_DOCS", -1);
     e->opt_solve.prog_lds = num("GFT_SOLVE_PROG_LDS", 1) ? 1u : 0u;
+    const long pf = num("GFT_SOLVE_PF_TERMS", 0);
+    e->opt_solve.forced_pf = pf == 6 || pf == 12 ? (uint32_t)pf : 0u;
 }
 
 }  // namespace
@@ -264,6 +266,7 @@ int install_tables(gft_engine* e, TableSet&& set, uint32_t flags) {
     e->pool.valid_docs = ~0ull;
     e->learned.unit_max = kScan2UnitMax;
     e->learned.scan4_density = 0.06;
+    e->learned.unit_entries = 0;
     e->built = true;
     return GFT_OK;
 }

@@ -1,5 +1,6 @@
 // gft_debug.cpp -- the gft_debug_* hooks of include/gft.h: host restatements and pure planners that the tests and tools
-// call without a device (gft_debug_learned_unit, gft_debug_last_unit_route and gft_debug_last_fold_bits alone read a handle).
+// call without a device (gft_debug_learned_unit, gft_debug_last_unit_route, gft_debug_last_fold_bits and
+// gft_debug_last_solve_pf alone read a handle).
 #include "gft_engine.hpp"
 
 #include <unordered_set>
@@ -236,6 +237,13 @@ int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uin
 int gft_debug_pool_entries(const gft_engine* e, uint64_t* entries) {
     if (!e || !entries) return GFT_E_INVALID;
     *entries = e->pool.total;
+    return GFT_OK;
+}
+
+int gft_debug_last_solve_pf(const gft_engine* e, uint32_t* pf_terms, uint32_t* unit_entries) {
+    if (!e || !pf_terms) return GFT_E_INVALID;
+    *pf_terms = e->last_pf_terms;
+    if (unit_entries) *unit_entries = e->learned.unit_entries;
     return GFT_OK;
 }
 

@@ -137,6 +137,8 @@ struct gft_engine {
     DevBuf d_wide_slot, d_wide_theta;      // pairs of wide INORD groups, a region per wave of the solver's grid
     DevBuf d_solve_dbg;                    // GFT_SOLVE_DEBUG & 8: phase clocks
     uint32_t ctl_epoch = 1;                // k_units_single batches are numbered from 2 (their control-block flags)
+    uint32_t solve_unit_entries = 0;       // learned.unit_entries as the last scan_pipeline found it: what that batch's solver plans with
+    uint32_t last_pf_terms = 0;            // the prefetch depth of the last solver launch (gft_debug_last_solve_pf)
     const char* last_unit_route = "";      // how scan_pipeline made the unit table of the last batch it launched (gft_debug_last_unit_route)
     // gft_process_device_begin / _end: up to two batches enqueued, their read-backs landing in pinned slots of their own
     struct Pending {

@@ -259,6 +259,7 @@ static int enqueue_scan(gft_engine* e, const ScanBatch& b, ScanLaunch& L) {
 static void learn_from_batch(gft_engine* e, const ScanLaunch& L, const BatchVerdict& v) {
     const ScanKernel k = e->plan.kernel;
     learn(e->learned, k, k == ScanKernel::scan5 ? e->plan.s5plan.fifo_cap : kScan2FifoCap, L.ordered, v.total, v.text_lo, v.text_hi);
+    e->learned.unit_entries = v.n_units ? (uint32_t)std::min<uint64_t>((v.total + v.n_units - 1) / v.n_units, 0xFFFFFFFFu) : 0u;
 }
 
 // How a batch gets its unit table
@@ -398,6 +399,7 @@ int scan_pipeline(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_of
     ScanLaunch L;
     if (defer) *defer = L;
     e->pool = PoolState();                // the pool is about to be overwritten
+    e->solve_unit_entries = e->learned.unit_entries;     // (what the batches BEFORE this one taught: its solver plans with that)
     HIP_TRY(e->d_match_off.ensure((n_docs + 1) * 8), "match_off alloc");
     if (n_docs == 0) {
         HIP_TRY(hipMemsetAsync(e->d_match_off.p, 0, 8, st), "memset");
@@ -598,8 +600,10 @@ int solve_pipeline(gft_engine* e, uint64_t n_docs, const gft_extra_matches* d_ex
     SolveShape shape;
     shape.n_slots = S.n_slots; shape.n_exprs = S.n_exprs; shape.fprog_words = S.fprog_words;
     shape.has_rare = S.has_rare; shape.wide_pairs = e->progs.wide_pairs;
+    shape.unit_entries = e->solve_unit_entries;        // (the batch before: a deferred scan's own count is read back behind its solver)
     const SolvePlan plan = plan_solve(shape, e->lds_max, e->n_cus, n_docs, e->opt_solve);
     S.tile_words = plan.tile_words;
+    e->last_pf_terms = plan.pf_terms;
     if (!plan.p_in_lds) {
         HIP_TRY(e->d_pscratch.ensure((size_t)plan.grid * S.n_slots * 8), "presence scratch alloc");
         S.p_scratch = e->d_pscratch.as<uint64_t>();

@@ -678,7 +678,8 @@ template <> struct AType<64> { using type = Mask64; };
 // G = documents per group = bits of a presence-matrix element: 64 when 8 bytes per slot fit LDS, else 32 / 16 / 8 so that
 // large dictionaries still keep P in LDS (the evaluation then covers fewer documents per operation, but P stops being an
 // L2 ping-pong of atomics and random reads)
-template <bool P_LDS, bool PROG_LDS, int G, int RARE, bool DBG = false>   // RARE: 0 no NOT / INORD word, 1 some, 2 some and a wide INORD group
+// PF: slab entries per lane that the build prefetches (solve_plan.hpp kPfShallowEntries): 6 or 12 where it pipelines (RARE 0)
+template <bool P_LDS, bool PROG_LDS, int G, int RARE, bool DBG, int PF>   // RARE: 0 no NOT / INORD word, 1 some, 2 some and a wide INORD group
 __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const SolveParams S) {
     const uint32_t dbg = DBG ? S.dbg : 0u;      // timing-study knock-outs (GFT_SOLVE_DEBUG): compiled out of production launches
     using PT = typename PType<G>::type;
@@ -719,7 +720,7 @@ __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const Solve
     // ahead of the next, behind the evaluation, so none of them ever waits for the one before it:
     //   group g + 3: its range of units                                  (`rng`)
     //   group g + 2: this thread's first unit: slab, count, document     (`nxt`)
-    //   group g + 1: the first kPfTerms slab entries of that unit        (`pf_t`; a unit of up to 192 matches)
+    //   group g + 1: the first kPfTerms slab entries of that unit        (`pf_t`; a unit of up to kPfTerms * 16 matches)
     // -- the build of the common case is LDS atomics on registers.  All of it stays in VECTOR registers and every load
     // is unconditional (indices clamped, validity checked where the value is used): a scalar value or a predicate derived
     // from a load would make the wave wait for it on the spot.
@@ -728,7 +729,8 @@ __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const Solve
     // entries are read where they are needed, two round trips in front of every build (keeping the unit in flight as
     // well already costs more in spills than it hides: 0.81 against 0.66 ms with 50 % INORD expressions)
     constexpr bool PIPE = !RARE;
-    constexpr int kPfTerms = 12;
+    constexpr int kPfTerms = PF;
+    static_assert(PF == 12 || (PF == 6 && PIPE), "two prefetch depths for the kernels that pipeline, 12 for the others");
     struct UnitPf { uint64_t u, U1, s; uint32_t n, doc; };      // u: this thread's first unit (valid if u < U1)
     struct Range { uint64_t U0, U1; };
     const uint32_t member = threadIdx.x % kTeam;
@@ -983,7 +985,7 @@ __global__ void __launch_bounds__(kSolveBlockThreads) k_solve_groups(const Solve
 hipError_t launch_solve(const SolveParams& S, const SolvePlan& plan, hipStream_t st) {
     if (!S.n_docs || !S.n_exprs) return hipSuccess;
     void (*run)(const SolveParams) = nullptr;
-#define X(P_LDS, PROG_LDS, G, RARE, DBG) if (solve_kernel_is(plan, P_LDS, PROG_LDS, G, RARE, DBG)) run = k_solve_groups<P_LDS, PROG_LDS, G, RARE, DBG>;
+#define X(P_LDS, PROG_LDS, G, RARE, DBG, PF) if (solve_kernel_is(plan, P_LDS, PROG_LDS, G, RARE, DBG, PF)) run = k_solve_groups<P_LDS, PROG_LDS, G, RARE, DBG, PF>;
     GFT_SOLVE_KERNELS(X)
 #undef X
     if (!run || !plan.grid) return hipErrorInvalidValue;

@@ -40,6 +40,9 @@ SolvePlan plan_solve(const SolveShape& s, size_t lds_max, unsigned n_cus, uint64
     // timing studies: the benchmark's shape (presence matrix and programs in LDS, 64 documents per group) and the shape of
     // a 100 000-term dictionary (8 documents per group, programs in L2) only; any other shape runs its production kernel
     p.dbg_variant = opt.dbg && !wide && p.p_in_lds && ((p.group_docs == 64 && p.prog_in_lds) || (p.group_docs == 8 && !p.prog_in_lds));
+    // the build's prefetch depth (kPfShallowEntries): only the kernels without a NOT / INORD word pipeline and have two
+    const bool shallow = opt.forced_pf ? opt.forced_pf == 6 : s.unit_entries > 0 && s.unit_entries <= kPfShallowEntries;
+    p.pf_terms = p.rare == 0 && shallow ? 6u : 12u;
     p.lds_bytes = solve_lds_bytes(s.n_slots, p.tile_words, p.group_docs, p.p_in_lds, s.fprog_words, s.n_exprs, p.prog_in_lds);
     const uint64_t n_groups = (n_docs + p.group_docs - 1) / p.group_docs;
     p.per_cu = (unsigned)std::max<size_t>(1, std::min<size_t>(8, lds_max / (p.lds_bytes + kSlackPerCu)));
@@ -48,7 +51,7 @@ SolvePlan plan_solve(const SolveShape& s, size_t lds_max, unsigned n_cus, uint64
 }
 
 bool solve_kernel_exists(const SolvePlan& p) {
-#define X(P_LDS, PROG_LDS, G, RARE, DBG) if (solve_kernel_is(p, P_LDS, PROG_LDS, G, RARE, DBG)) return true;
+#define X(P_LDS, PROG_LDS, G, RARE, DBG, PF) if (solve_kernel_is(p, P_LDS, PROG_LDS, G, RARE, DBG, PF)) return true;
     GFT_SOLVE_KERNELS(X)
 #undef X
     return false;
@@ -56,18 +59,31 @@ bool solve_kernel_exists(const SolvePlan& p) {
 
 }  // namespace gft
 
-// ---- test hook (include/gft.h): the functions above and nothing else ---------------------------------------------------------
+// ---- test hooks (include/gft.h): the functions above and nothing else --------------------------------------------------------
+// plan[0 .. 10] as gft_debug_plan_solve documents them, plan[11] = pf_terms
+extern "C" int gft_debug_plan_solve_pf(uint32_t n_slots, uint32_t n_exprs, uint32_t fprog_words, int has_rare, uint32_t wide_pairs,
+                                       uint32_t unit_entries, uint64_t lds_max, uint32_t n_cus, uint64_t n_docs, int forced_group,
+                                       int prog_lds, uint32_t dbg, uint32_t forced_pf, uint64_t* plan) try {
+    if (!plan || (forced_pf != 0 && forced_pf != 6 && forced_pf != 12)) return GFT_E_INVALID;
+    gft::SolveShape s;
+    s.n_slots = n_slots; s.n_exprs = n_exprs; s.fprog_words = fprog_words; s.has_rare = has_rare != 0; s.wide_pairs = wide_pairs;
+    s.unit_entries = unit_entries;
+    gft::SolveOptions o;
+    o.forced_group = forced_group; o.prog_lds = prog_lds != 0; o.dbg = dbg; o.forced_pf = forced_pf;
+    const gft::SolvePlan p = gft::plan_solve(s, (size_t)lds_max, n_cus, n_docs, o);
+    const uint64_t out[12] = {p.group_docs, p.p_in_lds, p.prog_in_lds, p.rare, p.dbg_variant, p.tile_words, p.wide_cap, p.lds_bytes,
+                              p.per_cu, p.grid, gft::solve_kernel_exists(p), p.pf_terms};
+    std::copy(out, out + 12, plan);
+    return GFT_OK;
+} GFT_CATCH(nullptr)
+
 extern "C" int gft_debug_plan_solve(uint32_t n_slots, uint32_t n_exprs, uint32_t fprog_words, int has_rare, uint32_t wide_pairs,
                                     uint64_t lds_max, uint32_t n_cus, uint64_t n_docs, int forced_group, int prog_lds, uint32_t dbg,
                                     uint64_t* plan) try {
     if (!plan) return GFT_E_INVALID;
-    gft::SolveShape s;
-    s.n_slots = n_slots; s.n_exprs = n_exprs; s.fprog_words = fprog_words; s.has_rare = has_rare != 0; s.wide_pairs = wide_pairs;
-    gft::SolveOptions o;
-    o.forced_group = forced_group; o.prog_lds = prog_lds != 0; o.dbg = dbg;
-    const gft::SolvePlan p = gft::plan_solve(s, (size_t)lds_max, n_cus, n_docs, o);
-    const uint64_t out[11] = {p.group_docs, p.p_in_lds, p.prog_in_lds, p.rare, p.dbg_variant, p.tile_words, p.wide_cap, p.lds_bytes,
-                              p.per_cu, p.grid, gft::solve_kernel_exists(p)};
-    std::copy(out, out + 11, plan);
-    return GFT_OK;
+    uint64_t out[12];
+    const int rc = gft_debug_plan_solve_pf(n_slots, n_exprs, fprog_words, has_rare, wide_pairs, 0, lds_max, n_cus, n_docs, forced_group,
+                                           prog_lds, dbg, 0, out);
+    if (rc == GFT_OK) std::copy(out, out + 11, plan);
+    return rc;
 } GFT_CATCH(nullptr)

@@ -1063,6 +1063,10 @@ int gft_debug_scan_plan(const uint8_t* terms_blob, const uint64_t* term_off, uin
  * at end offsets >= 3 of the document; occurrences that end at offsets 0..2 and terms of four bytes or more are written
  * every time. */
 int gft_debug_pool_entries(const gft_engine* e, uint64_t* entries);
+/* The solver launch of the last batch (read-only): *pf_terms = the prefetch depth its plan chose (6 or 12; 0 before the first
+ * solver launch), *unit_entries (nullable) = what the handle has learnt for the NEXT plan: the mean pool entries per work unit
+ * of the last completed batch, rounded up (0: none yet, or nothing matched). */
+int gft_debug_last_solve_pf(const gft_engine* e, uint32_t* pf_terms, uint32_t* unit_entries);
 
 /* The judgement on a batch alone, on the host (csrc/batch_verdict.cpp): decodes the seven 64-bit words of a control-block
  * read-back and judges them against what a deferred scan launch knew -- single / epoch (its unit table came from the
@@ -1106,6 +1110,13 @@ int gft_debug_program_shape(const uint32_t* prog_words, const uint64_t* prog_off
 int gft_debug_plan_solve(uint32_t n_slots, uint32_t n_exprs, uint32_t fprog_words, int has_rare, uint32_t wide_pairs,
                          uint64_t lds_max, uint32_t n_cus, uint64_t n_docs, int forced_group, int prog_lds, uint32_t dbg,
                          uint64_t* plan);
+
+/* The same with what decides the prefetch depth of the presence-matrix build: unit_entries, the mean pool entries per unit of the
+ * last completed batch (0: unknown), and forced_pf, what GFT_SOLVE_PF_TERMS would say (0: unset, 6 or 12; anything else is
+ * GFT_E_INVALID).  plan[12] = the eleven words of gft_debug_plan_solve, then pf_terms (6 or 12). */
+int gft_debug_plan_solve_pf(uint32_t n_slots, uint32_t n_exprs, uint32_t fprog_words, int has_rare, uint32_t wide_pairs,
+                            uint32_t unit_entries, uint64_t lds_max, uint32_t n_cus, uint64_t n_docs, int forced_group, int prog_lds,
+                            uint32_t dbg, uint32_t forced_pf, uint64_t* plan);
 
 /* The host solver alone (csrc/host_solve.cpp: dsl/expression.go:66-142 restated over the postfix words, lists materialised):
  * Solve of ONE program over ONE document's map, given as n_lists keys -- slots[k] with the positions
