@@ -120,6 +120,7 @@ void gft_engine_destroy(gft_engine* e) {
         if (e->pend[k].rb) (void)hipHostFree(e->pend[k].rb);
         if (e->pend[k].ev) (void)hipEventDestroy(e->pend[k].ev);
     }
+    if (e->d_excerpt.pin) (void)hipHostFree(e->d_excerpt.pin);
     destroy_multi(e);
     // the device buffers free themselves with the engine, on its device; its own stream outlives them
     hipStream_t own = e->own_stream ? e->stream : nullptr;

@@ -206,6 +206,14 @@ struct gft_engine {
     // passes want, the mapped spans between the check and the write pass, the flag word
     struct LowerMapBufs { DevBuf tab, off, mapped, ctl; } d_lmap;
 
+    // excerpts round the hit spans (gft_excerpt.hip): every span's window, document, suffix minimum, head mark and share of its
+    // excerpt's length, the tiles' minima and carries, the two prefix sums with scan partials and read-back words of their own,
+    // and the compact offsets the select's copy pass searches
+    struct ExcerptBufs {
+        DevBuf ws, we, sdoc, smin, head, share, tmin, carry, rank, pos, partial, ctl, c_off, c_src;
+        uint64_t* pin = nullptr;           // pinned landing place of the control block's read-backs (freed with the handle)
+    } d_excerpt;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

@@ -399,6 +399,92 @@ def map_spans_to_source_host(blob, doc_off, span_off, start, length):
         raise GftError(rc, "gft_debug_map_spans_to_source")
 
 
+EXCERPT_RUNES = 1                                   # GFT_EXCERPT_RUNES
+
+
+def excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes):
+    """what Engine.excerpt_spans_device and Finder.ExcerptsDevice share: `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start,
+    d_span_len, before, after, flags, d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel,
+    d_doc_exc_off, byref(n_exc), byref(total))` is gft_excerpt_spans_device on some handle and raises on an error.  Two calls: count
+    only, then into tensors of exactly the sizes counted.  Returns (out uint8 [total] -- a view with 64 zero bytes behind it --,
+    exc_off int64 [m + 1], exc_doc int64 [m], exc_start int32 [m], exc_span_off int64 [m + 1], span_rel int32 [spans], doc_exc_off
+    int64 [n + 1])"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("excerpt_spans_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel():
+        raise ValueError("excerpt_spans_device: doc_off, span_off and the span arrays do not describe the same batch")
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
+            length.data_ptr() if length.numel() else None, int(before), int(after), EXCERPT_RUNES if runes else 0)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+    dev = text.device
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, None, 0, None, None, None, None, 0, None, None, C.byref(m), C.byref(total))
+    nm, nb = int(m.value), int(total.value)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=dev)          # (64 bytes of slack: the result is a blob for the next call)
+    exc_off, exc_span_off = (torch.empty(nm + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    exc_doc = torch.empty(nm, dtype=torch.int64, device=dev)
+    exc_start = torch.empty(nm, dtype=torch.int32, device=dev)
+    span_rel = torch.zeros(start.numel(), dtype=torch.int32, device=dev)
+    doc_exc_off = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, buf.data_ptr(), nb, exc_off.data_ptr(), exc_doc.data_ptr() if nm else None, exc_start.data_ptr() if nm else None,
+         exc_span_off.data_ptr(), nm, span_rel.data_ptr() if span_rel.numel() else None, doc_exc_off.data_ptr(), C.byref(m), C.byref(total))
+    return buf[:nb], exc_off, exc_doc, exc_start, exc_span_off, span_rel, doc_exc_off
+
+
+def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=40, runes=True, cap_bytes=None, cap_exc=None, guard=0,
+                       flags=None, omit=(), count_only=False):
+    """gft_debug_excerpt_spans over host arrays -> a dict: n_exc, total, out uint8 [cap_bytes + guard], exc_off / exc_span_off uint64
+    [cap_exc + 1 + guard], exc_doc uint64 / exc_start uint32 [cap_exc + guard], span_rel uint32 [len(start) + guard], doc_exc_off
+    uint64 [n + 1 + guard]; no device needed.  Caps None: count first, then exactly what the result needs; the guard entries behind
+    the caps hold 0xA5.. and must come back untouched.  omit: names of outputs passed as NULL (they come back as None)"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
+    st, ln = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(length, dtype=np.uint32)
+    n_docs = off.size - 1
+    fl = (EXCERPT_RUNES if runes else 0) if flags is None else int(flags)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cb, eo, ed, es, eso, ce, rel, deo):
+        rc = L.gft_debug_excerpt_spans(_p(a) if a.size else None, _p(off), n_docs, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None,
+                                       int(before), int(after), fl, _p(out), cb, _p(eo), _p(ed), _p(es), _p(eso), ce, _p(rel), _p(deo),
+                                       C.byref(m), C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_excerpt_spans")
+    if cap_bytes is None or cap_exc is None or count_only:
+        call(None, 0, None, None, None, None, 0, None, None)
+        cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
+        cap_exc = int(m.value) if cap_exc is None else cap_exc
+    r = {"n_exc": int(m.value), "total": int(total.value)}
+    if count_only:
+        return r
+    big = 0xA5A5A5A5A5A5A5A5
+    arrs = {"out": np.full(cap_bytes + guard, 0xA5, dtype=np.uint8), "exc_off": np.full(cap_exc + 1 + guard, big, dtype=np.uint64),
+            "exc_doc": np.full(cap_exc + guard, big, dtype=np.uint64), "exc_start": np.full(cap_exc + guard, 0xA5A5A5A5, dtype=np.uint32),
+            "exc_span_off": np.full(cap_exc + 1 + guard, big, dtype=np.uint64), "span_rel": np.full(st.size + guard, 0xA5A5A5A5, dtype=np.uint32),
+            "doc_exc_off": np.full(n_docs + 1 + guard, big, dtype=np.uint64)}
+    for k in omit:
+        arrs[k] = None
+    for k in ("out", "exc_doc", "exc_start", "span_rel"):
+        if arrs[k] is not None and arrs[k].size == 0:
+            arrs[k] = None
+    call(arrs["out"], cap_bytes if arrs["out"] is not None else 0, arrs["exc_off"], arrs["exc_doc"], arrs["exc_start"], arrs["exc_span_off"], cap_exc,
+         arrs["span_rel"], arrs["doc_exc_off"])
+    r.update(arrs, n_exc=int(m.value), total=int(total.value))
+    return r
+
+
+def excerpt_shape():
+    """(spans of a tile of the excerpts' suffix-minimum scan, tiles of one carry trip) (gft_debug_excerpt_shape)"""
+    t, k = C.c_uint32(0), C.c_uint32(0)
+    _lib.load().gft_debug_excerpt_shape(C.byref(t), C.byref(k))
+    return int(t.value), int(k.value)
+
+
 def lowermap_shape():
     """(bytes of a piece, of a wave's trip, of a work unit at most, spans of a wave's tile) (gft_debug_lowermap_shape)"""
     v = [C.c_uint32(0) for _ in range(4)]
@@ -631,6 +717,26 @@ class Engine:
         source rune"""
         map_spans_to_source_tensor(lambda *a: self._check(self._L.gft_map_spans_to_source_device(self._h, *a)), text, doc_off, span_off, start,
                                    length)
+
+    def excerpt_spans_device(self, text, doc_off, span_off, start, length, before=40, after=40, runes=True):
+        """the text around the hit spans, cut and gathered on the device (gft_excerpt_spans_device).  text, doc_off: the batch the
+        spans index; span_off, start, length: what hit_spans_device returned for it (or map_spans_to_source_device rewrote).  The
+        window of a span reaches `before` bytes in front of it and `after` behind it, clipped to its document; runes: widened so that
+        it cuts no UTF-8 sequence; windows that overlap or touch are one excerpt.  Returns device tensors (out uint8 [total] -- the
+        excerpts back to back, a view with 64 zero bytes behind it --, exc_off int64 [m + 1], exc_doc int64 [m], exc_start int32 [m],
+        exc_span_off int64 [m + 1], span_rel int32 [spans], doc_exc_off int64 [n + 1]); (out, exc_off, exc_span_off, span_rel,
+        length) is what redact_spans_device takes.  The call runs twice: count only, then into tensors of exactly those sizes"""
+        return excerpt_spans_tensor(lambda *a: self._check(self._L.gft_excerpt_spans_device(self._h, *a)), text, doc_off, span_off, start,
+                                    length, before, after, runes)
+
+    @staticmethod
+    def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=40, runes=True):
+        """the host twin of excerpt_spans_device over numpy arrays (gft_debug_excerpt_spans): the same tuple, as numpy arrays"""
+        r = excerpt_spans_host(blob, doc_off, span_off, start, length, before, after, runes)
+        m, total = r["n_exc"], r["total"]
+        return (r["out"][:total] if r["out"] is not None else np.zeros(0, dtype=np.uint8), r["exc_off"][:m + 1],
+                r["exc_doc"][:m] if m else np.zeros(0, dtype=np.uint64), r["exc_start"][:m] if m else np.zeros(0, dtype=np.uint32),
+                r["exc_span_off"][:m + 1], r["span_rel"] if r["span_rel"] is not None else np.zeros(0, dtype=np.uint32), r["doc_exc_off"])
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

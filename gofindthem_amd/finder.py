@@ -509,6 +509,58 @@ class Finder:
         n = int(text_off[-1].item()) if text_off.numel() else 0
         return text[:n].cpu().numpy().tobytes(), lowered
 
+    # -- the text around the hits (csrc/gft_excerpt.hip) ---------------------------------------------------------------------------
+    def ExcerptsDevice(self, text, doc_off, span_off, start, length, lowered=False, source=False, before=40, after=40, runes=True):
+        """Engine.excerpt_spans_device on the finder's engine behind SpansDevice (gft_finder_excerpts_device): text, doc_off the
+        batch, span_off / start / length and `lowered` what SpansDevice returned for it, source as it was called.  With source, or
+        for a batch that was not lowered, the excerpts are cut from `text`; otherwise from the batch's lower-case form, which the
+        finder lowers on the device again.  Returns (out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, doc_exc_off, cut_lowered)
+        -- device tensors as Engine.excerpt_spans_device gives them, and whether the lowered text was cut.  Needs what ProcessDevice
+        needs"""
+        from .engine import excerpt_spans_tensor
+        cut = C.c_int(0)
+
+        def call(d_text, d_off, n, d_so, d_st, d_ln, *rest):
+            self._check(self._L.gft_finder_excerpts_device(self._h, d_text, d_off, n, d_so, d_st, d_ln, 1 if lowered else 0, 1 if source else 0,
+                                                           *rest, C.byref(cut)))
+        out = excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes)
+        return out + (bool(cut.value),)
+
+    def ExcerptLines(self, data, before=40, after=40, want=None, source=True, runes=True):
+        """bytes -> (idx, excerpts, lowered): idx the numbers of the lines that hit `want` (want_mask(); None: any expression),
+        excerpts[k] the list of (start_in_line, bytes, [(rel_start, rel_end, keyword), ...]) of line idx[k]: the text `before` bytes
+        in front of and `after` bytes behind every hit of SpansLines, windows that overlap or touch merged, cut on rune borders
+        (runes), with the hits' positions inside the excerpt.  A line that hit through negated keywords alone has no excerpt.  One
+        upload; the excerpt blob, its index arrays, the span arrays and the rows come down -- never the lines.  lowered True: the
+        batch left ASCII; with source=True (the default) the excerpts are still substrings of the caller's lines at start_in_line,
+        with source=False they are cut from the lines' lower-case form.  Device route only, as SpansLines: a finder with regex
+        terms, an injected engine or several devices has no host route to the spans (the cut itself has one:
+        Engine.excerpt_spans_host) and is refused with GFT_E_UNSUPPORTED before anything is uploaded"""
+        data = bytes(data)
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "ExcerptLines needs the device route, as the hit spans do: the GPU substring engine, no regex "
+                                                      "terms, one device")
+        buf = self._resident(data)
+        off, bm, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want, source)
+        out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, _, _ = self.ExcerptsDevice(buf, off, span_off, start, length, lowered, source,
+                                                                                             before, after, runes)
+        rows = bm.cpu().numpy().view(np.uint32).reshape(int(off.numel()) - 1, -1)
+        w = self.want_mask() if want is None else np.ascontiguousarray(want, dtype=np.uint32)
+        w = self.want_mask() & w
+        hit = np.nonzero((rows & w[None, :]).any(axis=1))[0] if rows.shape[1] else np.zeros(0, dtype=np.int64)
+        blob = out.cpu().numpy().tobytes()
+        eo, ed, es, eso, rel, ln, tm = (t.cpu().numpy() for t in (exc_off, exc_doc, exc_start, exc_span_off, span_rel, length, term))
+        terms = {}
+        tp, tl = C.c_void_p(), C.c_uint32()
+        for t in np.unique(tm).tolist():
+            self._check_engine(self._L.gft_term(self.engine_handle(), int(t), C.byref(tp), C.byref(tl)))
+            terms[t] = C.string_at(tp.value, tl.value)
+        per_line = {}
+        for k in range(ed.size):
+            hits = [(int(rel[j]), int(rel[j]) + int(ln[j]), terms[int(tm[j])]) for j in range(int(eso[k]), int(eso[k + 1]))]
+            per_line.setdefault(int(ed[k]), []).append((int(es[k]), blob[int(eo[k]):int(eo[k + 1])], hits))
+        return hit.astype(np.uint64), [per_line.get(d, []) for d in hit.tolist()], lowered
+
     # -- documents routed to one bucket per tag (csrc/gft_route.hip) -----------------------------------------------------------
     def route_masks(self, buckets=None):
         """the host masks of the route calls: a list of want_mask() rows, one per bucket.  None: one bucket per tag in tag-id order

@@ -531,6 +531,65 @@ int gft_debug_map_spans_to_source(const uint8_t* blob, const uint64_t* doc_off, 
 /* where that walk's borders are: the bytes of a piece, of a wave's trip and of a work unit at most; the spans of a wave's tile */
 void gft_debug_lowermap_shape(uint32_t* piece_bytes, uint32_t* trip_bytes, uint32_t* unit_bytes, uint32_t* tile_spans);
 
+/* ---- Excerpts on the device: the text around the hits, cut and gathered (csrc/gft_excerpt.hip) -------------------------------
+ * The last step of split -> process -> (select | route) -> spans -> (map) -> excerpt: for a resident batch and its hit spans, the
+ * windows of text around the spans, merged where they meet, back to back in one blob -- with the index arrays that tie every
+ * excerpt to its document and every span to its excerpt.  A view of the text the caller gave: no scan, no dictionary.
+ * Input: the batch under the scans' placement contract (no alignment, d_doc_off[0] may be non-zero, 64 readable bytes of slack
+ * behind d_doc_off[n_docs]; neither the lead bytes nor the slack ever change the answer) and the span CSR gft_hit_spans_device
+ * wrote for it, or gft_map_spans_to_source_device rewrote for its source: the spans [d_span_off[0], d_span_off[n_docs]) of
+ * d_span_start / d_span_len.
+ * Window: of span (start, len) in document d of L bytes, [max(0, start - before), min(L, start + len + after)), in 64 bits:
+ * before = after = 0xFFFFFFFF gives the whole document.  With GFT_EXCERPT_RUNES in flags a window is widened so that it cuts no
+ * UTF-8 sequence: its start moves back while the byte at the start is a continuation byte 10xxxxxx, its end forward while the
+ * byte at the end is one; each at most three steps, neither past the document's first byte or its end.  Only bytes of the
+ * document itself are consulted -- never the lead, the slack or a neighbouring document.
+ * Merge: the excerpts of a document are the connected components of the union of its windows; windows that overlap or touch
+ * (a.end == b.start) are one excerpt, a gap of one byte separates two.  Excerpts never cross a document border, even where two
+ * documents' windows touch in the blob.  A window of no bytes (a len == 0 span with before = after = 0, a span of an empty
+ * document) that touches no other is an excerpt of no bytes.
+ * Span order: within a document the spans' ends start + len must not descend -- the scan's canonical order (end ascending, length
+ * descending) guarantees it and the monotone source map keeps it.  A batch that breaks the order, or a span with start + len > L,
+ * is found on the device before anything is written: GFT_E_INVALID, and nothing at all is written.  Under this order the excerpts
+ * are runs of consecutive spans, which is why the outputs index the caller's own span arrays.
+ * Outputs, device memory, each nullable on its own: d_out, the excerpts back to back in span order (= document order); d_exc_off
+ * [n_exc + 1], usable as the doc_off of d_out; d_exc_doc, the document of each excerpt; d_exc_start, its first byte relative to
+ * its document; d_exc_span_off [n_exc + 1]: excerpt k holds the spans [d_exc_span_off[k], d_exc_span_off[k + 1]) of the caller's
+ * span arrays; d_span_rel, parallel to d_span_start (the entries [d_span_off[0], d_span_off[n_docs]) are written): each span's
+ * start relative to its excerpt; d_doc_exc_off [n_docs + 1], the documents' CSR over the excerpts.  (d_out, d_exc_off, n_exc,
+ * d_exc_span_off, d_span_rel, d_span_len) is a valid argument list of gft_redact_spans_device: masking inside the excerpts needs
+ * no further call.
+ * Cap protocol of gft_compact_device with two caps: cap_exc counts excerpt entries (d_exc_off and d_exc_span_off have cap_exc + 1,
+ * d_exc_doc and d_exc_start cap_exc), cap_bytes bytes of d_out; nothing is stored at or past any array + cap; an excerpt that
+ * cap_bytes cuts is written up to the cap, and d_exc_off keeps the uncut offsets.  d_span_rel and d_doc_exc_off are sized by the
+ * input, are never capped and are complete when given.  All outputs NULL with both caps 0 counts only; GFT_OK either way, and
+ * *n_exc / *total_bytes (host, nullable) are always handed back.
+ * Launches on the engine's stream (gft_profile_read): "excerpt_window" (a lane a span: its document by a binary search, the
+ * window, the snap, the checks), "excerpt_smin" (the suffix minimum of the window starts over the whole batch: tile minima, one
+ * workgroup's carry trips, the tiles' scans; heads marked), "excerpt_scan" (two prefix sums), "excerpt_place", "excerpt_copy" (the
+ * select's copy kernel: a lane a 16-byte chunk of the output).  The call waits for the stream.
+ * Needs no dictionary and no programs; leaves gft_last_nonascii alone.  Handles over several devices: GFT_E_UNSUPPORTED.  Between
+ * gft_process_device_begin and _end only after _complete.  n_docs == 0, no spans and len == 0 spans are valid.  GFT_E_INVALID:
+ * unknown flag bits; an output that overlaps an input or another output; document or span offsets that descend; a document of
+ * 4 GiB or more.  GFT_E_NOMEM: no room for the work buffers (56 bytes a span, 16 an excerpt).  The handle stays usable after any
+ * error. */
+#define GFT_EXCERPT_RUNES 1u
+int gft_excerpt_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                             const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len, uint32_t before,
+                             uint32_t after, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc,
+                             uint32_t* d_exc_start, uint64_t* d_exc_span_off, uint64_t cap_exc, uint32_t* d_span_rel,
+                             uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes);
+/* The host form, no HIP device needed, same contract, all pointers host (the 64 bytes of slack are not asked for here): the
+ * passes tile by tile, carry trip by carry trip and lane by lane through the source the kernels are compiled from
+ * (csrc/gft_excerpt_piece.hpp); the copy is a memcpy per excerpt. */
+int gft_debug_excerpt_spans(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                            const uint32_t* span_start, const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags,
+                            uint8_t* out, uint64_t cap_bytes, uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start,
+                            uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel, uint64_t* doc_exc_off, uint64_t* n_exc,
+                            uint64_t* total_bytes);
+/* where that walk's borders are: the spans of a tile of the suffix-minimum scan, the tiles of one carry trip */
+void gft_debug_excerpt_shape(uint32_t* tile_spans, uint32_t* trip_tiles);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -633,6 +692,17 @@ int gft_finder_hit_spans_source_device(gft_finder* f, const uint8_t* d_text_blob
                                        const uint32_t* d_hit_bitmap, const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off,
                                        uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap, uint64_t* total,
                                        int* lowered);
+/* gft_excerpt_spans_device on the finder's engine, behind one of the two calls above: spans_lowered is the *lowered that call
+ * reported, source non-zero when it was the source form.  With source, or for a batch that was not lowered, the excerpts are cut
+ * from the caller's batch (the mapped spans index it).  Otherwise the spans index the lowered text: the finder lowers the batch on
+ * the device again, as it did for the scan, cuts the excerpts from that text and sets *lowered = 1 (else 0) -- d_exc_start and
+ * d_span_rel are then positions of the lowered documents.  Everything else is gft_excerpt_spans_device's contract; the refusals of
+ * gft_finder_process_device in its words. */
+int gft_finder_excerpts_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                               const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered, int source, uint32_t before, uint32_t after,
+                               uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start,
+                               uint64_t* d_exc_span_off, uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc,
+                               uint64_t* total_bytes, int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
