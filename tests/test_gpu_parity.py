@@ -530,6 +530,7 @@ def test_unique_terms_mode_is_the_cloudflare_engine_output(eng):
     oo = torch.from_numpy(toff.astype(np.int64)).cuda()
     m = eng.scan_device(t.data_ptr(), oo.data_ptr(), 700, fold=True, unique=True)
     assert int(m.n_matches) == int(mo[-1])
+    # (the lists of the device-resident call are read back and compared in test_gpu_scan_modes.py)
 
 
 @needs_extra_kernels
@@ -604,6 +605,7 @@ def test_rune_offsets_are_the_anknown_engine_positions(eng):
     """GFT_POS_RUNES = AnknownEngine.FindSubstrings (finder/substringEngine.go:44-53): MultiPatternSearch([]rune(text)) reports
     Position over runes.  Expected: the oracle's byte offsets mapped through Go's string -> []rune decoding
     (oracle/runes_ref.py: multi-byte runes count once, every invalid byte is one U+FFFD)."""
+    import scan_modes
     from oracle.runes_ref import rune_index_table
     terms = ["lo", "w\u00f6rld", "\u20acuro", "x", "\U0001d11e", "\u00e9", "rld"]
     o = both(eng, sorted(t.encode("utf-8") for t in terms))
@@ -616,8 +618,10 @@ def test_rune_offsets_are_the_anknown_engine_positions(eng):
     off[1:] = np.cumsum([len(r) for r in raw])
     wo, wt, wp = o.scan(blob, off)
     want = wp.copy()
+    assert raw == scan_modes.parity_rune_texts()
     for d, r in enumerate(raw):
         tab = rune_index_table(r)
+        assert tab == scan_modes.rune_table(r).tolist()              # (the strict-decoder reference reads it the same)
         for m in range(int(wo[d]), int(wo[d + 1])):
             want[m] = tab[int(wp[m])]
     mo, ti, po = eng.scan(blob, off, runes=True)
@@ -634,6 +638,7 @@ def test_rune_offsets_are_the_anknown_engine_positions(eng):
     want = wp.copy()
     for d in range(40):
         tab = rune_index_table(bytes(text[int(toff[d]):int(toff[d + 1])]))
+        assert tab == scan_modes.rune_table(bytes(text[int(toff[d]):int(toff[d + 1])])).tolist()
         for m in range(int(wo[d]), int(wo[d + 1])):
             want[m] = tab[int(wp[m])]
     mo, ti, po = eng.scan(text, toff, runes=True)
