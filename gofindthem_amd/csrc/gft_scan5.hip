@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "gft_kernels.hpp"
 
@@ -51,15 +52,18 @@ struct Ctx5 {
 typedef __attribute__((address_space(3))) uint32_t lds_w32;
 __device__ __forceinline__ lds_w32* scan5_seen(const Ctx5& o) { return (lds_w32*)(o.fifo + o.fifo_cap + kScan5SurvX); }
 
-__device__ __forceinline__ void out_append(const Scan2Params& P, Ctx5& o, bool em, uint32_t term, uint32_t pos) {
+// POS: the launch wants positions (Scan2Params::want_pos, a constant of the launch: k_scan5's template parameter).  Without
+// them an entry is the term alone and `pos` is dead: no caller computes it
+template <bool POS>
+__device__ __forceinline__ void out_append(Ctx5& o, bool em, uint32_t term, uint32_t pos) {
     const uint64_t mask = __ballot(em);
     if (em) {
         const uint32_t idx = o.nf + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
         if (!o.direct) {
-            if (idx < o.fifo_cap - o.npend) o.fifo[idx] = P.want_pos ? term | (pos - o.pos_base) << o.term_bits : term;
+            if (idx < o.fifo_cap - o.npend) o.fifo[idx] = POS ? term | (pos - o.pos_base) << o.term_bits : term;
         } else {
             KARG(pool_term)[o.dbase + idx] = term;
-            if (P.want_pos) KARG(pool_pos)[o.dbase + idx] = pos;
+            if (POS) KARG(pool_pos)[o.dbase + idx] = pos;
         }
     }
     o.nf += (uint32_t)__popcll(mask);
@@ -76,6 +80,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // (a tenth of them: emitting in place cost three appends per 64 candidates, whoever had a hit), 64 parked jobs make one
 // trip.  The jobs wait at the end of the match fifo, which gives up that room (a unit whose matches then do not fit is
 // walked again with the appends going to the pool: the fifo is all theirs then).
+template <bool POS>
 __device__ __forceinline__ void short_trip(const Ctx& c, Ctx5& o, uint32_t ubase, uint32_t n) {       // the n (<= 64) most recently parked jobs
     const uint32_t lane = lane_id();
     const bool on = lane < n;
@@ -88,7 +93,7 @@ __device__ __forceinline__ void short_trip(const Ctx& c, Ctx5& o, uint32_t ubase
     // of every earlier one that hold the same record exactly one finds its bit clear.  A job at p < 3 may stand in front of
     // terms its record holds (L > p + 1): it emits as ever and leaves the bit alone, a later one then emits the whole record
     // (measured and set aside: the same OR in park_short, so that a record seen is not parked again -- DESIGN.md 4.1c)
-    if (!c.P.want_pos && sid && p >= 3) {
+    if (!POS && sid && p >= 3) {
         const uint32_t bit = 1u << (sid & 31);
         if (__hip_atomic_fetch_or(scan5_seen(o) + (sid >> 5), bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT) & bit) sid = 0;
     }
@@ -101,10 +106,11 @@ __device__ __forceinline__ void short_trip(const Ctx& c, Ctx5& o, uint32_t ubase
     for (uint32_t j = 0; j < 3; j++) {
         if (j && !__any(r[j] != 0)) break;
         const uint32_t L = r[j] >> 28;
-        out_append(c.P, o, r[j] != 0 && L <= p + 1, r[j] & 0x0FFFFFFFu, c.P.pos_end ? p : p + 1 - L);
+        out_append<POS>(o, r[j] != 0 && L <= p + 1, r[j] & 0x0FFFFFFFu, POS ? (c.P.pos_end ? p : p + 1 - L) : 0u);
     }
 }
 // sid != 0: this lane's candidate (list entry rel) ends short terms; wave-uniform call
+template <bool POS>
 __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase, uint32_t rel, uint32_t sid, uint32_t x3) {
     if (!__any(sid != 0)) return;
     if (__builtin_expect(__any(sid == 255) && KARG(short3_big) != nullptr, 0)) {
@@ -115,7 +121,7 @@ __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase
 #pragma unroll
         for (uint32_t j = 0; j < 3; j++) {
             const uint32_t L = r[j] >> 28;
-            out_append(c.P, o, r[j] != 0 && L <= p + 1, r[j] & 0x0FFFFFFFu, c.P.pos_end ? p : p + 1 - L);
+            out_append<POS>(o, r[j] != 0 && L <= p + 1, r[j] & 0x0FFFFFFFu, POS ? (c.P.pos_end ? p : p + 1 - L) : 0u);
         }
         return;
     }
@@ -123,7 +129,7 @@ __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase
     const uint32_t n = (uint32_t)__popcll(m);
     if (o.npend + n > o.fifo_cap / 2) {                            // (never in practice: keep half of the fifo for matches)
         wave_lds_sync();
-        while (o.npend) short_trip(c, o, ubase, o.npend < 64 ? o.npend : 64);
+        while (o.npend) short_trip<POS>(c, o, ubase, o.npend < 64 ? o.npend : 64);
         wave_lds_sync();
     }
     if (!o.direct && o.nf + o.npend + n > o.fifo_cap) o.lost = true;   // (the jobs go where matches are)
@@ -137,6 +143,7 @@ __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase
 // record id}; ids of 255 name cells whose records live in global memory (short3_big / srec_big).  These trips emit every
 // occurrence on presence-only launches too: a record id names a 3-window of GROUPS here and its terms are verified against the
 // text, so two positions with one id can differ in what they emit -- short_trip's once-per-record rule does not carry over --
+template <bool POS>
 __device__ __forceinline__ void short_trip_g(const Ctx& c, Ctx5& o, lds_u8* lsg, uint32_t ubase, uint32_t n) {
     const Scan2Params& P = c.P;
     const uint32_t lane = lane_id();
@@ -159,7 +166,7 @@ __device__ __forceinline__ void short_trip_g(const Ctx& c, Ctx5& o, lds_u8* lsg,
             if (j < cnt) { w0 = g[1 + 2 * j]; w1 = g[2 + 2 * j]; }
             const uint32_t L = w0 >> 28;
             const bool ok = w0 != 0 && L <= p + 1 && ((W ^ w1) >> ((32 - 8 * L) & 31)) == 0;
-            out_append(P, o, ok, w0 & 0x0FFFFFFFu, P.pos_end ? p : p + 1 - L);
+            out_append<POS>(o, ok, w0 & 0x0FFFFFFFu, POS ? (P.pos_end ? p : p + 1 - L) : 0u);
         }
         if (b) sid = 0;
     }
@@ -171,16 +178,17 @@ __device__ __forceinline__ void short_trip_g(const Ctx& c, Ctx5& o, lds_u8* lsg,
         if (j && !__any(w0 != 0)) break;
         const uint32_t L = w0 >> 28;
         const bool ok = w0 != 0 && L <= p + 1 && ((W ^ r[2 * j + 1]) >> ((32 - 8 * L) & 31)) == 0;
-        out_append(P, o, ok, w0 & 0x0FFFFFFFu, P.pos_end ? p : p + 1 - L);
+        out_append<POS>(o, ok, w0 & 0x0FFFFFFFu, POS ? (P.pos_end ? p : p + 1 - L) : 0u);
     }
 }
+template <bool POS>
 __device__ __forceinline__ void park_short_g(const Ctx& c, Ctx5& o, lds_u8* lsg, uint32_t ubase, uint32_t rel, uint32_t sid) {
     if (!__any(sid != 0)) return;
     const uint64_t m = __ballot(sid != 0);
     const uint32_t n = (uint32_t)__popcll(m);
     if (o.npend + n > o.fifo_cap / 2) {
         wave_lds_sync();
-        while (o.npend) short_trip_g(c, o, lsg, ubase, o.npend < 64 ? o.npend : 64);
+        while (o.npend) short_trip_g<POS>(c, o, lsg, ubase, o.npend < 64 ? o.npend : 64);
         wave_lds_sync();
     }
     if (!o.direct && o.nf + o.npend + n > o.fifo_cap) o.lost = true;   // (the jobs go where matches are)
@@ -189,6 +197,7 @@ __device__ __forceinline__ void park_short_g(const Ctx& c, Ctx5& o, lds_u8* lsg,
 }
 
 // gft_scan2_dev.hpp finish_long / drain_deferred with the text in LDS and the 4-byte fifo
+template <bool POS>
 __device__ __forceinline__ void finish_long5(const Ctx& c, Ctx5& o, bool on, uint32_t rel, const Cand& k, const Slot& s0, const Slot& s1,
                                              Front t, uint32_t tl, Deferred& d) {
     const Scan2Params& P = c.P;
@@ -202,7 +211,7 @@ __device__ __forceinline__ void finish_long5(const Ctx& c, Ctx5& o, bool on, uin
         const uint32_t kmax = wave_kmax(act ? e.a.z & kScan2LenMask : 0);
         if (P.fold) front_fold_upto(t, folded, kmax);
         const bool ok = act && entry_ok(c, k.p, t, tl, e, kmax);
-        out_append(P, o, ok, e.a.y, match_pos(P, k.p, e.a.z));
+        out_append<POS>(o, ok, e.a.y, POS ? match_pos(P, k.p, e.a.z) : 0u);
     }
     if (!__any(multi)) return;
     const uint32_t n_ent = multi ? e.a.z : 0, more_at = e.a.y & ~kScan2Multi;
@@ -218,29 +227,31 @@ __device__ __forceinline__ void finish_long5(const Ctx& c, Ctx5& o, bool on, uin
         return;
     }
     Slot cur = e;
-    if (multi) cur = slot_load(&P.more[more_at]);
+    if (multi) cur = slot_load(&KARG(more)[more_at]);
     for (uint32_t j = 0; __any(j < n_ent); j++) {
         const bool act = j < n_ent;
         Slot nxt = cur;
-        if (j + 1 < n_ent) nxt = slot_load(&P.more[more_at + j + 1]);
+        if (j + 1 < n_ent) nxt = slot_load(&KARG(more)[more_at + j + 1]);
         const uint32_t kmax = wave_kmax(act ? cur.a.z & kScan2LenMask : 0);
         if (P.fold) front_fold_upto(t, folded, kmax);
         const bool ok = act && entry_ok(c, k.p, t, tl, cur, kmax);
-        out_append(P, o, ok, cur.a.y, match_pos(P, k.p, cur.a.z));
+        out_append<POS>(o, ok, cur.a.y, POS ? match_pos(P, k.p, cur.a.z) : 0u);
         cur = nxt;
     }
 }
 
 
+template <bool POS>
 __device__ __forceinline__ void drain_deferred5(const Ctx& c, Ctx5& o, uint32_t ubase, Deferred& d) {
     const Scan2Params& P = c.P;
     const uint32_t lane = lane_id();
     wave_lds_sync();
+    const Scan2Slot* more = KARG(more);
     for (uint32_t i0 = 0; i0 < d.n; i0 += 64) {
         const bool on = i0 + lane < d.n;
         const uint2 it = d.list[on ? i0 + lane : 0];
         const uint32_t p = ubase + it.x;
-        const Slot e = slot_load(&P.more[it.y]);
+        const Slot e = slot_load(&more[it.y]);
         const Text8 t8 = cand_load(c, p);
         Front t = front_load(c, p, t8.tw);
         const uint32_t tl = tail_load(c, p);
@@ -248,15 +259,16 @@ __device__ __forceinline__ void drain_deferred5(const Ctx& c, Ctx5& o, uint32_t 
         uint32_t folded = 0;
         if (P.fold) front_fold_upto(t, folded, kmax);
         const bool ok = on && entry_ok(c, p, t, tl, e, kmax);
-        out_append(P, o, ok, e.a.y, match_pos(P, p, e.a.z));
+        out_append<POS>(o, ok, e.a.y, POS ? match_pos(P, p, e.a.z) : 0u);
     }
     d.n = 0;
     __builtin_amdgcn_wave_barrier();
 }
 
 // FPT_LDS: the fingerprint table is staged in LDS; DBG: the timing-study instantiation (GFT_SCAN_DEBUG); SG: the short terms
-// come from the group-indexed tables of the stride-2 kernel (an alphabet of more than 32 byte classes: short_trip_g)
-template <bool FPT_LDS, bool DBG, bool SG>
+// come from the group-indexed tables of the stride-2 kernel (an alphabet of more than 32 byte classes: short_trip_g); POS:
+// the launch wants positions (P.want_pos != 0) -- without them no position is computed, packed, carried or stored
+template <bool FPT_LDS, bool DBG, bool SG, bool POS>
 __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
     extern __shared__ __align__(16) uint8_t smem[];
     uint8_t* grp = smem;                                          // byte -> filter group
@@ -308,14 +320,16 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
     auto static_slabs = [&]() { return (uint64_t)gridDim.x * kScan5Waves * KARG(slab); };
     uint64_t slab_next = ((uint64_t)blockIdx.x * kScan5Waves + wave) * KARG(slab);   // wave-uniform
     uint32_t wave_matches = 0;                                    // (a wave's share of a launch stays far below 2^32)
-    bool told_nonascii = false;
+    // the fold-safety verdict is wanted (a folded launch that asks for it) and not given yet: the one flag the unit loop carries
+    bool told_nonascii = !(P.fold && P.nonascii);
     uint32_t slab_left = KARG(slab);
 
     // work distribution as in gft_scan2.hip: the workgroup owns the units b * waves + k * (grid * waves) + [0, waves) of
     // every round k, its waves take them one by one from a counter in LDS
     constexpr uint32_t wg_waves = kScan5Waves;                    // (a constant: item / wg_waves is a shift, not a division per unit)
-    const uint64_t round_units = (uint64_t)gridDim.x * wg_waves, wg_first = (uint64_t)blockIdx.x * wg_waves;
-    auto unit_of = [&](uint32_t item) -> uint64_t { return (uint64_t)(item / wg_waves) * round_units + wg_first + item % wg_waves; };
+    // (a round's units and the workgroup's first one fit 32 bits: the 64-bit unit number is one widening multiply away)
+    const uint32_t round_units = gridDim.x * wg_waves, wg_first = blockIdx.x * wg_waves;
+    auto unit_of = [&](uint32_t item) -> uint64_t { return (uint64_t)(item / wg_waves) * round_units + (wg_first + item % wg_waves); };
     uint64_t u = unit_of(wave), nu = 0;                           // wave-uniform
     Unit un_n{0, 0, 0};
     uint64_t abs_n = 0, end_n = 0;                               // the next unit's document: blob offsets of its first byte and of the byte behind it
@@ -335,7 +349,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
         const bool more_units = nu < P.n_units;
         if (more_units) un_n = P.units[nu];
         const Ctx c{P, cls, nullptr, P.short3_bytes ? short3 : nullptr, fpt, lrec, P.text + doc_abs, doc_abs, kp2,
-                    doc_abs < 7, doc_abs < 23, un.lo, un.hi, doc_abs + un.hi + 4 > P.text_bytes, DBG ? P.dbg : 0u};
+                    doc_abs < 7, doc_abs < 23, un.lo, un.hi, doc_abs + un.hi + 4 > KARG(text_bytes), DBG ? P.dbg : 0u};
         const uint32_t nborder = un.lo < kScan2MaxOff ? un.lo : kScan2MaxOff;
         const uint32_t ubase = un.lo - kScan2MaxOff;               // candidate lists hold p - ubase (may wrap; p never does)
         const uint32_t own = un.hi - un.lo;
@@ -343,7 +357,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
         const uint32_t my_lo = un.lo + lane * C;
         const uint32_t my_hi = my_lo + C < un.hi ? my_lo + C : un.hi;
         const uint32_t nvalid = my_lo < un.hi ? my_hi - my_lo : 0;
-        Ctx5 o{fifo, P.s5_fifo_cap, 0, 0, false, false, 0, P.s5_term_bits, un.lo - P.s5_pos_bias};
+        Ctx5 o{fifo, P.s5_fifo_cap, 0, 0, false, false, 0, POS ? P.s5_term_bits : 0u, POS ? un.lo - P.s5_pos_bias : 0u};
 
         // ---- FILTER -----------------------------------------------------------------------------------------------------
         uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
@@ -365,7 +379,6 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
             pq = mad24s(h2, G, h1);
             mark(0);
             uint32_t acc = 0, njobs = 0, hib = 0;                // hib: OR of the lane's text (a byte >= 0x80 anywhere?)
-            const bool want_fold = P.fold && P.nonascii;
             const uint32_t ndw = C >> 2;                         // dwords per lane (wave-uniform, <= 32)
             const uint32_t npieces = (ndw + 3) >> 2;
             for (uint32_t q = 0; q < npieces; q++) {
@@ -376,7 +389,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                 // lane that saw one").  The all-ASCII instantiation keeps the two ORs: the extra loop-carried state cost the
                 // headline 1.2 % when both shared the code (round 3)
                 if constexpr (SG) {
-                    if (want_fold && !told_nonascii)
+                    if (!told_nonascii)
                         fold_job_push(q * 16 < nvalid && (((w[0] | w[1]) | (w[2] | w[3])) & 0x80808080u) != 0, lane * C + q * 16, cand, P.cand_cap, njobs);
                 }
                 if (q + 1 < npieces && (q + 1) * 16 < nvalid) nxt = *reinterpret_cast<const U128u*>(src + (q + 1) * 16);
@@ -431,7 +444,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
             // ASCII folding is not strings.ToLower once the text leaves ASCII (finder.go:140-142): the pieces of the lanes that
             // met a byte >= 0x80 are judged now (gft_foldsafe_dev.hpp; which of a lane's pieces it was is not kept -- text that
             // leaves ASCII is the exception for the dictionaries this kernel serves, the filter loop pays two ORs for it)
-            if (!SG && want_fold && !told_nonascii && __any((hib & 0x80808080u) != 0)) {
+            if (!SG && !told_nonascii && __any((hib & 0x80808080u) != 0)) {
                 for (uint32_t q = 0; q < npieces; q++)
                     fold_job_push((hib & 0x80808080u) != 0 && q * 16 < nvalid, lane * C + q * 16, cand, P.cand_cap, njobs);
             }
@@ -442,9 +455,9 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                 uint32_t bits = 1u;
                 if (njobs <= P.cand_cap) {
                     FOLD_JOB_VARS(fj_);
-                    bits = fold_jobs_begin(P.text, end_v, doc_abs + un.lo, own, un.lo == 0, cand, njobs, FOLD_JOB_PASS(fj_)) || fold_jobs_finish(FOLD_JOB_PASS(fj_)) ? 2u : 0u;
+                    bits = fold_jobs_begin(KARG(text), end_v, doc_abs + un.lo, own, un.lo == 0, cand, njobs, FOLD_JOB_PASS(fj_)) || fold_jobs_finish(FOLD_JOB_PASS(fj_)) ? 2u : 0u;
                 }
-                if (bits) { told_nonascii = true; if (lane == 0) atomicOr(P.nonascii, bits); }
+                if (bits) { told_nonascii = true; if (lane == 0) atomicOr(KARG(nonascii), bits); }
             }
             // positions past the lane's range carry garbage flags
             m0 = nvalid >= 32 ? m0 : (nvalid ? m0 & ((1u << nvalid) - 1) : 0);
@@ -549,7 +562,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         if (i0 + 64 * q < ptotal)                  // (positions in front of the unit: long terms only)
                         {
                             const uint32_t sidq = on[q] && rel[q] >= kScan2MaxOff ? k[q].sid : 0;
-                            if (SG) park_short_g(c, o, lsg, ubase, rel[q], sidq); else park_short(c, o, ubase, rel[q], sidq, k[q].x3);
+                            if (SG) park_short_g<POS>(c, o, lsg, ubase, rel[q], sidq); else park_short<POS>(c, o, ubase, rel[q], sidq, k[q].x3);
                         }
                     const uint64_t below = (1ull << lane) - 1;
 #pragma unroll
@@ -597,7 +610,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         b_tl = tail_load(c, b_k.p);
                     }
                 }
-                while (o.npend) { if (SG) short_trip_g(c, o, lsg, ubase, o.npend < 64 ? o.npend : 64); else short_trip(c, o, ubase, o.npend < 64 ? o.npend : 64); }
+                while (o.npend) { if (SG) short_trip_g<POS>(c, o, lsg, ubase, o.npend < 64 ? o.npend : 64); else short_trip<POS>(c, o, ubase, o.npend < 64 ? o.npend : 64); }
                 if (DBG && (P.dbg & 2)) { if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(KARG(dbg_counters) + 2), (unsigned long long)ns); }
                 mark(3);
                 Deferred dfr;
@@ -607,7 +620,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                 if (ns) {
                     b_k.tw = b_t8.tw;
                     b_fr.f[0] = b_t8.tw;
-                    finish_long5(c, o, b_on, b_rel, b_k, b_s0, b_s1, b_fr, b_tl, dfr);
+                    finish_long5<POS>(c, o, b_on, b_rel, b_k, b_s0, b_s1, b_fr, b_tl, dfr);
                 }
                 for (uint32_t i0 = 64; i0 < ns; i0 += 64) {
                     const bool on = i0 + lane < ns;
@@ -624,7 +637,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         const Front fr = front_load(c, p, t8.tw);
                         const uint32_t tl5 = tail_load(c, p);
                         k.tw = t8.tw;
-                        finish_long5(c, o, on, rel, k, s0, s1, fr, tl5, dfr);
+                        finish_long5<POS>(c, o, on, rel, k, s0, s1, fr, tl5, dfr);
                     } else {
                         const Text8 t8 = cand_load(c, p);
                         const Front fr = front_load(c, p, t8.tw);
@@ -632,10 +645,10 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         cand_keys<false>(c, p, t8, k);
                         const Slot s0 = slot_load(&P.slots[scan2_pair_slot(k.x, 0, P.slot_shift, P.slot_seed)]);
                         const Slot s1 = slot_load(&P.slots[scan2_pair_slot(k.x, 1, P.slot_shift, P.slot_seed)]);
-                        finish_long5(c, o, on, rel, k, s0, s1, fr, tl5, dfr);
+                        finish_long5<POS>(c, o, on, rel, k, s0, s1, fr, tl5, dfr);
                     }
                 }
-                if (dfr.n) drain_deferred5(c, o, ubase, dfr);
+                if (dfr.n) drain_deferred5<POS>(c, o, ubase, dfr);
                 wave_lds_sync();
                 l0 = l1;
                 mark(4);
@@ -672,11 +685,11 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
             const bool room = base + nh <= KARG(pool_cap);
             if (lane == 0) { KARG(unit_start)[u] = base; KARG(unit_count)[u] = room ? nh : 0u; }
             if (room && !o.direct) {
-                const uint32_t tmask = (1u << o.term_bits) - 1u;
+                const uint32_t tmask = POS ? (1u << o.term_bits) - 1u : 0u;
                 for (uint32_t i = lane; i < nh; i += 64) {
                     const uint32_t e = fifo[i];
                     // (streaming stores: the pool is read by the NEXT kernel, its lines should not push the units' text out of L2)
-                    if (P.want_pos) {
+                    if constexpr (POS) {
                         __builtin_nontemporal_store(e & tmask, &KARG(pool_term)[base + i]);
                         __builtin_nontemporal_store(o.pos_base + (e >> o.term_bits), &KARG(pool_pos)[base + i]);
                     } else {
@@ -743,13 +756,18 @@ hipError_t launch_scan5(const Scan2Params& P, unsigned n_cus, hipStream_t st) {
     const size_t lds = scan5_fixed_lds(P.s5_dual, P.short3_bytes, P.shorts_words, fl ? kScan2FptSize : P.s5_bloom_lg ? (1u << P.s5_bloom_lg) / 8 : 0) +
                        (size_t)kScan5Waves * scan5_wave_lds(P.s5_fifo_cap, P.cand_cap);
     using Kern = void (*)(const Scan2Params);
-    // (the timing-study instantiations exist for the direct short-term table only)
+    // one instantiation per (fingerprint table in LDS, short-term tables by group, positions wanted); the timing-study
+    // instantiations exist for the direct short-term table only
+    const auto pick = [&](auto pos) -> Kern {
+        constexpr bool POS = decltype(pos)::value;
 #ifdef GFT_S5_SG_CLOCKS       // (study builds, tools/build_variant.sh: the phase clocks of the large-alphabet instantiation)
-    const Kern fn = P.s5_sG ? (P.dbg && fl ? k_scan5<true, true, true> : fl ? k_scan5<true, false, true> : k_scan5<false, false, true>)
-#else
-    const Kern fn = P.s5_sG ? (fl ? k_scan5<true, false, true> : k_scan5<false, false, true>)
+        if (P.s5_sG && P.dbg && fl) return k_scan5<true, true, true, POS>;
 #endif
-                    : P.dbg ? (fl ? k_scan5<true, true, false> : k_scan5<false, true, false>) : (fl ? k_scan5<true, false, false> : k_scan5<false, false, false>);
+        if (P.s5_sG) return fl ? k_scan5<true, false, true, POS> : k_scan5<false, false, true, POS>;
+        if (P.dbg) return fl ? k_scan5<true, true, false, POS> : k_scan5<false, true, false, POS>;
+        return fl ? k_scan5<true, false, false, POS> : k_scan5<false, false, false, POS>;
+    };
+    const Kern fn = P.want_pos ? pick(std::true_type{}) : pick(std::false_type{});
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     uint64_t g = (P.n_units + kScan5Waves - 1) / kScan5Waves;
