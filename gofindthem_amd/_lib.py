@@ -177,6 +177,13 @@ SYMBOLS = {
     "gft_debug_excerpt_shape": (None, [C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_excerpts_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
                                        C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_mark_spans_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64),
+                                  C.POINTER(_u64)]),
+    "gft_debug_mark_spans": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64),
+                                 C.POINTER(_u64)]),
+    "gft_debug_mark_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gft_finder_mark_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp,
+                                   C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
     "gft_debug_lowermap_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_group_process_json_lines": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),

@@ -609,6 +609,34 @@ Error Finder::ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
+                         const uint32_t* d_span_len, bool spans_lowered, bool source, const uint8_t* open, uint32_t open_len, const uint8_t* close,
+                         uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint32_t* d_span_new,
+                         uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes, int* lowered) {
+    last_code_ = 0;
+    if (lowered) *lowered = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    const uint8_t* d_text = d_blob;
+    const uint64_t* d_off = d_doc_off;
+    // spans that index the lowered text mark the lowered text: lowered again here, as the spans call lowered it
+    if (spans_lowered && !source && n_docs) {
+        if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+            last_code_ = GFT_E_UNSUPPORTED;
+            return "marks in a lowered batch need a case-insensitive finder with the device ToLower on a single device";
+        }
+        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_text, &d_off);
+        if (rc) return fail_gft(rc);
+        if (lowered) *lowered = 1;
+    }
+    int rc = gft_mark_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, open, open_len, close, close_len, flags,
+                                   d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, n_runs, total_bytes);
+    return rc ? fail_gft(rc) : Error();
+}
+
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
     if (!gpu_sub_ || !regexes_.empty()) {
@@ -935,6 +963,18 @@ int gft_finder_excerpts_device(gft_finder* f, const uint8_t* d_text_blob, const 
     return finder_ret(f, f->finder->ExcerptsDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
                                                    before, after, flags, d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc,
                                                    d_span_rel, d_doc_exc_off, n_exc, total_bytes, lowered), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                           const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered, int source, const uint8_t* open,
+                           uint32_t open_len, const uint8_t* close, uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
+                           uint64_t* d_out_off, uint32_t* d_span_new, uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes,
+                           int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->MarkDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
+                                               open, open_len, close, close_len, flags, d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, n_runs,
+                                               total_bytes, lowered), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

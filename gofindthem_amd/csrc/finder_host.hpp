@@ -150,6 +150,12 @@ public:
                          const uint32_t* d_span_len, bool spans_lowered, bool source, uint32_t before, uint32_t after, uint32_t flags, uint8_t* d_out,
                          uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off,
                          uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes, int* lowered);
+    // gft_mark_spans_device on the finder's engine behind HitSpansDevice, under ExcerptsDevice's rule: source or an unlowered batch
+    // marks the caller's batch; else the lowered text, lowered on the device again -- *lowered = 1
+    Error MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
+                     const uint32_t* d_span_len, bool spans_lowered, bool source, const uint8_t* open, uint32_t open_len, const uint8_t* close,
+                     uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint32_t* d_span_new,
+                     uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes, int* lowered);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

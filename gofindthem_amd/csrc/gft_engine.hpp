@@ -214,6 +214,9 @@ struct gft_engine {
         uint64_t* pin = nullptr;           // pinned landing place of the control block's read-backs (freed with the handle)
     } d_excerpt;
 
+    // highlight (gft_mark.hip): the run passes work in the excerpt's buffers; the insertion list and the marker block are its own
+    struct MarkBufs { DevBuf q, marks; } d_mark;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

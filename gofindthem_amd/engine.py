@@ -485,6 +485,91 @@ def excerpt_shape():
     return int(t.value), int(k.value)
 
 
+MARK_MAX = 255                                      # GFT_MARK_MAX
+
+
+def mark_spans_tensor(call, text, doc_off, span_off, start, length, open=b"<em>", close=b"</em>"):
+    """what Engine.mark_spans_device and Finder.MarkDevice share: `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start,
+    d_span_len, open, open_len, close, close_len, flags, d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, byref(n_runs),
+    byref(total))` is gft_mark_spans_device on some handle and raises on an error.  Two calls: count only with NULL outputs, then
+    into tensors of exactly the sizes counted.  Returns (out uint8 [total] -- the marked documents back to back, a view with 64
+    zero bytes behind it --, out_off int64 [n + 1], span_new int32 [spans], doc_run_off int64 [n + 1])"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("mark_spans_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel():
+        raise ValueError("mark_spans_device: doc_off, span_off and the span arrays do not describe the same batch")
+    open, close = bytes(open), bytes(close)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
+            length.data_ptr() if length.numel() else None, open or None, len(open), close or None, len(close), 0)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+    dev = text.device
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, None, 0, None, None, None, C.byref(m), C.byref(total))
+    nb = int(total.value)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=dev)          # (64 bytes of slack: the result is a blob for the next call)
+    out_off, doc_run_off = (torch.empty(n_docs + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    span_new = torch.zeros(start.numel(), dtype=torch.int32, device=dev)
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, buf.data_ptr(), nb, out_off.data_ptr(), span_new.data_ptr() if span_new.numel() else None, doc_run_off.data_ptr(),
+         C.byref(m), C.byref(total))
+    return buf[:nb], out_off, span_new, doc_run_off
+
+
+def mark_spans_host(blob, doc_off, span_off, start, length, open=b"<em>", close=b"</em>", cap_bytes=None, guard=0, flags=0, omit=(),
+                    count_only=False, open_len=None, close_len=None, shift=0):
+    """gft_debug_mark_spans over host arrays -> a dict: n_runs, total, out uint8 [cap_bytes + guard], out_off / doc_run_off uint64
+    [n + 1 + guard], span_new uint32 [len(start) + guard]; no device needed.  cap_bytes None: count first, then exactly what the
+    result needs; the guard entries behind hold 0xA5.. and must come back untouched.  omit: names of outputs passed as NULL (they
+    come back as None).  open_len / close_len: lengths to pass instead of the markers' own; a marker None is passed as NULL.
+    shift: bytes the output's first byte lies behind a 16-byte border"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
+    st, ln = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(length, dtype=np.uint32)
+    n_docs = off.size - 1
+    ol = (len(open) if open is not None else 0) if open_len is None else int(open_len)
+    cl = (len(close) if close is not None else 0) if close_len is None else int(close_len)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cb, oo, sn, dro):
+        rc = L.gft_debug_mark_spans(_p(a) if a.size else None, _p(off), n_docs, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None,
+                                    bytes(open) if open else None, ol, bytes(close) if close else None, cl, int(flags), _p(out), cb, _p(oo), _p(sn),
+                                    _p(dro), C.byref(m), C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_mark_spans")
+    if cap_bytes is None or count_only:
+        call(None, 0, None, None, None)
+        cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
+    r = {"n_runs": int(m.value), "total": int(total.value)}
+    if count_only:
+        return r
+    big = 0xA5A5A5A5A5A5A5A5
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    lead = (-raw.ctypes.data) % 16 + int(shift)
+    arrs = {"out": raw[lead:lead + cap_bytes + guard], "out_off": np.full(n_docs + 1 + guard, big, dtype=np.uint64),
+            "span_new": np.full(st.size + guard, 0xA5A5A5A5, dtype=np.uint32), "doc_run_off": np.full(n_docs + 1 + guard, big, dtype=np.uint64)}
+    for k in omit:
+        arrs[k] = None
+    for k in ("out", "span_new"):
+        if arrs[k] is not None and arrs[k].size == 0:
+            arrs[k] = None
+    r.update(arrs)
+    call(arrs["out"], cap_bytes if arrs["out"] is not None else 0, arrs["out_off"], arrs["span_new"], arrs["doc_run_off"])
+    r.update(n_runs=int(m.value), total=int(total.value))
+    return r
+
+
+def mark_shape():
+    """(spans of a tile of the run passes' suffix-minimum scan, tiles of one carry trip, bytes of a lane's chunk of the output, bytes
+    of a wave's tile) (gft_debug_mark_shape)"""
+    v = [C.c_uint32(0) for _ in range(4)]
+    _lib.load().gft_debug_mark_shape(*(C.byref(x) for x in v))
+    return tuple(int(x.value) for x in v)
+
+
 def lowermap_shape():
     """(bytes of a piece, of a wave's trip, of a work unit at most, spans of a wave's tile) (gft_debug_lowermap_shape)"""
     v = [C.c_uint32(0) for _ in range(4)]
@@ -737,6 +822,34 @@ class Engine:
         return (r["out"][:total] if r["out"] is not None else np.zeros(0, dtype=np.uint8), r["exc_off"][:m + 1],
                 r["exc_doc"][:m] if m else np.zeros(0, dtype=np.uint64), r["exc_start"][:m] if m else np.zeros(0, dtype=np.uint32),
                 r["exc_span_off"][:m + 1], r["span_rel"] if r["span_rel"] is not None else np.zeros(0, dtype=np.uint32), r["doc_exc_off"])
+
+    def mark_spans_device(self, text, doc_off, span_off, start, length, open=b"<em>", close=b"</em>"):
+        """the batch's text with `open` in front of every hit and `close` behind it, written on the device (gft_mark_spans_device).
+        text, doc_off: the batch the spans index; span_off, start, length: what hit_spans_device returned for it,
+        map_spans_to_source_device rewrote, or excerpt_spans_device handed back as (exc_span_off, span_rel, length) for its blob.
+        Spans that overlap or touch share one pair of markers.  Returns device tensors (out uint8 [total] -- the marked documents
+        back to back, a view with 64 zero bytes behind it --, out_off int64 [n + 1], span_new int32 [spans] -- every span's start in
+        its marked document --, doc_run_off int64 [n + 1]); (out, out_off, span_off, span_new, length) is what redact_spans_device,
+        excerpt_spans_device and this call take.  The call runs twice: count only, then into tensors of exactly those sizes"""
+        return mark_spans_tensor(lambda *a: self._check(self._L.gft_mark_spans_device(self._h, *a)), text, doc_off, span_off, start, length,
+                                 open, close)
+
+    @staticmethod
+    def mark_spans_tensor(call, text, doc_off, span_off, start, length, open=b"<em>", close=b"</em>"):
+        """the module's mark_spans_tensor: the count call and the fill call round any gft_mark_spans_device-shaped `call`"""
+        return mark_spans_tensor(call, text, doc_off, span_off, start, length, open, close)
+
+    @staticmethod
+    def mark_spans_host(blob, doc_off, span_off, start, length, open=b"<em>", close=b"</em>"):
+        """the host twin of mark_spans_device over numpy arrays (gft_debug_mark_spans): the same tuple, as numpy arrays"""
+        r = mark_spans_host(blob, doc_off, span_off, start, length, open, close)
+        return (r["out"][:r["total"]] if r["out"] is not None else np.zeros(0, dtype=np.uint8), r["out_off"],
+                r["span_new"] if r["span_new"] is not None else np.zeros(0, dtype=np.uint32), r["doc_run_off"])
+
+    @staticmethod
+    def mark_shape():
+        """(tile_spans, trip_tiles, chunk_bytes, tile_bytes) of the highlight's walk (gft_debug_mark_shape)"""
+        return mark_shape()
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

@@ -526,7 +526,7 @@ class Finder:
         out = excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes)
         return out + (bool(cut.value),)
 
-    def ExcerptLines(self, data, before=40, after=40, want=None, source=True, runes=True):
+    def ExcerptLines(self, data, before=40, after=40, want=None, source=True, runes=True, mark=None):
         """bytes -> (idx, excerpts, lowered): idx the numbers of the lines that hit `want` (want_mask(); None: any expression),
         excerpts[k] the list of (start_in_line, bytes, [(rel_start, rel_end, keyword), ...]) of line idx[k]: the text `before` bytes
         in front of and `after` bytes behind every hit of SpansLines, windows that overlap or touch merged, cut on rune borders
@@ -535,7 +535,9 @@ class Finder:
         batch left ASCII; with source=True (the default) the excerpts are still substrings of the caller's lines at start_in_line,
         with source=False they are cut from the lines' lower-case form.  Device route only, as SpansLines: a finder with regex
         terms, an injected engine or several devices has no host route to the spans (the cut itself has one:
-        Engine.excerpt_spans_host) and is refused with GFT_E_UNSUPPORTED before anything is uploaded"""
+        Engine.excerpt_spans_host) and is refused with GFT_E_UNSUPPORTED before anything is uploaded.  mark=(open, close): the excerpt
+        blob goes through the mark call on the device before it comes down (MarkDevice's rule): every excerpt's bytes are the marked
+        ones, and rel_start / rel_end index them"""
         data = bytes(data)
         if not self._takes_device_route():
             raise FinderError(_lib.GFT_E_UNSUPPORTED, "ExcerptLines needs the device route, as the hit spans do: the GPU substring engine, no regex "
@@ -544,6 +546,11 @@ class Finder:
         off, bm, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want, source)
         out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, _, _ = self.ExcerptsDevice(buf, off, span_off, start, length, lowered, source,
                                                                                              before, after, runes)
+        if mark is not None:
+            # the excerpts are a batch with a span CSR of their own: marked as such, never across an excerpt's border
+            from .engine import mark_spans_tensor
+            out, exc_off, span_rel, _ = mark_spans_tensor(lambda *a: self._check_engine(self._L.gft_mark_spans_device(self.engine_handle(), *a)),
+                                                          out, exc_off, exc_span_off, span_rel, length, mark[0], mark[1])
         rows = bm.cpu().numpy().view(np.uint32).reshape(int(off.numel()) - 1, -1)
         w = self.want_mask() if want is None else np.ascontiguousarray(want, dtype=np.uint32)
         w = self.want_mask() & w
@@ -560,6 +567,38 @@ class Finder:
             hits = [(int(rel[j]), int(rel[j]) + int(ln[j]), terms[int(tm[j])]) for j in range(int(eso[k]), int(eso[k + 1]))]
             per_line.setdefault(int(ed[k]), []).append((int(es[k]), blob[int(eo[k]):int(eo[k + 1])], hits))
         return hit.astype(np.uint64), [per_line.get(d, []) for d in hit.tolist()], lowered
+
+    # -- markers written round the hits (csrc/gft_mark.hip) ---------------------------------------------------------------------------
+    def MarkDevice(self, text, doc_off, span_off, start, length, lowered=False, source=False, open=b"<em>", close=b"</em>"):
+        """Engine.mark_spans_device on the finder's engine behind SpansDevice (gft_finder_mark_device): text, doc_off the batch,
+        span_off / start / length and `lowered` what SpansDevice returned for it, source as it was called.  With source, or for a
+        batch that was not lowered, the caller's batch is marked; otherwise the batch's lower-case form, which the finder lowers on
+        the device again.  Returns (out, out_off, span_new, doc_run_off, marked_lowered) -- device tensors as
+        Engine.mark_spans_device gives them, and whether the lowered text was marked.  Needs what ProcessDevice needs"""
+        from .engine import mark_spans_tensor
+        low = C.c_int(0)
+
+        def call(d_text, d_off, n, d_so, d_st, d_ln, *rest):
+            self._check(self._L.gft_finder_mark_device(self._h, d_text, d_off, n, d_so, d_st, d_ln, 1 if lowered else 0, 1 if source else 0,
+                                                       *rest, C.byref(low)))
+        out = mark_spans_tensor(call, text, doc_off, span_off, start, length, open, close)
+        return out + (bool(low.value),)
+
+    def HighlightLines(self, data, open=b"<em>", close=b"</em>", want=None, source=True):
+        """bytes -> (bytes, lowered): the blob with `open` in front of and `close` behind every keyword occurrence that is a witness of
+        a true, wanted expression; occurrences that overlap or touch share one pair.  One upload, then split, process, spans and the
+        marks on the device, one download of the marked blob.  lowered True: the batch left ASCII; with source=True (the default)
+        the caller's bytes are marked all the same (the spans are mapped back to them), with source=False the lines' lower-case
+        form.  Device route only, as SpansLines: a finder with regex terms, an injected engine or several devices has no host route
+        to the spans and is refused with GFT_E_UNSUPPORTED before anything is uploaded"""
+        data = bytes(data)
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "HighlightLines needs the device route, as the hit spans do: the GPU substring engine, no "
+                                                      "regex terms, one device")
+        buf = self._resident(data)
+        off, _, span_off, start, length, _, lowered = self._spans_of_lines(buf, len(data), want, source)
+        out = self.MarkDevice(buf, off, span_off, start, length, lowered, source, open, close)[0]
+        return out.cpu().numpy().tobytes(), lowered
 
     # -- documents routed to one bucket per tag (csrc/gft_route.hip) -----------------------------------------------------------
     def route_masks(self, buckets=None):

@@ -591,6 +591,61 @@ int gft_debug_excerpt_spans(const uint8_t* blob, const uint64_t* doc_off, uint64
 /* where that walk's borders are: the spans of a tile of the suffix-minimum scan, the tiles of one carry trip */
 void gft_debug_excerpt_shape(uint32_t* tile_spans, uint32_t* trip_tiles);
 
+/* ---- Highlight on the device: markers written round the hits (csrc/gft_mark.hip) --------------------------------------------
+ * Between "where" (the spans) and "show it" (the excerpts): the text of a resident batch with `open` written in front of every
+ * hit and `close` behind it -- <em> .. </em>, ** .. **, ANSI colour codes.  The text grows; the index outputs keep every call
+ * behind this one usable on the marked text.  No scan, no dictionary, no programs; gft_last_nonascii is left alone.
+ * Input: the batch under the scans' placement contract (no alignment, d_doc_off[0] may be non-zero, 64 readable bytes of slack;
+ * neither the lead bytes nor the slack change the answer), and a span CSR as gft_hit_spans_device wrote it,
+ * gft_map_spans_to_source_device rewrote it, or gft_excerpt_spans_device handed it back as (d_exc_span_off, d_span_rel,
+ * d_span_len) for its blob.  open and close are HOST memory, 0 .. GFT_MARK_MAX bytes each, copied by the call; NULL is allowed
+ * where the length is 0.  flags must be 0.
+ * Runs: the runs of a document are the connected components of the union of its spans [start, start + len); spans that overlap,
+ * nest, repeat or touch (a.end == b.start) are one run, a gap of one byte separates two; a run never crosses a document border.
+ * By definition the runs are the excerpts gft_excerpt_spans_device forms for the same input with before = after = 0, flags = 0;
+ * a len == 0 span that touches nothing is a run of no bytes.  The order requirement is the excerpt's: within a document
+ * start + len must not descend.  A batch that breaks it, or a span with start + len > L, is found on the device before anything
+ * is written: GFT_E_INVALID, and nothing at all is written.
+ * Output text: document d of L bytes with R(d) runs becomes its own bytes with open in front of the first byte of every run and
+ * close behind its last: L + R(d) * (open_len + close_len) bytes.  A run of no bytes at p gets open and close back to back at p.
+ * Nothing is inserted outside a document.  d_out holds the marked documents back to back in input order; with both lengths 0 it
+ * is the batch's text byte for byte.
+ * Index outputs, device memory, each nullable on its own, never capped, complete when given: d_out_off [n_docs + 1]
+ * (d_out_off[0] = 0), the doc_off of d_out; d_span_new, parallel to d_span_start (the entries [d_span_off[0], d_span_off[n_docs])
+ * are written): the span's start in its MARKED document, start + (r + 1) * open_len + r * close_len with r the index of the span's
+ * run within its document; d_doc_run_off [n_docs + 1], the documents' CSR over the runs.  No marker lies inside a run, so
+ * (d_out, d_out_off, n_docs, d_span_off, d_span_new, d_span_len) is a valid argument list of gft_redact_spans_device, of
+ * gft_excerpt_spans_device and of this call itself: the order and the in-document checks hold on it.
+ * Cap protocol of gft_compact_device: cap_bytes counts bytes of d_out; a byte at or past the cap is not written, be it text or
+ * marker; nothing is stored at or past d_out + cap_bytes; d_out == NULL with cap_bytes == 0 counts only; GFT_OK either way, and
+ * *n_runs / *total_bytes (host, nullable) are always handed back.
+ * Launches on the engine's stream (gft_profile_read): "mark_runs" (the span checks, the suffix minimum and the heads: the
+ * excerpt's passes), "mark_scan" (the prefix sum of the heads; the marked lengths checked), "mark_place" (d_out_off, d_span_new,
+ * d_doc_run_off and the insertion list: 2 * n_runs blob positions, open at the even and close at the odd entries), "mark_copy"
+ * (from the output side: a wave a 4 KiB tile, a lane a 16-byte chunk, the markers in LDS).  The call waits for the stream.
+ * Between gft_process_device_begin and _end it is allowed only after _complete.  n_docs == 0 and no spans are valid: the output is
+ * then a copy of the text.  GFT_E_UNSUPPORTED: a handle over several devices.  GFT_E_INVALID: flags != 0; a marker longer than
+ * GFT_MARK_MAX; a non-zero length with a NULL marker; an output that overlaps an input or another output; document or span
+ * offsets that descend; a document of 4 GiB or more, or one that would reach 4 GiB once marked (d_span_new is 32-bit).
+ * GFT_E_NOMEM: no room for the work buffers (48 bytes a span, 16 a run).  Every refusal comes before any store, and the handle
+ * stays usable after any error. */
+#define GFT_MARK_MAX 255u   /* bytes of one marker */
+int gft_mark_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                          const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len,
+                          const uint8_t* open, uint32_t open_len, const uint8_t* close, uint32_t close_len, uint32_t flags,
+                          uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint32_t* d_span_new, uint64_t* d_doc_run_off,
+                          uint64_t* n_runs, uint64_t* total_bytes);
+/* The host form, no HIP device needed, same contract, all pointers host (the 64 bytes of slack are not asked for here): the
+ * runs by the excerpt's host walk, the copy tile by tile and lane by lane through the source the kernels are compiled from
+ * (csrc/gft_mark_piece.hpp). */
+int gft_debug_mark_spans(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                         const uint32_t* span_start, const uint32_t* span_len, const uint8_t* open, uint32_t open_len,
+                         const uint8_t* close, uint32_t close_len, uint32_t flags, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
+                         uint32_t* span_new, uint64_t* doc_run_off, uint64_t* n_runs, uint64_t* total_bytes);
+/* where that walk's borders are: the spans of a tile of the suffix-minimum scan, the tiles of one carry trip, the bytes of a
+ * lane's chunk of the output and of a wave's tile */
+void gft_debug_mark_shape(uint32_t* tile_spans, uint32_t* trip_tiles, uint32_t* chunk_bytes, uint32_t* tile_bytes);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -704,6 +759,14 @@ int gft_finder_excerpts_device(gft_finder* f, const uint8_t* d_text_blob, const 
                                uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start,
                                uint64_t* d_exc_span_off, uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc,
                                uint64_t* total_bytes, int* lowered);
+/* gft_mark_spans_device on the finder's engine, under the rule of gft_finder_excerpts_device: with source, or for a batch that
+ * was not lowered, the caller's batch is marked; otherwise the finder lowers the batch on the device again, marks that text and
+ * sets *lowered = 1 (else 0).  Everything else is gft_mark_spans_device's contract. */
+int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                           const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered, int source, const uint8_t* open,
+                           uint32_t open_len, const uint8_t* close, uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
+                           uint64_t* d_out_off, uint32_t* d_span_new, uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes,
+                           int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
