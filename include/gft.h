@@ -562,7 +562,9 @@ void gft_debug_lowermap_shape(uint32_t* piece_bytes, uint32_t* trip_bytes, uint3
  * no further call.
  * Cap protocol of gft_compact_device with two caps: cap_exc counts excerpt entries (d_exc_off and d_exc_span_off have cap_exc + 1,
  * d_exc_doc and d_exc_start cap_exc), cap_bytes bytes of d_out; nothing is stored at or past any array + cap; an excerpt that
- * cap_bytes cuts is written up to the cap, and d_exc_off keeps the uncut offsets.  d_span_rel and d_doc_exc_off are sized by the
+ * cap_bytes cuts is written up to the cap, and d_exc_off keeps the uncut offsets.  The d_exc_span_off entries below the cap -- the
+ * last of them, d_exc_span_off[cap_exc], too -- are indexes into the caller's span arrays like all the others: they count from the
+ * arrays' first entry, not from d_span_off[0].  d_span_rel and d_doc_exc_off are sized by the
  * input, are never capped and are complete when given.  All outputs NULL with both caps 0 counts only; GFT_OK either way, and
  * *n_exc / *total_bytes (host, nullable) are always handed back.
  * Launches on the engine's stream (gft_profile_read): "excerpt_window" (a lane a span: its document by a binary search, the
@@ -602,7 +604,8 @@ void gft_debug_excerpt_shape(uint32_t* tile_spans, uint32_t* trip_tiles);
  * where the length is 0.  flags must be 0.
  * Runs: the runs of a document are the connected components of the union of its spans [start, start + len); spans that overlap,
  * nest, repeat or touch (a.end == b.start) are one run, a gap of one byte separates two; a run never crosses a document border.
- * By definition the runs are the excerpts gft_excerpt_spans_device forms for the same input with before = after = 0, flags = 0;
+ * By definition the runs are the excerpts gft_excerpt_spans_device forms for the same input with before = after = 0, flags = 0
+ * (that call's d_exc_span_off, capped or not, names the runs' first spans by their indexes in the caller's span arrays);
  * a len == 0 span that touches nothing is a run of no bytes.  The order requirement is the excerpt's: within a document
  * start + len must not descend.  A batch that breaks it, or a span with start + len > L, is found on the device before anything
  * is written: GFT_E_INVALID, and nothing at all is written.

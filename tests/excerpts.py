@@ -24,19 +24,21 @@ class Case:
             setattr(c, k, v)
         return c
 
-    def arrays(self, fill=0x00):
-        """(blob uint8, doc_off, span_off uint64, start, len uint32): the lead bytes hold `fill`"""
+    def arrays(self, fill=0x00, span_lead=0, span_tail=0):
+        """(blob uint8, doc_off, span_off uint64, start, len uint32): the lead bytes hold `fill`.  span_lead / span_tail: entries of
+        the span arrays in front of the batch's spans (span_off[0] = span_lead) and behind them; they hold FULL, FULL -- a span
+        every call would refuse if it read it"""
         blob = bytes([fill]) * self.lead + b"".join(self.docs)
         off = np.zeros(len(self.docs) + 1, dtype=np.uint64)
         off[0] = self.lead
         if self.docs:
             off[1:] = self.lead + np.cumsum([len(d) for d in self.docs], dtype=np.uint64)
-        so = np.zeros(len(self.docs) + 1, dtype=np.uint64)
+        so = np.full(len(self.docs) + 1, span_lead, dtype=np.uint64)
         if self.docs:
-            so[1:] = np.cumsum([len(s) for s in self.spans], dtype=np.uint64)
+            so[1:] = span_lead + np.cumsum([len(s) for s in self.spans], dtype=np.uint64)
         flat = [x for s in self.spans for x in s]
-        st = np.array([a for a, _ in flat], dtype=np.uint32)
-        ln = np.array([b for _, b in flat], dtype=np.uint32)
+        st = np.array([FULL] * span_lead + [a for a, _ in flat] + [FULL] * span_tail, dtype=np.uint32)
+        ln = np.array([FULL] * span_lead + [b for _, b in flat] + [FULL] * span_tail, dtype=np.uint32)
         return np.frombuffer(blob, dtype=np.uint8), off, so, st, ln
 
 
@@ -63,12 +65,15 @@ def window(doc, start, length, before, after, runes, text=None, base=0):
     return lo, hi
 
 
-def expected(case, mutant=None):
+def expected(case, mutant=None, span_lead=0, span_tail=0):
     """a dict of what the call hands back under exact caps: n_exc, total, out (bytes), exc_off, exc_doc, exc_start, exc_span_off,
-    span_rel, doc_exc_off (lists).  Excerpts in document order, inside a document by position."""
+    span_rel, doc_exc_off (lists).  Excerpts in document order, inside a document by position.  span_lead / span_tail: the batch as
+    arrays(fill, span_lead, span_tail) hands it over; the outputs are stated at the caller's indexes: exc_span_off absolute,
+    span_rel of span_lead + spans + span_tail entries, None where the call must leave the entry as it was"""
     out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, doc_exc_off = [], [0], [], [], [], [], [0]
     text = b"\xbf" * case.lead + b"".join(case.docs)
-    base, s_base, total = case.lead, 0, 0
+    base, s_base, total = case.lead, span_lead, 0
+    heads = []                                                      # per span: 1 where an excerpt begins (the base mutants' rank)
     pending = None                                                  # the cross_doc mutant: the last excerpt, in blob positions
     for d, (doc, spans) in enumerate(zip(case.docs, case.spans)):
         wins = [window(doc, a, n, case.before, case.after, case.runes, text if mutant == "lead_snap" else None, base) for a, n in spans]
@@ -88,7 +93,11 @@ def expected(case, mutant=None):
             assert mem == list(range(mem[0], mem[0] + len(mem))), "the reference's own premise: an excerpt is a run of spans"
             if mutant == "head_start":
                 S = wins[mem[0]][0]
-            if mutant == "cross_doc" and pending is not None and pending == base + S and exc_doc:
+            # first_from_k: "first span of its document" decided from k, the index behind the base, instead of span_lead + k -- true
+            # only for k == 0 and, by accident, where k equals the absolute span_off[d]: with span_lead == 0 always, else hardly ever
+            glue = mutant == "cross_doc" or (mutant == "first_from_k" and mem[0] == 0 and s_base - span_lead not in (0, s_base))
+            heads += [0 if glue and pending is not None and pending == base + S and exc_doc else 1] + [0] * (len(mem) - 1)
+            if glue and pending is not None and pending == base + S and exc_doc:
                 # glue to the excerpt in front: it ended where this one begins in the blob
                 out.append(doc[S:E])
                 total += E - S
@@ -110,6 +119,22 @@ def expected(case, mutant=None):
         s_base += len(spans)
         doc_exc_off.append(len(exc_doc))
     exc_span_off.append(s_base)
+    n = s_base - span_lead
+    assert len(heads) == len(span_rel) == n
+    if mutant == "rel_at_k":                                        # the parallel output written at k instead of span_lead + k
+        span_rel = span_rel + [None] * (span_lead + span_tail)
+    else:
+        span_rel = [None] * span_lead + span_rel + [None] * span_tail
+    if mutant == "eso_rebased":                                     # exc_span_off counted from the batch's first span
+        exc_span_off = [v - span_lead for v in exc_span_off]
+    if mutant == "deo_at_abs":                                      # the excerpts in front of span span_off[d], not span_off[d] - span_lead
+        rank, so = [0], span_lead
+        for h in heads:
+            rank.append(rank[-1] + h)
+        doc_exc_off = []
+        for spans in [[]] + case.spans:
+            so += len(spans)
+            doc_exc_off.append(rank[min(so, n)])
     return {"n_exc": len(exc_doc), "total": total, "out": b"".join(out), "exc_off": exc_off, "exc_doc": exc_doc, "exc_start": exc_start,
             "exc_span_off": exc_span_off, "span_rel": span_rel, "doc_exc_off": doc_exc_off}
 
@@ -117,12 +142,14 @@ def expected(case, mutant=None):
 ARRAYS = ("exc_off", "exc_doc", "exc_start", "exc_span_off", "span_rel", "doc_exc_off")
 
 
-def same(got, want):
-    """None, or what differs first.  got: a dict with numpy arrays cut to their sizes and out as bytes"""
+def same(got, want, untouched=None):
+    """None, or what differs first.  got: a dict with numpy arrays cut to their sizes and out as bytes.  untouched: the value an entry
+    of span_rel holds where the reference says None (the call must leave it alone)"""
     if (got["n_exc"], got["total"]) != (want["n_exc"], want["total"]):
         return "n_exc, total: got %r, want %r" % ((got["n_exc"], got["total"]), (want["n_exc"], want["total"]))
     for k in ARRAYS:
-        g, w = np.asarray(got[k]).astype(np.int64), np.asarray(want[k], dtype=np.int64)
+        w = [untouched if v is None else v for v in want[k]] if k == "span_rel" else want[k]
+        g, w = np.asarray(got[k]).astype(np.int64), np.asarray(w, dtype=np.int64)
         if g.shape != w.shape:
             return "%s: %d entries, want %d" % (k, g.size, w.size)
         if not np.array_equal(g, w):
@@ -262,20 +289,32 @@ def random_cases(n=60, seed=2024):
 
 
 MUTANTS = ("no_touch", "cross_doc", "lead_snap", "head_start")
+# wrong readings of the span base that only span_off[0] != 0 tells apart: the parallel output written at k instead of s0 + k;
+# exc_span_off rebased to 0; "first span of its document" decided from k; doc_exc_off read at span_off[d] instead of span_off[d] - s0
+BASE_MUTANTS = ("rel_at_k", "eso_rebased", "first_from_k", "deo_at_abs")
 
 
-def assert_not_vacuous(tile, trip):
-    """every mutant of the reference differs from the reference on some fixed case: the cases can tell them apart"""
+def assert_not_vacuous(tile, trip, span_lead=1, span_tail=1):
+    """every mutant of the reference differs from the reference on some fixed case: the cases can tell them apart.  The base mutants
+    are the reference itself on every fixed case handed over with span_off[0] == 0 -- that is the gap -- and differ on some fixed
+    case handed over behind span_lead entries.  Returns {mutant: the names of the fixed cases that catch it}"""
+    small = [c for c in fixed_cases(tile, trip) if len(c.docs) < 500 and sum(map(len, c.spans)) < 2000]
+    told = {}
     for m in MUTANTS:
-        told = [c.name for c in fixed_cases(tile, trip) if len(c.docs) < 500 and sum(map(len, c.spans)) < 2000 and _differs(c, m)]
-        assert told, "no fixed case tells the mutant %r from the contract" % m
-    return True
+        told[m] = [c.name for c in small if _differs(c, m)]
+        assert told[m], "no fixed case tells the mutant %r from the contract" % m
+    for m in BASE_MUTANTS:
+        blind = [c.name for c in small if _differs(c, m)]
+        assert not blind, "the mutant %r shows without a span base on %r: it is no base mutant" % (m, blind)
+        told[m] = [c.name for c in small if _differs(c, m, span_lead, span_tail)]
+        assert told[m], "no fixed case behind a span base of %d tells the mutant %r from the contract" % (span_lead, m)
+    return told
 
 
-def _differs(case, mutant):
+def _differs(case, mutant, span_lead=0, span_tail=0):
     try:
-        got = expected(case, mutant)
+        got = expected(case, mutant, span_lead, span_tail)
     except (AssertionError, IndexError):                            # (the mutant breaks the reference's own premises: it differs)
         return True
-    want = expected(case)
+    want = expected(case, None, span_lead, span_tail)
     return any(got[k] != want[k] for k in want)

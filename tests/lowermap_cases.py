@@ -94,27 +94,66 @@ def map_spans(doc, start, length):
     return s_start, s_len
 
 
-def expected(docs, spans):
-    """spans: per document a (start, length) pair of arrays -> (span_off u64, start u32, len u32) mapped, or None when refused"""
-    so = np.zeros(len(docs) + 1, np.uint64)
-    st, ln = [], []
+FULL = 0xFFFFFFFF
+# wrong readings of the span base that only span_off[0] != 0 tells apart: the mapped span written at k instead of s0 + k; the limit
+# of gft_map_spans_limit taken as a count behind s0 instead of an index into the caller's arrays
+BASE_MUTANTS = ("mapped_at_k", "limit_relative")
+
+
+def expected(docs, spans, span_lead=0, span_tail=0, limit=None, mutant=None):
+    """spans: per document a (start, length) pair of arrays -> (span_off u64, start u32, len u32) mapped, or None when refused.
+    span_lead / span_tail: the batch as flat(spans, span_lead, span_tail) hands it over; the arrays are stated at the caller's
+    indexes, and an entry outside [span_off[0], span_off[n_docs]) keeps what flat() put there.  limit: only the spans at the
+    caller's indexes below it are mapped (gft_map_spans_limit); the others keep their lowered values and are not judged"""
+    so, st, ln = flat(spans, span_lead, span_tail)
+    s0, end = int(so[0]), int(so[-1])
+    if limit is not None:
+        end = min(end, s0 + limit) if mutant == "limit_relative" else min(end, max(limit, s0))
+    new_st, new_ln = st.copy(), ln.copy()
     for d, (doc, (s, n)) in enumerate(zip(docs, spans)):
-        got = map_spans(doc, s, n)
+        lo = int(so[d])
+        k = max(0, min(len(s), end - lo))                           # the spans of this document below the limit
+        got = map_spans(doc, np.asarray(s)[:k], np.asarray(n)[:k])
         if got is None:
             return None
-        so[d + 1] = so[d] + np.uint64(len(got[0]))
-        st.append(got[0]); ln.append(got[1])
-    cat = lambda xs: np.concatenate(xs).astype(np.uint32) if xs else np.zeros(0, np.uint32)   # noqa: E731
-    return so, cat(st), cat(ln)
+        at = lo - s0 if mutant == "mapped_at_k" else lo
+        new_st[at:at + k], new_ln[at:at + k] = got[0].astype(np.uint32), got[1].astype(np.uint32)
+    return so, new_st, new_ln
 
 
-def flat(spans):
-    """the lowered spans as the arrays the calls take: (span_off u64 [n + 1], start u32, len u32)"""
-    so = np.zeros(len(spans) + 1, np.uint64)
+def flat(spans, span_lead=0, span_tail=0):
+    """the lowered spans as the arrays the calls take: (span_off u64 [n + 1], start u32, len u32).  span_lead / span_tail: entries in
+    front of the batch's spans (span_off[0] = span_lead) and behind them; they hold FULL, FULL -- a span the call would refuse if
+    it read it"""
+    so = np.full(len(spans) + 1, span_lead, np.uint64)
     if spans:
-        so[1:] = np.cumsum([len(s) for s, _ in spans], dtype=np.uint64)
-    cat = lambda xs: np.concatenate([np.asarray(x, np.int64) for x in xs]).astype(np.uint32) if xs else np.zeros(0, np.uint32)   # noqa: E731
-    return so, cat([s for s, _ in spans]), cat([n for _, n in spans])
+        so[1:] = span_lead + np.cumsum([len(s) for s, _ in spans], dtype=np.uint64)
+    pad = lambda k: [np.full(k, FULL, np.int64)]                    # noqa: E731
+    cat = lambda xs: np.concatenate([np.asarray(x, np.int64) for x in xs]).astype(np.uint32)   # noqa: E731
+    return so, cat(pad(span_lead) + [s for s, _ in spans] + pad(span_tail)), cat(pad(span_lead) + [n for _, n in spans] + pad(span_tail))
+
+
+def base_docs():
+    """a small batch whose spans move and change length under the map: what assert_not_vacuous and the tests of runs use"""
+    docs = ["CAFÉ İK one".encode(), b"", "İİ two Ⱥ Ⱥ".encode(), b"plain", b"three \xff\xff K".replace(b"K", "\u212a".encode()), "Ⱥ".encode() * 9]
+    return docs, [every_byte(d, n_random=12, seed=i) if i != 3 else (np.zeros(0, np.int64), np.zeros(0, np.int64)) for i, d in enumerate(docs)]
+
+
+def assert_not_vacuous(span_lead=1, span_tail=1):
+    """the base mutants are the reference itself with span_off[0] == 0 -- that is the gap -- and differ behind span_lead entries, on
+    the batch of base_docs(); the limit at every index from 0 to past the end.  Returns {mutant: the (span_lead, limit) that catch it}"""
+    docs, spans = base_docs()
+    n = sum(len(s) for s, _ in spans)
+    told = {}
+    for m in BASE_MUTANTS:
+        limits = [None] if m == "mapped_at_k" else [0, 1, n // 2, n, n + 1, n + span_lead, n + span_lead + 5]
+        differs = lambda lead, tail, lim: any(not np.array_equal(a, b) for a, b in zip(expected(docs, spans, lead, tail, lim, m),   # noqa: E731
+                                                                                       expected(docs, spans, lead, tail, lim)))
+        blind = [lim for lim in limits if differs(0, 0, lim)]
+        assert not blind, "the mutant %r shows without a span base at the limits %r" % (m, blind)
+        told[m] = [(span_lead, lim) for lim in limits if differs(span_lead, span_tail, lim)]
+        assert told[m], "a span base of %d does not tell the mutant %r from the contract" % (span_lead, m)
+    return told
 
 
 def every_byte(doc, n_random=200, seed=1):

@@ -9,6 +9,7 @@ import functools
 import numpy as np
 
 MARK_MAX = 255
+FULL = 0xFFFFFFFF
 CHUNK, TRIP, TILE = 16, 1024, 4096                  # the copy's geometry as the header states it (checked against mark_shape by the tests)
 
 
@@ -26,19 +27,21 @@ class Case:
             setattr(c, k, v)
         return c
 
-    def arrays(self, fill=0x00):
-        """(blob uint8, doc_off, span_off uint64, start, len uint32): the lead bytes hold `fill`"""
+    def arrays(self, fill=0x00, span_lead=0, span_tail=0):
+        """(blob uint8, doc_off, span_off uint64, start, len uint32): the lead bytes hold `fill`.  span_lead / span_tail: entries of
+        the span arrays in front of the batch's spans (span_off[0] = span_lead) and behind them; they hold FULL, FULL -- a span
+        every call would refuse if it read it"""
         blob = bytes([fill]) * self.lead + b"".join(self.docs)
         off = np.zeros(len(self.docs) + 1, dtype=np.uint64)
         off[0] = self.lead
         if self.docs:
             off[1:] = self.lead + np.cumsum([len(d) for d in self.docs], dtype=np.uint64)
-        so = np.zeros(len(self.docs) + 1, dtype=np.uint64)
+        so = np.full(len(self.docs) + 1, span_lead, dtype=np.uint64)
         if self.docs:
-            so[1:] = np.cumsum([len(s) for s in self.spans], dtype=np.uint64)
+            so[1:] = span_lead + np.cumsum([len(s) for s in self.spans], dtype=np.uint64)
         flat = [x for s in self.spans for x in s]
-        st = np.array([a for a, _ in flat], dtype=np.uint32)
-        ln = np.array([b for _, b in flat], dtype=np.uint32)
+        st = np.array([FULL] * span_lead + [a for a, _ in flat] + [FULL] * span_tail, dtype=np.uint32)
+        ln = np.array([FULL] * span_lead + [b for _, b in flat] + [FULL] * span_tail, dtype=np.uint32)
         return np.frombuffer(blob, dtype=np.uint8), off, so, st, ln
 
 
@@ -74,15 +77,27 @@ def mark_doc(doc, spans, open, close, mutant=None):
     return pieces, new, comps
 
 
-def expected(case, mutant=None):
-    """a dict of what the call hands back under an exact cap: n_runs, total, out (bytes), out_off, span_new, doc_run_off (lists)"""
+def expected(case, mutant=None, span_lead=0, span_tail=0):
+    """a dict of what the call hands back under an exact cap: n_runs, total, out (bytes), out_off, span_new, doc_run_off (lists).
+    span_lead / span_tail: the batch as arrays(fill, span_lead, span_tail) hands it over; span_new is stated at the caller's
+    indexes, span_lead + spans + span_tail entries, None where the call must leave the entry as it was"""
     out, out_off, span_new, doc_run_off = [], [0], [], [0]
     n_runs, total, open_end = 0, 0, False
+    heads, k = [], 0                                                # per span: 1 where a run begins (the base mutants' rank)
     for doc, spans in zip(case.docs, case.spans):
         pieces, new, comps = mark_doc(doc, spans, case.open, case.close, mutant)
+        firsts, seen = [S for S, _ in comps], set()
+        for a, _ in spans:
+            r = bisect.bisect_right(firsts, a) - 1
+            heads.append(0 if r in seen else 1)
+            seen.add(r)
         if mutant == "batch_rank":
             new = [v + n_runs * (len(case.open) + len(case.close)) for v in new]
-        if mutant == "cross_doc" and open_end and comps and comps[0][0] == 0 and comps[0][1] > 0:
+        # first_from_k: "first span of its document" decided from k, the index behind the base, instead of span_lead + k -- true only
+        # for k == 0 and, by accident, where k equals the absolute span_off[d]: with span_lead == 0 always, else hardly ever
+        glue = mutant == "cross_doc" or (mutant == "first_from_k" and k not in (0, span_lead + k))
+        k += len(spans)
+        if glue and open_end and comps and comps[0][0] == 0 and comps[0][1] > 0:
             # the run in front ended at its document's end and this one begins at its document's start: one run across the border
             assert out[-2] == case.close and pieces[1] == case.open
             total -= len(out[-2]) + len(pieces[1])
@@ -94,6 +109,19 @@ def expected(case, mutant=None):
         total += sum(len(p) for p in pieces)
         out_off.append(total)
         doc_run_off.append(n_runs)
+    if mutant == "new_at_k":                                        # the parallel output written at k instead of span_lead + k
+        span_new = span_new + [None] * (span_lead + span_tail)
+    else:
+        span_new = [None] * span_lead + span_new + [None] * span_tail
+    if mutant == "dro_at_abs":                                      # the runs in front of span span_off[d], not span_off[d] - span_lead
+        rank, so, both = [0], span_lead, len(case.open) + len(case.close)
+        for h in heads:
+            rank.append(rank[-1] + h)
+        was, doc_run_off = doc_run_off, []
+        for spans in [[]] + case.spans:
+            so += len(spans)
+            doc_run_off.append(rank[min(so, len(heads))])
+        out_off = [o + (r - w) * both for o, r, w in zip(out_off, doc_run_off, was)]
     return {"n_runs": n_runs, "total": total, "out": b"".join(out), "out_off": out_off, "span_new": span_new, "doc_run_off": doc_run_off}
 
 
@@ -202,13 +230,24 @@ def random_cases(seed, n_cases=40):
 
 
 MUTANTS = ("no_touch", "close_early", "batch_rank", "empty_run_dropped", "cross_doc")
+# wrong readings of the span base that only span_off[0] != 0 tells apart: span_new written at k instead of s0 + k; "first span of its
+# document" decided from k; doc_run_off (and out_off with it) read at span_off[d] instead of span_off[d] - s0
+BASE_MUTANTS = ("new_at_k", "first_from_k", "dro_at_abs")
 
 
 @functools.lru_cache(maxsize=None)
-def assert_not_vacuous():
-    """every mutant of the reference is told apart from the reference by some fixed case"""
+def assert_not_vacuous(span_lead=1, span_tail=1):
+    """every mutant of the reference is told apart from the reference by some fixed case.  The base mutants are the reference itself
+    on every fixed case handed over with span_off[0] == 0 -- that is the gap -- and differ on some fixed case handed over behind
+    span_lead entries.  Returns {mutant: the names of the fixed cases that catch it}"""
     cases = fixed_cases()
+    told = {}
     for mutant in MUTANTS:
-        told = [c.name for c in cases if not same(expected(c, mutant), expected(c))]
-        assert told, "no fixed case tells the mutant %r from the contract" % mutant
-    return True
+        told[mutant] = [c.name for c in cases if not same(expected(c, mutant), expected(c))]
+        assert told[mutant], "no fixed case tells the mutant %r from the contract" % mutant
+    for mutant in BASE_MUTANTS:
+        blind = [c.name for c in cases if not same(expected(c, mutant), expected(c))]
+        assert not blind, "the mutant %r shows without a span base on %r: it is no base mutant" % (mutant, blind)
+        told[mutant] = [c.name for c in cases if not same(expected(c, mutant, span_lead, span_tail), expected(c, None, span_lead, span_tail))]
+        assert told[mutant], "no fixed case behind a span base of %d tells the mutant %r from the contract" % (span_lead, mutant)
+    return told

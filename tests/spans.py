@@ -297,34 +297,46 @@ def expected():
 FillCase = collections.namedtuple("FillCase", "name blob doc_off span_off start length mask ok")
 
 
-def redact_reference(f):
-    """the masked bytes, by slicing a bytearray"""
+def redact_reference(f, mutant=None):
+    """the masked bytes, by slicing a bytearray; the spans are read at the caller's indexes, [span_off[0], span_off[n_docs]).  None:
+    a span that was read reaches past its document (the call refuses).  mutant "span_at_k": the spans read at k, the index behind
+    the base, instead of span_off[0] + k"""
     out = bytearray(f.blob.tobytes())
+    s0 = int(f.span_off[0])
     for d in range(len(f.doc_off) - 1):
         for s in range(int(f.span_off[d]), int(f.span_off[d + 1])):
-            a = int(f.doc_off[d]) + int(f.start[s])
-            out[a:a + int(f.length[s])] = bytes([f.mask]) * int(f.length[s])
+            at = s - s0 if mutant == "span_at_k" else s
+            a, n = int(f.doc_off[d]) + int(f.start[at]), int(f.length[at])
+            if a + n > int(f.doc_off[d + 1]):
+                return None
+            out[a:a + n] = bytes([f.mask]) * n
     return bytes(out)
 
 
-def fill_case(name, doc_lens, spans, mask=0x2A, seed=1, lead=0, ok=True):
-    """spans: per document a list of (start, len)"""
+FULL = 0xFFFFFFFF
+
+
+def fill_case(name, doc_lens, spans, mask=0x2A, seed=1, lead=0, ok=True, span_lead=0, span_tail=0):
+    """spans: per document a list of (start, len).  span_lead / span_tail: entries of the span arrays in front of the batch's spans
+    (span_off[0] = span_lead) and behind them; they hold FULL, FULL -- a span the call would refuse if it read it"""
     rng = np.random.default_rng(seed)
     off = np.zeros(len(doc_lens) + 1, dtype=np.uint64)
     off[0] = lead
     off[1:] = lead + np.cumsum(np.asarray(doc_lens, dtype=np.uint64))
     blob = rng.integers(0, 256, int(off[-1]) + 64, dtype=np.uint8)
     blob[blob == mask] ^= 0x55                                          # (a masked byte is then one the fill wrote)
-    so = np.zeros(len(doc_lens) + 1, dtype=np.uint64)
-    so[1:] = np.cumsum([len(s) for s in spans], dtype=np.uint64)
-    flat = [p for s in spans for p in s]
+    so = np.full(len(doc_lens) + 1, span_lead, dtype=np.uint64)
+    so[1:] = span_lead + np.cumsum([len(s) for s in spans], dtype=np.uint64)
+    flat = [(FULL, FULL)] * span_lead + [p for s in spans for p in s] + [(FULL, FULL)] * span_tail
     return FillCase(name, blob, off, so, np.asarray([p[0] for p in flat], dtype=np.uint32), np.asarray([p[1] for p in flat], dtype=np.uint32), mask, ok)
 
 
 @functools.lru_cache(maxsize=None)
-def fill_cases():
+def fill_cases(span_lead=0, span_tail=0):
+    """the same batches -- texts, spans, names -- whatever the base: only the span arrays' placement differs"""
     _, S = spans_shape()
     big = 7424
+    fill_case = functools.partial(globals()["fill_case"], span_lead=span_lead, span_tail=span_tail)
     c = [fill_case("spans of 1, 63, 64, 65 and 7 424 bytes", [9000], [[(3, 1), (10, 63), (100, 64), (200, 65), (1000, big)]], seed=2, lead=5),
          fill_case("a span of 7 424 bytes among one-byte spans", [50, big + 2, 50], [[(k, 1) for k in range(0, 50, 3)], [(1, big)], [(49, 1), (0, 1)]], seed=3),
          fill_case("overlapping, nested, identical and adjacent spans", [200],
@@ -367,4 +379,16 @@ def assert_not_vacuous():
     assert idx, "no case would notice a walk that ignores row_idx"
     some = [c.name for c in cases if 0 < exp[c.name][0] < len(matches(c)[1])]
     assert len(some) > 20, len(some)
+    assert_fill_not_vacuous()
     return nots, tails, idx, some
+
+
+def assert_fill_not_vacuous(span_lead=1, span_tail=1):
+    """the redaction that reads its spans at k instead of span_off[0] + k is the reference itself on every fill case handed over with
+    span_off[0] == 0 -- that is the gap -- and differs (masks other bytes, or is refused over the poison in front) on some fill case
+    handed over behind span_lead entries.  Returns the names of those"""
+    blind = [f.name for f in fill_cases() if f.ok and redact_reference(f, "span_at_k") != redact_reference(f)]
+    assert not blind, "the mutant span_at_k shows without a span base on %r" % blind
+    told = [f.name for f in fill_cases(span_lead, span_tail) if f.ok and redact_reference(f, "span_at_k") != redact_reference(f)]
+    assert told, "no fill case behind a span base of %d tells the mutant span_at_k from the contract" % span_lead
+    return told

@@ -10,7 +10,10 @@
 // the output arrays of cap entries --, so a read outside them (a snap that leaves its document at the blob's ends) or a store past
 // a cap is an error of the sanitizer.  N seeded random rounds, each: a random batch (empty documents, documents without spans,
 // continuation bytes in runs of up to five, zero-length spans, ends ascending), random before / after (0 and 0xFFFFFFFF among
-// them), the flag on or off; every few rounds more spans than a tile, and once more than a carry trip's.  The brute force marks,
+// them), the flag on or off; every few rounds more spans than a tile, and once more than a carry trip's.  Every round draws a
+// span base s0, 0 among the values: span_off[0] = s0, the span arrays are blocks of exactly s0 + n entries whose first s0 hold a
+// span no document could hold, span_rel is a block of s0 + n entries too, and the brute force is indexed the same way -- a walk
+// that dropped a base reads the poison or stores where the brute force left the pattern.  The brute force marks,
 // per document, the closed interval of every window on a grid of whole and half positions -- touching windows share a point, a
 // gap of one byte leaves one unmarked -- and reads the excerpts off the runs of marked points.  The walk runs under exact caps,
 // count only, and caps that cut the list and the bytes; then one span's end is put in front of its neighbour's and one span past
@@ -45,7 +48,10 @@ struct Batch {
     std::vector<uint64_t> doc_off, span_off;
     std::vector<uint32_t> start, len;
     uint32_t before, after, flags;
+    uint64_t s0 = 0;               // span_off[0]: the entries [0, s0) of start / len are poison
 };
+
+constexpr uint32_t kPoison = 0xFFFFFFFFu, kUntouched = 0xA5A5A5A5u;
 
 struct Result {
     std::vector<uint8_t> out;
@@ -61,7 +67,7 @@ Result brute(const Batch& B) {
     const uint64_t n_docs = B.doc_off.size() - 1;
     R.exc_off.push_back(0);
     R.doc_exc_off.push_back(0);
-    R.span_rel.assign(B.start.size(), 0);
+    R.span_rel.assign(B.start.size(), kUntouched);                 // (the entries below s0 are never written)
     for (uint64_t d = 0; d < n_docs; d++) {
         const uint8_t* doc = B.text.data() + B.doc_off[d];
         const uint64_t L = B.doc_off[d + 1] - B.doc_off[d];
@@ -115,8 +121,12 @@ Batch random_batch(uint64_t n_docs, uint64_t max_len, uint64_t max_spans, uint64
     B.before = reach[rnd(9)];
     B.after = reach[rnd(9)];
     B.flags = rnd(3) ? GFT_EXCERPT_RUNES : 0;
+    static const uint64_t base[] = {0, 0, 1, 2, kExcTile - 1, kExcTile, kExcTile + 1, 3 * kExcTile + 7};
+    B.s0 = rnd(9) < 8 ? base[rnd(8)] : rnd(1000);
+    B.start.assign(B.s0, kPoison);
+    B.len.assign(B.s0, kPoison);
     B.doc_off.push_back(0);
-    B.span_off.push_back(0);
+    B.span_off.push_back(B.s0);
     for (uint64_t d = 0; d < n_docs; d++) {
         const uint64_t L = rnd(5) ? rnd(max_len + 1) : 0;
         for (uint64_t i = 0; i < L; i++) {
@@ -154,6 +164,7 @@ void check(const Batch& B, const Result& want, uint64_t cap_bytes, uint64_t cap_
     std::unique_ptr<uint64_t[]> exc_off(new uint64_t[cap_exc + 1]), exc_doc(new uint64_t[cap_exc ? cap_exc : 1]), exc_span_off(new uint64_t[cap_exc + 1]),
         doc_exc_off(new uint64_t[n_docs + 1]);
     std::unique_ptr<uint32_t[]> exc_start(new uint32_t[cap_exc ? cap_exc : 1]), span_rel(new uint32_t[B.start.size() ? B.start.size() : 1]);
+    for (size_t s = 0; s < B.start.size(); s++) span_rel[s] = kUntouched;
     uint64_t got_m = ~0ull, got_total = ~0ull;
     const int rc = excerpt_spans_host(text.get(), doc_off.get(), n_docs, span_off.get(), start.get(), len.get(), B.before, B.after, B.flags,
                                       cap_bytes ? out.get() : nullptr, cap_bytes, exc_off.get(), cap_exc ? exc_doc.get() : nullptr,
@@ -214,7 +225,7 @@ int main(int argc, char** argv) {
         }
         const Result want = brute(B);
         const uint64_t m = want.exc_doc.size(), total = want.out.size();
-        if (round == 7) expect(B.start.size() > (uint64_t)kExcTile * kExcCarryTiles, "round 7 is to pass a carry trip", round);
+        if (round == 7) expect(B.start.size() - B.s0 > (uint64_t)kExcTile * kExcCarryTiles, "round 7 is to pass a carry trip", round);
         check(B, want, total, m, round);
         check(B, want, 0, 0, round);
         if (m) check(B, want, rnd(total + 1), rnd(m), round);
@@ -237,6 +248,11 @@ int main(int argc, char** argv) {
                 check_refused(bad, round);
                 break;
             }
+        }
+        if (B.s0) {                                                                                   // span_off[n_docs] < span_off[0]
+            Batch bad = B;
+            bad.span_off.back() = B.s0 - 1;
+            check_refused(bad, round);
         }
     }
     if (fails) {

@@ -14,7 +14,9 @@
 // a longer document, a non-zero doc_off[0] behind lead bytes that would complete a rune.  Then N seeded random rounds.  Each
 // batch: EVERY single-byte span of every lowered document, the whole-document span, empty spans (at the lowered end too) and
 // random ones, mapped by the walk and by the decoder; the same with a limit that leaves the tail of the arrays alone; and one span
-// made a byte too long, which must be refused with both arrays untouched.
+// made a byte too long, which must be refused with both arrays untouched.  Every batch draws a span base s0, 0 among the values:
+// span_off[0] = s0, the span arrays are blocks of exactly s0 + n entries whose first s0 hold a span no document could hold and
+// must come back as they were, the decoder's answer is indexed the same way, and the limit is an index into these arrays.
 // Exit code 0: walk and decoder agree everywhere.
 #include <cstdio>
 #include <cstdlib>
@@ -88,8 +90,10 @@ void check_batch(const Batch& bt, const char* what) {
         off[d + 1] = text.size();
     }
     text.insert(text.end(), 64, 0x89);                              // slack that would complete a rune
-    std::vector<uint64_t> so(n_docs + 1, 0);
-    std::vector<uint32_t> st, ln, want_st, want_ln;
+    static const uint64_t base[] = {0, 0, 1, 2, kMapTile - 1, kMapTile, kMapTile + 1, 3 * kMapTile + 5};
+    const uint64_t s0 = rnd(9) < 8 ? base[rnd(8)] : rnd(600);
+    std::vector<uint64_t> so(n_docs + 1, s0);
+    std::vector<uint32_t> st(s0, 0xFFFFFFFFu), ln(st), want_st(st), want_ln(st);
     for (uint64_t d = 0; d < n_docs; d++) {
         uint32_t B = 0;
         const std::vector<Rune> rs = decode(bt.docs[d], &B);
@@ -115,7 +119,7 @@ void check_batch(const Batch& bt, const char* what) {
         }
         so[d + 1] = st.size();
     }
-    const uint64_t n = st.size();
+    const uint64_t n = st.size() - s0, end = st.size();
     spans_seen += n;
     auto p_text = exact(text);
     auto p_off = exact(off);
@@ -130,7 +134,7 @@ void check_batch(const Batch& bt, const char* what) {
     };
     std::vector<uint32_t> ga, gb;
     if (run(st, ln, ~0ull, ga, gb) != GFT_OK || ga != want_st || gb != want_ln) {
-        for (uint64_t k = 0; k < n; k++)
+        for (uint64_t k = 0; k < end && k < ga.size(); k++)
             if (ga[k] != want_st[k] || gb[k] != want_ln[k]) {
                 fprintf(stderr, "%s: span %llu (%u, %u): walk (%u, %u), decoder (%u, %u)\n", what, (unsigned long long)k, st[k], ln[k], ga[k], gb[k],
                         want_st[k], want_ln[k]);
@@ -141,9 +145,9 @@ void check_batch(const Batch& bt, const char* what) {
     }
     if (!n) return;
     // a limit: the entries at and past it are left alone
-    const uint64_t limit = rnd(n + 1);
+    const uint64_t limit = rnd(end + 2);                            // (below s0, inside, at the end and past it)
     if (run(st, ln, limit, ga, gb) != GFT_OK) { fprintf(stderr, "%s: refused under a limit\n", what); fails++; return; }
-    for (uint64_t k = 0; k < n; k++) {
+    for (uint64_t k = 0; k < end; k++) {
         const bool ok = k < limit ? ga[k] == want_st[k] && gb[k] == want_ln[k] : ga[k] == st[k] && gb[k] == ln[k];
         if (!ok) { fprintf(stderr, "%s: limit %llu, entry %llu\n", what, (unsigned long long)limit, (unsigned long long)k); fails++; return; }
     }
@@ -157,6 +161,17 @@ void check_batch(const Batch& bt, const char* what) {
         bad_ln[k] = B - st[k] + 1;
         if (run(st, bad_ln, ~0ull, ga, gb) != GFT_E_INVALID || ga != st || gb != bad_ln) {
             fprintf(stderr, "%s: a span past the lowered end was taken, or the refusal wrote\n", what);
+            fails++;
+        }
+    }
+    if (s0) {                                                       // span_off[n_docs] < span_off[0]
+        std::vector<uint64_t> down(so);
+        down.back() = s0 - 1;
+        auto p_down = exact(down);
+        auto pa = exact(st), pb = exact(ln);
+        const int rc = lowermap_host(p_text.get(), p_off.get(), n_docs, p_down.get(), pa.get(), pb.get(), ~0ull);
+        if (rc != GFT_E_INVALID || memcmp(pa.get(), st.data(), end * 4) || memcmp(pb.get(), ln.data(), end * 4)) {
+            fprintf(stderr, "%s: span offsets that descend were taken, or the refusal wrote\n", what);
             fails++;
         }
     }

@@ -10,7 +10,9 @@
 // the markers, the output of cap bytes --, so a read outside them or a store past the cap is an error of the sanitizer.  N seeded
 // random rounds, each: a random batch (empty documents, documents without spans, zero-length spans, spans that nest, repeat and
 // touch, ends ascending, lead bytes in front of the first document), random markers of 0 .. GFT_MARK_MAX bytes, the output at a
-// random residue of the 16-byte grid; every few rounds more spans than a tile, and once more than a carry trip's.  The brute force
+// random residue of the 16-byte grid; every few rounds more spans than a tile, and once more than a carry trip's.  Every round
+// draws a span base s0, 0 among the values: span_off[0] = s0, the span arrays and span_new are blocks of exactly s0 + n entries,
+// the first s0 spans are poison, and the brute force is indexed the same way.  The brute force
 // paints, per document, a grid of whole and half positions -- touching spans share a point, a gap of one byte leaves one
 // unpainted --, reads the runs off the painted stretches and splices byte by byte.  The walk runs under an exact cap, count
 // only, and caps that cut; then one span's end is put in front of its neighbour's and one span past its document's end, which must
@@ -44,7 +46,10 @@ struct Batch {
     std::vector<uint8_t> text, open, close;
     std::vector<uint64_t> doc_off, span_off;
     std::vector<uint32_t> start, len;
+    uint64_t s0 = 0;               // span_off[0]: the entries [0, s0) of start / len are poison
 };
+
+constexpr uint32_t kPoison = 0xFFFFFFFFu, kUntouched = 0xA5A5A5A5u;
 
 struct Result {
     std::vector<uint8_t> out;
@@ -58,7 +63,7 @@ Result brute(const Batch& B) {
     const uint64_t n_docs = B.doc_off.size() - 1;
     R.out_off.push_back(0);
     R.doc_run_off.push_back(0);
-    R.span_new.assign(B.start.size(), 0);
+    R.span_new.assign(B.start.size(), kUntouched);                 // (the entries below s0 are never written)
     uint64_t runs = 0;
     for (uint64_t d = 0; d < n_docs; d++) {
         const uint8_t* doc = B.text.data() + B.doc_off[d];
@@ -97,7 +102,11 @@ Batch random_batch(uint64_t want_spans) {
     const uint64_t lead = rnd(20);
     B.text.assign(lead, 0xEE);
     B.doc_off.push_back(lead);
-    B.span_off.push_back(0);
+    static const uint64_t base[] = {0, 0, 1, 2, kExcTile - 1, kExcTile, kExcTile + 1, 3 * kExcTile + 7};
+    B.s0 = rnd(9) < 8 ? base[rnd(8)] : rnd(1000);
+    B.start.assign(B.s0, kPoison);
+    B.len.assign(B.s0, kPoison);
+    B.span_off.push_back(B.s0);
     for (uint64_t d = 0; d < n_docs; d++) {
         const uint64_t L = want_spans ? want_spans + rnd(50) : (rnd(4) ? rnd(150) : 0);
         for (uint64_t i = 0; i < L; i++) B.text.push_back((uint8_t)(1 + rnd(255)));
@@ -141,7 +150,7 @@ int walk(const Batch& B, uint64_t cap, uint32_t shift, Result& R, uint64_t& runs
     memset(out.get(), pat, cap + shift);
     R.out_off.assign(n_docs + 1, 0xA5A5A5A5A5A5A5A5ull);
     R.doc_run_off.assign(n_docs + 1, 0xA5A5A5A5A5A5A5A5ull);
-    R.span_new.assign(B.start.size(), 0xA5A5A5A5u);
+    R.span_new.assign(B.start.size(), kUntouched);
     auto oo = exact(R.out_off);
     auto dro = exact(R.doc_run_off);
     auto sn = exact(R.span_new);
@@ -198,6 +207,14 @@ void one_round(uint64_t round, uint64_t want_spans) {
         expect(std::all_of(X.out.begin(), X.out.end(), [](uint8_t v) { return v == 0xA5; }), "past the end: text written", round);
         expect(std::all_of(X.doc_run_off.begin(), X.doc_run_off.end(), [](uint64_t v) { return v == 0xA5A5A5A5A5A5A5A5ull; }), "past the end: offsets written", round);
         break;
+    }
+    if (B.s0 && B.doc_off.size() > 1) {                              // span_off[n_docs] < span_off[0]
+        Batch C = B;
+        C.span_off.back() = B.s0 - 1;
+        Result X;
+        expect(walk(C, total, shift, X, runs, bytes, 0xA5) == GFT_E_INVALID && runs == 0 && bytes == 0, "offsets: not refused", round);
+        expect(std::all_of(X.out.begin(), X.out.end(), [](uint8_t v) { return v == 0xA5; }), "offsets: text written", round);
+        expect(std::all_of(X.span_new.begin(), X.span_new.end(), [](uint32_t v) { return v == kUntouched; }), "offsets: span_new written", round);
     }
 }
 

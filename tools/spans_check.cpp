@@ -12,7 +12,9 @@
 // and compared with a recursive evaluation of the definition; a random match CSR with documents of 0 matches and of more than a
 // match tile, random rows with ones in their tail bits, every kind of row_idx and mask, filtered by the walk under full caps,
 // count only and a cap that cuts the list; the spans of the result, overlapping as they come, masked in a random text by the fill
-// walk and by a byte loop; and one span made a byte too long, which must be refused with the text untouched.
+// walk and by a byte loop; and one span made a byte too long, which must be refused with the text untouched.  The redaction gets
+// its spans behind a span base s0 drawn every round, 0 among the values: span_off[0] = s0, the span arrays are blocks of exactly
+// s0 + n entries whose first s0 hold a span no document could hold, and the byte loop is indexed the same way.
 // Exit code 0: walks and brute force agree everywhere.
 #include <cstdio>
 #include <cstdlib>
@@ -180,14 +182,22 @@ void one_round(int round) {
     for (auto& b : text) b = (uint8_t)rng();
     std::vector<uint8_t> ref = text;
     const uint32_t mask = (uint32_t)rnd(256);
+    // the spans behind a base: [s0, s0 + total) of arrays of exactly s0 + total entries, poison in front
+    static const uint64_t base[] = {0, 0, 1, 2, kSpanTile - 1, kSpanTile, kSpanTile + 1, 3 * kSpanTile + 5};
+    const uint64_t s0 = rnd(9) < 8 ? base[rnd(8)] : rnd(600);
+    std::vector<uint64_t> f_off(r_off);
+    for (auto& o : f_off) o += s0;
+    std::vector<uint32_t> f_start(s0, 0xFFFFFFFFu), f_len(s0, 0xFFFFFFFFu);
+    f_start.insert(f_start.end(), r_start.begin(), r_start.end());
+    f_len.insert(f_len.end(), r_len.begin(), r_len.end());
     for (uint64_t d = 0; d < n_docs; d++)
-        for (uint64_t s = r_off[d]; s < r_off[d + 1]; s++)
-            for (uint32_t j = 0; j < r_len[s]; j++) ref[doff[d] + r_start[s] + j] = (uint8_t)mask;
+        for (uint64_t s = f_off[d]; s < f_off[d + 1]; s++)
+            for (uint32_t j = 0; j < f_len[s]; j++) ref[doff[d] + f_start[s] + j] = (uint8_t)mask;
     auto a_doff = exact(doff);
-    auto a_soff = exact(r_off);
-    auto a_start = exact(r_start);
+    auto a_soff = exact(f_off);
+    auto a_start = exact(f_start);
     {
-        auto a_slen = exact(r_len);
+        auto a_slen = exact(f_len);
         auto t = exact(text);
         CHECK(redact_spans_host(t.get(), a_doff.get(), n_docs, a_soff.get(), a_start.get(), a_slen.get(), mask) == GFT_OK, "the fill was refused");
         CHECK(!memcmp(t.get(), ref.data(), text.size()), "the masked text");
@@ -199,11 +209,21 @@ void one_round(int round) {
         const uint64_t s = rnd(total);
         uint64_t d = 0;
         while (r_off[d + 1] <= s) d++;
-        std::vector<uint32_t> bad = r_len;
-        bad[s] = (uint32_t)(doff[d + 1] - doff[d] - r_start[s] + 1);
+        std::vector<uint32_t> bad = f_len;
+        bad[s0 + s] = (uint32_t)(doff[d + 1] - doff[d] - r_start[s] + 1);
         auto a_bad = exact(bad);
         auto t = exact(text);
         CHECK(redact_spans_host(t.get(), a_doff.get(), n_docs, a_soff.get(), a_start.get(), a_bad.get(), mask) == GFT_E_INVALID, "a span past its document was taken");
+        CHECK(!memcmp(t.get(), text.data(), text.size()), "a refused fill wrote");
+        runs++;
+    }
+    if (s0) {                                                       // span_off[n_docs] < span_off[0]
+        std::vector<uint64_t> down(f_off);
+        down.back() = s0 - 1;
+        auto a_down = exact(down);
+        auto a_slen = exact(f_len);
+        auto t = exact(text);
+        CHECK(redact_spans_host(t.get(), a_doff.get(), n_docs, a_down.get(), a_start.get(), a_slen.get(), mask) == GFT_E_INVALID, "span offsets that descend were taken");
         CHECK(!memcmp(t.get(), text.data(), text.size()), "a refused fill wrote");
         runs++;
     }
