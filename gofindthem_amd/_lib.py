@@ -11,6 +11,7 @@ GFT_E_NOMEM, GFT_E_INTERNAL, GFT_W_NO_RCCL = -7, -8, 1
 GFT_POS_START, GFT_POS_END = 0, 1
 GFT_JSON_OK, GFT_JSON_SYNTAX, GFT_JSON_DEPTH, GFT_JSON_PATH, GFT_JSON_KEY, GFT_JSON_DUP, GFT_JSON_TEXT = range(7)
 GFT_FOLD_ASCII = 1
+GFT_STATS_ACCUMULATE = 1
 GFT_SCAN_UNIQUE = 2
 GFT_POS_RUNES = 4
 OP_UNIT, OP_AND, OP_OR, OP_NOT, OP_INORD = 1, 2, 3, 4, 5
@@ -184,6 +185,13 @@ SYMBOLS = {
     "gft_debug_mark_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_mark_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp,
                                    C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp]),
+    "gft_count_columns_device": (_i, [_vp, _vp, _u64, _u32, _vp, _u32, _vp]),
+    "gft_batch_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),
+    "gft_debug_term_stats": (_i, [_vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp]),
+    "gft_debug_count_columns": (_i, [_vp, _u64, _u32, _vp, _u32, _vp]),
+    "gft_debug_stats_shape": (None, [C.POINTER(_u32)] * 8),
+    "gft_finder_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),
     "gft_debug_lowermap_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_group_process_json_lines": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),

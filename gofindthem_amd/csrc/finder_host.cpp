@@ -637,6 +637,39 @@ Error Finder::MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint6
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                              uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first, int* lowered) {
+    last_code_ = 0;
+    if (lowered) *lowered = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    std::vector<Record> none;
+    Error err = collect(std::string(), false, none);
+    if (!err.empty()) return err;
+    int again = 0;
+    int rc = gft_batch_term_stats_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, flags, doc_base,
+                                         d_occ, d_docs, d_first, &again);
+    if (rc) return fail_gft(rc);
+    if (!again) return "";
+    // as HitSpansDevice: the batch is lowered in full on the device and scanned again from there (nothing was counted so far)
+    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "term statistics of a batch that leaves ASCII need the device ToLower on a single device";
+    }
+    const uint8_t* d_low = nullptr;
+    const uint64_t* d_low_off = nullptr;
+    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
+    if (rc) return fail_gft(rc);
+    rc = gft_batch_term_stats_device(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, flags, doc_base, d_occ, d_docs, d_first,
+                                     nullptr);
+    if (rc) return fail_gft(rc);
+    if (lowered) *lowered = 1;
+    return "";
+}
+
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
     if (!gpu_sub_ || !regexes_.empty()) {
@@ -975,6 +1008,15 @@ int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint
     return finder_ret(f, f->finder->MarkDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
                                                open, open_len, close, close_len, flags, d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, n_runs,
                                                total_bytes, lowered), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,
+                                 const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first,
+                                 int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->TermStatsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, flags, doc_base, d_occ, d_docs, d_first, lowered),
+                      GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

@@ -156,6 +156,10 @@ public:
                      const uint32_t* d_span_len, bool spans_lowered, bool source, const uint8_t* open, uint32_t open_len, const uint8_t* close,
                      uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint32_t* d_span_new,
                      uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes, int* lowered);
+    // gft_batch_term_stats_device on the finder's engine under the case rule of HitSpansDevice: a batch that leaves ASCII is lowered
+    // on the device and counted from there -- *lowered = 1; an accumulating array sees every batch once
+    Error TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                          uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first, int* lowered);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

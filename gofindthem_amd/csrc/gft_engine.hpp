@@ -217,6 +217,11 @@ struct gft_engine {
     // highlight (gft_mark.hip): the run passes work in the excerpt's buffers; the insertion list and the marker block are its own
     struct MarkBufs { DevBuf q, marks; } d_mark;
 
+    // term statistics and column counts (gft_stats.hip): the check pass's flag words, the workgroups' bitset rows for dictionaries
+    // whose bitset leaves LDS, and the span CSR of the kept matches that gft_batch_term_stats_device counts (the starts are what
+    // gft_hit_spans_device asks for with any cap; they are not read)
+    struct StatsBufs { DevBuf ctl, rows, span_off, span_start, span_term; } d_stats;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

@@ -570,6 +570,40 @@ def mark_shape():
     return tuple(int(x.value) for x in v)
 
 
+STATS_SHAPE_FIELDS = ("step_entries", "step_docs", "set_slots", "cache_slots", "large_entries", "bitset_lds_terms", "range_weight", "column_rows")
+
+
+def stats_shape():
+    """the borders of the term statistics' walk as a dict (gft_debug_stats_shape): STATS_SHAPE_FIELDS"""
+    v = [C.c_uint32(0) for _ in STATS_SHAPE_FIELDS]
+    _lib.load().gft_debug_stats_shape(*(C.byref(x) for x in v))
+    return {k: int(x.value) for k, x in zip(STATS_SHAPE_FIELDS, v)}
+
+
+def term_stats_host(off, term, n_terms, occ=None, docs=None, first=None, flags=0, doc_base=0, n_docs=None):
+    """gft_debug_term_stats over host arrays, in place: off uint64 [n_docs + 1], term uint32 (indexed by off's values), occ / docs /
+    first uint64 [n_terms] or None (passed as NULL).  Raises GftError on a refusal; no device needed"""
+    o, t = np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(term, dtype=np.uint32)
+    n_docs = o.size - 1 if n_docs is None else n_docs
+    for a in (occ, docs, first):
+        assert a is None or (a.dtype == np.uint64 and a.flags.c_contiguous)
+    rc = _lib.load().gft_debug_term_stats(_p(o) if o.size else None, _p(t) if t.size else None, n_docs, n_terms, int(flags), int(doc_base),
+                                          _p(occ), _p(docs), _p(first))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_term_stats")
+
+
+def count_columns_host(bitmap, n_rows, n_cols, count, row_idx=None, flags=0):
+    """gft_debug_count_columns over host arrays, in place: bitmap uint32 rows of ceil(n_cols / 32) words, count uint64 [n_cols],
+    row_idx uint64 [n_rows] or None.  Raises GftError on a refusal; no device needed"""
+    bm = np.ascontiguousarray(bitmap, dtype=np.uint32)
+    ri = np.ascontiguousarray(row_idx, dtype=np.uint64) if row_idx is not None else None
+    rc = _lib.load().gft_debug_count_columns(_p(bm) if bm.size else None, n_rows, n_cols, _p(ri) if ri is not None and ri.size else None,
+                                             int(flags), _p(count) if count is not None and count.size else None)
+    if rc != 0:
+        raise GftError(rc, "gft_debug_count_columns")
+
+
 def lowermap_shape():
     """(bytes of a piece, of a wave's trip, of a work unit at most, spans of a wave's tile) (gft_debug_lowermap_shape)"""
     v = [C.c_uint32(0) for _ in range(4)]
@@ -850,6 +884,73 @@ class Engine:
     def mark_shape():
         """(tile_spans, trip_tiles, chunk_bytes, tile_bytes) of the highlight's walk (gft_debug_mark_shape)"""
         return mark_shape()
+
+    # -- term statistics and column counts (csrc/gft_stats.hip) ----------------------------------------------------------------
+    def term_stats_raw(self, d_off_ptr, d_term_ptr, n_docs, n_terms, flags, doc_base, d_occ_ptr, d_docs_ptr, d_first_ptr):
+        """gft_term_stats_device on device pointers as they are (None: NULL); the caller has drained the streams that wrote them"""
+        self._check(self._L.gft_term_stats_device(self._h, d_off_ptr, d_term_ptr, n_docs, n_terms, int(flags), int(doc_base), d_occ_ptr,
+                                                  d_docs_ptr, d_first_ptr))
+
+    def term_stats_device(self, off, term, n_docs, n_terms, occ=None, docs=None, first=None, accumulate=False, doc_base=0):
+        """how often each term occurs in a term CSR on the device, in how many documents, and in which first
+        (gft_term_stats_device).  off: int64 [n_docs + 1] (off[0] may be non-zero); term: int32, indexed by off's values -- the
+        (match_off, term_id) of scan_device or the (span_off, term) of hit_spans_device, as tensors or as device pointers (int).
+        occ, docs, first: int64 [n_terms] device tensors; what is not given is allocated (first reads -1, that is UINT64_MAX, where a
+        term did not occur).  accumulate: add to what the given tensors hold, first becoming the minimum; doc_base: the documents in
+        front of this batch.  Returns (occ, docs, first); only they would have to come down"""
+        import torch
+        given = [a for a in (off, occ, docs, first) if hasattr(a, "device")]
+        dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+        occ, docs = (torch.zeros(n_terms, dtype=torch.int64, device=dev) if a is None else a for a in (occ, docs))
+        first = torch.full((n_terms,), -1, dtype=torch.int64, device=dev) if first is None else first
+        for a in (occ, docs, first):
+            assert a.dtype == torch.int64 and a.numel() == n_terms and a.is_contiguous()
+        torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda a: (a if isinstance(a, int) or a is None else (a.data_ptr() if a.numel() else None))  # noqa: E731
+        self.term_stats_raw(ptr(off), ptr(term), n_docs, n_terms, _lib.GFT_STATS_ACCUMULATE if accumulate else 0, doc_base,
+                            *(a.data_ptr() if n_terms else None for a in (occ, docs, first)))
+        return occ, docs, first
+
+    def count_columns_device(self, bitmap, n_cols, row_idx=None, count=None, accumulate=False):
+        """in how many rows each column of a hit bitmap is set (gft_count_columns_device).  bitmap: int32 [n, ceil(n_cols / 32)] on the
+        device, as process_device leaves it (bits at and above n_cols are ignored); row_idx: None, or int64 [m]: the rows to count,
+        repeats counting repeatedly (the doc_idx of a routed bucket); count: int64 [n_cols], allocated when not given; accumulate:
+        add to it.  Returns count"""
+        import torch
+        dev = bitmap.device
+        n_rows = int(row_idx.numel()) if row_idx is not None else (int(bitmap.shape[0]) if bitmap.dim() == 2 else 0)
+        if count is None:
+            count = torch.zeros(n_cols, dtype=torch.int64, device=dev)
+        assert count.dtype == torch.int64 and count.numel() == n_cols
+        torch.cuda.current_stream(dev).synchronize()
+        self._check(self._L.gft_count_columns_device(self._h, bitmap.data_ptr() if bitmap.numel() else None, n_rows, n_cols,
+                                                     row_idx.data_ptr() if row_idx is not None and row_idx.numel() else None,
+                                                     _lib.GFT_STATS_ACCUMULATE if accumulate else 0, count.data_ptr() if n_cols else None))
+        return count
+
+    @staticmethod
+    def term_stats_host(off, term, n_terms, accumulate_into=None, doc_base=0):
+        """the host twin of term_stats_device over numpy arrays (gft_debug_term_stats) -> (occ, docs, first) uint64"""
+        if accumulate_into is None:
+            occ, docs, first = (np.zeros(n_terms, dtype=np.uint64) for _ in range(3))
+        else:
+            occ, docs, first = accumulate_into
+        term_stats_host(off, term, n_terms, occ, docs, first, _lib.GFT_STATS_ACCUMULATE if accumulate_into is not None else 0, doc_base)
+        return occ, docs, first
+
+    @staticmethod
+    def count_columns_host(bitmap, n_cols, row_idx=None):
+        """the host twin of count_columns_device over numpy arrays (gft_debug_count_columns) -> count uint64 [n_cols]"""
+        bm = np.ascontiguousarray(bitmap, dtype=np.uint32)
+        n_rows = len(row_idx) if row_idx is not None else (bm.shape[0] if bm.ndim == 2 else 0)
+        count = np.zeros(n_cols, dtype=np.uint64)
+        count_columns_host(bm, n_rows, n_cols, count, row_idx)
+        return count
+
+    @staticmethod
+    def stats_shape():
+        """the borders of the statistics' walk (gft_debug_stats_shape) as a dict"""
+        return stats_shape()
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

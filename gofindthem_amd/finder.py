@@ -689,6 +689,80 @@ class Finder:
             bucket_doc, bucket_byte = route_docs_host(data, off, bm, self.n_expressions, masks, "every", False, count_only=True)[:2]
         return np.diff(bucket_doc), np.diff(bucket_byte)
 
+    # -- how often each keyword hit, and where (csrc/gft_stats.hip) ------------------------------------------------------------
+    def TermStatsDevice(self, text, doc_off, bitmap=None, want=None, accumulate_into=None, doc_base=0):
+        """the keyword statistics of a resident batch (gft_finder_term_stats_device).  text, doc_off as for ProcessDevice; bitmap: the
+        rows ProcessDevice left -- the statistics are those of the KEPT matches, the witness occurrences of true, wanted expressions
+        (want: want_mask(), None: every expression) --, or None: of every dictionary match of the batch.  accumulate_into: None, or
+        the (occ, docs, first) a former call returned: the batch is added to them, doc_base being the documents in front of it.
+        Returns (occ, docs, first, lowered): int64 [n_terms] device tensors indexed by the engine's term id -- occurrences, documents,
+        doc_base + first document (-1: none) -- and whether the batch left ASCII and was lowered on the device first.  Needs what
+        ProcessDevice needs"""
+        import torch
+        n = int(doc_off.numel()) - 1
+        lowered = C.c_int(0)
+        w = None
+        if want is not None:
+            w = np.ascontiguousarray(self.want_mask() & np.ascontiguousarray(want, dtype=np.uint32))
+        # (the dictionary is built by the first call that scans: n_terms is known only then -- a count-free call builds it)
+        self._check(self._L.gft_finder_term_stats_device(self._h, text.data_ptr(), doc_off.data_ptr(), 0, None, None, 0, 0, None, None, None,
+                                                         C.byref(lowered)))
+        nt = int(self._L.gft_n_terms(self.engine_handle()))
+        if accumulate_into is None:
+            occ, docs = (torch.zeros(nt, dtype=torch.int64, device=text.device) for _ in range(2))
+            first = torch.full((nt,), -1, dtype=torch.int64, device=text.device)
+        else:
+            occ, docs, first = accumulate_into
+            assert all(a.dtype == torch.int64 and a.numel() == nt for a in (occ, docs, first))
+        torch.cuda.current_stream(text.device).synchronize()
+        self._check(self._L.gft_finder_term_stats_device(
+            self._h, text.data_ptr(), doc_off.data_ptr(), n, bitmap.data_ptr() if bitmap is not None and bitmap.numel() else None,
+            w.ctypes.data if w is not None and w.size else None, _lib.GFT_STATS_ACCUMULATE if accumulate_into is not None else 0, int(doc_base),
+            *(a.data_ptr() if nt else None for a in (occ, docs, first)), C.byref(lowered)))
+        return occ, docs, first, bool(lowered.value)
+
+    def TermStatsLines(self, data, want=None, kept=True):
+        """bytes -> ({keyword: (occurrences, documents, first_line)}, lowered) over the lines of a blob, for the keywords that
+        occurred, keyed by the dictionary's text of the term (bytes, as gft_term gives it).  kept=True: the occurrences that are
+        witnesses of a true, wanted expression (want: want_mask(), None: any) -- what SpansLines lists; kept=False: every occurrence
+        of every keyword.  One upload; only the counters come down.  lowered as SpansLines returns it.  Device route only"""
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "term statistics need the device route: the GPU substring engine, no regex terms, one device")
+        if not self.n_expressions:                                   # (no dictionary: nothing can occur)
+            return {}, False
+        data = bytes(data)
+        buf = self._resident(data)
+        if kept:
+            off, bm = self.ProcessLinesDevice(buf, len(data))
+            if not bm.numel():                                       # (no lines)
+                return {}, False
+        else:
+            off, bm = self.SplitLinesDevice(buf, len(data), 0), None
+        occ, docs, first, lowered = self.TermStatsDevice(buf, off, bm, want if kept else None)
+        occ, docs, first = (a.cpu().numpy() for a in (occ, docs, first))
+        out = {}
+        tp, tl = C.c_void_p(), C.c_uint32()
+        for t in np.nonzero(occ)[0].tolist():
+            self._check_engine(self._L.gft_term(self.engine_handle(), int(t), C.byref(tp), C.byref(tl)))
+            out[C.string_at(tp.value, tl.value)] = (int(occ[t]), int(docs[t]), int(first[t]))
+        return out, lowered
+
+    def CountExpressions(self, data):
+        """bytes -> a uint64 array with one count per expression index: the number of lines of the blob on which the expression is
+        true.  Neither rows nor lines come down (gft_count_columns_device over the rows ProcessLinesDevice left).  Device route only"""
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "expression counts need the device route: the GPU substring engine, no regex terms, one device")
+        import torch
+        data = bytes(data)
+        buf = self._resident(data)
+        off, bm = self.ProcessLinesDevice(buf, len(data))
+        E = self.n_expressions
+        count = torch.zeros(E, dtype=torch.int64, device=buf.device)
+        torch.cuda.current_stream(buf.device).synchronize()
+        self._check_engine(self._L.gft_count_columns_device(self.engine_handle(), bm.data_ptr() if bm.numel() else None, int(off.numel()) - 1, E, None,
+                                                            0, count.data_ptr() if E else None))
+        return count.cpu().numpy().astype(np.uint64)
+
     def _takes_device_route(self):
         """asks the handle: the split of an empty blob (gft_finder_split_lines_device, count only) answers what ProcessDevice asks
         of the finder -- the GPU substring engine, no regex terms, one device -- and whether there is a device at all.  Any other

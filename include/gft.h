@@ -649,6 +649,60 @@ int gft_debug_mark_spans(const uint8_t* blob, const uint64_t* doc_off, uint64_t 
  * lane's chunk of the output and of a wave's tile */
 void gft_debug_mark_shape(uint32_t* tile_spans, uint32_t* trip_tiles, uint32_t* chunk_bytes, uint32_t* tile_bytes);
 
+/* ---- Term statistics on the device: how often each keyword hit, in how many documents, and where first -----------------
+ * The histogram of a term list in CSR form on the engine's device: the entries of document d are d_term[d_off[d] .. d_off[d + 1]);
+ * d_off[0] may be non-zero (a run of documents cut from a larger batch).  The arguments are (match_off, term_id) of
+ * gft_scan_device -- with or without GFT_SCAN_UNIQUE --, or (d_span_off, d_span_term) of gft_hit_spans_device, of a selected or
+ * routed blob too.  The call runs no scan, needs neither a dictionary nor programs and leaves gft_last_nonascii alone.
+ * Output: three arrays of n_terms uint64, each nullable on its own (all three NULL only validates the input):
+ *   d_occ[t]    the number of entries with term t
+ *   d_docs[t]   the number of documents whose run holds t at least once
+ *   d_first[t]  doc_base + the smallest such document, UINT64_MAX when there is none
+ * Without GFT_STATS_ACCUMULATE the arrays are overwritten (untouched terms read 0, 0, UINT64_MAX).  With it the counts are added
+ * to what the arrays hold and d_first becomes the minimum of what it holds and the new value: the statistics of a stream of
+ * batches stay on the device, doc_base being the number of documents in front of this batch.  All counters are 64-bit end to end.
+ * Launches on the engine's stream (gft_profile_read): "stats_check" (a descending offset, a term id >= n_terms: found on the
+ * device before anything is written -- the list is not trusted, no atomic ever lands outside the counters), "stats_count" (a
+ * workgroup a range of whole documents of near-equal weight; counts combined in LDS, one global atomic per workgroup, distinct
+ * term and counter; csrc/gft_stats_piece.hpp).  The call waits for the stream.  Between gft_process_device_begin and _end it is
+ * allowed only after _complete.  n_docs == 0, an empty list and n_terms == 0 (with an empty list) are valid.
+ * GFT_E_UNSUPPORTED: a handle over several devices.  GFT_E_INVALID, before anything is written and with the three arrays byte for
+ * byte as they were: an offset that descends; a term id >= n_terms; an output that overlaps an input or another output; a size
+ * beyond the address space; unknown flag bits.  GFT_E_NOMEM: no room for the work buffers -- 16 bytes of flags, and, only with
+ * n_terms above the bitset's LDS limit (gft_debug_stats_shape), ceil(n_terms / 32) * 4 bytes per workgroup of the count pass
+ * (three per compute unit at most); nothing per entry.  The handle stays usable after any error. */
+#define GFT_STATS_ACCUMULATE 1u
+int gft_term_stats_device(gft_engine* e, const uint64_t* d_off, const uint32_t* d_term, uint64_t n_docs, uint32_t n_terms,
+                          uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first);
+/* d_count[c] = the number of rows r with bit c set, for the n_cols columns of a bitmap in gft_process's layout (ceil(n_cols / 32)
+ * words a row; finder rows and the group finder's rule rows alike).  Bits at and above n_cols are ignored, whatever they hold.
+ * With d_row_idx (nullable) the counted rows are d_row_idx[0 .. n_rows), repeated indices counting repeatedly: the per-expression
+ * counts of a routed bucket.  GFT_STATS_ACCUMULATE adds to d_count, without it the array is overwritten.  One launch
+ * (gft_profile_read: "stats_columns"); overlap and size checks, GFT_E_UNSUPPORTED and the _complete rule as above. */
+int gft_count_columns_device(gft_engine* e, const uint32_t* d_bitmap, uint64_t n_rows, uint32_t n_cols, const uint64_t* d_row_idx,
+                             uint32_t flags, uint64_t* d_count);
+/* The statistics of a resident batch in one call: with d_hit_bitmap the KEPT matches -- gft_hit_spans_device in count-then-fill
+ * form into buffers of the engine's, then the histogram of (span_off, span_term) --, with d_hit_bitmap == NULL every dictionary
+ * match -- gft_scan_device's canonical CSR.  scan_flags: GFT_FOLD_ASCII or 0; n_terms is gft_n_terms.  It counts as a scan.
+ * nonascii (nullable): set to 1, with NOTHING counted, when the scan folded and the batch was not fold-safe (gft_last_nonascii):
+ * the caller lowers the batch and calls again -- an accumulating array never sees a batch twice.  With nonascii == NULL such a
+ * batch is counted as scanned. */
+int gft_batch_term_stats_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
+                                const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
+                                uint64_t* d_docs, uint64_t* d_first, int* nonascii);
+/* The host forms, no HIP device needed, same contracts, all pointers host: the kernels' walks workgroup by workgroup, step by step
+ * and lane by lane through the source they are compiled from (csrc/gft_stats_piece.hpp). */
+int gft_debug_term_stats(const uint64_t* off, const uint32_t* term, uint64_t n_docs, uint32_t n_terms, uint32_t flags, uint64_t doc_base,
+                         uint64_t* occ, uint64_t* docs, uint64_t* first);
+int gft_debug_count_columns(const uint32_t* bitmap, uint64_t n_rows, uint32_t n_cols, const uint64_t* row_idx, uint32_t flags,
+                            uint64_t* count);
+/* where those walks' borders are: the entries and the documents of a step at most, the slots of the step's set and of the
+ * workgroup's cache (a term's slot is term mod cache_slots; the pairs (d, t) and (d, t + set_slots) meet in the set), the entries
+ * at which a document takes the large path, the n_terms up to which its bitset lies in LDS, the weight (entries + documents) a
+ * workgroup owns at least, the rows a workgroup of the column count owns */
+void gft_debug_stats_shape(uint32_t* step_entries, uint32_t* step_docs, uint32_t* set_slots, uint32_t* cache_slots, uint32_t* large_entries,
+                           uint32_t* bitset_lds_terms, uint32_t* range_weight, uint32_t* column_rows);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -770,6 +824,15 @@ int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint
                            uint32_t open_len, const uint8_t* close, uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
                            uint64_t* d_out_off, uint32_t* d_span_new, uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes,
                            int* lowered);
+/* Term statistics of a resident batch on the finder's engine under the finder's case rule, as gft_finder_hit_spans_device runs:
+ * a batch that leaves ASCII is lowered on the device first and *lowered set to 1 (term ids do not depend on positions: nothing is
+ * mapped back).  d_hit_bitmap non-NULL: the statistics of the KEPT matches -- the witness occurrences of true, wanted expressions
+ * (want: host words, NULL = every expression); NULL: of every dictionary match of the batch.  n_terms of the arrays is the
+ * engine's (gft_n_terms of the finder's engine); flags, doc_base and the three arrays as gft_term_stats_device takes them.  The
+ * refusals of gft_finder_hit_spans_device in its words. */
+int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                 const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
+                                 uint64_t* d_docs, uint64_t* d_first, int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
