@@ -192,6 +192,17 @@ SYMBOLS = {
     "gft_debug_count_columns": (_i, [_vp, _u64, _u32, _vp, _u32, _vp]),
     "gft_debug_stats_shape": (None, [C.POINTER(_u32)] * 8),
     "gft_finder_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),
+    "gft_filter_word_matches_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "gft_debug_filter_word_matches": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "gft_debug_word_rune": (_u32, [_u32]),
+    "gft_debug_words_shape": (None, [C.POINTER(_u32)] * 3),
+    "gft_scan_words_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    "gft_process_words_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    "gft_process_words": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    "gft_hit_spans_words_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    "gft_batch_term_stats_words_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),
+    "gft_finder_set_whole_words": (_i, [_vp, _i]),
+    "gft_finder_whole_words": (_i, [_vp]),
     "gft_debug_lowermap_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_group_process_json_lines": (_i, [_vp, _vp, _u64, C.c_char_p, _u64, C.c_char_p, _u64, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_emulate_scan": (_i, [_vp, _vp, _u32, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _u64, C.POINTER(_u64)]),

@@ -309,6 +309,7 @@ static bool all_ascii(const uint8_t* p, uint64_t n) {
 Error Finder::ProcessText(const std::string& text_in, std::vector<ExpressionResult>& expRes) {
     expRes.clear();
     last_code_ = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
     // strings.ToLower (finder.go:140-142).  ASCII text that only the device reads (GPU substring engine, no regex terms)
     // is folded by the scan kernel while it is read; anything else is lower-cased here first (it may change byte lengths)
     const bool host_engines = !gpu_sub_ || !regexes_.empty();
@@ -326,7 +327,9 @@ Error Finder::ProcessText(const std::string& text_in, std::vector<ExpressionResu
     gft_extra_matches x{xoff, xs.data(), xp.data()};
     const size_t words = (total_programs() + 31) / 32;        // hidden prefilter programs sit behind the user's
     std::vector<uint32_t> bm(std::max<size_t>(words, 1), 0);
-    int rc = gft_process(gpu_->handle(), (const uint8_t*)text.data(), doff, 1, fold_on_device ? GFT_FOLD_ASCII : 0, &x, bm.data());
+    // (whole words: no host engine has run, recs is empty)
+    int rc = wholeWords_ ? gft_process_words(gpu_->handle(), (const uint8_t*)text.data(), doff, 1, fold_on_device ? GFT_FOLD_ASCII : 0, bm.data())
+                         : gft_process(gpu_->handle(), (const uint8_t*)text.data(), doff, 1, fold_on_device ? GFT_FOLD_ASCII : 0, &x, bm.data());
     if (rc) return fail_gft(rc);
     for (size_t i = 0; i < expressions_.size(); i++)
         if (bm[i >> 5] >> (i & 31) & 1)
@@ -336,6 +339,7 @@ Error Finder::ProcessText(const std::string& text_in, std::vector<ExpressionResu
 
 Error Finder::process_texts(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t* bitmap, bool sparse) {
     last_code_ = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
     // case folding: ASCII-only batches fold on the device while the text is read; anything else goes through
     // strings.ToLower on the host first (it may change byte lengths, finder.go:140-142)
     uint32_t flags = 0;
@@ -395,6 +399,28 @@ Error Finder::process_texts(const uint8_t* blob, const uint64_t* doc_off, uint64
     gft_extra_matches x{xoff.data(), xs.data(), xp.data()};
     // (a disabled prefilter still leaves its programs out: total_programs() == expressions_.size() then)
     gft_sparse sp{};
+    if (wholeWords_) {
+        // the rows of gft_process_words; the sparse form is compacted here, by the code behind gft_debug_compact_host, as the
+        // prefilter route's rows are
+        const size_t uw = (expressions_.size() + 31) / 32;
+        std::vector<uint32_t> bm(sparse ? (size_t)n_docs * uw + 1 : 0, 0);
+        int rc = gft_process_words(gpu_->handle(), blob, doc_off, n_docs, flags, sparse ? bm.data() : bitmap);
+        if (rc) return fail_gft(rc);
+        if (optimistic && gft_last_nonascii(gpu_->handle())) {
+            struct Reset { bool& f; ~Reset() { f = false; } } reset{force_host_lower_};
+            force_host_lower_ = true;
+            return process_texts(blob, doc_off, n_docs, bitmap, sparse);
+        }
+        if (sparse) {
+            sp_row_off_.assign(n_docs + 1, 0);
+            const uint32_t n_user = (uint32_t)expressions_.size();
+            const uint64_t n_true = compact_host(bm.data(), n_docs, n_user, tag_ids_.data(), sp_row_off_.data(), nullptr, nullptr, 0);
+            sp_idx_.assign(n_true + 1, 0); sp_tag_.assign(n_true + 1, 0);
+            compact_host(bm.data(), n_docs, n_user, tag_ids_.data(), sp_row_off_.data(), sp_idx_.data(), sp_tag_.data(), n_true);
+            sparse_ = Sparse{sp_row_off_.data(), sp_idx_.data(), sp_tag_.data()};
+        }
+        return "";
+    }
     int rc = sparse ? gft_process_sparse(gpu_->handle(), blob, doc_off, n_docs, flags, per_doc_engines && n_docs ? &x : nullptr, &sp)
                     : gft_process(gpu_->handle(), blob, doc_off, n_docs, flags, per_doc_engines && n_docs ? &x : nullptr, bitmap);
     if (rc) return fail_gft(rc);
@@ -483,8 +509,19 @@ Error Finder::process_texts_prefiltered(const uint8_t* blob, const uint64_t* doc
     return "";
 }
 
+Error Finder::words_refusal() {
+    if (!wholeWords_) return "";
+    const char* why = !gpu_sub_ ? "a foreign substring engine"
+                      : !regexes_.empty() ? "regex terms"
+                      : (gpu_ && gpu_->handle() && gft_n_devices(gpu_->handle()) != 1) ? "an engine over several devices" : nullptr;
+    if (!why) return "";
+    last_code_ = GFT_E_UNSUPPORTED;
+    return std::string("whole-word matching needs the GPU substring engine on one device and no regex terms: this finder has ") + why;
+}
+
 Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
@@ -493,8 +530,8 @@ Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, ui
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
-    int rc = gft_process_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, nullptr,
-                                d_bitmap);
+    int rc = wholeWords_ ? gft_process_words_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap)
+                         : gft_process_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, nullptr, d_bitmap);
     if (rc) return fail_gft(rc);
     return repeat_if_not_ascii(d_blob, d_doc_off, n_docs, d_bitmap);
 }
@@ -547,6 +584,7 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
         last_code_ = GFT_E_INVALID;
         return "hit spans in source positions need the span offsets and the length array whenever spans are written";
     }
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
@@ -555,8 +593,10 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
-    int rc = gft_hit_spans_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, d_row_idx, want, d_span_off,
-                                  d_span_start, d_span_len, d_span_term, cap, total);
+    // (with the whole-word option the filter runs on the text that was scanned, in front of any map back to the source)
+    const auto spans_call = wholeWords_ ? gft_hit_spans_words_device : gft_hit_spans_device;
+    int rc = spans_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, d_row_idx, want, d_span_off,
+                        d_span_start, d_span_len, d_span_term, cap, total);
     if (rc) return fail_gft(rc);
     if (caseSensitive_ || !n_docs || !gft_last_nonascii(gpu_->handle())) return "";
     // as repeat_if_not_ascii: the batch is lowered in full on the device and scanned again from there; the spans then index the
@@ -569,8 +609,8 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
     const uint64_t* d_low_off = nullptr;
     rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
     if (rc) return fail_gft(rc);
-    rc = gft_hit_spans_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, d_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
-                              d_span_term, cap, total);
+    rc = spans_call(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, d_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
+                    d_span_term, cap, total);
     if (rc) return fail_gft(rc);
     if (lowered) *lowered = 1;
     // the spans that were written (those below the cap) index the lowered text: back to the caller's bytes, in place
@@ -641,6 +681,7 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
                               uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first, int* lowered) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
@@ -650,8 +691,9 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
     int again = 0;
-    int rc = gft_batch_term_stats_device(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, flags, doc_base,
-                                         d_occ, d_docs, d_first, &again);
+    const auto stats_call = wholeWords_ ? gft_batch_term_stats_words_device : gft_batch_term_stats_device;
+    int rc = stats_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, flags, doc_base,
+                        d_occ, d_docs, d_first, &again);
     if (rc) return fail_gft(rc);
     if (!again) return "";
     // as HitSpansDevice: the batch is lowered in full on the device and scanned again from there (nothing was counted so far)
@@ -663,8 +705,8 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     const uint64_t* d_low_off = nullptr;
     rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
     if (rc) return fail_gft(rc);
-    rc = gft_batch_term_stats_device(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, flags, doc_base, d_occ, d_docs, d_first,
-                                     nullptr);
+    rc = stats_call(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, flags, doc_base, d_occ, d_docs, d_first,
+                    nullptr);
     if (rc) return fail_gft(rc);
     if (lowered) *lowered = 1;
     return "";
@@ -672,6 +714,10 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
 
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
+    if (wholeWords_) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "whole-word matching has no pipelined form: ProcessDevice takes the batch";
+    }
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
@@ -715,7 +761,8 @@ Error Finder::repeat_if_not_ascii(const uint8_t* d_blob, const uint64_t* d_doc_o
         const uint64_t* d_low_off = nullptr;
         int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
         if (rc) return fail_gft(rc);
-        rc = gft_process_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, nullptr, d_bitmap);
+        rc = wholeWords_ ? gft_process_words_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, d_bitmap)
+                         : gft_process_device(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, nullptr, d_bitmap);
         if (rc) return fail_gft(rc);
         lowered_on_device++;
         return "";
@@ -1031,6 +1078,19 @@ int gft_finder_process_device_end(gft_finder* f) try {
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->ProcessDeviceEnd(), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_set_whole_words(gft_finder* f, int on) try {
+    if (!f || !f->finder) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    f->finder->set_whole_words(on != 0);
+    return GFT_OK;
+} GFT_CATCH((f ? &f->err : nullptr))
+
+int gft_finder_whole_words(const gft_finder* f) {
+    if (!f || !f->finder) return 0;
+    GFT_FLOCK(f);
+    return f->finder->whole_words() ? 1 : 0;
+}
 
 int gft_finder_lowered_batches(const gft_finder* f, uint64_t* on_device, uint64_t* on_host) try {
     if (!f || !f->finder || !on_device || !on_host) return GFT_E_INVALID;

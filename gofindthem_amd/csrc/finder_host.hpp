@@ -164,6 +164,12 @@ public:
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();
     Error ForceBuild();
+    // whole-word matching (gft_words.hip): with the option on ProcessText / ProcessTexts / ProcessTextsSparse, ProcessDevice,
+    // HitSpansDevice and TermStatsDevice answer from the occurrences that stand at word borders (gft_process_words*,
+    // gft_hit_spans_words_device, gft_batch_term_stats_words_device); a foreign substring engine, regex terms or several devices
+    // make every processing call fail with GFT_E_UNSUPPORTED, ProcessDeviceBegin always does
+    void set_whole_words(bool on) { wholeWords_ = on; }
+    bool whole_words() const { return wholeWords_; }
     const std::vector<std::string>& GetKeywords() const { return keywords_; }
     const std::vector<std::string>& GetRegexes() const { return regexes_; }
 
@@ -220,6 +226,8 @@ private:
     SubstringEngine* subEng_;
     RegexEngine* rgxEng_;
     bool caseSensitive_;
+    bool wholeWords_ = false;
+    Error words_refusal();               // "" or, with the option on, why this finder cannot match whole words (last_code_ set)
     GpuEngine* gpu_;
     bool gpu_sub_;                       // subEng_ is the GPU engine itself: scanning is fused into gft_process
     bool programs_dirty_ = true;

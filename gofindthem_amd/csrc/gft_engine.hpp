@@ -222,6 +222,14 @@ struct gft_engine {
     // gft_hit_spans_device asks for with any cap; they are not read)
     struct StatsBufs { DevBuf ctl, rows, span_off, span_start, span_term; } d_stats;
 
+    // whole-word matching (gft_words.hip): the class table (uploaded with the first call), the check pass's flag words, the marks of
+    // a list's entries with their prefix sums and scan partials; the kept matches of gft_scan_words_device / gft_process_words_device
+    // (off, pos, term), the spans gft_hit_spans_words_device filters, the kept spans gft_batch_term_stats_words_device counts
+    struct WordBufs {
+        bool table_up = false;
+        DevBuf tab_row, tab_bits, ctl, keep, rank, partial, off, pos, term, span_off, span_start, span_len, span_term, stat_off, stat_start, stat_term;
+    } d_words;
+
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
     // the tag rows of a batch, the flag words, staging for the host-pointer entry points
     struct RuleBufs {

@@ -604,6 +604,81 @@ def count_columns_host(bitmap, n_rows, n_cols, count, row_idx=None, flags=0):
         raise GftError(rc, "gft_debug_count_columns")
 
 
+WORDS_POS_END = 1                                   # GFT_WORDS_POS_END
+
+
+def word_rune(cp):
+    """True when cp is a word rune of the whole-word rule (gft_debug_word_rune): category L*, M*, N* or Pc"""
+    return bool(_lib.load().gft_debug_word_rune(int(cp)))
+
+
+def words_shape():
+    """the borders of the word filter's walk as a dict (gft_debug_words_shape): tile_entries, table_rows, table_bytes"""
+    v = [C.c_uint32(0) for _ in range(3)]
+    _lib.load().gft_debug_words_shape(*(C.byref(x) for x in v))
+    return dict(zip(("tile_entries", "table_rows", "table_bytes"), (int(x.value) for x in v)))
+
+
+def filter_word_matches_host(blob, doc_off, off, pos, length=None, term=None, term_len=None, pos_end=False, cap=None, guard=0, flags=None,
+                             with_len=True, with_term=True):
+    """gft_debug_filter_word_matches over host arrays -> (total, out_off uint64 [n + 1 + guard], pos, len, term uint32 [cap + guard]); no
+    device needed.  off uint64 [n_docs + 1] (off[0] may be non-zero), pos / length / term uint32 indexed by off's values; length
+    None: the lengths are term_len[term].  cap None: count first, then exactly the total; the guard entries behind the caps hold
+    0xA5.. and must come back untouched.  with_len / with_term False: that output is not passed (None is returned for it)"""
+    L = _lib.load()
+    b = np.ascontiguousarray(blob, dtype=np.uint8)
+    do, o = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(off, dtype=np.uint64)
+    n_docs = do.size - 1
+    ps = np.ascontiguousarray(pos, dtype=np.uint32)
+    ln = np.ascontiguousarray(length, dtype=np.uint32) if length is not None else None
+    tm = np.ascontiguousarray(term, dtype=np.uint32) if term is not None else None
+    tl = np.ascontiguousarray(term_len, dtype=np.uint32) if term_len is not None else None
+    fl = (WORDS_POS_END if pos_end else 0) if flags is None else int(flags)
+    with_term = with_term and tm is not None
+    total = C.c_uint64(0)
+    opt = lambda a: _p(a) if a is not None and a.size else None     # noqa: E731
+
+    def call(oo, a, bb, c, cp):
+        rc = L.gft_debug_filter_word_matches(opt(b), _p(do), n_docs, _p(o), opt(ps), opt(ln), opt(tm), opt(tl), tl.size if tl is not None else 0, fl,
+                                             _p(oo), _p(a), _p(bb), _p(c), cp, C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_filter_word_matches")
+    if cap is None:
+        call(None, None, None, None, 0)
+        cap = int(total.value)
+    out_off = np.full(n_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    arrs = [np.full(cap + guard, 0xA5A5A5A5, dtype=np.uint32) for _ in range(3)]
+    call(out_off, arrs[0] if cap or guard else None, arrs[1] if with_len and (cap or guard) else None,
+         arrs[2] if with_term and (cap or guard) else None, cap)
+    return int(total.value), out_off, arrs[0], arrs[1] if with_len else None, arrs[2] if with_term else None
+
+
+def filter_word_matches_tensor(call, text, doc_off, off, pos, length, term, term_len, pos_end):
+    """gft_filter_word_matches_device through `call(d_text, d_doc_off, n_docs, d_off, d_pos, d_len, d_term, d_term_len, n_terms, flags,
+    d_out_off, d_out_pos, d_out_len, d_out_term, cap, byref(total))`.  Two calls: count only, then into tensors of exactly the size
+    counted.  Returns (out_off int64 [n + 1], pos, len, term int32 [total]; term None without term ids)"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (off, 8, "off"), (pos, 4, "pos")) + \
+            tuple((t, 4, w) for t, w in ((length, "length"), (term, "term"), (term_len, "term_len")) if t is not None):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("filter_word_matches_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or off.numel() != n_docs + 1 or (length is None and (term is None or term_len is None)):
+        raise ValueError("filter_word_matches_device: doc_off, off and the entry arrays do not describe the same list")
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None   # noqa: E731
+    args = (ptr(text), doc_off.data_ptr(), n_docs, off.data_ptr(), ptr(pos), ptr(length), ptr(term), ptr(term_len),
+            int(term_len.numel()) if term_len is not None else 0, WORDS_POS_END if pos_end else 0)
+    total = C.c_uint64(0)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, None, None, None, None, 0, C.byref(total))
+    n = int(total.value)
+    out_off = torch.empty(n_docs + 1, dtype=torch.int64, device=text.device)
+    o_pos, o_len, o_term = (torch.empty(n, dtype=torch.int32, device=text.device) for _ in range(3))
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, out_off.data_ptr(), ptr(o_pos), ptr(o_len), ptr(o_term) if term is not None else None, n, C.byref(total))
+    return out_off, o_pos, o_len, (o_term if term is not None else None)
+
+
 def lowermap_shape():
     """(bytes of a piece, of a wave's trip, of a work unit at most, spans of a wave's tile) (gft_debug_lowermap_shape)"""
     v = [C.c_uint32(0) for _ in range(4)]
@@ -951,6 +1026,60 @@ class Engine:
     def stats_shape():
         """the borders of the statistics' walk (gft_debug_stats_shape) as a dict"""
         return stats_shape()
+
+    # -- whole-word matching (csrc/gft_words.hip) ---------------------------------------------------------------------------------
+    def filter_word_matches_device(self, text, doc_off, off, pos, length=None, term=None, term_len=None, pos_end=False):
+        """a match or span list filtered at word borders on the device (gft_filter_word_matches_device).  text: torch.uint8; doc_off,
+        off: int64 [n + 1] (off[0] may be non-zero); pos, length, term: int32 indexed by off's values -- (match_off, pos, None,
+        term_id) of scan_device with term_len = the dictionary's lengths (int32 [n_terms]), or (span_off, start, len, term) of
+        hit_spans_device.  pos_end: pos is the occurrence's last byte.  Returns device tensors (out_off int64 [n + 1], pos, len int32
+        [total], term int32 [total] or None): the kept entries in the order given.  Counts first, then fills"""
+        return filter_word_matches_tensor(lambda *a: self._check(self._L.gft_filter_word_matches_device(self._h, *a)), text, doc_off, off, pos,
+                                          length, term, term_len, pos_end)
+
+    def filter_word_matches_raw(self, *args):
+        """gft_filter_word_matches_device on device pointers as they are (None: NULL), behind the handle: (d_text, d_doc_off, n_docs,
+        d_off, d_pos, d_len, d_term, d_term_len, n_terms, flags, d_out_off, d_out_pos, d_out_len, d_out_term, cap) -> total"""
+        total = C.c_uint64(0)
+        self._check(self._L.gft_filter_word_matches_device(self._h, *args, C.byref(total)))
+        return int(total.value)
+
+    @staticmethod
+    def filter_word_matches_host(blob, doc_off, off, pos, length=None, term=None, term_len=None, pos_end=False):
+        """the host twin of filter_word_matches_device over numpy arrays (gft_debug_filter_word_matches) -> (out_off uint64 [n + 1],
+        pos, len uint32 [total], term uint32 [total] or None)"""
+        total, oo, p, ln, tm = filter_word_matches_host(blob, doc_off, off, pos, length, term, term_len, pos_end)
+        return oo, p[:total], ln[:total], (tm[:total] if tm is not None else None)
+
+    @staticmethod
+    def words_shape():
+        """the borders of the word filter's walk (gft_debug_words_shape) as a dict"""
+        return words_shape()
+
+    def scan_words_device(self, d_text_ptr, d_doc_off_ptr, n_docs, fold=False):
+        """scan_device followed by the word filter: device pointers in -> GftMatches with DEVICE pointers to the whole-word matches
+        (valid until the next call)"""
+        m = GftMatches()
+        self._check(self._L.gft_scan_words_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, _lib.GFT_FOLD_ASCII if fold else 0, C.byref(m)))
+        return m
+
+    def process_words_device(self, d_text_ptr, d_doc_off_ptr, n_docs, d_bitmap_ptr, fold=False):
+        """process_device from the whole-word matches alone (gft_process_words_device)"""
+        self._check(self._L.gft_process_words_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, _lib.GFT_FOLD_ASCII if fold else 0, d_bitmap_ptr))
+
+    def process_words(self, blob, doc_off, fold=False):
+        """host numpy in -> uint32 bitmap [n_docs, ceil(E/32)] from the whole-word matches alone (gft_process_words)"""
+        n_docs = len(doc_off) - 1
+        bm = np.zeros((n_docs, (self.n_exprs + 31) // 32), dtype=np.uint32)
+        self._check(self._L.gft_process_words(self._h, _p(blob), _p(doc_off), n_docs, _lib.GFT_FOLD_ASCII if fold else 0, _p(bm) if bm.size else None))
+        return bm
+
+    def hit_spans_words_device(self, text, doc_off, bitmap, want=None, row_idx=None, fold=False):
+        """hit_spans_device with the whole-word rule (gft_hit_spans_words_device): same arguments, same result, only the spans that
+        stand at word borders"""
+        flags = _lib.GFT_FOLD_ASCII if fold else 0
+        return hit_spans_tensor(lambda t, o, n, *a: self._check(self._L.gft_hit_spans_words_device(self._h, t, o, n, flags, *a)), text, doc_off,
+                                bitmap, self.n_exprs, want, row_idx)
 
     def process_sparse(self, blob, doc_off, fold=False, extra=None):
         """host numpy in -> (row_off u64 [n_docs + 1], expr_idx u32, label u32 or None) (gft_process_sparse)"""

@@ -161,9 +161,12 @@ def _mk_find(obj, method):
 class Finder:
     """finder.Finder (finder/finder.go:32-240).  NewFinder(subEng, rgxEng, caseSensitive)."""
 
-    def __init__(self, subEng=None, rgxEng=None, caseSensitive=True, device=-1, allow_no_device=False, devices=None):
+    def __init__(self, subEng=None, rgxEng=None, caseSensitive=True, device=-1, allow_no_device=False, devices=None, whole_words=False):
         """allow_no_device: keep the handle when no HIP device exists, so the host-only half (expression
-        registry, parser, engine-build orchestration) can be exercised; every GPU step then fails with GFT_E_HIP."""
+        registry, parser, engine-build orchestration) can be exercised; every GPU step then fails with GFT_E_HIP.
+        whole_words: a keyword occurrence counts only where it stands at word borders (gft_finder_set_whole_words): `he` no longer
+        fires inside `ushers`.  Every Process*, Select*, Route*, Count*, Spans*, Redact*, Excerpt*, Highlight* and TermStats* call of
+        this finder then answers from those occurrences; needs the GPU substring engine on one device and no regex terms."""
         self._L = _lib.load()
         h = C.c_void_p()
         if devices is not None:        # one finder over several devices (gft_finder_create_multi)
@@ -187,6 +190,16 @@ class Finder:
             b, f = _mk_build(rgxEng), _mk_find(rgxEng, "FindRegexes")
             self._keep += [b, f, rgxEng]
             self._check(self._L.gft_finder_set_regex_engine(self._h, C.cast(b, C.c_void_p), C.cast(f, C.c_void_p), None))
+        if whole_words:
+            self._check(self._L.gft_finder_set_whole_words(self._h, 1))
+
+    @property
+    def whole_words(self):
+        return bool(self._L.gft_finder_whole_words(self._h))
+
+    @whole_words.setter
+    def whole_words(self, on):
+        self._check(self._L.gft_finder_set_whole_words(self._h, 1 if on else 0))
 
     def close(self):
         if getattr(self, "_h", None):

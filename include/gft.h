@@ -703,6 +703,79 @@ int gft_debug_count_columns(const uint32_t* bitmap, uint64_t n_rows, uint32_t n_
 void gft_debug_stats_shape(uint32_t* step_entries, uint32_t* step_docs, uint32_t* set_slots, uint32_t* cache_slots, uint32_t* large_entries,
                            uint32_t* bitset_lds_terms, uint32_t* range_weight, uint32_t* column_rows);
 
+/* ---- Whole-word matching on the device: a match or span list filtered at word borders (csrc/gft_words.hip) -----------------
+ * Every other call matches substrings: `he` fires inside `ushers`.  This one takes a list of occurrences in CSR form and the text
+ * they were found in, keeps the entries that stand at word borders and compacts the list stably.
+ * The rule.  A rune is a WORD rune when its Unicode general category starts with L, M or N, or is Pc -- letters, marks, numbers,
+ * connector punctuation (`_`); the table is csrc/unicode_word.inc.  U+FFFD and every byte the decoder rejects are no word runes.
+ * An occurrence is the bytes [s, e) of document D = text[doc_off[d] .. doc_off[d + 1]), s and e relative to the document; it is
+ * KEPT iff
+ *   NOT( word(utf8.DecodeLastRune(D[:s])) AND word(utf8.DecodeRune(D[s:e])) )   and
+ *   NOT( word(utf8.DecodeLastRune(D[s:e])) AND word(utf8.DecodeRune(D[e:])) )
+ * with Go's semantics: the strict decoder (overlong forms, surrogates, values above U+10FFFF are rejected), DecodeLastRune goes
+ * back over at most UTFMax - 1 bytes to a rune start and gives RuneError unless the rune decoded there ends exactly at the slice's
+ * end, an empty slice gives no rune and demands nothing.  So only a word rune against a word rune across an edge drops an
+ * occurrence; a keyword edge that is no word rune demands nothing (`c++` is kept in `c++x`, `.net` in `asp.net`); an entry of
+ * length 0 is kept; and nothing outside the document is ever looked at -- not the lead bytes, not the slack, not the neighbouring
+ * document, not the other half of a rune that a document border cuts.
+ * The list: the entries of document d are [d_off[d], d_off[d + 1]); d_off[0] may be non-zero (a run cut from a larger batch).
+ * Entry i lies at d_pos[i] and is d_len[i] bytes long when d_len is given, d_term_len[d_term[i]] otherwise (d_term_len: n_terms
+ * words on the device); d_term, when given, is carried through.  GFT_WORDS_POS_END: d_pos is the occurrence's LAST byte (the
+ * positions of a GFT_POS_END engine), otherwise its first.  The arguments are (match_off, pos, NULL, term_id) of gft_scan_device
+ * with the dictionary's lengths, or (span_off, span_start, span_len, span_term) of gft_hit_spans_device.
+ * The text lies as gft_scan_device takes it: no alignment, d_doc_off[0] may be non-zero; every text byte is read on its own and
+ * only inside its document.
+ * Output: the kept entries of document d, in the order given, are [d_out_off[d], d_out_off[d + 1]) of d_out_pos (the position as
+ * given), d_out_len (the length used) and d_out_term; d_out_off[0] = 0.  Cap protocol of gft_compact_device: cap counts entries;
+ * an entry at or past cap is NOT written and nothing is stored at or past any array + cap; d_out_off (n_docs + 1 entries,
+ * nullable, always complete when given) is not capped; all outputs NULL with cap == 0 counts only; GFT_OK in both cases and
+ * *total (host, nullable) is always handed back.  d_out_len and d_out_term may each be NULL on their own; d_out_term needs d_term.
+ * Launches on the engine's stream (gft_profile_read): "word_check" (the list is not trusted: an offset that descends, a term id
+ * >= n_terms when the lengths come from the term table, an entry that leaves its document are found on the device before a text
+ * byte is read or anything is written), "word_mark", "word_scan", "word_place".  The call waits for the stream.
+ * GFT_E_INVALID, with every output byte as it was: the three findings of the check; an output that overlaps an input or another
+ * output; unknown flag bits; a size beyond the address space.  GFT_E_UNSUPPORTED: a handle over several devices.  GFT_E_NOMEM: no
+ * room for the work buffers (12 bytes an entry).  Between gft_process_device_begin and _end only after _complete.  Needs no
+ * dictionary and no programs, leaves gft_last_nonascii alone; n_docs == 0 and an empty list are valid; the handle stays usable
+ * after any error. */
+#define GFT_WORDS_POS_END 1u
+int gft_filter_word_matches_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_off,
+                                   const uint32_t* d_pos, const uint32_t* d_len, const uint32_t* d_term, const uint32_t* d_term_len,
+                                   uint32_t n_terms, uint32_t flags, uint64_t* d_out_off, uint32_t* d_out_pos, uint32_t* d_out_len,
+                                   uint32_t* d_out_term, uint64_t cap, uint64_t* total);
+/* gft_scan_device followed by the filter, into library-owned buffers (valid until the next call on the engine): the whole-word
+ * matches of the batch as device pointers.  flags: GFT_FOLD_ASCII; GFT_SCAN_UNIQUE and GFT_POS_RUNES: GFT_E_INVALID.  It counts as a
+ * scan (gft_last_nonascii).  With GFT_FOLD_ASCII the borders are judged on the text as it lies: folding A-Z changes no class. */
+int gft_scan_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
+                          gft_matches* out_dev);
+/* The bitmap of gft_process_device, computed from the whole-word matches alone: the scan with positions, the filter, then the
+ * solver over the kept list as caller-supplied matches (slot = term id) while the scan's own units contribute nothing.
+ * gft_process_again finds no scan to reuse afterwards; a gft_process_device on the same handle before or after answers as ever.
+ * flags: GFT_FOLD_ASCII or 0.  GFT_E_UNSUPPORTED: a handle over several devices; a set of programs with an expression the host
+ * solves (gft_n_host_exprs > 0 -- the host solver is not fed from the kept list).  There is no _begin / _end form.
+ * gft_process_words is the host-buffer form (text_blob[0 .. doc_off[n_docs]) uploaded as gft_process uploads it). */
+int gft_process_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
+                             uint32_t* d_hit_bitmap);
+int gft_process_words(gft_engine* e, const uint8_t* text_blob, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags, uint32_t* hit_bitmap);
+/* gft_hit_spans_device with the whole-word rule: that call's spans, in count-then-fill form into buffers of the engine's, then the
+ * filter into the caller's arrays -- same signature, same cap protocol, same refusals. */
+int gft_hit_spans_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t flags,
+                               const uint32_t* d_hit_bitmap, const uint64_t* d_row_idx, const uint32_t* want, uint64_t* d_span_off,
+                               uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap, uint64_t* total);
+/* gft_batch_term_stats_device over the whole-word matches: gft_hit_spans_words_device with a bitmap, gft_scan_words_device without */
+int gft_batch_term_stats_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
+                                      const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
+                                      uint64_t* d_docs, uint64_t* d_first, int* nonascii);
+/* The filter on the host, no HIP device needed, same contract, all pointers host: the kernels' walk, entry tile by entry tile
+ * through the source they are compiled from (csrc/gft_words_piece.hpp). */
+int gft_debug_filter_word_matches(const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* off, const uint32_t* pos,
+                                  const uint32_t* len, const uint32_t* term, const uint32_t* term_len, uint32_t n_terms, uint32_t flags,
+                                  uint64_t* out_off, uint32_t* out_pos, uint32_t* out_len, uint32_t* out_term, uint64_t cap, uint64_t* total);
+/* 1 when cp is a word rune, 0 otherwise: 0 for surrogates, U+FFFD and every value above 0x10FFFF */
+uint32_t gft_debug_word_rune(uint32_t cp);
+/* where the walk's borders are: the entries a workgroup takes per step; the class table's rows of 256 bits and its bytes */
+void gft_debug_words_shape(uint32_t* tile_entries, uint32_t* table_rows, uint32_t* table_bytes);
+
 /* ---- finder.Finder mirror (finder/finder.go:32-240) ---------------------------------------------------------
  * Host-side orchestration with the reference's semantics: expression registry, keyword / regex sets, lazy engine
  * build with the same dirty flags (incl. the ForceBuild quirk, finder.go:218-235), error propagation, results in
@@ -838,6 +911,16 @@ int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, cons
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                                     uint32_t* d_hit_bitmap);
 int gft_finder_process_device_end(gft_finder* f);
+/* Whole-word matching (gft_filter_word_matches_device above).  With the option on, on the same handle:
+ * gft_finder_process_text / _texts / _texts_sparse go through gft_process_words (the sparse rows are compacted on the host),
+ * gft_finder_process_device through gft_process_words_device, the repeat on the device-lowered text included,
+ * gft_finder_hit_spans_device / _source_device through gft_hit_spans_words_device (the filter runs on the text that was scanned,
+ * before the map back to the source), gft_finder_term_stats_device through gft_batch_term_stats_words_device.  The select, route,
+ * redact, excerpt and mark calls take those calls' rows and spans and need nothing of their own.  With a foreign substring engine,
+ * regex terms or an engine over several devices each of these calls gives GFT_E_UNSUPPORTED and says which of them is the cause;
+ * gft_finder_process_device_begin gives GFT_E_UNSUPPORTED.  Off (the default) nothing changes. */
+int gft_finder_set_whole_words(gft_finder* f, int on);
+int gft_finder_whole_words(const gft_finder* f);
 /* batches that gft_finder_process_device / _end have repeated because they left ASCII, by path */
 int gft_finder_lowered_batches(const gft_finder* f, uint64_t* on_device, uint64_t* on_host);
 /* gft_compact_device on the finder's engine (d_tag_id: the tag id of every entry, or NULL): pairs with

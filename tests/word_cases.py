@@ -1,0 +1,215 @@
+"""The whole-word rule in plain Python, and the cases the word filter is tested on (host twin and device).
+
+A rune is a word rune when its general category starts with L, M or N, or is Pc.  An occurrence [s, e) of a document D is kept iff
+NOT(word(DecodeLastRune(D[:s])) and word(DecodeRune(D[s:e]))) and NOT(word(DecodeLastRune(D[s:e])) and word(DecodeRune(D[e:]))),
+with Go's utf8.DecodeRune / utf8.DecodeLastRune.  The classes come from an explicit dictionary over the alphabet below: nothing
+here depends on the Unicode version of the interpreter.  Occurrences are found with bytes.find."""
+import random
+
+import numpy as np
+
+E_INVALID, E_UNSUPPORTED = -1, -4
+RUNE_ERROR = 0xFFFD
+UTF_MAX = 4
+
+WORD = ["a", "b", "c", "_", "7", "\u00e9", "\u00df", "\u0416", "\u4e2d", "\u0301", "\u00bd", "\U0001d49c"]
+NOT_WORD = [" ", "-", "+", ".", "'", "\n", "\u00a0", "\u2014", "\u201c", "\u3001", "\U0001f600", "\ufffd"]
+INVALID = [b"\xff", b"\xa9", b"\xc3", b"\xc0\x80", b"\xed\xa0\x80", b"\xf4\x90\x80\x80"]
+CLASS = {ord(c): True for c in WORD}
+CLASS.update({ord(c): False for c in NOT_WORD})
+# (what else the tests' own sentences hold)
+CLASS.update({ord(c): True for c in "defghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ0123456789ïÉÀ"})
+CLASS.update({ord(c): False for c in "”,;:!?/()[]<>*\"#=\t\r"})
+SYMBOLS = [c.encode() for c in WORD + NOT_WORD] + INVALID
+NEIGHBOURS = [("word:" + repr(c), c.encode()) for c in WORD] + [("not:" + repr(c), c.encode()) for c in NOT_WORD] + \
+             [("bad:" + s.hex(), s) for s in INVALID]
+
+
+def decode_rune(p):
+    """utf8.DecodeRune -> (rune, size); (RUNE_ERROR, 0) for an empty slice, (RUNE_ERROR, 1) for an invalid sequence"""
+    n = len(p)
+    if n == 0:
+        return RUNE_ERROR, 0
+    b0 = p[0]
+    if b0 < 0x80:
+        return b0, 1
+    if b0 < 0xC2 or b0 > 0xF4:
+        return RUNE_ERROR, 1
+    need = 2 if b0 < 0xE0 else 3 if b0 < 0xF0 else 4
+    lo, hi = 0x80, 0xBF
+    if b0 == 0xE0:
+        lo = 0xA0
+    elif b0 == 0xED:
+        hi = 0x9F
+    elif b0 == 0xF0:
+        lo = 0x90
+    elif b0 == 0xF4:
+        hi = 0x8F
+    if n < need or not lo <= p[1] <= hi or any(p[k] & 0xC0 != 0x80 for k in range(2, need)):
+        return RUNE_ERROR, 1
+    cp = b0 & (0x1F if need == 2 else 0x0F if need == 3 else 0x07)
+    for k in range(1, need):
+        cp = cp << 6 | (p[k] & 0x3F)
+    return cp, need
+
+
+def decode_last_rune(p):
+    """utf8.DecodeLastRune, statement by statement"""
+    end = len(p)
+    if end == 0:
+        return RUNE_ERROR, 0
+    start = end - 1
+    r = p[start]
+    if r < 0x80:
+        return r, 1
+    lim = max(end - UTF_MAX, 0)
+    start -= 1
+    while start >= lim:
+        if p[start] & 0xC0 != 0x80:
+            break
+        start -= 1
+    start = max(start, 0)
+    r, size = decode_rune(p[start:end])
+    if start + size != end:
+        return RUNE_ERROR, 1
+    return r, size
+
+
+def is_word(rune_size):
+    r, size = rune_size
+    if size == 0 or r == RUNE_ERROR:
+        return False
+    return CLASS[r]                                             # (a KeyError: a case left the alphabet)
+
+
+def kept(doc, s, e):
+    if is_word(decode_last_rune(doc[:s])) and is_word(decode_rune(doc[s:e])):
+        return False
+    if is_word(decode_last_rune(doc[s:e])) and is_word(decode_rune(doc[e:])):
+        return False
+    return True
+
+
+def occurrences(doc, term):
+    out, at = [], doc.find(term)
+    while at >= 0 and term:
+        out.append(at)
+        at = doc.find(term, at + 1)
+    return out
+
+
+class Case:
+    """a batch (lead bytes, documents, slack bytes) and a list of entries (doc, start, len, term) in list order, with the arrays
+    the calls take: blob, doc_off, off (off[0] = e0 with e0 garbage entries in front), pos, length, term, term_len"""
+
+    def __init__(self, name, docs, terms, lead=b"", slack=b"", e0=0, entries=None, pos_end=False):
+        self.name, self.docs, self.terms, self.pos_end, self.e0 = name, [bytes(d) for d in docs], [bytes(t) for t in terms], pos_end, e0
+        self.lead = bytes(lead)
+        self.blob = np.frombuffer(self.lead + b"".join(self.docs) + bytes(slack) + b"a" * 64, dtype=np.uint8).copy()
+        self.doc_off = np.zeros(len(docs) + 1, dtype=np.uint64)
+        self.doc_off[0] = len(self.lead)
+        if docs:
+            self.doc_off[1:] = len(self.lead) + np.cumsum([len(d) for d in self.docs], dtype=np.uint64)
+        if entries is None:
+            # the engine's order: per document ascending by position, ties by term
+            entries = []
+            for d, doc in enumerate(self.docs):
+                here = [(s, t) for t, term in enumerate(self.terms) for s in occurrences(doc, term)]
+                entries += [(d, s, len(self.terms[t]), t) for s, t in sorted(here)]
+        self.entries = entries
+        n = len(entries)
+        self.n_docs, self.n = len(docs), n
+        self.term_len = np.array([len(t) for t in self.terms], dtype=np.uint32)
+        cnt = np.zeros(len(docs), dtype=np.uint64)
+        for d, _, _, _ in entries:
+            cnt[d] += 1
+        self.off = np.full(len(docs) + 1, e0, dtype=np.uint64)
+        if docs:
+            self.off[1:] = e0 + np.cumsum(cnt, dtype=np.uint64)
+        junk = [0x7FFFFFF0 + k for k in range(e0)]                 # (in front of off[0]: no entries, never read)
+        self.length = np.array(junk + [ln for _, _, ln, _ in entries], dtype=np.uint32)
+        self.term = np.array(junk + [t for _, _, _, t in entries], dtype=np.uint32)
+        self.pos = np.array(junk + [(s + ln - 1 if pos_end else s) & 0xFFFFFFFF for _, s, ln, _ in entries], dtype=np.uint32)
+        self.keep = [kept(self.docs[d], s, s + ln) for d, s, ln, _ in entries]
+
+    def reference(self):
+        """(out_off uint64 [n_docs + 1], pos, len, term uint32 [total])"""
+        out_off = np.zeros(self.n_docs + 1, dtype=np.uint64)
+        for (d, _, _, _), k in zip(self.entries, self.keep):
+            out_off[d + 1] += int(k)
+        out_off = np.cumsum(out_off, dtype=np.uint64)
+        idx = np.array([self.e0 + i for i, k in enumerate(self.keep) if k], dtype=np.int64)
+        return out_off, self.pos[idx], self.length[idx], self.term[idx]
+
+
+SENTENCE = "ushers he she hers naïve na “he” he—she c++x c++ x".encode()
+SENTENCE_TERMS = [b"he", b"she", b"hers", b"na", b"c++"]
+SENTENCE_KEPT = {b"he": [7, 32, 38], b"she": [10, 43], b"hers": [14], b"na": [26], b"c++": [SENTENCE.find(b"c++"), SENTENCE.rfind(b"c++")]}
+
+
+def neighbour_cases():
+    """every neighbour kind on both sides of an occurrence, for a keyword with word edges, with no word edge, and with an invalid
+    first byte; one document per pair, so the neighbours of one do not reach the next"""
+    cases = []
+    for kw in (b"ab", "éaé".encode(), b"+b+", b"\xffa"):
+        docs = [left + kw + right for _, left in NEIGHBOURS for _, right in NEIGHBOURS]
+        docs += [kw + right for _, right in NEIGHBOURS] + [left + kw for _, left in NEIGHBOURS] + [kw]
+        cases.append(Case("neighbours_%s" % kw.hex(), docs, [kw]))
+    return cases
+
+
+def border_cases(T):
+    """the cases at the document's and the walk's borders; T = tile_entries"""
+    cases = [Case("sentence", [SENTENCE], SENTENCE_TERMS)]
+    # an occurrence at a document's first and last byte with a letter just outside: the previous document, the lead, the slack
+    cases.append(Case("edges_outside", [b"xab", b"ab", b"abx", b"ab"], [b"ab"], lead=b"zzza", slack=b"bcd"))
+    cases.append(Case("edges_lead_only", [b"ab"], [b"ab"], lead=b"a", slack=b"a"))
+    # a rune cut by the document border: its halves are invalid bytes on both sides, never a letter
+    e, z = "é".encode(), "中".encode()
+    cases.append(Case("cut_rune", [b"ab" + e[:1], e[1:] + b"ab", b"ab" + z[:2], z[2:] + b"ab", z[:1] + b"ab" + z[:1], b"ab" + e[:1]], [b"ab"],
+                      lead=e[:1], slack=e[1:]))
+    cases.append(Case("cut_rune_in_term", [b"a" + e, b"a" + e[:1], e[1:] + b"a", b"a" + e[:1] + b"a"], [b"a" + e[:1], e[1:] + b"a"], slack=e[1:]))
+    # every start alignment 0..15 of the text in memory
+    for k in range(16):
+        cases.append(Case("align_%d" % k, [b"ab cab ab\xc3", b"\xa9ab", "abé éab ab".encode()], [b"ab"], lead=b"a" * k))
+    # lists of T - 1, T, T + 1 and 2T + 1 entries in one document; a document whose entries straddle a tile border
+    for n in (T - 1, T, T + 1, 2 * T + 1):
+        cases.append(Case("tile_%d" % n, [b" ".join(b"ab" if i % 3 else b"cab" for i in range(n))], [b"ab"]))
+    cases.append(Case("straddle", [b"ab " * (T - 3), b"ab-ab_ab ab7 ab", b"", b"ab " * 5], [b"ab"]))
+    # empty documents, and documents without entries between others
+    cases.append(Case("empties", [b"", b"ab", b"", b"", b"cc c", b"xabx", b"", b"ab"], [b"ab"]))
+    cases.append(Case("no_docs", [], [b"ab"]))
+    cases.append(Case("no_entries", [b"cc", b"", b"c"], [b"ab"]))
+    cases.append(Case("only_empty_docs", [b"", b"", b""], [b"ab"]))
+    # off[0] != 0; the lengths from the term table and from the entries; positions of last bytes; zero-length entries
+    cases.append(Case("off0", [b"ab ab", b"cab ab"], [b"ab"], e0=5))
+    cases.append(Case("pos_end", [SENTENCE, b"ab", b"cab ab"], SENTENCE_TERMS + [b"ab"], pos_end=True, e0=2))
+    cases.append(Case("zero_len", [b"abc", b""], [b""], entries=[(0, 0, 0, 0), (0, 1, 0, 0), (0, 3, 0, 0), (1, 0, 0, 0)]))
+    return cases
+
+
+RANDOM_TERMS = [b"ab", b"a", b"c+", b"+b", "é".encode(), "aé".encode(), b"b c", b"cab", b"\xffa"]
+
+
+def random_case(seed=20261020, n_docs=2000, max_symbols=40):
+    rng = random.Random(seed)
+    docs = [b"".join(rng.choice(SYMBOLS) for _ in range(rng.randint(0, max_symbols))) for _ in range(n_docs)]
+    return Case("random_%d" % n_docs, docs, RANDOM_TERMS, lead=b"ab\xc3", slack=b"\xa9ab")
+
+
+def check_outputs(case, total, out_off, pos, length, term, cap=None, guard=0):
+    """what a call returned for a case against the reference: the total, the complete offsets, the entries below the cap, and the
+    guard entries behind every array untouched"""
+    w_off, w_pos, w_len, w_term = case.reference()
+    assert total == len(w_pos), (case.name, total, len(w_pos))
+    assert (np.asarray(out_off[:case.n_docs + 1], dtype=np.uint64) == w_off).all(), case.name
+    n = total if cap is None else min(cap, total)
+    room = total if cap is None else cap
+    for got, want in ((pos, w_pos), (length, w_len), (term, w_term)):
+        if got is None:
+            continue
+        got = np.asarray(got).view(np.uint32) if np.asarray(got).dtype == np.int32 else np.asarray(got, dtype=np.uint32)
+        assert (got[:n] == want[:n]).all(), case.name
+        assert (got[n:room + guard] == 0xA5A5A5A5).all() or room + guard == n, (case.name, "stored at or past the cap")
+    if guard:
+        assert (np.asarray(out_off[case.n_docs + 1:]) == 0xA5A5A5A5A5A5A5A5).all(), case.name
