@@ -185,6 +185,13 @@ SYMBOLS = {
     "gft_debug_mark_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_mark_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp,
                                    C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_replace_spans_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                     _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_replace_spans": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp,
+                                    _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_replace_shape": (None, [C.POINTER(_u32)] * 6),
+    "gft_finder_replace_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp,
+                                      _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
     "gft_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _u32, _u32, _u64, _vp, _vp, _vp]),
     "gft_count_columns_device": (_i, [_vp, _vp, _u64, _u32, _vp, _u32, _vp]),
     "gft_batch_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),

@@ -677,6 +677,37 @@ Error Finder::MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint6
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::ReplaceDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
+                            const uint32_t* d_span_len, bool spans_lowered, bool source, const uint32_t* d_span_term, const uint32_t* term_rep,
+                            const uint8_t* rep_bytes, const uint64_t* rep_off, uint32_t n_reps, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
+                            uint64_t* d_out_off, uint64_t* d_doc_run_off, uint32_t* d_run_new, uint32_t* d_run_len, uint32_t* d_run_rep,
+                            uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes, int* lowered) {
+    last_code_ = 0;
+    if (lowered) *lowered = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    const uint8_t* d_text = d_blob;
+    const uint64_t* d_off = d_doc_off;
+    // spans that index the lowered text replace in the lowered text: lowered again here, as the spans call lowered it
+    if (spans_lowered && !source && n_docs) {
+        if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+            last_code_ = GFT_E_UNSUPPORTED;
+            return "replacements in a lowered batch need a case-insensitive finder with the device ToLower on a single device";
+        }
+        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_text, &d_off);
+        if (rc) return fail_gft(rc);
+        if (lowered) *lowered = 1;
+    }
+    // without a term map every span asks for id 0, whatever its term
+    int rc = gft_replace_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, term_rep ? d_span_term : nullptr,
+                                      term_rep, gft_n_terms(gpu_->handle()), rep_bytes, rep_off, n_reps, flags, d_out, cap_bytes, d_out_off,
+                                      d_doc_run_off, d_run_new, d_run_len, d_run_rep, cap_runs, n_runs, total_bytes);
+    return rc ? fail_gft(rc) : Error();
+}
+
 Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
                               uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first, int* lowered) {
     last_code_ = 0;
@@ -1055,6 +1086,20 @@ int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint
     return finder_ret(f, f->finder->MarkDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
                                                open, open_len, close, close_len, flags, d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, n_runs,
                                                total_bytes, lowered), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_replace_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                              const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered, int source, const uint32_t* d_span_term,
+                              const uint32_t* term_rep, const uint8_t* rep_bytes, const uint64_t* rep_off, uint32_t n_reps, uint32_t flags,
+                              uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_run_off, uint32_t* d_run_new,
+                              uint32_t* d_run_len, uint32_t* d_run_rep, uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes,
+                              int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->ReplaceDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
+                                                  d_span_term, term_rep, rep_bytes, rep_off, n_reps, flags, d_out, cap_bytes, d_out_off,
+                                                  d_doc_run_off, d_run_new, d_run_len, d_run_rep, cap_runs, n_runs, total_bytes, lowered),
+                      GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,

@@ -156,6 +156,13 @@ public:
                      const uint32_t* d_span_len, bool spans_lowered, bool source, const uint8_t* open, uint32_t open_len, const uint8_t* close,
                      uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint32_t* d_span_new,
                      uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes, int* lowered);
+    // gft_replace_spans_device on the finder's engine behind HitSpansDevice, under MarkDevice's rule; term_rep: host, a replacement id
+    // per term of the engine, NULL: id 0 for every term
+    Error ReplaceDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
+                        const uint32_t* d_span_len, bool spans_lowered, bool source, const uint32_t* d_span_term, const uint32_t* term_rep,
+                        const uint8_t* rep_bytes, const uint64_t* rep_off, uint32_t n_reps, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
+                        uint64_t* d_out_off, uint64_t* d_doc_run_off, uint32_t* d_run_new, uint32_t* d_run_len, uint32_t* d_run_rep,
+                        uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes, int* lowered);
     // gft_batch_term_stats_device on the finder's engine under the case rule of HitSpansDevice: a batch that leaves ASCII is lowered
     // on the device and counted from there -- *lowered = 1; an accumulating array sees every batch once
     Error TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,

@@ -217,6 +217,10 @@ struct gft_engine {
     // highlight (gft_mark.hip): the run passes work in the excerpt's buffers; the insertion list and the marker block are its own
     struct MarkBufs { DevBuf q, marks; } d_mark;
 
+    // replace (gft_replace.hip): the run passes work in the excerpt's buffers; every run's smallest id, the heads' replacement
+    // lengths and their prefix sum, the call's copies of the key map and the table, and the plan are its own
+    struct ReplaceBufs { DevBuf rid, pl, ppos, key_rep, rep_off, tab, at, delta, len, roff; } d_replace;
+
     // term statistics and column counts (gft_stats.hip): the check pass's flag words, the workgroups' bitset rows for dictionaries
     // whose bitset leaves LDS, and the span CSR of the kept matches that gft_batch_term_stats_device counts (the starts are what
     // gft_hit_spans_device asks for with any cap; they are not read)

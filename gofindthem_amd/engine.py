@@ -570,6 +570,126 @@ def mark_shape():
     return tuple(int(x.value) for x in v)
 
 
+REPLACE_MAX = 255                                   # GFT_REPLACE_MAX
+REPLACE_MAX_REPS = 65536
+
+
+def replace_table(reps):
+    """a list of replacements (bytes each; one bytes object: a table of one) -> (rep_bytes, rep_off uint64 [n + 1]) as the replace
+    calls take them"""
+    if isinstance(reps, (bytes, bytearray, memoryview)):
+        reps = [reps]
+    reps = [bytes(r) for r in reps]
+    off = np.zeros(len(reps) + 1, dtype=np.uint64)
+    if reps:
+        off[1:] = np.cumsum([len(r) for r in reps], dtype=np.uint64)
+    return b"".join(reps), off
+
+
+def replace_spans_tensor(call, text, doc_off, span_off, start, length, reps=b"[REDACTED]", key=None, key_rep=None):
+    """what Engine.replace_spans_device and Finder.ReplaceDevice share: `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start,
+    d_span_len, d_span_key, key_rep, n_keys, rep_bytes, rep_off, n_reps, flags, d_out, cap_bytes, d_out_off, d_doc_run_off, d_run_new,
+    d_run_len, d_run_rep, cap_runs, byref(n_runs), byref(total))` is gft_replace_spans_device on some handle and raises on an error.
+    Two calls: count only with NULL outputs, then into tensors of exactly the sizes counted.  Returns (out uint8 [total] -- the
+    replaced documents back to back, a view with 64 zero bytes behind it --, out_off int64 [n + 1], doc_run_off int64 [n + 1],
+    run_new, run_len, run_rep int32 [runs])"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    checks = [(text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")]
+    if key is not None:
+        checks.append((key, 4, "key"))
+    for t, size, what in checks:
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("replace_spans_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel() or (key is not None and key.numel() != start.numel()):
+        raise ValueError("replace_spans_device: doc_off, span_off and the span arrays do not describe the same batch")
+    rep_bytes, rep_off = replace_table(reps)
+    kr = None if key_rep is None else np.ascontiguousarray(key_rep, dtype=np.uint32)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
+            length.data_ptr() if length.numel() else None, key.data_ptr() if key is not None and key.numel() else None,
+            _p(kr) if kr is not None else None, kr.size if kr is not None else 0, rep_bytes or None, _p(rep_off), rep_off.size - 1, 0)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+    dev = text.device
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, None, 0, None, None, None, None, None, 0, C.byref(m), C.byref(total))
+    nb, nr = int(total.value), int(m.value)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=dev)          # (64 bytes of slack: the result is a blob for the next call)
+    out_off, doc_run_off = (torch.empty(n_docs + 1, dtype=torch.int64, device=dev) for _ in range(2))
+    run_new, run_len, run_rep = (torch.zeros(nr, dtype=torch.int32, device=dev) for _ in range(3))
+    torch.cuda.current_stream(dev).synchronize()
+    call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_run_off.data_ptr(), *((t.data_ptr() if nr else None) for t in (run_new, run_len, run_rep)),
+         nr, C.byref(m), C.byref(total))
+    return buf[:nb], out_off, doc_run_off, run_new, run_len, run_rep
+
+
+REPLACE_OUTPUTS = ("out", "out_off", "doc_run_off", "run_new", "run_len", "run_rep")
+
+
+def replace_spans_host(blob, doc_off, span_off, start, length, reps=b"[REDACTED]", key=None, key_rep=None, cap_bytes=None, cap_runs=None,
+                       guard=0, flags=0, omit=(), count_only=False, shift=0, table=None, n_keys=None):
+    """gft_debug_replace_spans over host arrays -> a dict: n_runs, total, out uint8 [cap_bytes + guard], out_off / doc_run_off uint64
+    [n + 1 + guard], run_new / run_len / run_rep uint32 [cap_runs + guard]; no device needed.  A cap None: count first, then exactly
+    what the result needs; the guard entries behind hold 0xA5.. and must come back untouched.  omit: names of outputs passed as NULL
+    (they come back as None).  key: the spans' keys, parallel to start (None: NULL); key_rep: the key map (None: NULL), n_keys: the
+    count to pass instead of its own.  table: (rep_bytes or None, rep_off, n_reps) to pass as they are instead of `reps`.  shift:
+    bytes the output's first byte lies behind a 16-byte border"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
+    st, ln = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(length, dtype=np.uint32)
+    ky = None if key is None else np.ascontiguousarray(key, dtype=np.uint32)
+    kr = None if key_rep is None else np.ascontiguousarray(key_rep, dtype=np.uint32)
+    nk = (kr.size if kr is not None else 0) if n_keys is None else int(n_keys)
+    n_docs = off.size - 1
+    if table is None:
+        rep_bytes, rep_off = replace_table(reps)
+        n_reps = rep_off.size - 1
+    else:
+        rep_bytes, rep_off, n_reps = table
+        rep_off = None if rep_off is None else np.ascontiguousarray(rep_off, dtype=np.uint64)
+    m, total = C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cb, oo, dro, rn, rl, rr, cr):
+        rc = L.gft_debug_replace_spans(_p(a) if a.size else None, _p(off), n_docs, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None,
+                                       _p(ky) if ky is not None and ky.size else None, _p(kr) if kr is not None and kr.size else None, nk,
+                                       rep_bytes or None, _p(rep_off), int(n_reps), int(flags), _p(out), cb, _p(oo), _p(dro), _p(rn), _p(rl),
+                                       _p(rr), cr, C.byref(m), C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_replace_spans")
+    if cap_bytes is None or cap_runs is None or count_only:
+        call(None, 0, None, None, None, None, None, 0)
+        cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
+        cap_runs = int(m.value) if cap_runs is None else cap_runs
+    r = {"n_runs": int(m.value), "total": int(total.value)}
+    if count_only:
+        return r
+    big = 0xA5A5A5A5A5A5A5A5
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    lead = (-raw.ctypes.data) % 16 + int(shift)
+    arrs = {"out": raw[lead:lead + cap_bytes + guard], "out_off": np.full(n_docs + 1 + guard, big, dtype=np.uint64),
+            "doc_run_off": np.full(n_docs + 1 + guard, big, dtype=np.uint64)}
+    for k in ("run_new", "run_len", "run_rep"):
+        arrs[k] = np.full(cap_runs + guard, 0xA5A5A5A5, dtype=np.uint32)
+    for k in omit:
+        arrs[k] = None
+    for k in ("out", "run_new", "run_len", "run_rep"):
+        if arrs[k] is not None and arrs[k].size == 0:
+            arrs[k] = None
+    r.update(arrs)
+    call(arrs["out"], cap_bytes if arrs["out"] is not None else 0, arrs["out_off"], arrs["doc_run_off"], arrs["run_new"], arrs["run_len"],
+         arrs["run_rep"], cap_runs)
+    r.update(n_runs=int(m.value), total=int(total.value))
+    return r
+
+
+def replace_shape():
+    """(spans of a tile of the run passes' suffix-minimum scan, tiles of one carry trip, bytes of a lane's chunk of the output, bytes
+    of a wave's tile, plan entries of a wave's window, bytes of a table that goes into LDS) (gft_debug_replace_shape)"""
+    v = [C.c_uint32(0) for _ in range(6)]
+    _lib.load().gft_debug_replace_shape(*(C.byref(x) for x in v))
+    return tuple(int(x.value) for x in v)
+
+
 STATS_SHAPE_FIELDS = ("step_entries", "step_docs", "set_slots", "cache_slots", "large_entries", "bitset_lds_terms", "range_weight", "column_rows")
 
 
@@ -959,6 +1079,40 @@ class Engine:
     def mark_shape():
         """(tile_spans, trip_tiles, chunk_bytes, tile_bytes) of the highlight's walk (gft_debug_mark_shape)"""
         return mark_shape()
+
+    # -- every hit run rewritten by its replacement (csrc/gft_replace.hip) -------------------------------------------------------
+    def replace_spans_device(self, text, doc_off, span_off, start, length, reps=b"[REDACTED]", key=None, key_rep=None):
+        """the batch's text with every run of hits replaced, written on the device (gft_replace_spans_device).  text, doc_off: the
+        batch the spans index; span_off, start, length: what hit_spans_device returned for it, map_spans_to_source_device rewrote, or
+        the excerpt, the mark or this call handed back for its own blob.  reps: one bytes object or a list of them, the table -- 0 ..
+        255 bytes each, b"" deletes; key: an int32 device tensor parallel to start (hit_spans_device's term ids, say), None: every
+        span asks for table entry 0; key_rep: a host array key -> table entry, None: the key is the entry.  A run of spans that
+        overlap or touch gets the smallest entry its spans ask for.  Returns device tensors (out uint8 [total] -- the replaced
+        documents back to back, a view with 64 zero bytes behind it --, out_off int64 [n + 1], doc_run_off int64 [n + 1], run_new,
+        run_len, run_rep int32 [runs]); (out, out_off, doc_run_off, run_new, run_len) is what redact_spans_device,
+        excerpt_spans_device, mark_spans_device and this call take.  The call runs twice: count only, then into tensors of exactly
+        those sizes"""
+        return replace_spans_tensor(lambda *a: self._check(self._L.gft_replace_spans_device(self._h, *a)), text, doc_off, span_off, start, length,
+                                    reps, key, key_rep)
+
+    @staticmethod
+    def replace_spans_tensor(call, text, doc_off, span_off, start, length, reps=b"[REDACTED]", key=None, key_rep=None):
+        """the module's replace_spans_tensor: the count call and the fill call round any gft_replace_spans_device-shaped `call`"""
+        return replace_spans_tensor(call, text, doc_off, span_off, start, length, reps, key, key_rep)
+
+    @staticmethod
+    def replace_spans_host(blob, doc_off, span_off, start, length, reps=b"[REDACTED]", key=None, key_rep=None):
+        """the host twin of replace_spans_device over numpy arrays (gft_debug_replace_spans): the same tuple, as numpy arrays"""
+        r = replace_spans_host(blob, doc_off, span_off, start, length, reps, key, key_rep)
+        z = np.zeros(0, dtype=np.uint32)
+        return (r["out"][:r["total"]] if r["out"] is not None else np.zeros(0, dtype=np.uint8), r["out_off"], r["doc_run_off"],
+                r["run_new"] if r["run_new"] is not None else z, r["run_len"] if r["run_len"] is not None else z,
+                r["run_rep"] if r["run_rep"] is not None else z)
+
+    @staticmethod
+    def replace_shape():
+        """(tile_spans, trip_tiles, chunk_bytes, tile_bytes, window, lds_table) of the replacement's walk (gft_debug_replace_shape)"""
+        return replace_shape()
 
     # -- term statistics and column counts (csrc/gft_stats.hip) ----------------------------------------------------------------
     def term_stats_raw(self, d_off_ptr, d_term_ptr, n_docs, n_terms, flags, doc_base, d_occ_ptr, d_docs_ptr, d_first_ptr):

@@ -613,6 +613,82 @@ class Finder:
         out = self.MarkDevice(buf, off, span_off, start, length, lowered, source, open, close)[0]
         return out.cpu().numpy().tobytes(), lowered
 
+    # -- every hit run rewritten by its replacement (csrc/gft_replace.hip) ------------------------------------------------------------
+    def ReplaceDevice(self, text, doc_off, span_off, start, length, term=None, lowered=False, source=False, reps=b"[REDACTED]", term_rep=None):
+        """Engine.replace_spans_device on the finder's engine behind SpansDevice (gft_finder_replace_device): text, doc_off the batch,
+        span_off / start / length / term and `lowered` what SpansDevice returned for it, source as it was called.  With source, or
+        for a batch that was not lowered, the caller's text is replaced; otherwise the batch's lower-case form, which the finder
+        lowers on the device again.  reps: the table (one bytes object or a list); term_rep: a host array with a table entry per term
+        of the engine, None: entry 0 for every term.  Returns (out, out_off, doc_run_off, run_new, run_len, run_rep,
+        replaced_lowered) -- device tensors as Engine.replace_spans_device gives them, and whether the lowered text was replaced.
+        Needs what ProcessDevice needs"""
+        from .engine import _p, replace_spans_tensor
+        low = C.c_int(0)
+        tr = None if term_rep is None else np.ascontiguousarray(term_rep, dtype=np.uint32)
+        if tr is not None and tr.size != int(self._L.gft_n_terms(self.engine_handle())):
+            raise ValueError("ReplaceDevice: term_rep needs an entry per term of the engine")
+
+        def call(d_text, d_off, n, d_so, d_st, d_ln, d_key, _key_rep, _n_keys, *rest):
+            self._check(self._L.gft_finder_replace_device(self._h, d_text, d_off, n, d_so, d_st, d_ln, 1 if lowered else 0, 1 if source else 0,
+                                                          d_key, _p(tr), *rest, C.byref(low)))
+        out = replace_spans_tensor(call, text, doc_off, span_off, start, length, reps, term if tr is not None else None)
+        return out + (bool(low.value),)
+
+    def _replace_table(self, with_):
+        """with_ of ReplaceLines -> (the table, a table entry per term of the engine or None)"""
+        if isinstance(with_, (bytes, bytearray, memoryview)):
+            return [bytes(with_)], None
+        self.ForceBuild()                                           # (the dictionary of the expressions added so far: what the scan will use)
+        eng = self.engine_handle()
+        tp, tl = C.c_void_p(), C.c_uint32()
+        terms = {}
+        for t in range(int(self._L.gft_n_terms(eng))):
+            self._check_engine(self._L.gft_term(eng, t, C.byref(tp), C.byref(tl)))
+            terms[C.string_at(tp.value, tl.value)] = t
+        default = bytes(with_.get(None, b"[REDACTED]"))
+        reps, ids = [], {}
+        term_rep = np.full(len(terms), -1, dtype=np.int64)
+        for kw, rep in with_.items():
+            if kw is None:
+                continue
+            rep = bytes(rep)
+            if rep not in ids:
+                ids[rep] = len(reps)
+                reps.append(rep)
+            key = kw.encode("utf-8") if isinstance(kw, str) else bytes(kw)
+            t = terms.get(key)
+            if t is None:                                           # (a case-insensitive finder holds its keywords lowered)
+                t = terms.get(key.decode("utf-8", "surrogateescape").lower().encode("utf-8", "surrogateescape"))
+            if t is None:
+                raise ValueError("ReplaceLines: %r is no keyword of this finder" % (kw,))
+            term_rep[t] = ids[rep]
+        if default not in ids:
+            ids[default] = len(reps)
+            reps.append(default)
+        term_rep[term_rep < 0] = ids[default]
+        return reps, term_rep.astype(np.uint32)
+
+    def ReplaceLines(self, data, with_=b"[REDACTED]", want=None, source=True):
+        """bytes -> (bytes, lowered): the blob with every keyword occurrence that is a witness of a true, wanted expression replaced;
+        occurrences that overlap or touch are replaced together, once.  with_: bytes, one replacement for every keyword (b"" deletes),
+        or a dict {keyword: bytes}; its optional key None is the default for the keywords it does not name, b"[REDACTED]" without
+        it.  Distinct byte strings become table entries in the dict's insertion order, the default last: where occurrences of
+        several keywords form one run, the run gets the replacement that comes first in the dict.  A keyword the finder's dictionary
+        does not hold is a ValueError.  One upload, then split, process, spans and the replacement on the device, one download of
+        the replaced blob.  lowered True: the batch left ASCII; with source=True (the default) the caller's bytes are replaced all
+        the same (the spans are mapped back to them), with source=False the lines' lower-case form.  Device route only, as
+        SpansLines: a finder with regex terms, an injected engine or several devices has no host route to the spans and is refused
+        with GFT_E_UNSUPPORTED before anything is uploaded"""
+        data = bytes(data)
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "ReplaceLines needs the device route, as the hit spans do: the GPU substring engine, no "
+                                                      "regex terms, one device")
+        reps, term_rep = self._replace_table(with_)
+        buf = self._resident(data)
+        off, _, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want, source)
+        out = self.ReplaceDevice(buf, off, span_off, start, length, term, lowered, source, reps, term_rep)[0]
+        return out.cpu().numpy().tobytes(), lowered
+
     # -- documents routed to one bucket per tag (csrc/gft_route.hip) -----------------------------------------------------------
     def route_masks(self, buckets=None):
         """the host masks of the route calls: a list of want_mask() rows, one per bucket.  None: one bucket per tag in tag-id order

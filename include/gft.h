@@ -649,6 +649,72 @@ int gft_debug_mark_spans(const uint8_t* blob, const uint64_t* doc_off, uint64_t 
  * lane's chunk of the output and of a wave's tile */
 void gft_debug_mark_shape(uint32_t* tile_spans, uint32_t* trip_tiles, uint32_t* chunk_bytes, uint32_t* tile_bytes);
 
+/* ---- Replace on the device: every hit run rewritten by its replacement (csrc/gft_replace.hip) --------------------------------
+ * The fourth thing to do about a hit, beside masking it (gft_redact_spans_device), marking it (gft_mark_spans_device) and cutting
+ * the text round it (gft_excerpt_spans_device): every run of hits becomes a placeholder -- [NAME], <host>, [KEY:aws] -- or is
+ * deleted; strings.NewReplacer over the spans.  Every run changes the text by its own amount, which may be negative.  No scan, no
+ * dictionary, no programs; gft_last_nonascii is left alone.
+ * Input: the batch under the scans' placement contract (no alignment, d_doc_off[0] may be non-zero, 64 readable bytes of slack;
+ * neither the lead bytes nor the slack change the answer), and a span CSR as gft_hit_spans_device wrote it,
+ * gft_map_spans_to_source_device rewrote it, or the excerpt, the mark or this call handed it back for its own blob;
+ * d_span_off[0] != 0 is valid.  The order rule and the in-document rule are the excerpt's: within a document start + len must not
+ * descend, and start + len <= L.  flags must be 0.
+ * Runs: gft_mark_spans_device's definition, word for word: the runs of a document are the connected components of the union of
+ * its spans [start, start + len); spans that overlap, nest, repeat or touch (a.end == b.start) are one run, a gap of one byte
+ * separates two; a run never crosses a document border; a len == 0 span that touches nothing is a run of no bytes.
+ * The table, HOST memory, copied by the call: n_reps replacements, 1 .. 65536; replacement k is rep_bytes[rep_off[k] ..
+ * rep_off[k + 1]), 0 .. GFT_REPLACE_MAX bytes, rep_off[0] == 0; length 0 deletes.  rep_bytes may be NULL when every length is 0.
+ * Which replacement a span asks for: with d_span_key NULL (device, parallel to d_span_start: the entries [d_span_off[0],
+ * d_span_off[n_docs]) are read) id 0; otherwise key = d_span_key[i], and the id is the key itself when key_rep is NULL and
+ * key_rep[key] when it is given (HOST memory, n_keys entries, copied by the call; key < n_keys must hold).  The id must be below
+ * n_reps.  d_span_term of gft_hit_spans_device is a valid d_span_key.  A run gets the SMALLEST id among its spans -- the table's
+ * order is the priority --, which does not depend on the order of the spans in the list (the scan's canonical order is end
+ * ascending: a run's first listed span is not its leftmost).
+ * Output text: document d becomes its own bytes with every run replaced by its replacement; the bytes outside the runs are kept
+ * byte for byte and in order; a run of no bytes at p gets its replacement inserted at p.  The documents stand back to back in
+ * input order; a document's new length is L - (its runs' bytes) + (their replacements' bytes).
+ * Index outputs, device memory, each nullable on its own: d_out_off [n_docs + 1] (d_out_off[0] = 0), the doc_off of d_out;
+ * d_doc_run_off [n_docs + 1], the documents' CSR over the runs -- these two are never capped --; per run, in batch order and
+ * capped by cap_runs: d_run_new, the replacement's first byte in its new document, d_run_len, the replacement's length, and
+ * d_run_rep, the id chosen.  (d_out, d_out_off, n_docs, d_doc_run_off, d_run_new, d_run_len) is by construction a valid span
+ * list of the redaction, the excerpt, the mark and this call on the replaced text: the placeholders can be highlighted, or the
+ * text round them cut.
+ * Cap protocol of gft_compact_device, two caps as in the excerpt call: cap_bytes counts bytes of d_out, cap_runs entries of the
+ * three per-run arrays; nothing is stored at or past any array plus its cap; with all outputs NULL and both caps 0 the call only
+ * counts; GFT_OK either way, and *n_runs / *total_bytes (host, nullable) are always handed back.
+ * Launches on the engine's stream (gft_profile_read): "replace_runs" (the span checks, the suffix minimum and the heads: the
+ * excerpt's passes), "replace_ids" (the prefix sum of the heads, every run's smallest id, the heads' replacement lengths),
+ * "replace_scan" (the prefix sums of the runs' bytes and of the replacements' bytes; the new lengths checked), "replace_place"
+ * (the index outputs and the plan: per run where its replacement begins in the output, the shift of the text behind it, its
+ * length and its place in the table), "replace_copy" (from the output side: a wave a 4 KiB tile, a lane a 16-byte chunk; a table
+ * of 4 KiB or less in LDS, a larger one read from L2).  The call waits for the stream.  Between gft_process_device_begin and _end
+ * it is allowed only after _complete.  n_docs == 0 and no spans are valid: the output is then a copy of the text.
+ * GFT_E_UNSUPPORTED: a handle over several devices.  GFT_E_INVALID: flags != 0; n_reps == 0 or above 65536; a replacement longer
+ * than GFT_REPLACE_MAX; a rep_off that descends or has rep_off[0] != 0; a key >= n_keys or an id >= n_reps (found on the device,
+ * like the order and the in-document violations); an output that overlaps an input or another output; document or span offsets
+ * that descend; a document of 4 GiB or more, or one that would reach 4 GiB once replaced.  GFT_E_NOMEM: no room for the work
+ * buffers (72 bytes a span, 24 a run, and the table: its bytes, 8 an entry, 4 a key).  Every refusal comes before any store, and
+ * the handle stays usable after any error. */
+#define GFT_REPLACE_MAX 255u   /* bytes of one replacement */
+int gft_replace_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                             const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len,
+                             const uint32_t* d_span_key, const uint32_t* key_rep, uint32_t n_keys, const uint8_t* rep_bytes,
+                             const uint64_t* rep_off, uint32_t n_reps, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
+                             uint64_t* d_out_off, uint64_t* d_doc_run_off, uint32_t* d_run_new, uint32_t* d_run_len, uint32_t* d_run_rep,
+                             uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes);
+/* The host form, no HIP device needed, same contract, all pointers host (the 64 bytes of slack are not asked for here): the
+ * runs by the excerpt's host walk, the copy tile by tile, trip by trip and lane by lane through the source the kernels are
+ * compiled from (csrc/gft_replace_piece.hpp). */
+int gft_debug_replace_spans(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                            const uint32_t* span_start, const uint32_t* span_len, const uint32_t* span_key, const uint32_t* key_rep,
+                            uint32_t n_keys, const uint8_t* rep_bytes, const uint64_t* rep_off, uint32_t n_reps, uint32_t flags,
+                            uint8_t* out, uint64_t cap_bytes, uint64_t* out_off, uint64_t* doc_run_off, uint32_t* run_new,
+                            uint32_t* run_len, uint32_t* run_rep, uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes);
+/* where that walk's borders are: the spans of a tile of the suffix-minimum scan, the tiles of one carry trip, the bytes of a
+ * lane's chunk of the output and of a wave's tile, the plan entries of a wave's window, the bytes of a table that goes into LDS */
+void gft_debug_replace_shape(uint32_t* tile_spans, uint32_t* trip_tiles, uint32_t* chunk_bytes, uint32_t* tile_bytes, uint32_t* window,
+                             uint32_t* lds_table);
+
 /* ---- Term statistics on the device: how often each keyword hit, in how many documents, and where first -----------------
  * The histogram of a term list in CSR form on the engine's device: the entries of document d are d_term[d_off[d] .. d_off[d + 1]);
  * d_off[0] may be non-zero (a run of documents cut from a larger batch).  The arguments are (match_off, term_id) of
@@ -897,6 +963,17 @@ int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint
                            uint32_t open_len, const uint8_t* close, uint32_t close_len, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes,
                            uint64_t* d_out_off, uint32_t* d_span_new, uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes,
                            int* lowered);
+/* gft_replace_spans_device on the finder's engine, under the rule of gft_finder_mark_device: with source, or for a batch that was
+ * not lowered, the caller's text is replaced; otherwise the finder lowers the batch on the device again, replaces in that text and
+ * sets *lowered = 1 (else 0).  d_span_term: the term ids gft_finder_hit_spans_device wrote (device, nullable: id 0 for every
+ * span); term_rep: HOST memory, gft_n_terms entries of the finder's engine, term -> replacement id, nullable -- NULL means id 0
+ * for every term.  Everything else is gft_replace_spans_device's contract. */
+int gft_finder_replace_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,
+                              const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered, int source,
+                              const uint32_t* d_span_term, const uint32_t* term_rep, const uint8_t* rep_bytes, const uint64_t* rep_off,
+                              uint32_t n_reps, uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_run_off,
+                              uint32_t* d_run_new, uint32_t* d_run_len, uint32_t* d_run_rep, uint64_t cap_runs, uint64_t* n_runs,
+                              uint64_t* total_bytes, int* lowered);
 /* Term statistics of a resident batch on the finder's engine under the finder's case rule, as gft_finder_hit_spans_device runs:
  * a batch that leaves ASCII is lowered on the device first and *lowered set to 1 (term ids do not depend on positions: nothing is
  * mapped back).  d_hit_bitmap non-NULL: the statistics of the KEPT matches -- the witness occurrences of true, wanted expressions
