@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch  # noqa: F401  (before libgft.so is loaded: one HIP runtime)
 
+import far_text as F
 import json_docs as J
 import select_docs as S
 import split_lines as SL
@@ -235,17 +236,24 @@ def test_handles_over_several_devices_are_refused():
 
 def test_an_output_past_four_gib(eng):
     """70 documents of 64 MiB, all but three selected: the output positions pass 2^32, the one place a 32-bit offset would hide.
-    Every byte is a cheap function of its position in the text"""
+    Every byte is the top byte of its 64-bit position times far_text.GOLDEN, which depends on every bit of the position: no two
+    documents, and no two positions 2^32 apart, hold the same bytes (the ramp this replaces repeated every 2 MiB, so every
+    document held the same bytes and the copy of a wrong document, or from a source position cut to 32 bits, passed)"""
     n, size = 70, 64 << 20
     text = torch.empty(n * size + 64, dtype=torch.uint8, device="cuda")
     ramp = torch.arange(size, dtype=torch.int64, device="cuda")
     for k in range(n):
-        text[k * size:(k + 1) * size] = ((((ramp + k * size) * 2654435761) >> 13) & 0xFF).to(torch.uint8)
+        text[k * size:(k + 1) * size] = F.top_byte_torch(ramp + k * size).to(torch.uint8)
     del ramp
+    assert text[(1 << 32) - 512:(1 << 32) + 512].cpu().numpy().tobytes() == F.top_byte(np.arange((1 << 32) - 512, (1 << 32) + 512)).tobytes()
     off = torch.arange(n + 1, dtype=torch.int64, device="cuda") * size
     rows = torch.full((n, 1), -2, dtype=torch.int32, device="cuda")                 # column 0 clear, the tail bits ones
     keep = [k for k in range(n) if k not in (0, 35, 69)]
     rows[keep, 0] = -1
+    # two different source documents differ in their first KiB, and so do positions 2^32 apart (with the old ramp neither held)
+    for a in range(n - 1):
+        assert not torch.equal(text[a * size:a * size + 1024], text[(a + 1) * size:(a + 1) * size + 1024]), a
+    assert not torch.equal(text[:1024], text[35 * size:35 * size + 1024]) and not torch.equal(text[size:size + 1024], text[65 * size:65 * size + 1024])
     out, out_off, doc_idx = eng.select_docs_device(text, off, rows, 1, None, "any")
     assert doc_idx.cpu().tolist() == keep and out_off.cpu().tolist() == [k * size for k in range(len(keep) + 1)]
     assert out.numel() == len(keep) * size > 1 << 32
