@@ -156,6 +156,13 @@ SYMBOLS = {
     "gft_select_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_debug_select_docs": (_i, [_vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_debug_select_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gft_context_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64,
+                                     C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_context_docs": (_i, [_vp, _vp, _u64, _vp, _u32, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64,
+                                    C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_context_shape": (None, [C.POINTER(_u32), C.POINTER(_u32), C.POINTER(_u32)]),
+    "gft_finder_context_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _u64,
+                                            C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_finder_select_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "gft_route_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),
     "gft_debug_route_docs": (_i, [_vp, _vp, _u64, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp]),

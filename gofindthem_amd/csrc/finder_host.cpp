@@ -561,6 +561,23 @@ Error Finder::SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off,
     return rc ? fail_gft(rc) : Error();
 }
 
+Error Finder::ContextDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                                uint32_t mode, const uint8_t* d_also, uint64_t before, uint64_t after, const uint8_t* d_fence, uint8_t* d_out,
+                                uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint8_t* d_kind, uint64_t cap_docs,
+                                uint64_t* d_group_off, uint64_t cap_groups, uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups,
+                                uint64_t* total_bytes) {
+    last_code_ = 0;
+    if (!gpu_sub_ || !regexes_.empty()) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "device-resident processing needs the GPU substring engine and no regex terms";
+    }
+    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    int rc = gft_context_docs_device(gpu_->handle(), d_blob, d_doc_off, n_docs, d_bitmap, (uint32_t)expressions_.size(), want, mode, d_also, before,
+                                     after, d_fence, d_out, cap_bytes, d_out_off, d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups, n_kept,
+                                     n_hits, n_groups, total_bytes);
+    return rc ? fail_gft(rc) : Error();
+}
+
 Error Finder::RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* masks,
                               uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,
                               uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte) {
@@ -1033,6 +1050,18 @@ int gft_finder_select_docs_device(gft_finder* f, const uint8_t* d_text_blob, con
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->SelectDocsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, mode, d_also, d_out, cap_bytes, d_out_off,
                                                      d_doc_idx, cap_docs, n_selected, total_bytes), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_context_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                   const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint64_t before,
+                                   uint64_t after, const uint8_t* d_fence, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off,
+                                   uint64_t* d_doc_idx, uint8_t* d_kind, uint64_t cap_docs, uint64_t* d_group_off, uint64_t cap_groups,
+                                   uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups, uint64_t* total_bytes) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->ContextDocsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, mode, d_also, before, after, d_fence, d_out,
+                                                      cap_bytes, d_out_off, d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups, n_kept, n_hits,
+                                                      n_groups, total_bytes), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,

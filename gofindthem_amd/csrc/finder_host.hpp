@@ -132,6 +132,11 @@ public:
     Error SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
                            uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
                            uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
+    // gft_context_docs_device on the finder's engine (n_cols = the expressions): what SelectDocsDevice asks, refused in its words
+    Error ContextDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                            uint32_t mode, const uint8_t* d_also, uint64_t before, uint64_t after, const uint8_t* d_fence, uint8_t* d_out,
+                            uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint8_t* d_kind, uint64_t cap_docs, uint64_t* d_group_off,
+                            uint64_t cap_groups, uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups, uint64_t* total_bytes);
     // gft_route_docs_device on the finder's engine (n_cols = the expressions): what SelectDocsDevice asks, refused in its words
     Error RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* masks,
                           uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,

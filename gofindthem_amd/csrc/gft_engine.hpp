@@ -189,6 +189,12 @@ struct gft_engine {
     // prefix sums, scan partials and read-back words of its own, and the compact offsets the copy pass searches
     struct SelectBufs { DevBuf want, len, sel, pos, rank, partial, ctl, c_off, c_src; } d_select;
 
+    // context lines round the documents that matched (gft_context.hip): the mask, the marks of a batch (then its group heads), the
+    // tiles' ballot words with what they say to the other tiles, the carries of the tiles and of the carry blocks, the keep flags
+    // and lengths, the three prefix sums with scan partials and read-back words of its own, and the compact offsets the select's
+    // copy pass searches
+    struct ContextBufs { DevBuf want, sel, len, keep, word_sel, word_fence, sum, carry, part, pos, rank, grank, partial, ctl, c_off, c_src; } d_context;
+
     // documents routed to per-bucket runs of one blob (gft_route.hip): the masks, the member words and lengths of a batch, the
     // (bucket, tile) counts with their prefix sums, the tiles' bytes, scan partials and read-back words of its own, and the
     // entries' lengths and compact offsets the select's copy pass searches

@@ -161,6 +161,96 @@ def select_shape():
     return int(c.value), int(t.value), int(k.value)
 
 
+CONTEXT_MAX = (1 << 64) - 1                         # before / after: every document up to the next fence
+
+
+def context_docs_tensor(call, text, doc_off, bitmap, n_cols, want, mode, also, before, after, fence):
+    """what Engine.context_docs_device and the finder's context call share: `call(d_text, d_doc_off, n_docs, d_bitmap, n_cols, want,
+    mode, d_also, before, after, d_fence, d_out, cap_bytes, d_out_off, d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups, byref(m),
+    byref(hits), byref(groups), byref(total))` is gft_context_docs_device on some handle and raises on an error.  Two calls: count
+    only, then into tensors of exactly the sizes counted"""
+    import torch
+    n_docs = int(doc_off.numel()) - 1
+    W = (n_cols + 31) // 32
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
+            (((also, 1, "also"),) if also is not None else ()) + (((fence, 1, "fence"),) if fence is not None else ()):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("context_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
+    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs) or \
+            (fence is not None and fence.numel() != n_docs):
+        raise ValueError("context_docs_device: doc_off, bitmap, also and fence do not describe the same batch")
+    if not (0 <= int(before) <= CONTEXT_MAX and 0 <= int(after) <= CONTEXT_MAX):
+        raise ValueError("context_docs_device: before and after are counts of documents, 0 .. 2^64 - 1")
+    w = _want_words(want, n_cols)
+    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), _select_mode(mode),
+            also.data_ptr() if also is not None else None, int(before), int(after), fence.data_ptr() if fence is not None else None)
+    m, hits, groups, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    counts = (C.byref(m), C.byref(hits), C.byref(groups), C.byref(total))
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, None, 0, None, None, None, 0, None, 0, *counts)
+    nm, ng, nb = int(m.value), int(groups.value), int(total.value)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
+    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
+    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    kind = torch.empty(nm, dtype=torch.uint8, device=text.device)
+    group_off = torch.empty(ng + 1, dtype=torch.int64, device=text.device)
+    torch.cuda.current_stream(text.device).synchronize()
+    call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_idx.data_ptr() if nm else None, kind.data_ptr() if nm else None, nm,
+         group_off.data_ptr(), ng, *counts)
+    return buf[:nb], out_off, doc_idx, kind, group_off
+
+
+def context_docs_host(blob, doc_off, rows, n_cols, want=None, mode="any", also=None, before=0, after=0, fence=None, cap_bytes=None,
+                      cap_docs=None, cap_groups=None, guard=0, out_shift=0, count_only=False):
+    """gft_debug_context_docs over host arrays -> (m, hits, groups, total, out uint8 [cap_bytes + guard], out_off uint64 [cap_docs + 1 +
+    guard], doc_idx uint64 [cap_docs + guard], kind uint8 [cap_docs + guard], group_off uint64 [cap_groups + 1 + guard]); no device
+    needed.  Caps None: count first, then exactly what the result needs; the guard entries behind the caps hold 0xA5 and must come
+    back untouched.  out_shift: the output starts that many bytes into its allocation's 16-byte grid.  The two offset arrays are
+    always passed; count_only: no array at all"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    n_docs = off.size - 1
+    W = (n_cols + 31) // 32
+    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
+    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    fe = np.ascontiguousarray(fence, dtype=np.uint8) if fence is not None else None
+    w = _want_words(want, n_cols)
+    m, hits, groups, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+
+    def call(out, cb, oo, di, ki, cd, go, cg):
+        rc = L.gft_debug_context_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), _select_mode(mode), _p(al),
+                                      int(before), int(after), _p(fe), out, cb, oo, di, ki, cd, go, cg, C.byref(m), C.byref(hits),
+                                      C.byref(groups), C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_context_docs")
+    if cap_bytes is None or cap_docs is None or cap_groups is None:
+        call(None, 0, None, None, None, 0, None, 0)
+        cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
+        cap_docs = int(m.value) if cap_docs is None else cap_docs
+        cap_groups = int(groups.value) if cap_groups is None else cap_groups
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 16 + out_shift
+    out = raw[at:at + cap_bytes + guard]
+    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    kind = np.full(cap_docs + guard, 0xA5, dtype=np.uint8)
+    group_off = np.full(cap_groups + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    if count_only:
+        call(None, 0, None, None, None, 0, None, 0)
+    else:
+        call(out.ctypes.data if cap_bytes or guard else None, cap_bytes, out_off.ctypes.data, doc_idx.ctypes.data if cap_docs or guard else None,
+             kind.ctypes.data if cap_docs or guard else None, cap_docs, group_off.ctypes.data, cap_groups)
+    return int(m.value), int(hits.value), int(groups.value), int(total.value), out, out_off, doc_idx, kind, group_off
+
+
+def context_shape():
+    """(documents per tile, tiles per carry block, carry blocks per trip of the spine) of the context kernels (gft_debug_context_shape)"""
+    t, c, s = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _lib.load().gft_debug_context_shape(C.byref(t), C.byref(c), C.byref(s))
+    return int(t.value), int(c.value), int(s.value)
+
+
 ROUTE_MODES = {"first": 0, "every": 1}              # gft_route_mode
 ROUTE_REST = 1                                      # GFT_ROUTE_REST
 ROUTE_MAX_BUCKETS = 64                              # GFT_ROUTE_MAX_BUCKETS
@@ -990,6 +1080,16 @@ class Engine:
         runs twice: count only, then into tensors of exactly those sizes"""
         return select_docs_tensor(lambda *a: self._check(self._L.gft_select_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols, want,
                                   mode, also)
+
+    def context_docs_device(self, text, doc_off, bitmap, n_cols, want=None, mode="any", also=None, before=0, after=0, fence=None):
+        """grep -A / -B / -C over a resident batch (gft_context_docs_device): the selected documents of select_docs_device and,
+        round each of them, up to `before` documents in front and `after` behind (CONTEXT_MAX: no limit).  fence: uint8 [n], a
+        non-zero byte at f lets no context cross between f - 1 and f.  Tensors as for select_docs_device.  Returns device tensors
+        (out uint8 [total], out_off int64 [m + 1], doc_idx int64 [m], kind uint8 [m] -- 1: selected, 0: context only --, group_off
+        int64 [g + 1]: the ranks at which the runs of consecutive kept documents begin, group_off[g] = m).  The call runs twice:
+        count only, then into tensors of exactly those sizes"""
+        return context_docs_tensor(lambda *a: self._check(self._L.gft_context_docs_device(self._h, *a)), text, doc_off, bitmap, n_cols,
+                                   want, mode, also, before, after, fence)
 
     def route_docs_device(self, text, doc_off, bitmap, n_cols, masks, mode="every", rest=False, also=None):
         """the documents of a resident batch routed to one bucket per mask, on the device (gft_route_docs_device).  Tensors as for

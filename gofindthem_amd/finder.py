@@ -437,6 +437,46 @@ class Finder:
         m, total, out, out_off, doc_idx = select_docs_host(data, off, bm, self.n_expressions, want, mode)
         return out[:total].tobytes(), out_off[:m + 1].copy(), doc_idx[:m].copy()
 
+    # -- context lines round the documents that matched (csrc/gft_context.hip) ---------------------------------------------------
+    def ContextDevice(self, text, doc_off, bitmap, want=None, mode="any", also=None, before=0, after=0, fence=None):
+        """Engine.context_docs_device on the finder's engine with n_cols = n_expressions (gft_finder_context_docs_device): the
+        documents SelectDevice selects and up to `before` documents in front of each and `after` behind, as device tensors (out
+        uint8, out_off int64 [m + 1], doc_idx int64 [m], kind uint8 [m], group_off int64 [g + 1]).  Needs what ProcessDevice needs"""
+        from .engine import context_docs_tensor
+
+        def call(d_text, d_off, n, d_bm, n_cols, w, m, d_also, *rest):
+            self._check(self._L.gft_finder_context_docs_device(self._h, d_text, d_off, n, d_bm, w, m, d_also, *rest))
+        return context_docs_tensor(call, text, doc_off, bitmap, self.n_expressions, want, mode, also, before, after, fence)
+
+    def ContextLinesDevice(self, buf, length, before=0, after=0, want=None, mode="any"):
+        """a resident blob of text lines -> the lines that hit and the lines round them (grep -B before -A after; mode "none": grep -v):
+        ProcessLinesDevice, then ContextDevice over its rows.  Returns (out, out_off, doc_idx, kind, group_off, doc_off, bitmap), all
+        on the device; a line keeps its newline"""
+        off, bm = self.ProcessLinesDevice(buf, length)
+        return self.ContextDevice(buf, off, bm, want, mode, None, before, after) + (off, bm)
+
+    def ContextLines(self, data, before=0, after=0, want=None, mode="any"):
+        """the host-memory form: bytes -> (the kept lines as bytes, out_off uint64 [m + 1], doc_idx uint64 [m], kind uint8 [m],
+        group_off uint64 [g + 1]).  One upload; only the kept lines and their arrays come down.  A finder that does not take the
+        device route splits, processes and decides on the host -- the kernels' walk behind gft_debug_split_lines and
+        gft_debug_context_docs --: the same result"""
+        import torch
+        data = bytes(data)
+        if self._takes_device_route():
+            dev = torch.device("cuda", self._device if self._device >= 0 else torch.cuda.current_device())
+            buf = torch.zeros(len(data) + 64, dtype=torch.uint8, device=dev)
+            if data:
+                buf[:len(data)] = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+            out, out_off, doc_idx, kind, group_off, _, _ = self.ContextLinesDevice(buf, len(data), before, after, want, mode)
+            return (out.cpu().numpy().tobytes(), out_off.cpu().numpy().astype(np.uint64), doc_idx.cpu().numpy().astype(np.uint64),
+                    kind.cpu().numpy(), group_off.cpu().numpy().astype(np.uint64))
+        from .engine import context_docs_host, split_lines_host
+        n, off = split_lines_host(data, 0)
+        off = off[:n + 1]
+        bm = self.ProcessTexts(blob=np.frombuffer(data + b"\0" * 64, dtype=np.uint8), doc_off=off)
+        m, _, g, total, out, out_off, doc_idx, kind, group_off = context_docs_host(data, off, bm, self.n_expressions, want, mode, None, before, after)
+        return out[:total].tobytes(), out_off[:m + 1].copy(), doc_idx[:m].copy(), kind[:m].copy(), group_off[:g + 1].copy()
+
     # -- where the expressions matched (csrc/gft_spans.hip) ----------------------------------------------------------------------
     def SpansDevice(self, text, doc_off, bitmap, want=None, row_idx=None, source=False):
         """Engine.hit_spans_device on the finder's engine under the finder's case rule (gft_finder_hit_spans_device), over the rows

@@ -375,6 +375,46 @@ int gft_debug_select_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t
  * wave's trip, and the bytes a wave owns (a tile) */
 void gft_debug_select_shape(uint32_t* chunk_bytes, uint32_t* trip_bytes, uint32_t* tile_bytes);
 
+/* ---- Context lines: the selected documents and the ones round them, on the device (csrc/gft_context.hip) -----------------
+ * grep -A / -B / -C over a resident batch whose documents are lines.  d_text_blob, d_doc_off, d_bitmap, n_cols, want (HOST), mode
+ * and d_also are those of gft_select_docs_device, and a document is SELECTED when that call would select it.  Document d is KEPT
+ * when some selected h satisfies d - after <= h <= d + before -- saturating: before and after may be 2^64 - 1 -- and no fence lies
+ * between h and d.  d_fence (nullable) [n_docs] bytes: a non-zero byte at f forbids context from crossing between f - 1 and f (a
+ * file border of a concatenated log, a bucket border of a routed blob): h and d are separated when a fence index lies in
+ * (min(h, d), max(h, d)].  d_fence[0] changes nothing.
+ * With m kept documents of `total` bytes: d_out, d_out_off [0..m] and d_doc_idx [m] are the select's outputs for the kept
+ * documents, in input order.  d_kind[r] = 1 when kept document r is itself selected, 0 when it is context only (grep's ':' and
+ * '-').  A group is a maximal run of kept documents with consecutive input indices and no fence inside (grep prints "--" between
+ * groups): d_group_off[g] is the rank r at which group g begins, d_group_off[n_groups] = m.
+ * Cap protocol of gft_select_docs_device: cap_bytes counts bytes of d_out (byte-exact); cap_docs entries of d_doc_idx and d_kind,
+ * d_out_off has cap_docs + 1; d_group_off has cap_groups + 1 and nothing is stored at d_group_off[> cap_groups].  *n_kept,
+ * *n_hits (the selected documents), *n_groups and *total_bytes (host, nullable) are always complete.  All device outputs NULL
+ * with all caps 0 counts only; an offset array that is not NULL always receives entry 0.  n_docs == 0 is valid.
+ * With before == after == 0 and no fence, d_out, d_out_off and d_doc_idx are those of gft_select_docs_device, d_kind is all 1 and
+ * the groups are the maximal runs of selected documents.
+ * Launches on the engine's stream (gft_profile_read: "context_mark", "context_reach", "context_carry", "context_decide",
+ * "context_scan", "context_place", "context_copy"); the call waits for the stream.  Slack and alignment as for the select.
+ * GFT_E_INVALID: a null argument; a cap without its array; an unknown mode; offsets that descend or a document of 4 GiB or more;
+ * an output that overlaps an input or another output.  Handles over several devices: GFT_E_UNSUPPORTED.  GFT_E_NOMEM: no room for
+ * the work buffers (36 bytes a document, a few words per 64 documents and 16 bytes a kept one).  Between gft_process_device_begin
+ * and _end only after _complete.  Needs no dictionary and no programs, leaves gft_last_nonascii alone, and the handle stays usable
+ * after any error. */
+int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap,
+                            uint32_t n_cols, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint64_t before, uint64_t after,
+                            const uint8_t* d_fence, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint8_t* d_kind,
+                            uint64_t cap_docs, uint64_t* d_group_off, uint64_t cap_groups, uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups,
+                            uint64_t* total_bytes);
+/* The same on the host, no HIP device needed: the kernels' walk tile by tile through the source they are compiled from
+ * (csrc/gft_context_piece.hpp).  All pointers host; same contract and refusals; only blob[doc_off[0], doc_off[n_docs]) is read.
+ * It is also what a finder takes when a batch's rows were completed on the host. */
+int gft_debug_context_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
+                           const uint32_t* want, uint32_t mode, const uint8_t* also, uint64_t before, uint64_t after, const uint8_t* fence,
+                           uint8_t* out, uint64_t cap_bytes, uint64_t* out_off, uint64_t* doc_idx, uint8_t* kind, uint64_t cap_docs,
+                           uint64_t* group_off, uint64_t cap_groups, uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups, uint64_t* total_bytes);
+/* where that walk's borders are: the documents a wave owns (a tile), the tiles of a carry block, and the carry blocks one trip
+ * of the spine pass resolves */
+void gft_debug_context_shape(uint32_t* tile_docs, uint32_t* carry_block_tiles, uint32_t* spine_trip_blocks);
+
 /* ---- Documents routed to per-bucket runs of one blob on the device (csrc/gft_route.hip) ----------------------------------
  * The K-way form of the select above: n_buckets column masks instead of one, and the output is ONE blob in which every bucket is
  * a contiguous run -- a stable counting sort of (document, bucket) entries in front of the select's copy kernel. */
@@ -920,6 +960,13 @@ int gft_finder_select_docs_device(gft_finder* f, const uint8_t* d_text_blob, con
                                   const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint8_t* d_out,
                                   uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* n_selected,
                                   uint64_t* total_bytes);
+/* gft_context_docs_device on the finder's engine with n_cols = gft_finder_n_expressions.  It asks of the finder what
+ * gft_finder_select_docs_device asks and refuses in its words. */
+int gft_finder_context_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                   const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t mode, const uint8_t* d_also, uint64_t before,
+                                   uint64_t after, const uint8_t* d_fence, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off,
+                                   uint64_t* d_doc_idx, uint8_t* d_kind, uint64_t cap_docs, uint64_t* d_group_off, uint64_t cap_groups,
+                                   uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups, uint64_t* total_bytes);
 /* gft_route_docs_device on the finder's engine with n_cols = gft_finder_n_expressions.  It asks of the finder what
  * gft_finder_select_docs_device asks and refuses in its words. */
 int gft_finder_route_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
