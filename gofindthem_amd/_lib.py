@@ -185,6 +185,13 @@ SYMBOLS = {
     "gft_debug_excerpt_shape": (None, [C.POINTER(_u32), C.POINTER(_u32)]),
     "gft_finder_excerpts_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
                                        C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_excerpt_spans_snap_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp,
+                                          _vp, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_excerpt_spans_snap": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
+                                         C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_debug_excerpt_snap_edges": (_i, [_vp, _u64, _u64, _u64, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "gft_finder_excerpts_snap_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _i, _i, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64,
+                                            _vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_i)]),
     "gft_mark_spans_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64),
                                   C.POINTER(_u64)]),
     "gft_debug_mark_spans": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64),

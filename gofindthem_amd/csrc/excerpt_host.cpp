@@ -2,7 +2,8 @@
 // pass and the mark pass of gft_excerpt.hip tile by tile, trip by trip, wave by wave and lane by lane through
 // gft_excerpt_piece.hpp, with the shuffles as array reads; the two prefix sums, the place and the finish pass; the copy excerpt by
 // excerpt.  Product code: a finder cuts with it when it does not take the device route.  It reads blob[doc_off[0],
-// doc_off[n_docs]) only and asks for no slack.
+// doc_off[n_docs]) only and asks for no slack.  gft_excerpt_spans_snap_device's walk is the same one with the <true> lane of the
+// window pass (excerpt_spans_snap_host); the class table is an argument, so this file links without the table's.
 #include <string.h>
 
 #include <algorithm>
@@ -37,15 +38,10 @@ void block_suffix_min(const uint64_t* v, uint32_t n_waves, uint64_t carry, uint6
     }
 }
 
-}  // namespace
-
-int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
-                       const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags, uint8_t* out, uint64_t cap_bytes,
-                       uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start, uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel,
-                       uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes) {
-    if (n_exc) *n_exc = 0;
-    if (total_bytes) *total_bytes = 0;
-    if (flags & ~(uint32_t)GFT_EXCERPT_RUNES) return GFT_E_INVALID;
+// both calls behind their own checks of flags and reach.  V: before, after, flags, reach and the class table are set
+int excerpt_walk(ExcView V, const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
+                 const uint32_t* span_len, uint8_t* out, uint64_t cap_bytes, uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start,
+                 uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel, uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes) {
     if (n_docs && (!doc_off || !span_off)) return GFT_E_INVALID;
     if (cap_bytes && !out) return GFT_E_INVALID;
     if (!n_docs) {                                                  // (span_off is not read, as on the device: no span, from index 0)
@@ -63,7 +59,8 @@ int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_
     if (excerpt_buffers_overlap(blob, doc_off[0], doc_off[n_docs], doc_off, n_docs, span_off, span_start, span_len, s0, n, out, cap_bytes, exc_off,
                                 exc_doc, exc_start, exc_span_off, cap_exc, span_rel, doc_exc_off))
         return GFT_E_INVALID;
-    const ExcView V{blob, doc_off, n_docs, span_off, span_start, span_len, before, after, flags};
+    V.text = blob; V.doc_off = doc_off; V.n_docs = n_docs; V.span_off = span_off; V.span_start = span_start; V.span_len = span_len;
+    const bool snap = (V.flags & (GFT_EXCERPT_WORDS | GFT_EXCERPT_LINES)) != 0;    // (the instantiation launch_excerpt_window picks)
     const uint64_t n_tiles = exc_tiles(n);
     std::vector<uint64_t> ws(n), we(n), sdoc(n), smin(n), tmin(n_tiles), carry(n_tiles);
     std::vector<uint32_t> head(n), share(n);
@@ -75,7 +72,7 @@ int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_
             const uint64_t k = tile * kExcTile + i;
             lane_v[i] = kExcNone;
             if (k >= n) continue;
-            bad |= exc_lane_window(V, s0 + k, sdoc[k], ws[k], we[k]);
+            bad |= snap ? exc_lane_window_t<true>(V, s0 + k, sdoc[k], ws[k], we[k]) : exc_lane_window_t<false>(V, s0 + k, sdoc[k], ws[k], we[k]);
             lane_v[i] = ws[k];
         }
         block_suffix_min(lane_v, kExcTile / 64, kExcNone, tot, incl, excl);
@@ -151,6 +148,34 @@ int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_
         if (len) memcpy(out + c_off[r], blob + c_src[r], (size_t)len);
     }
     return GFT_OK;
+}
+
+}  // namespace
+
+int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
+                       const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags, uint8_t* out, uint64_t cap_bytes,
+                       uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start, uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel,
+                       uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes) {
+    if (n_exc) *n_exc = 0;
+    if (total_bytes) *total_bytes = 0;
+    if (flags & ~(uint32_t)GFT_EXCERPT_RUNES) return GFT_E_INVALID;
+    ExcView V{};
+    V.before = before; V.after = after; V.flags = flags;
+    return excerpt_walk(V, blob, doc_off, n_docs, span_off, span_start, span_len, out, cap_bytes, exc_off, exc_doc, exc_start, exc_span_off, cap_exc,
+                        span_rel, doc_exc_off, n_exc, total_bytes);
+}
+
+int excerpt_spans_snap_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
+                            const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags, uint32_t reach, const WordTable& words,
+                            uint8_t* out, uint64_t cap_bytes, uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start, uint64_t* exc_span_off,
+                            uint64_t cap_exc, uint32_t* span_rel, uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes) {
+    if (n_exc) *n_exc = 0;
+    if (total_bytes) *total_bytes = 0;
+    if (!exc_snap_args_ok(flags, reach)) return GFT_E_INVALID;
+    ExcView V{};
+    V.before = before; V.after = after; V.flags = flags; V.reach = reach; V.words = words;
+    return excerpt_walk(V, blob, doc_off, n_docs, span_off, span_start, span_len, out, cap_bytes, exc_off, exc_doc, exc_start, exc_span_off, cap_exc,
+                        span_rel, doc_exc_off, n_exc, total_bytes);
 }
 
 }  // namespace gft

@@ -641,7 +641,8 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
 Error Finder::ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
                              const uint32_t* d_span_len, bool spans_lowered, bool source, uint32_t before, uint32_t after, uint32_t flags, uint8_t* d_out,
                              uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off,
-                             uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes, int* lowered) {
+                             uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes, int* lowered,
+                             bool snap, uint32_t reach) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
     if (!gpu_sub_ || !regexes_.empty()) {
@@ -661,8 +662,13 @@ Error Finder::ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
         if (rc) return fail_gft(rc);
         if (lowered) *lowered = 1;
     }
-    int rc = gft_excerpt_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, before, after, flags, d_out, cap_bytes,
-                                      d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel, d_doc_exc_off, n_exc, total_bytes);
+    // (the snap judges the text the excerpts are cut from)
+    int rc = snap ? gft_excerpt_spans_snap_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, before, after, flags, reach,
+                                                  d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel, d_doc_exc_off,
+                                                  n_exc, total_bytes)
+                  : gft_excerpt_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, before, after, flags, d_out,
+                                             cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel, d_doc_exc_off, n_exc,
+                                             total_bytes);
     return rc ? fail_gft(rc) : Error();
 }
 
@@ -1103,6 +1109,19 @@ int gft_finder_excerpts_device(gft_finder* f, const uint8_t* d_text_blob, const 
     return finder_ret(f, f->finder->ExcerptsDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
                                                    before, after, flags, d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc,
                                                    d_span_rel, d_doc_exc_off, n_exc, total_bytes, lowered), GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_excerpts_snap_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                    const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered,
+                                    int source, uint32_t before, uint32_t after, uint32_t flags, uint32_t reach, uint8_t* d_out,
+                                    uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off,
+                                    uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes,
+                                    int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->ExcerptsDevice(d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, spans_lowered != 0, source != 0,
+                                                   before, after, flags, d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc,
+                                                   d_span_rel, d_doc_exc_off, n_exc, total_bytes, lowered, true, reach), GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 
 int gft_finder_mark_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off,

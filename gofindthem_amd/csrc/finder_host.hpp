@@ -150,11 +150,13 @@ public:
                          uint64_t* total, int* lowered, bool source = false);
     // gft_excerpt_spans_device on the finder's engine behind HitSpansDevice: spans_lowered is what that call reported.  source (the
     // spans came from the source form of the call) or an unlowered batch: the excerpts are cut from the caller's batch; else from
-    // the lowered text, which is lowered on the device again as the spans call lowered it -- *lowered = 1
+    // the lowered text, which is lowered on the device again as the spans call lowered it -- *lowered = 1.  snap: the call is
+    // gft_excerpt_spans_snap_device with `reach` (flags may then hold a snap bit)
     Error ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,
                          const uint32_t* d_span_len, bool spans_lowered, bool source, uint32_t before, uint32_t after, uint32_t flags, uint8_t* d_out,
                          uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off,
-                         uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes, int* lowered);
+                         uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes, int* lowered,
+                         bool snap = false, uint32_t reach = 0);
     // gft_mark_spans_device on the finder's engine behind HitSpansDevice, under ExcerptsDevice's rule: source or an unlowered batch
     // marks the caller's batch; else the lowered text, lowered on the device again -- *lowered = 1
     Error MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, const uint32_t* d_span_start,

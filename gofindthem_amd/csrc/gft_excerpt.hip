@@ -9,7 +9,9 @@
 //                     that descend (these ctl[kExcCtlOffs] too: a word a condition, every lane stores the same 1)
 //   k_excerpt_window  returns at once when ctl[kExcCtlDocs] is raised.  A workgroup a tile of kExcTile spans, a lane a span: its document by a
 //                     binary search over span_off (span_doc_of), the window, the rune snap (at most six byte loads inside the
-//                     document), the two checks (ctl[kExcCtlSpans]) -> ws, we, sdoc; the tile's minimum of ws -> tmin
+//                     document), with a snap bit the walk of the two edges to a word or line border (the <true> instantiation,
+//                     which only gft_excerpt_spans_snap_device launches), the two checks (ctl[kExcCtlSpans]) -> ws, we, sdoc;
+//                     the tile's minimum of ws -> tmin
 //   k_excerpt_carry   ONE workgroup of kExcCarryTiles lanes, a lane a tile, the trips from the last to the first: a suffix-minimum
 //                     scan of tmin (shuffles inside the waves, LDS between them), exclusive -> carry; the minimum of the trip is
 //                     the carry of the trip in front of it
@@ -72,6 +74,10 @@ __global__ void __launch_bounds__(kExcTile) k_excerpt_docs(const ExcerptParams P
     if (bad_off) P.ctl[kExcCtlOffs] = 1;                            // (names the message)
 }
 
+// kSnap: the lane walks its two edges to a word or line border behind the rune snap (exc_snap_window), every step a single-byte
+// load inside the document, a rune decoded once; the class table stays in global memory.  false: the plain call's pass, and the
+// run pass of the mark and replace calls.
+template <bool kSnap>
 __global__ void __launch_bounds__(kExcTile) k_excerpt_window(const ExcerptParams P) {
     __shared__ uint64_t tot[kExcTile / 64];
     if (P.ctl[kExcCtlDocs]) return;                                 // (the same in every lane of the grid)
@@ -79,7 +85,7 @@ __global__ void __launch_bounds__(kExcTile) k_excerpt_window(const ExcerptParams
     uint64_t ws = kExcNone;
     if (k < P.n_spans) {
         uint64_t d, we;
-        if (exc_lane_window(P.V, P.s0 + k, d, ws, we)) P.ctl[kExcCtlSpans] = 1;
+        if (exc_lane_window_t<kSnap>(P.V, P.s0 + k, d, ws, we)) P.ctl[kExcCtlSpans] = 1;
         P.ws[k] = ws;
         P.we[k] = we;
         P.sdoc[k] = d;
@@ -173,7 +179,9 @@ hipError_t launch_excerpt_docs(const ExcerptParams& P, hipStream_t st) {
 
 hipError_t launch_excerpt_window(const ExcerptParams& P, hipStream_t st) {
     if (!P.n_spans) return hipSuccess;
-    k_excerpt_window<<<dim3((unsigned)exc_tiles(P.n_spans)), dim3(kExcTile), 0, st>>>(P);
+    const dim3 grid((unsigned)exc_tiles(P.n_spans));
+    if (P.V.flags & (GFT_EXCERPT_WORDS | GFT_EXCERPT_LINES)) k_excerpt_window<true><<<grid, dim3(kExcTile), 0, st>>>(P);
+    else k_excerpt_window<false><<<grid, dim3(kExcTile), 0, st>>>(P);
     return hipGetLastError();
 }
 

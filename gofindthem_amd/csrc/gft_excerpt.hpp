@@ -17,6 +17,12 @@ int excerpt_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_
                        const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags, uint8_t* out, uint64_t cap_bytes,
                        uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start, uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel,
                        uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes);
+// gft_excerpt_spans_snap_device's contract the same way: flags may hold one of GFT_EXCERPT_WORDS / GFT_EXCERPT_LINES, an edge moves
+// `reach` bytes at most.  words: the class table the word snap judges by (word_table_host() of gft_words.hpp; not read otherwise)
+int excerpt_spans_snap_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off, const uint32_t* span_start,
+                            const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags, uint32_t reach, const WordTable& words,
+                            uint8_t* out, uint64_t cap_bytes, uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start, uint64_t* exc_span_off,
+                            uint64_t cap_exc, uint32_t* span_rel, uint64_t* doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes);
 
 // an output of the call overlaps one of its inputs (the text is [lo, hi) of the blob, the spans [s0, s0 + n)) or another output
 inline bool excerpt_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,

@@ -8,6 +8,13 @@
 // document's first byte or its end: only bytes of the document itself are read.  The kernels work in positions of the blob:
 // ws = a + window start, we = a + window end.
 //
+// Snaps (gft_excerpt_spans_snap_device).  With GFT_EXCERPT_WORDS (which implies the rune snap: an edge inside a rune cuts no word
+// while its neighbours do, and the rule would not be monotone) the start then steps back and the end forward, a rune a step,
+// while the edge CUTS A WORD -- word(DecodeLastRune(D[:p])) and word(DecodeRune(D[p:])), the predicate and decoders of
+// gft_words_piece.hpp --; with GFT_EXCERPT_LINES they step a byte at a time until they stand behind a '\n' / on one.  An edge
+// that would move more than `reach` bytes stays where it began.  Both only grow a window, are monotone in the edge they start
+// from and read single bytes of the document alone, so everything below holds for snapped windows as it stands.
+//
 // Cuts.  The spans' ends ascend inside a document, so do the windows' (clipping and the snap are monotone), and with them the
 // excerpts -- the connected components of the union of a document's windows, touching windows joined -- are runs of consecutive
 // spans.  With smin(k) = min of ws over the spans k, k + 1, ... of the whole batch (a later document's windows begin at or behind
@@ -27,6 +34,7 @@
 #include "../../include/gft.h"
 #include "gft_select_piece.hpp"
 #include "gft_spans_piece.hpp"
+#include "gft_words_piece.hpp"
 
 namespace gft {
 
@@ -66,6 +74,69 @@ GFT_HD inline uint64_t exc_snap_end(const uint8_t* doc, uint64_t L, uint64_t hi)
     for (uint32_t s = 0; s < 3 && hi < L && exc_is_cont(doc[hi]); s++) hi++;
     return hi;
 }
+// the word snap.  The rune stepped over was decoded as the far side of the cut before: every rune of the walk is decoded once.
+GFT_HD inline uint64_t exc_word_start(const WordTable& T, const uint8_t* doc, uint64_t L, uint64_t lo, uint32_t reach) {
+    if (lo == 0 || lo >= L || !words_first_is_word(T, doc + lo, L - lo)) return lo;
+    uint64_t p = lo;
+    while (p > 0) {                                                 // (a word rune begins at p)
+        const uint32_t r = words_last_word_size(T, doc, p);
+        if (!r) break;
+        if (lo - (p - r) > reach) return lo;                        // the word is longer than the reach: given up
+        p -= r;
+    }
+    return p;
+}
+GFT_HD inline uint64_t exc_word_end(const WordTable& T, const uint8_t* doc, uint64_t L, uint64_t hi, uint32_t reach) {
+    if (hi == 0 || hi >= L || !words_last_is_word(T, doc, hi)) return hi;
+    uint64_t p = hi;
+    while (p < L) {                                                 // (a word rune ends at p)
+        const uint32_t r = words_first_word_size(T, doc + p, L - p);
+        if (!r) break;
+        if ((p + r) - hi > reach) return hi;
+        p += r;
+    }
+    return p;
+}
+// the line snap: the start behind a newline or at 0, the end on a newline or at L
+GFT_HD inline uint64_t exc_line_start(const uint8_t* doc, uint64_t L, uint64_t lo, uint32_t reach) {
+    (void)L;
+    uint64_t p = lo;
+    while (p > 0 && doc[p - 1] != '\n') {
+        if (lo - (p - 1) > reach) return lo;
+        p--;
+    }
+    return p;
+}
+GFT_HD inline uint64_t exc_line_end(const uint8_t* doc, uint64_t L, uint64_t hi, uint32_t reach) {
+    uint64_t p = hi;
+    while (p < L && doc[p] != '\n') {
+        if ((p + 1) - hi > reach) return hi;
+        p++;
+    }
+    return p;
+}
+// the flags and the reach of a snapped call are ones the call takes
+GFT_HD inline bool exc_snap_args_ok(uint32_t flags, uint32_t reach) {
+    if (flags & ~(uint32_t)(GFT_EXCERPT_RUNES | GFT_EXCERPT_WORDS | GFT_EXCERPT_LINES)) return false;
+    if ((flags & GFT_EXCERPT_WORDS) && (flags & GFT_EXCERPT_LINES)) return false;
+    return reach <= GFT_EXCERPT_REACH_MAX;
+}
+// the snaps of a clipped window [lo, hi) of doc[0, L), in the contract's order.  kSnap false: the rune snap alone
+template <bool kSnap>
+GFT_HD inline void exc_snap_window(const WordTable& T, const uint8_t* doc, uint64_t L, uint32_t flags, uint32_t reach, uint64_t& lo, uint64_t& hi) {
+    if (flags & (GFT_EXCERPT_RUNES | (kSnap ? GFT_EXCERPT_WORDS : 0u))) {
+        lo = exc_snap_start(doc, L, lo);
+        hi = exc_snap_end(doc, L, hi);
+    }
+    if (!kSnap) return;
+    if (flags & GFT_EXCERPT_WORDS) {
+        lo = exc_word_start(T, doc, L, lo, reach);
+        hi = exc_word_end(T, doc, L, hi, reach);
+    } else if (flags & GFT_EXCERPT_LINES) {
+        lo = exc_line_start(doc, L, lo, reach);
+        hi = exc_line_end(doc, L, hi, reach);
+    }
+}
 // span (start, len) lies inside a document of L bytes
 GFT_HD inline uint32_t exc_span_ok(uint64_t L, uint32_t start, uint32_t len) { return ((uint64_t)start + len <= L) ? 1u : 0u; }
 // the end of a span is not in front of the end of the span before it (same document)
@@ -81,11 +152,15 @@ struct ExcView {
     const uint32_t* span_start;
     const uint32_t* span_len;
     uint32_t before, after, flags;
+    uint32_t reach;                // the snapped call's; 0 and an empty table: the plain call
+    WordTable words;               // GFT_EXCERPT_WORDS: the class table (the device copy in the kernels)
 };
 
 // the window pass's lane: span s (span_off[0] <= s < span_off[n_docs]) -> its document, its snapped window in blob positions, and
 // the flag bits it raises.  A refused span still gets a window inside its document, so that nothing behind it reads astray.
-GFT_HD inline uint64_t exc_lane_window(const ExcView& V, uint64_t s, uint64_t& d, uint64_t& ws, uint64_t& we) {
+// kSnap: the word or line snap of V.flags behind the rune snap; false: the plain call's lane, which knows neither.
+template <bool kSnap>
+GFT_HD inline uint64_t exc_lane_window_t(const ExcView& V, uint64_t s, uint64_t& d, uint64_t& ws, uint64_t& we) {
     d = span_doc_of(V.span_off, V.n_docs, s);
     const uint64_t a = V.doc_off[d], b = V.doc_off[d + 1];
     if (!sel_doc_ok(a, b)) { ws = we = a; return kExcBadDoc; }
@@ -95,13 +170,13 @@ GFT_HD inline uint64_t exc_lane_window(const ExcView& V, uint64_t s, uint64_t& d
     if (s > V.span_off[d] && !exc_order_ok(V.span_start[s - 1], V.span_len[s - 1], start, len)) bad |= kExcBadSpan;
     uint64_t lo, hi;
     exc_window(L, start, len, V.before, V.after, lo, hi);
-    if (V.flags & GFT_EXCERPT_RUNES) {
-        lo = exc_snap_start(V.text + a, L, lo);
-        hi = exc_snap_end(V.text + a, L, hi);
-    }
+    exc_snap_window<kSnap>(V.words, V.text + a, L, V.flags, V.reach, lo, hi);
     ws = a + lo;
     we = a + hi;
     return bad;
+}
+GFT_HD inline uint64_t exc_lane_window(const ExcView& V, uint64_t s, uint64_t& d, uint64_t& ws, uint64_t& we) {
+    return exc_lane_window_t<false>(V, s, d, ws, we);
 }
 
 // ---- the suffix minimum -------------------------------------------------------------------------------------------------------

@@ -38,7 +38,13 @@ inline bool words_outputs_overlap(const uint64_t* out_off, uint64_t n_docs, cons
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 
+struct gft_engine;
+
 namespace gft {
+
+// the class table on the device (e->d_words.tab_row / tab_bits): uploaded by the first call of a handle that needs it, under the
+// caller's lock and DeviceGuard.  Returns a gft_status (gft_words_api.cpp)
+int ensure_word_table(gft_engine* e);
 
 // Work buffers: 16 bytes of flag words, 4 bytes of marks and 8 bytes of ranks an entry, the prefix sum's partials.
 struct WordsParams {

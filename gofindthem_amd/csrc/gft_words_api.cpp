@@ -15,9 +15,10 @@ const char kWhoProcess[] = "gft_process_words_device";
 const char kWhoSpans[] = "gft_hit_spans_words_device";
 const char kWhoStats[] = "gft_batch_term_stats_words_device";
 constexpr uint64_t kWordsMax = 1ull << 38;                          // entries and documents: the place pass's grid stays below 2^31
+}  // namespace
 
-// the class table on the device: uploaded by the first call of a handle
-int ensure_word_table(gft_engine* e) {
+// the class table on the device: uploaded by the first call of a handle (the excerpt's word snap asks for it too)
+int gft::ensure_word_table(gft_engine* e) {
     auto& S = e->d_words;
     if (S.table_up) return GFT_OK;
     const WordTable& T = word_table_host();
@@ -29,6 +30,8 @@ int ensure_word_table(gft_engine* e) {
     S.table_up = true;
     return GFT_OK;
 }
+
+namespace {
 
 struct FilterArgs {
     const uint8_t* text; const uint64_t* doc_off; uint64_t n_docs;

@@ -91,6 +91,39 @@ GFT_HD inline uint32_t words_last_is_word(const WordTable& T, const uint8_t* p, 
     return 0u;
 }
 
+// The two decoders once more for a walk that steps over the rune it judged (the excerpt's word snap, gft_excerpt_piece.hpp): the
+// SIZE of the word rune that begins at the slice's first byte / ends at its last, 0 where words_first_is_word /
+// words_last_is_word answer 0.  The same statements and the same reads.
+GFT_HD inline uint32_t words_first_word_size(const WordTable& T, const uint8_t* p, uint64_t n) {
+    if (!n) return 0u;
+    const uint32_t b0 = p[0];
+    if (b0 < 0x80u) return words_ascii_word(b0);
+    if (b0 < 0xC2u || b0 > 0xF4u) return 0u;
+    const uint32_t need = b0 < 0xE0u ? 2u : b0 < 0xF0u ? 3u : 4u;
+    if (n < need) return 0u;
+    const uint32_t b1 = p[1], b2 = need > 2 ? p[2] : 0u, b3 = need > 3 ? p[3] : 0u;
+    uint32_t cp = 0;
+    return (tolower_decode(b0, b1, b2, b3, cp) && words_is_word(T, cp)) ? need : 0u;
+}
+GFT_HD inline uint32_t words_last_word_size(const WordTable& T, const uint8_t* p, uint64_t n) {
+    if (!n) return 0u;
+    const uint32_t last = p[n - 1];
+    if (last < 0x80u) return words_ascii_word(last);
+    if (last >= 0xC0u) return 0u;
+    const uint32_t back = n < 4 ? (uint32_t)n - 1u : 3u;
+    for (uint32_t k = 1; k <= back; k++) {
+        const uint32_t b = p[n - 1 - k];
+        if ((b & 0xC0u) == 0x80u) continue;
+        if (b < 0xC2u || b > 0xF4u) return 0u;
+        const uint32_t need = b < 0xE0u ? 2u : b < 0xF0u ? 3u : 4u;
+        if (need != k + 1u) return 0u;
+        const uint8_t* q = p + (n - 1 - k);
+        uint32_t cp = 0;
+        return (tolower_decode(b, q[1], need > 2 ? q[2] : 0u, need > 3 ? q[3] : 0u, cp) && words_is_word(T, cp)) ? need : 0u;
+    }
+    return 0u;
+}
+
 // the occurrence [s, e) of the document doc[0 .. n): 1 when it is kept (s <= e <= n: the check pass saw to that)
 GFT_HD inline uint32_t words_kept(const WordTable& T, const uint8_t* doc, uint64_t n, uint64_t s, uint64_t e) {
     if (s == e) return 1u;

@@ -490,15 +490,26 @@ def map_spans_to_source_host(blob, doc_off, span_off, start, length):
 
 
 EXCERPT_RUNES = 1                                   # GFT_EXCERPT_RUNES
+EXCERPT_WORDS = 2                                   # GFT_EXCERPT_WORDS
+EXCERPT_LINES = 4                                   # GFT_EXCERPT_LINES
+EXCERPT_REACH_MAX = 4096                            # GFT_EXCERPT_REACH_MAX
 
 
-def excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes):
+def excerpt_snap_flag(snap):
+    """snap=None | "words" | "lines" -> the flag bit of the snapped calls"""
+    try:
+        return {None: 0, "words": EXCERPT_WORDS, "lines": EXCERPT_LINES}[snap]
+    except (KeyError, TypeError):
+        raise ValueError('snap must be None, "words" or "lines", not %r' % (snap,)) from None
+
+
+def excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes, snap=None, reach=64):
     """what Engine.excerpt_spans_device and Finder.ExcerptsDevice share: `call(d_text, d_doc_off, n_docs, d_span_off, d_span_start,
     d_span_len, before, after, flags, d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel,
     d_doc_exc_off, byref(n_exc), byref(total))` is gft_excerpt_spans_device on some handle and raises on an error.  Two calls: count
     only, then into tensors of exactly the sizes counted.  Returns (out uint8 [total] -- a view with 64 zero bytes behind it --,
     exc_off int64 [m + 1], exc_doc int64 [m], exc_start int32 [m], exc_span_off int64 [m + 1], span_rel int32 [spans], doc_exc_off
-    int64 [n + 1])"""
+    int64 [n + 1]).  snap "words" / "lines": `call` is gft_excerpt_spans_snap_device and gets `reach` behind flags"""
     import torch
     n_docs = int(doc_off.numel()) - 1
     for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off"), (span_off, 8, "span_off"), (start, 4, "start"), (length, 4, "len")):
@@ -507,7 +518,9 @@ def excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, a
     if n_docs < 0 or span_off.numel() != n_docs + 1 or start.numel() != length.numel():
         raise ValueError("excerpt_spans_device: doc_off, span_off and the span arrays do not describe the same batch")
     args = (text.data_ptr(), doc_off.data_ptr(), n_docs, span_off.data_ptr(), start.data_ptr() if start.numel() else None,
-            length.data_ptr() if length.numel() else None, int(before), int(after), EXCERPT_RUNES if runes else 0)
+            length.data_ptr() if length.numel() else None, int(before), int(after), (EXCERPT_RUNES if runes else 0) | excerpt_snap_flag(snap))
+    if snap is not None:
+        args += (int(reach),)
     m, total = C.c_uint64(0), C.c_uint64(0)
     dev = text.device
     torch.cuda.current_stream(dev).synchronize()
@@ -526,25 +539,27 @@ def excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, a
 
 
 def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=40, runes=True, cap_bytes=None, cap_exc=None, guard=0,
-                       flags=None, omit=(), count_only=False):
+                       flags=None, omit=(), count_only=False, snap=None, reach=64, snap_call=None):
     """gft_debug_excerpt_spans over host arrays -> a dict: n_exc, total, out uint8 [cap_bytes + guard], exc_off / exc_span_off uint64
     [cap_exc + 1 + guard], exc_doc uint64 / exc_start uint32 [cap_exc + guard], span_rel uint32 [len(start) + guard], doc_exc_off
     uint64 [n + 1 + guard]; no device needed.  Caps None: count first, then exactly what the result needs; the guard entries behind
-    the caps hold 0xA5.. and must come back untouched.  omit: names of outputs passed as NULL (they come back as None)"""
+    the caps hold 0xA5.. and must come back untouched.  omit: names of outputs passed as NULL (they come back as None).  snap
+    "words" / "lines" (or snap_call=True with any flags): gft_debug_excerpt_spans_snap with `reach`"""
     L = _lib.load()
     a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
     off, so = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(span_off, dtype=np.uint64)
     st, ln = np.ascontiguousarray(start, dtype=np.uint32), np.ascontiguousarray(length, dtype=np.uint32)
     n_docs = off.size - 1
-    fl = (EXCERPT_RUNES if runes else 0) if flags is None else int(flags)
+    fl = ((EXCERPT_RUNES if runes else 0) | excerpt_snap_flag(snap)) if flags is None else int(flags)
+    snapped = (snap is not None) if snap_call is None else bool(snap_call)
     m, total = C.c_uint64(0), C.c_uint64(0)
 
     def call(out, cb, eo, ed, es, eso, ce, rel, deo):
-        rc = L.gft_debug_excerpt_spans(_p(a) if a.size else None, _p(off), n_docs, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None,
-                                       int(before), int(after), fl, _p(out), cb, _p(eo), _p(ed), _p(es), _p(eso), ce, _p(rel), _p(deo),
-                                       C.byref(m), C.byref(total))
+        head = (_p(a) if a.size else None, _p(off), n_docs, _p(so), _p(st) if st.size else None, _p(ln) if ln.size else None, int(before), int(after), fl)
+        tail = (_p(out), cb, _p(eo), _p(ed), _p(es), _p(eso), ce, _p(rel), _p(deo), C.byref(m), C.byref(total))
+        rc = L.gft_debug_excerpt_spans_snap(*head, int(reach), *tail) if snapped else L.gft_debug_excerpt_spans(*head, *tail)
         if rc != 0:
-            raise GftError(rc, "gft_debug_excerpt_spans")
+            raise GftError(rc, "gft_debug_excerpt_spans_snap" if snapped else "gft_debug_excerpt_spans")
     if cap_bytes is None or cap_exc is None or count_only:
         call(None, 0, None, None, None, None, 0, None, None)
         cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
@@ -566,6 +581,17 @@ def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=
          arrs["span_rel"], arrs["doc_exc_off"])
     r.update(arrs, n_exc=int(m.value), total=int(total.value))
     return r
+
+
+def excerpt_snap_edges(doc, lo, hi, snap, reach=64, runes=False, flags=None):
+    """the snapped window of the clipped window [lo, hi) of one document (gft_debug_excerpt_snap_edges) -> (lo, hi); no device needed"""
+    a = np.frombuffer(bytes(doc), dtype=np.uint8)
+    fl = ((EXCERPT_RUNES if runes else 0) | excerpt_snap_flag(snap)) if flags is None else int(flags)
+    lo_out, hi_out = C.c_uint64(0), C.c_uint64(0)
+    rc = _lib.load().gft_debug_excerpt_snap_edges(_p(a) if a.size else None, a.size, int(lo), int(hi), fl, int(reach), C.byref(lo_out), C.byref(hi_out))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_excerpt_snap_edges")
+    return int(lo_out.value), int(hi_out.value)
 
 
 def excerpt_shape():
@@ -1132,21 +1158,29 @@ class Engine:
         map_spans_to_source_tensor(lambda *a: self._check(self._L.gft_map_spans_to_source_device(self._h, *a)), text, doc_off, span_off, start,
                                    length)
 
-    def excerpt_spans_device(self, text, doc_off, span_off, start, length, before=40, after=40, runes=True):
+    def excerpt_spans_device(self, text, doc_off, span_off, start, length, before=40, after=40, runes=True, snap=None, reach=64):
         """the text around the hit spans, cut and gathered on the device (gft_excerpt_spans_device).  text, doc_off: the batch the
         spans index; span_off, start, length: what hit_spans_device returned for it (or map_spans_to_source_device rewrote).  The
         window of a span reaches `before` bytes in front of it and `after` behind it, clipped to its document; runes: widened so that
         it cuts no UTF-8 sequence; windows that overlap or touch are one excerpt.  Returns device tensors (out uint8 [total] -- the
         excerpts back to back, a view with 64 zero bytes behind it --, exc_off int64 [m + 1], exc_doc int64 [m], exc_start int32 [m],
         exc_span_off int64 [m + 1], span_rel int32 [spans], doc_exc_off int64 [n + 1]); (out, exc_off, exc_span_off, span_rel,
-        length) is what redact_spans_device takes.  The call runs twice: count only, then into tensors of exactly those sizes"""
-        return excerpt_spans_tensor(lambda *a: self._check(self._L.gft_excerpt_spans_device(self._h, *a)), text, doc_off, span_off, start,
-                                    length, before, after, runes)
+        length) is what redact_spans_device takes.  The call runs twice: count only, then into tensors of exactly those sizes.
+        snap="words": every window then grows to the borders of the words its edges cut (the whole-word rule's word class; implies
+        runes); snap="lines": to the line borders round it, the newlines outside -- with before = after = 0 the lines the hits stand
+        in.  An edge moves `reach` bytes at most (up to EXCERPT_REACH_MAX) and stays where it was when its word or line is longer
+        (gft_excerpt_spans_snap_device).  snap=None is the plain call"""
+        if snap is None:
+            return excerpt_spans_tensor(lambda *a: self._check(self._L.gft_excerpt_spans_device(self._h, *a)), text, doc_off, span_off, start,
+                                        length, before, after, runes)
+        return excerpt_spans_tensor(lambda *a: self._check(self._L.gft_excerpt_spans_snap_device(self._h, *a)), text, doc_off, span_off, start,
+                                    length, before, after, runes, snap, reach)
 
     @staticmethod
-    def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=40, runes=True):
-        """the host twin of excerpt_spans_device over numpy arrays (gft_debug_excerpt_spans): the same tuple, as numpy arrays"""
-        r = excerpt_spans_host(blob, doc_off, span_off, start, length, before, after, runes)
+    def excerpt_spans_host(blob, doc_off, span_off, start, length, before=40, after=40, runes=True, snap=None, reach=64):
+        """the host twin of excerpt_spans_device over numpy arrays (gft_debug_excerpt_spans, with snap gft_debug_excerpt_spans_snap):
+        the same tuple, as numpy arrays"""
+        r = excerpt_spans_host(blob, doc_off, span_off, start, length, before, after, runes, snap=snap, reach=reach)
         m, total = r["n_exc"], r["total"]
         return (r["out"][:total] if r["out"] is not None else np.zeros(0, dtype=np.uint8), r["exc_off"][:m + 1],
                 r["exc_doc"][:m] if m else np.zeros(0, dtype=np.uint64), r["exc_start"][:m] if m else np.zeros(0, dtype=np.uint32),

@@ -563,23 +563,25 @@ class Finder:
         return text[:n].cpu().numpy().tobytes(), lowered
 
     # -- the text around the hits (csrc/gft_excerpt.hip) ---------------------------------------------------------------------------
-    def ExcerptsDevice(self, text, doc_off, span_off, start, length, lowered=False, source=False, before=40, after=40, runes=True):
+    def ExcerptsDevice(self, text, doc_off, span_off, start, length, lowered=False, source=False, before=40, after=40, runes=True, snap=None,
+                       reach=64):
         """Engine.excerpt_spans_device on the finder's engine behind SpansDevice (gft_finder_excerpts_device): text, doc_off the
         batch, span_off / start / length and `lowered` what SpansDevice returned for it, source as it was called.  With source, or
         for a batch that was not lowered, the excerpts are cut from `text`; otherwise from the batch's lower-case form, which the
         finder lowers on the device again.  Returns (out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, doc_exc_off, cut_lowered)
         -- device tensors as Engine.excerpt_spans_device gives them, and whether the lowered text was cut.  Needs what ProcessDevice
-        needs"""
+        needs.  snap="words" | "lines", reach: Engine.excerpt_spans_device's (gft_finder_excerpts_snap_device); the snap judges the
+        text the excerpts are cut from"""
         from .engine import excerpt_spans_tensor
         cut = C.c_int(0)
+        fn = self._L.gft_finder_excerpts_device if snap is None else self._L.gft_finder_excerpts_snap_device
 
         def call(d_text, d_off, n, d_so, d_st, d_ln, *rest):
-            self._check(self._L.gft_finder_excerpts_device(self._h, d_text, d_off, n, d_so, d_st, d_ln, 1 if lowered else 0, 1 if source else 0,
-                                                           *rest, C.byref(cut)))
-        out = excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes)
+            self._check(fn(self._h, d_text, d_off, n, d_so, d_st, d_ln, 1 if lowered else 0, 1 if source else 0, *rest, C.byref(cut)))
+        out = excerpt_spans_tensor(call, text, doc_off, span_off, start, length, before, after, runes, snap, reach)
         return out + (bool(cut.value),)
 
-    def ExcerptLines(self, data, before=40, after=40, want=None, source=True, runes=True, mark=None):
+    def ExcerptLines(self, data, before=40, after=40, want=None, source=True, runes=True, mark=None, snap=None, reach=64):
         """bytes -> (idx, excerpts, lowered): idx the numbers of the lines that hit `want` (want_mask(); None: any expression),
         excerpts[k] the list of (start_in_line, bytes, [(rel_start, rel_end, keyword), ...]) of line idx[k]: the text `before` bytes
         in front of and `after` bytes behind every hit of SpansLines, windows that overlap or touch merged, cut on rune borders
@@ -590,7 +592,9 @@ class Finder:
         terms, an injected engine or several devices has no host route to the spans (the cut itself has one:
         Engine.excerpt_spans_host) and is refused with GFT_E_UNSUPPORTED before anything is uploaded.  mark=(open, close): the excerpt
         blob goes through the mark call on the device before it comes down (MarkDevice's rule): every excerpt's bytes are the marked
-        ones, and rel_start / rel_end index them"""
+        ones, and rel_start / rel_end index them.  snap="words": the excerpts begin and end at word borders (a word longer than
+        `reach` bytes is cut where the window cut it); snap="lines" is for documents that hold several lines, as ExcerptsDevice
+        takes them -- here every document is a line already, and the snap gives the whole line when it is within reach"""
         data = bytes(data)
         if not self._takes_device_route():
             raise FinderError(_lib.GFT_E_UNSUPPORTED, "ExcerptLines needs the device route, as the hit spans do: the GPU substring engine, no regex "
@@ -598,7 +602,7 @@ class Finder:
         buf = self._resident(data)
         off, bm, span_off, start, length, term, lowered = self._spans_of_lines(buf, len(data), want, source)
         out, exc_off, exc_doc, exc_start, exc_span_off, span_rel, _, _ = self.ExcerptsDevice(buf, off, span_off, start, length, lowered, source,
-                                                                                             before, after, runes)
+                                                                                             before, after, runes, snap, reach)
         if mark is not None:
             # the excerpts are a batch with a span CSR of their own: marked as such, never across an excerpt's border
             from .engine import mark_spans_tensor

@@ -633,6 +633,45 @@ int gft_debug_excerpt_spans(const uint8_t* blob, const uint64_t* doc_off, uint64
 /* where that walk's borders are: the spans of a tile of the suffix-minimum scan, the tiles of one carry trip */
 void gft_debug_excerpt_shape(uint32_t* tile_spans, uint32_t* trip_tiles);
 
+/* Excerpts snapped to word or line borders: gft_excerpt_spans_device with two more flag bits and `reach`, the most bytes a snap
+ * may move an edge (at most GFT_EXCERPT_REACH_MAX: a lane walks its edges byte by byte, rune by rune).  With neither bit, or with
+ * reach == 0, the call is gft_excerpt_spans_device bit for bit and launches the same kernels.
+ * The window [lo, hi) of a span in its document D of L bytes is the one above -- clipped, then rune-snapped when
+ * GFT_EXCERPT_RUNES or GFT_EXCERPT_WORDS is set: the word snap implies the rune snap --, and then grows by ONE of two snaps.
+ * GFT_EXCERPT_WORDS.  A position p, 0 < p < L, CUTS A WORD iff word(utf8.DecodeLastRune(D[:p])) and word(utf8.DecodeRune(D[p:])),
+ * with the word class and the two strict decoders of gft_filter_word_matches_device: RuneError is no word rune, and nothing
+ * outside D is read -- not the lead, the slack, a neighbouring document or the other half of a rune a document border cuts.
+ * Start: p = lo; while p cuts a word, with r the size of the rune that ends at p: if lo - (p - r) > reach the start STAYS lo (the
+ * word is longer than the reach: given up, not cut `reach` bytes further out), else p -= r.  End: p = hi; while p cuts a word,
+ * with r the size of the rune at p: if (p + r) - hi > reach the end stays hi, else p += r.
+ * GFT_EXCERPT_LINES.  No decoding, and no rune snap unless GFT_EXCERPT_RUNES asks for it.  Start: p = lo; while p > 0 and
+ * D[p - 1] != '\n': if lo - (p - 1) > reach the start stays lo, else p--.  End: p = hi; while p < L and D[p] != '\n': if
+ * (p + 1) - hi > reach the end stays hi, else p++.  The newline itself lies outside the window, so hits on two adjacent lines are
+ * two excerpts; '\r' is a byte like any other.  before = after = 0 gives the lines the hits stand in: grep's output inside every
+ * document.
+ * Both snaps only grow a window (a span stays inside its own), are monotone in the edge they start from, stay inside [0, L] and
+ * move no edge by more than reach.  Everything else -- merge, span order, outputs, cap protocol, profile names, work buffers, the
+ * refusals -- is gft_excerpt_spans_device's; GFT_EXCERPT_WORDS uploads the word class table on a handle's first such call.
+ * GFT_E_INVALID in addition: both snap bits; reach > GFT_EXCERPT_REACH_MAX; unknown flag bits. */
+#define GFT_EXCERPT_WORDS 2u
+#define GFT_EXCERPT_LINES 4u
+#define GFT_EXCERPT_REACH_MAX 4096u
+int gft_excerpt_spans_snap_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                  const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len, uint32_t before,
+                                  uint32_t after, uint32_t flags, uint32_t reach, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_exc_off,
+                                  uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off, uint64_t cap_exc, uint32_t* d_span_rel,
+                                  uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes);
+/* The host form of the snapped call, as gft_debug_excerpt_spans is of the plain one: the same header, the same walk. */
+int gft_debug_excerpt_spans_snap(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                                 const uint32_t* span_start, const uint32_t* span_len, uint32_t before, uint32_t after, uint32_t flags,
+                                 uint32_t reach, uint8_t* out, uint64_t cap_bytes, uint64_t* exc_off, uint64_t* exc_doc, uint32_t* exc_start,
+                                 uint64_t* exc_span_off, uint64_t cap_exc, uint32_t* span_rel, uint64_t* doc_exc_off, uint64_t* n_exc,
+                                 uint64_t* total_bytes);
+/* The two edge walks on their own: the window [lo, hi) of the document doc[0, L), lo <= hi <= L, already clipped -> the snapped
+ * window (the implied rune snap first, then the word or line snap).  GFT_E_INVALID as above, and for lo > hi or hi > L. */
+int gft_debug_excerpt_snap_edges(const uint8_t* doc, uint64_t L, uint64_t lo, uint64_t hi, uint32_t flags, uint32_t reach, uint64_t* lo_out,
+                                 uint64_t* hi_out);
+
 /* ---- Highlight on the device: markers written round the hits (csrc/gft_mark.hip) --------------------------------------------
  * Between "where" (the spans) and "show it" (the excerpts): the text of a resident batch with `open` written in front of every
  * hit and `close` behind it -- <em> .. </em>, ** .. **, ANSI colour codes.  The text grows; the index outputs keep every call
@@ -1002,6 +1041,14 @@ int gft_finder_excerpts_device(gft_finder* f, const uint8_t* d_text_blob, const 
                                uint32_t flags, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start,
                                uint64_t* d_exc_span_off, uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc,
                                uint64_t* total_bytes, int* lowered);
+/* gft_excerpt_spans_snap_device on the finder's engine: gft_finder_excerpts_device with `reach`.  The rule for lowered batches
+ * and `source` is unchanged: the snap judges the text the excerpts are cut from. */
+int gft_finder_excerpts_snap_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                                    const uint64_t* d_span_off, const uint32_t* d_span_start, const uint32_t* d_span_len, int spans_lowered,
+                                    int source, uint32_t before, uint32_t after, uint32_t flags, uint32_t reach, uint8_t* d_out,
+                                    uint64_t cap_bytes, uint64_t* d_exc_off, uint64_t* d_exc_doc, uint32_t* d_exc_start, uint64_t* d_exc_span_off,
+                                    uint64_t cap_exc, uint32_t* d_span_rel, uint64_t* d_doc_exc_off, uint64_t* n_exc, uint64_t* total_bytes,
+                                    int* lowered);
 /* gft_mark_spans_device on the finder's engine, under the rule of gft_finder_excerpts_device: with source, or for a batch that
  * was not lowered, the caller's batch is marked; otherwise the finder lowers the batch on the device again, marks that text and
  * sets *lowered = 1 (else 0).  Everything else is gft_mark_spans_device's contract. */
