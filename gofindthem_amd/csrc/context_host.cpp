@@ -147,7 +147,7 @@ int context_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_d
         if (grank[d + 1] != g && group_off && g <= cap_groups) group_off[g] = r;
     }
     // k_select_copy
-    const SelGeom G{std::min(total, cap_bytes), (uint32_t)((uintptr_t)out & 15u)};
+    const SelGeom G = sel_geom(total, cap_bytes, out);
     select_copy_host(blob, c_off.data(), c_src.data(), m, G, out);
     return GFT_OK;
 }

@@ -25,6 +25,8 @@
 
 #include <algorithm>
 
+#include "gft_bitrows.hpp"
+
 namespace gft {
 
 constexpr uint32_t kBitRowsBlock = 256;     // 4 waves
@@ -43,7 +45,7 @@ inline BitRows bit_rows(const uint32_t* d_bitmap, uint64_t n_rows, uint32_t n_ex
     B.bitmap = d_bitmap;
     B.n_rows = n_rows;
     B.W = (n_exprs + 31) / 32;
-    while ((1u << B.lg) < B.W && B.lg < 6) B.lg++;
+    B.lg = bit_row_lg(B.W);
     B.tail = (n_exprs & 31) ? (1u << (n_exprs & 31)) - 1 : 0xFFFFFFFFu;
     return B;
 }

@@ -22,17 +22,11 @@ inline bool context_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t h
                                     const uint32_t* bitmap, uint32_t n_cols, const uint8_t* also, const uint8_t* fence, const uint8_t* out,
                                     uint64_t cap_bytes, const uint64_t* out_off, const uint64_t* doc_idx, const uint8_t* kind, uint64_t cap_docs,
                                     const uint64_t* group_off, uint64_t cap_groups) {
-    const void* outs[5] = {out, out_off, doc_idx, kind, group_off};
-    const uint64_t out_n[5] = {cap_bytes, out_off ? (cap_docs + 1) * 8 : 0, cap_docs * 8, cap_docs, group_off ? (cap_groups + 1) * 8 : 0};
-    const void* ins[5] = {text ? text + lo : nullptr, doc_off, bitmap, also, fence};
-    const uint64_t in_n[5] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, n_docs * ((n_cols + 31) / 32) * 4, n_docs, n_docs};
-    for (int o = 0; o < 5; o++) {
-        for (int i = 0; i < 5; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 5; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {out_off, out_off ? (cap_docs + 1) * 8 : 0}, {doc_idx, cap_docs * 8}, {kind, cap_docs},
+                              {group_off, group_off ? (cap_groups + 1) * 8 : 0}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8},
+                             {bitmap, n_docs * ((n_cols + 31) / 32) * 4}, {also, n_docs}, {fence, n_docs}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

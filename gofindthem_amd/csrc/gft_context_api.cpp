@@ -60,8 +60,7 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
     // the select's mark pass decides who is selected, and finds offsets that descend and documents of 4 GiB or more (ctl[4])
     SelectParams M{};
     M.text = d_text_blob; M.doc_off = d_doc_off; M.n_docs = n_docs; M.bitmap = d_bitmap;
-    M.W = W;
-    while ((1u << M.lg) < W && M.lg < 6) M.lg++;
+    M.W = W; M.lg = bit_row_lg(W);
     M.mode = mode; M.want = S.want.as<uint32_t>(); M.also = d_also;
     M.len = S.len.as<uint32_t>(); M.sel = S.sel.as<uint32_t>(); M.ctl = S.ctl.as<uint64_t>();
     ContextParams P{};
@@ -118,13 +117,8 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
         HIP_TRY(launch_context_place(P, st), "context place kernel launch");
     }
     // the bytes: the select's copy pass over the compact arrays
-    SelectParams C{};
-    C.text = d_text_blob; C.c_off = P.c_off; C.c_src = P.c_src; C.m = P.m; C.total = P.total; C.out = d_out;
-    C.G = SelGeom{std::min(P.total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
-    if (C.G.end) {
-        ProfScope ps(e, "context_copy");
-        HIP_TRY(launch_select_copy(C, st), "context copy kernel launch");
-    }
+    if ((rc = select_copy_run(e, d_text_blob, P.c_off, P.c_src, P.m, P.total, d_out, cap_bytes, "context_copy", "context copy kernel launch")))
+        return rc;
     HIP_TRY(hipStreamSynchronize(st), "context copy");
     return GFT_OK;
 } GFT_CATCH((e ? &e->err : nullptr))

@@ -29,17 +29,11 @@ inline bool excerpt_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t h
                                     const uint32_t* span_start, const uint32_t* span_len, uint64_t s0, uint64_t n, const uint8_t* out,
                                     uint64_t cap_bytes, const uint64_t* exc_off, const uint64_t* exc_doc, const uint32_t* exc_start,
                                     const uint64_t* exc_span_off, uint64_t cap_exc, const uint32_t* span_rel, const uint64_t* doc_exc_off) {
-    const void* outs[7] = {out, exc_off, exc_doc, exc_start, exc_span_off, span_rel ? span_rel + s0 : nullptr, doc_exc_off};
-    const uint64_t out_n[7] = {cap_bytes, (cap_exc + 1) * 8, cap_exc * 8, cap_exc * 4, (cap_exc + 1) * 8, n * 4, (n_docs + 1) * 8};
-    const void* ins[5] = {text ? text + lo : nullptr, doc_off, span_off, span_start ? span_start + s0 : nullptr, span_len ? span_len + s0 : nullptr};
-    const uint64_t in_n[5] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, (n_docs + 1) * 8, n * 4, n * 4};
-    for (int o = 0; o < 7; o++) {
-        for (int i = 0; i < 5; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 7; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {exc_off, (cap_exc + 1) * 8}, {exc_doc, cap_exc * 8}, {exc_start, cap_exc * 4},
+                              {exc_span_off, (cap_exc + 1) * 8}, {span_rel ? span_rel + s0 : nullptr, n * 4}, {doc_exc_off, (n_docs + 1) * 8}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}, {span_off, (n_docs + 1) * 8},
+                             {span_start ? span_start + s0 : nullptr, n * 4}, {span_len ? span_len + s0 : nullptr, n * 4}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

@@ -3,6 +3,7 @@
 // host walk behind gft_debug_excerpt_spans / gft_debug_excerpt_spans_snap / gft_debug_excerpt_snap_edges.
 #include "gft_engine.hpp"
 #include "gft_excerpt.hpp"
+#include "gft_span_runs.hpp"
 #include "gft_words.hpp"
 
 using namespace gft;
@@ -26,11 +27,7 @@ int excerpt_run(gft_engine* e, const char* kWho, const uint8_t* d_text_blob, con
     if (cap_exc > (~0ull >> 4) || n_docs > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(kWho) + ": a size beyond the address space");
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
-    // the control block and its pinned landing place; the ends of the span list and of the text -- how many lanes the passes get,
-    // and what the outputs must not meet -- gathered by one lane and read back in one copy
     auto& X = e->d_excerpt;
-    if ((rc = room(e, X.ctl, kExcCtlWords * 8, kExcRoom))) return rc;
-    if (!X.pin) HIP_TRY(hipHostMalloc((void**)&X.pin, kExcCtlWords * 8, hipHostMallocDefault), "pinned alloc");
     SyncOnExit drain(e);                                            // (the pinned words are handed to asynchronous copies)
     ExcerptParams P{};
     P.V = ExcView{d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, before, after, flags};
@@ -39,44 +36,13 @@ int excerpt_run(gft_engine* e, const char* kWho, const uint8_t* d_text_blob, con
         P.V.words = WordTable{e->d_words.tab_row.as<uint16_t>(), e->d_words.tab_bits.as<uint32_t>()};
     }
     P.V.reach = reach;
-    P.ctl = X.ctl.as<uint64_t>();
-    HIP_TRY(hipMemsetAsync(P.ctl, 0, kExcCtlWords * 8, st), "excerpt control block");
-    uint64_t ends[4] = {0, 0, 0, 0};
-    if (n_docs) {
-        HIP_TRY(launch_excerpt_ends(P, st), "excerpt ends kernel launch");
-        HIP_TRY(hipMemcpyAsync(X.pin, P.ctl + kExcCtlEnds, 32, hipMemcpyDeviceToHost, st), "span offsets");
-        HIP_TRY(hipStreamSynchronize(st), "span offsets");
-        for (int k = 0; k < 4; k++) ends[k] = X.pin[k];
-    }
-    if (ends[1] < ends[0] || ends[1] - ends[0] > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (ends[3] < ends[2]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    const uint64_t s0 = ends[0], n = ends[1] - ends[0];
-    if (n && (!d_span_start || !d_span_len)) return fail(e, GFT_E_INVALID, "null argument");
-    if (ends[3] > ends[2] && !d_text_blob) return fail(e, GFT_E_INVALID, "null argument");
-    if (excerpt_buffers_overlap(d_text_blob, ends[2], ends[3], d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, s0, n, d_out, cap_bytes,
+    SpanRun R{kWho, "excerpt", "mark", kExcRoom};
+    if ((rc = span_run_begin(e, P, R))) return rc;
+    const uint64_t n = R.n;
+    if (excerpt_buffers_overlap(d_text_blob, R.lo, R.hi, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, R.s0, n, d_out, cap_bytes,
                                 d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel, d_doc_exc_off))
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": an output overlaps an input or another output");
-    const uint64_t n_tiles = exc_tiles(n);
-    if ((rc = room(e, X.ws, n * 8, kExcRoom)) || (rc = room(e, X.we, n * 8, kExcRoom)) || (rc = room(e, X.sdoc, n * 8, kExcRoom)) ||
-        (rc = room(e, X.smin, n * 8, kExcRoom)) || (rc = room(e, X.head, n * 4, kExcRoom)) || (rc = room(e, X.share, n * 4, kExcRoom)) ||
-        (rc = room(e, X.rank, (n + 1) * 8, kExcRoom)) || (rc = room(e, X.pos, (n + 1) * 8, kExcRoom)) ||
-        (rc = room(e, X.tmin, n_tiles * 8, kExcRoom)) || (rc = room(e, X.carry, n_tiles * 8, kExcRoom)) ||
-        (rc = room(e, X.partial, scan_partials_needed(std::max<uint64_t>(n, 1)) * 8, kExcRoom)))
-        return rc;
-    P.s0 = s0; P.n_spans = n;
-    P.ws = X.ws.as<uint64_t>(); P.we = X.we.as<uint64_t>(); P.sdoc = X.sdoc.as<uint64_t>(); P.smin = X.smin.as<uint64_t>();
-    P.tmin = X.tmin.as<uint64_t>(); P.carry = X.carry.as<uint64_t>(); P.head = X.head.as<uint32_t>(); P.share = X.share.as<uint32_t>();
-    P.rank = X.rank.as<uint64_t>(); P.pos = X.pos.as<uint64_t>();
-    {
-        ProfScope ps(e, "excerpt_window");
-        HIP_TRY(launch_excerpt_docs(P, st), "excerpt document kernel launch");
-        HIP_TRY(launch_excerpt_window(P, st), "excerpt window kernel launch");
-    }
-    {
-        ProfScope ps(e, "excerpt_smin");
-        HIP_TRY(launch_excerpt_carry(P, st), "excerpt carry kernel launch");
-        HIP_TRY(launch_excerpt_mark(P, st), "excerpt mark kernel launch");
-    }
+    if ((rc = span_run_room(e, P, R, true)) || (rc = span_run_launch(e, P, R, "excerpt_window", "excerpt_smin"))) return rc;
     if (n) {
         ProfScope ps(e, "excerpt_scan");
         HIP_TRY(launch_exclusive_scan(P.head, n, X.rank.as<uint64_t>(), X.partial.as<uint64_t>(), st), "excerpt scan");
@@ -88,11 +54,7 @@ int excerpt_run(gft_engine* e, const char* kWho, const uint8_t* d_text_blob, con
     const uint64_t* h_ctl = X.pin;
     HIP_TRY(hipMemcpyAsync(X.pin, P.ctl, (kExcCtlOffs + 1) * 8, hipMemcpyDeviceToHost, st), "excerpt totals");
     HIP_TRY(hipStreamSynchronize(st), "excerpt totals");
-    if (h_ctl[kExcCtlOffs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (h_ctl[kExcCtlDocs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    if (h_ctl[kExcCtlSpans])
-        return fail(e, GFT_E_INVALID, std::string(kWho) + ": a span reaches past the end of its document, or the spans' ends descend inside a "
-                                                          "document (nothing was written)");
+    if ((rc = span_run_verdict(e, R, h_ctl))) return rc;
     P.m = h_ctl[kExcCtlExc]; P.total = h_ctl[kExcCtlTotal];
     if (n_exc) *n_exc = P.m;
     if (total_bytes) *total_bytes = P.total;
@@ -106,14 +68,9 @@ int excerpt_run(gft_engine* e, const char* kWho, const uint8_t* d_text_blob, con
         HIP_TRY(launch_excerpt_finish(P, st), "excerpt finish kernel launch");
         if (!n_docs && d_doc_exc_off) HIP_TRY(hipMemsetAsync(d_doc_exc_off, 0, 8, st), "excerpt offsets");
     }
-    // the select's copy pass over the excerpts: only what it reads of SelectParams is set
-    SelectParams C{};
-    C.text = d_text_blob; C.c_off = P.c_off; C.c_src = P.c_src; C.m = P.m; C.total = P.total; C.out = d_out;
-    C.G = SelGeom{std::min(P.total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
-    if (C.G.end) {
-        ProfScope ps(e, "excerpt_copy");
-        HIP_TRY(launch_select_copy(C, st), "excerpt copy kernel launch");
-    }
+    // the select's copy pass over the excerpts
+    if ((rc = select_copy_run(e, d_text_blob, P.c_off, P.c_src, P.m, P.total, d_out, cap_bytes, "excerpt_copy", "excerpt copy kernel launch")))
+        return rc;
     HIP_TRY(hipStreamSynchronize(st), "excerpt copy");
     return GFT_OK;
 }

@@ -2,7 +2,7 @@
 // and the host walk behind gft_debug_map_spans_to_source.
 #include "gft_engine.hpp"
 #include "gft_lowermap.hpp"
-#include "gft_select.hpp"
+#include "gft_overlap.hpp"
 
 using namespace gft;
 using namespace gft::api;
@@ -10,6 +10,15 @@ using namespace gft::api;
 namespace {
 constexpr RoomTexts kMapRoom{"no device memory for the span map's work buffers", "span map alloc"};
 const char kWho[] = "gft_map_spans_to_source_device";
+
+// a span array (the call rewrites entries [s0, s0 + n) of both in place) overlaps the text [lo, hi) of the blob, the offsets or the
+// other span array
+bool map_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
+                         const uint32_t* span_start, const uint32_t* span_len, uint64_t s0, uint64_t n) {
+    const ByteRange outs[] = {{span_start + s0, n * 4}, {span_len + s0, n * 4}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}, {span_off, (n_docs + 1) * 8}};
+    return outputs_overlap(outs, ins);
+}
 
 int map_spans(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_span_off, uint32_t* d_span_start,
               uint32_t* d_span_len, uint64_t limit) {
@@ -33,15 +42,8 @@ int map_spans(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, u
     if ((rc = room(e, M.off, (n_docs + 1) * 8, kMapRoom))) return rc;
     uint64_t nu = 0, total = 0, range[2] = {0, 0};
     if ((rc = lower_count(e, d_text, d_doc_off, n_docs, nullptr, 0, M.off.as<uint64_t>(), &nu, &total, kWho, "lowermap_table", range))) return rc;
-    {
-        const uint64_t text_n = range[1] > range[0] ? range[1] - range[0] : 0;
-        const uint32_t *a = d_span_start + ends[0], *b = d_span_len + ends[0];
-        const void* ins[3] = {d_text + range[0], d_doc_off, d_span_off};
-        const uint64_t in_n[3] = {text_n, (n_docs + 1) * 8, (n_docs + 1) * 8};
-        bool meet = select_meet(a, n * 4, b, n * 4);
-        for (int i = 0; i < 3; i++) meet = meet || select_meet(a, n * 4, ins[i], in_n[i]) || select_meet(b, n * 4, ins[i], in_n[i]);
-        if (meet) return fail(e, GFT_E_INVALID, std::string(kWho) + ": a span array overlaps the text, the offsets or the other span array");
-    }
+    if (map_buffers_overlap(d_text, range[0], range[1], d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, ends[0], n))
+        return fail(e, GFT_E_INVALID, std::string(kWho) + ": a span array overlaps the text, the offsets or the other span array");
     const uint64_t slots = lowermap_slots(range[1] - range[0], nu);
     if ((rc = room(e, M.tab, slots * 4, kMapRoom)) || (rc = room(e, M.mapped, n * 8, kMapRoom)) || (rc = room(e, M.ctl, 4, kMapRoom))) return rc;
     const LowerTable T{e->d_lw.page.as<uint16_t>(), e->d_lw.delta.as<int32_t>(), (uint32_t)lower_table_host().page.size()};
@@ -100,14 +102,7 @@ int gft_debug_map_spans_to_source(const uint8_t* blob, const uint64_t* doc_off, 
     const uint64_t s0 = span_off[0], n = span_off[n_docs] - s0;
     if (!n) return GFT_OK;
     if (!span_start || !span_len) return GFT_E_INVALID;
-    {
-        const uint32_t *a = span_start + s0, *b = span_len + s0;
-        const void* ins[3] = {blob ? blob + lo : nullptr, doc_off, span_off};
-        const uint64_t in_n[3] = {len, (n_docs + 1) * 8, (n_docs + 1) * 8};
-        bool meet = select_meet(a, n * 4, b, n * 4);
-        for (int i = 0; i < 3; i++) meet = meet || select_meet(a, n * 4, ins[i], in_n[i]) || select_meet(b, n * 4, ins[i], in_n[i]);
-        if (meet) return GFT_E_INVALID;
-    }
+    if (map_buffers_overlap(blob, lo, lo + len, doc_off, n_docs, span_off, span_start, span_len, s0, n)) return GFT_E_INVALID;
     std::vector<uint8_t> text((size_t)len + 64, 0);
     if (len) memcpy(text.data(), blob + lo, (size_t)len);
     std::vector<uint64_t> off(n_docs + 1);

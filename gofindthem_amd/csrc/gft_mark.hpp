@@ -22,17 +22,11 @@ int mark_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_doc
 inline bool mark_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* span_off,
                                  const uint32_t* span_start, const uint32_t* span_len, uint64_t s0, uint64_t n, const uint8_t* out,
                                  uint64_t cap_bytes, const uint64_t* out_off, const uint32_t* span_new, const uint64_t* doc_run_off) {
-    const void* outs[4] = {out, out_off, span_new ? span_new + s0 : nullptr, doc_run_off};
-    const uint64_t out_n[4] = {cap_bytes, (n_docs + 1) * 8, n * 4, (n_docs + 1) * 8};
-    const void* ins[5] = {text ? text + lo : nullptr, doc_off, span_off, span_start ? span_start + s0 : nullptr, span_len ? span_len + s0 : nullptr};
-    const uint64_t in_n[5] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, (n_docs + 1) * 8, n * 4, n * 4};
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < 5; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 4; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {out_off, (n_docs + 1) * 8}, {span_new ? span_new + s0 : nullptr, n * 4},
+                              {doc_run_off, (n_docs + 1) * 8}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}, {span_off, (n_docs + 1) * 8},
+                             {span_start ? span_start + s0 : nullptr, n * 4}, {span_len ? span_len + s0 : nullptr, n * 4}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

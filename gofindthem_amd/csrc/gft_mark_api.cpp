@@ -4,6 +4,7 @@
 
 #include "gft_engine.hpp"
 #include "gft_mark.hpp"
+#include "gft_span_runs.hpp"
 
 using namespace gft;
 using namespace gft::api;
@@ -36,51 +37,21 @@ int gft_mark_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
     uint8_t block[kMarkWords * 8];                                  // the markers, copied out of the caller's memory (outlives the drain)
-    // the run passes are the excerpt's, in the excerpt's buffers: the control block, its pinned landing place, the ends
+    // the run passes are the excerpt's, in the excerpt's buffers (gft_span_runs.hpp)
     auto& X = e->d_excerpt;
     auto& K = e->d_mark;
-    if ((rc = room(e, X.ctl, kExcCtlWords * 8, kMarkRoom))) return rc;
-    if (!X.pin) HIP_TRY(hipHostMalloc((void**)&X.pin, kExcCtlWords * 8, hipHostMallocDefault), "pinned alloc");
     SyncOnExit drain(e);                                            // (the pinned words are handed to asynchronous copies)
     MarkParams P{};
     P.X.V = ExcView{d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, 0, 0, 0};
-    P.X.ctl = X.ctl.as<uint64_t>();
-    HIP_TRY(hipMemsetAsync(P.X.ctl, 0, kExcCtlWords * 8, st), "mark control block");
-    uint64_t ends[4] = {0, 0, 0, 0};
-    if (n_docs) {
-        HIP_TRY(launch_excerpt_ends(P.X, st), "mark ends kernel launch");
-        HIP_TRY(hipMemcpyAsync(X.pin, P.X.ctl + kExcCtlEnds, 32, hipMemcpyDeviceToHost, st), "span offsets");
-        HIP_TRY(hipStreamSynchronize(st), "span offsets");
-        for (int k = 0; k < 4; k++) ends[k] = X.pin[k];
-    }
-    if (ends[1] < ends[0] || ends[1] - ends[0] > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (ends[3] < ends[2]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    const uint64_t s0 = ends[0], n = ends[1] - ends[0];
-    if (n && (!d_span_start || !d_span_len)) return fail(e, GFT_E_INVALID, "null argument");
-    if (ends[3] > ends[2] && !d_text_blob) return fail(e, GFT_E_INVALID, "null argument");
-    if (mark_buffers_overlap(d_text_blob, ends[2], ends[3], d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, s0, n, d_out, cap_bytes,
-                             d_out_off, d_span_new, d_doc_run_off))
+    SpanRun R{kWho, "mark", "heads", kMarkRoom};
+    if ((rc = span_run_begin(e, P.X, R))) return rc;
+    const uint64_t n = R.n;
+    if (mark_buffers_overlap(d_text_blob, R.lo, R.hi, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, R.s0, n, d_out, cap_bytes, d_out_off,
+                             d_span_new, d_doc_run_off))
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": an output overlaps an input or another output");
-    const uint64_t n_tiles = exc_tiles(n);
-    if ((rc = room(e, X.ws, n * 8, kMarkRoom)) || (rc = room(e, X.we, n * 8, kMarkRoom)) || (rc = room(e, X.sdoc, n * 8, kMarkRoom)) ||
-        (rc = room(e, X.smin, n * 8, kMarkRoom)) || (rc = room(e, X.head, n * 4, kMarkRoom)) || (rc = room(e, X.share, n * 4, kMarkRoom)) ||
-        (rc = room(e, X.rank, (n + 1) * 8, kMarkRoom)) || (rc = room(e, X.tmin, n_tiles * 8, kMarkRoom)) ||
-        (rc = room(e, X.carry, n_tiles * 8, kMarkRoom)) ||
-        (rc = room(e, X.partial, scan_partials_needed(std::max<uint64_t>(n, 1)) * 8, kMarkRoom)) ||
-        (rc = room(e, K.marks, kMarkWords * 8, kMarkRoom)))
-        return rc;
-    P.X.s0 = s0; P.X.n_spans = n;
-    P.X.ws = X.ws.as<uint64_t>(); P.X.we = X.we.as<uint64_t>(); P.X.sdoc = X.sdoc.as<uint64_t>(); P.X.smin = X.smin.as<uint64_t>();
-    P.X.tmin = X.tmin.as<uint64_t>(); P.X.carry = X.carry.as<uint64_t>(); P.X.head = X.head.as<uint32_t>(); P.X.share = X.share.as<uint32_t>();
-    P.X.rank = X.rank.as<uint64_t>();
-    P.M = MarkPlan{nullptr, 0, ends[2], ends[3] - ends[2], open_len, close_len};
-    {
-        ProfScope ps(e, "mark_runs");
-        HIP_TRY(launch_excerpt_docs(P.X, st), "mark document kernel launch");
-        HIP_TRY(launch_excerpt_window(P.X, st), "mark window kernel launch");
-        HIP_TRY(launch_excerpt_carry(P.X, st), "mark carry kernel launch");
-        HIP_TRY(launch_excerpt_mark(P.X, st), "mark heads kernel launch");
-    }
+    if ((rc = span_run_room(e, P.X, R, false)) || (rc = room(e, K.marks, kMarkWords * 8, kMarkRoom))) return rc;
+    P.M = MarkPlan{nullptr, 0, R.lo, R.hi - R.lo, open_len, close_len};
+    if ((rc = span_run_launch(e, P.X, R, "mark_runs", "mark_runs"))) return rc;
     {
         ProfScope ps(e, "mark_scan");
         if (n) {
@@ -93,14 +64,10 @@ int gft_mark_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
     const uint64_t* h_ctl = X.pin;
     HIP_TRY(hipMemcpyAsync(X.pin, P.X.ctl, (kMarkCtlGrow + 1) * 8, hipMemcpyDeviceToHost, st), "mark totals");
     HIP_TRY(hipStreamSynchronize(st), "mark totals");
-    if (h_ctl[kExcCtlOffs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (h_ctl[kExcCtlDocs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    if (h_ctl[kExcCtlSpans])
-        return fail(e, GFT_E_INVALID, std::string(kWho) + ": a span reaches past the end of its document, or the spans' ends descend inside a "
-                                                          "document (nothing was written)");
+    if ((rc = span_run_verdict(e, R, h_ctl))) return rc;
     if (h_ctl[kMarkCtlGrow])
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": a document would reach 4 GiB once marked (nothing was written)");
-    const uint64_t runs = h_ctl[kExcCtlExc], total = (ends[3] - ends[2]) + runs * ((uint64_t)open_len + close_len);
+    const uint64_t runs = h_ctl[kExcCtlExc], total = (R.hi - R.lo) + runs * ((uint64_t)open_len + close_len);
     if (n_runs) *n_runs = runs;
     if (total_bytes) *total_bytes = total;
     if ((rc = room(e, K.q, 2 * runs * 8, kMarkRoom))) return rc;
@@ -109,7 +76,7 @@ int gft_mark_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
     P.marks = K.marks.as<uint64_t>();
     P.out_off = d_out_off; P.span_new = d_span_new; P.doc_run_off = d_doc_run_off;
     P.out = d_out;
-    P.G = SelGeom{std::min(total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
+    P.G = sel_geom(total, cap_bytes, d_out);
     {
         ProfScope ps(e, "mark_place");
         HIP_TRY(launch_mark_place(P, st), "mark place kernel launch");

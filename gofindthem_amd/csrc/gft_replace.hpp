@@ -33,18 +33,12 @@ inline bool replace_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t h
                                     const uint32_t* span_start, const uint32_t* span_len, const uint32_t* span_key, uint64_t s0, uint64_t n,
                                     const uint8_t* out, uint64_t cap_bytes, const uint64_t* out_off, const uint64_t* doc_run_off,
                                     const uint32_t* run_new, const uint32_t* run_len, const uint32_t* run_rep, uint64_t cap_runs) {
-    const void* outs[6] = {out, out_off, doc_run_off, run_new, run_len, run_rep};
-    const uint64_t out_n[6] = {cap_bytes, (n_docs + 1) * 8, (n_docs + 1) * 8, cap_runs * 4, cap_runs * 4, cap_runs * 4};
-    const void* ins[6] = {text ? text + lo : nullptr, doc_off, span_off, span_start ? span_start + s0 : nullptr, span_len ? span_len + s0 : nullptr,
-                          span_key ? span_key + s0 : nullptr};
-    const uint64_t in_n[6] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, (n_docs + 1) * 8, n * 4, n * 4, n * 4};
-    for (int o = 0; o < 6; o++) {
-        for (int i = 0; i < 6; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 6; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {out_off, (n_docs + 1) * 8}, {doc_run_off, (n_docs + 1) * 8}, {run_new, cap_runs * 4},
+                              {run_len, cap_runs * 4}, {run_rep, cap_runs * 4}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}, {span_off, (n_docs + 1) * 8},
+                             {span_start ? span_start + s0 : nullptr, n * 4}, {span_len ? span_len + s0 : nullptr, n * 4},
+                             {span_key ? span_key + s0 : nullptr, n * 4}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

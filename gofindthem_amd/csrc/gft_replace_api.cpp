@@ -6,6 +6,7 @@
 
 #include "gft_engine.hpp"
 #include "gft_replace.hpp"
+#include "gft_span_runs.hpp"
 
 using namespace gft;
 using namespace gft::api;
@@ -46,63 +47,34 @@ int gft_replace_spans_device(gft_engine* e, const uint8_t* d_text_blob, const ui
     const std::vector<uint64_t> h_off(rep_off, rep_off + n_reps + 1);
     std::vector<uint32_t> h_keys;
     if (d_span_key && key_rep) h_keys.assign(key_rep, key_rep + n_keys);
-    // the run passes are the excerpt's, in the excerpt's buffers: the control block, its pinned landing place, the ends
+    // the run passes are the excerpt's, in the excerpt's buffers (gft_span_runs.hpp)
     auto& X = e->d_excerpt;
     auto& K = e->d_replace;
-    if ((rc = room(e, X.ctl, kExcCtlWords * 8, kRepRoom))) return rc;
-    if (!X.pin) HIP_TRY(hipHostMalloc((void**)&X.pin, kExcCtlWords * 8, hipHostMallocDefault), "pinned alloc");
     SyncOnExit drain(e);                                            // (the pinned words and the vectors are handed to asynchronous copies)
     ReplaceParams P{};
     P.X.V = ExcView{d_text_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, 0, 0, 0};
-    P.X.ctl = X.ctl.as<uint64_t>();
-    HIP_TRY(hipMemsetAsync(P.X.ctl, 0, kExcCtlWords * 8, st), "replace control block");
-    uint64_t ends[4] = {0, 0, 0, 0};
-    if (n_docs) {
-        HIP_TRY(launch_excerpt_ends(P.X, st), "replace ends kernel launch");
-        HIP_TRY(hipMemcpyAsync(X.pin, P.X.ctl + kExcCtlEnds, 32, hipMemcpyDeviceToHost, st), "span offsets");
-        HIP_TRY(hipStreamSynchronize(st), "span offsets");
-        for (int k = 0; k < 4; k++) ends[k] = X.pin[k];
-    }
-    if (ends[1] < ends[0] || ends[1] - ends[0] > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (ends[3] < ends[2]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    const uint64_t s0 = ends[0], n = ends[1] - ends[0];
-    if (n && (!d_span_start || !d_span_len)) return fail(e, GFT_E_INVALID, "null argument");
-    if (ends[3] > ends[2] && !d_text_blob) return fail(e, GFT_E_INVALID, "null argument");
-    if (replace_buffers_overlap(d_text_blob, ends[2], ends[3], d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, d_span_key, s0, n, d_out,
+    SpanRun R{kWho, "replace", "heads", kRepRoom};
+    if ((rc = span_run_begin(e, P.X, R))) return rc;
+    const uint64_t n = R.n;
+    if (replace_buffers_overlap(d_text_blob, R.lo, R.hi, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, d_span_key, R.s0, n, d_out,
                                 cap_bytes, d_out_off, d_doc_run_off, d_run_new, d_run_len, d_run_rep, cap_runs))
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": an output overlaps an input or another output");
-    const uint64_t n_tiles = exc_tiles(n);
-    if ((rc = room(e, X.ws, n * 8, kRepRoom)) || (rc = room(e, X.we, n * 8, kRepRoom)) || (rc = room(e, X.sdoc, n * 8, kRepRoom)) ||
-        (rc = room(e, X.smin, n * 8, kRepRoom)) || (rc = room(e, X.head, n * 4, kRepRoom)) || (rc = room(e, X.share, n * 4, kRepRoom)) ||
-        (rc = room(e, X.rank, (n + 1) * 8, kRepRoom)) || (rc = room(e, X.pos, (n + 1) * 8, kRepRoom)) ||
-        (rc = room(e, X.tmin, n_tiles * 8, kRepRoom)) || (rc = room(e, X.carry, n_tiles * 8, kRepRoom)) ||
-        (rc = room(e, X.partial, scan_partials_needed(std::max<uint64_t>(n, 1)) * 8, kRepRoom)) || (rc = room(e, K.rid, n * 4, kRepRoom)) ||
-        (rc = room(e, K.pl, n * 4, kRepRoom)) || (rc = room(e, K.ppos, (n + 1) * 8, kRepRoom)) ||
-        (rc = room(e, K.key_rep, h_keys.size() * 4, kRepRoom)) || (rc = room(e, K.rep_off, h_off.size() * 8, kRepRoom)) ||
-        (rc = room(e, K.tab, h_tab.size(), kRepRoom)))
+    if ((rc = span_run_room(e, P.X, R, true)) || (rc = room(e, K.rid, n * 4, kRepRoom)) || (rc = room(e, K.pl, n * 4, kRepRoom)) ||
+        (rc = room(e, K.ppos, (n + 1) * 8, kRepRoom)) || (rc = room(e, K.key_rep, h_keys.size() * 4, kRepRoom)) ||
+        (rc = room(e, K.rep_off, h_off.size() * 8, kRepRoom)) || (rc = room(e, K.tab, h_tab.size(), kRepRoom)))
         return rc;
-    P.X.s0 = s0; P.X.n_spans = n;
-    P.X.ws = X.ws.as<uint64_t>(); P.X.we = X.we.as<uint64_t>(); P.X.sdoc = X.sdoc.as<uint64_t>(); P.X.smin = X.smin.as<uint64_t>();
-    P.X.tmin = X.tmin.as<uint64_t>(); P.X.carry = X.carry.as<uint64_t>(); P.X.head = X.head.as<uint32_t>(); P.X.share = X.share.as<uint32_t>();
-    P.X.rank = X.rank.as<uint64_t>(); P.X.pos = X.pos.as<uint64_t>();
     P.span_key = d_span_key;
     P.key_rep = h_keys.empty() ? nullptr : K.key_rep.as<uint32_t>();
     P.n_keys = n_keys; P.n_reps = n_reps;
     P.rep_off = K.rep_off.as<uint64_t>(); P.tab = K.tab.as<uint8_t>(); P.tab_bytes = tab_bytes;
     P.rid = K.rid.as<uint32_t>(); P.pl = K.pl.as<uint32_t>(); P.ppos = K.ppos.as<uint64_t>();
-    P.text_len = ends[3] - ends[2];
-    P.R.base = ends[2];
+    P.text_len = R.hi - R.lo;
+    P.R.base = R.lo;
     if (d_span_key && key_rep && !n_keys && n) return fail(e, GFT_E_INVALID, std::string(kWho) + ": a key at or past n_keys (nothing was written)");
     HIP_TRY(hipMemcpyAsync(K.rep_off.p, h_off.data(), h_off.size() * 8, hipMemcpyHostToDevice, st), "replace table");
     HIP_TRY(hipMemcpyAsync(K.tab.p, h_tab.data(), h_tab.size(), hipMemcpyHostToDevice, st), "replace table");
     if (!h_keys.empty()) HIP_TRY(hipMemcpyAsync(K.key_rep.p, h_keys.data(), h_keys.size() * 4, hipMemcpyHostToDevice, st), "replace table");
-    {
-        ProfScope ps(e, "replace_runs");
-        HIP_TRY(launch_excerpt_docs(P.X, st), "replace document kernel launch");
-        HIP_TRY(launch_excerpt_window(P.X, st), "replace window kernel launch");
-        HIP_TRY(launch_excerpt_carry(P.X, st), "replace carry kernel launch");
-        HIP_TRY(launch_excerpt_mark(P.X, st), "replace heads kernel launch");
-    }
+    if ((rc = span_run_launch(e, P.X, R, "replace_runs", "replace_runs"))) return rc;
     {
         ProfScope ps(e, "replace_ids");
         if (n) {
@@ -127,11 +99,7 @@ int gft_replace_spans_device(gft_engine* e, const uint8_t* d_text_blob, const ui
     const uint64_t* h_ctl = X.pin;
     HIP_TRY(hipMemcpyAsync(X.pin, P.X.ctl, (kRepCtlKey + 1) * 8, hipMemcpyDeviceToHost, st), "replace totals");
     HIP_TRY(hipStreamSynchronize(st), "replace totals");
-    if (h_ctl[kExcCtlOffs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": span offsets descend");
-    if (h_ctl[kExcCtlDocs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": document offsets descend, or a document of 4 GiB or more");
-    if (h_ctl[kExcCtlSpans])
-        return fail(e, GFT_E_INVALID, std::string(kWho) + ": a span reaches past the end of its document, or the spans' ends descend inside a "
-                                                          "document (nothing was written)");
+    if ((rc = span_run_verdict(e, R, h_ctl))) return rc;
     if (h_ctl[kRepCtlKey])
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": a key at or past n_keys, or a replacement id at or past n_reps (nothing was written)");
     if (h_ctl[kRepCtlGrow])
@@ -143,11 +111,11 @@ int gft_replace_spans_device(gft_engine* e, const uint8_t* d_text_blob, const ui
         (rc = room(e, K.roff, runs * 4, kRepRoom)))
         return rc;
     P.at = K.at.as<uint64_t>(); P.delta = K.delta.as<uint64_t>(); P.len = K.len.as<uint32_t>(); P.roff = K.roff.as<uint32_t>();
-    P.R = RepPlan{P.at, P.delta, P.len, P.roff, runs, ends[2]};
+    P.R = RepPlan{P.at, P.delta, P.len, P.roff, runs, R.lo};
     P.out_off = d_out_off; P.doc_run_off = d_doc_run_off;
     P.run_new = d_run_new; P.run_len = d_run_len; P.run_rep = d_run_rep; P.cap_runs = cap_runs;
     P.out = d_out;
-    P.G = SelGeom{std::min(total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
+    P.G = sel_geom(total, cap_bytes, d_out);
     {
         ProfScope ps(e, "replace_place");
         HIP_TRY(launch_replace_place(P, st), "replace place kernel launch");

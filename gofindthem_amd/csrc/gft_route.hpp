@@ -38,17 +38,11 @@ inline bool route_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi,
                                   const uint8_t* out, uint64_t cap_bytes, const uint64_t* out_off, const uint64_t* doc_idx, uint64_t cap_docs,
                                   const uint64_t* bucket_doc, const uint64_t* bucket_byte, uint32_t B) {
     const uint64_t W = (n_cols + 31) / 32;
-    const void* outs[5] = {out, out_off, doc_idx, bucket_doc, bucket_byte};
-    const uint64_t out_n[5] = {cap_bytes, out_off ? (cap_docs + 1) * 8 : 0, cap_docs * 8, (uint64_t)(B + 1) * 8, (uint64_t)(B + 1) * 8};
-    const void* ins[5] = {text ? text + lo : nullptr, doc_off, bitmap, also, masks};
-    const uint64_t in_n[5] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, n_docs * W * 4, n_docs, n_buckets * W * 4};
-    for (int o = 0; o < 5; o++) {
-        for (int i = 0; i < 5; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 5; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {out_off, out_off ? (cap_docs + 1) * 8 : 0}, {doc_idx, cap_docs * 8},
+                              {bucket_doc, (uint64_t)(B + 1) * 8}, {bucket_byte, (uint64_t)(B + 1) * 8}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}, {bitmap, n_docs * W * 4},
+                             {also, n_docs}, {masks, n_buckets * W * 4}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

@@ -58,8 +58,7 @@ int gft_route_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
         return rc;
     RouteParams P{};
     P.doc_off = d_doc_off; P.n_docs = n_docs; P.n_tiles = n_tiles; P.bitmap = d_bitmap;
-    P.W = W;
-    while ((1u << P.lg) < W && P.lg < 6) P.lg++;
+    P.W = W; P.lg = bit_row_lg(W);
     P.n_buckets = n_buckets; P.B = B; P.mode = mode; P.rest = rest; P.masks = S.masks.as<uint32_t>(); P.also = d_also;
     P.member = S.member.as<uint64_t>(); P.len = S.len.as<uint32_t>(); P.cnt = S.cnt.as<uint32_t>(); P.tile_bytes = S.tile_bytes.as<uint64_t>();
     P.base = S.base.as<uint64_t>(); P.ctl = S.ctl.as<uint64_t>();
@@ -105,13 +104,7 @@ int gft_route_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
         HIP_TRY(launch_exclusive_scan(P.ent_len, P.m, S.c_off.as<uint64_t>(), S.partial.as<uint64_t>(), st), "route scan");
         HIP_TRY(launch_route_finish(P, st), "route scan");
     }
-    SelectParams C{};
-    C.text = d_text_blob; C.c_off = S.c_off.as<uint64_t>(); C.c_src = S.c_src.as<uint64_t>(); C.m = P.m; C.total = total; C.out = d_out;
-    C.G = SelGeom{std::min(total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
-    if (C.G.end) {
-        ProfScope ps(e, "route_copy");
-        HIP_TRY(launch_select_copy(C, st), "route copy kernel launch");
-    }
+    if ((rc = select_copy_run(e, d_text_blob, P.c_off, P.c_src, P.m, total, d_out, cap_bytes, "route_copy", "route copy kernel launch"))) return rc;
     HIP_TRY(hipMemcpyAsync(h_ctl + kRouteCtlByte, P.ctl + kRouteCtlByte, (B + 1) * 8, hipMemcpyDeviceToHost, st), "route copy");
     HIP_TRY(hipStreamSynchronize(st), "route copy");
     if (bucket_byte)

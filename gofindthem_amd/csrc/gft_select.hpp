@@ -4,6 +4,8 @@
 #include <stdint.h>
 
 #include "../../include/gft.h"
+#include "gft_bitrows.hpp"
+#include "gft_overlap.hpp"
 #include "gft_select_piece.hpp"
 
 namespace gft {
@@ -24,26 +26,14 @@ inline void select_want_words(const uint32_t* want, uint32_t n_cols, uint32_t* d
     if (W && (n_cols & 31)) dst[W - 1] &= (1u << (n_cols & 31)) - 1;
 }
 
-// two byte ranges meet (an empty one meets nothing)
-inline bool select_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && an && bn && x < y + bn && y < x + an;
-}
 // an output of the call overlaps one of its inputs (the text is [lo, hi) of the blob), or another output
 inline bool select_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs,
                                    const uint32_t* bitmap, uint32_t n_cols, const uint8_t* also, const uint8_t* out, uint64_t cap_bytes,
                                    const uint64_t* out_off, const uint64_t* doc_idx, uint64_t cap_docs) {
-    const void* outs[3] = {out, out_off, doc_idx};
-    const uint64_t out_n[3] = {cap_bytes, out_off ? (cap_docs + 1) * 8 : 0, cap_docs * 8};
-    const void* ins[4] = {text ? text + lo : nullptr, doc_off, bitmap, also};
-    const uint64_t in_n[4] = {hi > lo ? hi - lo : 0, (n_docs + 1) * 8, n_docs * ((n_cols + 31) / 32) * 4, n_docs};
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 4; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 3; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+    const ByteRange outs[] = {{out, cap_bytes}, {out_off, out_off ? (cap_docs + 1) * 8 : 0}, {doc_idx, cap_docs * 8}};
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8},
+                             {bitmap, n_docs * ((n_cols + 31) / 32) * 4}, {also, n_docs}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

@@ -10,6 +10,22 @@ namespace {
 constexpr RoomTexts kSelectRoom{"no device memory for the select's work buffers", "select alloc"};
 }
 
+namespace gft::api {
+
+int select_copy_run(gft_engine* e, const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, uint64_t total, uint8_t* out,
+                    uint64_t cap_bytes, const char* stage, const char* what) {
+    SelectParams C{};                                               // (only what the copy reads is set)
+    C.text = text; C.c_off = const_cast<uint64_t*>(c_off); C.c_src = const_cast<uint64_t*>(c_src); C.m = m; C.total = total; C.out = out;
+    C.G = sel_geom(total, cap_bytes, out);
+    if (C.G.end) {
+        ProfScope ps(e, stage);
+        HIP_TRY(launch_select_copy(C, e->stream), what);
+    }
+    return GFT_OK;
+}
+
+}  // namespace gft::api
+
 extern "C" {
 
 int gft_select_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap,
@@ -46,8 +62,7 @@ int gft_select_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint
         return rc;
     SelectParams P{};
     P.text = d_text_blob; P.doc_off = d_doc_off; P.n_docs = n_docs; P.bitmap = d_bitmap;
-    P.W = W;
-    while ((1u << P.lg) < W && P.lg < 6) P.lg++;
+    P.W = W; P.lg = bit_row_lg(W);
     P.mode = mode; P.want = S.want.as<uint32_t>(); P.also = d_also;
     P.len = S.len.as<uint32_t>(); P.sel = S.sel.as<uint32_t>(); P.pos = S.pos.as<uint64_t>(); P.rank = S.rank.as<uint64_t>();
     P.ctl = S.ctl.as<uint64_t>();
@@ -76,7 +91,7 @@ int gft_select_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint
     if ((rc = room(e, S.c_off, (P.m + 1) * 8, kSelectRoom)) || (rc = room(e, S.c_src, P.m * 8, kSelectRoom))) return rc;
     P.c_off = S.c_off.as<uint64_t>(); P.c_src = S.c_src.as<uint64_t>();
     P.out = d_out; P.out_off = d_out_off; P.doc_idx = d_doc_idx; P.cap_docs = cap_docs;
-    P.G = SelGeom{std::min(P.total, cap_bytes), (uint32_t)((uintptr_t)d_out & 15u)};
+    P.G = sel_geom(P.total, cap_bytes, d_out);
     {
         ProfScope ps(e, "select_place");
         HIP_TRY(launch_select_place(P, st), "select place kernel launch");

@@ -51,6 +51,10 @@ struct SelGeom {
     uint64_t end;          // bytes to write: min(total, cap_bytes)
     uint32_t a;            // the output address & 15
 };
+// the geometry of a call that has `total` bytes for an output of cap_bytes at `out`
+inline SelGeom sel_geom(uint64_t total, uint64_t cap_bytes, const void* out) {
+    return SelGeom{total < cap_bytes ? total : cap_bytes, (uint32_t)((uintptr_t)out & 15u)};
+}
 GFT_HD inline uint64_t sel_chunks(const SelGeom& G) { return G.end ? (G.end + G.a + kSelChunk - 1) / kSelChunk : 0; }
 GFT_HD inline uint64_t sel_tiles(const SelGeom& G) { return (sel_chunks(G) + kSelTile / kSelChunk - 1) / (kSelTile / kSelChunk); }
 // chunk c's positions [lo, hi); lo == hi: none (c is past the range)

@@ -22,16 +22,9 @@ int redact_spans_host(uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, c
 
 // an output of a spans call (span_off [n_docs + 1], three arrays of cap words) overlaps one of the n_in input ranges, or another
 inline bool spans_outputs_overlap(const uint64_t* span_off, uint64_t n_docs, const uint32_t* s0, const uint32_t* s1, const uint32_t* s2, uint64_t cap,
-                                  const void* const* ins, const uint64_t* in_n, int n_in) {
-    const void* outs[4] = {span_off, s0, s1, s2};
-    const uint64_t out_n[4] = {span_off ? (n_docs + 1) * 8 : 0, cap * 4, cap * 4, cap * 4};
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < n_in; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 4; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+                                  const ByteRange* ins, size_t n_in) {
+    const ByteRange outs[] = {{span_off, span_off ? (n_docs + 1) * 8 : 0}, {s0, cap * 4}, {s1, cap * 4}, {s2, cap * 4}};
+    return outputs_overlap(outs, 4, ins, n_in);
 }
 
 }  // namespace gft

@@ -54,10 +54,10 @@ int gft_hit_spans_device(gft_engine* e, const uint8_t* d_text_blob, const uint64
     if ((rc = refine_nonascii(e, d_text_blob, d_doc_off, n_docs, flags, v))) return rc;
     const uint64_t nm = v.total;
     {
-        const void* ins[4] = {d_text_blob ? d_text_blob + v.text_lo : nullptr, d_doc_off, d_hit_bitmap, d_row_idx};
         // (with d_row_idx the rows the call reads are not known on the host: the first row stands for the bitmap)
-        const uint64_t in_n[4] = {v.text_hi > v.text_lo ? v.text_hi - v.text_lo : 0, (n_docs + 1) * 8, (d_row_idx ? 1 : n_docs) * (uint64_t)W * 4, n_docs * 8};
-        if (spans_outputs_overlap(d_span_off, n_docs, d_span_start, d_span_len, d_span_term, cap, ins, in_n, 4))
+        const ByteRange ins[4] = {{d_text_blob ? d_text_blob + v.text_lo : nullptr, v.text_hi > v.text_lo ? v.text_hi - v.text_lo : 0},
+                                  {d_doc_off, (n_docs + 1) * 8}, {d_hit_bitmap, (d_row_idx ? 1 : n_docs) * (uint64_t)W * 4}, {d_row_idx, n_docs * 8}};
+        if (spans_outputs_overlap(d_span_off, n_docs, d_span_start, d_span_len, d_span_term, cap, ins, 4))
             return fail(e, GFT_E_INVALID, "gft_hit_spans_device: an output overlaps an input or another output");
     }
     if (!n_docs || !nm) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/gft.h"
+#include "gft_overlap.hpp"
 #include "gft_stats_piece.hpp"
 
 namespace gft {
@@ -15,29 +16,19 @@ int term_stats_host(const uint64_t* off, const uint32_t* term, uint64_t n_docs, 
 // gft_count_columns_device's contract on host pointers, workgroup by workgroup
 int count_columns_host(const uint32_t* bitmap, uint64_t n_rows, uint32_t n_cols, const uint64_t* row_idx, uint32_t flags, uint64_t* count);
 
-// two byte ranges meet (an empty one meets nothing)
-inline bool stats_meet(const void* a, uint64_t an, const void* b, uint64_t bn) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return a && b && an && bn && x < y + bn && y < x + an;
-}
 // an output of the term statistics overlaps an input (the entries are [e0, e0 + n) of term) or another output
 inline bool stats_buffers_overlap(const uint64_t* off, uint64_t n_docs, const uint32_t* term, uint64_t e0, uint64_t n, uint32_t n_terms,
                                   const uint64_t* occ, const uint64_t* docs, const uint64_t* first) {
-    const void* outs[3] = {occ, docs, first};
-    const void* ins[2] = {off, term ? term + e0 : nullptr};
-    const uint64_t in_n[2] = {(n_docs + 1) * 8, n * 4};
-    for (int o = 0; o < 3; o++) {
-        for (int i = 0; i < 2; i++)
-            if (stats_meet(outs[o], (uint64_t)n_terms * 8, ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 3; p++)
-            if (stats_meet(outs[o], (uint64_t)n_terms * 8, outs[p], (uint64_t)n_terms * 8)) return true;
-    }
-    return false;
+    const uint64_t out_n = (uint64_t)n_terms * 8;
+    const ByteRange outs[] = {{occ, out_n}, {docs, out_n}, {first, out_n}};
+    const ByteRange ins[] = {{off, (n_docs + 1) * 8}, {term ? term + e0 : nullptr, n * 4}};
+    return outputs_overlap(outs, ins);
 }
 // the counts overlap the bitmap (its first n_rows rows; with row_idx the rows' extent is the caller's) or the row indices
 inline bool columns_buffers_overlap(const uint32_t* bitmap, uint64_t n_rows, uint32_t n_cols, const uint64_t* row_idx, const uint64_t* count) {
-    return stats_meet(count, (uint64_t)n_cols * 8, bitmap, (row_idx ? 0 : n_rows) * stats_col_words(n_cols) * 4) ||
-           stats_meet(count, (uint64_t)n_cols * 8, row_idx, n_rows * 8);
+    const ByteRange outs[] = {{count, (uint64_t)n_cols * 8}};
+    const ByteRange ins[] = {{bitmap, (row_idx ? 0 : n_rows) * stats_col_words(n_cols) * 4}, {row_idx, n_rows * 8}};
+    return outputs_overlap(outs, ins);
 }
 
 }  // namespace gft

@@ -21,16 +21,9 @@ int filter_word_matches_host(const uint8_t* text, const uint64_t* doc_off, uint6
 
 // an output of the filter (out_off [n_docs + 1], three arrays of cap words) overlaps one of the n_in input ranges, or another
 inline bool words_outputs_overlap(const uint64_t* out_off, uint64_t n_docs, const uint32_t* o0, const uint32_t* o1, const uint32_t* o2, uint64_t cap,
-                                  const void* const* ins, const uint64_t* in_n, int n_in) {
-    const void* outs[4] = {out_off, o0, o1, o2};
-    const uint64_t out_n[4] = {out_off ? (n_docs + 1) * 8 : 0, cap * 4, cap * 4, cap * 4};
-    for (int o = 0; o < 4; o++) {
-        for (int i = 0; i < n_in; i++)
-            if (select_meet(outs[o], out_n[o], ins[i], in_n[i])) return true;
-        for (int p = o + 1; p < 4; p++)
-            if (select_meet(outs[o], out_n[o], outs[p], out_n[p])) return true;
-    }
-    return false;
+                                  const ByteRange* ins, size_t n_in) {
+    const ByteRange outs[] = {{out_off, out_off ? (n_docs + 1) * 8 : 0}, {o0, cap * 4}, {o1, cap * 4}, {o2, cap * 4}};
+    return outputs_overlap(outs, 4, ins, n_in);
 }
 
 }  // namespace gft

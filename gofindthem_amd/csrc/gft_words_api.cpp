@@ -68,11 +68,11 @@ int filter_run(gft_engine* e, const FilterArgs& A, uint64_t* total, const char* 
     if (n && (!A.text || !A.pos || (!A.len && (!A.term || !A.term_len)))) return fail(e, GFT_E_INVALID, "null argument");
     if (n && A.out_term && !A.term) return fail(e, GFT_E_INVALID, w + ": term ids asked for, none given");
     {
-        const void* ins[9] = {A.text ? A.text + ends[2] : nullptr, A.doc_off, A.off, A.pos ? A.pos + e0 : nullptr, A.len ? A.len + e0 : nullptr,
-                              A.term ? A.term + e0 : nullptr, A.len ? nullptr : A.term_len, A.more_in[0], A.more_in[1]};
-        const uint64_t in_n[9] = {ends[3] > ends[2] ? ends[3] - ends[2] : 0, (A.n_docs + 1) * 8, (A.n_docs + 1) * 8, n * 4, n * 4, n * 4,
-                                  (uint64_t)A.n_terms * 4, A.more_n[0], A.more_n[1]};
-        if (words_outputs_overlap(A.out_off, A.n_docs, A.out_pos, A.out_len, A.out_term, A.cap, ins, in_n, 9))
+        const ByteRange ins[9] = {{A.text ? A.text + ends[2] : nullptr, ends[3] > ends[2] ? ends[3] - ends[2] : 0},
+                                  {A.doc_off, (A.n_docs + 1) * 8}, {A.off, (A.n_docs + 1) * 8}, {A.pos ? A.pos + e0 : nullptr, n * 4},
+                                  {A.len ? A.len + e0 : nullptr, n * 4}, {A.term ? A.term + e0 : nullptr, n * 4},
+                                  {A.len ? nullptr : A.term_len, (uint64_t)A.n_terms * 4}, {A.more_in[0], A.more_n[0]}, {A.more_in[1], A.more_n[1]}};
+        if (words_outputs_overlap(A.out_off, A.n_docs, A.out_pos, A.out_len, A.out_term, A.cap, ins, 9))
             return fail(e, GFT_E_INVALID, w + ": an output overlaps an input or another output");
     }
     auto& S = e->d_words;

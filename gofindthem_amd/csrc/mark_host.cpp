@@ -106,7 +106,7 @@ int mark_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_doc
     if (open_len) memcpy(marks, open, open_len);
     if (close_len) memcpy(reinterpret_cast<uint8_t*>(marks) + kMarkSlot, close, close_len);
     const MarkPlan M{q.data(), 2 * m, base, doc_off[n_docs] - base, open_len, close_len};
-    const SelGeom G{std::min(total, cap_bytes), (uint32_t)((uintptr_t)out & 15u)};
+    const SelGeom G = sel_geom(total, cap_bytes, out);
     for (uint64_t tile = 0, tiles = sel_tiles(G); tile < tiles; tile++) copy_tile(M, blob, marks, G, tile, out);
     return GFT_OK;
 }

@@ -152,7 +152,7 @@ int replace_spans_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_
     std::vector<uint8_t> tab((size_t)rep_off[n_reps] + kRepTableSlack, 0);
     if (rep_off[n_reps]) memcpy(tab.data(), rep_bytes, rep_off[n_reps]);
     const RepPlan R{at.data(), delta.data(), len.data(), roff.data(), m, base};
-    const SelGeom G{std::min(total, cap_bytes), (uint32_t)((uintptr_t)out & 15u)};
+    const SelGeom G = sel_geom(total, cap_bytes, out);
     for (uint64_t tile = 0, tiles = sel_tiles(G); tile < tiles; tile++) copy_tile(R, blob, tab.data(), G, tile, out);
     return GFT_OK;
 }

@@ -109,7 +109,7 @@ int route_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_doc
         if (bucket_byte) bucket_byte[b] = c_off[at];
     }
     // k_select_copy
-    const SelGeom G{std::min(total, cap_bytes), (uint32_t)((uintptr_t)out & 15u)};
+    const SelGeom G = sel_geom(total, cap_bytes, out);
     select_copy_host(blob, c_off.data(), c_src.data(), m, G, out);
     return GFT_OK;
 }

@@ -34,9 +34,9 @@ int hit_spans_host(const uint64_t* match_off, const uint32_t* term_id, const uin
     const uint64_t nm = match_off[n_docs];
     const uint32_t W = (n_exprs + 31) / 32;
     if (nm && (!term_id || !pos || !term_len || !wit_off || (W && !bitmap))) return GFT_E_INVALID;
-    const void* ins[5] = {match_off, term_id, pos, bitmap, row_idx};
-    const uint64_t in_n[5] = {(n_docs + 1) * 8, nm * 4, nm * 4, row_idx ? (uint64_t)W * 4 : n_docs * W * 4, n_docs * 8};
-    if (spans_outputs_overlap(span_off, n_docs, span_start, span_len, span_term, cap, ins, in_n, 5)) return GFT_E_INVALID;
+    const ByteRange ins[5] = {{match_off, (n_docs + 1) * 8}, {term_id, nm * 4}, {pos, nm * 4},
+                              {bitmap, row_idx ? (uint64_t)W * 4 : n_docs * W * 4}, {row_idx, n_docs * 8}};
+    if (spans_outputs_overlap(span_off, n_docs, span_start, span_len, span_term, cap, ins, 5)) return GFT_E_INVALID;
     // k_span_mark, a workgroup's step at a time
     std::vector<uint32_t> keep(nm);
     for (uint64_t m0 = 0; m0 < nm; m0 += kSpanMarkBlock)

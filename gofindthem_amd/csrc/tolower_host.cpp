@@ -9,6 +9,7 @@
 #include "../../include/gft.h"
 #include "dsl_compile.hpp"
 #include "gft_guard.hpp"
+#include "gft_overlap.hpp"
 
 namespace gft {
 
@@ -35,14 +36,10 @@ const LowerTableHost& lower_table_host() {
 
 bool lower_buffers_overlap(const uint8_t* text, uint64_t lo, uint64_t hi, const uint64_t* doc_off, uint64_t n_docs, const uint8_t* out,
                            uint64_t cap, const uint64_t* out_off) {
-    auto meet = [](const void* a, uint64_t an, const void* b, uint64_t bn) {
-        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-        return an && bn && x < y + bn && y < x + an;
-    };
-    const uint64_t off_bytes = (n_docs + 1) * 8;
-    const uint64_t text_bytes = hi > lo ? hi - lo : 0;    // (the slack behind it is read, but no byte of it decides anything)
-    return meet(text + lo, text_bytes, out, cap) || meet(text + lo, text_bytes, out_off, off_bytes) || meet(doc_off, off_bytes, out, cap) ||
-           meet(doc_off, off_bytes, out_off, off_bytes) || meet(out, cap, out_off, off_bytes);
+    const ByteRange outs[] = {{out, cap}, {out_off, (n_docs + 1) * 8}};
+    // (the slack behind the text is read, but no byte of it decides anything)
+    const ByteRange ins[] = {{text ? text + lo : nullptr, hi > lo ? hi - lo : 0}, {doc_off, (n_docs + 1) * 8}};
+    return outputs_overlap(outs, ins);
 }
 
 // the unit table (k_unit_count, the prefix sum, k_unit_fill)

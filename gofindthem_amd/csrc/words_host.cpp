@@ -37,10 +37,10 @@ int filter_word_matches_host(const uint8_t* text, const uint64_t* doc_off, uint6
     {
         uint64_t lo = doc_off[0], hi = doc_off[0];
         for (uint64_t d = 0; d <= n_docs; d++) { lo = std::min(lo, doc_off[d]); hi = std::max(hi, doc_off[d]); }
-        const void* ins[7] = {text ? text + lo : nullptr, doc_off, off, pos ? pos + e0 : nullptr, len ? len + e0 : nullptr,
-                              term ? term + e0 : nullptr, len ? nullptr : term_len};
-        const uint64_t in_n[7] = {hi - lo, (n_docs + 1) * 8, (n_docs + 1) * 8, n * 4, n * 4, n * 4, (uint64_t)n_terms * 4};
-        if (words_outputs_overlap(out_off, n_docs, out_pos, out_len, out_term, cap, ins, in_n, 7)) return GFT_E_INVALID;
+        const ByteRange ins[7] = {{text ? text + lo : nullptr, hi - lo}, {doc_off, (n_docs + 1) * 8}, {off, (n_docs + 1) * 8},
+                                  {pos ? pos + e0 : nullptr, n * 4}, {len ? len + e0 : nullptr, n * 4}, {term ? term + e0 : nullptr, n * 4},
+                                  {len ? nullptr : term_len, (uint64_t)n_terms * 4}};
+        if (words_outputs_overlap(out_off, n_docs, out_pos, out_len, out_term, cap, ins, 7)) return GFT_E_INVALID;
     }
     // k_words_check
     bool bad = false;
