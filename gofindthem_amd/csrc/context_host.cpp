@@ -31,15 +31,7 @@ int context_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_d
     select_want_words(want, n_cols, wm.data());
     // k_select_mark
     std::vector<uint32_t> sel(n_docs);
-    bool bad = false;
-    for (uint64_t d = 0; d < n_docs; d++) {
-        SelRow r{0, 1};
-        for (uint32_t j = 0; j < W; j++) r = sel_row_join(r, sel_row_word(bitmap[d * W + j], wm[j]));
-        uint32_t s = sel_row_decide(r, mode);
-        if (also && also[d]) s = 1;
-        if (!sel_doc_ok(doc_off[d], doc_off[d + 1])) bad = true;
-        sel[d] = s;
-    }
+    const bool bad = !select_mark_host(doc_off, n_docs, bitmap, W, wm.data(), mode, also, sel.data(), nullptr);
     if (bad) return GFT_E_INVALID;
     if (doc_off[n_docs] > doc_off[0] && !blob) return GFT_E_INVALID;
     if (context_buffers_overlap(blob, doc_off[0], doc_off[n_docs], doc_off, n_docs, bitmap, n_cols, also, fence, out, cap_bytes, out_off, doc_idx,
@@ -130,19 +122,12 @@ int context_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_d
     if (total_bytes) *total_bytes = total;
     // k_ctx_place
     std::vector<uint64_t> c_off(m + 1), c_src(m);
-    c_off[m] = total;
-    if (out_off && m <= cap_docs) out_off[m] = total;
+    const SelPlace O{doc_off, pos.data(), rank.data(), c_off.data(), c_src.data(), out_off, doc_idx, cap_docs};
+    sel_place_close(O, m, total);
     if (group_off && groups <= cap_groups) group_off[groups] = m;
-    for (uint64_t d = 0; d < n_docs; d++) {
-        const uint64_t r = rank[d];
-        if (rank[d + 1] == r) continue;
-        c_off[r] = pos[d];
-        c_src[r] = doc_off[d];
-        if (out_off && r <= cap_docs) out_off[r] = pos[d];
-        if (r < cap_docs) {
-            doc_idx[r] = d;
-            kind[r] = (uint8_t)((word_sel[d / kCtxTile] >> (d % kCtxTile)) & 1u);
-        }
+    for (uint64_t d = 0, r; d < n_docs; d++) {
+        if (!sel_place_doc(O, d, r)) continue;
+        if (r < cap_docs) kind[r] = (uint8_t)((word_sel[d / kCtxTile] >> (d % kCtxTile)) & 1u);
         const uint64_t g = grank[d];
         if (grank[d + 1] != g && group_off && g <= cap_groups) group_off[g] = r;
     }

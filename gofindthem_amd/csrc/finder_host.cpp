@@ -519,14 +519,19 @@ Error Finder::words_refusal() {
     return std::string("whole-word matching needs the GPU substring engine on one device and no regex terms: this finder has ") + why;
 }
 
-Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
-    last_code_ = 0;
-    if (Error werr = words_refusal(); !werr.empty()) return werr;
+Error Finder::resident_refusal() {
     if (!gpu_sub_ || !regexes_.empty()) {
         last_code_ = GFT_E_UNSUPPORTED;
         return "device-resident processing needs the GPU substring engine and no regex terms";
     }
     if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    return "";
+}
+
+Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
+    last_code_ = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
@@ -538,11 +543,7 @@ Error Finder::ProcessDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, ui
 
 Error Finder::SplitLinesDevice(const uint8_t* d_blob, uint64_t len, uint32_t mode, uint64_t* d_doc_off, uint64_t cap, uint64_t* n_docs) {
     last_code_ = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     int rc = gft_split_lines_device(gpu_->handle(), d_blob, len, mode, d_doc_off, cap, n_docs);
     return rc ? fail_gft(rc) : Error();
 }
@@ -551,11 +552,7 @@ Error Finder::SelectDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off,
                                uint32_t mode, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* d_doc_idx,
                                uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes) {
     last_code_ = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     int rc = gft_select_docs_device(gpu_->handle(), d_blob, d_doc_off, n_docs, d_bitmap, (uint32_t)expressions_.size(), want, mode, d_also, d_out,
                                     cap_bytes, d_out_off, d_doc_idx, cap_docs, n_selected, total_bytes);
     return rc ? fail_gft(rc) : Error();
@@ -567,11 +564,7 @@ Error Finder::ContextDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off
                                 uint64_t* d_group_off, uint64_t cap_groups, uint64_t* n_kept, uint64_t* n_hits, uint64_t* n_groups,
                                 uint64_t* total_bytes) {
     last_code_ = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     int rc = gft_context_docs_device(gpu_->handle(), d_blob, d_doc_off, n_docs, d_bitmap, (uint32_t)expressions_.size(), want, mode, d_also, before,
                                      after, d_fence, d_out, cap_bytes, d_out_off, d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups, n_kept,
                                      n_hits, n_groups, total_bytes);
@@ -582,11 +575,7 @@ Error Finder::RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
                               uint32_t n_buckets, uint32_t mode, uint32_t flags, const uint8_t* d_also, uint8_t* d_out, uint64_t cap_bytes,
                               uint64_t* d_out_off, uint64_t* d_doc_idx, uint64_t cap_docs, uint64_t* bucket_doc, uint64_t* bucket_byte) {
     last_code_ = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     int rc = gft_route_docs_device(gpu_->handle(), d_blob, d_doc_off, n_docs, d_bitmap, (uint32_t)expressions_.size(), masks, n_buckets, mode, flags,
                                    d_also, d_out, cap_bytes, d_out_off, d_doc_idx, cap_docs, bucket_doc, bucket_byte);
     return rc ? fail_gft(rc) : Error();
@@ -602,11 +591,7 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
         return "hit spans in source positions need the span offsets and the length array whenever spans are written";
     }
     if (Error werr = words_refusal(); !werr.empty()) return werr;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
@@ -645,11 +630,7 @@ Error Finder::ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
                              bool snap, uint32_t reach) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
     // spans that index the lowered text are cut from the lowered text: lowered again here, as the spans call lowered it
@@ -678,11 +659,7 @@ Error Finder::MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint6
                          uint64_t* d_doc_run_off, uint64_t* n_runs, uint64_t* total_bytes, int* lowered) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
     // spans that index the lowered text mark the lowered text: lowered again here, as the spans call lowered it
@@ -707,11 +684,7 @@ Error Finder::ReplaceDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, ui
                             uint64_t cap_runs, uint64_t* n_runs, uint64_t* total_bytes, int* lowered) {
     last_code_ = 0;
     if (lowered) *lowered = 0;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
     // spans that index the lowered text replace in the lowered text: lowered again here, as the spans call lowered it
@@ -736,11 +709,7 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     last_code_ = 0;
     if (lowered) *lowered = 0;
     if (Error werr = words_refusal(); !werr.empty()) return werr;
-    if (!gpu_sub_ || !regexes_.empty()) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "device-resident processing needs the GPU substring engine and no regex terms";
-    }
-    if (n_begun_) { last_code_ = GFT_E_INVALID; return "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first"; }
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;

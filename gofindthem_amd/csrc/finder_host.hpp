@@ -242,6 +242,7 @@ private:
     bool caseSensitive_;
     bool wholeWords_ = false;
     Error words_refusal();               // "" or, with the option on, why this finder cannot match whole words (last_code_ set)
+    Error resident_refusal();            // "" or why a resident batch cannot be taken: engine or regex terms, batches in flight (last_code_ set)
     GpuEngine* gpu_;
     bool gpu_sub_;                       // subEng_ is the GPU engine itself: scanning is fused into gft_process
     bool programs_dirty_ = true;

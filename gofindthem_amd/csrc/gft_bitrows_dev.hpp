@@ -6,6 +6,7 @@
 //   walk_bit_rows<false>  popcount per row                                      -> Sink::count(row, c)
 //   walk_bit_rows<true>   exclusive prefix of the word popcounts inside a row, then every lane hands the set bits of its
 //                         word, lowest first, to Sink::emit(key, x, Sink::base(row) + prefix ...)
+//   join_bit_rows         an arbitrary value per word joined over the row (gft_select.hip, gft_route.hip): at the end of this file
 //
 // Both passes read the bitmap with the lanes of a wave on consecutive words.  W <= 64: a wave takes 64 / W' rows at once
 // (W' = W rounded up to a power of two; a row is a segment of W' lanes, the lanes W..W'-1 of a segment idle) and reduces /
@@ -26,6 +27,7 @@
 #include <algorithm>
 
 #include "gft_bitrows.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -140,6 +142,54 @@ __device__ __forceinline__ void walk_bit_rows(const BitRows& B, const Sink& S) {
             }
         }
     }
+}
+
+// ---- join_bit_rows: an arbitrary value per word, joined over the row ----------------------------------------------------------
+// The same walk for a row that is not counted but compared (gft_select.hip: with `want`; gft_route.hip: with every mask).  One
+// group of 64 / W' rows in flight, no tail mask (the sinks' column words are cut to n_cols), W == 0 is the caller's.  The sink:
+//   Value, Col                  what is joined; what a lane knows about its column
+//   Value identity()            the row of no words, and what an idle lane holds
+//   Col column(j)               word j's column context, j < W: asked once in front of the loop for W <= 64 (the stores of finish
+//                               keep the compiler from hoisting it on its own), per step above that
+//   Value word(w, col)          what word w of a row says
+//   Value join(a, b)
+//   Value exchange(v, s)        v of the lane s away (xor)
+//   void finish(row, v)         the finished row, in one lane
+template <class Sink>
+__device__ __forceinline__ void join_bit_rows(const BitRows& B, const Sink& S) {
+    using Value = typename Sink::Value;
+    const WaveId id(kBitRowsBlock);
+    const uint32_t W = B.W;
+    if (W <= 64) {
+        const uint32_t Wp = 1u << B.lg, R = 64u >> B.lg;
+        const uint32_t seg = id.lane >> B.lg, j = id.lane & (Wp - 1);
+        typename Sink::Col col{};
+        if (j < W) col = S.column(j);
+        const uint64_t n_groups = (B.n_rows + R - 1) / R;
+        for (uint64_t g = id.wave; g < n_groups; g += id.n_waves) {
+            const uint64_t row = g * R + seg;
+            Value v = (j < W && row < B.n_rows) ? S.word(B.bitmap[row * W + j], col) : S.identity();
+            for (uint32_t s = 1; s < Wp; s <<= 1) v = S.join(v, S.exchange(v, s));
+            if (j == 0 && row < B.n_rows) S.finish(row, v);
+        }
+    } else {
+        for (uint64_t row = id.wave; row < B.n_rows; row += id.n_waves) {
+            const uint32_t* r = B.bitmap + row * W;
+            Value v = S.identity();                                 // (the carry from step to step)
+            for (uint32_t k = 0; k < W; k += 64) {
+                const uint32_t j = k + id.lane;
+                if (j < W) v = S.join(v, S.word(r[j], S.column(j)));
+            }
+            for (uint32_t s = 1; s < 64; s <<= 1) v = S.join(v, S.exchange(v, s));
+            if (id.lane == 0) S.finish(row, v);
+        }
+    }
+}
+
+// blocks of kBitRowsBlock threads for a kernel around join_bit_rows; flat: it has no words to walk and takes a thread a row
+inline unsigned join_rows_grid(const BitRows& B, bool flat, unsigned n_cus) {
+    const uint64_t waves = flat ? (B.n_rows + 63) / 64 : B.W <= 64 ? (B.n_rows + (64u >> B.lg) - 1) / (64u >> B.lg) : B.n_rows;
+    return wave_grid(waves, kBitRowsBlock, n_cus);
 }
 
 }  // namespace gft

@@ -6,7 +6,7 @@
 //                        lane 0 stores them and what they say to the other tiles (last / first selected, last / first fence)
 //   k_ctx_carry_blocks   a wave a carry block of 64 tiles, a lane a tile: the block's own four extrema and its selected count
 //   k_ctx_carry_spine    ONE wave over the blocks, 64 per trip: the maxima forward, the minima backward, exclusive, in place; the
-//                        selected count of the batch -> ctl[5]
+//                        selected count of the batch -> ctl[kCtxCtlHits]
 //   k_ctx_carry_tiles    a wave a carry block again: the exclusive extrema inside the block joined with the block's -> carry[t]
 //   k_ctx_decide         a wave a tile again: every lane finds its nearest selected document on either side that no fence separates
 //                        (clz / ctz on the masked words inside the tile, the carry outside) -> keep, len, newgroup; the left
@@ -23,21 +23,13 @@
 #include <algorithm>
 
 #include "gft_context.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
 
 constexpr uint32_t kCtxBlock = 256;         // 4 waves, each on a tile (or a carry block) of its own: no LDS, no barrier
-
-__device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32 | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-__device__ __forceinline__ uint64_t lane_value64(uint64_t v, int lane) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), lane) << 32 | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-}
-__device__ __forceinline__ uint64_t up64(uint64_t v, uint32_t s) { return __shfl_up(v, s, 64); }
-__device__ __forceinline__ uint64_t down64(uint64_t v, uint32_t s) { return __shfl_down(v, s, 64); }
 
 // over the lanes of a wave: the maximum / minimum of the lanes in front of / behind this one (exclusive), and of all in `all`
 __device__ __forceinline__ uint64_t wave_max_front(uint64_t v, uint32_t lane, uint64_t& all) {
@@ -63,17 +55,8 @@ __device__ __forceinline__ uint64_t wave_min_behind(uint64_t v, uint32_t lane, u
     return lane < 63 ? ex : kCtxNone;
 }
 
-struct WaveId {
-    uint32_t lane;
-    uint64_t wave, n_waves;
-};
-__device__ __forceinline__ WaveId wave_id() {
-    const uint64_t thread = (uint64_t)blockIdx.x * kCtxBlock + threadIdx.x;
-    return WaveId{threadIdx.x & 63u, thread >> 6, ((uint64_t)gridDim.x * kCtxBlock) >> 6};
-}
-
 __global__ void __launch_bounds__(kCtxBlock) k_ctx_reach(const ContextParams P) {
-    const WaveId w = wave_id();
+    const WaveId w(kCtxBlock);
     for (uint64_t t = w.wave; t < P.n_tiles; t += w.n_waves) {
         const uint64_t base = t * kCtxTile, d = base + w.lane;
         const bool in = d < P.n_docs;
@@ -91,7 +74,7 @@ __global__ void __launch_bounds__(kCtxBlock) k_ctx_reach(const ContextParams P) 
 }
 
 __global__ void __launch_bounds__(kCtxBlock) k_ctx_carry_blocks(const ContextParams P) {
-    const WaveId w = wave_id();
+    const WaveId w(kCtxBlock);
     for (uint64_t b = w.wave; b < P.n_blocks; b += w.n_waves) {
         const uint64_t t = b * kCtxCarry + w.lane;
         const bool in = t < P.n_tiles;
@@ -153,11 +136,11 @@ __global__ void __launch_bounds__(kCtxSpine) k_ctx_carry_spine(const ContextPara
     }
 #pragma unroll
     for (uint32_t s = 32; s; s >>= 1) hits += down64(hits, s);
-    if (lane == 0) P.ctl[5] = hits;
+    if (lane == 0) P.ctl[kCtxCtlHits] = hits;
 }
 
 __global__ void __launch_bounds__(kCtxBlock) k_ctx_carry_tiles(const ContextParams P) {
-    const WaveId w = wave_id();
+    const WaveId w(kCtxBlock);
     for (uint64_t b = w.wave; b < P.n_blocks; b += w.n_waves) {
         const uint64_t t = b * kCtxCarry + w.lane;
         const bool in = t < P.n_tiles;
@@ -176,7 +159,7 @@ __global__ void __launch_bounds__(kCtxBlock) k_ctx_carry_tiles(const ContextPara
 }
 
 __global__ void __launch_bounds__(kCtxBlock) k_ctx_decide(const ContextParams P) {
-    const WaveId w = wave_id();
+    const WaveId w(kCtxBlock);
     for (uint64_t t = w.wave; t < P.n_tiles; t += w.n_waves) {
         const uint64_t base = t * kCtxTile, d = base + w.lane;
         // (the same in every lane: scalar values)
@@ -197,59 +180,45 @@ __global__ void __launch_bounds__(kCtxBlock) k_ctx_decide(const ContextParams P)
 }
 
 __global__ void k_ctx_pack(const ContextParams P) {
-    P.ctl[0] = P.pos[P.n_docs];
-    P.ctl[1] = P.rank[P.n_docs];
-    P.ctl[2] = P.doc_off[0];
-    P.ctl[3] = P.doc_off[P.n_docs];
-    P.ctl[6] = P.grank[P.n_docs];
+    P.ctl[kSelCtlTotal] = P.pos[P.n_docs];
+    P.ctl[kSelCtlM] = P.rank[P.n_docs];
+    P.ctl[kSelCtlLo] = P.doc_off[0];
+    P.ctl[kSelCtlHi] = P.doc_off[P.n_docs];
+    P.ctl[kCtxCtlGroups] = P.grank[P.n_docs];
 }
 
 __global__ void __launch_bounds__(kCtxBlock) k_ctx_place(const ContextParams P) {
     const uint64_t d = (uint64_t)blockIdx.x * kCtxBlock + threadIdx.x;
     if (d == 0) {
-        P.c_off[P.m] = P.total;
-        if (P.out_off && P.m <= P.cap_docs) P.out_off[P.m] = P.total;
+        sel_place_close(P, P.m, P.total);
         if (P.group_off && P.groups <= P.cap_groups) P.group_off[P.groups] = P.m;
     }
-    if (d >= P.n_docs) return;
-    const uint64_t r = P.rank[d];
-    if (P.rank[d + 1] == r) return;                                 // not kept
-    const uint64_t at = P.pos[d];
-    P.c_off[r] = at;
-    P.c_src[r] = P.doc_off[d];
-    if (P.out_off && r <= P.cap_docs) P.out_off[r] = at;
-    if (r < P.cap_docs) {
-        P.doc_idx[r] = d;
-        P.kind[r] = (uint8_t)((P.word_sel[d / kCtxTile] >> (d % kCtxTile)) & 1u);
-    }
+    uint64_t r;
+    if (d >= P.n_docs || !sel_place_doc(P, d, r)) return;
+    if (r < P.cap_docs) P.kind[r] = (uint8_t)((P.word_sel[d / kCtxTile] >> (d % kCtxTile)) & 1u);
     const uint64_t g = P.grank[d];
     if (P.grank[d + 1] != g && P.group_off && g <= P.cap_groups) P.group_off[g] = r;
-}
-
-unsigned wave_grid(uint64_t waves, unsigned n_cus) {
-    const uint64_t blocks = std::min<uint64_t>((waves + kCtxBlock / 64 - 1) / (kCtxBlock / 64), (uint64_t)std::max(n_cus, 1u) * 8);
-    return (unsigned)std::max<uint64_t>(blocks, 1);
 }
 
 }  // namespace
 
 hipError_t launch_context_reach(const ContextParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
-    k_ctx_reach<<<dim3(wave_grid(P.n_tiles, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
+    k_ctx_reach<<<dim3(wave_grid(P.n_tiles, kCtxBlock, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 
 hipError_t launch_context_carry(const ContextParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
-    k_ctx_carry_blocks<<<dim3(wave_grid(P.n_blocks, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
+    k_ctx_carry_blocks<<<dim3(wave_grid(P.n_blocks, kCtxBlock, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
     k_ctx_carry_spine<<<dim3(1), dim3(kCtxSpine), 0, st>>>(P);
-    k_ctx_carry_tiles<<<dim3(wave_grid(P.n_blocks, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
+    k_ctx_carry_tiles<<<dim3(wave_grid(P.n_blocks, kCtxBlock, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 
 hipError_t launch_context_decide(const ContextParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
-    k_ctx_decide<<<dim3(wave_grid(P.n_tiles, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
+    k_ctx_decide<<<dim3(wave_grid(P.n_tiles, kCtxBlock, n_cus)), dim3(kCtxBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 

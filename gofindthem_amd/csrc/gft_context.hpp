@@ -53,7 +53,7 @@ struct ContextParams {
     const uint64_t* pos;       // [n_docs + 1]   exclusive prefix sums of len, keep, newgroup
     const uint64_t* rank;
     const uint64_t* grank;
-    uint64_t* ctl;             // [7]            total, kept, doc_off[0], doc_off[n_docs], flag (k_select_mark), hits, groups
+    uint64_t* ctl;             // [kCtxCtlWords] the select's words (the flag is k_select_mark's), then hits and groups
     uint64_t* c_off;           // [m + 1]        place -> the select's copy pass
     uint64_t* c_src;           // [m]
     uint64_t m, total, groups;

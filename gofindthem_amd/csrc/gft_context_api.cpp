@@ -1,14 +1,13 @@
 // gft_context_api.cpp -- context lines round the documents that matched (gft_context.hip): gft_context_docs_device, and the host
 // walk behind gft_debug_context_docs.
 #include "gft_context.hpp"
-#include "gft_engine.hpp"
-#include "gft_select.hpp"
+#include "gft_doc_gather.hpp"
 
 using namespace gft;
 using namespace gft::api;
 
 namespace {
-constexpr RoomTexts kContextRoom{"no device memory for the context call's work buffers", "context alloc"};
+constexpr DocGather kContext{"gft_context_docs_device", "context", {"no device memory for the context call's work buffers", "context alloc"}};
 }
 
 extern "C" {
@@ -38,31 +37,20 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
         return fail(e, GFT_E_INVALID, "gft_context_docs_device: a size beyond the address space");
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
-    if (!n_docs) {
-        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, st), "context offsets");
-        if (d_group_off) HIP_TRY(hipMemsetAsync(d_group_off, 0, 8, st), "context offsets");
-        HIP_TRY(hipStreamSynchronize(st), "context offsets");
-        return GFT_OK;
-    }
+    if (!n_docs) return doc_gather_empty(e, kContext, d_out_off, d_group_off);
     auto& S = e->d_context;
     std::vector<uint32_t> h_want(std::max<uint32_t>(W, 1), 0);
     SyncOnExit drain(e);                                            // (h_want is handed to an asynchronous copy)
     select_want_words(want, n_cols, h_want.data());
     const uint64_t n_tiles = ctx_tiles(n_docs), n_blocks = ctx_blocks(n_tiles);
-    if ((rc = room(e, S.want, (uint64_t)W * 4, kContextRoom)) || (rc = room(e, S.sel, n_docs * 4, kContextRoom)) ||
-        (rc = room(e, S.len, n_docs * 4, kContextRoom)) || (rc = room(e, S.keep, n_docs * 4, kContextRoom)) ||
-        (rc = room(e, S.word_sel, n_tiles * 8, kContextRoom)) || (rc = room(e, S.word_fence, n_tiles * 8, kContextRoom)) ||
-        (rc = room(e, S.sum, n_tiles * 32, kContextRoom)) || (rc = room(e, S.carry, n_tiles * 32, kContextRoom)) ||
-        (rc = room(e, S.part, n_blocks * 40, kContextRoom)) || (rc = room(e, S.pos, (n_docs + 1) * 8, kContextRoom)) ||
-        (rc = room(e, S.rank, (n_docs + 1) * 8, kContextRoom)) || (rc = room(e, S.grank, (n_docs + 1) * 8, kContextRoom)) ||
-        (rc = room(e, S.partial, scan_partials_needed(n_docs) * 8, kContextRoom)) || (rc = room(e, S.ctl, 56, kContextRoom)))
+    if ((rc = room(e, S.want, (uint64_t)W * 4, kContext.room)) || (rc = room(e, S.sel, n_docs * 4, kContext.room)) ||
+        (rc = room(e, S.len, n_docs * 4, kContext.room)) || (rc = room(e, S.keep, n_docs * 4, kContext.room)) ||
+        (rc = room(e, S.word_sel, n_tiles * 8, kContext.room)) || (rc = room(e, S.word_fence, n_tiles * 8, kContext.room)) ||
+        (rc = room(e, S.sum, n_tiles * 32, kContext.room)) || (rc = room(e, S.carry, n_tiles * 32, kContext.room)) ||
+        (rc = room(e, S.part, n_blocks * 40, kContext.room)) || (rc = room(e, S.pos, (n_docs + 1) * 8, kContext.room)) ||
+        (rc = room(e, S.rank, (n_docs + 1) * 8, kContext.room)) || (rc = room(e, S.grank, (n_docs + 1) * 8, kContext.room)) ||
+        (rc = room(e, S.partial, scan_partials_needed(n_docs) * 8, kContext.room)) || (rc = room(e, S.ctl, kCtxCtlWords * 8, kContext.room)))
         return rc;
-    // the select's mark pass decides who is selected, and finds offsets that descend and documents of 4 GiB or more (ctl[4])
-    SelectParams M{};
-    M.text = d_text_blob; M.doc_off = d_doc_off; M.n_docs = n_docs; M.bitmap = d_bitmap;
-    M.W = W; M.lg = bit_row_lg(W);
-    M.mode = mode; M.want = S.want.as<uint32_t>(); M.also = d_also;
-    M.len = S.len.as<uint32_t>(); M.sel = S.sel.as<uint32_t>(); M.ctl = S.ctl.as<uint64_t>();
     ContextParams P{};
     P.doc_off = d_doc_off; P.n_docs = n_docs; P.n_tiles = n_tiles; P.n_blocks = n_blocks;
     P.sel = S.sel.as<uint32_t>(); P.fence = d_fence; P.before = before; P.after = after;
@@ -71,12 +59,11 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
     P.keep = S.keep.as<uint32_t>(); P.len = S.len.as<uint32_t>();
     P.newgroup = S.sel.as<uint32_t>();                              // (the marks are in the tiles' words by then)
     P.pos = S.pos.as<uint64_t>(); P.rank = S.rank.as<uint64_t>(); P.grank = S.grank.as<uint64_t>(); P.ctl = S.ctl.as<uint64_t>();
-    {
-        ProfScope ps(e, "context_mark");
-        if (W) HIP_TRY(hipMemcpyAsync(S.want.p, h_want.data(), (size_t)W * 4, hipMemcpyHostToDevice, st), "context mask upload");
-        HIP_TRY(hipMemsetAsync(P.ctl, 0, 56, st), "context mark");
-        HIP_TRY(launch_select_mark(M, e->n_cus, st), "context mark kernel launch");
-    }
+    // the select's mark pass decides who is selected, and finds offsets that descend and documents of 4 GiB or more
+    SelectParams M{};
+    if ((rc = doc_gather_select_mark(e, kContext, M, d_text_blob, d_doc_off, n_docs, d_bitmap, n_cols, mode, d_also, h_want.data(), S.want, S.len, S.sel,
+                                     S.ctl, kCtxCtlWords)))
+        return rc;
     {
         ProfScope ps(e, "context_reach");
         HIP_TRY(launch_context_reach(P, e->n_cus, st), "context reach kernel launch");
@@ -96,19 +83,17 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
         HIP_TRY(launch_exclusive_scan(P.newgroup, n_docs, S.grank.as<uint64_t>(), S.partial.as<uint64_t>(), st), "context scan");
         HIP_TRY(launch_context_pack(P, st), "context scan");
     }
-    uint64_t h_ctl[7] = {0, 0, 0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctl, P.ctl, 56, hipMemcpyDeviceToHost, st), "context totals");
-    HIP_TRY(hipStreamSynchronize(st), "context totals");
-    if (h_ctl[4]) return fail(e, GFT_E_INVALID, "gft_context_docs_device: document offsets descend, or a document of 4 GiB or more");
-    if (context_buffers_overlap(d_text_blob, h_ctl[2], h_ctl[3], d_doc_off, n_docs, d_bitmap, n_cols, d_also, d_fence, d_out, cap_bytes, d_out_off,
-                                d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups))
-        return fail(e, GFT_E_INVALID, "gft_context_docs_device: an output overlaps an input");
-    P.total = h_ctl[0]; P.m = h_ctl[1]; P.groups = h_ctl[6];
+    uint64_t h_ctl[kCtxCtlWords] = {0};
+    if ((rc = doc_gather_read(e, kContext, P.ctl, h_ctl, kCtxCtlWords))) return rc;
+    if (context_buffers_overlap(d_text_blob, h_ctl[kSelCtlLo], h_ctl[kSelCtlHi], d_doc_off, n_docs, d_bitmap, n_cols, d_also, d_fence, d_out, cap_bytes,
+                                d_out_off, d_doc_idx, d_kind, cap_docs, d_group_off, cap_groups))
+        return doc_gather_overlap(e, kContext);
+    P.total = h_ctl[kSelCtlTotal]; P.m = h_ctl[kSelCtlM]; P.groups = h_ctl[kCtxCtlGroups];
     if (n_kept) *n_kept = P.m;
-    if (n_hits) *n_hits = h_ctl[5];
+    if (n_hits) *n_hits = h_ctl[kCtxCtlHits];
     if (n_groups) *n_groups = P.groups;
     if (total_bytes) *total_bytes = P.total;
-    if ((rc = room(e, S.c_off, (P.m + 1) * 8, kContextRoom)) || (rc = room(e, S.c_src, P.m * 8, kContextRoom))) return rc;
+    if ((rc = room(e, S.c_off, (P.m + 1) * 8, kContext.room)) || (rc = room(e, S.c_src, P.m * 8, kContext.room))) return rc;
     P.c_off = S.c_off.as<uint64_t>(); P.c_src = S.c_src.as<uint64_t>();
     P.out_off = d_out_off; P.doc_idx = d_doc_idx; P.kind = d_kind; P.cap_docs = cap_docs;
     P.group_off = d_group_off; P.cap_groups = cap_groups;
@@ -117,10 +102,7 @@ int gft_context_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uin
         HIP_TRY(launch_context_place(P, st), "context place kernel launch");
     }
     // the bytes: the select's copy pass over the compact arrays
-    if ((rc = select_copy_run(e, d_text_blob, P.c_off, P.c_src, P.m, P.total, d_out, cap_bytes, "context_copy", "context copy kernel launch")))
-        return rc;
-    HIP_TRY(hipStreamSynchronize(st), "context copy");
-    return GFT_OK;
+    return doc_gather_copy(e, kContext, d_text_blob, P.c_off, P.c_src, P.m, P.total, d_out, cap_bytes);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_context_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,

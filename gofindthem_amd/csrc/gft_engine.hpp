@@ -405,13 +405,6 @@ int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off,
                 uint64_t* d_out_off, uint64_t* n_units, uint64_t* total, const char* who, const char* stage = nullptr,
                 uint64_t* text_range = nullptr);
 
-// ---- gft_select_api.cpp ------------------------------------------------------------------------------------------------
-// the select's copy pass over compact arrays another call has filled: the m entries c_off [m + 1] / c_src [m] of `text`, `total`
-// bytes of them, into out[0, cap_bytes) under the gft_profile_read name `stage` (no byte to write: no launch, no stage).
-// what: what fail_hip names
-int select_copy_run(gft_engine* e, const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, uint64_t total, uint8_t* out,
-                    uint64_t cap_bytes, const char* stage, const char* what);
-
 // ---- gft_staging.cpp ---------------------------------------------------------------------------------------------------
 // device -> pageable host memory through the bounce buffers; synchronous: returns when dst holds the bytes
 int d2h_staged(gft_engine* e, void* dst, const void* src, size_t bytes);

@@ -1,6 +1,7 @@
 // gft_excerpt_api.cpp -- excerpts: the text around the hit spans, cut and gathered (gft_excerpt.hip, the copy pass of
 // gft_select.hip): gft_excerpt_spans_device, gft_excerpt_spans_snap_device (the windows snapped to word or line borders), and the
 // host walk behind gft_debug_excerpt_spans / gft_debug_excerpt_spans_snap / gft_debug_excerpt_snap_edges.
+#include "gft_doc_gather.hpp"
 #include "gft_engine.hpp"
 #include "gft_excerpt.hpp"
 #include "gft_span_runs.hpp"

@@ -26,16 +26,13 @@
 #include <algorithm>
 
 #include "gft_mark.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
 
 constexpr uint32_t kMarkBlock = 256;        // 4 waves; the copy pass: a tile each
-
-__device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32 | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
 
 __global__ void __launch_bounds__(kExcTile) k_mark_check(const MarkParams P) {
     const ExcerptParams& X = P.X;
@@ -76,7 +73,7 @@ __global__ void __launch_bounds__(kMarkBlock) k_mark_copy(const MarkParams P) {
     __shared__ uint32_t wrel[kMarkBlock / 64][kMarkWindow];
     if (threadIdx.x < kMarkWords) marks[threadIdx.x] = P.marks[threadIdx.x];
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wv = first_lane32(threadIdx.x >> 6);
     const uint64_t tile = (uint64_t)blockIdx.x * (kMarkBlock / 64) + wv;
     const SelGeom G = P.G;
     const MarkPlan M = P.M;

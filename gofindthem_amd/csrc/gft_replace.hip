@@ -33,15 +33,13 @@
 #include <algorithm>
 
 #include "gft_replace.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
 
 constexpr uint32_t kRepBlock = 256;         // 4 waves; the copy pass: a tile each
-
-__device__ __forceinline__ uint32_t first_lane32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t first_lane64(uint64_t v) { return (uint64_t)first_lane32((uint32_t)(v >> 32)) << 32 | first_lane32((uint32_t)v); }
 
 __global__ void __launch_bounds__(kExcTile) k_replace_ids(const ReplaceParams P) {
     const ExcerptParams& X = P.X;

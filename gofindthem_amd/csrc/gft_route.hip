@@ -3,11 +3,11 @@
 //   (text, doc_off, hit rows, n_buckets masks, mode, rest, also)  ->  out: the entries' documents back to back, bucket by bucket
 //   and in input order inside a bucket, out_off, doc_idx; the bucket borders in entries and in bytes
 //
-//   k_route_mark    reads the rows with the walk of k_select_mark (64 / W' rows per wave for W <= 64, a row per wave in steps of
-//                   64 words above that).  A lane compares its word with the same word of every mask -- the masks lie in LDS for
-//                   W <= 64 (at most 64 x 64 words, 16 KB; lanes on consecutive words: no bank conflict), and come through L2
-//                   above that -- and the 64-bit hit words are joined over the row by xor shuffles
-//                   -> member[d] (bit b: an entry in bucket b), len[d]; raises ctl[flag] as mark_finish of the select does
+//   k_route_mark    reads the rows with join_bit_rows of gft_bitrows_dev.hpp, as k_select_mark does (64 / W' rows per wave for
+//                   W <= 64, a row per wave in steps of 64 words above that).  A lane compares its word with the same word of
+//                   every mask -- the masks lie in LDS for W <= 64 (at most 64 x 64 words, 16 KB; lanes on consecutive words: no
+//                   bank conflict), and come through L2 above that -- and the 64-bit hit words are joined over the row by xor shuffles
+//                   -> member[d] (bit b: an entry in bucket b), len[d]; raises ctl[kRouteCtlFlag] as the select's mark pass does
 //   k_route_count   a wave a tile of 64 documents, lane b owns bucket b: per bucket one ballot of bit b and a popcount
 //                   -> cnt[b * n_tiles + tile]; tile_bytes[tile] (the lengths once per entry, joined by shuffles)
 //   (k_scan_* of gft_kernels.hip: cnt -> base, B * n_tiles entries in one pass: every (bucket, tile) base, the borders, m)
@@ -24,6 +24,7 @@
 
 #include <algorithm>
 
+#include "gft_bitrows_dev.hpp"
 #include "gft_kernels.hpp"
 #include "gft_route.hpp"
 
@@ -31,64 +32,56 @@ namespace gft {
 
 namespace {
 
-constexpr uint32_t kRouteBlock = 256;                   // 4 waves
+constexpr uint32_t kRouteBlock = kBitRowsBlock;         // 4 waves
 constexpr uint32_t kRouteLdsWords = 64 * 64;            // the masks of W <= 64: GFT_ROUTE_MAX_BUCKETS rows of at most 64 words
 
-__device__ __forceinline__ uint64_t shuffle_xor64(uint64_t v, int s) {
-    return (uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), s, 64) << 32 | (uint32_t)__shfl_xor((int)(uint32_t)v, s, 64);
-}
-
-__device__ __forceinline__ void route_mark_finish(const RouteParams& P, uint64_t row, uint64_t hits) {
-    const uint64_t a = P.doc_off[row], b = P.doc_off[row + 1];
-    const uint32_t ok = sel_doc_ok(a, b);
-    if (!ok) P.ctl[kRouteCtlFlag] = 1;
-    P.len[row] = ok ? (uint32_t)(b - a) : 0u;
-    P.member[row] = route_member(hits, P.n_buckets, P.mode, P.rest, (P.also && P.also[row]) ? 1u : 0u);
-}
+// What join_bit_rows joins over a row: the 64-bit word of the masks the row's words meet.  Masks: where the masks lie -- the
+// kernel's LDS array itself for W <= 64 (so that the inlined walk reads it as LDS), the engine's copy above that.
+template <class Masks>
+struct RouteSink {
+    using Value = uint64_t;
+    using Col = uint32_t;
+    const RouteParams& P;
+    Masks masks;
+    __device__ __forceinline__ uint64_t identity() const { return 0; }
+    __device__ __forceinline__ uint32_t column(uint32_t j) const { return j; }
+    __device__ __forceinline__ uint64_t word(uint32_t w, uint32_t j) const {
+        uint64_t hits = 0;
+        if (w)
+            for (uint32_t k = 0; k < P.n_buckets; k++) hits |= route_word_bit(w, masks[(uint64_t)k * P.W + j], k);
+        return hits;
+    }
+    __device__ __forceinline__ uint64_t join(uint64_t a, uint64_t b) const { return a | b; }
+    __device__ __forceinline__ uint64_t exchange(uint64_t v, uint32_t s) const { return shuffle_xor64(v, (int)s); }
+    __device__ __forceinline__ void finish(uint64_t row, uint64_t hits) const {
+        const uint64_t a = P.doc_off[row], b = P.doc_off[row + 1];
+        const uint32_t ok = sel_doc_ok(a, b);
+        if (!ok) P.ctl[kRouteCtlFlag] = 1;
+        P.len[row] = ok ? (uint32_t)(b - a) : 0u;
+        P.member[row] = route_member(hits, P.n_buckets, P.mode, P.rest, (P.also && P.also[row]) ? 1u : 0u);
+    }
+};
 
 __global__ void __launch_bounds__(kRouteBlock) k_route_mark(const RouteParams P) {
     __shared__ uint32_t s_masks[kRouteLdsWords];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t thread = (uint64_t)blockIdx.x * kRouteBlock + threadIdx.x, n_threads = (uint64_t)gridDim.x * kRouteBlock;
-    const uint64_t wave = thread >> 6, n_waves = n_threads >> 6;
-    const uint32_t W = P.W, K = P.n_buckets;
-    if (W == 0 || K == 0) {
-        for (uint64_t row = thread; row < P.n_docs; row += n_threads) route_mark_finish(P, row, 0);
-    } else if (W <= 64) {
-        for (uint32_t i = threadIdx.x; i < K * W; i += kRouteBlock) s_masks[i] = P.masks[i];
+    const BitRows B{P.bitmap, P.n_docs, P.W, P.lg, 0};
+    if (P.W == 0 || P.n_buckets == 0) {
+        const RouteSink<const uint32_t*> S{P, P.masks};
+        const uint64_t thread = (uint64_t)blockIdx.x * kRouteBlock + threadIdx.x, n_threads = (uint64_t)gridDim.x * kRouteBlock;
+        for (uint64_t row = thread; row < P.n_docs; row += n_threads) S.finish(row, 0);
+    } else if (P.W <= 64) {
+        for (uint32_t i = threadIdx.x; i < P.n_buckets * P.W; i += kRouteBlock) s_masks[i] = P.masks[i];
         __syncthreads();
-        const uint32_t Wp = 1u << P.lg, R = 64u >> P.lg;
-        const uint32_t seg = lane >> P.lg, j = lane & (Wp - 1);
-        const uint64_t n_groups = (P.n_docs + R - 1) / R;
-        for (uint64_t g = wave; g < n_groups; g += n_waves) {
-            const uint64_t row = g * R + seg;
-            const uint32_t w = (j < W && row < P.n_docs) ? P.bitmap[row * W + j] : 0u;
-            uint64_t hits = 0;
-            if (w)
-                for (uint32_t k = 0; k < K; k++) hits |= route_word_bit(w, s_masks[k * W + j], k);
-            for (uint32_t s = 1; s < Wp; s <<= 1) hits |= shuffle_xor64(hits, (int)s);
-            if (j == 0 && row < P.n_docs) route_mark_finish(P, row, hits);
-        }
+        join_bit_rows(B, RouteSink<const uint32_t (&)[kRouteLdsWords]>{P, s_masks});
     } else {
-        for (uint64_t row = wave; row < P.n_docs; row += n_waves) {
-            const uint32_t* r = P.bitmap + row * W;
-            uint64_t hits = 0;                                      // (the carry from step to step)
-            for (uint32_t k0 = 0; k0 < W; k0 += 64) {
-                const uint32_t j = k0 + lane;
-                const uint32_t w = j < W ? r[j] : 0u;
-                if (w)
-                    for (uint32_t k = 0; k < K; k++) hits |= route_word_bit(w, P.masks[(uint64_t)k * W + j], k);
-            }
-            for (uint32_t s = 1; s < 64; s <<= 1) hits |= shuffle_xor64(hits, (int)s);
-            if (lane == 0) route_mark_finish(P, row, hits);
-        }
+        join_bit_rows(B, RouteSink<const uint32_t*>{P, P.masks});
     }
 }
 
 __global__ void __launch_bounds__(kRouteBlock) k_route_count(const RouteParams P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kRouteBlock + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * kRouteBlock) >> 6;
-    for (uint64_t tile = wave; tile < P.n_tiles; tile += n_waves) {
+    const WaveId w(kRouteBlock);
+    const uint32_t lane = w.lane;
+    for (uint64_t tile = w.wave; tile < P.n_tiles; tile += w.n_waves) {
         const uint64_t d = tile * kRouteTileDocs + lane;
         const uint64_t mem = d < P.n_docs ? P.member[d] : 0ull;
         uint64_t bytes = d < P.n_docs ? route_doc_bytes(P.len[d], mem) : 0ull;
@@ -123,9 +116,9 @@ __global__ void __launch_bounds__(kRouteBlock) k_route_pack(const RouteParams P)
 }
 
 __global__ void __launch_bounds__(kRouteBlock) k_route_place(const RouteParams P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = ((uint64_t)blockIdx.x * kRouteBlock + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * kRouteBlock) >> 6;
-    for (uint64_t tile = wave; tile < P.n_tiles; tile += n_waves) {
+    const WaveId w(kRouteBlock);
+    const uint32_t lane = w.lane;
+    for (uint64_t tile = w.wave; tile < P.n_tiles; tile += w.n_waves) {
         const uint64_t d = tile * kRouteTileDocs + lane;
         const bool in = d < P.n_docs;
         const uint64_t mem = in ? P.member[d] : 0ull;
@@ -150,26 +143,18 @@ __global__ void __launch_bounds__(kRouteBlock) k_route_finish(const RouteParams 
     if (P.out_off && r <= P.m && r <= P.cap_docs) P.out_off[r] = P.c_off[r];
 }
 
-unsigned route_wave_grid(uint64_t n_tiles, unsigned n_cus) {
-    const uint64_t blocks = std::min<uint64_t>((n_tiles + kRouteBlock / 64 - 1) / (kRouteBlock / 64), (uint64_t)std::max(n_cus, 1u) * 8);
-    return (unsigned)std::max<uint64_t>(blocks, 1);
-}
-
 }  // namespace
 
 hipError_t launch_route_mark(const RouteParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
-    // threads that have work: a document each (no words, no masks), a row per segment of W' lanes (W <= 64), a row per wave
-    const bool flat = P.W == 0 || P.n_buckets == 0;
-    const uint64_t threads = flat ? P.n_docs : P.W <= 64 ? ((P.n_docs + (64u >> P.lg) - 1) / (64u >> P.lg)) * 64 : P.n_docs * 64;
-    const uint64_t blocks = std::min<uint64_t>((threads + kRouteBlock - 1) / kRouteBlock, (uint64_t)std::max(n_cus, 1u) * 8);
-    k_route_mark<<<dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(kRouteBlock), 0, st>>>(P);
+    const bool flat = P.W == 0 || P.n_buckets == 0;                 // (no words or no masks: a thread a document)
+    k_route_mark<<<dim3(join_rows_grid(BitRows{P.bitmap, P.n_docs, P.W, P.lg, 0}, flat, n_cus)), dim3(kRouteBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 
 hipError_t launch_route_count(const RouteParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_tiles) return hipSuccess;
-    k_route_count<<<dim3(route_wave_grid(P.n_tiles, n_cus)), dim3(kRouteBlock), 0, st>>>(P);
+    k_route_count<<<dim3(wave_grid(P.n_tiles, kRouteBlock, n_cus)), dim3(kRouteBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 
@@ -180,7 +165,7 @@ hipError_t launch_route_pack(const RouteParams& P, hipStream_t st) {
 
 hipError_t launch_route_place(const RouteParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_tiles || !P.m) return hipSuccess;
-    k_route_place<<<dim3(route_wave_grid(P.n_tiles, n_cus)), dim3(kRouteBlock), 0, st>>>(P);
+    k_route_place<<<dim3(wave_grid(P.n_tiles, kRouteBlock, n_cus)), dim3(kRouteBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 

@@ -25,9 +25,10 @@ inline void route_mask_words(const uint32_t* masks, uint32_t n_buckets, uint32_t
 }
 
 // the words of the control block the host reads back: the entries, the bytes, the text's range, the flag, then the B + 1 bucket
-// borders in entries and -- with the final synchronisation -- in bytes
+// borders in entries and -- with the final synchronisation -- in bytes.  The range and the flag lie where the select has them: the
+// shared read-back (gft_doc_gather.hpp) looks there
 enum : uint32_t {
-    kRouteCtlM = 0, kRouteCtlTotal = 1, kRouteCtlLo = 2, kRouteCtlHi = 3, kRouteCtlFlag = 4, kRouteCtlDoc = 5,
+    kRouteCtlM = 0, kRouteCtlTotal = 1, kRouteCtlLo = kSelCtlLo, kRouteCtlHi = kSelCtlHi, kRouteCtlFlag = kSelCtlFlag, kRouteCtlDoc = 5,
     kRouteCtlByte = kRouteCtlDoc + GFT_ROUTE_MAX_BUCKETS + 1, kRouteCtlWords = kRouteCtlByte + GFT_ROUTE_MAX_BUCKETS + 1
 };
 

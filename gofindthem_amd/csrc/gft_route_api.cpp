@@ -1,13 +1,13 @@
 // gft_route_api.cpp -- documents routed to per-bucket runs of one blob (gft_route.hip): gft_route_docs_device, and the host walk
 // behind gft_debug_route_docs.
-#include "gft_engine.hpp"
+#include "gft_doc_gather.hpp"
 #include "gft_route.hpp"
 
 using namespace gft;
 using namespace gft::api;
 
 namespace {
-constexpr RoomTexts kRouteRoom{"no device memory for the route's work buffers", "route alloc"};
+constexpr DocGather kRoute{"gft_route_docs_device", "route", {"no device memory for the route's work buffers", "route alloc"}};
 #define GFT_STR2(x) #x
 #define GFT_STR(x) GFT_STR2(x)
 }
@@ -41,20 +41,16 @@ int gft_route_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
     if (cap_docs > (~0ull >> 4) || n_docs > (~0ull >> 4)) return fail(e, GFT_E_INVALID, "gft_route_docs_device: a size beyond the address space");
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
-    if (!n_docs) {
-        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, st), "route offsets");
-        HIP_TRY(hipStreamSynchronize(st), "route offsets");
-        return GFT_OK;
-    }
+    if (!n_docs) return doc_gather_empty(e, kRoute, d_out_off);
     auto& S = e->d_route;
     const uint64_t n_tiles = route_tiles(n_docs), n_cells = (uint64_t)B * n_tiles;
     std::vector<uint32_t> h_masks(std::max<uint64_t>((uint64_t)n_buckets * W, 1), 0);
     SyncOnExit drain(e);                                            // (h_masks is handed to an asynchronous copy)
     if (W) route_mask_words(masks, n_buckets, n_cols, h_masks.data());
-    if ((rc = room(e, S.masks, (uint64_t)n_buckets * W * 4, kRouteRoom)) || (rc = room(e, S.member, n_docs * 8, kRouteRoom)) ||
-        (rc = room(e, S.len, n_docs * 4, kRouteRoom)) || (rc = room(e, S.cnt, n_cells * 4, kRouteRoom)) ||
-        (rc = room(e, S.tile_bytes, n_tiles * 8, kRouteRoom)) || (rc = room(e, S.base, (n_cells + 1) * 8, kRouteRoom)) ||
-        (rc = room(e, S.partial, scan_partials_needed(n_cells) * 8, kRouteRoom)) || (rc = room(e, S.ctl, kRouteCtlWords * 8, kRouteRoom)))
+    if ((rc = room(e, S.masks, (uint64_t)n_buckets * W * 4, kRoute.room)) || (rc = room(e, S.member, n_docs * 8, kRoute.room)) ||
+        (rc = room(e, S.len, n_docs * 4, kRoute.room)) || (rc = room(e, S.cnt, n_cells * 4, kRoute.room)) ||
+        (rc = room(e, S.tile_bytes, n_tiles * 8, kRoute.room)) || (rc = room(e, S.base, (n_cells + 1) * 8, kRoute.room)) ||
+        (rc = room(e, S.partial, scan_partials_needed(n_cells) * 8, kRoute.room)) || (rc = room(e, S.ctl, kRouteCtlWords * 8, kRoute.room)))
         return rc;
     RouteParams P{};
     P.doc_off = d_doc_off; P.n_docs = n_docs; P.n_tiles = n_tiles; P.bitmap = d_bitmap;
@@ -79,19 +75,17 @@ int gft_route_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint6
         HIP_TRY(launch_route_pack(P, st), "route scan");
     }
     uint64_t h_ctl[kRouteCtlWords] = {0};
-    HIP_TRY(hipMemcpyAsync(h_ctl, P.ctl, (kRouteCtlDoc + B + 1) * 8, hipMemcpyDeviceToHost, st), "route totals");
-    HIP_TRY(hipStreamSynchronize(st), "route totals");
-    if (h_ctl[kRouteCtlFlag]) return fail(e, GFT_E_INVALID, "gft_route_docs_device: document offsets descend, or a document of 4 GiB or more");
+    if ((rc = doc_gather_read(e, kRoute, P.ctl, h_ctl, kRouteCtlDoc + B + 1))) return rc;
     if (route_buffers_overlap(d_text_blob, h_ctl[kRouteCtlLo], h_ctl[kRouteCtlHi], d_doc_off, n_docs, d_bitmap, n_cols, masks, n_buckets, d_also, d_out,
                               cap_bytes, d_out_off, d_doc_idx, cap_docs, bucket_doc, bucket_byte, B))
-        return fail(e, GFT_E_INVALID, "gft_route_docs_device: an output overlaps an input");
+        return doc_gather_overlap(e, kRoute);
     P.m = h_ctl[kRouteCtlM];
     const uint64_t total = h_ctl[kRouteCtlTotal];
     if (bucket_doc)
         for (uint32_t b = 0; b <= B; b++) bucket_doc[b] = h_ctl[kRouteCtlDoc + b];
     if (!bucket_byte && !d_out_off && !cap_bytes && !cap_docs) return GFT_OK;      // a count of documents: the answer is here
-    if ((rc = room(e, S.ent_len, P.m * 4, kRouteRoom)) || (rc = room(e, S.c_off, (P.m + 1) * 8, kRouteRoom)) ||
-        (rc = room(e, S.c_src, P.m * 8, kRouteRoom)) || (rc = room(e, S.partial, scan_partials_needed(std::max(P.m, n_cells)) * 8, kRouteRoom)))
+    if ((rc = room(e, S.ent_len, P.m * 4, kRoute.room)) || (rc = room(e, S.c_off, (P.m + 1) * 8, kRoute.room)) ||
+        (rc = room(e, S.c_src, P.m * 8, kRoute.room)) || (rc = room(e, S.partial, scan_partials_needed(std::max(P.m, n_cells)) * 8, kRoute.room)))
         return rc;
     P.ent_len = S.ent_len.as<uint32_t>(); P.c_src = S.c_src.as<uint64_t>(); P.c_off = S.c_off.as<uint64_t>();
     P.out_off = d_out_off; P.doc_idx = d_doc_idx; P.cap_docs = cap_docs;

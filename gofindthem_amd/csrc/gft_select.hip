@@ -2,10 +2,10 @@
 //
 //   (text, doc_off, hit rows, want, mode, also)  ->  out: the selected documents back to back, out_off, doc_idx
 //
-//   k_select_mark   reads the rows with the lanes of a wave on consecutive words (64 / W' rows per wave for W <= 64, a row per
-//                   wave in steps of 64 words above that -- the walk of gft_bitrows_dev.hpp, written out here because a row is
-//                   not counted but compared with `want`), joins (any, all) over the row, applies the mode and `also`
-//                   -> len[d], sel[d]; raises ctl[4] for offsets that descend or a document of 4 GiB or more
+//   k_select_mark   reads the rows with join_bit_rows of gft_bitrows_dev.hpp (the lanes of a wave on consecutive words: 64 / W'
+//                   rows per wave for W <= 64, a row per wave in steps of 64 words above that), joins (any, all) against
+//                   `want` over the row, applies the mode and `also`
+//                   -> len[d], sel[d]; raises ctl[kSelCtlFlag] for offsets that descend or a document of 4 GiB or more
 //   (k_scan_* of gft_kernels.hip: len -> pos, sel -> rank; k_select_pack gathers what the host reads back into ctl)
 //   k_select_place  a thread a document: the compact arrays c_off / c_src (complete), the caller's out_off / doc_idx (capped)
 //   k_select_copy   from the OUTPUT side: a wave owns a tile of 4 KiB of the output, a lane a 16-byte chunk aligned to the output
@@ -22,6 +22,7 @@
 
 #include <algorithm>
 
+#include "gft_bitrows_dev.hpp"
 #include "gft_kernels.hpp"
 #include "gft_select.hpp"
 
@@ -29,86 +30,53 @@ namespace gft {
 
 namespace {
 
-constexpr uint32_t kSelBlock = 256;         // 4 waves; the copy pass: a tile each
+constexpr uint32_t kSelBlock = kBitRowsBlock;   // 4 waves; the copy pass: a tile each
 
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ __forceinline__ uint64_t lane_value64(uint64_t v, int lane) {
-    return (uint64_t)lane_value((uint32_t)(v >> 32), lane) << 32 | lane_value((uint32_t)v, lane);
-}
-__device__ __forceinline__ uint64_t shuffle64(uint64_t v, int lane) {
-    return (uint64_t)(uint32_t)__shfl((int)(v >> 32), lane, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
-}
-__device__ __forceinline__ uint64_t first_lane64(uint64_t v) {
-    return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32 | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-}
-
-__device__ __forceinline__ void mark_finish(const SelectParams& P, uint64_t row, SelRow r) {
-    uint32_t s = sel_row_decide(r, P.mode);
-    if (P.also && P.also[row]) s = 1;
-    const uint64_t a = P.doc_off[row], b = P.doc_off[row + 1];
-    const uint32_t ok = sel_doc_ok(a, b);
-    if (!ok) P.ctl[4] = 1;
-    P.len[row] = (s && ok) ? (uint32_t)(b - a) : 0u;
-    P.sel[row] = s;
-}
+// what join_bit_rows joins over a row: (any, all) of the row's words against the same words of `want`
+struct SelectSink {
+    using Value = SelRow;
+    using Col = uint32_t;
+    const SelectParams& P;
+    __device__ __forceinline__ SelRow identity() const { return SelRow{0, 1}; }
+    __device__ __forceinline__ uint32_t column(uint32_t j) const { return P.want[j]; }
+    __device__ __forceinline__ SelRow word(uint32_t w, uint32_t want) const { return sel_row_word(w, want); }
+    __device__ __forceinline__ SelRow join(SelRow a, SelRow b) const { return sel_row_join(a, b); }
+    __device__ __forceinline__ SelRow exchange(SelRow r, uint32_t s) const {
+        return SelRow{(uint32_t)__shfl_xor((int)r.any, (int)s, 64), (uint32_t)__shfl_xor((int)r.all, (int)s, 64)};
+    }
+    __device__ __forceinline__ void finish(uint64_t row, SelRow r) const {
+        uint32_t s = sel_row_decide(r, P.mode);
+        if (P.also && P.also[row]) s = 1;
+        const uint64_t a = P.doc_off[row], b = P.doc_off[row + 1];
+        const uint32_t ok = sel_doc_ok(a, b);
+        if (!ok) P.ctl[kSelCtlFlag] = 1;
+        P.len[row] = (s && ok) ? (uint32_t)(b - a) : 0u;
+        P.sel[row] = s;
+    }
+};
 
 __global__ void __launch_bounds__(kSelBlock) k_select_mark(const SelectParams P) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t thread = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x, n_threads = (uint64_t)gridDim.x * kSelBlock;
-    const uint64_t wave = thread >> 6, n_waves = n_threads >> 6;
-    const uint32_t W = P.W;
-    if (W == 0) {
-        for (uint64_t row = thread; row < P.n_docs; row += n_threads) mark_finish(P, row, SelRow{0, 1});
-    } else if (W <= 64) {
-        const uint32_t Wp = 1u << P.lg, R = 64u >> P.lg;
-        const uint32_t seg = lane >> P.lg, j = lane & (Wp - 1);
-        const uint32_t wm = j < W ? P.want[j] : 0u;
-        const uint64_t n_groups = (P.n_docs + R - 1) / R;
-        for (uint64_t g = wave; g < n_groups; g += n_waves) {
-            const uint64_t row = g * R + seg;
-            const uint32_t w = (j < W && row < P.n_docs) ? P.bitmap[row * W + j] : 0u;
-            SelRow r = sel_row_word(w, wm);
-            for (uint32_t s = 1; s < Wp; s <<= 1) {
-                r.any |= (uint32_t)__shfl_xor((int)r.any, (int)s, 64);
-                r.all &= (uint32_t)__shfl_xor((int)r.all, (int)s, 64);
-            }
-            if (j == 0 && row < P.n_docs) mark_finish(P, row, r);
-        }
+    const SelectSink S{P};
+    if (P.W == 0) {
+        const uint64_t thread = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x, n_threads = (uint64_t)gridDim.x * kSelBlock;
+        for (uint64_t row = thread; row < P.n_docs; row += n_threads) S.finish(row, S.identity());
     } else {
-        for (uint64_t row = wave; row < P.n_docs; row += n_waves) {
-            const uint32_t* r = P.bitmap + row * W;
-            SelRow acc{0, 1};                                       // (the carry from step to step)
-            for (uint32_t k = 0; k < W; k += 64) {
-                const uint32_t j = k + lane;
-                if (j < W) acc = sel_row_join(acc, sel_row_word(r[j], P.want[j]));
-            }
-            const SelRow all{__ballot(acc.any != 0) ? 1u : 0u, __ballot(acc.all == 0) ? 0u : 1u};
-            if (lane == 0) mark_finish(P, row, all);
-        }
+        join_bit_rows(BitRows{P.bitmap, P.n_docs, P.W, P.lg, 0}, S);
     }
 }
 
 __global__ void k_select_pack(const SelectParams P) {
-    P.ctl[0] = P.pos[P.n_docs];
-    P.ctl[1] = P.rank[P.n_docs];
-    P.ctl[2] = P.doc_off[0];
-    P.ctl[3] = P.doc_off[P.n_docs];
+    P.ctl[kSelCtlTotal] = P.pos[P.n_docs];
+    P.ctl[kSelCtlM] = P.rank[P.n_docs];
+    P.ctl[kSelCtlLo] = P.doc_off[0];
+    P.ctl[kSelCtlHi] = P.doc_off[P.n_docs];
 }
 
 __global__ void __launch_bounds__(kSelBlock) k_select_place(const SelectParams P) {
     const uint64_t d = (uint64_t)blockIdx.x * kSelBlock + threadIdx.x;
-    if (d == 0) {
-        P.c_off[P.m] = P.total;
-        if (P.out_off && P.m <= P.cap_docs) P.out_off[P.m] = P.total;
-    }
-    if (d >= P.n_docs) return;
-    const uint64_t r = P.rank[d];
-    if (P.rank[d + 1] == r) return;                                 // not selected
-    const uint64_t at = P.pos[d];
-    P.c_off[r] = at;
-    P.c_src[r] = P.doc_off[d];
-    if (P.out_off && r <= P.cap_docs) P.out_off[r] = at;
-    if (r < P.cap_docs) P.doc_idx[r] = d;
+    uint64_t r;
+    if (d == 0) sel_place_close(P, P.m, P.total);
+    if (d < P.n_docs) sel_place_doc(P, d, r);
 }
 
 // the window across the lanes as sel_lift reads it
@@ -119,7 +87,7 @@ struct WindowRel {
 
 __global__ void __launch_bounds__(kSelBlock) k_select_copy(const SelectParams P) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wv = first_lane32(threadIdx.x >> 6);
     const uint64_t tile = (uint64_t)blockIdx.x * (kSelBlock / 64) + wv;
     const SelGeom G = P.G;
     if (tile >= sel_tiles(G)) return;                               // (the same in every lane)
@@ -178,10 +146,7 @@ __global__ void __launch_bounds__(kSelBlock) k_select_copy(const SelectParams P)
 
 hipError_t launch_select_mark(const SelectParams& P, unsigned n_cus, hipStream_t st) {
     if (!P.n_docs) return hipSuccess;
-    // threads that have work: a document each (W == 0), a row per segment of W' lanes (W <= 64), a row per wave
-    const uint64_t threads = P.W == 0 ? P.n_docs : P.W <= 64 ? ((P.n_docs + (64u >> P.lg) - 1) / (64u >> P.lg)) * 64 : P.n_docs * 64;
-    const uint64_t blocks = std::min<uint64_t>((threads + kSelBlock - 1) / kSelBlock, (uint64_t)std::max(n_cus, 1u) * 8);
-    k_select_mark<<<dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(kSelBlock), 0, st>>>(P);
+    k_select_mark<<<dim3(join_rows_grid(BitRows{P.bitmap, P.n_docs, P.W, P.lg, 0}, P.W == 0, n_cus)), dim3(kSelBlock), 0, st>>>(P);
     return hipGetLastError();
 }
 

@@ -16,6 +16,11 @@ int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
                      const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
                      uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes);
 
+// The mark pass of k_select_mark over every document: sel[d], and len[d] where len is asked for; wm: `want` as select_want_words
+// leaves it.  False when offsets descend or a document has 4 GiB or more.
+bool select_mark_host(const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t W, const uint32_t* wm, uint32_t mode,
+                      const uint8_t* also, uint32_t* sel, uint32_t* len);
+
 // the copy pass alone, every tile of G: the compact arrays c_off [m + 1] / c_src [m] in whatever order their entries come
 void select_copy_host(const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, const SelGeom& G, uint8_t* out);
 
@@ -56,7 +61,7 @@ struct SelectParams {
     uint32_t* sel;             // [n_docs]       mark: 0 / 1
     const uint64_t* pos;       // [n_docs + 1]   exclusive prefix sum of len
     const uint64_t* rank;      // [n_docs + 1]   ... of sel
-    uint64_t* ctl;             // [5]            total, m, doc_off[0], doc_off[n_docs], flag (offsets descend / 4 GiB)
+    uint64_t* ctl;             // [kSelCtlWords] (the context call: [kCtxCtlWords], its own block)
     uint64_t* c_off;           // [m + 1]        place -> copy
     uint64_t* c_src;           // [m]
     uint64_t m, total;

@@ -1,30 +1,13 @@
 // gft_select_api.cpp -- the documents that matched, gathered into one blob (gft_select.hip): gft_select_docs_device, and the host
 // walk behind gft_debug_select_docs.
-#include "gft_engine.hpp"
-#include "gft_select.hpp"
+#include "gft_doc_gather.hpp"
 
 using namespace gft;
 using namespace gft::api;
 
 namespace {
-constexpr RoomTexts kSelectRoom{"no device memory for the select's work buffers", "select alloc"};
+constexpr DocGather kSelect{"gft_select_docs_device", "select", {"no device memory for the select's work buffers", "select alloc"}};
 }
-
-namespace gft::api {
-
-int select_copy_run(gft_engine* e, const uint8_t* text, const uint64_t* c_off, const uint64_t* c_src, uint64_t m, uint64_t total, uint8_t* out,
-                    uint64_t cap_bytes, const char* stage, const char* what) {
-    SelectParams C{};                                               // (only what the copy reads is set)
-    C.text = text; C.c_off = const_cast<uint64_t*>(c_off); C.c_src = const_cast<uint64_t*>(c_src); C.m = m; C.total = total; C.out = out;
-    C.G = sel_geom(total, cap_bytes, out);
-    if (C.G.end) {
-        ProfScope ps(e, stage);
-        HIP_TRY(launch_select_copy(C, e->stream), what);
-    }
-    return GFT_OK;
-}
-
-}  // namespace gft::api
 
 extern "C" {
 
@@ -46,62 +29,43 @@ int gft_select_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint
     if (cap_docs > (~0ull >> 4) || n_docs > (~0ull >> 4)) return fail(e, GFT_E_INVALID, "gft_select_docs_device: a size beyond the address space");
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
-    if (!n_docs) {
-        if (d_out_off) HIP_TRY(hipMemsetAsync(d_out_off, 0, 8, st), "select offsets");
-        HIP_TRY(hipStreamSynchronize(st), "select offsets");
-        return GFT_OK;
-    }
+    if (!n_docs) return doc_gather_empty(e, kSelect, d_out_off);
     auto& S = e->d_select;
     std::vector<uint32_t> h_want(std::max<uint32_t>(W, 1), 0);
     SyncOnExit drain(e);                                            // (h_want is handed to an asynchronous copy)
     select_want_words(want, n_cols, h_want.data());
-    if ((rc = room(e, S.want, (uint64_t)W * 4, kSelectRoom)) || (rc = room(e, S.len, n_docs * 4, kSelectRoom)) ||
-        (rc = room(e, S.sel, n_docs * 4, kSelectRoom)) || (rc = room(e, S.pos, (n_docs + 1) * 8, kSelectRoom)) ||
-        (rc = room(e, S.rank, (n_docs + 1) * 8, kSelectRoom)) || (rc = room(e, S.partial, scan_partials_needed(n_docs) * 8, kSelectRoom)) ||
-        (rc = room(e, S.ctl, 40, kSelectRoom)))
+    if ((rc = room(e, S.want, (uint64_t)W * 4, kSelect.room)) || (rc = room(e, S.len, n_docs * 4, kSelect.room)) ||
+        (rc = room(e, S.sel, n_docs * 4, kSelect.room)) || (rc = room(e, S.pos, (n_docs + 1) * 8, kSelect.room)) ||
+        (rc = room(e, S.rank, (n_docs + 1) * 8, kSelect.room)) || (rc = room(e, S.partial, scan_partials_needed(n_docs) * 8, kSelect.room)) ||
+        (rc = room(e, S.ctl, kSelCtlWords * 8, kSelect.room)))
         return rc;
     SelectParams P{};
-    P.text = d_text_blob; P.doc_off = d_doc_off; P.n_docs = n_docs; P.bitmap = d_bitmap;
-    P.W = W; P.lg = bit_row_lg(W);
-    P.mode = mode; P.want = S.want.as<uint32_t>(); P.also = d_also;
-    P.len = S.len.as<uint32_t>(); P.sel = S.sel.as<uint32_t>(); P.pos = S.pos.as<uint64_t>(); P.rank = S.rank.as<uint64_t>();
-    P.ctl = S.ctl.as<uint64_t>();
-    {
-        ProfScope ps(e, "select_mark");
-        if (W) HIP_TRY(hipMemcpyAsync(S.want.p, h_want.data(), (size_t)W * 4, hipMemcpyHostToDevice, st), "select mask upload");
-        HIP_TRY(hipMemsetAsync(P.ctl, 0, 40, st), "select mark");
-        HIP_TRY(launch_select_mark(P, e->n_cus, st), "select mark kernel launch");
-    }
+    P.pos = S.pos.as<uint64_t>(); P.rank = S.rank.as<uint64_t>();
+    if ((rc = doc_gather_select_mark(e, kSelect, P, d_text_blob, d_doc_off, n_docs, d_bitmap, n_cols, mode, d_also, h_want.data(), S.want, S.len, S.sel,
+                                     S.ctl, kSelCtlWords)))
+        return rc;
     {
         ProfScope ps(e, "select_scan");
         HIP_TRY(launch_exclusive_scan(P.len, n_docs, S.pos.as<uint64_t>(), S.partial.as<uint64_t>(), st), "select scan");
         HIP_TRY(launch_exclusive_scan(P.sel, n_docs, S.rank.as<uint64_t>(), S.partial.as<uint64_t>(), st), "select scan");
         HIP_TRY(launch_select_pack(P, st), "select scan");
     }
-    uint64_t h_ctl[5] = {0, 0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(h_ctl, P.ctl, 40, hipMemcpyDeviceToHost, st), "select totals");
-    HIP_TRY(hipStreamSynchronize(st), "select totals");
-    if (h_ctl[4]) return fail(e, GFT_E_INVALID, "gft_select_docs_device: document offsets descend, or a document of 4 GiB or more");
-    if (select_buffers_overlap(d_text_blob, h_ctl[2], h_ctl[3], d_doc_off, n_docs, d_bitmap, n_cols, d_also, d_out, cap_bytes, d_out_off,
-                               d_doc_idx, cap_docs))
-        return fail(e, GFT_E_INVALID, "gft_select_docs_device: an output overlaps an input");
-    P.total = h_ctl[0]; P.m = h_ctl[1];
+    uint64_t h_ctl[kSelCtlWords] = {0};
+    if ((rc = doc_gather_read(e, kSelect, P.ctl, h_ctl, kSelCtlWords))) return rc;
+    if (select_buffers_overlap(d_text_blob, h_ctl[kSelCtlLo], h_ctl[kSelCtlHi], d_doc_off, n_docs, d_bitmap, n_cols, d_also, d_out, cap_bytes,
+                               d_out_off, d_doc_idx, cap_docs))
+        return doc_gather_overlap(e, kSelect);
+    P.total = h_ctl[kSelCtlTotal]; P.m = h_ctl[kSelCtlM];
     if (n_selected) *n_selected = P.m;
     if (total_bytes) *total_bytes = P.total;
-    if ((rc = room(e, S.c_off, (P.m + 1) * 8, kSelectRoom)) || (rc = room(e, S.c_src, P.m * 8, kSelectRoom))) return rc;
+    if ((rc = room(e, S.c_off, (P.m + 1) * 8, kSelect.room)) || (rc = room(e, S.c_src, P.m * 8, kSelect.room))) return rc;
     P.c_off = S.c_off.as<uint64_t>(); P.c_src = S.c_src.as<uint64_t>();
-    P.out = d_out; P.out_off = d_out_off; P.doc_idx = d_doc_idx; P.cap_docs = cap_docs;
-    P.G = sel_geom(P.total, cap_bytes, d_out);
+    P.out_off = d_out_off; P.doc_idx = d_doc_idx; P.cap_docs = cap_docs;
     {
         ProfScope ps(e, "select_place");
         HIP_TRY(launch_select_place(P, st), "select place kernel launch");
     }
-    if (P.G.end) {
-        ProfScope ps(e, "select_copy");
-        HIP_TRY(launch_select_copy(P, st), "select copy kernel launch");
-    }
-    HIP_TRY(hipStreamSynchronize(st), "select copy");
-    return GFT_OK;
+    return doc_gather_copy(e, kSelect, d_text_blob, P.c_off, P.c_src, P.m, P.total, d_out, cap_bytes);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_select_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,

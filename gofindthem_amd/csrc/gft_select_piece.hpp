@@ -46,6 +46,39 @@ GFT_HD inline uint32_t sel_row_decide(SelRow r, uint32_t mode) {
 // the document [a, b) of the offsets: 0 when they descend or it has 4 GiB or more
 GFT_HD inline uint32_t sel_doc_ok(uint64_t a, uint64_t b) { return (b >= a && b - a < (1ull << 32)) ? 1u : 0u; }
 
+// ---- the control block the host reads back: the select's words, then the two the context call adds -------------------------
+// (bytes, documents kept, doc_off[0], doc_off[n_docs]; flag: offsets descend, or a document of 4 GiB or more)
+enum : uint32_t {
+    kSelCtlTotal = 0, kSelCtlM = 1, kSelCtlLo = 2, kSelCtlHi = 3, kSelCtlFlag = 4, kSelCtlWords = 5,
+    kCtxCtlHits = 5, kCtxCtlGroups = 6, kCtxCtlWords = 7
+};
+
+// ---- the place pass: P is a parameter block with doc_off, pos, rank, c_off, c_src, out_off, doc_idx, cap_docs ----------------
+// what the host walks place through
+struct SelPlace {
+    const uint64_t *doc_off, *pos, *rank;
+    uint64_t *c_off, *c_src, *out_off, *doc_idx;
+    uint64_t cap_docs;
+};
+// document d, if it is kept: the compact arrays (complete), the caller's out_off / doc_idx (capped); r: its rank
+template <class P>
+GFT_HD inline bool sel_place_doc(const P& p, uint64_t d, uint64_t& r) {
+    r = p.rank[d];
+    if (p.rank[d + 1] == r) return false;
+    const uint64_t at = p.pos[d];
+    p.c_off[r] = at;
+    p.c_src[r] = p.doc_off[d];
+    if (p.out_off && r <= p.cap_docs) p.out_off[r] = at;
+    if (r < p.cap_docs) p.doc_idx[r] = d;
+    return true;
+}
+// the closing entries behind the m kept documents
+template <class P>
+GFT_HD inline void sel_place_close(const P& p, uint64_t m, uint64_t total) {
+    p.c_off[m] = total;
+    if (p.out_off && m <= p.cap_docs) p.out_off[m] = total;
+}
+
 // ---- the copy pass ---------------------------------------------------------------------------------------------------------
 struct SelGeom {
     uint64_t end;          // bytes to write: min(total, cap_bytes)

@@ -25,17 +25,11 @@
 
 #include "gft_kernels.hpp"
 #include "gft_spans.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
-
-__device__ __forceinline__ uint64_t shuffle64(uint64_t v, int lane) {
-    return (uint64_t)(uint32_t)__shfl((int)(v >> 32), lane, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
-}
-__device__ __forceinline__ uint64_t shuffle_up64(uint64_t v, unsigned by) {
-    return (uint64_t)(uint32_t)__shfl_up((int)(v >> 32), by, 64) << 32 | (uint32_t)__shfl_up((int)(uint32_t)v, by, 64);
-}
 
 __global__ void __launch_bounds__(kSpanMarkBlock) k_span_mark(const SpanParams P) {
     const uint64_t n_threads = (uint64_t)gridDim.x * kSpanMarkBlock;
@@ -86,7 +80,7 @@ __global__ void __launch_bounds__(kSpanMarkBlock) k_redact_fill(const RedactPara
     uint64_t incl = len;
 #pragma unroll
     for (unsigned by = 1; by < 64; by <<= 1) {
-        const uint64_t up = shuffle_up64(incl, by);
+        const uint64_t up = up64(incl, by);
         if (lane >= by) incl += up;
     }
     const LaneExcl excl{incl - len};

@@ -18,6 +18,7 @@
 
 #include "gft_kernels.hpp"
 #include "gft_split.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -35,14 +36,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
     return v;
 }
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
-__device__ __forceinline__ uint64_t lane_value64(uint64_t v, int lane) {
-    return (uint64_t)lane_value((uint32_t)(v >> 32), lane) << 32 | lane_value((uint32_t)v, lane);
-}
-__device__ __forceinline__ uint64_t shuffle64(uint64_t v, int lane) {
-    return (uint64_t)(uint32_t)__shfl((int)(v >> 32), lane, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
-}
-
 // the wave's tile: its four trips' pieces in registers (w[t]: the piece at o[t], n[t] of its bytes in the blob)
 struct TilePieces {
     uint32_t w[kSplitTrips][4];

@@ -1,0 +1,41 @@
+// gft_wave_dev.hpp -- the lane kit of the wave64 kernels: 64-bit values moved between the lanes of a wave, who a lane is in a
+// grid of waves, and the grid such a kernel gets.  For .hip files.  (The scan and solve kernels keep their own.)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+namespace gft {
+
+// the value of the first active lane / of a lane that is the same in every lane: scalar values
+__device__ __forceinline__ uint32_t first_lane32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t first_lane64(uint64_t v) { return (uint64_t)first_lane32((uint32_t)(v >> 32)) << 32 | first_lane32((uint32_t)v); }
+__device__ __forceinline__ uint32_t lane_value(uint32_t v, int lane) { return (uint32_t)__builtin_amdgcn_readlane((int)v, lane); }
+__device__ __forceinline__ uint64_t lane_value64(uint64_t v, int lane) { return (uint64_t)lane_value((uint32_t)(v >> 32), lane) << 32 | lane_value((uint32_t)v, lane); }
+// the value of a lane each lane names for itself, as two 32-bit halves
+__device__ __forceinline__ uint64_t shuffle64(uint64_t v, int lane) {
+    return (uint64_t)(uint32_t)__shfl((int)(v >> 32), lane, 64) << 32 | (uint32_t)__shfl((int)(uint32_t)v, lane, 64);
+}
+__device__ __forceinline__ uint64_t shuffle_xor64(uint64_t v, int s) {
+    return (uint64_t)(uint32_t)__shfl_xor((int)(v >> 32), s, 64) << 32 | (uint32_t)__shfl_xor((int)(uint32_t)v, s, 64);
+}
+// the value of the lane s below / above (the lane's own where there is none): HIP's 64-bit overloads
+__device__ __forceinline__ uint64_t up64(uint64_t v, uint32_t s) { return __shfl_up(v, s, 64); }
+__device__ __forceinline__ uint64_t down64(uint64_t v, uint32_t s) { return __shfl_down(v, s, 64); }
+
+// a lane's place in a one-dimensional grid of blocks of `block` threads (a multiple of 64)
+struct WaveId {
+    uint32_t lane;
+    uint64_t wave, n_waves;
+    __device__ __forceinline__ explicit WaveId(uint32_t block)
+        : lane(threadIdx.x & 63u), wave(((uint64_t)blockIdx.x * block + threadIdx.x) >> 6), n_waves(((uint64_t)gridDim.x * block) >> 6) {}
+};
+
+// blocks of `block` threads for `waves` waves that have work: 8 blocks per CU at most, one at least
+inline unsigned wave_grid(uint64_t waves, uint32_t block, unsigned n_cus) {
+    const uint64_t blocks = std::min<uint64_t>((waves + block / 64 - 1) / (block / 64), (uint64_t)std::max(n_cus, 1u) * 8);
+    return (unsigned)std::max<uint64_t>(blocks, 1);
+}
+
+}  // namespace gft

@@ -82,6 +82,22 @@ void select_copy_host(const uint8_t* text, const uint64_t* c_off, const uint64_t
     for (uint64_t tile = 0, n = sel_tiles(G); tile < n; tile++) copy_tile(text, c_off, c_src, m, G, tile, out);
 }
 
+bool select_mark_host(const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t W, const uint32_t* wm, uint32_t mode,
+                      const uint8_t* also, uint32_t* sel, uint32_t* len) {
+    bool good = true;
+    for (uint64_t d = 0; d < n_docs; d++) {
+        SelRow r{0, 1};
+        for (uint32_t j = 0; j < W; j++) r = sel_row_join(r, sel_row_word(bitmap[d * W + j], wm[j]));
+        uint32_t s = sel_row_decide(r, mode);
+        if (also && also[d]) s = 1;
+        const uint32_t ok = sel_doc_ok(doc_off[d], doc_off[d + 1]);
+        if (!ok) good = false;
+        if (len) len[d] = (s && ok) ? (uint32_t)(doc_off[d + 1] - doc_off[d]) : 0u;
+        sel[d] = s;
+    }
+    return good;
+}
+
 int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint32_t* bitmap, uint32_t n_cols,
                      const uint32_t* want, uint32_t mode, const uint8_t* also, uint8_t* out, uint64_t cap_bytes, uint64_t* out_off,
                      uint64_t* doc_idx, uint64_t cap_docs, uint64_t* n_selected, uint64_t* total_bytes) {
@@ -99,17 +115,7 @@ int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
     select_want_words(want, n_cols, wm.data());
     // k_select_mark
     std::vector<uint32_t> len(n_docs), sel(n_docs);
-    bool bad = false;
-    for (uint64_t d = 0; d < n_docs; d++) {
-        SelRow r{0, 1};
-        for (uint32_t j = 0; j < W; j++) r = sel_row_join(r, sel_row_word(bitmap[d * W + j], wm[j]));
-        uint32_t s = sel_row_decide(r, mode);
-        if (also && also[d]) s = 1;
-        const uint32_t ok = sel_doc_ok(doc_off[d], doc_off[d + 1]);
-        if (!ok) bad = true;
-        len[d] = (s && ok) ? (uint32_t)(doc_off[d + 1] - doc_off[d]) : 0u;
-        sel[d] = s;
-    }
+    const bool bad = !select_mark_host(doc_off, n_docs, bitmap, W, wm.data(), mode, also, sel.data(), len.data());
     if (bad) return GFT_E_INVALID;
     if (doc_off[n_docs] > doc_off[0] && !blob) return GFT_E_INVALID;
     if (select_buffers_overlap(blob, doc_off[0], doc_off[n_docs], doc_off, n_docs, bitmap, n_cols, also, out, cap_bytes, out_off, doc_idx,
@@ -123,16 +129,9 @@ int select_docs_host(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_do
     if (total_bytes) *total_bytes = total;
     // k_select_place
     std::vector<uint64_t> c_off(m + 1), c_src(m);
-    c_off[m] = total;
-    if (out_off && m <= cap_docs) out_off[m] = total;
-    for (uint64_t d = 0; d < n_docs; d++) {
-        const uint64_t r = rank[d];
-        if (rank[d + 1] == r) continue;
-        c_off[r] = pos[d];
-        c_src[r] = doc_off[d];
-        if (out_off && r <= cap_docs) out_off[r] = pos[d];
-        if (r < cap_docs) doc_idx[r] = d;
-    }
+    const SelPlace O{doc_off, pos.data(), rank.data(), c_off.data(), c_src.data(), out_off, doc_idx, cap_docs};
+    sel_place_close(O, m, total);
+    for (uint64_t d = 0, r; d < n_docs; d++) sel_place_doc(O, d, r);
     // k_select_copy
     const SelGeom G = sel_geom(total, cap_bytes, out);
     select_copy_host(blob, c_off.data(), c_src.data(), m, G, out);

@@ -89,29 +89,60 @@ def _want_words(want, n_cols):
     return w if w.size else np.zeros(1, dtype=np.uint32)
 
 
+def _docs_tensor_args(who, text, doc_off, bitmap, n_cols, also, *fence):
+    """the checks the *_docs_tensor functions make on their device tensors (fence: only for the call that has one) -> (n_docs, the
+    five arguments every such C call begins with, also's address or None)"""
+    n_docs = int(doc_off.numel()) - 1
+    W = (n_cols + 31) // 32
+    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
+            (((also, 1, "also"),) if also is not None else ()) + (((fence[0], 1, "fence"),) if fence and fence[0] is not None else ()):
+        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
+            raise ValueError("%s: %s must be a contiguous device tensor of %d-byte integers" % (who, what, size))
+    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs) or \
+            (fence and fence[0] is not None and fence[0].numel() != n_docs):
+        raise ValueError("%s: doc_off, bitmap%s do not describe the same batch" % (who, ", also and fence" if fence else " and also"))
+    return n_docs, (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols), \
+        also.data_ptr() if also is not None else None
+
+
+def _docs_out_tensors(text, nm, nb):
+    import torch                                                           # (the blob, out_off and doc_idx of exactly nm documents, nb bytes)
+    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
+    return buf, torch.empty(nm + 1, dtype=torch.int64, device=text.device), torch.empty(nm, dtype=torch.int64, device=text.device)
+
+
+def _docs_host_args(blob, doc_off, rows, n_cols, also):
+    """the arrays of a *_docs_host call as the library reads them -> (the arrays, to be kept alive; n_docs; the five arguments every
+    such C call begins with; also's address or None)"""
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+    n_docs = off.size - 1
+    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if (n_cols + 31) // 32 and n_docs > 0 else None
+    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    return (a, off, bm, al), n_docs, (a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols), _p(al)
+
+
+def _docs_host_outputs(cap_bytes, cap_docs, guard, out_shift):
+    """out (out_shift bytes into its allocation's 16-byte grid), out_off and doc_idx, filled with 0xA5 up to and including the guard"""
+    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
+    at = (-raw.ctypes.data) % 16 + out_shift
+    return raw[at:at + cap_bytes + guard], np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64), \
+        np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+
+
 def select_docs_tensor(call, text, doc_off, bitmap, n_cols, want, mode, also):
     """what Engine.select_docs_device and the finders' select calls share: `call(d_text, d_doc_off, n_docs, d_bitmap, n_cols, want,
     mode, d_also, d_out, cap_bytes, d_out_off, d_doc_idx, cap_docs, byref(m), byref(total))` is gft_select_docs_device on some
     handle and raises on an error.  Two calls: count only, then into tensors of exactly the sizes counted"""
     import torch
-    n_docs = int(doc_off.numel()) - 1
-    W = (n_cols + 31) // 32
-    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
-            (((also, 1, "also"),) if also is not None else ()):
-        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
-            raise ValueError("select_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
-    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs):
-        raise ValueError("select_docs_device: doc_off, bitmap and also do not describe the same batch")
+    n_docs, head, d_also = _docs_tensor_args("select_docs_device", text, doc_off, bitmap, n_cols, also)
     w = _want_words(want, n_cols)
-    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), _select_mode(mode),
-            also.data_ptr() if also is not None else None)
+    args = head + (_p(w), _select_mode(mode), d_also)
     m, total = C.c_uint64(0), C.c_uint64(0)
     torch.cuda.current_stream(text.device).synchronize()
     call(*args, None, 0, None, None, 0, C.byref(m), C.byref(total))
     nm, nb = int(m.value), int(total.value)
-    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
-    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
-    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    buf, out_off, doc_idx = _docs_out_tensors(text, nm, nb)
     torch.cuda.current_stream(text.device).synchronize()
     call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_idx.data_ptr() if nm else None, nm, C.byref(m), C.byref(total))
     return buf[:nb], out_off, doc_idx
@@ -124,29 +155,19 @@ def select_docs_host(blob, doc_off, rows, n_cols, want=None, mode="any", also=No
     entries behind the caps hold 0xA5 and must come back untouched.  out_shift: the output starts that many bytes into its
     allocation's 16-byte grid.  out_off, with its cap_docs + 1 entries, is always passed; count_only: no array at all"""
     L = _lib.load()
-    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
-    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-    n_docs = off.size - 1
-    W = (n_cols + 31) // 32
-    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
-    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    keep, n_docs, head, p_also = _docs_host_args(blob, doc_off, rows, n_cols, also)
     w = _want_words(want, n_cols)
     m, total = C.c_uint64(0), C.c_uint64(0)
 
     def call(out, cb, oo, di, cd):
-        rc = L.gft_debug_select_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), _select_mode(mode), _p(al),
-                                     out, cb, oo, di, cd, C.byref(m), C.byref(total))
+        rc = L.gft_debug_select_docs(*head, _p(w), _select_mode(mode), p_also, out, cb, oo, di, cd, C.byref(m), C.byref(total))
         if rc != 0:
             raise GftError(rc, "gft_debug_select_docs")
     if cap_bytes is None or cap_docs is None:
         call(None, 0, None, None, 0)
         cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
         cap_docs = int(m.value) if cap_docs is None else cap_docs
-    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
-    at = (-raw.ctypes.data) % 16 + out_shift
-    out = raw[at:at + cap_bytes + guard]
-    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
-    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    out, out_off, doc_idx = _docs_host_outputs(cap_bytes, cap_docs, guard, out_shift)
     if count_only:
         call(None, 0, None, None, 0)
     else:
@@ -170,28 +191,17 @@ def context_docs_tensor(call, text, doc_off, bitmap, n_cols, want, mode, also, b
     byref(hits), byref(groups), byref(total))` is gft_context_docs_device on some handle and raises on an error.  Two calls: count
     only, then into tensors of exactly the sizes counted"""
     import torch
-    n_docs = int(doc_off.numel()) - 1
-    W = (n_cols + 31) // 32
-    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
-            (((also, 1, "also"),) if also is not None else ()) + (((fence, 1, "fence"),) if fence is not None else ()):
-        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
-            raise ValueError("context_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
-    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs) or \
-            (fence is not None and fence.numel() != n_docs):
-        raise ValueError("context_docs_device: doc_off, bitmap, also and fence do not describe the same batch")
+    n_docs, head, d_also = _docs_tensor_args("context_docs_device", text, doc_off, bitmap, n_cols, also, fence)
     if not (0 <= int(before) <= CONTEXT_MAX and 0 <= int(after) <= CONTEXT_MAX):
         raise ValueError("context_docs_device: before and after are counts of documents, 0 .. 2^64 - 1")
     w = _want_words(want, n_cols)
-    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), _select_mode(mode),
-            also.data_ptr() if also is not None else None, int(before), int(after), fence.data_ptr() if fence is not None else None)
+    args = head + (_p(w), _select_mode(mode), d_also, int(before), int(after), fence.data_ptr() if fence is not None else None)
     m, hits, groups, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     counts = (C.byref(m), C.byref(hits), C.byref(groups), C.byref(total))
     torch.cuda.current_stream(text.device).synchronize()
     call(*args, None, 0, None, None, None, 0, None, 0, *counts)
     nm, ng, nb = int(m.value), int(groups.value), int(total.value)
-    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
-    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
-    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    buf, out_off, doc_idx = _docs_out_tensors(text, nm, nb)
     kind = torch.empty(nm, dtype=torch.uint8, device=text.device)
     group_off = torch.empty(ng + 1, dtype=torch.int64, device=text.device)
     torch.cuda.current_stream(text.device).synchronize()
@@ -208,20 +218,14 @@ def context_docs_host(blob, doc_off, rows, n_cols, want=None, mode="any", also=N
     back untouched.  out_shift: the output starts that many bytes into its allocation's 16-byte grid.  The two offset arrays are
     always passed; count_only: no array at all"""
     L = _lib.load()
-    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
-    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-    n_docs = off.size - 1
-    W = (n_cols + 31) // 32
-    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
-    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    keep, n_docs, head, p_also = _docs_host_args(blob, doc_off, rows, n_cols, also)
     fe = np.ascontiguousarray(fence, dtype=np.uint8) if fence is not None else None
     w = _want_words(want, n_cols)
     m, hits, groups, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
 
     def call(out, cb, oo, di, ki, cd, go, cg):
-        rc = L.gft_debug_context_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), _select_mode(mode), _p(al),
-                                      int(before), int(after), _p(fe), out, cb, oo, di, ki, cd, go, cg, C.byref(m), C.byref(hits),
-                                      C.byref(groups), C.byref(total))
+        rc = L.gft_debug_context_docs(*head, _p(w), _select_mode(mode), p_also, int(before), int(after), _p(fe), out, cb, oo, di, ki, cd, go, cg,
+                                      C.byref(m), C.byref(hits), C.byref(groups), C.byref(total))
         if rc != 0:
             raise GftError(rc, "gft_debug_context_docs")
     if cap_bytes is None or cap_docs is None or cap_groups is None:
@@ -229,11 +233,7 @@ def context_docs_host(blob, doc_off, rows, n_cols, want=None, mode="any", also=N
         cap_bytes = int(total.value) if cap_bytes is None else cap_bytes
         cap_docs = int(m.value) if cap_docs is None else cap_docs
         cap_groups = int(groups.value) if cap_groups is None else cap_groups
-    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
-    at = (-raw.ctypes.data) % 16 + out_shift
-    out = raw[at:at + cap_bytes + guard]
-    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
-    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    out, out_off, doc_idx = _docs_host_outputs(cap_bytes, cap_docs, guard, out_shift)
     kind = np.full(cap_docs + guard, 0xA5, dtype=np.uint8)
     group_off = np.full(cap_groups + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
     if count_only:
@@ -279,27 +279,17 @@ def route_docs_tensor(call, text, doc_off, bitmap, n_cols, masks, mode, rest, al
     gft_route_docs_device on some handle and raises on an error.  Two calls: count only, then into tensors of exactly the sizes
     counted.  count_only: the first call alone -> (bucket_doc, bucket_byte)"""
     import torch
-    n_docs = int(doc_off.numel()) - 1
-    W = (n_cols + 31) // 32
-    for t, size, what in ((text, 1, "text"), (doc_off, 8, "doc_off")) + (((bitmap, 4, "bitmap"),) if W and n_docs > 0 else ()) + \
-            (((also, 1, "also"),) if also is not None else ()):
-        if not t.is_cuda or not t.is_contiguous() or t.element_size() != size:
-            raise ValueError("route_docs_device: %s must be a contiguous device tensor of %d-byte integers" % (what, size))
-    if n_docs < 0 or (W and n_docs > 0 and bitmap.numel() != n_docs * W) or (also is not None and also.numel() != n_docs):
-        raise ValueError("route_docs_device: doc_off, bitmap and also do not describe the same batch")
+    n_docs, head, d_also = _docs_tensor_args("route_docs_device", text, doc_off, bitmap, n_cols, also)
     K, w = _mask_rows(masks, n_cols)
     B = K + (1 if rest else 0)
-    args = (text.data_ptr(), doc_off.data_ptr(), n_docs, bitmap.data_ptr() if W and n_docs > 0 else None, n_cols, _p(w), K, _route_mode(mode),
-            ROUTE_REST if rest else 0, also.data_ptr() if also is not None else None)
+    args = head + (_p(w), K, _route_mode(mode), ROUTE_REST if rest else 0, d_also)
     bucket_doc, bucket_byte = np.zeros(B + 1, dtype=np.uint64), np.zeros(B + 1, dtype=np.uint64)
     torch.cuda.current_stream(text.device).synchronize()
     call(*args, None, 0, None, None, 0, _p(bucket_doc), _p(bucket_byte))
     if count_only:
         return bucket_doc, bucket_byte
     nm, nb = int(bucket_doc[B]), int(bucket_byte[B])
-    buf = torch.zeros(nb + 64, dtype=torch.uint8, device=text.device)      # (64 bytes of slack: the result is a blob for the next call)
-    out_off = torch.empty(nm + 1, dtype=torch.int64, device=text.device)
-    doc_idx = torch.empty(nm, dtype=torch.int64, device=text.device)
+    buf, out_off, doc_idx = _docs_out_tensors(text, nm, nb)
     torch.cuda.current_stream(text.device).synchronize()
     call(*args, buf.data_ptr(), nb, out_off.data_ptr(), doc_idx.data_ptr() if nm else None, nm, _p(bucket_doc), _p(bucket_byte))
     return buf[:nb], out_off, doc_idx, bucket_doc, bucket_byte
@@ -312,30 +302,21 @@ def route_docs_host(blob, doc_off, rows, n_cols, masks, mode="every", rest=False
     exactly what the result needs; the guard entries behind the caps hold 0xA5 and must come back untouched.  out_shift: the output
     starts that many bytes into its allocation's 16-byte grid.  count_only: no array at all"""
     L = _lib.load()
-    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
-    off = np.ascontiguousarray(doc_off, dtype=np.uint64)
-    n_docs = off.size - 1
-    W = (n_cols + 31) // 32
-    bm = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1) if W and n_docs > 0 else None
-    al = np.ascontiguousarray(also, dtype=np.uint8) if also is not None else None
+    keep, n_docs, head, p_also = _docs_host_args(blob, doc_off, rows, n_cols, also)
     K, w = _mask_rows(masks, n_cols)
     B = K + (1 if rest else 0)
     bucket_doc, bucket_byte = np.zeros(B + 1, dtype=np.uint64), np.zeros(B + 1, dtype=np.uint64)
 
     def call(out, cb, oo, di, cd):
-        rc = L.gft_debug_route_docs(a.ctypes.data if a.size else None, off.ctypes.data, n_docs, _p(bm), n_cols, _p(w), K, _route_mode(mode),
-                                    ROUTE_REST if rest else 0, _p(al), out, cb, oo, di, cd, _p(bucket_doc), _p(bucket_byte))
+        rc = L.gft_debug_route_docs(*head, _p(w), K, _route_mode(mode), ROUTE_REST if rest else 0, p_also, out, cb, oo, di, cd, _p(bucket_doc),
+                                    _p(bucket_byte))
         if rc != 0:
             raise GftError(rc, "gft_debug_route_docs")
     if cap_bytes is None or cap_docs is None or count_only:
         call(None, 0, None, None, 0)
         cap_bytes = int(bucket_byte[B]) if cap_bytes is None else cap_bytes
         cap_docs = int(bucket_doc[B]) if cap_docs is None else cap_docs
-    raw = np.full(cap_bytes + guard + 32, 0xA5, dtype=np.uint8)
-    at = (-raw.ctypes.data) % 16 + out_shift
-    out = raw[at:at + cap_bytes + guard]
-    out_off = np.full(cap_docs + 1 + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
-    doc_idx = np.full(cap_docs + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+    out, out_off, doc_idx = _docs_host_outputs(cap_bytes, cap_docs, guard, out_shift)
     if not count_only:
         call(out.ctypes.data if cap_bytes or guard else None, cap_bytes, out_off.ctypes.data, doc_idx.ctypes.data if cap_docs or guard else None, cap_docs)
     return bucket_doc, bucket_byte, out, out_off, doc_idx

@@ -219,6 +219,9 @@ def test_refusals_leave_the_handle_usable(eng):
     assert "null argument" in L.gft_last_error(eng._h).decode()
     assert call(mode=3) == E                                                                 # unknown mode
     assert "gft_context_docs_device: unknown mode" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_context_docs_device: unknown mode"
+    assert call(cd=1 << 61) == E                                                 # a size beyond the address space
+    assert L.gft_last_error(eng._h).decode() == "gft_context_docs_device: a size beyond the address space"
     assert call(o=None) == E and call(oop=None) == E and call(dip=None) == E and call(kip=None) == E and call(gop=None) == E      # a cap without its array
     assert call(o=d.text.data_ptr() + int(c.doc_off[0]), cb=3) == E                          # the output over the text ...
     assert call(o=d.off.data_ptr(), cb=3) == E                                               # ... the offsets ...
@@ -228,6 +231,7 @@ def test_refusals_leave_the_handle_usable(eng):
     assert call(oop=d.rows.data_ptr()) == E and call(dip=d.off.data_ptr()) == E and call(kip=d.fence.data_ptr()) == E
     assert call(gop=d.off.data_ptr()) == E and call(gop=oo.data_ptr()) == E and call(kip=out.data_ptr()) == E       # two outputs
     assert "overlaps" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_context_docs_device: an output overlaps an input"
     down = d.off.clone()
     down[3], down[4] = d.off[4].item(), d.off[3].item()
     if down[3] == down[4]:
@@ -235,10 +239,12 @@ def test_refusals_leave_the_handle_usable(eng):
     torch.cuda.synchronize()
     assert call(doc_off=down.data_ptr()) == E                                                # offsets that descend
     assert "gft_context_docs_device: document offsets descend" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_context_docs_device: document offsets descend, or a document of 4 GiB or more"
     huge = d.off.clone()
     huge[d.n] += 1 << 32
     torch.cuda.synchronize()
     assert call(doc_off=huge.data_ptr(), o=None, cb=0, oop=None, dip=None, kip=None, cd=0, gop=None, cg=0) == E      # a document of 4 GiB or more
+    assert L.gft_last_error(eng._h).decode() == "gft_context_docs_device: document offsets descend, or a document of 4 GiB or more"
     with pytest.raises(ValueError):
         eng.context_docs_device(d.text, d.off, d.rows, c.n_cols, np.zeros(W + 1, np.uint32))
     with pytest.raises(ValueError):

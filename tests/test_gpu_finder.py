@@ -720,3 +720,47 @@ def test_cu_margin_leaves_results_alone():
     assert L.gft_set_cu_margin(eh, 8) != 0
     f.ProcessDeviceEnd()
     assert L.gft_set_cu_margin(eh, 8) == 0
+
+
+# ---- what every resident-batch method refuses before anything else -------------------------------------------------
+RESIDENT_CALLS = ("gft_finder_process_device", "gft_finder_split_lines_device", "gft_finder_select_docs_device", "gft_finder_context_docs_device",
+                  "gft_finder_route_docs_device", "gft_finder_hit_spans_device", "gft_finder_hit_spans_source_device", "gft_finder_excerpts_device",
+                  "gft_finder_excerpts_snap_device", "gft_finder_mark_device", "gft_finder_replace_device", "gft_finder_term_stats_device")
+
+
+def _no_arguments(fn):
+    """a call's arguments behind the handle: no array, no size, a place for every count (nothing is read before the refusals)"""
+    import ctypes as C
+    return [C.pointer(t._type_()) if hasattr(t, "contents") else None if t is C.c_void_p else 0 for t in fn.argtypes[1:]]
+
+
+def test_resident_methods_refuse_the_wrong_finder_and_batches_in_flight():
+    import torch
+    L = _lib.load()
+    wrong = "device-resident processing needs the GPU substring engine and no regex terms"
+    rgx = Finder(GpuEngine(), PyRegexpEngine(), False)
+    rgx.AddExpressions(['"ab"', 'r"c+d"'])
+    foreign = Finder(EmptyEngine(), EmptyRgxEngine(), False)
+    foreign.AddExpressions(['"ab"'])
+    for f in (rgx, foreign):
+        for name in RESIDENT_CALLS:
+            fn = getattr(L, name)
+            assert fn(f._h, *_no_arguments(fn)) == _lib.GFT_E_UNSUPPORTED, name
+            assert L.gft_finder_last_error(f._h).decode() == wrong, name
+        f.close()
+    f = Finder(GpuEngine(), EmptyRgxEngine(), False)
+    f.AddExpressions(['"ab"', '"cd" and not "ab"'])
+    blob = b"ab\ncd\nxx\n"
+    buf = torch.zeros(len(blob) + 64, dtype=torch.uint8, device="cuda")
+    buf[:len(blob)] = torch.frombuffer(bytearray(blob), dtype=torch.uint8).cuda()
+    off = torch.tensor([0, 3, 6, 9], dtype=torch.int64, device="cuda")
+    bm = torch.zeros((3, 1), dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    f.ProcessDeviceBegin(buf.data_ptr(), off.data_ptr(), 3, bm.data_ptr())
+    for name in RESIDENT_CALLS:
+        fn = getattr(L, name)
+        assert fn(f._h, *_no_arguments(fn)) == _lib.GFT_E_INVALID, name
+        assert L.gft_finder_last_error(f._h).decode() == "batches of ProcessDeviceBegin are in flight: ProcessDeviceEnd first", name
+    f.ProcessDeviceEnd()
+    assert bm.cpu().view(-1).tolist() == [1, 2, 0]
+    f.close()

@@ -221,9 +221,13 @@ def test_refusals_leave_the_handle_usable(eng):
                                        hd.ctypes.data, hb.ctypes.data)
     assert call() == 0 and hd[:K + 2].tolist() == bd
     assert call(mode=2) == E                                                     # unknown mode
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: unknown mode"
+    assert call(cd=1 << 61) == E                                                 # a size beyond the address space
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: a size beyond the address space"
     assert call(flags=2, also=None) == E and call(flags=3) == E                  # unknown flag bits
     assert call(flags=0) == E                                                    # also without rest
     assert "GFT_ROUTE_REST" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: d_also needs GFT_ROUTE_REST"
     assert call(flags=0, also=None) == 0
     assert call(masks=many.ctypes.data, k=65, flags=0, also=None) == U           # 65 buckets
     assert "64" in L.gft_last_error(eng._h).decode()
@@ -237,6 +241,7 @@ def test_refusals_leave_the_handle_usable(eng):
     assert call(o=d.also.data_ptr() + d.n - 1, cb=1) == E                        # ... the last byte of `also`
     assert call(oop=d.rows.data_ptr()) == E and call(dip=d.off.data_ptr()) == E
     assert "overlaps" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: an output overlaps an input"
     down = d.off.clone()
     down[3], down[4] = d.off[4].item(), d.off[3].item()
     if down[3] == down[4]:
@@ -244,10 +249,12 @@ def test_refusals_leave_the_handle_usable(eng):
     torch.cuda.synchronize()
     assert call(doc_off=down.data_ptr()) == E                                    # offsets that descend
     assert "descend" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: document offsets descend, or a document of 4 GiB or more"
     huge = d.off.clone()
     huge[d.n] += 1 << 32
     torch.cuda.synchronize()
     assert call(doc_off=huge.data_ptr(), o=None, cb=0, oop=None, dip=None, cd=0) == E      # a document of 4 GiB or more
+    assert L.gft_last_error(eng._h).decode() == "gft_route_docs_device: document offsets descend, or a document of 4 GiB or more"
     with pytest.raises(ValueError):
         eng.route_docs_device(d.text, d.off, d.rows, c.n_cols, np.zeros((2, W + 1), np.uint32))
     with pytest.raises(GftError) as ei:

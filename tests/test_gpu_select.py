@@ -183,6 +183,9 @@ def test_refusals_leave_the_handle_usable(eng):
                                         dip, cd, C.byref(m), C.byref(t))
     assert call() == 0
     assert call(mode=3) == E                                                     # unknown mode
+    assert L.gft_last_error(eng._h).decode() == "gft_select_docs_device: unknown mode"
+    assert call(cd=1 << 61) == E                                                 # a size beyond the address space
+    assert L.gft_last_error(eng._h).decode() == "gft_select_docs_device: a size beyond the address space"
     assert call(o=None) == E and call(oop=None) == E and call(dip=None) == E     # a cap without its array
     assert call(o=d.text.data_ptr() + int(c.doc_off[0]), cb=3) == E              # the output over the text ...
     assert call(o=d.off.data_ptr(), cb=3) == E                                   # ... the offsets ...
@@ -190,6 +193,7 @@ def test_refusals_leave_the_handle_usable(eng):
     assert call(o=d.also.data_ptr() + d.n - 1, cb=1) == E                        # ... the last byte of `also`
     assert call(oop=d.rows.data_ptr()) == E and call(dip=d.off.data_ptr()) == E
     assert "overlaps" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_select_docs_device: an output overlaps an input"
     down = d.off.clone()
     down[3], down[4] = d.off[4].item(), d.off[3].item()
     if down[3] == down[4]:
@@ -197,10 +201,12 @@ def test_refusals_leave_the_handle_usable(eng):
     torch.cuda.synchronize()
     assert call(doc_off=down.data_ptr()) == E                                    # offsets that descend
     assert "descend" in L.gft_last_error(eng._h).decode()
+    assert L.gft_last_error(eng._h).decode() == "gft_select_docs_device: document offsets descend, or a document of 4 GiB or more"
     huge = d.off.clone()
     huge[d.n] += 1 << 32
     torch.cuda.synchronize()
     assert call(doc_off=huge.data_ptr(), o=None, cb=0, oop=None, dip=None, cd=0) == E      # a document of 4 GiB or more
+    assert L.gft_last_error(eng._h).decode() == "gft_select_docs_device: document offsets descend, or a document of 4 GiB or more"
     with pytest.raises(ValueError):
         eng.select_docs_device(d.text, d.off, d.rows, c.n_cols, np.zeros(W + 1, np.uint32))
     got = eng.select_docs_device(d.text, d.off, d.rows, c.n_cols, c.want, c.mode, d.also)
