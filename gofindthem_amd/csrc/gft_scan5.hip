@@ -331,24 +331,31 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
     const uint32_t round_units = gridDim.x * wg_waves, wg_first = blockIdx.x * wg_waves;
     auto unit_of = [&](uint32_t item) -> uint64_t { return (uint64_t)(item / wg_waves) * round_units + (wg_first + item % wg_waves); };
     uint64_t u = unit_of(wave), nu = 0;                           // wave-uniform
-    Unit un_n{0, 0, 0};
-    uint64_t abs_n = 0, end_n = 0;                               // the next unit's document: blob offsets of its first byte and of the byte behind it
-    if (u < P.n_units) { un_n = P.units[u]; abs_n = P.doc_off[un_n.doc]; end_n = P.doc_off[un_n.doc + 1]; }
+    // The NEXT unit's record and its document's blob offsets (first byte, the byte behind the last) travel over the back edge
+    // in the registers their loads fill.  The loads are unconditional, at an index clamped to the last unit (unit 0 exists
+    // whenever the kernel runs), and whether there is a next unit is asked where the values are used, by the loop's condition:
+    // under `if (more units)` the compiler copies the loaded registers at the join and waits for them on the spot -- vmcnt(0),
+    // which also drains the flush's stores of the unit before -- in front of the unit's own text ("The unit
+    // boundary").  units_arrived() marks where the three are complete, so that no later wait is booked to them
+    Unit un_n;
+    uint64_t abs_n, end_n;
+    auto request_unit = [&](uint64_t k) {
+        un_n = P.units[k < P.n_units ? k : P.n_units - 1];
+        abs_n = P.doc_off[un_n.doc]; end_n = P.doc_off[un_n.doc + 1];
+    };
+    auto units_arrived = [&]() { asm volatile("" : : "v"(un_n.doc), "v"(un_n.lo), "v"(un_n.hi), "v"(abs_n), "v"(end_n)); };
+    request_unit(u);
+    units_arrived();
+    // (the text pointer is read where the unit before ends, in front of its flush: the text request at a unit's top then
+    // stands behind no scalar load either)
+    const uint8_t* text_n = KARG(text);
     for (; u < P.n_units; u = nu) {
         const Unit un{(uint32_t)__builtin_amdgcn_readfirstlane(un_n.doc), (uint32_t)__builtin_amdgcn_readfirstlane(un_n.lo),
                       (uint32_t)__builtin_amdgcn_readfirstlane(un_n.hi)};
         const uint64_t doc_abs = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(abs_n >> 32)) << 32 |
                                  (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)abs_n);
         const uint64_t end_v = end_n;                             // (the document's end is read by the fold-safety check only: kept in its vector register)
-        {
-            uint32_t item = 0;
-            if (lane == 0) item = __hip_atomic_fetch_add(wg_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            nu = unit_of((uint32_t)__builtin_amdgcn_readfirstlane(item));
-        }
-        mark(7);
-        const bool more_units = nu < P.n_units;
-        if (more_units) un_n = P.units[nu];
-        const Ctx c{P, cls, nullptr, P.short3_bytes ? short3 : nullptr, fpt, lrec, P.text + doc_abs, doc_abs, kp2,
+        const Ctx c{P, cls, nullptr, P.short3_bytes ? short3 : nullptr, fpt, lrec, text_n + doc_abs, doc_abs, kp2,
                     doc_abs < 7, doc_abs < 23, un.lo, un.hi, doc_abs + un.hi + 4 > KARG(text_bytes), DBG ? P.dbg : 0u};
         const uint32_t nborder = un.lo < kScan2MaxOff ? un.lo : kScan2MaxOff;
         const uint32_t ubase = un.lo - kScan2MaxOff;               // candidate lists hold p - ubase (may wrap; p never does)
@@ -359,19 +366,33 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
         const uint32_t nvalid = my_lo < un.hi ? my_hi - my_lo : 0;
         Ctx5 o{fifo, P.s5_fifo_cap, 0, 0, false, false, 0, POS ? P.s5_term_bits : 0u, POS ? un.lo - P.s5_pos_bias : 0u};
 
+        // the unit's own first bytes are requested before anything else: each lane's history word and first 16-byte piece (an
+        // empty unit has no lane with nvalid != 0)
+        const uint8_t* src = c.dbase + my_lo;
+        uint32_t hist = 0;
+        U128u nxt{0, 0, 0, 0};
+        if (nvalid) {
+            if (doc_abs + my_lo >= 4) hist = load_u32_unaligned(src - 4);
+            else for (uint32_t i = 1; i <= 3 && i <= doc_abs + my_lo; i++) hist |= (uint32_t)src[-(int)i] << (32 - 8 * i);
+            nxt = *reinterpret_cast<const U128u*>(src);
+        }
+        // ... then the wave's next work item and its record, behind the text in the wave's in-order memory path: the record
+        // arrives under the wait for the piece, its document's offsets under the filter
+        {
+            uint32_t item = 0;
+            if (lane == 0) item = __hip_atomic_fetch_add(wg_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            nu = unit_of((uint32_t)__builtin_amdgcn_readfirstlane(item));
+        }
+        mark(7);
+        request_unit(nu);
+
         // ---- FILTER -----------------------------------------------------------------------------------------------------
         uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
         if (own) {
             // the groups of the three bytes in front of the lane's range (the pad group in front of the document)
             uint32_t h1 = P.s5_pad_g, h2 = P.s5_pad_g, h3 = P.s5_pad_g, pq = 0;      // g[j-1], g[j-2], g[j-3]; pq = h2 * G + h1
             (void)h2;
-            const uint8_t* src = c.dbase + my_lo;
-            U128u nxt{0, 0, 0, 0};
             if (nvalid) {
-                uint32_t hist = 0;
-                if (doc_abs + my_lo >= 4) hist = load_u32_unaligned(src - 4);
-                else for (uint32_t i = 1; i <= 3 && i <= doc_abs + my_lo; i++) hist |= (uint32_t)src[-(int)i] << (32 - 8 * i);
-                nxt = *reinterpret_cast<const U128u*>(src);
                 if (my_lo >= 1) h1 = lgrp[hist >> 24];
                 if (my_lo >= 2) h2 = lgrp[(hist >> 16) & 0xFF];
                 if (my_lo >= 3) h3 = lgrp[(hist >> 8) & 0xFF];
@@ -466,7 +487,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
             m3 = nvalid >= 128 ? m3 : (nvalid > 96 ? m3 & ((1u << (nvalid - 96)) - 1) : 0);
         }
         mark(1);
-        if (more_units) { abs_n = P.doc_off[un_n.doc]; end_n = P.doc_off[un_n.doc + 1]; }
+        units_arrived();
 
         if (DBG && P.dbg) {
             if (P.dbg & 2) {
@@ -669,6 +690,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                 if (slab_next + nh > KARG(pool_cap)) break;        // (beyond the pool: nothing is written, the host runs the batch again)
             }
         }
+        text_n = KARG(text);                                        // (for the next unit's top: back under the flush)
         if (ftotal) {
             const uint32_t nh = o.nf;
             if (!o.direct && nh > slab_left) {

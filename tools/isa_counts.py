@@ -7,9 +7,15 @@
 Per kernel: the registers and spills of its .amdhsa / metadata lines, its size in bytes, and instruction counts by kind in the whole
 kernel and inside the unit loop.  Kinds: VALU = v_* without the two lane-spill moves and without v_readfirstlane, SALU = s_* without
 s_load* / s_buffer_load* (scalar memory), s_waitcnt, s_nop, s_endpgm, s_barrier and the branches (s_branch, s_cbranch_*, counted as
-`branch`); LDS = ds_*; VMEM = global_* / flat_* / buffer_* / scratch_*.  The unit loop is the widest backward branch of the kernel
-(the `for (; u < P.n_units; u = nu)` loop encloses everything but table staging and the epilogue); `once` = the instructions of the
-loop's blocks that are NOT inside any inner loop, i.e. that run once per unit or less.
+`branch`); LDS = ds_*; VMEM = global_* / flat_* / buffer_* / scratch_*.  The unit loop is the largest top-level loop of the
+kernel by the compiler's loop comments (the `for (; u < P.n_units; u = nu)` loop encloses everything but table staging and the
+epilogue); `once` = the instructions of the loop's blocks that are NOT inside any inner loop, i.e. that run once per unit or less.  `vmcnt(0)` = the s_waitcnt instructions
+that drain the vector-memory counter (loads AND stores), counted in the same three scopes.
+
+    python3 tools/isa_counts.py scan5.s [kernel-name-substring] --once-vmem
+
+lists, per kernel and in layout order, the vector-memory instructions and the vmcnt waits of the `once` part: what a unit issues
+and waits for between the flush of the unit before and its own filter ("The unit boundary").
 """
 import re
 import subprocess
@@ -82,46 +88,59 @@ def kernels(path):
 
 
 def analyse(body):
-    ins = []                                   # (mnemonic, branch target or None)
-    labels = {}
-    for t in body:
-        t = t.split(";")[0].strip()
-        if not t or t.startswith("."):
-            m = re.match(r"^(\.LBB\w+):", t)
-            if m:
-                labels[m.group(1)] = len(ins)
-            continue
-        m = re.match(r"^(\.LBB\w+):", t)
+    """The loops are the compiler's own: its comments name every block's innermost loop ("in Loop: Header=BB10_59 Depth=1") and
+    every header ("Loop Header: Depth=2").  The unit loop is the top-level loop with the most instructions; `once` = its blocks
+    of depth 1.  (Backward branches do not find it: the layout puts blocks of the epilogue in front of the loop.)"""
+    ins = []                                   # (mnemonic, the instruction's text, top-level loop header or None, loop depth)
+    top, depth = None, 0
+    for raw in body:
+        code, _, comment = raw.partition(";")
+        code = code.strip()
+        label = re.match(r"^(\.LBB\w+):", code)
+        block = label or re.match(r"^\s*%bb\.\d+:", comment)
+        m = re.search(r"in Loop: Header=(BB\w+) Depth=(\d+)", comment)
         if m:
-            labels[m.group(1)] = len(ins)
+            depth = int(m.group(2))
+            if depth == 1:
+                top = m.group(1)
+        elif re.search(r"Loop Header: Depth=(\d+)", comment):
+            depth = int(re.search(r"Loop Header: Depth=(\d+)", comment).group(1))
+            if depth == 1 and label:
+                top = label.group(1)[2:]
+        elif block and "Parent Loop" not in comment:
+            top, depth = None, 0               # (a block outside every loop)
+        if label or not code or code.startswith("."):
             continue
-        parts = t.split()
-        tgt = parts[1] if parts[0].startswith(("s_branch", "s_cbranch")) and len(parts) > 1 else None
-        ins.append((parts[0], tgt))
-    back = [(labels[tg], i) for i, (m, tg) in enumerate(ins) if tg in labels and labels[tg] <= i]
-    whole = Counter(kind(m) for m, _ in ins)
-    if not back:
-        return whole, Counter(), Counter(), len(ins)
-    lo, hi = max(back, key=lambda b: b[1] - b[0])
-    loop = Counter(kind(m) for m, _ in ins[lo:hi + 1])
-    inner = [b for b in back if lo <= b[0] and b[1] <= hi and (b[0], b[1]) != (lo, hi)]
-    covered = [False] * len(ins)
-    for a, b in inner:
-        for i in range(a, b + 1):
-            covered[i] = True
-    once = Counter(kind(ins[i][0]) for i in range(lo, hi + 1) if not covered[i])
-    return whole, loop, once, len(ins)
+        parts = code.split()
+        ins.append((parts[0], " ".join(parts), top if depth else None, depth))
+
+    def count(sel):
+        c = Counter(kind(m) for m, _, _, _ in sel)
+        c["vmcnt(0)"] = sum(1 for m, t, _, _ in sel if m == "s_waitcnt" and "vmcnt(0)" in t)
+        return c
+
+    whole = count(ins)
+    sizes = Counter(t for _, _, t, _ in ins if t)
+    if not sizes:
+        return whole, Counter(), Counter(), len(ins), []
+    unit = sizes.most_common(1)[0][0]
+    loop = count([i for i in ins if i[2] == unit])
+    sel = [i for i in ins if i[2] == unit and i[3] == 1]
+    vmem = [t for m, t, _, _ in sel if kind(m) == "VMEM" or (m == "s_waitcnt" and "vmcnt" in t)]
+    return whole, loop, count(sel), len(ins), vmem
 
 
 def main():
-    path = sys.argv[1]
-    want = sys.argv[2] if len(sys.argv) > 2 else "k_scan5"
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    path = args[0]
+    want = args[1] if len(args) > 1 else "k_scan5"
+    listing = "--once-vmem" in sys.argv
     bodies, meta = kernels(path)
-    cols = ["VALU", "SALU", "v_readlane", "v_writelane", "LDS", "VMEM", "SMEM", "branch"]
+    cols = ["VALU", "SALU", "v_readlane", "v_writelane", "LDS", "VMEM", "SMEM", "branch", "vmcnt(0)"]
     for sym in sorted(bodies):
         if want not in sym:
             continue
-        whole, loop, once, n = analyse(bodies[sym])
+        whole, loop, once, n, vmem = analyse(bodies[sym])
         mt = meta.get(sym, {})
         print(demangle(sym).replace("gft::(anonymous namespace)::", "").replace("(gft::Scan2Params)", ""))
         print("  VGPRs %s  SGPRs %s  spilled SGPRs %s  spilled VGPRs %s  scratch %s B  instructions %d" % (
@@ -129,6 +148,9 @@ def main():
             mt.get("vgpr_spill_count", "?"), mt.get("private_segment_fixed_size", "?"), n))
         for tag, c in (("whole kernel", whole), ("unit loop", loop), ("  once per unit", once)):
             print("  %-16s" % tag + "  ".join("%s %d" % (k, c.get(k, 0)) for k in cols))
+        if listing:
+            for t in vmem:
+                print("      " + t)
 
 
 if __name__ == "__main__":
