@@ -12,6 +12,7 @@ GFT_POS_START, GFT_POS_END = 0, 1
 GFT_JSON_OK, GFT_JSON_SYNTAX, GFT_JSON_DEPTH, GFT_JSON_PATH, GFT_JSON_KEY, GFT_JSON_DUP, GFT_JSON_TEXT = range(7)
 GFT_FOLD_ASCII = 1
 GFT_STATS_ACCUMULATE = 1
+GFT_SCORE_DISTINCT = 1
 GFT_SCAN_UNIQUE = 2
 GFT_POS_RUNES = 4
 OP_UNIT, OP_AND, OP_OR, OP_NOT, OP_INORD = 1, 2, 3, 4, 5
@@ -213,6 +214,17 @@ SYMBOLS = {
     "gft_debug_count_columns": (_i, [_vp, _u64, _u32, _vp, _u32, _vp]),
     "gft_debug_stats_shape": (None, [C.POINTER(_u32)] * 8),
     "gft_finder_term_stats_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _vp, C.POINTER(_i)]),
+    "gft_score_docs_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _u32, _vp, C.POINTER(_u64)]),
+    "gft_top_docs_device": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "gft_gather_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_batch_top_docs_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_i)]),
+    "gft_batch_top_docs_words_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, C.POINTER(_u64),
+                                            C.POINTER(_i)]),
+    "gft_debug_score_docs": (_i, [_vp, _vp, _u64, _u32, _vp, _u32, _vp, C.POINTER(_u64)]),
+    "gft_debug_top_docs": (_i, [_vp, _u64, _u32, _u64, _vp, _vp, C.POINTER(_u64)]),
+    "gft_debug_gather_docs": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "gft_debug_rank_shape": (None, [C.POINTER(_u32)] * 10),
+    "gft_finder_top_docs_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _vp, _vp, _vp, C.POINTER(_u64), C.POINTER(_i)]),
     "gft_filter_word_matches_device": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_filter_word_matches": (_i, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     "gft_debug_word_rune": (_u32, [_u32]),

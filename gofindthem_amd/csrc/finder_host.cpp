@@ -735,6 +735,39 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     return "";
 }
 
+Error Finder::TopDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                        const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx,
+                        uint64_t* d_top_score, uint64_t* n_top, int* lowered) {
+    last_code_ = 0;
+    if (lowered) *lowered = 0;
+    if (n_top) *n_top = 0;
+    if (Error werr = words_refusal(); !werr.empty()) return werr;
+    if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
+    std::vector<Record> none;
+    Error err = collect(std::string(), false, none);
+    if (!err.empty()) return err;
+    int again = 0;
+    const auto top_call = wholeWords_ ? gft_batch_top_docs_words_device : gft_batch_top_docs_device;
+    int rc = top_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, weights, flags, k, doc_base,
+                      d_score, d_top_idx, d_top_score, n_top, &again);
+    if (rc) return fail_gft(rc);
+    if (!again) return "";
+    // as TermStatsDevice: the batch is lowered in full on the device and scanned again from there (nothing was written so far)
+    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return "the ranking of a batch that leaves ASCII needs the device ToLower on a single device";
+    }
+    const uint8_t* d_low = nullptr;
+    const uint64_t* d_low_off = nullptr;
+    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
+    if (rc) return fail_gft(rc);
+    rc = top_call(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, weights, flags, k, doc_base, d_score, d_top_idx,
+                  d_top_score, n_top, nullptr);
+    if (rc) return fail_gft(rc);
+    if (lowered) *lowered = 1;
+    return "";
+}
+
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {
     last_code_ = 0;
     if (wholeWords_) {
@@ -1125,6 +1158,16 @@ int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, cons
     if (!f) return GFT_E_INVALID;
     GFT_FLOCK(f);
     return finder_ret(f, f->finder->TermStatsDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, flags, doc_base, d_occ, d_docs, d_first, lowered),
+                      GFT_E_ENGINE);
+} GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
+
+int gft_finder_top_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_hit_bitmap,
+                               const uint32_t* want, const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score,
+                               uint64_t* d_top_idx, uint64_t* d_top_score, uint64_t* n_top, int* lowered) try {
+    if (!f) return GFT_E_INVALID;
+    GFT_FLOCK(f);
+    return finder_ret(f, f->finder->TopDevice(d_text_blob, d_doc_off, n_docs, d_hit_bitmap, want, weights, flags, k, doc_base, d_score, d_top_idx,
+                                              d_top_score, n_top, lowered),
                       GFT_E_ENGINE);
 } GFT_CATCH((f ? &const_cast<gft_finder*>(f)->err : nullptr))
 

@@ -174,6 +174,11 @@ public:
     // on the device and counted from there -- *lowered = 1; an accumulating array sees every batch once
     Error TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
                           uint32_t flags, uint64_t doc_base, uint64_t* d_occ, uint64_t* d_docs, uint64_t* d_first, int* lowered);
+    // gft_batch_top_docs_device (with the whole-word option its words twin) on the finder's engine under the same case rule: a batch
+    // that leaves ASCII is lowered on the device and ranked from there -- *lowered = 1; document indices are those of the source
+    Error TopDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
+                    const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx,
+                    uint64_t* d_top_score, uint64_t* n_top, int* lowered);
     // pipelined: Begin enqueues (gft_process_device_begin), End completes the oldest batch begun, the ToLower repeat included
     Error ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
     Error ProcessDeviceEnd();

@@ -232,6 +232,15 @@ struct gft_engine {
     // gft_hit_spans_device asks for with any cap; they are not read)
     struct StatsBufs { DevBuf ctl, rows, span_off, span_start, span_term; } d_stats;
 
+    // scores, the top list and the gather by index list (gft_rank.hip): the control block, the call's copy of the weights, the
+    // workgroups' bitset rows of the distinct mode, the select's histograms, the place tiles' counts with their prefix sums and scan
+    // partials, the candidates; the gather's lengths and the compact arrays the select's copy pass searches; the scores and the span
+    // CSR of the kept matches that gft_batch_top_docs_device ranks
+    struct RankBufs {
+        DevBuf ctl, weights, rows, hist, tile_gt, tile_eq, gt_pos, eq_pos, partial, cand_score, cand_idx, len, c_off, c_src, score, span_off,
+            span_start, span_term;
+    } d_rank;
+
     // whole-word matching (gft_words.hip): the class table (uploaded with the first call), the check pass's flag words, the marks of
     // a list's entries with their prefix sums and scan partials; the kept matches of gft_scan_words_device / gft_process_words_device
     // (off, pos, term), the spans gft_hit_spans_words_device filters, the kept spans gft_batch_term_stats_words_device counts
@@ -404,6 +413,13 @@ int host_eval(gft_engine* e, const gft_extra_matches* extra, uint64_t n_docs, co
 int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off, uint64_t n_docs, const uint8_t* d_out, uint64_t cap,
                 uint64_t* d_out_off, uint64_t* n_units, uint64_t* total, const char* who, const char* stage = nullptr,
                 uint64_t* text_range = nullptr);
+
+// ---- gft_rank_api.cpp --------------------------------------------------------------------------------------------------
+// the tail of gft_batch_top_docs_device and its words twin behind their scan: the list's scores into d_score (NULL: a buffer of the
+// engine's), then the top list of those scores, the select starting at the maximum the score pass found.  who: the entry point
+int batch_top_tail(gft_engine* e, const char* who, const uint64_t* d_off, const uint32_t* d_term, uint64_t n_docs, uint32_t n_terms,
+                   const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx,
+                   uint64_t* d_top_score, uint64_t* n_top);
 
 // ---- gft_staging.cpp ---------------------------------------------------------------------------------------------------
 // device -> pageable host memory through the bounce buffers; synchronous: returns when dst holds the bytes

@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "gft_stats.hpp"
+#include "gft_stats_dev.hpp"
 
 namespace gft {
 
@@ -130,11 +131,6 @@ __device__ __forceinline__ void cache_step(const StatsParams& P, const Cache& C,
     __syncthreads();
 }
 
-struct LdsRel {
-    const uint32_t* p;
-    __device__ __forceinline__ uint32_t operator[](uint32_t k) const { return p[k]; }
-};
-
 __global__ void __launch_bounds__(kStatsBlock) k_stats_count(const StatsParams P) {
     __shared__ uint64_t s_set[kStatsSetSlots];                      // the step's set; the large path's bitset
     __shared__ uint64_t c_first[kStatsCacheSlots];
@@ -173,12 +169,7 @@ __global__ void __launch_bounds__(kStatsBlock) k_stats_count(const StatsParams P
                     t[j] = P.term[e0 + i];
                     const uint32_t dl = stats_find_doc(rel, nd, i);
                     doc[j] = P.doc_base + d + dl;
-                    const uint64_t key = stats_set_key(dl, t[j]);
-                    for (uint32_t s = stats_set_slot(dl, t[j]);; s = stats_set_next(s)) {
-                        const uint64_t old = atomicCAS(reinterpret_cast<ull*>(&s_set[s]), 0ull, (ull)key);
-                        if (old == 0) { fst |= 1u << j; mine[j] = s; break; }
-                        if (old == key) break;
-                    }
+                    if (stats_set_first(s_set, dl, t[j], mine[j])) fst |= 1u << j;
                 }
                 __syncthreads();                                    // (every key is in the set before the first is taken out)
 #pragma unroll
@@ -202,8 +193,7 @@ __global__ void __launch_bounds__(kStatsBlock) k_stats_count(const StatsParams P
                     if (i >= ne) continue;
                     live |= 1u << j;
                     t[j] = P.term[e0 + c0 + i];
-                    const uint32_t bit = 1u << (t[j] & 31u);
-                    if (!(atomicOr(&bits[t[j] >> 5], bit) & bit)) fst |= 1u << j;
+                    if (stats_bitset_first(bits, t[j])) fst |= 1u << j;
                 }
                 cache_step(P, C, live, t, fst, doc);
             }

@@ -821,6 +821,73 @@ def count_columns_host(bitmap, n_rows, n_cols, count, row_idx=None, flags=0):
         raise GftError(rc, "gft_debug_count_columns")
 
 
+RANK_SHAPE_FIELDS = ("step_entries", "step_docs", "large_entries", "set_slots", "weight_lds_terms", "bitset_lds_terms", "range_weight",
+                     "digit_bits", "place_tile", "max_k")
+
+
+def rank_shape():
+    """the borders of the ranking's walks as a dict (gft_debug_rank_shape): RANK_SHAPE_FIELDS"""
+    v = [C.c_uint32(0) for _ in RANK_SHAPE_FIELDS]
+    _lib.load().gft_debug_rank_shape(*(C.byref(x) for x in v))
+    return {k: int(x.value) for k, x in zip(RANK_SHAPE_FIELDS, v)}
+
+
+def score_docs_host(off, term, n_terms, weights=None, distinct=False, score=None, flags=None, n_docs=None):
+    """gft_debug_score_docs over host arrays: off uint64 [n_docs + 1], term uint32 (indexed by off's values), weights uint32 [n_terms]
+    or None (every term 1) -> (score uint64 [n_docs] -- the given array, in place, or a new one --, max_score).  Raises GftError on a
+    refusal; no device needed"""
+    o, t = np.ascontiguousarray(off, dtype=np.uint64), np.ascontiguousarray(term, dtype=np.uint32)
+    n_docs = max(o.size - 1, 0) if n_docs is None else n_docs
+    w = np.ascontiguousarray(weights, dtype=np.uint32) if weights is not None else None
+    score = np.zeros(n_docs, dtype=np.uint64) if score is None else score
+    assert score.dtype == np.uint64 and score.flags.c_contiguous
+    mx = C.c_uint64(0)
+    rc = _lib.load().gft_debug_score_docs(_p(o) if o.size else None, _p(t) if t.size else None, n_docs, n_terms, _p(w) if w is not None and w.size else None,
+                                          int(flags) if flags is not None else (_lib.GFT_SCORE_DISTINCT if distinct else 0),
+                                          _p(score) if score.size else None, C.byref(mx))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_score_docs")
+    return score, int(mx.value)
+
+
+def top_docs_host(score, k, doc_base=0, top_idx=None, top_score=None, n_docs=None):
+    """gft_debug_top_docs over a host uint64 array -> (top_idx, top_score) uint64 [n_top]; with the two arrays given ([k], written in
+    place up to n_top) -> n_top.  Raises GftError on a refusal; no device needed"""
+    sc = np.ascontiguousarray(score, dtype=np.uint64)
+    n_docs = sc.size if n_docs is None else n_docs
+    given = top_idx is not None
+    if not given:
+        top_idx, top_score = np.zeros(max(k, 1), dtype=np.uint64), np.zeros(max(k, 1), dtype=np.uint64)
+    n = C.c_uint64(0)
+    rc = _lib.load().gft_debug_top_docs(_p(sc) if sc.size else None, n_docs, int(k), int(doc_base), _p(top_idx), _p(top_score), C.byref(n))
+    if rc != 0:
+        raise GftError(rc, "gft_debug_top_docs")
+    return int(n.value) if given else (top_idx[:n.value], top_score[:n.value])
+
+
+def gather_docs_host(blob, doc_off, idx, idx_base=0, cap_bytes=None, guard=0, out_shift=0):
+    """gft_debug_gather_docs over host arrays -> (total, out uint8 [cap_bytes + guard], out_off uint64 [m + 1 + guard]); no device
+    needed.  cap_bytes None: count first (out NULL, cap 0), then exactly what the result needs; the guard entries behind the caps
+    hold 0xA5 and must come back untouched; out_shift as select_docs_host takes it"""
+    L = _lib.load()
+    a = np.frombuffer(bytes(blob), dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob, dtype=np.uint8)
+    off, ix = np.ascontiguousarray(doc_off, dtype=np.uint64), np.ascontiguousarray(idx, dtype=np.uint64)
+    n_docs, m = max(off.size - 1, 0), ix.size
+    total = C.c_uint64(0)
+
+    def call(out, cb, oo):
+        rc = L.gft_debug_gather_docs(a.ctypes.data if a.size else None, _p(off) if n_docs else None, n_docs, _p(ix) if m else None, m, int(idx_base), out, cb,
+                                     oo, C.byref(total))
+        if rc != 0:
+            raise GftError(rc, "gft_debug_gather_docs")
+    if cap_bytes is None:
+        call(None, 0, np.zeros(m + 1, dtype=np.uint64).ctypes.data)
+        cap_bytes = int(total.value)
+    out, out_off, _ = _docs_host_outputs(cap_bytes, m, guard, out_shift)
+    call(out.ctypes.data if cap_bytes else None, cap_bytes, out_off.ctypes.data)
+    return int(total.value), out, out_off
+
+
 WORDS_POS_END = 1                                   # GFT_WORDS_POS_END
 
 
@@ -1295,6 +1362,91 @@ class Engine:
     def stats_shape():
         """the borders of the statistics' walk (gft_debug_stats_shape) as a dict"""
         return stats_shape()
+
+    # -- scores, the top list, documents by index list (csrc/gft_rank.hip) -------------------------------------------------------
+    def score_docs_raw(self, d_off_ptr, d_term_ptr, n_docs, n_terms, weights, flags, d_score_ptr):
+        """gft_score_docs_device on device pointers as they are (None: NULL); weights: a host uint32 array or None -> max_score; the
+        caller has drained the streams that wrote the list"""
+        mx = C.c_uint64(0)
+        self._check(self._L.gft_score_docs_device(self._h, d_off_ptr, d_term_ptr, n_docs, n_terms, _p(weights), int(flags), d_score_ptr, C.byref(mx)))
+        return int(mx.value)
+
+    def score_docs_device(self, off, term, n_docs, n_terms, weights=None, distinct=False, score=None):
+        """a score per document of a term CSR on the device (gft_score_docs_device): the sum of weights[t] over a document's entries,
+        with distinct over its distinct terms.  off, term as term_stats_device takes them (tensors or device pointers); weights: a host
+        array of n_terms uint32, None: every term 1; score: an int64 [n_docs] device tensor, allocated when not given.  Returns
+        (score, max_score)"""
+        import torch
+        given = [a for a in (off, term, score) if hasattr(a, "device")]
+        dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+        score = torch.zeros(n_docs, dtype=torch.int64, device=dev) if score is None else score
+        assert score.dtype == torch.int64 and score.numel() == n_docs and score.is_contiguous()
+        w = np.ascontiguousarray(weights, dtype=np.uint32) if weights is not None else None
+        assert w is None or w.size == n_terms
+        torch.cuda.current_stream(dev).synchronize()
+        ptr = lambda a: (a if isinstance(a, int) or a is None else (a.data_ptr() if a.numel() else None))  # noqa: E731
+        mx = self.score_docs_raw(ptr(off), ptr(term), n_docs, n_terms, w if w is not None and w.size else None,
+                                 _lib.GFT_SCORE_DISTINCT if distinct else 0, ptr(score))
+        return score, mx
+
+    def top_docs_raw(self, d_score_ptr, n_docs, k, doc_base, d_top_idx_ptr, d_top_score_ptr):
+        """gft_top_docs_device on device pointers as they are -> n_top"""
+        n = C.c_uint64(0)
+        self._check(self._L.gft_top_docs_device(self._h, d_score_ptr, n_docs, int(k), int(doc_base), d_top_idx_ptr, d_top_score_ptr, C.byref(n)))
+        return int(n.value)
+
+    def top_docs_device(self, score, k=10, doc_base=0):
+        """the k best documents of an int64 device tensor read as uint64 (gft_top_docs_device): larger score first, among equals the
+        smaller index first, no document of score 0.  Returns (top_idx, top_score): int64 device tensors of n_top entries"""
+        import torch
+        assert score.dtype == torch.int64 and score.is_contiguous()
+        idx, val = (torch.empty(max(k, 1), dtype=torch.int64, device=score.device) for _ in range(2))
+        torch.cuda.current_stream(score.device).synchronize()
+        n = self.top_docs_raw(score.data_ptr() if score.numel() else None, int(score.numel()), k, doc_base, idx.data_ptr(), val.data_ptr())
+        return idx[:n], val[:n]
+
+    def gather_docs_raw(self, *args):
+        """gft_gather_docs_device on device pointers as they are: (d_text, d_doc_off, n_docs, d_idx, m, idx_base, d_out, cap_bytes,
+        d_out_off) -> total_bytes"""
+        total = C.c_uint64(0)
+        self._check(self._L.gft_gather_docs_device(self._h, *args, C.byref(total)))
+        return int(total.value)
+
+    def gather_docs_device(self, text, doc_off, idx, idx_base=0):
+        """the documents idx names, in idx's order, repeats allowed, as one blob on the device (gft_gather_docs_device).  text: uint8
+        with 64 bytes of slack; doc_off, idx: int64 device tensors.  Returns (out uint8 [total] -- a view with 64 zero bytes behind
+        it --, out_off int64 [m + 1]).  Two calls: count only, then into a tensor of exactly the size counted"""
+        import torch
+        n_docs, m = int(doc_off.numel()) - 1, int(idx.numel())
+        out_off = torch.empty(m + 1, dtype=torch.int64, device=text.device)
+        torch.cuda.current_stream(text.device).synchronize()
+        head = (text.data_ptr(), doc_off.data_ptr(), n_docs, idx.data_ptr() if m else None, m, int(idx_base))
+        total = self.gather_docs_raw(*head, None, 0, out_off.data_ptr())
+        buf = torch.zeros(total + 64, dtype=torch.uint8, device=text.device)
+        torch.cuda.current_stream(text.device).synchronize()
+        self.gather_docs_raw(*head, buf.data_ptr(), total, out_off.data_ptr())
+        return buf[:total], out_off
+
+    @staticmethod
+    def score_docs_host(off, term, n_terms, weights=None, distinct=False):
+        """the host twin of score_docs_device over numpy arrays (gft_debug_score_docs) -> (score uint64 [n_docs], max_score)"""
+        return score_docs_host(off, term, n_terms, weights, distinct)
+
+    @staticmethod
+    def top_docs_host(score, k=10, doc_base=0):
+        """the host twin of top_docs_device (gft_debug_top_docs) -> (top_idx, top_score) uint64 [n_top]"""
+        return top_docs_host(score, k, doc_base)
+
+    @staticmethod
+    def gather_docs_host(blob, doc_off, idx, idx_base=0):
+        """the host twin of gather_docs_device (gft_debug_gather_docs) -> (out uint8 [total], out_off uint64 [m + 1])"""
+        total, out, out_off = gather_docs_host(blob, doc_off, idx, idx_base)
+        return out[:total], out_off
+
+    @staticmethod
+    def rank_shape():
+        """the borders of the ranking's walks (gft_debug_rank_shape) as a dict"""
+        return rank_shape()
 
     # -- whole-word matching (csrc/gft_words.hip) ---------------------------------------------------------------------------------
     def filter_word_matches_device(self, text, doc_off, off, pos, length=None, term=None, term_len=None, pos_end=False):

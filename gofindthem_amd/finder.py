@@ -165,7 +165,7 @@ class Finder:
         """allow_no_device: keep the handle when no HIP device exists, so the host-only half (expression
         registry, parser, engine-build orchestration) can be exercised; every GPU step then fails with GFT_E_HIP.
         whole_words: a keyword occurrence counts only where it stands at word borders (gft_finder_set_whole_words): `he` no longer
-        fires inside `ushers`.  Every Process*, Select*, Route*, Count*, Spans*, Redact*, Excerpt*, Highlight* and TermStats* call of
+        fires inside `ushers`.  Every Process*, Select*, Route*, Count*, Spans*, Redact*, Excerpt*, Highlight*, TermStats* and Top* call of
         this finder then answers from those occurrences; needs the GPU substring engine on one device and no regex terms."""
         self._L = _lib.load()
         h = C.c_void_p()
@@ -678,10 +678,8 @@ class Finder:
         out = replace_spans_tensor(call, text, doc_off, span_off, start, length, reps, term if tr is not None else None)
         return out + (bool(low.value),)
 
-    def _replace_table(self, with_):
-        """with_ of ReplaceLines -> (the table, a table entry per term of the engine or None)"""
-        if isinstance(with_, (bytes, bytearray, memoryview)):
-            return [bytes(with_)], None
+    def _engine_terms(self):
+        """{the dictionary's text of a term: its id} of the expressions added so far"""
         self.ForceBuild()                                           # (the dictionary of the expressions added so far: what the scan will use)
         eng = self.engine_handle()
         tp, tl = C.c_void_p(), C.c_uint32()
@@ -689,6 +687,23 @@ class Finder:
         for t in range(int(self._L.gft_n_terms(eng))):
             self._check_engine(self._L.gft_term(eng, t, C.byref(tp), C.byref(tl)))
             terms[C.string_at(tp.value, tl.value)] = t
+        return terms
+
+    @staticmethod
+    def _term_of(terms, kw, who):
+        key = kw.encode("utf-8") if isinstance(kw, str) else bytes(kw)
+        t = terms.get(key)
+        if t is None:                                               # (a case-insensitive finder holds its keywords lowered)
+            t = terms.get(key.decode("utf-8", "surrogateescape").lower().encode("utf-8", "surrogateescape"))
+        if t is None:
+            raise ValueError("%s: %r is no keyword of this finder" % (who, kw))
+        return t
+
+    def _replace_table(self, with_):
+        """with_ of ReplaceLines -> (the table, a table entry per term of the engine or None)"""
+        if isinstance(with_, (bytes, bytearray, memoryview)):
+            return [bytes(with_)], None
+        terms = self._engine_terms()
         default = bytes(with_.get(None, b"[REDACTED]"))
         reps, ids = [], {}
         term_rep = np.full(len(terms), -1, dtype=np.int64)
@@ -699,13 +714,7 @@ class Finder:
             if rep not in ids:
                 ids[rep] = len(reps)
                 reps.append(rep)
-            key = kw.encode("utf-8") if isinstance(kw, str) else bytes(kw)
-            t = terms.get(key)
-            if t is None:                                           # (a case-insensitive finder holds its keywords lowered)
-                t = terms.get(key.decode("utf-8", "surrogateescape").lower().encode("utf-8", "surrogateescape"))
-            if t is None:
-                raise ValueError("ReplaceLines: %r is no keyword of this finder" % (kw,))
-            term_rep[t] = ids[rep]
+            term_rep[self._term_of(terms, kw, "ReplaceLines")] = ids[rep]
         if default not in ids:
             ids[default] = len(reps)
             reps.append(default)
@@ -879,6 +888,80 @@ class Finder:
             self._check_engine(self._L.gft_term(self.engine_handle(), int(t), C.byref(tp), C.byref(tl)))
             out[C.string_at(tp.value, tl.value)] = (int(occ[t]), int(docs[t]), int(first[t]))
         return out, lowered
+
+    # -- which documents matched most (csrc/gft_rank.hip) ----------------------------------------------------------------------
+    def TopDevice(self, text, doc_off, bitmap=None, want=None, k=10, weights=None, distinct=False):
+        """the scores of a resident batch and its k best documents (gft_finder_top_docs_device).  text, doc_off, bitmap and want as
+        TermStatsDevice takes them: with the rows ProcessDevice left the KEPT matches score, with None every dictionary match.  A
+        document's score is the sum of weights[t] over its scoring occurrences, with distinct over its distinct keywords; weights: a
+        host array with a uint32 per term of the engine, None: every keyword 1.  Returns (top_idx, top_score, scores, lowered): int64
+        device tensors -- the at most k documents with a score above 0, larger score first, among equals the smaller index first;
+        their scores; every document's score -- and whether the batch left ASCII and was lowered on the device first (the indices
+        are the caller's either way).  Needs what ProcessDevice needs"""
+        import torch
+        n = int(doc_off.numel()) - 1
+        lowered, n_top = C.c_int(0), C.c_uint64(0)
+        w = None
+        if want is not None:
+            w = np.ascontiguousarray(self.want_mask() & np.ascontiguousarray(want, dtype=np.uint32))
+        wt = None
+        if weights is not None:
+            self.ForceBuild()
+            wt = np.ascontiguousarray(weights, dtype=np.uint32)
+            if wt.size != int(self._L.gft_n_terms(self.engine_handle())):
+                raise ValueError("TopDevice: weights needs an entry per term of the engine")
+        scores = torch.zeros(n, dtype=torch.int64, device=text.device)
+        idx, val = (torch.empty(max(k, 1), dtype=torch.int64, device=text.device) for _ in range(2))
+        torch.cuda.current_stream(text.device).synchronize()
+        self._check(self._L.gft_finder_top_docs_device(
+            self._h, text.data_ptr(), doc_off.data_ptr(), n, bitmap.data_ptr() if bitmap is not None and bitmap.numel() else None,
+            w.ctypes.data if w is not None and w.size else None, wt.ctypes.data if wt is not None and wt.size else None,
+            _lib.GFT_SCORE_DISTINCT if distinct else 0, int(k), 0, scores.data_ptr() if n else None, idx.data_ptr(), val.data_ptr(),
+            C.byref(n_top), C.byref(lowered)))
+        return idx[:n_top.value], val[:n_top.value], scores, bool(lowered.value)
+
+    def TopLines(self, data, k=10, weights=None, distinct=False, want=None, kept=True):
+        """bytes -> ([(line_index, score, line_bytes), ...], lowered): the at most k lines of a blob that matched most, best first.  A
+        line's score is the sum of its scoring occurrences' weights -- kept=True: the occurrences that are witnesses of a true, wanted
+        expression (want: want_mask(), None: any), what SpansLines lists; kept=False: every occurrence of every keyword --, with
+        distinct every keyword of a line once.  weights: None (every keyword 1), or a dict {keyword: int}; its optional key None is
+        the weight of the keywords it does not name, 1 without it; 0 mutes a keyword; a keyword the finder's dictionary does not hold
+        is a ValueError.  One upload; the k lines come down through gft_gather_docs_device, from the caller's own bytes even when the
+        batch was lowered (lowered True), each with its newline.  Device route only"""
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, "the top lines need the device route: the GPU substring engine, no regex terms, one device")
+        if not self.n_expressions:                                   # (no dictionary: nothing can occur)
+            return [], False
+        data = bytes(data)
+        wt = None
+        if weights is not None:
+            terms = self._engine_terms()
+            wt = np.full(len(terms), int(weights.get(None, 1)), dtype=np.uint32)
+            for kw, v in weights.items():
+                if kw is not None:
+                    wt[self._term_of(terms, kw, "TopLines")] = int(v)
+        buf = self._resident(data)
+        if kept:
+            off, bm = self.ProcessLinesDevice(buf, len(data))
+            if not bm.numel():                                       # (no lines)
+                return [], False
+        else:
+            off, bm = self.SplitLinesDevice(buf, len(data), 0), None
+        idx, val, _, lowered = self.TopDevice(buf, off, bm, want if kept else None, k, wt, distinct)
+        m = int(idx.numel())
+        if not m:
+            return [], lowered
+        import torch
+        out_off = torch.empty(m + 1, dtype=torch.int64, device=buf.device)
+        total = C.c_uint64(0)
+        head = (self.engine_handle(), buf.data_ptr(), off.data_ptr(), int(off.numel()) - 1, idx.data_ptr(), m, 0)
+        torch.cuda.current_stream(buf.device).synchronize()
+        self._check_engine(self._L.gft_gather_docs_device(*head, None, 0, out_off.data_ptr(), C.byref(total)))
+        out = torch.zeros(total.value + 64, dtype=torch.uint8, device=buf.device)
+        torch.cuda.current_stream(buf.device).synchronize()
+        self._check_engine(self._L.gft_gather_docs_device(*head, out.data_ptr(), total.value, out_off.data_ptr(), C.byref(total)))
+        blob, oo = out[:total.value].cpu().numpy().tobytes(), out_off.cpu().numpy()
+        return [(int(i), int(v), blob[int(oo[j]):int(oo[j + 1])]) for j, (i, v) in enumerate(zip(idx.cpu().tolist(), val.cpu().tolist()))], lowered
 
     def CountExpressions(self, data):
         """bytes -> a uint64 array with one count per expression index: the number of lines of the blob on which the expression is

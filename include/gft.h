@@ -848,6 +848,77 @@ int gft_debug_count_columns(const uint32_t* bitmap, uint64_t n_rows, uint32_t n_
 void gft_debug_stats_shape(uint32_t* step_entries, uint32_t* step_docs, uint32_t* set_slots, uint32_t* cache_slots, uint32_t* large_entries,
                            uint32_t* bitset_lds_terms, uint32_t* range_weight, uint32_t* column_rows);
 
+/* ---- Rank on the device: a score per document, the k best documents, documents by index list (csrc/gft_rank.hip) ----------
+ * Which documents matched most.  All arithmetic is integer: every result is exact and reproducible.
+ *
+ * gft_score_docs_device.  The list is the CSR gft_term_stats_device takes -- (match_off, term_id) of gft_scan_device or (d_span_off,
+ * d_span_term) of gft_hit_spans_device; d_off[0] may be non-zero.  d_score[d] = the sum of weights[t] over the entries of document
+ * d; with GFT_SCORE_DISTINCT over the DISTINCT terms of d.  weights: HOST memory, n_terms words, copied by the call; NULL = every
+ * term 1; a weight of 0 mutes a term.  Fewer than 2^32 entries of 32-bit weights cannot overflow the 64-bit sum.  Every one of the
+ * n_docs scores is written, an empty document's is 0; *max_score (host, nullable) is the largest.  The call needs neither a
+ * dictionary nor programs and leaves gft_last_nonascii alone.  Launches (gft_profile_read): "score_check" -- the statistics' check
+ * pass: a descending offset or a term id >= n_terms is found on the device before anything is written --, "score_docs" -- the
+ * statistics' walk (csrc/gft_stats_piece.hpp): a workgroup owns a range of whole documents of near-equal weight and walks it in
+ * steps of whole documents whose sums lie in LDS; a document of large_entries entries or more is summed by a whole workgroup; the
+ * distinct mode asks the step's set and the large path's bitset as the statistics' docs counter does.  A document has one owner:
+ * its score goes out by a plain store, no atomic touches d_score, no workgroup waits for another.  The weights lie in LDS while
+ * n_terms <= weight_lds_terms (gft_debug_rank_shape), above that they are read through the cache.  The call waits for the stream.
+ * Refusals and rules are gft_term_stats_device's: GFT_E_INVALID with d_score byte for byte as it was (unknown flag bits, a
+ * descending offset, a term id >= n_terms, d_score over an input, a size beyond the address space), GFT_E_UNSUPPORTED for a handle
+ * over several devices, between _begin and _end only after _complete, the handle usable after any error.  Work buffers: 80 bytes
+ * of control block, n_terms * 4 bytes of weights, in the distinct mode above bitset_lds_terms a bitset row per workgroup; nothing
+ * per entry or document. */
+#define GFT_SCORE_DISTINCT 1u
+int gft_score_docs_device(gft_engine* e, const uint64_t* d_off, const uint32_t* d_term, uint64_t n_docs, uint32_t n_terms,
+                          const uint32_t* weights, uint32_t flags, uint64_t* d_score, uint64_t* max_score);
+/* The k best of a score array.  The order is total: the larger score first, among equal scores the smaller document index first.  A
+ * document whose score is 0 is never listed: *n_top (host) = min(k, number of non-zero scores).  d_top_idx[r] = doc_base + d and
+ * d_top_score[r] its score for r < *n_top; the entries at and past *n_top are not written.  k <= 4096 (max_k: one workgroup's sort
+ * in LDS, 16 bytes a candidate); a larger k is GFT_E_INVALID; k == 0 and n_docs == 0 are valid and list nothing.  d_score is any
+ * uint64 array, not only one gft_score_docs_device wrote: nothing about it is trusted.  Launches: "top_max" (the largest score),
+ * "top_select" -- a radix select over the 64-bit key, digit_bits bits a pass from the digit of the maximum's top bit down: a
+ * histogram launch (LDS bins, one atomic per workgroup and non-empty bin) and a one-wave pick that leaves the prefix and the rank
+ * still looked for in the control block, so the host reads nothing between the passes; with fewer than k documents there is no
+ * k-th score and no select --, "top_place" (score above the threshold T, and the first k - c documents in index order with score
+ * T, c the scores above it: ballots per tile of place_tile documents behind the tiles' prefix sums), "top_sort" (one workgroup, a
+ * bitonic network in LDS).  No workgroup waits for another; the call waits for the stream.  Refusals as above, the two arrays byte
+ * for byte as they were; an output over the scores or over the other output is one of them.  Work buffers: the control block, 16 KB
+ * of histograms, 24 bytes per tile of place_tile documents (0.024 bytes a document) with the prefix sum's partials, 16 bytes a
+ * candidate. */
+int gft_top_docs_device(gft_engine* e, const uint64_t* d_score, uint64_t n_docs, uint32_t k, uint64_t doc_base, uint64_t* d_top_idx,
+                        uint64_t* d_top_score, uint64_t* n_top);
+/* Documents by index list: the output side of gft_select_docs_device for a list instead of a bitmap.  Output document j is input
+ * document d_idx[j] - idx_base, in list order; repeats are allowed.  It materialises the top list, and any doc_idx a select, a route
+ * or a context call returned, in any order.  d_out_off [m + 1] is complete whatever the cap; *total_bytes the bytes of the listed
+ * documents.  Cap protocol, the 64 bytes of slack behind the text, the overlap refusals and the 4 GiB document limit are the
+ * select's: nothing is stored at or past d_out + min(total, cap_bytes); d_out == NULL with cap_bytes == 0 counts only.  Launches:
+ * "gather_place" (every index checked against n_docs on the device: an index outside -- or a listed document whose offsets descend
+ * or that has 4 GiB or more -- is GFT_E_INVALID before a byte is written), "gather_scan", "gather_copy" (the select's copy pass).
+ * Work buffers: 20 bytes per list entry. */
+int gft_gather_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint64_t* d_idx,
+                           uint64_t m, uint64_t idx_base, uint8_t* d_out, uint64_t cap_bytes, uint64_t* d_out_off, uint64_t* total_bytes);
+/* Scores and top list of a resident batch in one call, as gft_batch_term_stats_device counts one: with d_hit_bitmap the KEPT matches
+ * score (gft_hit_spans_device in count-then-fill form into buffers of the engine's), with NULL every dictionary match.  weights:
+ * host, gft_n_terms words, or NULL.  d_score [n_docs] is nullable when only the list is wanted.  The select starts at the maximum
+ * the score pass found.  nonascii as there: set to 1 with NOTHING written when the scan folded and the batch was not fold-safe. */
+int gft_batch_top_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
+                              const uint32_t* d_hit_bitmap, const uint32_t* want, const uint32_t* weights, uint32_t flags, uint32_t k,
+                              uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx, uint64_t* d_top_score, uint64_t* n_top,
+                              int* nonascii);
+/* The host forms, no HIP device needed, same contracts, all pointers host: the kernels' walks step by step and lane by lane through
+ * the source they are compiled from (csrc/gft_rank_piece.hpp). */
+int gft_debug_score_docs(const uint64_t* off, const uint32_t* term, uint64_t n_docs, uint32_t n_terms, const uint32_t* weights, uint32_t flags,
+                         uint64_t* score, uint64_t* max_score);
+int gft_debug_top_docs(const uint64_t* score, uint64_t n_docs, uint32_t k, uint64_t doc_base, uint64_t* top_idx, uint64_t* top_score,
+                       uint64_t* n_top);
+int gft_debug_gather_docs(const uint8_t* blob, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* idx, uint64_t m, uint64_t idx_base,
+                          uint8_t* out, uint64_t cap_bytes, uint64_t* out_off, uint64_t* total_bytes);
+/* where those walks' borders are: the entries and the documents of a step at most, the entries at which a document takes the large
+ * path, the slots of the step's set, the n_terms up to which the weights and the large path's bitset lie in LDS, the weight a
+ * workgroup owns at least, the bits of a select pass, the documents of a place tile, the largest k */
+void gft_debug_rank_shape(uint32_t* step_entries, uint32_t* step_docs, uint32_t* large_entries, uint32_t* set_slots, uint32_t* weight_lds_terms,
+                          uint32_t* bitset_lds_terms, uint32_t* range_weight, uint32_t* digit_bits, uint32_t* place_tile, uint32_t* max_k);
+
 /* ---- Whole-word matching on the device: a match or span list filtered at word borders (csrc/gft_words.hip) -----------------
  * Every other call matches substrings: `he` fires inside `ushers`.  This one takes a list of occurrences in CSR form and the text
  * they were found in, keeps the entries that stand at word borders and compacts the list stably.
@@ -911,6 +982,11 @@ int gft_hit_spans_words_device(gft_engine* e, const uint8_t* d_text_blob, const 
 int gft_batch_term_stats_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
                                       const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
                                       uint64_t* d_docs, uint64_t* d_first, int* nonascii);
+/* gft_batch_top_docs_device over the whole-word matches, the same way */
+int gft_batch_top_docs_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
+                                    const uint32_t* d_hit_bitmap, const uint32_t* want, const uint32_t* weights, uint32_t flags, uint32_t k,
+                                    uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx, uint64_t* d_top_score, uint64_t* n_top,
+                                    int* nonascii);
 /* The filter on the host, no HIP device needed, same contract, all pointers host: the kernels' walk, entry tile by entry tile
  * through the source they are compiled from (csrc/gft_words_piece.hpp). */
 int gft_debug_filter_word_matches(const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* off, const uint32_t* pos,
@@ -1077,6 +1153,14 @@ int gft_finder_replace_device(gft_finder* f, const uint8_t* d_text_blob, const u
 int gft_finder_term_stats_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
                                  const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
                                  uint64_t* d_docs, uint64_t* d_first, int* lowered);
+/* Scores and top list of a resident batch on the finder's engine (gft_batch_top_docs_device; with the whole-word option its words
+ * twin) under the same case rule: a batch that leaves ASCII is lowered on the device first and *lowered set to 1 -- document indices
+ * are the same in both forms, the list needs no mapping back.  weights: host, gft_n_terms of the finder's engine, or NULL; flags, k,
+ * doc_base, d_score (nullable), the two top arrays and n_top as gft_batch_top_docs_device takes them.  The refusals of
+ * gft_finder_term_stats_device. */
+int gft_finder_top_docs_device(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
+                               const uint32_t* d_hit_bitmap, const uint32_t* want, const uint32_t* weights, uint32_t flags, uint32_t k,
+                               uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx, uint64_t* d_top_score, uint64_t* n_top, int* lowered);
 /* ... pipelined (gft_process_device_begin / _end): _end also lowers and repeats a batch that left ASCII, as above (a younger
  * batch in flight is completed in place first) */
 int gft_finder_process_device_begin(gft_finder* f, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs,
