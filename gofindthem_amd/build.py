@@ -20,7 +20,7 @@ ARCH = "gfx950"
 EXTRA = os.environ.get("GFT_EXTRA_KERNELS", "0") == "1"
 HIP_SOURCES = ["gft_kernels.hip", "gft_solve.hip", "gft_scan3.hip", "gft_scan5.hip", "gft_compact.hip", "gft_tolower.hip", "gft_rules.hip", "gft_json.hip", "gft_tags.hip", "gft_result.hip", "gft_tagdoc.hip", "gft_split.hip", "gft_select.hip", "gft_context.hip", "gft_route.hip", "gft_spans.hip", "gft_lowermap.hip", "gft_excerpt.hip", "gft_mark.hip", "gft_replace.hip", "gft_stats.hip", "gft_words.hip", "gft_rank.hip"] + (["gft_scan2.hip", "gft_scan4.hip"] if EXTRA else [])
 STAMP = os.path.join(CSRC, ".build_flags")
-CXX_SOURCES = ["gft_api.cpp", "gft_pipeline.cpp", "gft_process.cpp", "gft_staging.cpp", "gft_lower_api.cpp", "gft_rules_api.cpp", "gft_tags_api.cpp", "gft_result_api.cpp", "gft_tagdoc_api.cpp", "gft_json_api.cpp", "gft_split_api.cpp", "split_host.cpp", "gft_select_api.cpp", "select_host.cpp", "gft_context_api.cpp", "context_host.cpp", "gft_route_api.cpp", "route_host.cpp", "gft_spans_api.cpp", "spans_host.cpp", "gft_lowermap_api.cpp", "lowermap_host.cpp", "gft_span_runs.cpp", "gft_doc_gather.cpp", "gft_excerpt_api.cpp", "excerpt_host.cpp", "gft_mark_api.cpp", "mark_host.cpp", "gft_replace_api.cpp", "replace_host.cpp", "gft_stats_api.cpp", "stats_host.cpp", "gft_rank_api.cpp", "rank_host.cpp", "gft_words_api.cpp", "words_host.cpp", "witness_terms.cpp", "gft_debug.cpp",
+CXX_SOURCES = ["gft_api.cpp", "gft_pipeline.cpp", "gft_process.cpp", "gft_staging.cpp", "gft_lower_api.cpp", "gft_rules_api.cpp", "gft_tags_api.cpp", "gft_result_api.cpp", "gft_tagdoc_api.cpp", "gft_json_api.cpp", "gft_split_api.cpp", "split_host.cpp", "gft_select_api.cpp", "select_host.cpp", "gft_context_api.cpp", "context_host.cpp", "gft_route_api.cpp", "route_host.cpp", "gft_spans_api.cpp", "spans_host.cpp", "gft_lowermap_api.cpp", "lowermap_host.cpp", "gft_span_runs.cpp", "gft_doc_gather.cpp", "gft_excerpt_api.cpp", "excerpt_host.cpp", "gft_mark_api.cpp", "mark_host.cpp", "gft_replace_api.cpp", "replace_host.cpp", "gft_term_list.cpp", "gft_stats_api.cpp", "stats_host.cpp", "gft_rank_api.cpp", "rank_host.cpp", "gft_words_api.cpp", "words_host.cpp", "witness_terms.cpp", "gft_debug.cpp",
                "gft_multi.cpp", "ac_tables.cpp", "scan2_tables.cpp", "scan3_tables.cpp", "dsl_compile.cpp", "finder_host.cpp", "json_mini.cpp", "group_dsl.cpp", "group_host.cpp", "group_records.cpp", "group_json.cpp", "group_tags.cpp", "group_api.cpp", "host_solve.cpp", "compact_host.cpp", "program_set.cpp", "table_set.cpp", "batch_verdict.cpp", "solve_plan.cpp", "tolower_host.cpp", "rule_set.cpp", "tag_entries.cpp", "rules_json.cpp", "tags_json.cpp", "json_schema.cpp", "json_paths.cpp"]
 
 

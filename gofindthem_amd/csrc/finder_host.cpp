@@ -581,6 +581,44 @@ Error Finder::RouteDocsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     return rc ? fail_gft(rc) : Error();
 }
 
+// run(d_text, d_doc_off, scan_flags, &again) is a batch call that scans: on the caller's batch with the finder's fold flag, and -- if
+// it reports that the batch left ASCII (again != 0: nothing was written) -- on the batch lowered in full on the device, flags 0, as
+// repeat_if_not_ascii.  unsupported: what a finder that cannot lower on its one device says then
+template <class Run>
+Error Finder::scan_twice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const char* unsupported, int* lowered, Run run) {
+    int again = 0;
+    int rc = run(d_blob, d_doc_off, caseSensitive_ ? 0u : (uint32_t)GFT_FOLD_ASCII, &again);
+    if (rc) return fail_gft(rc);
+    if (!again) return "";
+    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return unsupported;
+    }
+    const uint8_t* d_low = nullptr;
+    const uint64_t* d_low_off = nullptr;
+    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
+    if (rc) return fail_gft(rc);
+    rc = run(d_low, d_low_off, 0u, nullptr);
+    if (rc) return fail_gft(rc);
+    if (lowered) *lowered = 1;
+    return "";
+}
+
+// Spans that index the lowered text are cut from the lowered text: the batch is lowered again here, as the spans call lowered it,
+// and d_text / d_off then name that copy.  what: the caller's noun, as its refusal begins ("excerpts of", "marks in")
+Error Finder::cut_from_lowered(const char* what, bool spans_lowered, bool source, uint64_t n_docs, const uint8_t*& d_text, const uint64_t*& d_off,
+                               int* lowered) {
+    if (!spans_lowered || source || !n_docs) return "";
+    if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
+        last_code_ = GFT_E_UNSUPPORTED;
+        return std::string(what) + " a lowered batch need a case-insensitive finder with the device ToLower on a single device";
+    }
+    int rc = gft_lower_owned(gpu_->handle(), d_text, d_off, n_docs, &d_text, &d_off);
+    if (rc) return fail_gft(rc);
+    if (lowered) *lowered = 1;
+    return "";
+}
+
 Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint64_t* d_row_idx,
                              const uint32_t* want, uint64_t* d_span_off, uint32_t* d_span_start, uint32_t* d_span_len, uint32_t* d_span_term, uint64_t cap,
                              uint64_t* total, int* lowered, bool source) {
@@ -597,27 +635,20 @@ Error Finder::HitSpansDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
     if (!err.empty()) return err;
     // (with the whole-word option the filter runs on the text that was scanned, in front of any map back to the source)
     const auto spans_call = wholeWords_ ? gft_hit_spans_words_device : gft_hit_spans_device;
-    int rc = spans_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, d_row_idx, want, d_span_off,
-                        d_span_start, d_span_len, d_span_term, cap, total);
-    if (rc) return fail_gft(rc);
-    if (caseSensitive_ || !n_docs || !gft_last_nonascii(gpu_->handle())) return "";
-    // as repeat_if_not_ascii: the batch is lowered in full on the device and scanned again from there; the spans then index the
-    // lowered text, whose lengths may differ from the caller's
-    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "hit spans of a batch that leaves ASCII need the device ToLower on a single device";
-    }
-    const uint8_t* d_low = nullptr;
-    const uint64_t* d_low_off = nullptr;
-    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
-    if (rc) return fail_gft(rc);
-    rc = spans_call(gpu_->handle(), d_low, d_low_off, n_docs, /*flags*/ 0, d_bitmap, d_row_idx, want, d_span_off, d_span_start, d_span_len,
-                    d_span_term, cap, total);
-    if (rc) return fail_gft(rc);
+    int low = 0;
+    err = scan_twice(d_blob, d_doc_off, n_docs, "hit spans of a batch that leaves ASCII need the device ToLower on a single device", &low,
+                     [&](const uint8_t* d_text, const uint64_t* d_off, uint32_t scan_flags, int* again) {
+                         int rc = spans_call(gpu_->handle(), d_text, d_off, n_docs, scan_flags, d_bitmap, d_row_idx, want, d_span_off, d_span_start,
+                                             d_span_len, d_span_term, cap, total);
+                         if (!rc && again) *again = scan_flags && n_docs && gft_last_nonascii(gpu_->handle());
+                         return rc;
+                     });
+    if (!err.empty() || !low) return err;
     if (lowered) *lowered = 1;
-    // the spans that were written (those below the cap) index the lowered text: back to the caller's bytes, in place
+    // the spans then index the lowered text, whose lengths may differ from the caller's; those that were written (below the cap) go
+    // back to the caller's bytes, in place
     if (source && cap) {
-        rc = gft_map_spans_limit(gpu_->handle(), d_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, cap);
+        int rc = gft_map_spans_limit(gpu_->handle(), d_blob, d_doc_off, n_docs, d_span_off, d_span_start, d_span_len, cap);
         if (rc) return fail_gft(rc);
     }
     return "";
@@ -633,16 +664,7 @@ Error Finder::ExcerptsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, u
     if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
-    // spans that index the lowered text are cut from the lowered text: lowered again here, as the spans call lowered it
-    if (spans_lowered && !source && n_docs) {
-        if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-            last_code_ = GFT_E_UNSUPPORTED;
-            return "excerpts of a lowered batch need a case-insensitive finder with the device ToLower on a single device";
-        }
-        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_text, &d_off);
-        if (rc) return fail_gft(rc);
-        if (lowered) *lowered = 1;
-    }
+    if (Error lerr = cut_from_lowered("excerpts of", spans_lowered, source, n_docs, d_text, d_off, lowered); !lerr.empty()) return lerr;
     // (the snap judges the text the excerpts are cut from)
     int rc = snap ? gft_excerpt_spans_snap_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, before, after, flags, reach,
                                                   d_out, cap_bytes, d_exc_off, d_exc_doc, d_exc_start, d_exc_span_off, cap_exc, d_span_rel, d_doc_exc_off,
@@ -662,16 +684,7 @@ Error Finder::MarkDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint6
     if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
-    // spans that index the lowered text mark the lowered text: lowered again here, as the spans call lowered it
-    if (spans_lowered && !source && n_docs) {
-        if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-            last_code_ = GFT_E_UNSUPPORTED;
-            return "marks in a lowered batch need a case-insensitive finder with the device ToLower on a single device";
-        }
-        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_text, &d_off);
-        if (rc) return fail_gft(rc);
-        if (lowered) *lowered = 1;
-    }
+    if (Error lerr = cut_from_lowered("marks in", spans_lowered, source, n_docs, d_text, d_off, lowered); !lerr.empty()) return lerr;
     int rc = gft_mark_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, open, open_len, close, close_len, flags,
                                    d_out, cap_bytes, d_out_off, d_span_new, d_doc_run_off, n_runs, total_bytes);
     return rc ? fail_gft(rc) : Error();
@@ -687,16 +700,7 @@ Error Finder::ReplaceDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, ui
     if (Error rerr = resident_refusal(); !rerr.empty()) return rerr;
     const uint8_t* d_text = d_blob;
     const uint64_t* d_off = d_doc_off;
-    // spans that index the lowered text replace in the lowered text: lowered again here, as the spans call lowered it
-    if (spans_lowered && !source && n_docs) {
-        if (caseSensitive_ || !device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-            last_code_ = GFT_E_UNSUPPORTED;
-            return "replacements in a lowered batch need a case-insensitive finder with the device ToLower on a single device";
-        }
-        int rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_text, &d_off);
-        if (rc) return fail_gft(rc);
-        if (lowered) *lowered = 1;
-    }
+    if (Error lerr = cut_from_lowered("replacements in", spans_lowered, source, n_docs, d_text, d_off, lowered); !lerr.empty()) return lerr;
     // without a term map every span asks for id 0, whatever its term
     int rc = gft_replace_spans_device(gpu_->handle(), d_text, d_off, n_docs, d_span_off, d_span_start, d_span_len, term_rep ? d_span_term : nullptr,
                                       term_rep, gft_n_terms(gpu_->handle()), rep_bytes, rep_off, n_reps, flags, d_out, cap_bytes, d_out_off,
@@ -713,26 +717,12 @@ Error Finder::TermStatsDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, 
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
-    int again = 0;
     const auto stats_call = wholeWords_ ? gft_batch_term_stats_words_device : gft_batch_term_stats_device;
-    int rc = stats_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, flags, doc_base,
-                        d_occ, d_docs, d_first, &again);
-    if (rc) return fail_gft(rc);
-    if (!again) return "";
-    // as HitSpansDevice: the batch is lowered in full on the device and scanned again from there (nothing was counted so far)
-    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "term statistics of a batch that leaves ASCII need the device ToLower on a single device";
-    }
-    const uint8_t* d_low = nullptr;
-    const uint64_t* d_low_off = nullptr;
-    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
-    if (rc) return fail_gft(rc);
-    rc = stats_call(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, flags, doc_base, d_occ, d_docs, d_first,
-                    nullptr);
-    if (rc) return fail_gft(rc);
-    if (lowered) *lowered = 1;
-    return "";
+    return scan_twice(d_blob, d_doc_off, n_docs, "term statistics of a batch that leaves ASCII need the device ToLower on a single device", lowered,
+                      [&](const uint8_t* d_text, const uint64_t* d_off, uint32_t scan_flags, int* again) {
+                          return stats_call(gpu_->handle(), d_text, d_off, n_docs, scan_flags, d_bitmap, want, flags, doc_base, d_occ, d_docs, d_first,
+                                            again);
+                      });
 }
 
 Error Finder::TopDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const uint32_t* d_bitmap, const uint32_t* want,
@@ -746,26 +736,12 @@ Error Finder::TopDevice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64
     std::vector<Record> none;
     Error err = collect(std::string(), false, none);
     if (!err.empty()) return err;
-    int again = 0;
     const auto top_call = wholeWords_ ? gft_batch_top_docs_words_device : gft_batch_top_docs_device;
-    int rc = top_call(gpu_->handle(), d_blob, d_doc_off, n_docs, caseSensitive_ ? 0 : GFT_FOLD_ASCII, d_bitmap, want, weights, flags, k, doc_base,
-                      d_score, d_top_idx, d_top_score, n_top, &again);
-    if (rc) return fail_gft(rc);
-    if (!again) return "";
-    // as TermStatsDevice: the batch is lowered in full on the device and scanned again from there (nothing was written so far)
-    if (!device_tolower_ || gft_n_devices(gpu_->handle()) != 1) {
-        last_code_ = GFT_E_UNSUPPORTED;
-        return "the ranking of a batch that leaves ASCII needs the device ToLower on a single device";
-    }
-    const uint8_t* d_low = nullptr;
-    const uint64_t* d_low_off = nullptr;
-    rc = gft_lower_owned(gpu_->handle(), d_blob, d_doc_off, n_docs, &d_low, &d_low_off);
-    if (rc) return fail_gft(rc);
-    rc = top_call(gpu_->handle(), d_low, d_low_off, n_docs, /*scan_flags*/ 0, d_bitmap, want, weights, flags, k, doc_base, d_score, d_top_idx,
-                  d_top_score, n_top, nullptr);
-    if (rc) return fail_gft(rc);
-    if (lowered) *lowered = 1;
-    return "";
+    return scan_twice(d_blob, d_doc_off, n_docs, "the ranking of a batch that leaves ASCII needs the device ToLower on a single device", lowered,
+                      [&](const uint8_t* d_text, const uint64_t* d_off, uint32_t scan_flags, int* again) {
+                          return top_call(gpu_->handle(), d_text, d_off, n_docs, scan_flags, d_bitmap, want, weights, flags, k, doc_base, d_score,
+                                          d_top_idx, d_top_score, n_top, again);
+                      });
 }
 
 Error Finder::ProcessDeviceBegin(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap) {

@@ -262,6 +262,12 @@ private:
     unsigned first_begun_ = 0, n_begun_ = 0;
     bool device_tolower_;                // GFT_DEVICE_TOLOWER (read at creation; 0: a batch that leaves ASCII is lowered on the host)
     Error repeat_if_not_ascii(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t* d_bitmap);
+    // the two repeats of the resident-batch calls (finder_host.cpp): a call that scans, run again on the lowered batch if the batch
+    // left ASCII; and a call that cuts from the text its spans index, handed the lowered batch when those are lowered spans
+    template <class Run>
+    Error scan_twice(const uint8_t* d_blob, const uint64_t* d_doc_off, uint64_t n_docs, const char* unsupported, int* lowered, Run run);
+    Error cut_from_lowered(const char* what, bool spans_lowered, bool source, uint64_t n_docs, const uint8_t*& d_text, const uint64_t*& d_off,
+                           int* lowered);
 };
 
 }  // namespace gft

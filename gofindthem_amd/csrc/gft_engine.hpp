@@ -227,26 +227,29 @@ struct gft_engine {
     // lengths and their prefix sum, the call's copies of the key map and the table, and the plan are its own
     struct ReplaceBufs { DevBuf rid, pl, ppos, key_rep, rep_off, tab, at, delta, len, roff; } d_replace;
 
-    // term statistics and column counts (gft_stats.hip): the check pass's flag words, the workgroups' bitset rows for dictionaries
-    // whose bitset leaves LDS, and the span CSR of the kept matches that gft_batch_term_stats_device counts (the starts are what
-    // gft_hit_spans_device asks for with any cap; they are not read)
-    struct StatsBufs { DevBuf ctl, rows, span_off, span_start, span_term; } d_stats;
+    // term statistics and column counts (gft_stats.hip): the check pass's flag words and the workgroups' bitset rows for
+    // dictionaries whose bitset leaves LDS
+    struct StatsBufs { DevBuf ctl, rows; } d_stats;
+
+    // the kept matches of a batch call with a hit bitmap, as a span CSR (gft_term_list.cpp): batch_term_list fills it from
+    // gft_hit_spans_device or its whole-word twin for gft_batch_term_stats_device, gft_batch_top_docs_device and their twins, whose
+    // consumers read off and term (the starts are what the spans call asks for with any cap).  It holds until the next such call.
+    struct KeptBufs { DevBuf off, start, term; } d_kept;
 
     // scores, the top list and the gather by index list (gft_rank.hip): the control block, the call's copy of the weights, the
     // workgroups' bitset rows of the distinct mode, the select's histograms, the place tiles' counts with their prefix sums and scan
-    // partials, the candidates; the gather's lengths and the compact arrays the select's copy pass searches; the scores and the span
-    // CSR of the kept matches that gft_batch_top_docs_device ranks
+    // partials, the candidates; the gather's lengths and the compact arrays the select's copy pass searches; the scores of
+    // gft_batch_top_docs_device when the caller asks for none
     struct RankBufs {
-        DevBuf ctl, weights, rows, hist, tile_gt, tile_eq, gt_pos, eq_pos, partial, cand_score, cand_idx, len, c_off, c_src, score, span_off,
-            span_start, span_term;
+        DevBuf ctl, weights, rows, hist, tile_gt, tile_eq, gt_pos, eq_pos, partial, cand_score, cand_idx, len, c_off, c_src, score;
     } d_rank;
 
     // whole-word matching (gft_words.hip): the class table (uploaded with the first call), the check pass's flag words, the marks of
     // a list's entries with their prefix sums and scan partials; the kept matches of gft_scan_words_device / gft_process_words_device
-    // (off, pos, term), the spans gft_hit_spans_words_device filters, the kept spans gft_batch_term_stats_words_device counts
+    // (off, pos, term), the spans gft_hit_spans_words_device filters (the filter's input, which its output must not overlap)
     struct WordBufs {
         bool table_up = false;
-        DevBuf tab_row, tab_bits, ctl, keep, rank, partial, off, pos, term, span_off, span_start, span_len, span_term, stat_off, stat_start, stat_term;
+        DevBuf tab_row, tab_bits, ctl, keep, rank, partial, off, pos, term, span_off, span_start, span_len, span_term;
     } d_words;
 
     // rule evaluation for records (gft_rules.hip): the installed set's shape and its arrays on the device, the leaf bitmap and
@@ -415,8 +418,9 @@ int lower_count(gft_engine* e, const uint8_t* d_text, const uint64_t* d_doc_off,
                 uint64_t* text_range = nullptr);
 
 // ---- gft_rank_api.cpp --------------------------------------------------------------------------------------------------
-// the tail of gft_batch_top_docs_device and its words twin behind their scan: the list's scores into d_score (NULL: a buffer of the
-// engine's), then the top list of those scores, the select starting at the maximum the score pass found.  who: the entry point
+// the tail of gft_batch_top_docs_device and its words twin behind batch_term_list (which has tested k and the top arrays): the
+// list's scores into d_score (NULL: a buffer of the engine's), then the top list of those scores, the select starting at the
+// maximum the score pass found.  who: the entry point
 int batch_top_tail(gft_engine* e, const char* who, const uint64_t* d_off, const uint32_t* d_term, uint64_t n_docs, uint32_t n_terms,
                    const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx,
                    uint64_t* d_top_score, uint64_t* n_top);

@@ -4,6 +4,7 @@
 #include "gft_doc_gather.hpp"
 #include "gft_rank.hpp"
 #include "gft_stats.hpp"
+#include "gft_term_list.hpp"
 
 using namespace gft;
 using namespace gft::api;
@@ -30,21 +31,13 @@ int score_run(gft_engine* e, const char* who, const uint64_t* d_off, const uint3
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
     SyncOnExit drain(e);                                            // (the weights and words of this frame are handed to asynchronous copies)
-    uint64_t ends[2] = {0, 0};
-    if (n_docs) {
-        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, 8, hipMemcpyDeviceToHost, st), "list offsets");
-        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n_docs, 8, hipMemcpyDeviceToHost, st), "list offsets");
-        HIP_TRY(hipStreamSynchronize(st), "list offsets");
-    }
-    if (ends[1] < ends[0]) return fail(e, GFT_E_INVALID, std::string(who) + ": offsets descend (nothing was written)");
-    const uint64_t n = ends[1] - ends[0];
-    if (n > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(who) + ": a size beyond the address space");
-    if (n && !d_term) return fail(e, GFT_E_INVALID, "null argument");
-    if (n && !n_terms) return fail(e, GFT_E_INVALID, std::string(who) + ": entries but no terms");
-    if (score_buffers_overlap(d_off, n_docs, d_term, ends[0], n, d_score)) return fail(e, GFT_E_INVALID, std::string(who) + ": the scores overlap an input");
+    ListEnds L{};
+    if ((rc = list_head(e, who, d_off, d_term, n_docs, n_terms, L))) return rc;
+    const uint64_t n = L.n;
+    if (score_buffers_overlap(d_off, n_docs, d_term, L.e0, n, d_score)) return fail(e, GFT_E_INVALID, std::string(who) + ": the scores overlap an input");
     auto& R = e->d_rank;
     ScoreParams P{};
-    P.off = d_off; P.term = d_term; P.n_docs = n_docs; P.e0 = ends[0]; P.n = n; P.n_terms = n_terms;
+    P.off = d_off; P.term = d_term; P.n_docs = n_docs; P.e0 = L.e0; P.n = n; P.n_terms = n_terms;
     P.distinct = flags & GFT_SCORE_DISTINCT; P.score = d_score;
     P.grid = (uint32_t)stats_grid(n, n_docs, score_resident(e->n_cus));
     if ((rc = room(e, R.ctl, kRankCtlWords * 8, kRankRoom))) return rc;
@@ -61,12 +54,7 @@ int score_run(gft_engine* e, const char* who, const uint64_t* d_off, const uint3
         HIP_TRY(hipMemsetAsync(P.rows, 0, bytes, st), "score bitset rows");
     }
     HIP_TRY(hipMemsetAsync(P.ctl, 0, kRankCtlWords * 8, st), "score control block");
-    {
-        ProfScope ps(e, "score_check");
-        StatsParams C{};                                            // (only what the check reads is set)
-        C.off = d_off; C.term = d_term; C.n_docs = n_docs; C.e0 = ends[0]; C.n = n; C.n_terms = n_terms; C.ctl = P.ctl;
-        HIP_TRY(launch_stats_check(C, e->n_cus, st), "score check kernel launch");
-    }
+    if ((rc = list_check_launch(e, "score", d_off, d_term, n_docs, L, n_terms, P.ctl))) return rc;
     {
         ProfScope ps(e, "score_docs");
         HIP_TRY(launch_score_docs(P, st), "score kernel launch");
@@ -74,8 +62,7 @@ int score_run(gft_engine* e, const char* who, const uint64_t* d_off, const uint3
     uint64_t h_ctl[kRankCtlWords] = {0};
     HIP_TRY(hipMemcpyAsync(h_ctl, P.ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st), "score flags");
     HIP_TRY(hipStreamSynchronize(st), "score flags");
-    if (h_ctl[kStatsCtlOffs]) return fail(e, GFT_E_INVALID, std::string(who) + ": offsets descend (nothing was written)");
-    if (h_ctl[kStatsCtlTerms]) return fail(e, GFT_E_INVALID, std::string(who) + ": a term id that is no index of the weights (nothing was written)");
+    if ((rc = list_check_verdict(e, who, h_ctl, "the weights"))) return rc;
     if (max_out) *max_out = h_ctl[kRankCtlMax];
     return GFT_OK;
 }
@@ -157,8 +144,6 @@ namespace gft::api {
 int batch_top_tail(gft_engine* e, const char* who, const uint64_t* d_off, const uint32_t* d_term, uint64_t n_docs, uint32_t n_terms,
                    const uint32_t* weights, uint32_t flags, uint32_t k, uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx,
                    uint64_t* d_top_score, uint64_t* n_top) {
-    if (k > kRankMaxK) return fail(e, GFT_E_INVALID, std::string(who) + ": k above 4096");   // (before the scores are written)
-    if (k && (!d_top_idx || !d_top_score)) return fail(e, GFT_E_INVALID, "null argument");
     int rc;
     if (!d_score && n_docs) {
         DeviceGuard g(e->device);
@@ -168,7 +153,7 @@ int batch_top_tail(gft_engine* e, const char* who, const uint64_t* d_off, const 
     if (top_buffers_overlap(d_score, n_docs, k, d_top_idx, d_top_score))
         return fail(e, GFT_E_INVALID, std::string(who) + ": an output overlaps the scores or the other output");
     uint64_t mx = 0;
-    if ((rc = score_run(e, who, n_docs ? d_off : nullptr, d_term, n_docs, n_terms, weights, flags, d_score, &mx))) return rc;
+    if ((rc = score_run(e, who, d_off, d_term, n_docs, n_terms, weights, flags, d_score, &mx))) return rc;
     return top_run(e, who, d_score, n_docs, k, doc_base, d_top_idx, d_top_score, n_top, &mx);
 }
 
@@ -244,46 +229,15 @@ int gft_batch_top_docs_device(gft_engine* e, const uint8_t* d_text_blob, const u
                               int* nonascii) try {
     if (!e) return GFT_E_INVALID;
     GFT_LOCK(e);
-    if (nonascii) *nonascii = 0;
     if (n_top) *n_top = 0;
-    if (flags & ~GFT_SCORE_DISTINCT) return fail(e, GFT_E_INVALID, std::string(kWhoBatch) + ": unknown flag bits");
-    if (scan_flags & ~GFT_FOLD_ASCII) return fail(e, GFT_E_INVALID, std::string(kWhoBatch) + ": scan_flags is GFT_FOLD_ASCII or 0");
-    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, std::string(kWhoBatch) + ": single-device handles only");
-    const uint32_t n_terms = gft_n_terms(e);
-    const uint64_t* off = nullptr;
-    const uint32_t* term = nullptr;
-    int rc;
-    if (d_hit_bitmap) {
-        // the kept matches: counted, then filled into buffers of the engine's (the offsets are complete after the first call)
-        auto& S = e->d_rank;
-        uint64_t total = 0;
-        {
-            DeviceGuard g(e->device);
-            if ((rc = room(e, S.span_off, (n_docs + 1) * 8, kRankRoom))) return rc;
-        }
-        if ((rc = gft_hit_spans_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.span_off.as<uint64_t>(), nullptr,
-                                       nullptr, nullptr, 0, &total)))
-            return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        if (total) {
-            {
-                DeviceGuard g(e->device);
-                if ((rc = room(e, S.span_term, total * 4, kRankRoom)) || (rc = room(e, S.span_start, total * 4, kRankRoom))) return rc;
-            }
-            if ((rc = gft_hit_spans_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.span_off.as<uint64_t>(),
-                                           S.span_start.as<uint32_t>(), nullptr, S.span_term.as<uint32_t>(), total, &total)))
-                return rc;
-        }
-        off = S.span_off.as<uint64_t>();
-        term = S.span_term.as<uint32_t>();
-    } else {
-        gft_matches m{};
-        if ((rc = gft_scan_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, &m))) return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        off = m.match_off;
-        term = m.term_id;
-    }
-    return batch_top_tail(e, kWhoBatch, off, term, n_docs, n_terms, weights, flags, k, doc_base, d_score, d_top_idx, d_top_score, n_top);
+    BatchList A{};
+    A.who = kWhoBatch; A.d_text = d_text_blob; A.d_doc_off = d_doc_off; A.n_docs = n_docs; A.scan_flags = scan_flags;
+    A.d_hit_bitmap = d_hit_bitmap; A.want = want; A.flags = flags; A.known_flags = GFT_SCORE_DISTINCT; A.room = kRankRoom;
+    A.top = true; A.k = k; A.d_top_idx = d_top_idx; A.d_top_score = d_top_score;
+    TermList T{};
+    int rc = batch_term_list(e, A, T, nonascii);
+    if (rc || (nonascii && *nonascii)) return rc;
+    return batch_top_tail(e, kWhoBatch, T.off, T.term, n_docs, gft_n_terms(e), weights, flags, k, doc_base, d_score, d_top_idx, d_top_score, n_top);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_score_docs(const uint64_t* off, const uint32_t* term, uint64_t n_docs, uint32_t n_terms, const uint32_t* weights, uint32_t flags,

@@ -3,6 +3,7 @@
 // gft_debug_count_columns.
 #include "gft_engine.hpp"
 #include "gft_stats.hpp"
+#include "gft_term_list.hpp"
 
 using namespace gft;
 using namespace gft::api;
@@ -29,22 +30,14 @@ int gft_term_stats_device(gft_engine* e, const uint64_t* d_off, const uint32_t* 
     DeviceGuard g(e->device);
     hipStream_t st = e->stream;
     SyncOnExit drain(e);                                            // (words of this frame are handed to asynchronous copies)
-    uint64_t ends[2] = {0, 0};
-    if (n_docs) {
-        HIP_TRY(hipMemcpyAsync(&ends[0], d_off, 8, hipMemcpyDeviceToHost, st), "list offsets");
-        HIP_TRY(hipMemcpyAsync(&ends[1], d_off + n_docs, 8, hipMemcpyDeviceToHost, st), "list offsets");
-        HIP_TRY(hipStreamSynchronize(st), "list offsets");
-    }
-    if (ends[1] < ends[0]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": offsets descend (nothing was written)");
-    const uint64_t n = ends[1] - ends[0];
-    if (n > (~0ull >> 4)) return fail(e, GFT_E_INVALID, std::string(kWho) + ": a size beyond the address space");
-    if (n && !d_term) return fail(e, GFT_E_INVALID, "null argument");
-    if (n && !n_terms) return fail(e, GFT_E_INVALID, std::string(kWho) + ": entries but no terms");
-    if (stats_buffers_overlap(d_off, n_docs, d_term, ends[0], n, n_terms, d_occ, d_docs, d_first))
+    ListEnds L{};
+    if ((rc = list_head(e, kWho, d_off, d_term, n_docs, n_terms, L))) return rc;
+    const uint64_t n = L.n;
+    if (stats_buffers_overlap(d_off, n_docs, d_term, L.e0, n, n_terms, d_occ, d_docs, d_first))
         return fail(e, GFT_E_INVALID, std::string(kWho) + ": an output overlaps an input or another output");
     auto& S = e->d_stats;
     StatsParams P{};
-    P.off = d_off; P.term = d_term; P.n_docs = n_docs; P.e0 = ends[0]; P.n = n; P.n_terms = n_terms;
+    P.off = d_off; P.term = d_term; P.n_docs = n_docs; P.e0 = L.e0; P.n = n; P.n_terms = n_terms;
     P.accumulate = flags & GFT_STATS_ACCUMULATE; P.doc_base = doc_base;
     P.occ = d_occ; P.docs = d_docs; P.first = d_first;
     P.grid = (uint32_t)stats_grid(n, n_docs, stats_resident(e->n_cus));
@@ -58,10 +51,7 @@ int gft_term_stats_device(gft_engine* e, const uint64_t* d_off, const uint32_t* 
         HIP_TRY(hipMemsetAsync(P.rows, 0, bytes, st), "stats bitset rows");
     }
     HIP_TRY(hipMemsetAsync(P.ctl, 0, kStatsCtlWords * 8, st), "stats control block");
-    {
-        ProfScope ps(e, "stats_check");
-        HIP_TRY(launch_stats_check(P, e->n_cus, st), "stats check kernel launch");
-    }
+    if ((rc = list_check_launch(e, "stats", d_off, d_term, n_docs, L, n_terms, P.ctl))) return rc;
     if (any_out) {
         ProfScope ps(e, "stats_count");
         if (!P.accumulate) HIP_TRY(launch_stats_init(P, st), "stats init kernel launch");
@@ -70,9 +60,7 @@ int gft_term_stats_device(gft_engine* e, const uint64_t* d_off, const uint32_t* 
     uint64_t h_ctl[kStatsCtlWords] = {0, 0};
     HIP_TRY(hipMemcpyAsync(h_ctl, P.ctl, sizeof h_ctl, hipMemcpyDeviceToHost, st), "stats flags");
     HIP_TRY(hipStreamSynchronize(st), "stats flags");
-    if (h_ctl[kStatsCtlOffs]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": offsets descend (nothing was written)");
-    if (h_ctl[kStatsCtlTerms]) return fail(e, GFT_E_INVALID, std::string(kWho) + ": a term id that is no index of the counters (nothing was written)");
-    return GFT_OK;
+    return list_check_verdict(e, kWho, h_ctl, "the counters");
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_count_columns_device(gft_engine* e, const uint32_t* d_bitmap, uint64_t n_rows, uint32_t n_cols, const uint64_t* d_row_idx, uint32_t flags,
@@ -105,45 +93,13 @@ int gft_batch_term_stats_device(gft_engine* e, const uint8_t* d_text_blob, const
                                 uint64_t* d_docs, uint64_t* d_first, int* nonascii) try {
     if (!e) return GFT_E_INVALID;
     GFT_LOCK(e);
-    if (nonascii) *nonascii = 0;
-    if (flags & ~GFT_STATS_ACCUMULATE) return fail(e, GFT_E_INVALID, std::string(kWhoBatch) + ": unknown flag bits");
-    if (scan_flags & ~GFT_FOLD_ASCII) return fail(e, GFT_E_INVALID, std::string(kWhoBatch) + ": scan_flags is GFT_FOLD_ASCII or 0");
-    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, std::string(kWhoBatch) + ": single-device handles only");
-    const uint32_t n_terms = gft_n_terms(e);
-    const uint64_t* off = nullptr;
-    const uint32_t* term = nullptr;
-    int rc;
-    if (d_hit_bitmap) {
-        // the kept matches: counted, then filled into buffers of the engine's (the offsets are complete after the first call)
-        auto& S = e->d_stats;
-        uint64_t total = 0;
-        {
-            DeviceGuard g(e->device);
-            if ((rc = room(e, S.span_off, (n_docs + 1) * 8, kStatsRoom))) return rc;
-        }
-        if ((rc = gft_hit_spans_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.span_off.as<uint64_t>(), nullptr,
-                                       nullptr, nullptr, 0, &total)))
-            return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        if (total) {
-            {
-                DeviceGuard g(e->device);
-                if ((rc = room(e, S.span_term, total * 4, kStatsRoom)) || (rc = room(e, S.span_start, total * 4, kStatsRoom))) return rc;
-            }
-            if ((rc = gft_hit_spans_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.span_off.as<uint64_t>(),
-                                           S.span_start.as<uint32_t>(), nullptr, S.span_term.as<uint32_t>(), total, &total)))
-                return rc;
-        }
-        off = S.span_off.as<uint64_t>();
-        term = S.span_term.as<uint32_t>();
-    } else {
-        gft_matches m{};
-        if ((rc = gft_scan_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, &m))) return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        off = m.match_off;
-        term = m.term_id;
-    }
-    return gft_term_stats_device(e, n_docs ? off : nullptr, term, n_docs, n_terms, flags, doc_base, d_occ, d_docs, d_first);
+    BatchList A{};
+    A.who = kWhoBatch; A.d_text = d_text_blob; A.d_doc_off = d_doc_off; A.n_docs = n_docs; A.scan_flags = scan_flags;
+    A.d_hit_bitmap = d_hit_bitmap; A.want = want; A.flags = flags; A.known_flags = GFT_STATS_ACCUMULATE; A.room = kStatsRoom;
+    TermList T{};
+    int rc = batch_term_list(e, A, T, nonascii);
+    if (rc || (nonascii && *nonascii)) return rc;
+    return gft_term_stats_device(e, T.off, T.term, n_docs, gft_n_terms(e), flags, doc_base, d_occ, d_docs, d_first);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_term_stats(const uint64_t* off, const uint32_t* term, uint64_t n_docs, uint32_t n_terms, uint32_t flags, uint64_t doc_base,

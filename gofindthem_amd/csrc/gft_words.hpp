@@ -9,6 +9,9 @@
 
 namespace gft {
 
+// entries and documents of one filter call: the place pass's grid stays below 2^31
+constexpr uint64_t kWordsMax = 1ull << 38;
+
 // the class table of unicode_word.inc in host memory, and its size in rows of 256 bits
 const WordTable& word_table_host();
 uint32_t word_table_rows();

@@ -2,6 +2,7 @@
 // gft_scan_words_device, gft_process_words_device / gft_process_words, gft_hit_spans_words_device,
 // gft_batch_term_stats_words_device, gft_batch_top_docs_words_device -- and the host walk behind gft_debug_filter_word_matches.
 #include "gft_engine.hpp"
+#include "gft_term_list.hpp"
 #include "gft_words.hpp"
 
 using namespace gft;
@@ -15,7 +16,6 @@ const char kWhoProcess[] = "gft_process_words_device";
 const char kWhoSpans[] = "gft_hit_spans_words_device";
 const char kWhoStats[] = "gft_batch_term_stats_words_device";
 const char kWhoTop[] = "gft_batch_top_docs_words_device";
-constexpr uint64_t kWordsMax = 1ull << 38;                          // entries and documents: the place pass's grid stays below 2^31
 }  // namespace
 
 // the class table on the device: uploaded by the first call of a handle (the excerpt's word snap asks for it too)
@@ -289,45 +289,13 @@ int gft_batch_term_stats_words_device(gft_engine* e, const uint8_t* d_text_blob,
                                       uint64_t* d_docs, uint64_t* d_first, int* nonascii) try {
     if (!e) return GFT_E_INVALID;
     GFT_LOCK(e);
-    if (nonascii) *nonascii = 0;
-    if (flags & ~GFT_STATS_ACCUMULATE) return fail(e, GFT_E_INVALID, std::string(kWhoStats) + ": unknown flag bits");
-    if (scan_flags & ~GFT_FOLD_ASCII) return fail(e, GFT_E_INVALID, std::string(kWhoStats) + ": scan_flags is GFT_FOLD_ASCII or 0");
-    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, std::string(kWhoStats) + ": single-device handles only");
-    const uint32_t n_terms = gft_n_terms(e);
-    const uint64_t* off = nullptr;
-    const uint32_t* term = nullptr;
-    int rc;
-    if (d_hit_bitmap) {
-        // the kept whole-word matches, counted and then filled into buffers of the engine's
-        auto& S = e->d_words;
-        uint64_t total = 0;
-        {
-            DeviceGuard g(e->device);
-            if (e->device >= 0 && (rc = room(e, S.stat_off, (n_docs + 1) * 8, kWordsRoom))) return rc;
-        }
-        if ((rc = gft_hit_spans_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.stat_off.as<uint64_t>(),
-                                             nullptr, nullptr, nullptr, 0, &total)))
-            return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        if (total) {
-            {
-                DeviceGuard g(e->device);
-                if ((rc = room(e, S.stat_term, total * 4, kWordsRoom)) || (rc = room(e, S.stat_start, total * 4, kWordsRoom))) return rc;
-            }
-            if ((rc = gft_hit_spans_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.stat_off.as<uint64_t>(),
-                                                 S.stat_start.as<uint32_t>(), nullptr, S.stat_term.as<uint32_t>(), total, &total)))
-                return rc;
-        }
-        off = S.stat_off.as<uint64_t>();
-        term = S.stat_term.as<uint32_t>();
-    } else {
-        gft_matches m{};
-        if ((rc = gft_scan_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, &m))) return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        off = m.match_off;
-        term = m.term_id;
-    }
-    return gft_term_stats_device(e, n_docs ? off : nullptr, term, n_docs, n_terms, flags, doc_base, d_occ, d_docs, d_first);
+    BatchList A{};
+    A.who = kWhoStats; A.words = true; A.d_text = d_text_blob; A.d_doc_off = d_doc_off; A.n_docs = n_docs; A.scan_flags = scan_flags;
+    A.d_hit_bitmap = d_hit_bitmap; A.want = want; A.flags = flags; A.known_flags = GFT_STATS_ACCUMULATE; A.room = kWordsRoom;
+    TermList T{};
+    int rc = batch_term_list(e, A, T, nonascii);
+    if (rc || (nonascii && *nonascii)) return rc;
+    return gft_term_stats_device(e, T.off, T.term, n_docs, gft_n_terms(e), flags, doc_base, d_occ, d_docs, d_first);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_batch_top_docs_words_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
@@ -336,46 +304,15 @@ int gft_batch_top_docs_words_device(gft_engine* e, const uint8_t* d_text_blob, c
                                     int* nonascii) try {
     if (!e) return GFT_E_INVALID;
     GFT_LOCK(e);
-    if (nonascii) *nonascii = 0;
     if (n_top) *n_top = 0;
-    if (flags & ~GFT_SCORE_DISTINCT) return fail(e, GFT_E_INVALID, std::string(kWhoTop) + ": unknown flag bits");
-    if (scan_flags & ~GFT_FOLD_ASCII) return fail(e, GFT_E_INVALID, std::string(kWhoTop) + ": scan_flags is GFT_FOLD_ASCII or 0");
-    if (!e->peers.empty()) return fail(e, GFT_E_UNSUPPORTED, std::string(kWhoTop) + ": single-device handles only");
-    const uint32_t n_terms = gft_n_terms(e);
-    const uint64_t* off = nullptr;
-    const uint32_t* term = nullptr;
-    int rc;
-    if (d_hit_bitmap) {
-        // the kept whole-word matches, counted and then filled into the buffers the statistics' twin fills
-        auto& S = e->d_words;
-        uint64_t total = 0;
-        {
-            DeviceGuard g(e->device);
-            if (e->device >= 0 && (rc = room(e, S.stat_off, (n_docs + 1) * 8, kWordsRoom))) return rc;
-        }
-        if ((rc = gft_hit_spans_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.stat_off.as<uint64_t>(),
-                                             nullptr, nullptr, nullptr, 0, &total)))
-            return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        if (total) {
-            {
-                DeviceGuard g(e->device);
-                if ((rc = room(e, S.stat_term, total * 4, kWordsRoom)) || (rc = room(e, S.stat_start, total * 4, kWordsRoom))) return rc;
-            }
-            if ((rc = gft_hit_spans_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, d_hit_bitmap, nullptr, want, S.stat_off.as<uint64_t>(),
-                                                 S.stat_start.as<uint32_t>(), nullptr, S.stat_term.as<uint32_t>(), total, &total)))
-                return rc;
-        }
-        off = S.stat_off.as<uint64_t>();
-        term = S.stat_term.as<uint32_t>();
-    } else {
-        gft_matches m{};
-        if ((rc = gft_scan_words_device(e, d_text_blob, d_doc_off, n_docs, scan_flags, &m))) return rc;
-        if (nonascii && (scan_flags & GFT_FOLD_ASCII) && n_docs && gft_last_nonascii(e)) { *nonascii = 1; return GFT_OK; }
-        off = m.match_off;
-        term = m.term_id;
-    }
-    return batch_top_tail(e, kWhoTop, off, term, n_docs, n_terms, weights, flags, k, doc_base, d_score, d_top_idx, d_top_score, n_top);
+    BatchList A{};
+    A.who = kWhoTop; A.words = true; A.d_text = d_text_blob; A.d_doc_off = d_doc_off; A.n_docs = n_docs; A.scan_flags = scan_flags;
+    A.d_hit_bitmap = d_hit_bitmap; A.want = want; A.flags = flags; A.known_flags = GFT_SCORE_DISTINCT; A.room = kWordsRoom;
+    A.top = true; A.k = k; A.d_top_idx = d_top_idx; A.d_top_score = d_top_score;
+    TermList T{};
+    int rc = batch_term_list(e, A, T, nonascii);
+    if (rc || (nonascii && *nonascii)) return rc;
+    return batch_top_tail(e, kWhoTop, T.off, T.term, n_docs, gft_n_terms(e), weights, flags, k, doc_base, d_score, d_top_idx, d_top_score, n_top);
 } GFT_CATCH((e ? &e->err : nullptr))
 
 int gft_debug_filter_word_matches(const uint8_t* text, const uint64_t* doc_off, uint64_t n_docs, const uint64_t* off, const uint32_t* pos,

@@ -832,6 +832,26 @@ class Finder:
         return np.diff(bucket_doc), np.diff(bucket_byte)
 
     # -- how often each keyword hit, and where (csrc/gft_stats.hip) ------------------------------------------------------------
+    def _want_words(self, want):
+        """want (None: every expression) as the mask words TermStatsDevice and TopDevice hand on: those of want_mask() among them"""
+        return None if want is None else np.ascontiguousarray(self.want_mask() & np.ascontiguousarray(want, dtype=np.uint32))
+
+    def _list_lines(self, data, kept, what, check=None):
+        """the opening of TermStatsLines and TopLines: the blob resident and split into lines -> (buf, off, bm), bm the rows
+        ProcessLinesDevice left (kept) or None (every occurrence); None when nothing can occur: no dictionary, or kept and no lines.
+        what: the noun of the refusal off the device route; check: what the caller has to refuse in front of the upload"""
+        if not self._takes_device_route():
+            raise FinderError(_lib.GFT_E_UNSUPPORTED, what + " the device route: the GPU substring engine, no regex terms, one device")
+        if not self.n_expressions:                                   # (no dictionary: nothing can occur)
+            return None
+        if check:
+            check()
+        buf = self._resident(data)
+        if not kept:
+            return buf, self.SplitLinesDevice(buf, len(data), 0), None
+        off, bm = self.ProcessLinesDevice(buf, len(data))
+        return (buf, off, bm) if bm.numel() else None                # (no lines)
+
     def TermStatsDevice(self, text, doc_off, bitmap=None, want=None, accumulate_into=None, doc_base=0):
         """the keyword statistics of a resident batch (gft_finder_term_stats_device).  text, doc_off as for ProcessDevice; bitmap: the
         rows ProcessDevice left -- the statistics are those of the KEPT matches, the witness occurrences of true, wanted expressions
@@ -843,9 +863,7 @@ class Finder:
         import torch
         n = int(doc_off.numel()) - 1
         lowered = C.c_int(0)
-        w = None
-        if want is not None:
-            w = np.ascontiguousarray(self.want_mask() & np.ascontiguousarray(want, dtype=np.uint32))
+        w = self._want_words(want)
         # (the dictionary is built by the first call that scans: n_terms is known only then -- a count-free call builds it)
         self._check(self._L.gft_finder_term_stats_device(self._h, text.data_ptr(), doc_off.data_ptr(), 0, None, None, 0, 0, None, None, None,
                                                          C.byref(lowered)))
@@ -868,18 +886,10 @@ class Finder:
         occurred, keyed by the dictionary's text of the term (bytes, as gft_term gives it).  kept=True: the occurrences that are
         witnesses of a true, wanted expression (want: want_mask(), None: any) -- what SpansLines lists; kept=False: every occurrence
         of every keyword.  One upload; only the counters come down.  lowered as SpansLines returns it.  Device route only"""
-        if not self._takes_device_route():
-            raise FinderError(_lib.GFT_E_UNSUPPORTED, "term statistics need the device route: the GPU substring engine, no regex terms, one device")
-        if not self.n_expressions:                                   # (no dictionary: nothing can occur)
+        lines = self._list_lines(bytes(data), kept, "term statistics need")
+        if lines is None:
             return {}, False
-        data = bytes(data)
-        buf = self._resident(data)
-        if kept:
-            off, bm = self.ProcessLinesDevice(buf, len(data))
-            if not bm.numel():                                       # (no lines)
-                return {}, False
-        else:
-            off, bm = self.SplitLinesDevice(buf, len(data), 0), None
+        buf, off, bm = lines
         occ, docs, first, lowered = self.TermStatsDevice(buf, off, bm, want if kept else None)
         occ, docs, first = (a.cpu().numpy() for a in (occ, docs, first))
         out = {}
@@ -901,9 +911,7 @@ class Finder:
         import torch
         n = int(doc_off.numel()) - 1
         lowered, n_top = C.c_int(0), C.c_uint64(0)
-        w = None
-        if want is not None:
-            w = np.ascontiguousarray(self.want_mask() & np.ascontiguousarray(want, dtype=np.uint32))
+        w = self._want_words(want)
         wt = None
         if weights is not None:
             self.ForceBuild()
@@ -928,25 +936,20 @@ class Finder:
         the weight of the keywords it does not name, 1 without it; 0 mutes a keyword; a keyword the finder's dictionary does not hold
         is a ValueError.  One upload; the k lines come down through gft_gather_docs_device, from the caller's own bytes even when the
         batch was lowered (lowered True), each with its newline.  Device route only"""
-        if not self._takes_device_route():
-            raise FinderError(_lib.GFT_E_UNSUPPORTED, "the top lines need the device route: the GPU substring engine, no regex terms, one device")
-        if not self.n_expressions:                                   # (no dictionary: nothing can occur)
-            return [], False
-        data = bytes(data)
         wt = None
-        if weights is not None:
-            terms = self._engine_terms()
-            wt = np.full(len(terms), int(weights.get(None, 1)), dtype=np.uint32)
-            for kw, v in weights.items():
-                if kw is not None:
-                    wt[self._term_of(terms, kw, "TopLines")] = int(v)
-        buf = self._resident(data)
-        if kept:
-            off, bm = self.ProcessLinesDevice(buf, len(data))
-            if not bm.numel():                                       # (no lines)
-                return [], False
-        else:
-            off, bm = self.SplitLinesDevice(buf, len(data), 0), None
+
+        def weigh():
+            nonlocal wt
+            if weights is not None:
+                terms = self._engine_terms()
+                wt = np.full(len(terms), int(weights.get(None, 1)), dtype=np.uint32)
+                for kw, v in weights.items():
+                    if kw is not None:
+                        wt[self._term_of(terms, kw, "TopLines")] = int(v)
+        lines = self._list_lines(bytes(data), kept, "the top lines need", weigh)
+        if lines is None:
+            return [], False
+        buf, off, bm = lines
         idx, val, _, lowered = self.TopDevice(buf, off, bm, want if kept else None, k, wt, distinct)
         m = int(idx.numel())
         if not m:

@@ -831,7 +831,14 @@ int gft_count_columns_device(gft_engine* e, const uint32_t* d_bitmap, uint64_t n
  * match -- gft_scan_device's canonical CSR.  scan_flags: GFT_FOLD_ASCII or 0; n_terms is gft_n_terms.  It counts as a scan.
  * nonascii (nullable): set to 1, with NOTHING counted, when the scan folded and the batch was not fold-safe (gft_last_nonascii):
  * the caller lowers the batch and calls again -- an accumulating array never sees a batch twice.  With nonascii == NULL such a
- * batch is counted as scanned. */
+ * batch is counted as scanned.
+ * This call, gft_batch_top_docs_device and their whole-word twins refuse in one order, each under the name of the entry point that
+ * was called, before anything is allocated or scanned: a null d_text_blob or d_doc_off with n_docs != 0 ("null argument"); unknown
+ * bits in flags, then in scan_flags; for the top calls k above 4096, then k != 0 without both top arrays; a handle over several
+ * devices (GFT_E_UNSUPPORTED); a handle without a device (GFT_E_HIP, "no HIP device available"); an n_docs beyond the address
+ * space (2^60 or more; above 2^38 for the twins: "a size beyond the address space").  What the list's source and its consumer
+ * refuse behind that -- a handle that is not built, batches in flight, the overlaps, the list's own faults -- they say in their
+ * own words, as when called directly. */
 int gft_batch_term_stats_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
                                 const uint32_t* d_hit_bitmap, const uint32_t* want, uint32_t flags, uint64_t doc_base, uint64_t* d_occ,
                                 uint64_t* d_docs, uint64_t* d_first, int* nonascii);
@@ -900,7 +907,9 @@ int gft_gather_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint
 /* Scores and top list of a resident batch in one call, as gft_batch_term_stats_device counts one: with d_hit_bitmap the KEPT matches
  * score (gft_hit_spans_device in count-then-fill form into buffers of the engine's), with NULL every dictionary match.  weights:
  * host, gft_n_terms words, or NULL.  d_score [n_docs] is nullable when only the list is wanted.  The select starts at the maximum
- * the score pass found.  nonascii as there: set to 1 with NOTHING written when the scan folded and the batch was not fold-safe. */
+ * the score pass found.  nonascii as there: set to 1 with NOTHING written when the scan folded and the batch was not fold-safe.
+ * The refusals in front of the scan and their order are written down there: k above 4096 and a missing top array are among them,
+ * so no scan runs for a call that asks for them. */
 int gft_batch_top_docs_device(gft_engine* e, const uint8_t* d_text_blob, const uint64_t* d_doc_off, uint64_t n_docs, uint32_t scan_flags,
                               const uint32_t* d_hit_bitmap, const uint32_t* want, const uint32_t* weights, uint32_t flags, uint32_t k,
                               uint64_t doc_base, uint64_t* d_score, uint64_t* d_top_idx, uint64_t* d_top_score, uint64_t* n_top,
