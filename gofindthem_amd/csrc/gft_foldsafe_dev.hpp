@@ -9,7 +9,8 @@
 // which is idle until the filter is done; fold_jobs_begin / fold_jobs_finish then take them 64 at a time, one piece per lane.  Documents are
 // judged one by one, as strings.ToLower sees them: a continuation byte at a document's start has no lead, a lead byte at a
 // document's end has no continuation (a unit in the middle of a document looks at the bytes of its neighbours).
-// Included inside namespace gft { namespace { ... } } of a scan kernel's .hip file.
+// Included inside namespace gft { namespace { ... } } of a scan kernel's .hip file, after gft_wave_dev.hpp (lane_id, wave_rank,
+// wave_lds_fence).
 #pragma once
 
 struct __attribute__((packed, aligned(1))) FoldPiece { uint32_t x, y, z, w; };
@@ -58,7 +59,7 @@ __device__ __forceinline__ void fold_job_push(bool high, uint32_t rel, uint16_t*
     const uint64_t m = __ballot(high);
     if (!m) return;
     if (high) {
-        const uint32_t idx = n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        const uint32_t idx = n + wave_rank(m);
         if (idx < cap) jobs[idx] = (uint16_t)rel;
     }
     n += (uint32_t)__popcll(m);
@@ -70,11 +71,9 @@ __device__ __forceinline__ void fold_job_push(bool high, uint32_t rel, uint16_t*
 // Returns: a piece broke the rule
 __device__ __forceinline__ bool fold_jobs_begin(const uint8_t* text, uint64_t doc_end, uint64_t unit_abs, uint32_t own, bool doc_start,
                                                 const uint16_t* jobs, uint32_t n, FOLD_JOB_REFS) {
-    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lane = lane_id();
     bool bad = false;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     for (uint32_t i0 = 0; i0 < n; i0 += 64) {
         if (i0) bad |= fold_piece_unsafe(w0, w1, w2, w3, jprev, jnext, jlim);
         const bool on = i0 + lane < n;

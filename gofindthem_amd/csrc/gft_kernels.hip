@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -18,9 +19,8 @@ namespace {
 
 constexpr uint32_t kLane = 64;
 
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+// inclusive prefix sum over the 64 lanes with __shfl_up (the DPP form, wave_incl_scan, is gft_wave_dev.hpp's)
+__device__ __forceinline__ uint32_t wave_incl_scan_shfl(uint32_t v) {
     const uint32_t l = lane_id();
 #pragma unroll
     for (int s = 1; s < 64; s <<= 1) {
@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(kScanBlockThreads) k_scan_units(const ScanPara
 
         uint32_t cnt = 0;
         if (active) cnt = walk_chunk<false>(P, buf, cls_lds, delta_lds, seg_lo, walk_from, my_lo, my_hi, 0);
-        const uint32_t incl = wave_incl_scan(cnt);
+        const uint32_t incl = wave_incl_scan_shfl(cnt);
         const uint32_t total = __shfl(incl, 63, 64);
         uint64_t base = 0;
         if (lane == 0) {
@@ -343,9 +343,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const Unit* __restrict__ 
             while ((own >> shift) > kSortBins) shift++;
             uint32_t t[kPer], p[kPer], k[kPer], bin[kPer], slot[kPer];
             for (uint32_t i = lane; i < kSortBins; i += kLane) bcnt[i] = 0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
 #pragma unroll
             for (uint32_t q = 0; q < kPer; q++) {
                 const uint32_t i = lane + q * kLane;
@@ -357,9 +355,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const Unit* __restrict__ 
                     slot[q] = atomicAdd(&bcnt[bin[q]], 1u);              // arrival order inside the bin
                 }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             // exclusive prefix sum over the bins: four consecutive bins per lane, a wave scan over the lane sums
             constexpr uint32_t kBinsPerLane = kSortBins / kLane;
             uint32_t c[kBinsPerLane], mine = 0, cmax = 0;
@@ -369,13 +365,11 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const Unit* __restrict__ 
                 mine += c[j];
                 cmax = c[j] > cmax ? c[j] : cmax;
             }
-            uint32_t run = wave_incl_scan(mine) - mine;
+            uint32_t run = wave_incl_scan_shfl(mine) - mine;
 #pragma unroll
             for (uint32_t j = 0; j < kBinsPerLane; j++) { bstart[lane * kBinsPerLane + j] = run; run += c[j]; }
             for (int sh = 32; sh; sh >>= 1) { const uint32_t o = __shfl_xor(cmax, sh, 64); cmax = o > cmax ? o : cmax; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             uint32_t base[kPer], cnt_b[kPer], rank[kPer];
 #pragma unroll
             for (uint32_t q = 0; q < kPer; q++) {
@@ -384,9 +378,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const Unit* __restrict__ 
                 rank[q] = 0;
                 if (lane + q * kLane < n) keys[base[q] + slot[q]] = k[q];       // keys grouped by bin
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             for (uint32_t j = 0; j < cmax; j++) {
 #pragma unroll
                 for (uint32_t q = 0; q < kPer; q++)
@@ -419,9 +411,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(const Unit* __restrict__ 
                         keys[lane + q * kLane] = j < n ? key_of(j, tt, pp) : 0xFFFFFFFFu;
                     }
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
                 const uint32_t tn = n - t0 < kScan2FifoCap ? n - t0 : kScan2FifoCap;
                 const uint32_t rounds = (((n - b0 < kScan2FifoCap ? n - b0 : kScan2FifoCap)) + kLane - 1) / kLane;   // own items in use
                 for (uint32_t j = 0; j < tn; j++) {

@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -253,12 +254,12 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan2(const Scan2Params P) {
                 uint32_t nf = 0;                                   // matches in the fifo (wave-uniform)
                 // passes over lane ranges whose flagged positions fit the LDS list (one pass for a typical unit)
                 for (uint32_t l0 = 0; l0 < 64;) {
-                    const uint32_t before = l0 ? lane_value(fincl, l0 - 1) : 0;
+                    const uint32_t before = l0 ? lane_value_at(fincl, l0 - 1) : 0;
                     const bool fits = lane >= l0 && fincl - before <= P.cand_cap;
                     const uint64_t fm = __ballot(fits) >> l0;
                     const uint32_t nl = fm == ~0ull >> l0 ? 64 - l0 : (uint32_t)__builtin_ctzll(~fm);   // lanes in this pass (>= 1)
                     const uint32_t l1 = l0 + nl;
-                    const uint32_t ptotal = lane_value(fincl, l1 - 1) - before;
+                    const uint32_t ptotal = lane_value_at(fincl, l1 - 1) - before;
                     if (lane >= l0 && lane < l1) {
                         uint32_t wpos = fincl - f - before;
                         const uint32_t rel = lane * C + kScan2MaxOff;
@@ -275,9 +276,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan2(const Scan2Params P) {
                             }
                         }
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_fence();
                     // stage A: every flagged position -> LDS-only decisions; short terms are emitted here, positions that may
                     // end a term of length >= 4 are compacted in place to the front of the list (write index <= read index)
                     // (kStageAWays candidates per lane and trip: their loads and table lookups are in flight together;
@@ -326,9 +325,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan2(const Scan2Params P) {
                             ns += (uint32_t)__popcll(sb);
                         }
                     }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_fence();
                     if (DBG && (P.dbg & 2)) { if (lane == 0) atomicAdd(reinterpret_cast<unsigned long long*>(KARG(dbg_counters) + 2), (unsigned long long)ns); }
                     mark(3);
                     if (P.prio) __builtin_amdgcn_s_setprio(3);
@@ -352,9 +349,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan2(const Scan2Params P) {
                         finish_long(c, on, rel, k, s0, s1, fr, tl, fifo, nf, dfr);
                     }
                     if (dfr.n) drain_deferred(c, ubase, fifo, nf, dfr);
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_fence();
                     l0 = l1;
                     mark(4);
                 }

@@ -1,66 +1,16 @@
-// gft_scan2_dev.hpp -- device helpers of the suffix-window scan kernels (gft_scan2.hip: one unit per wave iteration;
-// gft_scan4.hip: the streaming form): text loads around a flagged position, window keys, the fingerprint decision, bucket
-// slots and their byte compares, short-term records, the LDS match fifo.  Included inside namespace gft { namespace { ... } }
-// of a .hip file, after gft_kernels.hpp; KARG's parameter block is Scan2Params.
+// gft_scan2_dev.hpp -- device helpers of the scan2 family of suffix-window scan kernels (gft_scan5.hip: the default kernel;
+// gft_scan2.hip: one unit per wave iteration; gft_scan4.hip: the streaming form): the context, window keys, the fingerprint
+// decision, the byte compare of this family's slot layout, short-term records, the LDS match fifo.  What the family shares with
+// gft_scan3.hip (text loads around a flagged position, folding, slots, the long-term head compare) is gft_scan_dev.hpp,
+// included here; the lane primitives are gft_wave_dev.hpp's.  Included inside namespace gft { namespace { ... } } of a .hip
+// file, after gft_kernels.hpp and gft_wave_dev.hpp; KARG's parameter block is Scan2Params.
 #pragma once
-struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
-struct __attribute__((packed, aligned(1))) U128u { uint32_t x, y, z, w; };
-struct __attribute__((packed, aligned(1))) U64u { uint32_t lo, hi; };
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-// a * b + c on 24-bit operands: one full-rate instruction (the compiler's own choice is v_mul_lo_u32 / v_mad_u64_u32);
-// the wave-uniform multiplier comes straight from a scalar register (no v_mov to materialise it)
-__device__ __forceinline__ uint32_t mad24s(uint32_t a, uint32_t sb, uint32_t c) {
-    uint32_t d;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(sb), "v"(c));
-    return d;
-}
-// LDS tables at fixed addresses (the kernel's only LDS object is the dynamic array, which starts at 0; checked at
-// kernel entry): constant bases fold into the ds_read offset field
-typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) { return reinterpret_cast<const U32u*>(p)->v; }
-
-// Kernel arguments that are needed once per unit or less (output buffers, tables of the rare paths) are read from the
-// kernarg segment where they are used instead of living in scalar registers for the whole kernel: the unit loop keeps
-// more values alive than there are SGPRs, and every spilled one costs VALU slots (v_writelane / v_readlane).  The asm
-// makes the address opaque, so the load can be neither merged with the preloaded arguments nor hoisted.
-typedef __attribute__((address_space(4))) const uint8_t karg_u8;
-template <class T>
-__device__ __forceinline__ T karg_field(uint32_t off) {
-    karg_u8* ka = (karg_u8*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *(__attribute__((address_space(4))) const T*)(ka + off);
-}
+constexpr int kFrontWords = 5;      // a slot holds front[0..4]
+#include "gft_scan_dev.hpp"
 #define KARG(field) karg_field<decltype(Scan2Params::field)>((uint32_t)offsetof(Scan2Params, field))
 
-// ASCII lower-casing of four packed bytes (finder/finder.go:140-142 for ASCII text)
-__device__ __forceinline__ uint32_t fold4(uint32_t w) {
-    const uint32_t h = w & 0x7F7F7F7Fu;
-    const uint32_t ge_a = h + 0x3F3F3F3Fu;          // bit 7 set where byte >= 'A'
-    const uint32_t gt_z = h + 0x25252525u;          // bit 7 set where byte >  'Z'
-    const uint32_t up = ge_a & ~gt_z & ~w & 0x80808080u;
-    return w | (up >> 2);
-}
-__device__ __forceinline__ uint32_t fold1(uint32_t b) { return (b - 'A' < 26u) ? b + 32 : b; }
-
-// inclusive prefix sum over the 64 lanes with DPP moves (row shifts inside the four rows of 16 lanes, then the row
-// totals are broadcast into the rows behind them): ten VALU instructions, no LDS traffic, no index arithmetic
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);    // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);    // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);    // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);    // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1 and 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-// value of lane l (wave-uniform l) -- a scalar read instead of an LDS permute
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l));
-}
-
 struct Ctx {
+    typedef Scan2Params Params;
     const Scan2Params& P;
     const uint8_t* cls;        // LDS
     const uint32_t* filt;      // LDS
@@ -77,17 +27,6 @@ struct Ctx {
     uint32_t dbg;              // GFT_SCAN_DEBUG bits in the timing-study instantiations, the constant 0 in production
 };
 
-// the (up to) four bytes behind position p, text[p+1 .. p+4], for the tails of shifted terms; bytes past the blob end
-// read as zero (a tail that reached there would end outside the unit and is dropped by the range check anyway)
-__device__ __forceinline__ uint32_t tail_load(const Ctx& c, uint32_t p) {
-    if (__builtin_expect(c.near_end, 0)) {
-        uint32_t v = 0;
-        for (uint32_t b = 0; b < 4; b++)
-            if (c.doc_abs + p + 1 + b < c.P.text_bytes) v |= (uint32_t)c.dbase[(uint64_t)p + 1 + b] << (8 * b);
-        return v;
-    }
-    return load_u32_unaligned(c.dbase + (uint64_t)p + 1);
-}
 // reported position of a match whose window ends at p (lw = the slot's len word)
 __device__ __forceinline__ uint32_t match_pos(const Scan2Params& P, uint32_t p, uint32_t lw) {
     const uint32_t off = lw >> 24, L1 = lw & kScan2LenMask;
@@ -97,32 +36,9 @@ __device__ __forceinline__ uint32_t match_pos(const Scan2Params& P, uint32_t p, 
 // ---- verification of one flagged position p, in three separable steps so that several candidates can have their
 // the cheap LDS-only decisions (stage A) and the L2 bucket probes (stage B) can run as separate, dense passes ------------
 
-// step 1: one 8-byte load brings the window (bytes p-3..p) and the 4 bytes in front of it (p-7..p-4).
-// Positions before the document start need no special casing here: the bytes there (the previous document's, or
-// zeros in front of the blob) can only change keys of windows that reach across the start, and every term such a
-// window may name is longer than p + 1 and is dropped by the length check at emission.
+// step 1: cand_load (gft_scan_dev.hpp) brings the window (bytes p-3..p) and the 4 bytes in front of it (p-7..p-4).
 constexpr int kStageAWays = 2;      // stage A: candidates a lane works on at once
 struct Cand { uint32_t p, x, x3, tw, sid; bool go_long; };
-struct Text8 { uint32_t tw, w; };
-__device__ __forceinline__ Text8 cand_load_slow(const Ctx& c, uint32_t p) {   // within 7 bytes of the blob start
-    Text8 t{0, 0};
-    const uint64_t ab = c.doc_abs + p;
-    if (ab >= 7) {
-        const U64u v = *reinterpret_cast<const U64u*>(c.dbase + (int64_t)p - 7);
-        t.tw = v.lo; t.w = v.hi;
-    } else {
-        for (uint32_t i = 0; i <= (uint32_t)ab; i++) {        // oldest byte first; byte p ends up on top of w
-            t.tw = t.tw >> 8 | t.w << 24;
-            t.w = t.w >> 8 | (uint32_t)c.dbase[(int64_t)p - (int64_t)ab + i] << 24;
-        }
-    }
-    return t;
-}
-__device__ __forceinline__ Text8 cand_load(const Ctx& c, uint32_t p) {
-    if (__builtin_expect(c.near0, 0)) return cand_load_slow(c, p);        // wave-uniform: first document of the blob
-    const U64u v = *reinterpret_cast<const U64u*>(c.dbase + (int64_t)p - 7);
-    return Text8{v.lo, v.hi};
-}
 // window key, bucket hash and the short-term record id
 template <bool WANT_SID = true>
 __device__ __forceinline__ void cand_keys(const Ctx& c, uint32_t p, const Text8 t, Cand& k) {
@@ -157,43 +73,12 @@ __device__ __forceinline__ void cand_text(const Ctx& c, uint32_t p, Cand& k) {
 }
 
 // step 2 (bucket table): the 20 bytes in front of the window as the slots store them, f[k] = text[p-7-4k .. p-4-4k]
-struct Front { uint32_t f[5]; };
-__device__ __forceinline__ Front front_load(const Ctx& c, uint32_t p, uint32_t tw) {
-    Front t;
-    t.f[0] = tw;
-    if (__builtin_expect(c.near24, 0)) {                      // wave-uniform: first document of the blob
-        const uint64_t ab = c.doc_abs + p;
-#pragma unroll
-        for (int k = 1; k < 5; k++) {
-            uint32_t v = 0;
-            for (int b = 0; b < 4; b++)
-                if (ab >= (uint64_t)(7 + 4 * k - b)) v |= (uint32_t)c.dbase[(int64_t)p - 7 - 4 * k + b] << (8 * b);
-            t.f[k] = v;
-        }
-    } else {
-        const U128u v = *reinterpret_cast<const U128u*>(c.dbase + (int64_t)p - 23);
-        t.f[4] = v.x; t.f[3] = v.y; t.f[2] = v.z; t.f[1] = v.w;
-    }
-    return t;
-}
 __device__ __forceinline__ void front_fold(Front& t) {
 #pragma unroll
     for (int k = 0; k < 5; k++) t.f[k] = fold4(t.f[k]);
 }
 
-struct Slot { uint4 a, b; };      // a = {key, info, len, front[0]}, b = front[1..4]
-__device__ __forceinline__ Slot slot_load(const Scan2Slot* s) {
-    const uint4* q = reinterpret_cast<const uint4*>(s);
-    return Slot{q[0], q[1]};
-}
-// both candidate slots of key x -> the one that holds it; false: no term ends with this window
-__device__ __forceinline__ bool slot_pick(uint32_t x, const Slot& s0, const Slot& s1, Slot& out) {
-    const bool use1 = s1.a.x == x;
-    out.a = use1 ? s1.a : s0.a;
-    out.b = use1 ? s1.b : s0.b;
-    return use1 || s0.a.x == x;
-}
-
+// slot layout of this family: a = {key, info, len, front[0]}, b = front[1..4] (front[4] holds the tail of a shifted term)
 // does the term described by e have its window end at p (and its own end inside the unit)?  t = the (folded) bytes in
 // front of the window, tl = the raw bytes behind it.  kmax: dwords of `front` to look at (wave-uniform bound, or 5)
 // pd = p counted from the start of its document, [lo, hi) = where the term must END to be this caller's (one unit per wave
@@ -221,31 +106,7 @@ __device__ __forceinline__ bool entry_ok_x(const Ctx& c, uint32_t p, uint32_t pd
     const uint32_t pe = p + off;                                                   // where the term ends
     bool ok = L <= pd + 1 && diff == 0 && pe >= lo && pe < hi;
     const uint32_t inl = off ? kScan2InlineLen - 4 : kScan2InlineLen;
-    if (ok && L > inl) {
-        // the first L-inl bytes of the term against text[p+1-L .. p-inl], four bytes at a time from the end; term_blob
-        // carries 4 bytes of slack in front of every term, the text side needs 3 bytes of slack before the match
-        const uint8_t* tb = KARG(term_blob) + KARG(term_off)[e.a.y];
-        const uint8_t* tp = c.dbase + (int64_t)p + 1 - L;
-        const uint32_t n = L - inl;
-        if (c.doc_abs + p + 1 - L >= 3) {
-            uint32_t d2 = 0;
-            for (uint32_t j = 0; j * 4 < n; j++) {
-                const int32_t at = (int32_t)n - 4 - (int32_t)(j * 4);       // may be -1..-3 for the last chunk
-                uint32_t tv = load_u32_unaligned(tp + at);
-                const uint32_t wv = load_u32_unaligned(tb + at);
-                if (P.fold) tv = fold4(tv);
-                const uint32_t mask = at >= 0 ? 0xFFFFFFFFu : 0xFFFFFFFFu << (8 * (uint32_t)(-at));
-                d2 |= (tv ^ wv) & mask;
-            }
-            ok = d2 == 0;
-        } else {
-            for (uint32_t i = 0; i < n && ok; i++) {
-                uint32_t b = tp[i];
-                if (P.fold) b = fold1(b);
-                ok = b == tb[i];
-            }
-        }
-    }
+    if (ok && L > inl) ok = term_head_ok(c, p, L, inl, e.a.y);
     return ok;
 }
 __device__ __forceinline__ bool entry_ok(const Ctx& c, uint32_t p, const Front& t, uint32_t tl, const Slot& e, uint32_t kmax) {
@@ -318,7 +179,7 @@ __device__ __forceinline__ void cand_finish(const Ctx& c, const Cand& k, uint32_
 __device__ __forceinline__ void fifo_append(bool em, uint32_t term, uint32_t pos, uint2* fifo, uint32_t& nf) {
     const uint64_t mask = __ballot(em);
     if (em) {
-        const uint32_t idx = nf + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+        const uint32_t idx = nf + wave_rank(mask);
         if (idx < kScan2FifoCap) fifo[idx] = make_uint2(term, pos);
     }
     nf += (uint32_t)__popcll(mask);
@@ -341,18 +202,6 @@ __device__ __forceinline__ void finish_short(const Ctx& c, uint32_t p, uint32_t 
 __device__ __forceinline__ uint32_t wave_kmax(uint32_t L) {
     return __any(L > 20) ? 5 : __any(L > 16) ? 4 : __any(L > 12) ? 3 : __any(L > 8) ? 2 : 1;
 }
-// fold the first kmax dwords of t that are not folded yet (`done` = how many are; wave-uniform)
-__device__ __forceinline__ void front_fold_upto(Front& t, uint32_t& done, uint32_t kmax) {
-#pragma unroll
-    for (int k = 0; k < 5; k++)
-        if ((uint32_t)k >= done && (uint32_t)k < kmax) t.f[k] = fold4(t.f[k]);
-    done = kmax > done ? kmax : done;
-}
-
-// A wave's deferred bucket entries: {candidate position, index into `more`} pairs parked in LDS so that the entries
-// of multi-term buckets are verified densely (64 distinct entries per trip) instead of one round per bucket depth.
-struct Deferred { uint2* list; uint32_t cap, n; };
-
 // terms of length >= 4 ending at the lanes' positions (`on`: this lane has a candidate); wave-uniform call.
 // s0, s1: the key's two candidate slots; t: the bytes in front of the window, not yet folded.  One-term buckets are
 // verified here; the entries of multi-term buckets are deferred (or, if the list is full, verified in place).
@@ -379,8 +228,7 @@ __device__ __forceinline__ void finish_long(const Ctx& c, bool on, uint32_t rel,
         for (uint32_t j = 0; __any(j < n_ent); j++) {
             const uint64_t m = __ballot(j < n_ent);
             if (j < n_ent)
-                d.list[d.n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0))] =
-                    make_uint2(rel, more_at + j);
+                d.list[d.n + wave_rank(m)] = make_uint2(rel, more_at + j);
             d.n += (uint32_t)__popcll(m);
         }
         return;
@@ -404,9 +252,7 @@ __device__ __forceinline__ void finish_long(const Ctx& c, bool on, uint32_t rel,
 __device__ __forceinline__ void drain_deferred(const Ctx& c, uint32_t unit_lo, uint2* fifo, uint32_t& nf, Deferred& d) {
     const Scan2Params& P = c.P;
     const uint32_t lane = lane_id();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_fence();
     for (uint32_t i0 = 0; i0 < d.n; i0 += 64) {
         const bool on = i0 + lane < d.n;
         const uint2 it = d.list[on ? i0 + lane : 0];

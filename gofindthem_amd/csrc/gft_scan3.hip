@@ -20,76 +20,28 @@
 //            a larger pool if the cursor overran.
 // HBM traffic: text once + 8 B per match (4 B in presence-only mode); tables are LDS / L2 resident.  No MFMA (byte
 // automaton, not a contraction).
+// Device helpers: the lane primitives (prefix sum, ballot rank, LDS fence) are gft_wave_dev.hpp's; the text loads around a
+// probe, folding, slots and the long-term head compare are gft_scan_dev.hpp's, shared with the scan2 family.  Here: the
+// context, the output slab, this kernel's slot layout (entry_ok), finish_long / drain_deferred and the stages.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
 
+constexpr int kFrontWords = 4;      // a slot holds front[0..3] and the window
+#include "gft_scan_dev.hpp"
 #include "gft_foldsafe_dev.hpp"
 
-struct __attribute__((packed, aligned(1))) U32u { uint32_t v; };
-struct __attribute__((packed, aligned(1))) U128u { uint32_t x, y, z, w; };
-struct __attribute__((packed, aligned(1))) U64u { uint32_t lo, hi; };
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
-// a * b + c on 24-bit operands with the multiplier in a scalar register: one full-rate instruction
-__device__ __forceinline__ uint32_t mad24s(uint32_t a, uint32_t sb, uint32_t c) {
-    uint32_t d;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(sb), "v"(c));
-    return d;
-}
-// LDS tables at fixed addresses (the kernel's only LDS object is the dynamic array, which starts at 0; checked at kernel
-// entry): constant bases fold into the ds_read offset field
-typedef __attribute__((address_space(3))) const uint8_t lds_u8;
-typedef __attribute__((address_space(3))) const uint32_t lds_u32;
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t* p) { return reinterpret_cast<const U32u*>(p)->v; }
-
-// kernel arguments that are needed once per unit or less are read from the kernarg segment where they are used (see
-// gft_scan2.hip: the unit loop keeps more values alive than there are SGPRs)
-typedef __attribute__((address_space(4))) const uint8_t karg_u8;
-template <class T>
-__device__ __forceinline__ T karg_field(uint32_t off) {
-    karg_u8* ka = (karg_u8*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ka));
-    return *(__attribute__((address_space(4))) const T*)(ka + off);
-}
 #define KARG(field) karg_field<decltype(Scan3Params::field)>((uint32_t)offsetof(Scan3Params, field))
 
-// ASCII lower-casing of four packed bytes (finder/finder.go:140-142 for ASCII text)
-__device__ __forceinline__ uint32_t fold4(uint32_t w) {
-    const uint32_t h = w & 0x7F7F7F7Fu;
-    const uint32_t ge_a = h + 0x3F3F3F3Fu;          // bit 7 set where byte >= 'A'
-    const uint32_t gt_z = h + 0x25252525u;          // bit 7 set where byte >  'Z'
-    const uint32_t up = ge_a & ~gt_z & ~w & 0x80808080u;
-    return w | (up >> 2);
-}
-__device__ __forceinline__ uint32_t fold1(uint32_t b) { return (b - 'A' < 26u) ? b + 32 : b; }
-
-// inclusive prefix sum over the 64 lanes with DPP moves
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);    // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);    // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);    // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);    // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1 and 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
-    return v;
-}
-__device__ __forceinline__ uint32_t lane_value(uint32_t v, uint32_t l) {
-    return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l));
-}
-__device__ __forceinline__ void wave_lds_fence() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 struct Ctx {
+    typedef Scan3Params Params;
     const Scan3Params& P;
     const uint8_t* dbase;      // first byte of the document
     uint64_t doc_abs;          // offset of the document inside the text blob
@@ -110,7 +62,7 @@ struct Out {
     __device__ __forceinline__ void append(bool em, uint32_t t, uint32_t p) {
         const uint64_t mask = __ballot(em);
         if (em) {
-            const uint32_t idx = nf + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+            const uint32_t idx = nf + wave_rank(mask);
             if (idx < room) {
                 term[idx] = t;
                 if (pos) pos[idx] = p;
@@ -120,74 +72,7 @@ struct Out {
     }
 };
 
-// ---- text around a probe -------------------------------------------------------------------------------------------------
-// one 8-byte load: tw = text[p-7 .. p-4], w = text[p-3 .. p] (the window).  Bytes before the document start (the previous
-// document's, or zeros in front of the blob) can only change keys of windows that reach across the start, and every term
-// such a window may name is longer than p + 1 and is dropped by the length check at emission.
-struct Text8 { uint32_t tw, w; };
-__device__ __forceinline__ Text8 cand_load_slow(const Ctx& c, uint32_t p) {   // within 7 bytes of the blob start
-    Text8 t{0, 0};
-    const uint64_t ab = c.doc_abs + p;
-    if (ab >= 7) {
-        const U64u v = *reinterpret_cast<const U64u*>(c.dbase + (int64_t)p - 7);
-        t.tw = v.lo; t.w = v.hi;
-    } else {
-        for (uint32_t i = 0; i <= (uint32_t)ab; i++) {        // oldest byte first; byte p ends up on top of w
-            t.tw = t.tw >> 8 | t.w << 24;
-            t.w = t.w >> 8 | (uint32_t)c.dbase[(int64_t)p - (int64_t)ab + i] << 24;
-        }
-    }
-    return t;
-}
-__device__ __forceinline__ Text8 cand_load(const Ctx& c, uint32_t p) {
-    if (__builtin_expect(c.near0, 0)) return cand_load_slow(c, p);
-    const U64u v = *reinterpret_cast<const U64u*>(c.dbase + (int64_t)p - 7);
-    return Text8{v.lo, v.hi};
-}
-// the 20 bytes in front of the window as the slots store them, f[k] = text[p-7-4k .. p-4-4k]
-struct Front { uint32_t f[5]; };
-__device__ __forceinline__ Front front_load(const Ctx& c, uint32_t p, uint32_t tw) {
-    Front t;
-    t.f[0] = tw;
-    if (__builtin_expect(c.near24, 0)) {                      // wave-uniform: first document of the blob
-        const uint64_t ab = c.doc_abs + p;
-#pragma unroll
-        for (int k = 1; k < 5; k++) {
-            uint32_t v = 0;
-            for (int b = 0; b < 4; b++)
-                if (ab >= (uint64_t)(7 + 4 * k - b)) v |= (uint32_t)c.dbase[(int64_t)p - 7 - 4 * k + b] << (8 * b);
-            t.f[k] = v;
-        }
-    } else {
-        const U128u v = *reinterpret_cast<const U128u*>(c.dbase + (int64_t)p - 23);
-        t.f[4] = v.x; t.f[3] = v.y; t.f[2] = v.z; t.f[1] = v.w;
-    }
-    return t;
-}
-// the (up to) four bytes behind position p, text[p+1 .. p+4]; bytes past the blob end read as zero (a tail that reached
-// there would end outside the unit and is dropped by the range check anyway)
-__device__ __forceinline__ uint32_t tail_load(const Ctx& c, uint32_t p) {
-    if (__builtin_expect(c.near_end, 0)) {
-        uint32_t v = 0;
-        for (uint32_t b = 0; b < 4; b++)
-            if (c.doc_abs + p + 1 + b < c.P.text_bytes) v |= (uint32_t)c.dbase[(uint64_t)p + 1 + b] << (8 * b);
-        return v;
-    }
-    return load_u32_unaligned(c.dbase + (uint64_t)p + 1);
-}
-
 // ---- bucket table ---------------------------------------------------------------------------------------------------------
-struct Slot { uint4 a, b; };      // a = {key, info, len, front[0]}, b = front[1..4]
-__device__ __forceinline__ Slot slot_load(const Scan2Slot* s) {
-    const uint4* q = reinterpret_cast<const uint4*>(s);
-    return Slot{q[0], q[1]};
-}
-__device__ __forceinline__ bool slot_pick(uint32_t x, const Slot& s0, const Slot& s1, Slot& out) {
-    const bool use1 = s1.a.x == x;
-    out.a = use1 ? s1.a : s0.a;
-    out.b = use1 ? s1.b : s0.b;
-    return use1 || s0.a.x == x;
-}
 __device__ __forceinline__ int32_t slot_off(uint32_t lw) { return (int32_t)lw >> 24; }          // signed: -1 .. kScan2MaxOff
 // reported position of a match whose window ends at p (lw = the slot's len word)
 __device__ __forceinline__ uint32_t match_pos(const Scan3Params& P, uint32_t p, uint32_t lw) {
@@ -222,31 +107,7 @@ __device__ __forceinline__ bool entry_ok(const Ctx& c, uint32_t p, const Front& 
     const uint32_t pe = p + (uint32_t)off;                                         // where the term ends
     bool ok = L <= p + 1 && diff == 0 && pe >= c.lo && pe < c.hi;
     const uint32_t inl = off > 0 ? 16u : 20u;                                      // bytes the slot holds (window included)
-    if (ok && L > inl) {
-        // the first L-inl bytes of the term against text[p+1-L .. p-inl], four bytes at a time from the end; term_blob
-        // carries 4 bytes of slack in front of every term, the text side needs 3 bytes of slack before the match
-        const uint8_t* tb = KARG(term_blob) + KARG(term_off)[e.a.y];
-        const uint8_t* tp = c.dbase + (int64_t)p + 1 - L;
-        const uint32_t n = L - inl;
-        if (c.doc_abs + p + 1 - L >= 3) {
-            uint32_t d2 = 0;
-            for (uint32_t j = 0; j * 4 < n; j++) {
-                const int32_t at = (int32_t)n - 4 - (int32_t)(j * 4);       // may be -1..-3 for the last chunk
-                uint32_t tv = load_u32_unaligned(tp + at);
-                const uint32_t wv = load_u32_unaligned(tb + at);
-                if (P.fold) tv = fold4(tv);
-                const uint32_t mask = at >= 0 ? 0xFFFFFFFFu : 0xFFFFFFFFu << (8 * (uint32_t)(-at));
-                d2 |= (tv ^ wv) & mask;
-            }
-            ok = d2 == 0;
-        } else {
-            for (uint32_t i = 0; i < n && ok; i++) {
-                uint32_t b = tp[i];
-                if (P.fold) b = fold1(b);
-                ok = b == tb[i];
-            }
-        }
-    }
+    if (ok && L > inl) ok = term_head_ok(c, p, L, inl, e.a.y);
     return ok;
 }
 
@@ -254,17 +115,6 @@ __device__ __forceinline__ bool entry_ok(const Ctx& c, uint32_t p, const Front& 
 __device__ __forceinline__ uint32_t wave_kmax(uint32_t L) {
     return __any(L > 16) ? 4 : __any(L > 12) ? 3 : __any(L > 8) ? 2 : 1;
 }
-__device__ __forceinline__ void front_fold_upto(Front& t, uint32_t& done, uint32_t kmax) {
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if ((uint32_t)k >= done && (uint32_t)k < kmax) t.f[k] = fold4(t.f[k]);
-    done = kmax > done ? kmax : done;
-}
-
-// A wave's deferred bucket entries: {probe entry, index into `more`} pairs parked in LDS so that the entries of
-// multi-term buckets are verified densely (64 distinct entries per trip) instead of one round per bucket depth.
-struct Deferred { uint2* list; uint32_t cap, n; };
-
 // position of a listed probe: entries 0 and 1 are the border probes lo - 3 and lo - 1, entry t + 2 is probe t at lo + 2 t + 1
 __device__ __forceinline__ uint32_t probe_pos(const Ctx& c, uint32_t entry) { return c.lo + 2 * entry - 3; }
 
@@ -293,8 +143,7 @@ __device__ __forceinline__ void finish_long(const Ctx& c, bool on, uint32_t entr
         for (uint32_t j = 0; __any(j < n_ent); j++) {
             const uint64_t m = __ballot(j < n_ent);
             if (j < n_ent)
-                d.list[d.n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0))] =
-                    make_uint2(entry, more_at + j);
+                d.list[d.n + wave_rank(m)] = make_uint2(entry, more_at + j);
             d.n += (uint32_t)__popcll(m);
         }
         return;
@@ -628,12 +477,12 @@ __global__ void __launch_bounds__(kScan3Threads) k_scan3(const Scan3Params P) {
             uint32_t ns = 0, nj = 0;                               // parked survivors, parked short jobs
             // passes over lane ranges whose flagged probes fit the LDS list (one pass for a typical unit)
             for (uint32_t l0 = 0; l0 < 64;) {
-                const uint32_t before = l0 ? lane_value(fincl, l0 - 1) : 0;
+                const uint32_t before = l0 ? lane_value_at(fincl, l0 - 1) : 0;
                 const bool fits = lane >= l0 && fincl - before <= P.cand_cap;
                 const uint64_t fm = __ballot(fits) >> l0;
                 const uint32_t nl = fm == ~0ull >> l0 ? 64 - l0 : (uint32_t)__builtin_ctzll(~fm);   // lanes in this pass (>= 1)
                 const uint32_t l1 = l0 + nl;
-                const uint32_t ptotal = lane_value(fincl, l1 - 1) - before;
+                const uint32_t ptotal = lane_value_at(fincl, l1 - 1) - before;
                 if (lane >= l0 && lane < l1) {
                     uint32_t wpos = fincl - f - before;
                     if (lane == 0)
@@ -711,8 +560,7 @@ __global__ void __launch_bounds__(kScan3Threads) k_scan3(const Scan3Params P) {
                             const uint32_t sid1 = reg ? ls3[k[q].x3m] : 0u;
                             const bool has = (sid0 | sid1) != 0;
                             const uint64_t jb = __ballot(has);
-                            if (has) jobs[nj + __builtin_amdgcn_mbcnt_hi((uint32_t)(jb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)jb, 0))] =
-                                ent[q] | sid0 << 16 | sid1 << 24;
+                            if (has) jobs[nj + wave_rank(jb)] = ent[q] | sid0 << 16 | sid1 << 24;
                             nj += (uint32_t)__popcll(jb);
                         }
                     }
@@ -727,8 +575,7 @@ __global__ void __launch_bounds__(kScan3Threads) k_scan3(const Scan3Params P) {
                             stage_b(c, surv, ns, fifo);
                             if (P.prio) __builtin_amdgcn_s_setprio(2);
                         }
-                        if (go[q]) surv[ns + __builtin_amdgcn_mbcnt_hi((uint32_t)(sb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sb, 0))] =
-                            make_uint2(ent[q], k[q].x);
+                        if (go[q]) surv[ns + wave_rank(sb)] = make_uint2(ent[q], k[q].x);
                         ns += cnt;
                     }
                 }

@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -227,9 +228,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
                 rec[0] = v4u{(uint32_t)(dabs - base), dlen, (uint32_t)(b_abs - base), 0u};
                 rec[1] = v4u{bound_l, bincl - bound_l, 0u, 0u};
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
 
             const Ctx c{P, cls, filt, P.short3_bytes ? short3 : nullptr, fpt, lrec, P.text + base, base, kp2,
                         base < 7, base < 23, s_p, e_p, base + e_p + 4 > P.text_bytes, 0u};
@@ -239,9 +238,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
             int phase = 0;                       // (the enclosing phase of a flush, for the phase clocks)
             auto flush = [&]() {
                 mark(phase);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
                 for (uint32_t i0 = 0; i0 < ff.n; i0 += 64) {
                     const bool on = i0 + lane < ff.n;
                     const uint32_t e = ff.term[on ? i0 + lane : 0];
@@ -256,7 +253,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
                         const uint32_t bnd = __builtin_amdgcn_readfirstlane(rg.x), reg = __builtin_amdgcn_readfirstlane(rg.y);
                         const uint32_t cur = __builtin_amdgcn_readfirstlane(rg.z);
                         if (on && tag == t) {
-                            const uint32_t idx = cur + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+                            const uint32_t idx = cur + wave_rank(m);
                             if (idx < bnd && pool_ok) {
                                 const uint64_t at = chunk_base + reg + idx;
                                 __builtin_nontemporal_store(e & 0x1FFFFFFFu, &KARG(pool_term)[at]);
@@ -274,7 +271,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
             auto append = [&](bool em, uint32_t term, uint32_t tag, uint32_t pos) {
                 const uint64_t mask = __ballot(em);
                 if (em) {
-                    const uint32_t idx = ff.n + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+                    const uint32_t idx = ff.n + wave_rank(mask);
                     ff.term[idx] = term | tag << 29;
                     if (ff.pos) ff.pos[idx] = pos;
                 }
@@ -337,9 +334,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
             // a piece, decide the trip) and in the service loop that runs when queue A is full or the stream is over
             auto stage_b = [&](const uint32_t n) {
                 phase = 5;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
                 if (P.prio) __builtin_amdgcn_s_setprio(3);
                 const bool on = lane < n;
                 const uint32_t p = qbp[on ? lane : 0];
@@ -426,7 +421,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
                     const bool keep = a_on[q2] && k[q2].go_long && !(DBG && (P.dbg & 4));     // (timing study 4: no stage B)
                     const uint64_t sb = __ballot(keep);
                     if (keep) {
-                        const uint32_t idx = qb_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(sb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sb, 0));
+                        const uint32_t idx = qb_n + wave_rank(sb);
                         qbp[idx] = (uint16_t)k[q2].p;
                         qbk[idx] = k[q2].x;
                     }
@@ -437,9 +432,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
                 mark(4);
             };
             auto stage_a_issue = [&](const uint32_t n) {
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_fence();
 #pragma unroll
                 for (int q2 = 0; q2 < kStageAWays; q2++) {
                     const uint32_t i = 64 * q2 + lane;
@@ -463,14 +456,14 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
                 mark(3);
             };
             auto push_some = [&]() {
-                const uint32_t before = push_l0 ? lane_value(fincl, push_l0 - 1) : 0;
+                const uint32_t before = push_l0 ? lane_value_at(fincl, push_l0 - 1) : 0;
                 const uint32_t room = qa_cap - qa_n;
                 const bool fits = lane >= push_l0 && fincl - before <= room;
                 const uint64_t fm = __ballot(fits) >> push_l0;
                 const uint32_t nl = fm == ~0ull >> push_l0 ? 64 - push_l0 : (uint32_t)__builtin_ctzll(~fm);   // lanes that fit (may be 0)
                 if (nl) {
                     const uint32_t l1 = push_l0 + nl;
-                    const uint32_t ptotal = lane_value(fincl, l1 - 1) - before;
+                    const uint32_t ptotal = lane_value_at(fincl, l1 - 1) - before;
                     if (lane >= push_l0 && lane < l1) {
                         uint32_t wpos = qa_head + qa_n + fincl - fcnt - before;
                         const uint32_t p0 = s_p + push_rb + push_C * lane;
@@ -595,9 +588,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
 
             // ---- the units' records: region and count.  A unit that outgrew its region has nothing valid there: it goes on the
             // wave's list and is walked again, alone, with a region of the size counted
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_fence();
             const uint32_t cur_l = lane < nu ? tab_at(meta, kTabCur, lane) : 0u;
             const bool over = lane < nu && cur_l > bound_l;
             if (lane < nu && !over) {
@@ -608,7 +599,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan4(const Scan2Params P) {
             {
                 const uint64_t om = __ballot(over);                                  // (never on a second walk: its region is the count)
                 if (over) {
-                    const uint32_t at = n_redo + __builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)om, 0));
+                    const uint32_t at = n_redo + wave_rank(om);
                     redo_u[at] = (uint32_t)(u_first + lane);
                     redo_c[at] = cur_l;
                 }

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -58,7 +59,7 @@ template <bool POS>
 __device__ __forceinline__ void out_append(Ctx5& o, bool em, uint32_t term, uint32_t pos) {
     const uint64_t mask = __ballot(em);
     if (em) {
-        const uint32_t idx = o.nf + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+        const uint32_t idx = o.nf + wave_rank(mask);
         if (!o.direct) {
             if (idx < o.fifo_cap - o.npend) o.fifo[idx] = POS ? term | (pos - o.pos_base) << o.term_bits : term;
         } else {
@@ -68,12 +69,6 @@ __device__ __forceinline__ void out_append(Ctx5& o, bool em, uint32_t term, uint
     }
     o.nf += (uint32_t)__popcll(mask);
     if (!o.direct && o.nf + o.npend > o.fifo_cap) o.lost = true;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Short terms are emitted DENSELY: stage A only parks {position, record id} of the candidates whose 3-window ends one
@@ -128,12 +123,12 @@ __device__ __forceinline__ void park_short(const Ctx& c, Ctx5& o, uint32_t ubase
     const uint64_t m = __ballot(sid != 0);
     const uint32_t n = (uint32_t)__popcll(m);
     if (o.npend + n > o.fifo_cap / 2) {                            // (never in practice: keep half of the fifo for matches)
-        wave_lds_sync();
+        wave_lds_fence();
         while (o.npend) short_trip<POS>(c, o, ubase, o.npend < 64 ? o.npend : 64);
-        wave_lds_sync();
+        wave_lds_fence();
     }
     if (!o.direct && o.nf + o.npend + n > o.fifo_cap) o.lost = true;   // (the jobs go where matches are)
-    if (sid) o.fifo[o.fifo_cap - 1 - o.npend - __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0))] = rel | sid << 16;
+    if (sid) o.fifo[o.fifo_cap - 1 - o.npend - wave_rank(m)] = rel | sid << 16;
     o.npend += n;
 }
 
@@ -187,12 +182,12 @@ __device__ __forceinline__ void park_short_g(const Ctx& c, Ctx5& o, lds_u8* lsg,
     const uint64_t m = __ballot(sid != 0);
     const uint32_t n = (uint32_t)__popcll(m);
     if (o.npend + n > o.fifo_cap / 2) {
-        wave_lds_sync();
+        wave_lds_fence();
         while (o.npend) short_trip_g<POS>(c, o, lsg, ubase, o.npend < 64 ? o.npend : 64);
-        wave_lds_sync();
+        wave_lds_fence();
     }
     if (!o.direct && o.nf + o.npend + n > o.fifo_cap) o.lost = true;   // (the jobs go where matches are)
-    if (sid) o.fifo[o.fifo_cap - 1 - o.npend - __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0))] = rel | sid << 16;
+    if (sid) o.fifo[o.fifo_cap - 1 - o.npend - wave_rank(m)] = rel | sid << 16;
     o.npend += n;
 }
 
@@ -220,8 +215,7 @@ __device__ __forceinline__ void finish_long5(const Ctx& c, Ctx5& o, bool on, uin
         for (uint32_t j = 0; __any(j < n_ent); j++) {
             const uint64_t m = __ballot(j < n_ent);
             if (j < n_ent)
-                d.list[d.n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0))] =
-                    make_uint2(rel, more_at + j);
+                d.list[d.n + wave_rank(m)] = make_uint2(rel, more_at + j);
             d.n += (uint32_t)__popcll(m);
         }
         return;
@@ -245,7 +239,7 @@ template <bool POS>
 __device__ __forceinline__ void drain_deferred5(const Ctx& c, Ctx5& o, uint32_t ubase, Deferred& d) {
     const Scan2Params& P = c.P;
     const uint32_t lane = lane_id();
-    wave_lds_sync();
+    wave_lds_fence();
     const Scan2Slot* more = KARG(more);
     for (uint32_t i0 = 0; i0 < d.n; i0 += 64) {
         const bool on = i0 + lane < d.n;
@@ -505,15 +499,15 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
         for (uint32_t walk = 0; walk < 2 && ftotal; walk++) {
             o.nf = 0; o.npend = 0; o.lost = false;
             // (every walk emits a record's terms again -- the second one counts from nf = 0 like the first; the list build's
-            // wave_lds_sync stands between this and the first short-term trip)
+            // wave_lds_fence stands between this and the first short-term trip)
             if (lane < kScan5SeenWords) scan5_seen(o)[lane] = 0;
             for (uint32_t l0 = 0; l0 < 64;) {
-                const uint32_t before = l0 ? lane_value(fincl, l0 - 1) : 0;
+                const uint32_t before = l0 ? lane_value_at(fincl, l0 - 1) : 0;
                 const bool fits = lane >= l0 && fincl - before <= P.cand_cap;
                 const uint64_t fm = __ballot(fits) >> l0;
                 const uint32_t nl = fm == ~0ull >> l0 ? 64 - l0 : (uint32_t)__builtin_ctzll(~fm);   // lanes in this pass (>= 1)
                 const uint32_t l1 = l0 + nl;
-                const uint32_t ptotal = lane_value(fincl, l1 - 1) - before;
+                const uint32_t ptotal = lane_value_at(fincl, l1 - 1) - before;
                 if (lane >= l0 && lane < l1) {
                     uint32_t wpos = fincl - f - before;
                     if (lane == 0)
@@ -530,7 +524,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         }
                     }
                 }
-                wave_lds_sync();
+                wave_lds_fence();
                 // stage A: every flagged position -> LDS-only decisions; short terms are emitted here, positions that may end a
                 // term of length >= 4 are compacted in place to the front of the list (write index <= read index)
                 mark(2);
@@ -598,7 +592,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                         ns += (uint32_t)__popcll(sb);
                     }
                 }
-                wave_lds_sync();
+                wave_lds_fence();
                 mark(6);                                         // (stage A's trips end here; what follows until mark(3) is the short-term trips)
                 // stage B: the survivors, densely packed over the lanes, go to the L2 bucket table.  The first trip's loads -- the
                 // slots its keys name (they came along from stage A) and the text around the positions, the longest single wait
@@ -670,7 +664,7 @@ __global__ void __launch_bounds__(kScan2Threads) k_scan5(const Scan2Params P) {
                     }
                 }
                 if (dfr.n) drain_deferred5<POS>(c, o, ubase, dfr);
-                wave_lds_sync();
+                wave_lds_fence();
                 l0 = l1;
                 mark(4);
             }

@@ -18,12 +18,11 @@
 #include <type_traits>
 
 #include "gft_kernels.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
 namespace {
-
-__device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 
 // A wave-uniform word of a read-only table through the scalar unit (constant address space: s_load, counted by lgkmcnt).
 // As a plain global load it would be a VECTOR load plus v_readfirstlane -- and its s_waitcnt vmcnt(0) would wait for every

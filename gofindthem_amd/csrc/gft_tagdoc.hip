@@ -31,6 +31,7 @@
 #include <algorithm>
 
 #include "gft_tagdoc.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -81,13 +82,6 @@ struct TextOut {
         for (uint32_t k = 0; k < n; k++) dst[k] = src[k];
     }
 };
-
-// the wave's LDS writes before, its reads behind
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <bool FILL>
 __global__ void __launch_bounds__(kTagDocBlock) k_tagdoc(const TagDocParams P) {
@@ -142,7 +136,7 @@ __global__ void __launch_bounds__(kTagDocBlock) k_tagdoc(const TagDocParams P) {
                 L = (uint32_t)(o1 - o0);
             }
         }
-        wave_sync();                        // (the record before is done with the arrays)
+        wave_lds_fence();                        // (the record before is done with the arrays)
         for (uint32_t i = lane; i < L; i += 64) {
             const uint32_t f = P.leaf_field[o0 + i];
             uint32_t r = kNoRank;
@@ -150,7 +144,7 @@ __global__ void __launch_bounds__(kTagDocBlock) k_tagdoc(const TagDocParams P) {
             else if (P.valid[f >> 5] >> (f & 31) & 1u) r = P.field_rank[f];
             rank[i] = r;
         }
-        wave_sync();
+        wave_lds_fence();
         uint32_t mine = 0;
         bool twice = false;
         for (uint32_t i = lane; i < L; i += 64) {
@@ -172,7 +166,7 @@ __global__ void __launch_bounds__(kTagDocBlock) k_tagdoc(const TagDocParams P) {
 #pragma unroll
         for (uint32_t s = 1; s < 64; s <<= 1) mine += (uint32_t)__shfl_xor((int)mine, (int)s, 64);
         const uint32_t n_contrib = refused ? 0 : mine;
-        wave_sync();
+        wave_lds_fence();
         // ---- the walk.  The document's stores end before its separator, whatever the tables say
         const TextOut T{P.out, FILL ? std::min(P.cap, end - 1) : 0};
         int32_t prev_tag = -1, prev_pos = -1;   // of the last non-zero word of the rounds before (the same in every lane)

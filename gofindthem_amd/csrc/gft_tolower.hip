@@ -20,6 +20,7 @@
 
 #include "gft_kernels.hpp"
 #include "gft_tolower.hpp"
+#include "gft_wave_dev.hpp"
 
 namespace gft {
 
@@ -44,16 +45,6 @@ struct LowerParams {
 
 enum : int { kLowerCount = 0, kLowerWrite = 1, kLowerTable = 2 };
 
-// inclusive prefix sum over the 64 lanes with DPP moves (as gft_scan2_dev.hpp)
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);    // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);    // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);    // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);    // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);   // row_bcast:15 -> rows 1 and 3
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2 and 3
-    return v;
-}
 
 template <int MODE>
 __global__ void __launch_bounds__(kLowerBlock) k_lower(const LowerParams P) {
